@@ -22,6 +22,13 @@ Prints ONE JSON line (rank 0).  `value` = all walker-steps of the timed region /
 against the 8 TB/s HBM spec using ALGORITHMIC read bytes ((2*ndim+1)*8 B per walker-step,
 SURVEY.md 8(d)); `cpu_baseline` times the CPU oracle (a port of the reference algorithm, not
 KissMCMC.jl itself) on this box's host cores on a bounded sample of the same workload.
+
+A plain run (`--steps N --warmup W`) sets up, runs W warm-up steps, times exactly N steps (one run of the job: `value`,
+`ms_per_step`), and prints the line; its `check` and `roofline` come from that timed run.  `--full` adds everything else
+the line has carried: REPS timed repetitions of the whole job (`value` = their median), the per-phase rerun, the island
+mode, `other_configs`, `cpu_baseline` and, for N > 1, the link probe, the check of the timed run against the unsharded
+run and the extras.  `--dump-outputs DIR` writes what the timed path returned after its last step (positions, log-pdfs,
+acceptance counters, moments) as DIR/<name>.npy in float64; the inputs are seeded, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -63,6 +70,7 @@ SEED = 12345
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy rate is 6290 GB/s
 HBM_COPY_GBS = 6290.0   # what a float4 copy achieves on this chip (MI355X_MICROARCH.md:36)
 MALL_BYTES = 256 << 20  # Infinity Cache: a working set below this is served on-die between two uses (MI355X_MICROARCH.md:303-310)
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all, .npy headers included (a seeded sample of the walkers beyond it)
 
 
 def kernel_geometry(describe: str):
@@ -799,6 +807,24 @@ def emit(full: dict) -> None:
     sys.stdout.flush()
 
 
+def dump_outputs(path: str, outputs: dict) -> None:
+    """--dump-outputs: what the timed path returned after its last step, as <path>/<name>.npy in float64.  Per-walker arrays beyond
+    DUMP_BYTES in all are cut to a fixed, seeded sample of walkers (sorted; their indices in walker_index.npy)."""
+    arrays = {k: np.atleast_1d(np.asarray(v, dtype=np.float64)) for k, v in outputs.items() if v is not None}
+    nw = arrays["positions"].shape[0]
+    rows = [k for k in ("positions", "logp", "naccept") if k in arrays]        # one entry per walker; the moments are per dimension
+    fixed = sum(a.nbytes for k, a in arrays.items() if k not in rows) + 256 * (len(arrays) + 1)      # (+ a header per file)
+    row_bytes = sum(a.nbytes // nw for k, a in arrays.items() if k in rows) + 8       # (+ the index of a sampled walker)
+    if fixed + nw * (row_bytes - 8) > DUMP_BYTES:
+        keep = (DUMP_BYTES - fixed) // row_bytes
+        idx = np.sort(np.random.default_rng(SEED).choice(nw, size=keep, replace=False))
+        arrays.update({k: arrays[k][idx] for k in rows})
+        arrays["walker_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 class Job:
     """What every leg of a run shares: the arguments, this rank's place in the job, the workload."""
 
@@ -839,6 +865,11 @@ class Job:
             ref.run(gens)
             ref.sync()
             return ref.positions(), ref.naccept(), ref.moments()
+
+    @property
+    def reps(self) -> int:
+        """Timed runs of the whole job: exactly one (`--steps` steps) in a plain run, REPS with --full."""
+        return REPS if self.args.full else 1
 
     def timed(self, d, gens, warm):
         """`warm` generations, restart, then `gens` generations from a common start: seconds (this rank's; the caller takes the max)."""
@@ -900,7 +931,7 @@ def rendezvous(job: Job) -> None:
 
 
 def run_single(job: Job) -> dict:
-    """N = 1: the whole C2 job on one GPU -- `value` -- and, NOT `value`, the opt-in island mode on the same job."""
+    """N = 1: the whole C2 job on one GPU -- `value` -- and, with --full, NOT `value`, the opt-in island mode on the same job."""
     kmc, torch, args = job.kmc, job.torch, job.args
     s = kmc.Sampler(job.pdf, job.nw, NDIM, job.G, job.nburn, 1, 2.0, SEED, moments=True, device=job.local_rank)
     s.set_positions(job.th)
@@ -908,7 +939,7 @@ def run_single(job: Job) -> dict:
         s.run(GENS_PER_STEP)
     s.sync()
     runs = []
-    for _ in range(REPS):                    # the whole C2 job REPS times from the same start (>= 3 repetitions after a warm-up run)
+    for _ in range(job.reps):                # the whole C2 job once (--full: REPS times from the same start, SURVEY 8d: >= 3 repetitions after a warm-up run)
         s.set_positions(job.th)              # restart: the timed region is the whole C2 job
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -918,6 +949,14 @@ def run_single(job: Job) -> dict:
         runs.append((time.perf_counter() - t0, s.last_run_ms(), s.launch_count))      # (wall; HIP events on the sampler's own stream; launches since set_positions)
     res = {"how": s.describe(), "mode": "single"}
     Job.take_median(res, runs)               # `value`: the median repetition
+    res["msum"], res["msq"], res["nmom"] = s.moments()
+    res["acc"] = float(s.accept_ratio().mean())
+    if args.dump_outputs:
+        res["outputs"] = {"positions": s.positions(), "logp": s.logp(), "naccept": s.naccept(),
+                          "moment_sum": res["msum"], "moment_sumsq": res["msq"], "nmoment": res["nmom"]}
+    if not args.full:
+        s.close()
+        return res
     # not `value`: the same job once more in its two phases -- burn-in (no moments credited) and the credited half -- because the profile records
     # (profiles/traffic_c2.json) are taken per phase: launches that credit moments are ~0.4 us longer
     s.set_positions(job.th)
@@ -928,8 +967,6 @@ def run_single(job: Job) -> dict:
         s.sync()
         phase.append(s.last_run_ms() * 1e3 / max(1, s.launch_count - l0))
     res["phase_us"] = phase
-    res["msum"], res["msq"], res["nmom"] = s.moments()
-    res["acc"] = float(s.accept_ratio().mean())
     s.close()
     # Extra, NOT `value`: the opt-in island mode (256-walker islands resident in LDS, partners drawn inside the island, walkers
     # re-dealt every 64 generations) on the same job.
@@ -1095,7 +1132,7 @@ def run_sharded(job: Job) -> dict:
         if drv is None and rank == 0:
             note("[rank 0] falling back to the RCCL all-gather exchange")
         mode = "p2p" if drv is not None else "allgather"
-    if mode == "p2p":
+    if mode == "p2p" and args.full:
         # one fabric link measured with the pull's own access pattern, and this GPU alone on its 65 536 walkers: what the exact rule can reach (`fabric`)
         with rung("link-probe") as rg:
             lp = drv.link_probe()
@@ -1123,7 +1160,7 @@ def run_sharded(job: Job) -> dict:
                 drv.run(args.warmup * GENS_PER_STEP)
                 drv.sync()
                 runs = []
-                for _ in range(REPS):                    # the whole job REPS times from the same start, as at N = 1
+                for _ in range(job.reps):                # the whole job once (--full: REPS times from the same start), as at N = 1
                     drv.set_positions(th)                # barriers inside; restart the job
                     dist.barrier()
                     torch.cuda.synchronize()
@@ -1144,6 +1181,7 @@ def run_sharded(job: Job) -> dict:
                 job.take_median(res, runs)
                 res["msum"], res["msq"], res["nmom"] = drv.moments()
                 fpos, facc = drv.positions(), drv.naccept()
+                flogp = drv.logp() if args.dump_outputs else None      # (a collective: every rank)
                 res["how"] = drv.sampler.describe()
                 drv.close()
         except Exception as e:  # noqa: BLE001  (e.g. a peer wait that timed out: every rank then takes the fallback)
@@ -1158,7 +1196,7 @@ def run_sharded(job: Job) -> dict:
                 note("[rank 0] falling back to the RCCL all-gather exchange")
             mode = "allgather"
     if mode == "p2p":
-        if rank == 0:                                # the timed run itself, against the unsharded run of the whole job on one GPU
+        if rank == 0 and args.full:                  # the timed run itself, against the unsharded run of the whole job on one GPU
             rpos, racc, (rs, rq, rn) = job.unsharded(G)
             res["verified"] = bool(np.array_equal(rpos, fpos) and np.array_equal(racc, facc) and rn == res["nmom"] and
                                    np.allclose(rs, res["msum"], rtol=1e-10, atol=1e-6) and np.allclose(rq, res["msq"], rtol=1e-10, atol=1e-6))
@@ -1174,12 +1212,13 @@ def run_sharded(job: Job) -> dict:
         if nat is not None:
             with rung("allgather-run"):
                 runs = []
-                for rep in range(REPS):
+                for rep in range(job.reps):
                     t = job.max_over_ranks(job.timed(nat, G, min(args.warmup * GENS_PER_STEP, 200) if rep == 0 else 0))
                     runs.append((t, nat.sampler.last_run_ms(), nat.sampler.launch_count))
                 job.take_median(res, runs)
                 res["msum"], res["msq"], res["nmom"] = nat.moments()
                 facc, fpos = nat.naccept(), nat.positions()
+                flogp = nat.logp() if args.dump_outputs else None      # (a collective: every rank)
                 res["how"] = nat.sampler.describe()
                 nat.close()
             res["parallelism"] = f"walker-sharded x{world}, exact partner rule, native RCCL all-gather of the updated half per half-step ({res['how'].split(';')[-1].strip()})"
@@ -1208,14 +1247,18 @@ def run_sharded(job: Job) -> dict:
                 res["launches"] = 2 * G
                 res["msum"], res["msq"], res["nmom"] = sdrv.moments()
                 facc, fpos = sdrv.naccept(), sdrv.positions()
+                flogp = sdrv.logp() if args.dump_outputs else None     # (a collective: every rank)
                 res["how"] = ex.sampler.describe()
                 ex.close()
             res["parallelism"] = f"walker-sharded x{world}, exact partner rule, RCCL all-gather of the updated half per half-step (torch collective per half-step)"
             res["value_from"] = "torch-allgather-run"
-        if rank == 0:
+        if rank == 0 and args.full:
             rpos, racc, _ = job.unsharded(G)
             res["verified"] = bool(np.array_equal(rpos, fpos) and np.array_equal(racc, facc))
     res["acc"] = float(facc.sum() / nw / max(1, G - nburn))
+    if args.dump_outputs:
+        res["outputs"] = {"positions": fpos, "logp": flogp, "naccept": facc,
+                          "moment_sum": res["msum"], "moment_sumsq": res["msq"], "nmoment": res["nmom"]}
     if "elapsed_runs" not in res:                        # (the torch-collective fallback: one timed run)
         res["elapsed"] = job.max_over_ranks(res["elapsed"])
         res["elapsed_runs"] = [res["elapsed"]]
@@ -1327,6 +1370,8 @@ def full_record(job: Job, res: dict, timed_out=None) -> dict:
         out["ladder"] = list(LADDER)             # every rung rank 0 went through: {rung, ok, s}
         out["value_from"] = res["value_from"]    # the rung whose timed run is `value`
         out["check"]["timed_run_equals_unsharded_run"] = res["verified"]
+        if not args.full:                        # (the extras, the fabric block and the check against the unsharded run: --full)
+            return out
         out["dealt_mode"] = extras["dealt"] if extras["dealt"] is not None else {"error": timed_out or "not run"}
         if extras["allgather"] is not None or (timed_out and extras["allgather_started"]):
             out["allgather_mode"] = extras["allgather"] if extras["allgather"] is not None else {"error": timed_out}
@@ -1352,8 +1397,8 @@ def full_record(job: Job, res: dict, timed_out=None) -> dict:
                          "ge6x_expected_under_exact_rule": (proj >= 6.0) if proj else None,      # (north star: >= 6x at 8 GPUs; DESIGN section 7 says no for rand(ncos) over the whole half)
                          "push_bytes_per_link_per_launch": res["acc"] * walkers_per_launch * NDIM * 8,
                          "variants_us_per_launch": {tag: tc / 2048 * 1e6 for tag, tc in res["tried"]}}   # 1024 generations each
-    else:
-        out["island_mode"] = res.get("island")
+    elif "island" in res:
+        out["island_mode"] = res["island"]
     for key in ("other_configs", "cpu_baseline"):
         if key in res:
             out[key] = res[key]
@@ -1365,14 +1410,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the extra driver-timed C1/C3/C5 runs (profiling passes)")
-    ap.add_argument("--no-island", action="store_true", help="skip the extra island-mode run (profiling passes)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: repetitions, "
+                    "phases, island mode, other configs, CPU baseline; for N > 1 the link probe, the unsharded check and the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned after its last step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the extra driver-timed C1/C3/C5 runs (profiling passes)")
+    ap.add_argument("--no-island", action="store_true", help="with --full: skip the extra island-mode run (profiling passes)")
     ap.add_argument("--test-sleep", type=float, default=0.0, help=argparse.SUPPRESS)   # (tests of the launcher: every rank just sleeps)
     if len(sys.argv) >= 2 and sys.argv[1] == "--cpu-baseline-worker":       # (the CPU leg's own process, see cpu_baseline)
         print(json.dumps(cpu_baseline_worker(float(sys.argv[2]) if len(sys.argv) > 2 else 10.0)), flush=True)
         return
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: be the launcher (nothing in this process has touched the GPU yet, and nothing will)
@@ -1404,16 +1454,22 @@ def main():
 
     if not job.sharded:
         res = run_single(job)
-        if not args.no_other_configs:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res.pop("outputs"))
+        if args.full and not args.no_other_configs:
             res["other_configs"] = other_configs(kmc, job.local_rank)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
     else:
         rendezvous(job)
         res = run_sharded(job)
+        outputs = res.pop("outputs", None)
+        if outputs is not None and job.rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
         # `value` stands from here on: an extra that hangs costs its own numbers only (the watchdog prints the result as it stands)
         PENDING["line"] = lambda reason: emit(full_record(job, res, reason))
-        run_extras(job, res)
+        if args.full:
+            run_extras(job, res)
     if job.rank == 0:
         PENDING["line"] = None
         emit(full_record(job, res))

@@ -16,7 +16,7 @@ OUT=$R/gpurun_out/prof_r04
 if [ ! -s $R/.kmc_profile_head ]; then echo "profile_r04.sh: no .kmc_profile_head -- start the passes with scripts/profile_passes.sh (it refuses a dirty tree)"; exit 2; fi
 rm -rf $OUT && mkdir -p $OUT
 cp $R/.kmc_profile_head $OUT/head.txt
-BENCH="python3 $R/bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-island"
+BENCH="python3 $R/bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-island"
 # Round 6: every pass of a config runs in the launch mode the bench line runs that config in (the r05 C2 record was taken from the table
 # graph while the line ran the updated graph): C2 and C3 = the updated graph (128 generations per replay; what their launch-mode measurement picks in every
 # bench line on record), C5 and the HBM shapes = the table graph (what short jobs and C5's tie keep).  KMC_LAUNCH decides without measuring.

@@ -151,7 +151,7 @@ def main():
         if not tr:
             print(f"{cfg}: no kernel trace under {b}")
             continue
-        cmd = ("python3 bench.py --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-island" if cfg == "c2"
+        cmd = ("python3 bench.py --gpus 1 --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-island" if cfg == "c2"
                else f"python3 scripts/run_cfg.py {cfg.upper()} <gens> 1")
         out = {"tag": tag, "config": cfg.upper(), "shape": f"{nw} walkers x {nd} dims", "head": hd,
                "command": f"rocprofv3 --kernel-trace --stats --output-format csv -- {cmd}; PMC: the same command under --pmc <group> --kernel-trace, "

@@ -294,3 +294,27 @@ def test_scale_report_reads_the_measured_fabric_block(tmp_path):
     assert "at 61.2 GB/s (link-probe" in r.stdout and "projected speed-up 1.77 x, measured 1.61 x; >= 6 x expected: False" in r.stdout
     assert "at an ASSUMED 77 GB/s" in r.stdout                      # (the round-5 rehearsal line)
 
+
+
+def test_dumped_outputs_stay_within_budget_as_the_same_seeded_sample_of_walkers(tmp_path):
+    """--dump-outputs: float64 .npy files, at most DUMP_BYTES in all; an N > 1 ensemble beyond it is cut to a fixed, seeded sample of walkers
+    (the same rows of every per-walker array, run after run); the per-dimension moments stay whole."""
+    import numpy as np
+    nw = 8 * 65536
+    pos = np.arange(nw, dtype=np.float64)[:, None] + np.zeros((1, 32))
+    outs = {"positions": pos, "logp": -np.arange(nw, dtype=np.float64), "naccept": np.arange(nw, dtype=np.uint32), "moment_sum": np.ones(32),
+            "moment_sumsq": np.ones(32), "nmoment": 7}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["logp.npy", "moment_sum.npy", "moment_sumsq.npy", "naccept.npy", "nmoment.npy", "positions.npy", "walker_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in a.values())
+    idx = a["walker_index.npy"]
+    assert (np.diff(idx) > 0).all() and (a["positions.npy"][:, 5] == idx).all() and (a["logp.npy"] == -idx).all() and (a["naccept.npy"] == idx).all()
+    assert a["moment_sum.npy"].shape == (32,) and a["nmoment.npy"].tolist() == [7.0]
+    assert all((np.load(tmp_path / "b" / f) == v).all() for f, v in a.items())
+    small = {k: (v[:65536] if k in ("positions", "logp", "naccept") else v) for k, v in outs.items()}
+    bench.dump_outputs(str(tmp_path / "c"), small)                       # one GPU's ensemble fits whole
+    assert "walker_index.npy" not in os.listdir(tmp_path / "c") and np.load(tmp_path / "c" / "positions.npy").shape == (65536, 32)

@@ -24,7 +24,7 @@ def bench_env(test_opts, extra_env=None):
 
 def run_bench(extra_env, *args, **test_opts):
     env = bench_env({"backend": "gloo", "walkers": 4096, "timeout": 600, "rung-timeout": 240, **{k.replace("_", "-"): v for k, v in test_opts.items()}}, extra_env)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", *args],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", *args],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -86,7 +86,7 @@ def test_bench_two_ranks_under_torch_distributed_run():
     from portpick import rendezvous_port
     port = rendezvous_port()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"],
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -156,7 +156,7 @@ def test_bench_sharded_ladder_over_real_rccl_with_one_rank():
     from portpick import rendezvous_port
     port = rendezvous_port()
     env = bench_env({"force-sharded": True, "walkers": 8192, "rung-timeout": 240}, {"MASTER_PORT": str(port)})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -187,7 +187,7 @@ def test_bench_extras_fail_together_without_taking_the_result_down(point, key):
     """One rank failing in the local set-up of an EXTRA (dealt mode, all-gather record): every rank skips that extra together;
     `value` -- measured before -- stands, the extra carries an error instead of numbers, the job ends with status 0."""
     r_env = bench_env({"backend": "gloo", "walkers": 4096, "fault": point, "timeout": 600, "rung-timeout": 120})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"],
                        env=r_env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
@@ -203,7 +203,7 @@ def test_bench_an_extra_that_hangs_does_not_take_the_result_down():
     rung's watchdog expires on every rank -- and since `value` was measured before, rank 0 prints the line as it stands (the extra
     marked as timed out) and the job ends with status 0 instead of losing the measurement."""
     env = bench_env({"backend": "gloo", "walkers": 4096, "fault": "dealt_run_hang:1", "no-allgather-extra": True, "timeout": 600, "rung-timeout": 20})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
