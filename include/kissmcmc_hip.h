@@ -63,10 +63,13 @@ typedef enum kmc_density {
     KMC_MVNORMAL2    = 4, /* ndim == 2: -1/2 (d' P d), d = x - {p0,p1}, P = [[p2,p3],[p3,p4]] (precision matrix) */
     KMC_USER_DENSITY = 100, /* runtime-compiled: sum_d term(x_d) + sum_{d<n-1} pair(x_d, x_{d+1}); kmc_config.user_density
                               holds the handle made by kmc_user_density_create; params[0..5] are passed to it as p[] */
-    KMC_HOST_DENSITY = 101  /* ANY log-density, evaluated by the caller: per half-step the device writes the batch of
+    KMC_HOST_DENSITY = 101, /* ANY log-density, evaluated by the caller: per half-step the device writes the batch of
                               proposals, kmc_config.host_logpdf evaluates it on the host, the device accepts/rejects.
                               Keeps the reference's arbitrary `pdf` closure (src/samplers.jl:257); bound by the callback
                               and one PCIe round trip per half-step.  Single GPU, no island mode. */
+    KMC_DATA_DENSITY = 102  /* a log-prior plus a sum of per-observation terms over a data array held on the device:
+                              kmc_config.user_density holds the handle made by kmc_data_density_create; params[0..5] are
+                              passed to it as p[].  See kmc_data_density_create for the value contract. */
 } kmc_density;
 
 /* KMC_HOST_DENSITY callback: rows = dense [nrows][ndim]; write the log-pdf of every row to logp_out[nrows].
@@ -272,6 +275,28 @@ int         kmc_user_density_nblob(const kmc_user_density* ud);   /* 0 for densi
  * hasblob=true (src/samplers.jl:209-210) -- e.g. the blob0 a caller's init_blobs(blob0, nsamples) receives (:238). */
 kmc_status  kmc_logpdf_blob_eval_host(const kmc_config* cfg, const double* pos_host, double* logp_host, double* blob_host /* [nrows][nblob] */, int64_t nrows);
 void        kmc_user_density_destroy(kmc_user_density* ud);
+
+/* ---- data densities: the closure `pdf` of src/samplers.jl:257 as it usually is -- a log-prior plus a log-likelihood summed over
+ *      a dataset -- evaluated on the device, the data array copied there once.  Two C++ function bodies, compiled at run time:
+ *        term:  double term(const double* x, int n, const double* d, const double* p)   x = the proposal (n = ndim), d = ONE
+ *               observation row (ncols doubles), p = params[0..5]
+ *        prior: double prior(const double* x, int n, const double* p)                    (NULL or "": return 0.0;)
+ *      data: float64 [ndata][ncols], COPIED at creation (later changes to the caller's array have no effect).
+ *      Value contract (part of the interface: it keeps results a pure function of (seed, inputs), independent of launch geometry):
+ *        lp(x) = -inf                 if prior(x) == -inf   (the terms need not be evaluated)
+ *        lp(x) = prior(x) + S(x)      otherwise
+ *        S(x)  = the pairwise tree over t_j = term(x, d_j), j = 0 .. ndata-1, in index order: each level adds neighbours
+ *                (t0+t1), (t2+t3), ...; an odd last element passes up unchanged.  (The kernels may pad a short tail with +0.0: the
+ *                same value except for the sign of a zero sum.)
+ *      Creation compiles both bodies once (placeholder ndim): a body that does not compile is KMC_ERR_BAD_ARG with the compiler's
+ *      message, no device needed.  Limits: 1 <= ncols <= 16, 1 <= ndata <= 2^30, and a sampler's ndim <= 32.
+ *      Samplers run it as the host route's generation loop with the callback replaced by device kernels (per half-step: propose,
+ *      partial sums, fold, accept; eager launches, no host synchronisation): KMC_STORE_CHAIN / _LOGP, KMC_MOMENTS, KMC_STREAM_CHAIN,
+ *      KMC_CHAIN_BY_WALKER, kmc_sampler_set_state, kmc_emcee_run, kmc_logpdf_eval(_host).  KMC_ERR_UNSUPPORTED: KMC_F32, KMC_ISLANDS,
+ *      KMC_P2P, sharding, dealt sub-ensembles, kmc_sampler_init_ball, kmc_sampler_half_step, blobs, kmc_metropolis_run.
+ *      Freed with kmc_user_density_destroy. */
+kmc_status  kmc_data_density_create(const char* term_body, const char* prior_body /* NULL: 0 */, const double* data /* [ndata][ncols] */,
+                                    int64_t ndata, int32_t ncols, kmc_user_density** out);
 
 /* ---- one-shot: emcee + _emcee, src/samplers.jl:188-293 ---- */
 kmc_status  kmc_emcee_run(const kmc_config* cfg, const double* theta0 /* host [nwalkers][ndim] */,

@@ -19,6 +19,7 @@ OK, ERR_A_SCALE, ERR_ODD_WALKERS, ERR_TOO_FEW_WALKERS, ERR_BAD_ARG, ERR_NONFINIT
 GAUSSIAN_ISO, EXPONENTIAL, ROSENBROCK, LOGNORMAL, MVNORMAL2 = range(5)
 USER_DENSITY = 100
 HOST_DENSITY = 101
+DATA_DENSITY = 102
 HOST_LOGPDF_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_void_p)
 HOST_PROPOSE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int64, C.POINTER(C.c_double), C.c_void_p)
 HOST_ACCEPTED_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_uint8), C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p)
@@ -46,7 +47,7 @@ SYMBOLS = [
     "kmc_sampler_rccl_capture", "kmc_sampler_rccl_set_capture", "kmc_rccl_version", "kmc_device_free_bytes",
     "kmc_sampler_launch_mode", "kmc_updated_budget", "kmc_set_updated_budget_mb", "kmc_debug_accept_terms",
     "kmc_user_density_create_body_blob", "kmc_user_density_nblob", "kmc_logpdf_blob_eval_host", "kmc_sampler_get_blobs",
-    "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault",
+    "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault", "kmc_data_density_create",
 ]
 
 
@@ -213,6 +214,7 @@ def lib() -> C.CDLL:
     L.kmc_user_density_create.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.kmc_user_density_create_body.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.kmc_user_density_create_body_blob.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
+    L.kmc_data_density_create.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_int64, C.c_int32, C.POINTER(vp)]
     L.kmc_user_density_is_separable.restype = C.c_int
     L.kmc_user_density_is_separable.argtypes = [vp]
     L.kmc_user_density_nblob.restype = C.c_int

@@ -183,6 +183,13 @@ struct kmc_user_density {
     // ... and the modules loaded from them, per device: shared by every sampler over this density (hipModuleLoadData is ~0.5 ms,
     // half of what a sampler of the reference's sizes lives); unloaded when the last holder -- this object or a sampler -- lets go
     std::map<std::pair<const void*, int>, std::shared_ptr<void>> modules;
+    // kmc_data_density_create (KMC_DATA_DENSITY): two function bodies and the observations, copied at creation (kmc_data.hip)
+    bool is_data = false;
+    std::string data_term, data_prior;
+    int64_t ndata = 0;
+    int32_t ncols = 0;
+    std::vector<double> data;                        // [ndata][ncols], the caller's array as it was at creation
+    std::map<int, std::shared_ptr<void>> data_dev;   // ... and its copy on each device it was used on (under `mu`)
 };
 // Is the body run in its per-element form BY THE SAMPLER BEING BUILT on this thread?  The density's own flag, unless that sampler's check was blind
 // (kmc_sampler_create holds a SepOff for the rest of its set-up; afterwards the sampler's own `sep_off` says it).

@@ -656,6 +656,28 @@ KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
         s->have_run_events = true;
         return KMC_OK;
     }
+    if (s->data_eval) {
+        // per half-step: PROPOSE (the host route's first pass) -> partial sums -> fold -> ACCEPT, all on the sampler's stream
+        for (; ngen > 0; --ngen) {
+            KMC_TRY(chain_before(s, s->generation + 1));
+            for (int half = 0; half < 2; ++half) {
+                HalfStepArgs a = make_args(s, half, false, s->generation);
+                a.prop_out = s->d_prop;
+                a.prop_ld = (int32_t)s->ld;
+                HIP_TRY(launch_half_kernel(s, a));
+                HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_half, s->d_prop, s->h, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_p1, s->stream));
+                a.prop_out = nullptr;
+                a.p1_in = s->d_p1;
+                HIP_TRY(launch_half_kernel(s, a));
+                s->launches += 4;
+            }
+            s->generation += 1;
+            KMC_TRY(chain_after(s));
+        }
+        HIP_TRY(hipEventRecord(s->ev1, s->stream));
+        s->have_run_events = true;
+        return KMC_OK;
+    }
     if (s->host_eval) {
         // per half-step: PROPOSE on the device -> proposals to the host -> callback -> log-pdfs back
         // -> ACCEPT on the device (which recomputes the same proposals from the same draws)
@@ -877,6 +899,7 @@ KMC_EXPORT kmc_status kmc_sampler_half_step(kmc_sampler* s, int half)
     if (!s->positions_set) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_set_positions has not succeeded yet");
     if (s->p2p && !s->connected) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_p2p_connect has not been called");
     if (s->islands) return fail(KMC_ERR_UNSUPPORTED, "island mode advances whole generations: use kmc_sampler_run");
+    if (s->data_eval) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: whole generations only; use kmc_sampler_run");
     if (s->host_eval) return fail(KMC_ERR_UNSUPPORTED, "KMC_HOST_DENSITY: a half-step includes the host callback; use kmc_sampler_run");
     if (s->resident) return fail(KMC_ERR_UNSUPPORTED, "this small ensemble runs in resident mode (whole generations per launch); create it with KMC_NO_GRAPH to step by halves");
     HIP_TRY(hipSetDevice(s->cfg.device));             // (before unfuse: its copies, graph destruction and moment read-out belong to this sampler's device)

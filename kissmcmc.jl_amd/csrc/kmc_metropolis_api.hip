@@ -293,6 +293,7 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
 KMC_EXPORT kmc_status kmc_metropolis_validate(const kmc_metropolis_config* c)
 {
     if (!c) return fail(KMC_ERR_BAD_ARG, "null config");
+    if (c->density == KMC_DATA_DENSITY) return fail(KMC_ERR_UNSUPPORTED, "kmc_metropolis_run: not with KMC_DATA_DENSITY (the emcee samplers only)");
     if (c->dtype != KMC_F64) return fail(KMC_ERR_UNSUPPORTED, "only KMC_F64 is implemented");
     if (c->nchains <= 0 || c->ndim <= 0 || c->nthin <= 0 || c->niter < 0 || c->nburnin < 0)
         return fail(KMC_ERR_BAD_ARG, "nchains, ndim, nthin must be positive; niter, nburnin non-negative");

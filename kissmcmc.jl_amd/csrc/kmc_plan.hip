@@ -210,8 +210,8 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     if ((ragged || f32) && iter > 4) iter = 4;
     if ((c.flags & KMC_P2P) && iter > 8) iter = 8;
     p.ragged = ragged;
-    if (c.density == KMC_HOST_DENSITY) {
-        // bound by the host callback: the one-walker-per-lane kernel, any ndim
+    if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY) {
+        // bound by the host callback (or, for a data density, by the data kernels between the two passes): the one-walker-per-lane kernel, any ndim
         p.fn = half_step_host(); p.vec = false; p.ragged = false; p.L = 1; p.K = 1; p.ITER = 1;
         return p;
     }
@@ -253,6 +253,10 @@ kmc_status kmc_host::digest_params(const kmc_config& c, DensityParams* dp)
         for (int i = 0; i < 6; ++i) dp->p[i] = p[i];
         return KMC_OK;
     case KMC_HOST_DENSITY:
+        return KMC_OK;
+    case KMC_DATA_DENSITY:
+        if (!c.user_density) return fail(KMC_ERR_BAD_ARG, "KMC_DATA_DENSITY needs kmc_config.user_density");
+        for (int i = 0; i < 6; ++i) dp->p[i] = p[i];
         return KMC_OK;
     case KMC_GAUSSIAN_ISO:
         if (!(p[1] > 0.0)) return fail(KMC_ERR_BAD_ARG, "gaussian: sigma must be > 0");

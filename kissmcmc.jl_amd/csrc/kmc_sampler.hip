@@ -59,6 +59,19 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
         return fail(KMC_ERR_UNSUPPORTED, "ensemble too large");
     if (c->ngenerations >= (int64_t)1 << 31) return fail(KMC_ERR_UNSUPPORTED, "at most 2^31 - 1 generations (the step index is 32 bits)");
     if (c->density == KMC_USER_DENSITY && !c->user_density) return fail(KMC_ERR_BAD_ARG, "KMC_USER_DENSITY needs kmc_config.user_density");
+    if (c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->is_data)
+        return fail(KMC_ERR_BAD_ARG, "this handle was made by kmc_data_density_create: use density = KMC_DATA_DENSITY");
+    if (c->density == KMC_DATA_DENSITY) {
+        const kmc_user_density* ud = static_cast<const kmc_user_density*>(c->user_density);
+        if (!ud || !ud->is_data) return fail(KMC_ERR_BAD_ARG, "KMC_DATA_DENSITY needs kmc_config.user_density made by kmc_data_density_create");
+        if (c->dtype != KMC_F64) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: double rows only (no KMC_F32)");
+        if (c->flags & KMC_ISLANDS) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: no island mode (KMC_ISLANDS)");
+        if (c->flags & KMC_P2P) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: one GPU, no KMC_P2P");
+        if (c->shard_count > 1) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: one GPU, no sharding (shard_count must be 1)");
+        if (c->deal_count > 0) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: no dealt sub-ensembles (deal_count must be 0)");
+        if (c->flags & KMC_STORE_BLOBS) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: no blobs (KMC_STORE_BLOBS)");
+        if (c->ndim > kDataMaxDim) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: ndim must be <= " + std::to_string(kDataMaxDim));
+    }
     if (c->density == KMC_HOST_DENSITY) {
         if (!c->host_logpdf) return fail(KMC_ERR_BAD_ARG, "KMC_HOST_DENSITY needs kmc_config.host_logpdf");
         if ((c->flags & (KMC_P2P | KMC_ISLANDS)) || c->shard_count > 1)
@@ -273,7 +286,7 @@ namespace {
 int generation_wanted(const kmc_sampler* s)
 {
     const kmc_config& c = s->cfg;
-    if (c.density == KMC_HOST_DENSITY || s->f32 || s->nblob != 0 || c.shard_count != 1 || c.deal_count != 0 ||
+    if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY || s->f32 || s->nblob != 0 || c.shard_count != 1 || c.deal_count != 0 ||
         (c.flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) || std::getenv("KMC_PLAN") != nullptr)      // (KMC_PLAN: a geometry of the two-launch kernels was asked for)
         return 0;
     // lane-striped forms need a lane-striped density (menu, term / pair, a body recognised as a sum) and the vector kernels' plan
@@ -399,6 +412,13 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         }
     } else if (cfg->density == KMC_HOST_DENSITY) {
         s->host_eval = true;
+    } else if (cfg->density == KMC_DATA_DENSITY) {
+        // the host route's PROPOSE and ACCEPT passes, with the data kernels in place of the callback (kmc_launch.hip)
+        s->host_eval = true;
+        s->data_eval = true;
+        s->data_ud = static_cast<kmc_user_density*>(cfg->user_density);
+        st = load_data(s->data_ud, cfg->ndim, &s->dk);
+        if (st != KMC_OK) { kmc_sampler_destroy(s); return st; }
     } else {
         HalfStepFn v, g;
         lookup(cfg->density, 0, 0, 1, false, false, false, &v, &g, &s->logpdf_fn);
@@ -613,7 +633,15 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
             CREATE_TRY(hipMemsetAsync(s->d_glast, 0, nw * sizeof(uint32_t), s->stream));
         }
     }
-    if (s->host_eval) {
+    if (s->data_eval) {
+        CREATE_TRY(dev_alloc(s, &s->d_prop, (size_t)s->h * ldz * sizeof(double)));
+        CREATE_TRY(dev_alloc(s, &s->d_p1, (size_t)s->h * sizeof(double)));
+        // the plans are decided here, once (KMC_DEBUG=data-map may change later in the process: the kernels keep the geometry d_part was sized for)
+        s->plan_half = data_plan(s->data_ud, s->h);
+        s->plan_all = data_plan(s->data_ud, s->nrows);
+        s->part_doubles = std::max((size_t)s->plan_half.nblocks * (size_t)s->h, (size_t)s->plan_all.nblocks * (size_t)s->nrows);
+        CREATE_TRY(dev_alloc(s, &s->d_part, s->part_doubles * sizeof(double)));
+    } else if (s->host_eval) {
         CREATE_TRY(dev_alloc(s, &s->d_prop, (size_t)s->h * ldz * sizeof(double)));
         CREATE_TRY(dev_alloc(s, &s->d_p1, (size_t)s->h * sizeof(double)));
         CREATE_TRY(hipHostMalloc((void**)&s->h_prop, (size_t)s->h * (size_t)cfg->ndim * sizeof(double), hipHostMallocDefault));
@@ -761,6 +789,7 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
     cache_free(s->d_glast);
     cache_free(s->d_prop);
     cache_free(s->d_p1);
+    cache_free(s->d_part);
     if (s->h_prop) (void)hipHostFree(s->h_prop);
     if (s->h_p1) (void)hipHostFree(s->h_p1);
     cache_free(s->d_acc);
@@ -847,6 +876,13 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
             o << "one launch per generation (exact): generation_group L=" << s->fused_L << " K=" << s->plan.K << ", rows lane-striped, second-half walkers recompute their partner's first-half move, grid "
               << 2 * ((s->h + s->fused_tpb / s->fused_L - 1) / (s->fused_tpb / s->fused_L)) << " x " << s->fused_tpb;
         o << launch_mode_text(s, "generation");
+    } else if (s->data_eval) {
+        const DataPlan& ph = s->plan_half;
+        o << "data density (exact): per half-step propose kernel -> " << (ph.obs ? "data_partial_obs (one observation per lane, grid " + std::to_string(s->h)
+                                                                                 : "data_partial_lane (one proposal per lane, grid " + std::to_string((s->h + 63) / 64))
+          << " x " << ph.nblocks << " workgroups of 256, " << ph.rounds << " rounds per wave) -> data_fold -> accept kernel, eager launches; "
+          << s->data_ud->ndata << " observations of " << s->data_ud->ncols << " doubles; scratch " << ph.nblocks << " x " << s->h
+          << " tree nodes (at most 4096 x nwalkers doubles)";
     } else if (s->host_eval)
         o << "host-evaluated density (exact): per half-step propose kernel -> D2H -> callback -> H2D -> accept kernel, grid "
           << s->grid << " x 256";

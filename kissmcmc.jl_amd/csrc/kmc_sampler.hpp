@@ -37,6 +37,19 @@ struct UserKernels {
     hipFunction_t logpdf_sep = nullptr; // a body recognised as a sum over elements: the generated form, row by row (check_sum_form)
 };
 
+// kernels and device data of a data density (kmc_data.hip), and how one evaluation over `nprop` rows is cut
+struct DataKernels {
+    std::shared_ptr<void> keep, keep_data;   // the module and the device copy of the observations (shared with the density)
+    hipFunction_t lane = nullptr, obs = nullptr, fold = nullptr;
+    const double* data = nullptr;
+};
+struct DataPlan {
+    bool obs = false;         // lane per observation (few proposals) instead of proposal per lane
+    int32_t rounds = 1;       // chunks per wave
+    int32_t nblocks = 1;      // workgroup blocks of observations = tree nodes per proposal in the scratch buffer
+};
+constexpr int64_t kDataMaxDim = 32, kDataMaxCols = 16, kDataMaxRows = (int64_t)1 << 30;
+
 }  // namespace kmc_host
 
 struct kmc_sampler {
@@ -133,6 +146,13 @@ struct kmc_sampler {
     uint8_t* d_acc = nullptr;          // [h] accept outcomes of the current half-step (host_accepted only)
     uint8_t* h_acc = nullptr;          // pinned [h]
     hipEvent_t host_ev[kmc_host::kHostPieces] = {};   // proposals of a large half-step reach the host in pieces, each behind its event (kmc_sampler_run)
+    // data density (KMC_DATA_DENSITY): the host route's two passes with device kernels between them instead of the callback
+    bool data_eval = false;
+    kmc_user_density* data_ud = nullptr;
+    kmc_host::DataKernels dk{};
+    double* d_part = nullptr;          // tree nodes of the partial kernels, [nblocks][rows] (<= 4096 x nwalkers doubles)
+    size_t part_doubles = 0;           //   its size
+    kmc_host::DataPlan plan_half{}, plan_all{};   // how a half-step's proposals / the whole ensemble are cut: fixed at creation, d_part sized for both
     // resident mode: exact sampler, whole (small) ensemble in one workgroup's LDS, many generations per launch
     bool resident = false;
     kmc::ResidentFn resident_kernel = nullptr;
@@ -224,6 +244,13 @@ void drop_updated_graph(kmc_sampler* s);                               // the up
 kmc_status unfuse(kmc_sampler* s);                                     // back to the two-launch kernels, in place (kmc_launch.hip)
 void set_offline_compiler_hint(bool wanted);                          // runtime-compiled kernels of this thread: hipcc as a child process instead of hiprtc (kmc_rtc.hip)
 bool body_vec_possible(const kmc_user_density* ud, int64_t ndim);     // a function body inside the vector kernels, evaluated per walker (kmc_rtc.hip)
+
+// kmc_data.hip
+kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk);       // compile (cached) + module + device copy of the data
+DataPlan data_plan(const kmc_user_density* ud, int64_t nprop);                   // reads KMC_DEBUG=data-map: call it once per evaluation size, keep the result
+// one evaluation of nprop rows cut as `p` says; `part` holds part_doubles doubles (p.nblocks * nprop are written: refused beyond that)
+hipError_t launch_data_eval(const DataKernels& dk, const kmc_user_density* ud, const DataPlan& p, const double* prop, int64_t nprop, int32_t ld,
+                            const double* params, double* part, size_t part_doubles, double* out, hipStream_t st);
 
 // kmc_p2p.hip
 kmc_status check_p2p_err(kmc_sampler* s);                // a peer wait that timed out invalidates everything after it

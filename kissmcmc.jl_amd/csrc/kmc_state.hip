@@ -95,6 +95,7 @@ KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0
                                             uint64_t seed, int halving_steps, int ntries)
 {
     if (!s || !theta0 || !ball_radius || halving_steps < 1 || ntries < 1) return fail(KMC_ERR_BAD_ARG, "bad argument");
+    if (s->data_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with KMC_DATA_DENSITY (build the initial ensemble on the host, e.g. make_theta0s)");
     if (s->host_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball evaluates the density on the device; with KMC_HOST_DENSITY build the ball on the host");
     if (s->push) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball fills this rank's rows only; with KMC_P2P_PUSH use kmc_sampler_set_positions (the peers' copies must be filled too)");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -231,7 +232,9 @@ KMC_EXPORT kmc_status kmc_sampler_set_positions(kmc_sampler* s, const double* th
         HIP_TRY(fill_sync(s->d_flags, 0, 4096, s->stream));     // callers barrier across ranks before running
         HIP_TRY(fill_sync(s->d_err, 0, 64, s->stream));
     }
-    if (s->host_eval) {                                          // :209-210, on the caller's thread
+    if (s->data_eval) {                                          // :209-210, the same kernels as every half-step's proposals
+        HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_all, s->d_pos, (int64_t)nw, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_logp, s->stream));
+    } else if (s->host_eval) {                                   // :209-210, on the caller's thread
         std::vector<double> lp0(nw);
         if (s->cfg.host_logpdf(theta_host, (int64_t)nw, (int64_t)nd, lp0.data(), s->cfg.host_user) != 0) {
             s->positions_set = false;
@@ -611,6 +614,22 @@ KMC_EXPORT kmc_status kmc_logpdf_eval(const kmc_config* cfg, const double* pos_d
         return KMC_OK;
     }
     if (cfg->density == KMC_HOST_DENSITY) return fail(KMC_ERR_UNSUPPORTED, "KMC_HOST_DENSITY is evaluated by the caller, not on the device");
+    if (cfg->density == KMC_DATA_DENSITY) {
+        kmc_user_density* ud = static_cast<kmc_user_density*>(cfg->user_density);
+        if (!ud->is_data) return fail(KMC_ERR_BAD_ARG, "KMC_DATA_DENSITY needs kmc_config.user_density made by kmc_data_density_create");
+        if (cfg->ndim < 1 || cfg->ndim > kDataMaxDim) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: ndim must be in 1 .. " + std::to_string(kDataMaxDim));
+        DataKernels dk;
+        KMC_TRY(load_data(ud, cfg->ndim, &dk));
+        double* part = nullptr;
+        const DataPlan plan = data_plan(ud, nrows);                  // (one plan for the allocation and the launch)
+        const size_t part_doubles = (size_t)plan.nblocks * (size_t)nrows;
+        HIP_TRY(hipMalloc((void**)&part, part_doubles * sizeof(double)));
+        hipError_t e = launch_data_eval(dk, ud, plan, pos_dev, nrows, (int32_t)cfg->ndim, dp.p, part, part_doubles, logp_dev, (hipStream_t)hip_stream);
+        if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)hip_stream);     // (the scratch and dk's hold on the module end with this scope)
+        (void)hipFree(part);
+        HIP_TRY(e);
+        return KMC_OK;
+    }
     HalfStepFn v, g;
     LogpdfFn lp = nullptr;
     if (!lookup(cfg->density, 0, 0, 1, false, false, false, &v, &g, &lp)) return fail(KMC_ERR_BAD_ARG, "unknown density id");

@@ -302,6 +302,52 @@ class CDensity(ExprDensity):
         return lp, bl
 
 
+class DataDensity(ExprDensity):
+    """A log-prior plus a log-likelihood summed over a dataset, evaluated on the device -- what the reference's ``pdf`` closure
+    (``src/samplers.jl:257``) almost always is in a Bayesian model fit.  Two C++ function bodies, compiled at run time::
+
+        double term(const double* x, int n, const double* d, const double* p) { TERM }    // one observation row d[0..ncols)
+        double prior(const double* x, int n, const double* p) { PRIOR }                   // default: return 0.0;
+
+    ``x`` is the proposal (``n`` = ndim, at most 32), ``p`` the ``params`` (up to 6 doubles), ``data`` a float64 array
+    ``[ndata, ncols]`` (``ncols`` <= 16; a 1-D array is one column), COPIED at creation.  The log-density is ``-inf`` where the prior
+    is ``-inf``, else ``prior(x) + S(x)`` with ``S`` the pairwise tree over ``term(x, d_j)`` in index order (each level adds
+    neighbours, an odd last element passes up): part of the interface, so results do not depend on how the kernels cut the data.
+    Example (Gaussian linear regression, precision ``p[0]``)::
+
+        DataDensity("double r = d[1] - (x[0] + x[1] * d[0]); return -0.5 * p[0] * r * r;", np.column_stack([t, y]), params=[1.0])
+
+    ``kmc_data_density_create``.  Runs in the emcee samplers (chain, log-pdfs, moments, streamed chains, checkpoints); not with
+    ``dtype="f32"``, islands, sharding, ``init_ball``, blobs or Metropolis.
+    """
+
+    density_id = _lib.DATA_DENSITY
+    name = "data"
+
+    def __init__(self, term: str, data, prior: str | None = None, params=()):
+        import ctypes as C
+        if len(params) > 6:
+            raise ValueError("at most 6 parameters")
+        D = np.asarray(data, dtype=np.float64)
+        if D.ndim == 1:
+            D = D[:, None]
+        if D.ndim != 2:
+            raise ValueError("data must be a [ndata, ncols] array")
+        self.data = np.array(D, dtype=np.float64, order="C")          # (the library copies it too; this one is for the caller)
+        self.term, self.prior = str(term), (str(prior) if prior else None)
+        self.pair, self.nblob = None, 0
+        self._params = [float(v) for v in params]
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(self._L.kmc_data_density_create(self.term.encode(), self.prior.encode() if self.prior else None,
+                                                   self.data.ctypes.data_as(C.POINTER(C.c_double)), int(self.data.shape[0]),
+                                                   int(self.data.shape[1]), C.byref(h)))
+        self.user_handle = h
+
+    def __repr__(self):
+        return f"DataDensity(term={self.term!r}, data=<{self.data.shape[0]} x {self.data.shape[1]}>, prior={self.prior!r}, params={self._params})"
+
+
 class HostLogPdf(DeviceLogPdf):
     """ANY Python callable as the log-density -- the reference's ``pdf`` closure
     (``src/samplers.jl:257``) kept on the host.  The stretch move, the random draws, the accept test,

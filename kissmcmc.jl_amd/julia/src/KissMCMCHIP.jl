@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -133,6 +133,34 @@ function (d::ExprDensity)(x)
     xs = collect(Float64, x isa Number ? [x] : x); out = Ref(0.0)
     p8 = ntuple(i -> i <= length(d.p) ? d.p[i] : 0.0, 8)
     cfg = Ref(KmcConfig(density=Cint(100), params=p8, nwalkers=2, ndim=length(xs), user_density=d.handle))
+    st = ccall((:kmc_logpdf_eval_host, LIB), Cint, (Ref{KmcConfig}, Ptr{Float64}, Ref{Float64}, Int64), cfg, xs, out, 1)
+    st == 0 || error(last_error()); out[]
+end
+
+# A log-prior plus a sum of per-observation terms over a dataset, on the device (kmc_data_density_create): `term` is the body of
+# `double term(const double* x, int n, const double* d, const double* p)` (d = one observation row), `prior` that of
+# `double prior(const double* x, int n, const double* p)` (nothing: 0).  `data` is ndata x ncols (a vector: one column), copied at
+# creation; lp = -Inf where the prior is -Inf, else prior + the pairwise sum of the terms in observation order.
+mutable struct DataDensity <: DeviceLogPdf
+    handle::Ptr{Cvoid}; p::Vector{Float64}
+    function DataDensity(term::String, data::AbstractVecOrMat; prior::Union{String,Nothing}=nothing, params=Float64[])
+        D = data isa AbstractVector ? reshape(collect(Float64, data), :, 1) : collect(Float64, data)
+        rows = permutedims(D)                          # row-major [ndata][ncols] for the C ABI
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        st = ccall((:kmc_data_density_create, LIB), Cint, (Cstring, Cstring, Ptr{Float64}, Int64, Int32, Ref{Ptr{Cvoid}}),
+                   term, prior === nothing ? "" : prior, rows, size(D, 1), Int32(size(D, 2)), h)
+        st == 0 || error("kmc_data_density_create failed: $(last_error())")
+        d = new(h[], collect(Float64, params))
+        finalizer(x -> ccall((:kmc_user_density_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.handle), d)
+        return d
+    end
+end
+density_id(::DataDensity) = Cint(102); params(d::DataDensity) = d.p
+user_handle(d::DataDensity) = d.handle
+function (d::DataDensity)(x)
+    xs = collect(Float64, x isa Number ? [x] : x); out = Ref(0.0)
+    p8 = ntuple(i -> i <= length(d.p) ? d.p[i] : 0.0, 8)
+    cfg = Ref(KmcConfig(density=Cint(102), params=p8, nwalkers=2, ndim=length(xs), user_density=d.handle))
     st = ccall((:kmc_logpdf_eval_host, LIB), Cint, (Ref{KmcConfig}, Ptr{Float64}, Ref{Float64}, Int64), cfg, xs, out, 1)
     st == 0 || error(last_error()); out[]
 end
