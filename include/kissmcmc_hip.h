@@ -150,6 +150,20 @@ enum {
                                   per-rank progress flags; needs kmc_sampler_p2p_export/_connect (<= 8 shards) */
 };
 
+/* kmc_config.move: the proposal of a walker-step.
+ *   KMC_MOVE_STRETCH  the reference's stretch move (src/samplers.jl:250-260); the zeroed default.
+ *   KMC_MOVE_DE       differential evolution (opt-in, not in the reference; ter Braak 2006, emcee's DEMove): two distinct
+ *                     partners j != k, uniform over the complementary half, and y = x + g (x_j - x_k) with
+ *                     g = gamma0 (1 + sigma v), v uniform in (-1, 1); accepted when p1 - p0 >= log u (a symmetric move: no
+ *                     (N-1) log z term).  Its own Philox stream, key {seed_lo ^ 0x44454D56 ("DEMV"), seed_hi}, counter
+ *                     {step_lo, step_hi, walker, block} -- DESIGN.md section 2.  Two launches per generation, one GPU, double
+ *                     rows: KMC_ERR_UNSUPPORTED with KMC_ISLANDS, KMC_P2P, shard_count > 1, deal_count > 0, KMC_F32,
+ *                     KMC_STORE_BLOBS, a body density with blobs, and in kmc_sampler_rccl_init. */
+enum {
+    KMC_MOVE_STRETCH = 0,
+    KMC_MOVE_DE      = 1
+};
+
 #define KMC_P2P_HANDLE_BYTES 128
 #define KMC_RCCL_ID_BYTES 128
 
@@ -176,6 +190,10 @@ typedef struct kmc_config {
     kmc_host_accepted_fn host_accepted; /* KMC_HOST_DENSITY: per-half-step accept outcomes, or NULL */
     int32_t  deal_rank;     /* DEALT SUB-ENSEMBLES (opt-in, not the reference's partner rule; see kmc_sampler_deal_pack): this sampler is */
     int32_t  deal_count;    /* sub-ensemble deal_rank of deal_count; 0 = off.  nwalkers is then THIS sub-ensemble's size */
+    int32_t  move;          /* KMC_MOVE_STRETCH (0, the reference's move) or KMC_MOVE_DE */
+    int32_t  move_pad_;
+    double   de_gamma0;     /* KMC_MOVE_DE: gamma0 of the proposal; 0 -> 2.38 / sqrt(2 ndim) */
+    double   de_sigma;      /* KMC_MOVE_DE: relative jitter of gamma, in [0, 1); 0 = none */
 } kmc_config;
 
 /* Host output buffers of the one-shot call; any pointer may be NULL. */

@@ -29,6 +29,8 @@ STORE_CHAIN, STORE_LOGP, MOMENTS, NO_GRAPH, P2P, ISLANDS, P2P_FINEGRAINED, P2P_P
 STREAM_CHAIN = 2048
 CHAIN_BY_WALKER = 4096
 STORE_BLOBS = 8192
+# kmc_config.move
+MOVE_STRETCH, MOVE_DE = 0, 1
 P2P_HANDLE_BYTES = 128
 RCCL_ID_BYTES = 128
 
@@ -75,6 +77,10 @@ class Config(C.Structure):
         ("host_accepted", C.c_void_p),
         ("deal_rank", C.c_int32),
         ("deal_count", C.c_int32),
+        ("move", C.c_int32),
+        ("move_pad_", C.c_int32),
+        ("de_gamma0", C.c_double),
+        ("de_sigma", C.c_double),
     ]
 
 

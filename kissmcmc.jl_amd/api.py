@@ -48,7 +48,7 @@ def emcee_counts(niter: int, nwalkers: int, nburnin=None, nthin: int = 1):
 
 def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_scale: float = 2.0,
           use_progress_meter: bool = True, hasblob: bool = False, init_blobs=None, reduce_blob=None,
-          seed=None, device: int = 0, dtype: str = "f64", stream_chain=None):
+          seed=None, device: int = 0, dtype: str = "f64", stream_chain=None, move=None):
     """The affine-invariant ensemble sampler, on one MI355X.  ``dtype="f32"`` keeps the walkers in single
     precision on the device (a throughput option, device densities; everything returned is still float64).
 
@@ -62,6 +62,9 @@ def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_sc
     ``:268-272``), ``False`` keeps the whole chain on the device until the end, ``None`` (default) streams when the
     chain would not fit the device (more than 70 % of its free memory; page-locking the host arrays costs about as much
     as downloading a chain that does fit).
+
+    ``move``: ``None`` is the reference's stretch move with ``a_scale``; ``DEMove(gamma0=None, sigma=1e-5)`` the opt-in
+    differential-evolution move (two partners, no ``a_scale``; README "Differential-evolution move").
 
     ``hasblob=True`` (``:150-151, :194-196``): ``pdf`` is a host callable returning ``(p, blob)``; the blobs
     stay on the host and follow the device's accept decisions.  ``blobs[w] = init_blobs(blob0s[w],
@@ -128,7 +131,7 @@ def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_sc
         stream_chain = dtype == "f64" and chain_bytes > (1 << 30) and chain_bytes > 0.7 * _free_device_bytes(device)
     # (host arrays that cannot be page-locked are no reason to fail: the library then stages the by-walker blocks itself)
     with Sampler(pdf, nwalkers, ndim, niter_walker, nburnin_walker, nthin, a_scale, seed, store_chain=True, store_logp=True,
-                 device=device, dtype=dtype, stream_chain=bool(stream_chain), chain_by_walker=True, store_blobs=device_blobs) as s:
+                 device=device, dtype=dtype, stream_chain=bool(stream_chain), chain_by_walker=True, store_blobs=device_blobs, move=move) as s:
         try:
             s.set_positions(theta0s)
         except _lib.KmcError as e:

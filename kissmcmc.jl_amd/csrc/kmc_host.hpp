@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +74,9 @@ inline long debug_opt_long(const char* name, long absent)
 
 // kernel tables of the menu densities (kmc_inst_*.hip) and the digest of kmc_config.params the kernels take
 bool lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen, kmc::LogpdfFn* lp);
+// KMC_MOVE_DE: gamma0 as the kernels use it (kmc_config.de_gamma0, or 2.38 / sqrt(2 ndim) when that is 0)
+inline double de_gamma0_of(const kmc_config& c) { return c.de_gamma0 > 0.0 ? c.de_gamma0 : 2.38 / std::sqrt(2.0 * (double)c.ndim); }
+bool lookup_de(int density, int L, int K, int iter, bool ragged, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
 kmc_status digest_params(const kmc_config& c, kmc::DensityParams* dp);
 
 // runtime-compiled user densities (hiprtc)

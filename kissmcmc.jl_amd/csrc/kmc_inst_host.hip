@@ -5,4 +5,5 @@
 
 namespace kmc {
 HalfStepFn half_step_host() { return half_step_generic<HostEval, false>; }
+HalfStepFn half_step_host_de() { return half_step_de_generic<HostEval>; }
 }  // namespace kmc

@@ -1,0 +1,8 @@
+// Kernel instantiations for the log-normal log-density with the differential-evolution move (KMC_MOVE_DE, opt-in):
+// the vector kernels (exact and ragged rows) and the generic kernel, double rows on one GPU.
+#define KMC_TABLES_IMPL
+#include "kmc_tables.hpp"
+
+namespace kmc {
+void table_de_lognormal(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { de_part<LogNormal>(L, K, iter, ragged, vec, gen); }
+}  // namespace kmc

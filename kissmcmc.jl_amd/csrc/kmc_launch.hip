@@ -80,6 +80,11 @@ HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t 
     a.dc.c0 = std::sqrt(1.0 / s->cfg.a_scale);                            // src/samplers.jl:227
     a.dc.c1 = std::sqrt(s->cfg.a_scale) - std::sqrt(1.0 / s->cfg.a_scale);
     a.dc.nm1 = (double)(s->cfg.ndim - 1);
+    if (s->cfg.move == KMC_MOVE_DE) {                                     // the DE kernels read gamma0 and sigma here (kmc_device.hpp: de_gamma)
+        a.dc.c0 = de_gamma0_of(s->cfg);
+        a.dc.c1 = s->cfg.de_sigma;
+        a.dc.nm1 = 0.0;
+    }
     a.dp = s->dp;
     a.chain = s->d_chain;
     a.chain_logp = s->d_chain_logp;

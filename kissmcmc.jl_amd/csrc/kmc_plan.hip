@@ -24,6 +24,19 @@ bool kmc_host::lookup(int density, int L, int K, int iter, bool p2p, bool ragged
 }
 
 namespace kmc_host {
+// KMC_MOVE_DE: the differential-evolution kernels (kmc_inst_<density>_de.hip)
+bool lookup_de(int density, int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
+{
+    switch (density) {
+    case KMC_GAUSSIAN_ISO: table_de_gaussian_iso(L, K, iter, ragged, vec, gen); return true;
+    case KMC_EXPONENTIAL: table_de_exponential(L, K, iter, ragged, vec, gen); return true;
+    case KMC_ROSENBROCK: table_de_rosenbrock(L, K, iter, ragged, vec, gen); return true;
+    case KMC_LOGNORMAL: table_de_lognormal(L, K, iter, ragged, vec, gen); return true;
+    case KMC_MVNORMAL2: table_de_mvnormal2(L, K, iter, ragged, vec, gen); return true;
+    default: return false;
+    }
+}
+
 IslandFn island_fn(int density, int S, int K, bool ragged)
 {
     switch (density) {
@@ -205,6 +218,9 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
             while (iter >= 2 && iter * 2 <= L && iter * 2 * K <= 16 && waves1 / (iter * 2) >= 4096 && iter < 16) iter *= 2;
         }
     }
+    const bool de = c.move == KMC_MOVE_DE;
+    // (a DE kernel holds three row tiles -- own, two partners -- where the stretch kernel holds two: at most 8 chunks per lane each)
+    if (de && !env) while (iter > 1 && iter * K > 8) iter /= 2;
     const bool ragged = L > 0 && 2 * L * K != c.ndim;
     const bool f32 = c.dtype == KMC_F32;
     if ((ragged || f32) && iter > 4) iter = 4;
@@ -212,7 +228,7 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     p.ragged = ragged;
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY) {
         // bound by the host callback (or, for a data density, by the data kernels between the two passes): the one-walker-per-lane kernel, any ndim
-        p.fn = half_step_host(); p.vec = false; p.ragged = false; p.L = 1; p.K = 1; p.ITER = 1;
+        p.fn = de ? half_step_host_de() : half_step_host(); p.vec = false; p.ragged = false; p.L = 1; p.K = 1; p.ITER = 1;
         return p;
     }
     if (c.density == KMC_USER_DENSITY) {
@@ -231,7 +247,8 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
         }
         return p;
     }
-    lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen, &lp);
+    if (de) lookup_de(c.density, L, K, iter, ragged, &vec, &gen);
+    else lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen, &lp);
     if (!force_generic && L > 0 && 2 * L * K >= c.ndim && vec != nullptr) {
         p.fn = vec; p.vec = true; p.L = L; p.K = K; p.ITER = iter;
     } else {

@@ -109,6 +109,16 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
         if (c->dtype != KMC_F64 || P != 1 || (c->flags & (KMC_P2P | KMC_ISLANDS)))
             return fail(KMC_ERR_UNSUPPORTED, "KMC_STREAM_CHAIN: KMC_F64, one GPU, without KMC_P2P / KMC_ISLANDS / sharding");
     }
+    if (c->move != KMC_MOVE_STRETCH && c->move != KMC_MOVE_DE) return fail(KMC_ERR_BAD_ARG, "kmc_config.move must be KMC_MOVE_STRETCH or KMC_MOVE_DE");
+    if (c->move == KMC_MOVE_DE) {
+        if (!std::isfinite(c->de_gamma0) || c->de_gamma0 < 0.0) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_DE: de_gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim))");
+        if (!std::isfinite(c->de_sigma) || c->de_sigma < 0.0 || c->de_sigma >= 1.0) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_DE: de_sigma must be in [0, 1)");
+        const char* what = (c->flags & KMC_ISLANDS) ? "KMC_ISLANDS" : (c->flags & KMC_P2P) ? "KMC_P2P" : P > 1 ? "shard_count > 1"
+                         : c->deal_count > 0 ? "dealt sub-ensembles (deal_count > 0)" : c->dtype == KMC_F32 ? "KMC_F32"
+                         : (c->flags & KMC_STORE_BLOBS) ? "KMC_STORE_BLOBS" : nullptr;
+        if (!what && c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) what = "a density with blobs";
+        if (what) return fail(KMC_ERR_UNSUPPORTED, std::string("KMC_MOVE_DE: two launches per generation on one GPU with double rows -- not with ") + what);
+    }
     {
         const int nb = c->density == KMC_USER_DENSITY && c->user_density ? static_cast<const kmc_user_density*>(c->user_density)->nblob : 0;
         if ((c->flags & KMC_STORE_BLOBS) && nb == 0)
@@ -287,6 +297,7 @@ int generation_wanted(const kmc_sampler* s)
 {
     const kmc_config& c = s->cfg;
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY || s->f32 || s->nblob != 0 || c.shard_count != 1 || c.deal_count != 0 ||
+        c.move == KMC_MOVE_DE ||                                                                      // (DE: the two-launch kernels only)
         (c.flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) || std::getenv("KMC_PLAN") != nullptr)      // (KMC_PLAN: a geometry of the two-launch kernels was asked for)
         return 0;
     // lane-striped forms need a lane-striped density (menu, term / pair, a body recognised as a sum) and the vector kernels' plan
@@ -350,7 +361,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         const bool lane2 = cfg->nwalkers > 1024 && cfg->nwalkers <= 2048 && !s->f32 && cfg->ndim <= 8 && s->user->nblob == 0 && resident_lane_wanted(cfg->ndim);
         if (lane2) rlds = ((size_t)cfg->nwalkers * (size_t)((cfg->ndim | 1) + 1)) * sizeof(double);
         if ((!s->f32 || s->user->is_body || expr_lane) && (cfg->nwalkers <= ((s->user->is_body || expr_lane) ? 1024 : 256) || lane2) && cfg->ndim <= 32 && s->cfg.shard_count == 1 && !(s->user->is_body && cfg->deal_count > 0) &&
-            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) &&
+            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && cfg->move != KMC_MOVE_DE &&
             rlds <= 156 * 1024 && !debug_opt("no-resident"))    // (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
             rK = rK0;
         int iS = 0;
@@ -384,7 +395,8 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         auto load = [&]() {
             set_offline_compiler_hint(s->h_loc >= 8192 && rK == 0 && iS == 0);
             const kmc_status lst = load_user(s->user, s->plan.vec, s->plan.L, s->plan.K, s->plan.ITER, s->plan.ragged, &s->uk, rcode, 4 * rK != cfg->ndim, iS, s->f32,
-                                             cfg->ndim, (cfg->flags & KMC_P2P) != 0, (rK != 0 || iS != 0) ? 0 : generation_wanted(s) == 1 ? (int)cfg->ndim : generation_wanted(s) == 2 ? -(100 * s->plan.L + s->plan.K) : generation_wanted(s) == 3 ? -401 : 0);
+                                             cfg->ndim, (cfg->flags & KMC_P2P) != 0, (rK != 0 || iS != 0) ? 0 : generation_wanted(s) == 1 ? (int)cfg->ndim : generation_wanted(s) == 2 ? -(100 * s->plan.L + s->plan.K) : generation_wanted(s) == 3 ? -401 : 0,
+                                             cfg->move == KMC_MOVE_DE);
             set_offline_compiler_hint(false);
             return lst;
         };
@@ -448,7 +460,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         if (ea != hipSuccess) { (void)hipGetLastError(); kmc_sampler_destroy(s); return fail(KMC_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
     }
     if (!s->islands && cfg->density != KMC_USER_DENSITY && !s->host_eval && cfg->nwalkers <= 2048 && cfg->ndim <= 32 &&
-        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && !debug_opt("no-resident")) {
+        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && cfg->move != KMC_MOVE_DE && !debug_opt("no-resident")) {
         const int64_t chunks = s->ld / 2;
         int K = 1;
         while (2 * K < chunks) K *= 2;
@@ -580,7 +592,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     // kernels gained 6-10 % from it only while their loads sat behind exec-mask regions and scalar waits; without those they behave like the exact-size ones), and
     // 6-14 % in the large-ensemble geometries (ITER >= 4: bandwidth-bound, the ring is bytes); L = 16, ITER = 1 (C3's geometry) is +-1 % exact-size, -1..2 % ragged, and keeps it.
     // KMC_DEBUG=ring=0|1 forces it off / on wherever the kernel has one.
-    bool want_ring = s->plan.vec && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
+    bool want_ring = s->plan.vec && cfg->move != KMC_MOVE_DE && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
     {
         std::string forced;
         if (want_ring && debug_opt("ring", &forced)) want_ring = forced != "0";
@@ -897,6 +909,12 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
         char b[200];
         std::snprintf(b, sizeof(b), "; feeding thread per replay of %lld generations: wait for a free executable %.1f us, parameter updates %.1f us, hipGraphLaunch %.1f us (%lld replays)",
                       (long long)s->uchunk, s->feed_wait_ns / 1e3 / s->feed_replays, s->feed_update_ns / 1e3 / s->feed_replays, s->feed_launch_ns / 1e3 / s->feed_replays, (long long)s->feed_replays);
+        o << b;
+    }
+    if (s->cfg.move == KMC_MOVE_DE) {
+        char b[160];
+        std::snprintf(b, sizeof(b), "; differential-evolution move (KMC_MOVE_DE): gamma0 %.6g, sigma %.3g, kernel %s", de_gamma0_of(s->cfg), s->cfg.de_sigma,
+                      s->host_eval ? "half_step_de_generic (propose / accept passes)" : s->plan.vec ? "half_step_de_vec" : "half_step_de_generic");
         o << b;
     }
     if (s->budget_fallback) o << "; updated-graph budget of the process spent (kmc_set_updated_budget_mb): fell back to " << (s->launch_mode == 2 ? "eager launches" : "the table graph");

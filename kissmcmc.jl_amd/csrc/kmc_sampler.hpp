@@ -239,7 +239,7 @@ void chain_unregister(kmc_sampler* s);
 // kmc_rtc.hip
 kmc_status load_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged, UserKernels* uk,
                      int resident_K = 0, bool resident_ragged = false, int island_S = 0, bool f32 = false, int64_t ndim = 0, bool p2p = false,
-                     int generation_nd = 0);
+                     int generation_nd = 0, bool de = false);
 void drop_updated_graph(kmc_sampler* s);                               // the updated-graph mode's executables, events and template graph (kmc_launch.hip)
 kmc_status unfuse(kmc_sampler* s);                                     // back to the two-launch kernels, in place (kmc_launch.hip)
 void set_offline_compiler_hint(bool wanted);                          // runtime-compiled kernels of this thread: hipcc as a child process instead of hiprtc (kmc_rtc.hip)

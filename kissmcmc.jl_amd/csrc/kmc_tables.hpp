@@ -6,6 +6,7 @@
 #include "kmc_islands.hpp"
 #include "kmc_generation.hpp"
 #include "kmc_metropolis.hpp"
+#include "kmc_de.hpp"
 
 namespace kmc {
 
@@ -86,6 +87,38 @@ void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec
     if constexpr (PART == 0) *gen = half_step_generic<D, false, double>;
     else if constexpr (PART == 1) *gen = f32 ? half_step_generic<D, false, float> : half_step_generic<D, false, double>;
     else *gen = half_step_generic<D, true, double>;
+}
+
+// the differential-evolution move (KMC_MOVE_DE; kmc_inst_<density>_de.hip): the vector kernels of the geometries make_plan picks,
+// exact and ragged, double rows on one GPU, and the generic kernel
+template <class D, int L, int K, bool RAGGED>
+HalfStepFn vec_de_iter(int iter)
+{
+    auto one = [](auto it) -> HalfStepFn {
+        constexpr int ITER = decltype(it)::value;
+        if constexpr (ITER <= L && ITER * K <= 16) return half_step_de_vec<D, L, K, ITER, RAGGED>;
+        else return nullptr;
+    };
+    switch (iter) {
+    case 1: return one(std::integral_constant<int, 1>{});
+    case 2: return one(std::integral_constant<int, 2>{});
+    case 4: return one(std::integral_constant<int, 4>{});
+    case 8: if constexpr (!RAGGED) return one(std::integral_constant<int, 8>{}); else return nullptr;
+    case 16: if constexpr (!RAGGED) return one(std::integral_constant<int, 16>{}); else return nullptr;
+    default: return nullptr;
+    }
+}
+template <class D>
+void de_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
+{
+    *gen = half_step_de_generic<D>;
+    *vec = nullptr;
+    if constexpr (D::kHasFrag) {
+#define KMC_LK(l, k) if (L == l && K == k) { *vec = ragged ? vec_de_iter<D, l, k, true>(iter) : vec_de_iter<D, l, k, false>(iter); return; }
+        KMC_LK(1, 1) KMC_LK(2, 1) KMC_LK(4, 1) KMC_LK(4, 2) KMC_LK(8, 2) KMC_LK(16, 2) KMC_LK(32, 2) KMC_LK(64, 2)
+        KMC_LK(64, 4) KMC_LK(64, 8)
+#undef KMC_LK
+    }
 }
 
 // island mode: one workgroup per S-walker island, rows of up to 4*K doubles
@@ -239,13 +272,15 @@ MetropolisTabledFn metropolis_tabled_lookup(int ndim)
 #define KMC_DECLARE_DENSITY_TABLE(name) \
     void table_##name(int L, int K, int iter, bool p2p, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen, LogpdfFn* lp); \
     void part_var_##name(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen);                      \
-    void part_p2p_##name(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
+    void part_p2p_##name(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen);                                 \
+    void table_de_##name(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
 KMC_DECLARE_DENSITY_TABLE(gaussian_iso);
 KMC_DECLARE_DENSITY_TABLE(exponential);
 KMC_DECLARE_DENSITY_TABLE(rosenbrock);
 KMC_DECLARE_DENSITY_TABLE(lognormal);
 KMC_DECLARE_DENSITY_TABLE(mvnormal2);
 HalfStepFn half_step_host();
+HalfStepFn half_step_host_de();      // KMC_MOVE_DE
 IslandFn island_gaussian_iso(int S, int K, bool ragged);
 ResidentFn resident_gaussian_iso(int tpb, int K, bool ragged);
 ResidentFn resident_lane_gaussian_iso(int ndim, bool f32);

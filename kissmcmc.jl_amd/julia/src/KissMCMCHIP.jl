@@ -51,6 +51,10 @@ Base.@kwdef struct KmcConfig
     host_accepted::Ptr{Cvoid} = C_NULL                # KMC_HOST_DENSITY: accept outcomes per half-step (blobs), or NULL
     deal_rank::Int32 = 0                              # dealt sub-ensembles (multi-GPU, opt-in); deal_count = 0: off
     deal_count::Int32 = 0
+    move::Int32 = 0                                   # KMC_MOVE_STRETCH = 0 (the reference's move), KMC_MOVE_DE = 1 (opt-in)
+    move_pad_::Int32 = 0
+    de_gamma0::Float64 = 0.0                          # KMC_MOVE_DE: 0 -> 2.38 / sqrt(2 ndim)
+    de_sigma::Float64 = 0.0                           # KMC_MOVE_DE: relative jitter of gamma
 end
 
 Base.@kwdef mutable struct KmcOutputs
@@ -71,6 +75,8 @@ end
 const KMC_STORE_CHAIN = UInt32(1) << 0
 const KMC_STORE_LOGP = UInt32(1) << 1
 const KMC_CHAIN_BY_WALKER = UInt32(1) << 12     # chain delivered as [walker][sample][dim]: thetas[w][k] are contiguous
+const KMC_MOVE_STRETCH = Int32(0)              # kmc_config.move: the reference's stretch move (default)
+const KMC_MOVE_DE = Int32(1)                   # ... the opt-in differential-evolution move (one GPU, double rows)
 const KMC_STORE_BLOBS = UInt32(1) << 13         # a CDensity(body; nblob=m): the blob of every stored sample (src/samplers.jl:270, :117)
 
 last_error() = unsafe_string(ccall((:kmc_last_error, LIB), Cstring, ()))
@@ -219,18 +225,23 @@ end
 
 """
     emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter÷2, nthin=1, a_scale=2.0,
-          use_progress_meter=true, hasblob=false, init_blobs, reduce_blob!, seed=rand(UInt64), device=0, dtype=:f64)
+          use_progress_meter=true, hasblob=false, init_blobs, reduce_blob!, seed=rand(UInt64), device=0, dtype=:f64,
+          move=:stretch, de_gamma0=0.0, de_sigma=1e-5)
 
 Same meaning as KissMCMC.emcee (src/samplers.jl:188-197); returns
 `(thetas, accept_ratio, logdensities, blobs)` with `thetas[w][k]` (src/samplers.jl:292).
 `hasblob=true` needs a `pdf` that returns a blob: a host closure (`HostLogPdf(f; hasblob=true)`, blobs of any type, kept on
 the host) or a `CDensity(body; nblob=m)` (m doubles computed and carried on the device; `blobs[w][k]::Vector{Float64}`).
+`move=:de` selects the opt-in differential-evolution move (KMC_MOVE_DE; `de_gamma0=0` is 2.38/sqrt(2 ndim), `de_sigma` the
+relative jitter of gamma); `:stretch` is the reference's move with `a_scale`.
 """
 function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1, a_scale=2.0,
                use_progress_meter=true, hasblob=false,
                init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),      # init_output_vector :80-85
                reduce_blob! =(blobs, blob) -> push!(blobs, blob),                         # :196
-               seed=rand(UInt64), device=0, dtype=:f64)     # dtype=:f32: float rows on the device (KMC_F32), built-in densities
+               seed=rand(UInt64), device=0, dtype=:f64,     # dtype=:f32: float rows on the device (KMC_F32), built-in densities
+               move=:stretch, de_gamma0=0.0, de_sigma=1e-5)
+    move in (:stretch, :de) || error("move must be :stretch or :de")
     device_blobs = hasblob && pdf isa ExprDensity && pdf.nblob > 0
     hasblob && !device_blobs && !(pdf isa HostLogPdf && pdf.hasblob) &&
         error("hasblob=true needs a pdf that returns a blob: HostLogPdf(f; hasblob=true) or CDensity(body; nblob=m)")
@@ -279,7 +290,8 @@ function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin
         cfg = Ref(KmcConfig(dtype=(dtype == :f32 ? 1 : 0), density=density_id(pdf), params=p8, nwalkers=nwalkers, ndim=ndim,
                             ngenerations=niter_walker, nburnin=nburnin_walker, nthin=nthin, a_scale=a_scale, seed=UInt64(seed),
                             flags=KMC_STORE_CHAIN | KMC_STORE_LOGP | flag, device=Int32(device), user_density=user_handle(pdf),
-                            host_logpdf=host_fn, host_user=host_ctx, host_accepted=acc_fn))
+                            host_logpdf=host_fn, host_user=host_ctx, host_accepted=acc_fn,
+                            move=(move == :de ? KMC_MOVE_DE : KMC_MOVE_STRETCH), de_gamma0=Float64(de_gamma0), de_sigma=Float64(de_sigma)))
         st = GC.@preserve pdf theta chain clogp acc bl ccall((:kmc_emcee_run, LIB), Cint,
                                                        (Ref{KmcConfig}, Ptr{Float64}, Ref{KmcOutputs}), cfg, theta, out)
         (st == 9 && by_walker && occursin("KMC_CHAIN_BY_WALKER", last_error())) || break

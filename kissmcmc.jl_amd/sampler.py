@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from .densities import DeviceLogPdf
+from .moves import apply_move
 
 
 def _dp(a):
@@ -24,7 +25,7 @@ class Sampler:
                  device: int = 0, shard_rank: int = 0, shard_count: int = 1, p2p: bool = False,
                  island_gens: int = 0, island_size: int = 0, p2p_finegrained: bool = False, p2p_push: bool = False,
                  dtype: str = "f64", deal_rank: int = 0, deal_count: int = 0,
-                 stream_chain: bool = False, chain_by_walker: bool = False, store_blobs: bool = False):
+                 stream_chain: bool = False, chain_by_walker: bool = False, store_blobs: bool = False, move=None):
         if not isinstance(pdf, DeviceLogPdf):
             raise TypeError(
                 "pdf must be a menu log-density (GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2), "
@@ -78,6 +79,8 @@ class Sampler:
         cfg.device = int(device)
         cfg.shard_rank, cfg.shard_count = int(shard_rank), int(shard_count)
         cfg.deal_rank, cfg.deal_count = int(deal_rank), int(deal_count)   # dealt sub-ensembles (distributed.DealtEmcee)
+        apply_move(move, cfg)                  # None: the stretch move; DEMove: differential evolution (opt-in)
+        self.move = move
         cfg.user_density = pdf.user_handle     # runtime-compiled density (ExprDensity) or None
         cb = getattr(pdf, "c_callback", None)  # host-evaluated density (HostLogPdf) or None
         if cb is not None:
