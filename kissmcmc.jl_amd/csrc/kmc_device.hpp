@@ -1,6 +1,7 @@
 // kmc_device.hpp -- device-side building blocks of the stretch-move half-step (gfx950).
 //
 //   Philox4x32-10 counter RNG + the three per-walker-step draws   (reference src/samplers.jl:250,252,260)
+//   the differential-evolution move's stream and accept test      (KMC_MOVE_DE)
 //   stretch-factor inverse CDF                                     (reference src/samplers.jl:227)
 //   the log-density menu standing in for the user closure          (reference src/samplers.jl:257)
 //
@@ -141,6 +142,54 @@ __device__ __forceinline__ void lds_barrier()
 __device__ __forceinline__ bool accept_test(const Draw& d, double p1, double p0)
 {
     return ((d.t1 + p1) - p0) >= d.lu;
+}
+
+// The move a half-step kernel makes: the stretch move (the reference's, the default) or differential evolution
+// (KMC_MOVE_DE, opt-in; ter Braak 2006, emcee's DEMove): y = x + g (x_j - x_k), two distinct partners from the complementary half.
+enum class Move { Stretch, DE };
+
+// Differential-evolution move: its own Philox stream, key {seed_lo ^ "DEMV", seed_hi},
+// counter {step_lo, step_hi, walker, block}.  Block 0: partners j, k (distinct, uniform over the complementary half) and the accept
+// uniform; block 1: the jitter of gamma.  The kernels reuse Draw: partner = j, z = gamma of this step, t1 unused, lu = log u.
+// DrawConsts carries gamma0 in c0 and sigma in c1 for a DE sampler (kmc_launch.hip: make_args).  log u is log_pos_normal (u in [2^-53, 1)).
+constexpr uint32_t kDeKey = 0x44454D56u;   // "DEMV"
+__device__ __forceinline__ U4 de_bits(uint32_t seed_lo, uint32_t seed_hi, uint64_t step, uint32_t walker, uint32_t block)
+{
+    return philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), walker, block, seed_lo ^ kDeKey, seed_hi);
+}
+// the second partner: uniform over the h - 1 walkers other than j
+__device__ __forceinline__ uint32_t de_partner_k(uint32_t w1, uint32_t nhalf, uint32_t j)
+{
+    const uint32_t k = __umulhi(w1, nhalf - 1u);
+    return k + (k >= j ? 1u : 0u);
+}
+__device__ __forceinline__ double de_accept_u(const U4& w)
+{
+    const uint64_t k = ((uint64_t)w.z << 20) | (uint64_t)(w.w >> 12);
+    return ((double)k + 0.5) * 0x1.0p-52;
+}
+// gamma = gamma0 (1 + sigma v), v uniform in (-1, 1): separately rounded operations, no fma
+__device__ __forceinline__ double de_gamma(const DrawConsts& dc, uint32_t b1x)
+{
+    const double v = 2.0 * (((double)b1x + 0.5) * 0x1.0p-32) - 1.0;
+    return dc.c0 * (1.0 + dc.c1 * v);
+}
+__device__ __forceinline__ Draw de_draw(const DrawConsts& dc, uint64_t step, uint32_t walker, uint32_t* partner_k)
+{
+    const U4 w = de_bits(dc.seed_lo, dc.seed_hi, step, walker, 0u);
+    const U4 v = de_bits(dc.seed_lo, dc.seed_hi, step, walker, 1u);
+    Draw d;
+    d.partner = __umulhi(w.x, dc.nhalf);
+    *partner_k = de_partner_k(w.y, dc.nhalf, d.partner);
+    d.z = de_gamma(dc, v.x);
+    d.t1 = 0.0;
+    d.lu = log_pos_normal(de_accept_u(w));
+    return d;
+}
+// a symmetric move: p1 - p0 >= log u, no (N-1) log z term
+__device__ __forceinline__ bool de_accept_test(const Draw& d, double p1, double p0)
+{
+    return (p1 - p0) >= d.lu;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -4,5 +4,5 @@
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void table_de_exponential(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { de_part<Exponential>(L, K, iter, ragged, vec, gen); }
+void table_de_exponential(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { density_part<Exponential, 3>(L, K, iter, ragged, false, vec, gen); }
 }  // namespace kmc

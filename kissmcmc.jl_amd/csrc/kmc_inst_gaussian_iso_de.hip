@@ -4,5 +4,5 @@
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void table_de_gaussian_iso(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { de_part<GaussianIso>(L, K, iter, ragged, vec, gen); }
+void table_de_gaussian_iso(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { density_part<GaussianIso, 3>(L, K, iter, ragged, false, vec, gen); }
 }  // namespace kmc

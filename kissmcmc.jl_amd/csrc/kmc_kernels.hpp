@@ -29,6 +29,8 @@
 //       finds nothing dirty; streaming moments are a reduce-scatter over the wave.
 //   half_step_generic<Density>          any ndim; one walker per lane, scalar loops.  Used for ndim > 1024, for
 //       host-evaluated densities and with KMC_PLAN=generic.
+// half_step_de_vec / half_step_de_generic are the same two bodies with the differential-evolution move (Move::DE,
+// KMC_MOVE_DE).
 #pragma once
 #include "kmc_device.hpp"
 
@@ -429,11 +431,15 @@ static __device__ unsigned long long g_probe[2][8192][8];
 
 // RAGGED = false: ndim == 2*L*K exactly (row stride and every mask fold at compile time);
 // RAGGED = true : ndim < 2*L*K, runtime ndim and row stride (preloaded, see the body), tail chunks folded onto the row's last chunk.
-template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double>
+// M = Move::DE: the differential-evolution move -- block 0 of its Philox stream and a second partner row (xk)
+// in front of the first scheduling barrier, block 1 behind it; no draw ring; one GPU, double rows, no blobs.
+template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double, Move M = Move::Stretch>
 __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const HalfStepArgs& a)
 {
     static_assert(L >= 1 && L <= 64 && (L & (L - 1)) == 0, "L must be a power of two <= 64");
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
+    constexpr bool kDE = M == Move::DE;
+    static_assert(!kDE || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "the DE move: one GPU, double rows, no blobs (kmc_validate)");
     using V2 = typename RowOf<T>::V2;                   // one chunk = two consecutive elements of a row
     T* const posT = reinterpret_cast<T*>(f.pos);
     static_assert(ITER >= 1 && ITER <= L, "a group's scalar lanes must cover its iterations");
@@ -473,7 +479,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
 
     // ---- scalar layout: one walker per lane.  Lane (g, j) carries walker slot js = j % ITER of its group and,
     //      when draws are computed, the walker's q-th next step, q = j / ITER < Q; the lanes with q == 0
-    //      (j < ITER) feed this launch -------------------------------------------------------------------
+    //      (j < ITER) feed this launch (DE: the other lanes draw for a clamped walker and are never used) -----
     constexpr int Q = (L / ITER) >= 4 ? 4 : (L / ITER);                 // steps drawn per heavy launch
     // worth it when a wave carries few walkers (long rows): at <= 8 walkers per wave the per-walker scalar work
     // dominates the wave's instruction count; with more (C2: 16) the extra load in the chain costs what it saves
@@ -482,11 +488,11 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     // (round 2, one more bounded try for L = 8 -- C2 -- in both launch modes: 4.83 against 4.27 us per half-step under the table
     //  graph, 4.70 against 3.99 with the step preloaded: the ring entry is one more dependent load in front of the partner
     //  row, and at 16 walkers per wave the Philox it replaces was already hidden.  Dropped; profiles/NOTES.md.)
-    constexpr bool kRing = Q >= 2 && L >= 16 && L <= 32;
+    constexpr bool kRing = !kDE && Q >= 2 && L >= 16 && L <= 32;        // (DE: nothing to park -- it has no log z)
     const int64_t oth_row0 = (int64_t)(1 - half) * (int64_t)(P2P ? (uint32_t)nact : f.nhalf);
     const int  jq     = j / ITER, js = j - jq * ITER;
     const bool useA   = jq == 0;
-    const int  iA     = w0 + (jq < Q ? js : 0) * G + g;
+    const int  iA     = w0 + (kDE || jq < Q ? js : 0) * G + g;
     const bool validA = useA && (iA < nact);
     const int      iAc = iA < nact ? iA : nact - 1;
     const int64_t  rowA = own_row0 + iAc;                                // row in pos / index in logp, naccept
@@ -499,6 +505,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     // ---- row layout: own rows of every iteration (independent of the random draws) ----------
     bool    validB[ITER];
     double2 xc[ITER][K], xo[ITER][K];
+    double2 xk[ITER][K];                                                // DE: the second partner's rows (xo: the first's, then the proposal)
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int i = w0 + it * G + g;
@@ -530,12 +537,17 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     const bool fresh = ring_on && __all(!useA || e1y_hi == (uint32_t)step);
     U4 bits{0u, 0u, 0u, 0u};
     uint32_t partnerA = e1y_lo;                                         // :250
-    if (!fresh) {
+    uint32_t partnerK = 0u;                                             // DE: the second partner
+    if constexpr (kDE) {                                                // block 0: both partners and the accept uniform
+        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 0u);
+        partnerA = __umulhi(bits.x, f.nhalf);
+        partnerK = de_partner_k(bits.y, f.nhalf, partnerA);
+    } else if (!fresh) {
         bits = draw_bits(dcf, step + 2ull * (uint64_t)jq, (uint64_t)f.gw0 + (uint64_t)iAc);   // RNG keyed by the GLOBAL walker index
         partnerA = draw_partner(dcf, bits);
     }
 #if KMC_PROBE_PINS
-    asm volatile("" :: "v"(partnerA));
+    if constexpr (!kDE) asm volatile("" :: "v"(partnerA));
 #endif
     KMC_STAMP(1);                                       // Philox done: the partner index is known
 
@@ -549,9 +561,12 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     const int64_t shard_stride = 2 * (int64_t)a.hloc * ld;              // push: pos is (1 + nranks) blocks of a shard's rows -- block 0 this rank's, block 1 + q a copy of rank q's
     auto load_partner_rows = [&](int it) {
         const V2* oth;
+        const V2* othk = nullptr;                                       // DE: x_k
         if constexpr (!P2P) {
             const uint32_t partner = (uint32_t)__builtin_amdgcn_ds_bpermute((gbase + it) * 4, (int)partnerA);
+            const uint32_t pk = kDE ? (uint32_t)__builtin_amdgcn_ds_bpermute((gbase + it) * 4, (int)partnerK) : 0u;
             oth = reinterpret_cast<const V2*>(posT + row_off(oth_row0 + partner));
+            if constexpr (kDE) othk = reinterpret_cast<const V2*>(posT + row_off(oth_row0 + pk));
         } else {
             const int src = (gbase + it) * 4;
             const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)addrA);
@@ -570,6 +585,10 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) xo[it][k] = load_row(&oth[ck[k]]);
+        if constexpr (kDE) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) xk[it][k] = load_row(&othk[ck[k]]);
+        }
     };
     if constexpr (P2P) {
         // owner rank and row of the partner, resolved once per walker; the row address travels
@@ -607,7 +626,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     if (eager_late != 0) sch = a.sched_inline;
     const bool count  = (sch.flags & kCount) != 0;
     const bool sample = (sch.flags & kSample) != 0;
-    DrawConsts dc = a.dc;                                               // seed and nhalf from the front parameters
+    DrawConsts dc = a.dc;                                               // seed and nhalf from the front parameters (DE: gamma0 in c0, sigma in c1)
     dc.seed_lo = f.seed_lo; dc.seed_hi = f.seed_hi; dc.nhalf = f.nhalf;
     // Streaming moments are sojourn-weighted: a walker's value is credited, times the number of
     // samples it stood for, when it is replaced (and by flush_moments_vec at read-out).  Only waves
@@ -646,13 +665,17 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         if (do_mom && a.mring != nullptr) { ring_posted = a.mcnt[tid >> 6]; ring_swept = a.mswept[tid >> 6]; }
     }
 #if KMC_PROBE_PINS
-    asm volatile("" :: "s"(count ? 1 : 0), "s"(a.dc.c0));
+    if constexpr (!kDE) asm volatile("" :: "s"(count ? 1 : 0), "s"(a.dc.c0));
 #endif
     KMC_STAMP(3);                                       // the argument struct has arrived (schedule entry, constants)
     Draw dr;
     dr.partner = partnerA; dr.z = e1.x; dr.t1 = e0.x; dr.lu = e0.y;
     double ua = 0.5;
-    if (!fresh) {                                                       // the arithmetic of draw_finish, in two parts
+    if constexpr (kDE) {                                                // block 1: the jitter of gamma; z = gamma, t1 unused
+        const U4 b1 = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 1u);
+        dr.z = de_gamma(dc, b1.x);
+        dr.t1 = 0.0;
+    } else if (!fresh) {                                                // the arithmetic of draw_finish, in two parts
         const double uz = ((double)bits.y + 0.5) * 0x1.0p-32;
         const double t  = fma(uz, dc.c1, dc.c0);
         dr.z = t * t;                                                   // :252
@@ -664,7 +687,9 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
 #pragma unroll
     for (int it = kFirst; it < ITER; ++it) load_partner_rows(it);
     __builtin_amdgcn_sched_barrier(0);
-    if (!fresh) {
+    if constexpr (kDE) {
+        dr.lu = log_pos_normal(de_accept_u(bits));
+    } else if (!fresh) {
         dr.lu = log_pos_normal(ua);                                     // :260
         if constexpr (kRing) {
             if (ring_on && jq >= 1 && jq < Q && iA < nact) {            // park the walkers' next steps
@@ -675,14 +700,14 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         }
     }
 #if KMC_PROBE_PINS
-    asm volatile("" :: "v"(dr.lu), "v"(dr.t1));
+    if constexpr (!kDE) asm volatile("" :: "v"(dr.lu), "v"(dr.t1));
 #endif
     KMC_STAMP(4);                                       // both logarithms done, every partner-row load issued
     double zB[ITER];
 #pragma unroll
     for (int it = 0; it < ITER; ++it) zB[it] = bperm_f64((gbase + it) * 4, dr.z);
 
-    // ---- stretch move + log-pdf; xo becomes the proposal ------------------------------------
+    // ---- stretch or DE move + log-pdf; xo becomes the proposal ------------------------------
     double myp1 = 0.0;
     constexpr int kRowND = RowEvalTrait<Dens>::n;                       // > 0: a function body over the whole proposal (see below)
     double blob1[BlobTrait<Dens>::n > 0 ? BlobTrait<Dens>::n : 1];      // ... and the blob it returned (blob1 of src/samplers.jl:257), scalar layout
@@ -690,8 +715,13 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     for (int it = 0; it < ITER; ++it) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {                                   // :255
-            xo[it][k].x = as_stored<T>(fma(zB[it], xc[it][k].x - xo[it][k].x, xo[it][k].x));
-            xo[it][k].y = as_stored<T>(fma(zB[it], xc[it][k].y - xo[it][k].y, xo[it][k].y));
+            if constexpr (kDE) {                                        // y = x + g (x_j - x_k), separately rounded
+                xo[it][k].x = xc[it][k].x + zB[it] * (xo[it][k].x - xk[it][k].x);
+                xo[it][k].y = xc[it][k].y + zB[it] * (xo[it][k].y - xk[it][k].y);
+            } else {
+                xo[it][k].x = as_stored<T>(fma(zB[it], xc[it][k].x - xo[it][k].x, xo[it][k].x));
+                xo[it][k].y = as_stored<T>(fma(zB[it], xc[it][k].y - xo[it][k].y, xo[it][k].y));
+            }
         }
         if constexpr (MultiSumTrait<Dens>::n > 0) {                    // a function body feeding several sums over the elements
             double S[MultiSumTrait<Dens>::n];
@@ -736,11 +766,11 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     }
 
 #if KMC_PROBE_PINS
-    asm volatile("" :: "v"(myp1));
+    if constexpr (!kDE) asm volatile("" :: "v"(myp1));
 #endif
     KMC_STAMP(5);                                       // both rows have arrived, the proposal's log-pdf is reduced
     // ---- accept test in the scalar layout ---------------------------------------------------
-    const bool acc = validA && accept_test(dr, myp1, p0);               // :260
+    const bool acc = validA && (kDE ? de_accept_test(dr, myp1, p0) : accept_test(dr, myp1, p0));   // :260
     const unsigned long long accmask = __ballot(acc);
     if (acc) {
         store_wt(&logp_p[rowA], myp1);                                  // :262
@@ -852,7 +882,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     }
     KMC_STAMP(7);                                       // the last store is issued
 #ifdef KMC_PROBE
-    {
+    if constexpr (!kDE) {                               // (the DE kernels stamp, but keep no record)
         unsigned long long st[8];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         KMC_STAMP_READ(st[0], 80, 81); KMC_STAMP_READ(st[1], 82, 83); KMC_STAMP_READ(st[2], 84, 85); KMC_STAMP_READ(st[3], 86, 87);
@@ -866,6 +896,11 @@ template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = d
 __global__ __launch_bounds__(vec_tpb(L)) void half_step_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_vec_body<Dens, L, K, ITER, P2P, RAGGED, T>(KMC_FRONT_PACK, a);
+}
+template <class Dens, int L, int K, int ITER, bool RAGGED>
+__global__ __launch_bounds__(vec_tpb(L)) void half_step_de_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::DE>(KMC_FRONT_PACK, a);
 }
 
 // Moment read-out: credit every walker's current value with the samples it has stood for since it
@@ -925,10 +960,12 @@ __global__ __launch_bounds__(vec_tpb(L)) void flush_moments_vec(const FlushArgs 
 // ------------------------------------------------------------------------------------------
 // Generic kernel: one walker per lane, any ndim.
 // ------------------------------------------------------------------------------------------
-template <class Dens, bool P2P, class T = double>
+template <class Dens, bool P2P, class T = double, Move M = Move::Stretch>
 __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, const HalfStepArgs& a)
 {
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
+    constexpr bool kDE = M == Move::DE;
+    static_assert(!kDE || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "the DE move: one GPU, double rows, no blobs (kmc_validate)");
     const int tid = blockIdx.x * 256 + threadIdx.x;
     const SchedEntry sch = schedule_of(f, a);
     const uint64_t step = 2ull * (uint64_t)sch.gen + (uint64_t)a.half;      // (eager: sched_inline.gen)
@@ -938,12 +975,16 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     const bool count  = (sch.flags & kCount) != 0;
     const bool sample = (sch.flags & kSample) != 0;
     const int64_t gw = a.own_row0 + tid;                                // row in pos / index in logp, naccept
-    const Draw dr = draw_step(a.dc, step, (uint64_t)(a.gw0 + tid));
+    uint32_t partner_k = 0u;                                            // DE: the second partner
+    const Draw dr = kDE ? de_draw(a.dc, step, (uint32_t)(a.gw0 + tid), &partner_k)   // DE: partner = j, z = gamma, lu = log u
+                        : draw_step(a.dc, step, (uint64_t)(a.gw0 + tid));
     const int64_t ld = a.ld;
     T* own = reinterpret_cast<T*>(a.pos) + gw * ld;
     const T* oth;
+    const T* othk = nullptr;                                            // DE: x_k (oth: x_j)
     if constexpr (!P2P) {
         oth = reinterpret_cast<const T*>(a.pos) + (a.oth_row0 + dr.partner) * ld;
+        if constexpr (kDE) othk = reinterpret_cast<const T*>(a.pos) + (a.oth_row0 + partner_k) * ld;
     } else {
         const uint32_t q = a.hloc_shift >= 0 ? dr.partner >> a.hloc_shift : dr.partner / a.hloc;
         const uint32_t r = dr.partner - q * a.hloc;
@@ -962,24 +1003,25 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
         }
         return (double)oth[d];
     };
+    // element d of the proposal
+    auto y_at = [&](int d) -> double {
+        if constexpr (kDE) return own[d] + dr.z * (oth[d] - othk[d]);  // y = x + g (x_j - x_k), separately rounded
+        else { const double o = oth_at(d); return as_stored<T>(fma(dr.z, (double)own[d] - o, o)); }   // :255
+    };
 
     constexpr bool kHost = HostEvalTrait<Dens>::value;
     if constexpr (kHost) {
         if (a.prop_out != nullptr) {                                    // PROPOSE pass
-            for (int d = 0; d < ndim; ++d) { const double o = oth_at(d); a.prop_out[(int64_t)tid * a.prop_ld + d] = fma(dr.z, (double)own[d] - o, o); }
+            for (int d = 0; d < ndim; ++d) a.prop_out[(int64_t)tid * a.prop_ld + d] = y_at(d);
             return;
         }
     }
     typename Dens::Seq q;
     Dens::seq_init(q);
-    for (int d = 0; d < ndim; ++d) {
-        const double o = oth_at(d);
-        const double y = as_stored<T>(fma(dr.z, (double)own[d] - o, o));   // :255
-        Dens::seq_add(q, y, d, a.dp);
-    }
+    for (int d = 0; d < ndim; ++d) Dens::seq_add(q, y_at(d), d, a.dp);
     double p1 = Dens::seq_finish(q, ndim, a.dp);                         // :257
     if constexpr (kHost) p1 = a.p1_in[tid];
-    const bool acc = accept_test(dr, p1, p0);                           // :260
+    const bool acc = kDE ? de_accept_test(dr, p1, p0) : accept_test(dr, p1, p0);   // :260
     if constexpr (kHost) { if (a.acc_out != nullptr) a.acc_out[tid] = acc ? 1 : 0; }
 
     const bool do_mom = sample && a.msum != nullptr;
@@ -988,8 +1030,9 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     if (acc || do_mom || do_chain) {
         for (int d = 0; d < ndim; ++d) {
             const double xcd = (double)own[d];
-            const double o = acc ? oth_at(d) : 0.0;
-            const double cur = acc ? as_stored<T>(fma(dr.z, xcd - o, o)) : xcd;
+            double cur;
+            if constexpr (kDE) cur = acc ? xcd + dr.z * (oth[d] - othk[d]) : xcd;
+            else { const double o = acc ? oth_at(d) : 0.0; cur = acc ? as_stored<T>(fma(dr.z, xcd - o, o)) : xcd; }
             if (acc) own[d] = (T)cur;                                   // :261
             if (do_chain) reinterpret_cast<T*>(a.chain)[row * ld + d] = (T)cur;   // :269
             if (do_mom) {
@@ -1023,6 +1066,11 @@ template <class Dens, bool P2P, class T = double>
 __global__ __launch_bounds__(256) void half_step_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_generic_body<Dens, P2P, T>(KMC_FRONT_PACK, a);
+}
+template <class Dens>
+__global__ __launch_bounds__(256) void half_step_de_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_generic_body<Dens, false, double, Move::DE>(KMC_FRONT_PACK, a);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -353,7 +353,7 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
     // evaluated per walker on the whole proposal (kmc_kernels.hpp, RowEvalTrait; no blobs, ndim <= kBodyVecMaxDim)
     if (ud->is_body && ((with_vec && !sep_routed(ud) && !body_vec_possible(ud, ndim)) || island_S > 0))
         return fail(KMC_ERR_UNSUPPORTED, "this body density runs in the one-walker-per-lane kernels only");
-    // KMC_MOVE_DE: the differential-evolution forms of the two half-step kernels (no staged kernel; one GPU, double rows: kmc_validate)
+    // KMC_MOVE_DE: the two half-step bodies with Move::DE (no staged kernel; one GPU, double rows: kmc_validate)
     const bool staged = !de && !with_vec && staged_possible(ud, f32, ndim, p2p);
     char key[128];
     std::snprintf(key, sizeof(key), "%d:%d,%d,%d,%d|%d,%d|%d|%d|%lld|%d|%d|%d|%d|%d|%d", (int)with_vec, L, K, iter, (int)ragged, resident_K,
@@ -361,6 +361,7 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
                   generation_nd, (int)de);
     const char* peer = p2p ? "true" : "false";         // KMC_P2P: partner rows read from their owners (pull)
     const char* rowt = f32 ? "float" : "double";       // storage type of the walker rows (KMC_F32 / KMC_F64)
+    const char* move = de ? ", kmc::Move::DE" : "";    // the half-step bodies' move (the stretch move by default)
     std::lock_guard<std::mutex> lock(ud->mu);
     auto it = ud->code.find(key);
     if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
@@ -368,16 +369,15 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
     const char* envdir = std::getenv("KMC_CSRC_DIR");
     const std::string dir = envdir ? std::string(envdir) : library_dir() + "/csrc";
     const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_ker = read_file(dir + "/kmc_kernels.hpp"),
-                      h_isl = read_file(dir + "/kmc_islands.hpp"), h_gen = read_file(dir + "/kmc_generation.hpp"), h_de = read_file(dir + "/kmc_de.hpp");
-    if (h_dev.empty() || h_ker.empty() || h_isl.empty() || h_gen.empty() || h_de.empty())
+                      h_isl = read_file(dir + "/kmc_islands.hpp"), h_gen = read_file(dir + "/kmc_generation.hpp");
+    if (h_dev.empty() || h_ker.empty() || h_isl.empty() || h_gen.empty())
         return fail(KMC_ERR_BAD_ARG, "user density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
 
     std::ostringstream src;
-    src << "#include \"kmc_islands.hpp\"\n#include \"kmc_generation.hpp\"\n" << (de ? "#include \"kmc_de.hpp\"\n" : "") << user_functor_source(ud) << user_density_alias(ud, ndim)
+    src << "#include \"kmc_islands.hpp\"\n#include \"kmc_generation.hpp\"\n" << user_functor_source(ud) << user_density_alias(ud, ndim)
         << (ud->is_body && with_vec && sep_routed(ud) ? ud->sep_functor + (ud->sep_nacc > 1 ? "using UDV = kmc::SepDensityN<UserS>;\n" : "using UDV = kmc::SepDensity<UserS>;\n")
                                                 : std::string("using UDV = UD;\n"))
-        << (de ? std::string("extern \"C\" __global__ __launch_bounds__(256) void kmc_user_generic(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_de_generic_body<UD>(KMC_FRONT_PACK, a); }\n")
-               : "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_generic(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_generic_body<UD, " + std::string(peer) + ", " + rowt + ">(KMC_FRONT_PACK, a); }\n")
+        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_generic(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_generic_body<UD, " << peer << ", " << rowt << move << ">(KMC_FRONT_PACK, a); }\n"
         << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
         << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_init_ball(const kmc::InitBallArgs a) { kmc::init_ball_body<UD>(a); }\n";
     if (ud->is_body && with_vec && sep_routed(ud))
@@ -385,12 +385,9 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
     if (staged)
         src << "extern \"C\" __global__ __launch_bounds__(" << kStagedTPB << ") void kmc_user_staged(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_staged_body<UD, "
             << ndim << ">(KMC_FRONT_PACK, a); }\n";
-    if (with_vec && de)      // KMC_MOVE_DE (kmc_de.hpp)
-        src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_de_vec_body<UDV, "
-            << L << ", " << K << ", " << iter << ", " << (ragged ? "true" : "false") << ">(KMC_FRONT_PACK, a); }\n";
-    else if (with_vec)
+    if (with_vec)
         src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_vec_body<UDV, "
-            << L << ", " << K << ", " << iter << ", " << peer << ", " << (ragged ? "true" : "false") << ", " << rowt << ">(KMC_FRONT_PACK, a); }\n";
+            << L << ", " << K << ", " << iter << ", " << peer << ", " << (ragged ? "true" : "false") << ", " << rowt << move << ">(KMC_FRONT_PACK, a); }\n";
     if (resident_K == 2048 && island_S == 0 && ud->is_body)   // two walkers per thread (1026 .. 2048 walkers)
         src << "extern \"C\" __global__ __launch_bounds__(1024) void kmc_user_resident(const kmc::ResidentArgs a) { kmc::resident_lane2_body<UD, " << ndim << ">(a); }\n";
     else if (resident_K <= -100 && island_S == 0 && !ud->is_body)
@@ -413,12 +410,12 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
             << (-generation_nd) / 100 << ", " << (-generation_nd) % 100 << ">(KMC_GEN_FRONT_PACK, a); }\n";
     const std::string text = src.str();
 
-    const char* headers[5] = {h_ker.c_str(), h_dev.c_str(), h_isl.c_str(), h_gen.c_str(), h_de.c_str()};
-    const char* names[5] = {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_islands.hpp", "kmc_generation.hpp", "kmc_de.hpp"};
+    const char* headers[4] = {h_ker.c_str(), h_dev.c_str(), h_isl.c_str(), h_gen.c_str()};
+    const char* names[4] = {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_islands.hpp", "kmc_generation.hpp"};
     const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=14"};
     std::vector<char> code;
     std::string log;
-    const kmc_status cst = rtc_compile_cached(text, "kmc_user_density.hip", de ? 5 : 4, headers, names, 6, opts, &code, &log);
+    const kmc_status cst = rtc_compile_cached(text, "kmc_user_density.hip", 4, headers, names, 6, opts, &code, &log);
     if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "user density does not compile:\n" + log);
     if (cst != KMC_OK) return cst;
     auto ins = ud->code.emplace(key, std::move(code));

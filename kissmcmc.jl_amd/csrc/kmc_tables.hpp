@@ -6,7 +6,6 @@
 #include "kmc_islands.hpp"
 #include "kmc_generation.hpp"
 #include "kmc_metropolis.hpp"
-#include "kmc_de.hpp"
 
 namespace kmc {
 
@@ -21,33 +20,35 @@ using MetropolisFn = void (*)(const MetropolisArgs);
 using MetropolisTabledFn = void (*)(const MetropolisArgs, const double*, int);
 
 #ifdef KMC_TABLES_IMPL
-template <class D, int L, int K, int ITER, bool P2P, bool RAGGED, class T>
+template <class D, int L, int K, int ITER, bool P2P, bool RAGGED, class T, Move M>
 HalfStepFn vec_one()
 {
     // a group's ITER scalar lanes must fit in its L lanes; keep the register tile (ITER*K chunks) bounded
-    if constexpr (ITER <= L && ITER * K <= 16) return half_step_vec<D, L, K, ITER, P2P, RAGGED, T>;
-    else return nullptr;
+    if constexpr (ITER > L || ITER * K > 16) return nullptr;
+    else if constexpr (M == Move::DE) return half_step_de_vec<D, L, K, ITER, RAGGED>;
+    else return half_step_vec<D, L, K, ITER, P2P, RAGGED, T>;
 }
 
-template <class D, int L, int K, bool P2P, bool RAGGED, class T>
+template <class D, int L, int K, bool P2P, bool RAGGED, class T, Move M = Move::Stretch>
 HalfStepFn vec_iter(int iter)
 {
-    // full ITER range only for the single-GPU exact double kernels (tuning); the others: what make_plan picks
+    // full ITER range only for the single-GPU exact double kernels (tuning, and the DE move); the others: what make_plan picks
     constexpr bool kWide = !P2P && !RAGGED && sizeof(T) == 8;
     switch (iter) {
-    case 1: return vec_one<D, L, K, 1, P2P, RAGGED, T>();
-    case 2: return vec_one<D, L, K, 2, P2P, RAGGED, T>();
-    case 4: return vec_one<D, L, K, 4, P2P, RAGGED, T>();
-    case 8: if constexpr (kWide || (P2P && !RAGGED)) return vec_one<D, L, K, 8, P2P, RAGGED, T>(); else return nullptr;
-    case 16: if constexpr (kWide) return vec_one<D, L, K, 16, P2P, RAGGED, T>(); else return nullptr;
+    case 1: return vec_one<D, L, K, 1, P2P, RAGGED, T, M>();
+    case 2: return vec_one<D, L, K, 2, P2P, RAGGED, T, M>();
+    case 4: return vec_one<D, L, K, 4, P2P, RAGGED, T, M>();
+    case 8: if constexpr (kWide || (P2P && !RAGGED)) return vec_one<D, L, K, 8, P2P, RAGGED, T, M>(); else return nullptr;
+    case 16: if constexpr (kWide) return vec_one<D, L, K, 16, P2P, RAGGED, T, M>(); else return nullptr;
     default: return nullptr;
     }
 }
 
-// A density's kernels are instantiated in FOUR translation units, so that the build's longest job is a quarter of a density
-// (kmc_inst_<density>{,_var,_p2p,_lds}.hip): PART 0 = double rows, exact size, one GPU (incl. the tuning geometries);
-// PART 1 = ragged sizes and KMC_F32 rows, one GPU; PART 2 = the peer-to-peer kernels; (the LDS-resident and Metropolis
-// kernels are the fourth).  Each part only names -- and therefore only compiles -- its own instantiations.
+// A density's kernels are instantiated in FIVE translation units, so that the build's longest job is a fraction of a density
+// (kmc_inst_<density>{,_var,_p2p,_de,_lds}.hip): PART 0 = double rows, exact size, one GPU (incl. the tuning geometries);
+// PART 1 = ragged sizes and KMC_F32 rows, one GPU; PART 2 = the peer-to-peer kernels; PART 3 = the differential-evolution
+// move (KMC_MOVE_DE: exact and ragged double rows, one GPU); (the LDS-resident and Metropolis kernels are the fifth).  Each
+// part only names -- and therefore only compiles -- its own instantiations.
 template <class D, int L, int K, int PART>
 HalfStepFn vec_pick(int iter, bool ragged, bool f32)
 {
@@ -55,7 +56,8 @@ HalfStepFn vec_pick(int iter, bool ragged, bool f32)
     else if constexpr (PART == 1) {
         if (f32) return ragged ? vec_iter<D, L, K, false, true, float>(iter) : vec_iter<D, L, K, false, false, float>(iter);   // KMC_F32: single rows, one GPU
         return vec_iter<D, L, K, false, true, double>(iter);
-    } else return ragged ? vec_iter<D, L, K, true, true, double>(iter) : vec_iter<D, L, K, true, false, double>(iter);
+    } else if constexpr (PART == 2) return ragged ? vec_iter<D, L, K, true, true, double>(iter) : vec_iter<D, L, K, true, false, double>(iter);
+    else return ragged ? vec_iter<D, L, K, false, true, double, Move::DE>(iter) : vec_iter<D, L, K, false, false, double, Move::DE>(iter);
 }
 
 // geometries make_plan can pick: exact + ragged, single-GPU + P2P; the extra exact single-GPU ones
@@ -86,39 +88,8 @@ void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec
     *vec = vec_lookup<D, PART>(L, K, iter, ragged, f32);
     if constexpr (PART == 0) *gen = half_step_generic<D, false, double>;
     else if constexpr (PART == 1) *gen = f32 ? half_step_generic<D, false, float> : half_step_generic<D, false, double>;
-    else *gen = half_step_generic<D, true, double>;
-}
-
-// the differential-evolution move (KMC_MOVE_DE; kmc_inst_<density>_de.hip): the vector kernels of the geometries make_plan picks,
-// exact and ragged, double rows on one GPU, and the generic kernel
-template <class D, int L, int K, bool RAGGED>
-HalfStepFn vec_de_iter(int iter)
-{
-    auto one = [](auto it) -> HalfStepFn {
-        constexpr int ITER = decltype(it)::value;
-        if constexpr (ITER <= L && ITER * K <= 16) return half_step_de_vec<D, L, K, ITER, RAGGED>;
-        else return nullptr;
-    };
-    switch (iter) {
-    case 1: return one(std::integral_constant<int, 1>{});
-    case 2: return one(std::integral_constant<int, 2>{});
-    case 4: return one(std::integral_constant<int, 4>{});
-    case 8: if constexpr (!RAGGED) return one(std::integral_constant<int, 8>{}); else return nullptr;
-    case 16: if constexpr (!RAGGED) return one(std::integral_constant<int, 16>{}); else return nullptr;
-    default: return nullptr;
-    }
-}
-template <class D>
-void de_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
-{
-    *gen = half_step_de_generic<D>;
-    *vec = nullptr;
-    if constexpr (D::kHasFrag) {
-#define KMC_LK(l, k) if (L == l && K == k) { *vec = ragged ? vec_de_iter<D, l, k, true>(iter) : vec_de_iter<D, l, k, false>(iter); return; }
-        KMC_LK(1, 1) KMC_LK(2, 1) KMC_LK(4, 1) KMC_LK(4, 2) KMC_LK(8, 2) KMC_LK(16, 2) KMC_LK(32, 2) KMC_LK(64, 2)
-        KMC_LK(64, 4) KMC_LK(64, 8)
-#undef KMC_LK
-    }
+    else if constexpr (PART == 2) *gen = half_step_generic<D, true, double>;
+    else *gen = half_step_de_generic<D>;
 }
 
 // island mode: one workgroup per S-walker island, rows of up to 4*K doubles
@@ -267,8 +238,8 @@ MetropolisTabledFn metropolis_tabled_lookup(int ndim)
 #endif  // KMC_TABLES_IMPL
 
 // entry points per density: table_<density> (kmc_inst_<density>.hip: PART 0, the log-pdf and initial-ball kernels, and the
-// dispatch to the other parts), part_var_ / part_p2p_<density> (kmc_inst_<density>_var.hip / _p2p.hip), and the LDS-resident +
-// Metropolis tables below (kmc_inst_<density>_lds.hip)
+// dispatch to the other parts), part_var_ / part_p2p_<density> (kmc_inst_<density>_var.hip / _p2p.hip), table_de_<density> (PART 3,
+// kmc_inst_<density>_de.hip), and the LDS-resident + Metropolis tables below (kmc_inst_<density>_lds.hip)
 #define KMC_DECLARE_DENSITY_TABLE(name) \
     void table_##name(int L, int K, int iter, bool p2p, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen, LogpdfFn* lp); \
     void part_var_##name(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen);                      \
