@@ -72,11 +72,27 @@ inline long debug_opt_long(const char* name, long absent)
     return debug_opt(name, &v) && !v.empty() ? std::atol(v.c_str()) : absent;
 }
 
-// kernel tables of the menu densities (kmc_inst_*.hip) and the digest of kmc_config.params the kernels take
-bool lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen, kmc::LogpdfFn* lp);
+// The menu densities: f(D{}) with the density type D of a menu density id (its kernels: kmc_tables.hpp), `none` for any other id.
+template <class R, class F>
+R with_density(int density, R none, F&& f)
+{
+    switch (density) {
+    case KMC_GAUSSIAN_ISO: return f(kmc::GaussianIso{});
+    case KMC_EXPONENTIAL: return f(kmc::Exponential{});
+    case KMC_ROSENBROCK: return f(kmc::Rosenbrock{});
+    case KMC_LOGNORMAL: return f(kmc::LogNormal{});
+    case KMC_MVNORMAL2: return f(kmc::MvNormal2{});
+    default: return none;
+    }
+}
+// kernel tables of the menu densities (kmc_plan.hip; false / nullptr for any other id), their row-length rules and the digest of
+// kmc_config.params the kernels take
+bool lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
 // KMC_MOVE_DE: gamma0 as the kernels use it (kmc_config.de_gamma0, or 2.38 / sqrt(2 ndim) when that is 0)
 inline double de_gamma0_of(const kmc_config& c) { return c.de_gamma0 > 0.0 ? c.de_gamma0 : 2.38 / std::sqrt(2.0 * (double)c.ndim); }
 bool lookup_de(int density, int L, int K, int iter, bool ragged, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
+kmc::LogpdfFn logpdf_fn(int density);
+kmc_status check_ndim(int density, int64_t ndim);
 kmc_status digest_params(const kmc_config& c, kmc::DensityParams* dp);
 
 // runtime-compiled user densities (hiprtc)

@@ -1,15 +1,9 @@
-// Kernel instantiations for the exponential (README.md:15) log-density, part 0 of 4 (kmc_tables.hpp: vec_pick): double rows of exact size on
-// one GPU, the generic kernel, the log-pdf and initial-ball kernels -- and the dispatch to the other parts.
+// Kernel instantiations for the exponential (README.md:15) log-density, PART 0 (kmc_tables.hpp):
+// double rows of exact size on one GPU and the generic kernel; the log-pdf and initial-ball kernels.
 #define KMC_TABLES_IMPL
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void table_exponential(int L, int K, int iter, bool p2p, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen, LogpdfFn* lp)
-{
-    *lp = logpdf_rows<Exponential>;
-    if (p2p) { if (f32) { *vec = nullptr; *gen = nullptr; } else part_p2p_exponential(L, K, iter, ragged, vec, gen); }
-    else if (ragged || f32) part_var_exponential(L, K, iter, ragged, f32, vec, gen);
-    else density_part<Exponential, 0>(L, K, iter, false, false, vec, gen);
-}
-InitBallFn init_ball_exponential() { return init_ball<Exponential>; }
+KMC_INSTANTIATE_PART(Exponential, 0);
+KMC_INSTANTIATE_ROWS(Exponential);
 }  // namespace kmc

@@ -1,8 +1,8 @@
-// Kernel instantiations for the isotropic Gaussian log-density with the differential-evolution move (KMC_MOVE_DE, opt-in):
-// the vector kernels (exact and ragged rows) and the generic kernel, double rows on one GPU.
+// Kernel instantiations for the isotropic Gaussian log-density, PART 3 (kmc_tables.hpp):
+// the differential-evolution move (KMC_MOVE_DE, opt-in): vector (exact and ragged rows) and generic kernels, double rows, one GPU.
 #define KMC_TABLES_IMPL
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void table_de_gaussian_iso(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { density_part<GaussianIso, 3>(L, K, iter, ragged, false, vec, gen); }
+KMC_INSTANTIATE_PART(GaussianIso, 3);
 }  // namespace kmc

@@ -1,7 +1,8 @@
-// Kernel instantiations for the LogNormal log-density, part 2 of 4: the peer-to-peer kernels (KMC_P2P).
+// Kernel instantiations for the LogNormal log-density, PART 2 (kmc_tables.hpp):
+// the peer-to-peer kernels (KMC_P2P).
 #define KMC_TABLES_IMPL
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void part_p2p_lognormal(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { density_part<LogNormal, 2>(L, K, iter, ragged, false, vec, gen); }
+KMC_INSTANTIATE_PART(LogNormal, 2);
 }  // namespace kmc

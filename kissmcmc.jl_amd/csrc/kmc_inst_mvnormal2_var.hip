@@ -1,7 +1,8 @@
-// Kernel instantiations for the 2-D correlated normal (test/runtests.jl:60) log-density, part 1 of 4: ragged row sizes and KMC_F32 rows, one GPU.
+// Kernel instantiations for the 2-D correlated normal (test/runtests.jl:60) log-density, PART 1 (kmc_tables.hpp):
+// ragged row sizes and KMC_F32 rows, one GPU.
 #define KMC_TABLES_IMPL
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void part_var_mvnormal2(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen) { density_part<MvNormal2, 1>(L, K, iter, ragged, f32, vec, gen); }
+KMC_INSTANTIATE_PART(MvNormal2, 1);
 }  // namespace kmc

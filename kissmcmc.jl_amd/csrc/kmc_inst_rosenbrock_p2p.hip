@@ -1,7 +1,8 @@
-// Kernel instantiations for the chained Rosenbrock (test/runtests.jl:68 at N = 2) log-density, part 2 of 4: the peer-to-peer kernels (KMC_P2P).
+// Kernel instantiations for the chained Rosenbrock (test/runtests.jl:68 at N = 2) log-density, PART 2 (kmc_tables.hpp):
+// the peer-to-peer kernels (KMC_P2P).
 #define KMC_TABLES_IMPL
 #include "kmc_tables.hpp"
 
 namespace kmc {
-void part_p2p_rosenbrock(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen) { density_part<Rosenbrock, 2>(L, K, iter, ragged, false, vec, gen); }
+KMC_INSTANTIATE_PART(Rosenbrock, 2);
 }  // namespace kmc

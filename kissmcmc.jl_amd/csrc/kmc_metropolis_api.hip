@@ -18,30 +18,6 @@ using namespace kmc_host;
 // ------------------------------------------------------------------------------------------
 namespace {
 
-MetropolisFn metropolis_fn(int density, int ndim)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return metropolis_gaussian_iso(ndim);
-    case KMC_EXPONENTIAL: return metropolis_exponential(ndim);
-    case KMC_ROSENBROCK: return metropolis_rosenbrock(ndim);
-    case KMC_LOGNORMAL: return metropolis_lognormal(ndim);
-    case KMC_MVNORMAL2: return metropolis_mvnormal2(ndim);
-    default: return nullptr;
-    }
-}
-
-MetropolisTabledFn metropolis_tabled_fn(int density, int ndim)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return metropolis_tabled_gaussian_iso(ndim);
-    case KMC_EXPONENTIAL: return metropolis_tabled_exponential(ndim);
-    case KMC_ROSENBROCK: return metropolis_tabled_rosenbrock(ndim);
-    case KMC_LOGNORMAL: return metropolis_tabled_lognormal(ndim);
-    case KMC_MVNORMAL2: return metropolis_tabled_mvnormal2(ndim);
-    default: return nullptr;
-    }
-}
-
 int metropolis_nd(int64_t ndim) { return ndim <= 1 ? 1 : ndim <= 2 ? 2 : ndim <= 4 ? 4 : ndim <= 8 ? 8 : ndim <= 16 ? 16 : ndim <= 32 ? 32 : 0; }
 
 // runtime-compiled density: the Metropolis kernel (and the initial log-pdf kernel) for one register geometry
@@ -201,8 +177,8 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
             KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep, &b.mod));
             HIP_TRY(hipModuleGetFunction(&ulp, b.mod, "kmc_user_logpdf"));
         } else {
-            HalfStepFn v, g;
-            if (!lookup(c->density, 0, 0, 1, false, false, false, &v, &g, &lp)) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+            lp = logpdf_fn(c->density);
+            if (!lp) return fail(KMC_ERR_BAD_ARG, "unknown density id");
         }
     }
     const unsigned grid = (unsigned)((nc + 255) / 256);
@@ -319,8 +295,7 @@ KMC_EXPORT kmc_status kmc_metropolis_validate(const kmc_metropolis_config* c)
         if (!c->user_density) return fail(KMC_ERR_BAD_ARG, "KMC_USER_DENSITY needs kmc_metropolis_config.user_density");
         return KMC_OK;
     }
-    if (c->density == KMC_ROSENBROCK && c->ndim < 2) return fail(KMC_ERR_BAD_ARG, "rosenbrock needs ndim >= 2");
-    if (c->density == KMC_MVNORMAL2 && c->ndim != 2) return fail(KMC_ERR_BAD_ARG, "mvnormal2 needs ndim == 2");
+    KMC_TRY(check_ndim(c->density, c->ndim));
     kmc_config e{};
     e.density = c->density;
     for (int i = 0; i < 8; ++i) e.params[i] = c->params[i];
@@ -429,7 +404,8 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
         HIP_TRY(hipModuleGetFunction(&ulp, b.mod, "kmc_user_logpdf"));
         if (tabled) HIP_TRY(hipModuleGetFunction(&utfn, b.mod, "kmc_user_metropolis_tabled"));
     } else {
-        fn = metropolis_fn(c->density, (int)std::min<int64_t>(nd, 1 << 20));    // the geometry follows ndim (registers <= 32)
+        fn = with_density(c->density, MetropolisFn(nullptr),    // the geometry follows ndim (registers <= 32)
+                          [&](auto d) { return metropolis_lookup<decltype(d)>((int)std::min<int64_t>(nd, 1 << 20)); });
         if (!fn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
     }
     const unsigned grid = (unsigned)((nc + 255) / 256);
@@ -437,7 +413,7 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     int64_t table_steps = 0;
     if (tabled) {
         if (c->density != KMC_USER_DENSITY) {
-            tfn = metropolis_tabled_fn(c->density, (int)nd);
+            tfn = with_density(c->density, MetropolisTabledFn(nullptr), [&](auto d) { return metropolis_tabled_lookup<decltype(d)>((int)nd); });
             if (!tfn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tfn), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kMetroTileBytes));
         }
@@ -452,10 +428,7 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     const LogpdfArgs la{b.pos, b.logp, nc, (int32_t)nd, (int32_t)nd, dp, b.blob};      // (and blob0, :70-72)
     if (ulp) HIP_TRY(launch_module(ulp, grid, 256u, st, la));
     else {
-        HalfStepFn v, g;
-        LogpdfFn lp = nullptr;
-        lookup(c->density, 0, 0, 1, false, false, false, &v, &g, &lp);
-        hipLaunchKernelGGL(lp, dim3(grid), dim3(256), 0, st, la);
+        hipLaunchKernelGGL(logpdf_fn(c->density), dim3(grid), dim3(256), 0, st, la);
         HIP_TRY(hipGetLastError());
     }
 

@@ -1,5 +1,5 @@
-// kmc_plan.hip -- which kernel, in which geometry, for a configuration: the per-density kernel tables (instantiated in
-// kmc_inst_<density>*.hip), the launch plan per ndim (lanes per row, chunks per lane, walkers per wave), the parameter digest the
+// kmc_plan.hip -- which kernel, in which geometry, for a configuration: the dispatch of a menu density id to its kernel tables
+// (kmc_tables.hpp), the launch plan per ndim (lanes per row, chunks per lane, walkers per wave), the parameter digest the
 // kernels read, and the island / dealt permutations.  The sampler's lifecycle that uses them is kmc_sampler.hip.
 #include <algorithm>
 #include <cmath>
@@ -11,102 +11,29 @@
 using namespace kmc;
 using namespace kmc_host;
 
-bool kmc_host::lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen, LogpdfFn* lp)
+namespace kmc_host {
+// Which part of a density's kernels serves a configuration (kmc_tables.hpp); there are no P2P kernels for KMC_F32 rows.
+bool lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen)
 {
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: table_gaussian_iso(L, K, iter, p2p, ragged, f32, vec, gen, lp); return true;
-    case KMC_EXPONENTIAL: table_exponential(L, K, iter, p2p, ragged, f32, vec, gen, lp); return true;
-    case KMC_ROSENBROCK: table_rosenbrock(L, K, iter, p2p, ragged, f32, vec, gen, lp); return true;
-    case KMC_LOGNORMAL: table_lognormal(L, K, iter, p2p, ragged, f32, vec, gen, lp); return true;
-    case KMC_MVNORMAL2: table_mvnormal2(L, K, iter, p2p, ragged, f32, vec, gen, lp); return true;
-    default: return false;
-    }
+    return with_density(density, false, [&](auto d) {
+        using D = decltype(d);
+        if (p2p && f32) { *vec = nullptr; *gen = nullptr; }
+        else if (p2p) density_part<D, 2>(L, K, iter, ragged, false, vec, gen);
+        else if (ragged || f32) density_part<D, 1>(L, K, iter, ragged, f32, vec, gen);
+        else density_part<D, 0>(L, K, iter, false, false, vec, gen);
+        return true;
+    });
 }
 
-namespace kmc_host {
-// KMC_MOVE_DE: the differential-evolution kernels (kmc_inst_<density>_de.hip)
+// KMC_MOVE_DE: the differential-evolution kernels (PART 3)
 bool lookup_de(int density, int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
 {
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: table_de_gaussian_iso(L, K, iter, ragged, vec, gen); return true;
-    case KMC_EXPONENTIAL: table_de_exponential(L, K, iter, ragged, vec, gen); return true;
-    case KMC_ROSENBROCK: table_de_rosenbrock(L, K, iter, ragged, vec, gen); return true;
-    case KMC_LOGNORMAL: table_de_lognormal(L, K, iter, ragged, vec, gen); return true;
-    case KMC_MVNORMAL2: table_de_mvnormal2(L, K, iter, ragged, vec, gen); return true;
-    default: return false;
-    }
+    return with_density(density, false, [&](auto d) { density_part<decltype(d), 3>(L, K, iter, ragged, false, vec, gen); return true; });
 }
 
-IslandFn island_fn(int density, int S, int K, bool ragged)
+LogpdfFn logpdf_fn(int density)
 {
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return island_gaussian_iso(S, K, ragged);
-    case KMC_EXPONENTIAL: return island_exponential(S, K, ragged);
-    case KMC_ROSENBROCK: return island_rosenbrock(S, K, ragged);
-    case KMC_LOGNORMAL: return island_lognormal(S, K, ragged);
-    case KMC_MVNORMAL2: return island_mvnormal2(S, K, ragged);
-    default: return nullptr;
-    }
-}
-
-ResidentFn resident_fn(int density, int tpb, int K, bool ragged)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return resident_gaussian_iso(tpb, K, ragged);
-    case KMC_EXPONENTIAL: return resident_exponential(tpb, K, ragged);
-    case KMC_ROSENBROCK: return resident_rosenbrock(tpb, K, ragged);
-    case KMC_LOGNORMAL: return resident_lognormal(tpb, K, ragged);
-    case KMC_MVNORMAL2: return resident_mvnormal2(tpb, K, ragged);
-    default: return nullptr;
-    }
-}
-
-ResidentFn resident_lane_fn(int density, int ndim, bool f32)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return resident_lane_gaussian_iso(ndim, f32);
-    case KMC_EXPONENTIAL: return resident_lane_exponential(ndim, f32);
-    case KMC_ROSENBROCK: return resident_lane_rosenbrock(ndim, f32);
-    case KMC_LOGNORMAL: return resident_lane_lognormal(ndim, f32);
-    case KMC_MVNORMAL2: return resident_lane_mvnormal2(ndim, f32);
-    default: return nullptr;
-    }
-}
-
-ResidentFn resident_lane2_fn(int density, int ndim)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return resident_lane2_gaussian_iso(ndim);
-    case KMC_EXPONENTIAL: return resident_lane2_exponential(ndim);
-    case KMC_ROSENBROCK: return resident_lane2_rosenbrock(ndim);
-    case KMC_LOGNORMAL: return resident_lane2_lognormal(ndim);
-    case KMC_MVNORMAL2: return resident_lane2_mvnormal2(ndim);
-    default: return nullptr;
-    }
-}
-
-GenerationFn generation_fn(int density, int ndim)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return generation_lane_gaussian_iso(ndim);
-    case KMC_EXPONENTIAL: return generation_lane_exponential(ndim);
-    case KMC_ROSENBROCK: return generation_lane_rosenbrock(ndim);
-    case KMC_LOGNORMAL: return generation_lane_lognormal(ndim);
-    case KMC_MVNORMAL2: return generation_lane_mvnormal2(ndim);
-    default: return nullptr;
-    }
-}
-
-GenerationFn generation_group_fn(int density, int L, int K)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return generation_group_gaussian_iso(L, K);
-    case KMC_EXPONENTIAL: return generation_group_exponential(L, K);
-    case KMC_ROSENBROCK: return generation_group_rosenbrock(L, K);
-    case KMC_LOGNORMAL: return generation_group_lognormal(L, K);
-    case KMC_MVNORMAL2: return generation_group_mvnormal2(L, K);
-    default: return nullptr;
-    }
+    return with_density(density, LogpdfFn(nullptr), [](auto d) { return logpdf_lookup<decltype(d)>(); });
 }
 
 // resident mode with one walker per thread (short rows) or two lanes per walker: KMC_DEBUG=resident=pair decides for tests
@@ -117,18 +44,6 @@ bool resident_lane_wanted(int64_t ndim)
     return ndim <= 8;
 }
 int lane_nd(int64_t ndim) { return (int)ndim; }          // (the lane kernels are instantiated for the exact row length)
-
-InitBallFn init_ball_fn(int density)
-{
-    switch (density) {
-    case KMC_GAUSSIAN_ISO: return init_ball_gaussian_iso();
-    case KMC_EXPONENTIAL: return init_ball_exponential();
-    case KMC_ROSENBROCK: return init_ball_rosenbrock();
-    case KMC_LOGNORMAL: return init_ball_lognormal();
-    case KMC_MVNORMAL2: return init_ball_mvnormal2();
-    default: return nullptr;
-    }
-}
 
 // Philox4x32-10 on the host (only for the island deal; Salmon et al., SC'11).
 void philox_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
@@ -143,21 +58,28 @@ void philox_host(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// The deal of epoch e: slot s holds walker (A*s + C) mod N.  Epoch 0 is the identity; later epochs
-// take A (made coprime to N by stepping upwards) and C from Philox(ctr = {e, "ISLA", 0}, key = seed).
-void island_perm(uint64_t seed, int64_t epoch, int64_t N, int64_t* A, int64_t* C)
+// The affine permutation s -> (A*s + C) mod n of one Philox draw (ctr, key = seed): C uniform, A made coprime to n by
+// stepping upwards (wrapping to 1) from a draw in [1, n).
+static void affine_perm(const uint32_t ctr[4], uint64_t seed, int64_t n, int64_t* A, int64_t* C)
 {
-    if (epoch == 0 || N <= 2) { *A = 1; *C = 0; return; }
-    const uint32_t ctr[4] = {(uint32_t)epoch, (uint32_t)((uint64_t)epoch >> 32), 0x49534c41u, 0u};
     const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
     uint32_t w[4];
     philox_host(ctr, key, w);
     auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
-    int64_t a = (int64_t)((((uint64_t)w[0] << 32) | w[1]) % (uint64_t)N);
+    int64_t a = (int64_t)((((uint64_t)w[0] << 32) | w[1]) % (uint64_t)n);
     if (a < 1) a = 1;
-    while (gcd(a, N) != 1) a = (a % N + 1 >= N) ? 1 : a + 1;
+    while (gcd(a, n) != 1) a = (a + 1 >= n) ? 1 : a + 1;
     *A = a;
-    *C = (int64_t)((((uint64_t)w[2] << 32) | w[3]) % (uint64_t)N);
+    *C = (int64_t)((((uint64_t)w[2] << 32) | w[3]) % (uint64_t)n);
+}
+
+// The deal of epoch e: slot s holds walker (A*s + C) mod N.  Epoch 0 is the identity; later epochs
+// take (A, C) from Philox(ctr = {e, "ISLA", 0}, key = seed).
+void island_perm(uint64_t seed, int64_t epoch, int64_t N, int64_t* A, int64_t* C)
+{
+    if (epoch == 0 || N <= 2) { *A = 1; *C = 0; return; }
+    const uint32_t ctr[4] = {(uint32_t)epoch, (uint32_t)((uint64_t)epoch >> 32), 0x49534c41u, 0u};
+    affine_perm(ctr, seed, N, A, C);
 }
 
 // Dealt sub-ensembles (kmc_config.deal_count): the Philox key of sub-ensemble r, and the affine shuffle (A, C) its S
@@ -167,15 +89,7 @@ uint64_t deal_seed(uint64_t seed, int32_t rank) { return seed + (uint64_t)(rank 
 void deal_perm(uint64_t seed, int64_t epoch, int32_t rank, int64_t S, int64_t* A, int64_t* C)
 {
     const uint32_t ctr[4] = {(uint32_t)epoch, (uint32_t)((uint64_t)epoch >> 32), 0x4445414cu, (uint32_t)rank};
-    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    uint32_t w[4];
-    philox_host(ctr, key, w);
-    auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
-    int64_t a = (int64_t)((((uint64_t)w[0] << 32) | w[1]) % (uint64_t)S);
-    if (a < 1) a = 1;
-    while (gcd(a, S) != 1) a = (a + 1 >= S) ? 1 : a + 1;
-    *A = a;
-    *C = (int64_t)((((uint64_t)w[2] << 32) | w[3]) % (uint64_t)S);
+    affine_perm(ctr, seed, S, A, C);
 }
 
 // Default geometry per ndim; KMC_PLAN="L,K,ITER" (or "generic") overrides for tuning.
@@ -183,7 +97,6 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
 {
     Plan p;
     HalfStepFn vec = nullptr, gen = nullptr;
-    LogpdfFn lp = nullptr;
     int L = 0, K = 0, iter = 1;
     const char* env = std::getenv("KMC_PLAN");
     bool force_generic = false;
@@ -248,13 +161,21 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
         return p;
     }
     if (de) lookup_de(c.density, L, K, iter, ragged, &vec, &gen);
-    else lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen, &lp);
+    else lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen);
     if (!force_generic && L > 0 && 2 * L * K >= c.ndim && vec != nullptr) {
         p.fn = vec; p.vec = true; p.L = L; p.K = K; p.ITER = iter;
     } else {
         p.fn = gen; p.vec = false; p.L = 1; p.K = 1; p.ITER = 1;
     }
     return p;
+}
+
+// the menu densities' row lengths (kmc_validate, kmc_metropolis_validate)
+kmc_status check_ndim(int density, int64_t ndim)
+{
+    if (density == KMC_ROSENBROCK && ndim < 2) return fail(KMC_ERR_BAD_ARG, "rosenbrock needs ndim >= 2");
+    if (density == KMC_MVNORMAL2 && ndim != 2) return fail(KMC_ERR_BAD_ARG, "mvnormal2 needs ndim == 2");
+    return KMC_OK;
 }
 
 }  // namespace kmc_host

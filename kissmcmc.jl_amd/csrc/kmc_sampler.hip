@@ -85,8 +85,7 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
             return fail(KMC_ERR_UNSUPPORTED, "KMC_F32 rows: densities evaluated on the device only (built-in or runtime-compiled)");
     }
     if (c->host_accepted && c->density != KMC_HOST_DENSITY) return fail(KMC_ERR_BAD_ARG, "kmc_config.host_accepted needs KMC_HOST_DENSITY");
-    if (c->density == KMC_ROSENBROCK && c->ndim < 2) return fail(KMC_ERR_BAD_ARG, "rosenbrock needs ndim >= 2");
-    if (c->density == KMC_MVNORMAL2 && c->ndim != 2) return fail(KMC_ERR_BAD_ARG, "mvnormal2 needs ndim == 2");
+    KMC_TRY(check_ndim(c->density, c->ndim));
     const int P = c->shard_count <= 0 ? 1 : c->shard_count;
     if (c->shard_rank < 0 || c->shard_rank >= P) return fail(KMC_ERR_BAD_ARG, "shard_rank out of range");
     if ((c->nwalkers / 2) % P != 0) return fail(KMC_ERR_BAD_ARG, "nwalkers/2 must be divisible by shard_count");
@@ -432,8 +431,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         st = load_data(s->data_ud, cfg->ndim, &s->dk);
         if (st != KMC_OK) { kmc_sampler_destroy(s); return st; }
     } else {
-        HalfStepFn v, g;
-        lookup(cfg->density, 0, 0, 1, false, false, false, &v, &g, &s->logpdf_fn);
+        s->logpdf_fn = logpdf_fn(cfg->density);
     }
     // vec: a wave owns W = (64/L)*ITER walkers; generic: one walker per lane
     const int64_t per_wave = s->plan.vec ? (int64_t)(64 / s->plan.L) * s->plan.ITER : 64;
@@ -452,7 +450,8 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         if (s->island_lds < 4096) s->island_lds = 4096;          // the moment reduction reuses the buffer
         hipError_t ea = hipSuccess;
         if (!s->user) {
-            s->island_kernel = island_fn(cfg->density, (int)s->island_size, K, s->island_ragged);
+            s->island_kernel = with_density(cfg->density, IslandFn(nullptr),
+                                            [&](auto d) { return island_lookup<decltype(d)>((int)s->island_size, K, s->island_ragged); });
             if (!s->island_kernel) { kmc_sampler_destroy(s); return fail(KMC_ERR_UNSUPPORTED, "no island kernel for this density / ndim"); }
             ea = hipFuncSetAttribute(reinterpret_cast<const void*>(s->island_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->island_lds);
@@ -466,10 +465,13 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         while (2 * K < chunks) K *= 2;
         int rtpb = cfg->nwalkers <= 256 ? 256 : (cfg->nwalkers <= 512 ? 512 : 1024);
         size_t need = ((size_t)cfg->nwalkers * (size_t)(4 * (K + 1)) + (size_t)cfg->nwalkers) * sizeof(double);
-        ResidentFn rf = (!s->f32 && need <= 156 * 1024 && cfg->nwalkers <= 1024) ? resident_fn(cfg->density, rtpb, K, 4 * K != cfg->ndim) : nullptr;   // (float rows: the lane kernels only)
+        ResidentFn rf = (!s->f32 && need <= 156 * 1024 && cfg->nwalkers <= 1024)         // (float rows: the lane kernels only)
+                         ? with_density(cfg->density, ResidentFn(nullptr), [&](auto d) { return resident_lookup<decltype(d)>(rtpb, K, 4 * K != cfg->ndim); })
+                         : nullptr;
         if (cfg->nwalkers > 1024) {                       // 1026 .. 2048 walkers: two walkers per thread, short double rows, as LDS allows
             const size_t need2 = ((size_t)cfg->nwalkers * (size_t)((lane_nd(cfg->ndim) | 1) + 1)) * sizeof(double);
-            ResidentFn l2 = (!s->f32 && resident_lane_wanted(cfg->ndim) && need2 <= 156 * 1024) ? resident_lane2_fn(cfg->density, (int)cfg->ndim) : nullptr;
+            ResidentFn l2 = (!s->f32 && resident_lane_wanted(cfg->ndim) && need2 <= 156 * 1024) ? with_density(cfg->density, ResidentFn(nullptr), [&](auto d) { return resident_lane2_lookup<decltype(d)>((int)cfg->ndim); })
+                                                                                                      : nullptr;
             if (l2) {
                 rf = l2;
                 rtpb = (int)((cfg->nwalkers / 2 + 63) / 64 * 64);
@@ -479,7 +481,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
             }
         } else
         if (resident_lane_wanted(cfg->ndim)) {            // short rows: one walker per thread (measured faster up to ndim 8)
-            ResidentFn lf = resident_lane_fn(cfg->density, (int)cfg->ndim, s->f32);
+            ResidentFn lf = with_density(cfg->density, ResidentFn(nullptr), [&](auto d) { return resident_lane_lookup<decltype(d)>((int)cfg->ndim, s->f32); });
             if (lf) {
                 rf = lf;
                 rtpb = (int)((cfg->nwalkers + 63) / 64 * 64);
@@ -505,8 +507,11 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     if (const int kind = (!s->islands && !s->resident) ? generation_wanted(s) : 0) {          // one launch per generation (see generation_wanted)
         if (s->user) s->fused = s->uk.generation != nullptr;
         else {
-            s->generation_kernel = kind == 1 ? generation_fn(cfg->density, (int)cfg->ndim) : kind == 3 ? generation_group_fn(cfg->density, 4, 1)
-                                                                                             : generation_group_fn(cfg->density, s->plan.L, s->plan.K);
+            s->generation_kernel = with_density(cfg->density, GenerationFn(nullptr), [&](auto d) {
+                using D = decltype(d);
+                return kind == 1 ? generation_lane_lookup<D>((int)cfg->ndim) : kind == 3 ? generation_group_lookup<D>(4, 1)
+                                                                             : generation_group_lookup<D>(s->plan.L, s->plan.K);
+            });
             s->fused = s->generation_kernel != nullptr;
         }
         if (s->fused) {

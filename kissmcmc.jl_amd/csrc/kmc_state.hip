@@ -112,7 +112,7 @@ KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0
     double* d_ball = s->d_pos;                  // KMC_F32: the ball is drawn in double, then rounded into the float rows
     if (s->f32 && e == hipSuccess) e = hipMalloc((void**)&d_ball, nelem * sizeof(double));
     if (e == hipSuccess) e = fill_sync(d_ball, 0, nelem * sizeof(double), s->stream);
-    InitBallFn fn = s->user ? nullptr : init_ball_fn(s->cfg.density);
+    InitBallFn fn = s->user ? nullptr : with_density(s->cfg.density, InitBallFn(nullptr), [](auto d) { return init_ball_lookup<decltype(d)>(); });
     const int pieces = s->p2p ? 2 : 1;
     for (int piece = 0; piece < pieces && e == hipSuccess; ++piece) {
         InitBallArgs a{};
@@ -630,9 +630,8 @@ KMC_EXPORT kmc_status kmc_logpdf_eval(const kmc_config* cfg, const double* pos_d
         HIP_TRY(e);
         return KMC_OK;
     }
-    HalfStepFn v, g;
-    LogpdfFn lp = nullptr;
-    if (!lookup(cfg->density, 0, 0, 1, false, false, false, &v, &g, &lp)) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+    const LogpdfFn lp = logpdf_fn(cfg->density);
+    if (!lp) return fail(KMC_ERR_BAD_ARG, "unknown density id");
     hipLaunchKernelGGL(lp, dim3(grid), dim3(256), 0, (hipStream_t)hip_stream, la);
     HIP_TRY(hipGetLastError());
     return KMC_OK;

@@ -1,6 +1,14 @@
-// kmc_tables.hpp -- kernel instantiation tables.  Each density's table is compiled in its own
-// translation unit (kmc_inst_<density>.hip) so the build can run them in parallel; the host driver only
-// sees the per-density entry points declared at the bottom.
+// kmc_tables.hpp -- kernel instantiation tables.  The lookup templates below map a launch geometry to a kernel of density D.
+// Every translation unit sees their declarations.  Only the kmc_inst_<density>*.hip files define KMC_TABLES_IMPL: they see the
+// definitions and instantiate them explicitly for their density (KMC_INSTANTIATE_*).  So the host driver names them without
+// instantiating a kernel, and the build compiles a density's kernels in parallel, five translation units per density:
+//   kmc_inst_<density>.hip       density_part PART 0: double rows of exact size, one GPU (incl. the tuning geometries); the
+//                                log-pdf and initial-ball kernels
+//   kmc_inst_<density>_var.hip   density_part PART 1: ragged sizes and KMC_F32 rows, one GPU
+//   kmc_inst_<density>_p2p.hip   density_part PART 2: the peer-to-peer kernels (KMC_P2P)
+//   kmc_inst_<density>_de.hip    density_part PART 3: the differential-evolution move (KMC_MOVE_DE: exact and ragged double rows, one GPU)
+//   kmc_inst_<density>_lds.hip   the LDS-resident (islands, resident mode), one-launch-per-generation and many-chain Metropolis kernels
+// Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_de).
 #pragma once
 #include <type_traits>
 #include "kmc_islands.hpp"
@@ -18,6 +26,21 @@ using GenerationFn = void (*)(KMC_GEN_FRONT_TYPES, const GenerationArgs);
 using InitBallFn = void (*)(const InitBallArgs);
 using MetropolisFn = void (*)(const MetropolisArgs);
 using MetropolisTabledFn = void (*)(const MetropolisArgs, const double*, int);
+
+// (the part's vector kernel for this geometry or nullptr, its generic kernel)
+template <class D, int PART> void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen);
+template <class D> LogpdfFn logpdf_lookup();
+template <class D> InitBallFn init_ball_lookup();
+template <class D> IslandFn island_lookup(int S, int K, bool ragged);
+template <class D> ResidentFn resident_lookup(int tpb, int K, bool ragged);
+template <class D> ResidentFn resident_lane_lookup(int ndim, bool f32);
+template <class D> ResidentFn resident_lane2_lookup(int ndim);
+template <class D> GenerationFn generation_lane_lookup(int ndim);
+template <class D> GenerationFn generation_group_lookup(int L, int K);
+template <class D> MetropolisFn metropolis_lookup(int ndim);
+template <class D> MetropolisTabledFn metropolis_tabled_lookup(int ndim);
+HalfStepFn half_step_host();         // kmc_inst_host.hip
+HalfStepFn half_step_host_de();      // KMC_MOVE_DE
 
 #ifdef KMC_TABLES_IMPL
 template <class D, int L, int K, int ITER, bool P2P, bool RAGGED, class T, Move M>
@@ -44,11 +67,7 @@ HalfStepFn vec_iter(int iter)
     }
 }
 
-// A density's kernels are instantiated in FIVE translation units, so that the build's longest job is a fraction of a density
-// (kmc_inst_<density>{,_var,_p2p,_de,_lds}.hip): PART 0 = double rows, exact size, one GPU (incl. the tuning geometries);
-// PART 1 = ragged sizes and KMC_F32 rows, one GPU; PART 2 = the peer-to-peer kernels; PART 3 = the differential-evolution
-// move (KMC_MOVE_DE: exact and ragged double rows, one GPU); (the LDS-resident and Metropolis kernels are the fifth).  Each
-// part only names -- and therefore only compiles -- its own instantiations.
+// PART 0 .. 3 of density_part (see the top of this file); each part only names -- and therefore only compiles -- its own instantiations
 template <class D, int L, int K, int PART>
 HalfStepFn vec_pick(int iter, bool ragged, bool f32)
 {
@@ -81,7 +100,6 @@ HalfStepFn vec_lookup(int L, int K, int iter, bool ragged, bool f32)
     }
 }
 
-// (the part's vector kernel for this geometry or nullptr, its generic kernel)
 template <class D, int PART>
 void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen)
 {
@@ -91,6 +109,11 @@ void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec
     else if constexpr (PART == 2) *gen = half_step_generic<D, true, double>;
     else *gen = half_step_de_generic<D>;
 }
+
+template <class D>
+LogpdfFn logpdf_lookup() { return logpdf_rows<D>; }
+template <class D>
+InitBallFn init_ball_lookup() { return init_ball<D>; }
 
 // island mode: one workgroup per S-walker island, rows of up to 4*K doubles
 template <class D, int S>
@@ -235,67 +258,20 @@ MetropolisTabledFn metropolis_tabled_lookup(int ndim)
     if (ndim <= 8) return metropolis_chains_tabled<D, 8>;
     return nullptr;
 }
+// the explicit instantiations of one translation unit of density D (see the top of this file)
+#define KMC_INSTANTIATE_PART(D, PART) template void density_part<D, PART>(int, int, int, bool, bool, HalfStepFn*, HalfStepFn*)
+#define KMC_INSTANTIATE_ROWS(D) \
+    template LogpdfFn logpdf_lookup<D>(); \
+    template InitBallFn init_ball_lookup<D>()
+#define KMC_INSTANTIATE_LDS(D) \
+    template IslandFn island_lookup<D>(int, int, bool); \
+    template ResidentFn resident_lookup<D>(int, int, bool); \
+    template ResidentFn resident_lane_lookup<D>(int, bool); \
+    template ResidentFn resident_lane2_lookup<D>(int); \
+    template GenerationFn generation_lane_lookup<D>(int); \
+    template GenerationFn generation_group_lookup<D>(int, int); \
+    template MetropolisFn metropolis_lookup<D>(int); \
+    template MetropolisTabledFn metropolis_tabled_lookup<D>(int)
 #endif  // KMC_TABLES_IMPL
-
-// entry points per density: table_<density> (kmc_inst_<density>.hip: PART 0, the log-pdf and initial-ball kernels, and the
-// dispatch to the other parts), part_var_ / part_p2p_<density> (kmc_inst_<density>_var.hip / _p2p.hip), table_de_<density> (PART 3,
-// kmc_inst_<density>_de.hip), and the LDS-resident + Metropolis tables below (kmc_inst_<density>_lds.hip)
-#define KMC_DECLARE_DENSITY_TABLE(name) \
-    void table_##name(int L, int K, int iter, bool p2p, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen, LogpdfFn* lp); \
-    void part_var_##name(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen);                      \
-    void part_p2p_##name(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen);                                 \
-    void table_de_##name(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
-KMC_DECLARE_DENSITY_TABLE(gaussian_iso);
-KMC_DECLARE_DENSITY_TABLE(exponential);
-KMC_DECLARE_DENSITY_TABLE(rosenbrock);
-KMC_DECLARE_DENSITY_TABLE(lognormal);
-KMC_DECLARE_DENSITY_TABLE(mvnormal2);
-HalfStepFn half_step_host();
-HalfStepFn half_step_host_de();      // KMC_MOVE_DE
-IslandFn island_gaussian_iso(int S, int K, bool ragged);
-ResidentFn resident_gaussian_iso(int tpb, int K, bool ragged);
-ResidentFn resident_lane_gaussian_iso(int ndim, bool f32);
-ResidentFn resident_lane2_gaussian_iso(int ndim);
-GenerationFn generation_lane_gaussian_iso(int ndim);
-GenerationFn generation_group_gaussian_iso(int L, int K);
-InitBallFn init_ball_gaussian_iso();
-MetropolisFn metropolis_gaussian_iso(int ndim);
-MetropolisTabledFn metropolis_tabled_gaussian_iso(int ndim);
-IslandFn island_exponential(int S, int K, bool ragged);
-ResidentFn resident_exponential(int tpb, int K, bool ragged);
-ResidentFn resident_lane_exponential(int ndim, bool f32);
-ResidentFn resident_lane2_exponential(int ndim);
-GenerationFn generation_lane_exponential(int ndim);
-GenerationFn generation_group_exponential(int L, int K);
-InitBallFn init_ball_exponential();
-MetropolisFn metropolis_exponential(int ndim);
-MetropolisTabledFn metropolis_tabled_exponential(int ndim);
-IslandFn island_rosenbrock(int S, int K, bool ragged);
-ResidentFn resident_rosenbrock(int tpb, int K, bool ragged);
-ResidentFn resident_lane_rosenbrock(int ndim, bool f32);
-ResidentFn resident_lane2_rosenbrock(int ndim);
-GenerationFn generation_lane_rosenbrock(int ndim);
-GenerationFn generation_group_rosenbrock(int L, int K);
-InitBallFn init_ball_rosenbrock();
-MetropolisFn metropolis_rosenbrock(int ndim);
-MetropolisTabledFn metropolis_tabled_rosenbrock(int ndim);
-IslandFn island_lognormal(int S, int K, bool ragged);
-ResidentFn resident_lognormal(int tpb, int K, bool ragged);
-ResidentFn resident_lane_lognormal(int ndim, bool f32);
-ResidentFn resident_lane2_lognormal(int ndim);
-GenerationFn generation_lane_lognormal(int ndim);
-GenerationFn generation_group_lognormal(int L, int K);
-InitBallFn init_ball_lognormal();
-MetropolisFn metropolis_lognormal(int ndim);
-MetropolisTabledFn metropolis_tabled_lognormal(int ndim);
-IslandFn island_mvnormal2(int S, int K, bool ragged);
-ResidentFn resident_mvnormal2(int tpb, int K, bool ragged);
-ResidentFn resident_lane_mvnormal2(int ndim, bool f32);
-ResidentFn resident_lane2_mvnormal2(int ndim);
-GenerationFn generation_lane_mvnormal2(int ndim);
-GenerationFn generation_group_mvnormal2(int L, int K);
-InitBallFn init_ball_mvnormal2();
-MetropolisFn metropolis_mvnormal2(int ndim);
-MetropolisTabledFn metropolis_tabled_mvnormal2(int ndim);
 
 }  // namespace kmc
