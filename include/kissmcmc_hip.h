@@ -158,11 +158,24 @@ enum {
  *                     (N-1) log z term).  Its own Philox stream, key {seed_lo ^ 0x44454D56 ("DEMV"), seed_hi}, counter
  *                     {step_lo, step_hi, walker, block} -- DESIGN.md section 2.  Two launches per generation, one GPU, double
  *                     rows: KMC_ERR_UNSUPPORTED with KMC_ISLANDS, KMC_P2P, shard_count > 1, deal_count > 0, KMC_F32,
- *                     KMC_STORE_BLOBS, a body density with blobs, and in kmc_sampler_rccl_init. */
+ *                     KMC_STORE_BLOBS, a body density with blobs, and in kmc_sampler_rccl_init.
+ *   KMC_MOVE_SNOOKER  the DE snooker update (opt-in; ter Braak & Vrugt 2008, emcee's DESnookerMove): three distinct partners z, z1,
+ *                     z2, uniform over the complementary half (needs nwalkers >= 6), d = x - z, s = gamma T(d . (z1 - z2)) / T(d . d)
+ *                     and y = x + d s; accepted when (ndim - 1) log|1 + s| + p1 - p0 >= log u.  T is the fixed pairwise summation
+ *                     order of DESIGN.md section 2; the stream is the DE key family, blocks 2 and 3.  ndim >= 2 (KMC_ERR_BAD_ARG
+ *                     otherwise); refused like KMC_MOVE_DE.
+ *   KMC_MOVE_MIX      a weighted mixture of 2 to 4 DE / snooker members (mix_*): every HALF-STEP uses one member for all its
+ *                     walkers, the first whose cumulative normalised weight exceeds u_mix = (w0 + 1/2) 2^-32 of Philox key
+ *                     {seed_lo ^ 0x4D495856 ("MIXV"), seed_hi}, counter {step_lo, step_hi, 0, 0}: a pure function of (seed, step).
+ *                     Weights are normalised in double, in member order; the last member catches rounding.  A stretch member is
+ *                     KMC_ERR_UNSUPPORTED; the members' restrictions apply. */
 enum {
     KMC_MOVE_STRETCH = 0,
-    KMC_MOVE_DE      = 1
+    KMC_MOVE_DE      = 1,
+    KMC_MOVE_SNOOKER = 3,   /* (2 is not a move: KMC_ERR_BAD_ARG) */
+    KMC_MOVE_MIX     = 4
 };
+#define KMC_MIX_MAX 4
 
 #define KMC_P2P_HANDLE_BYTES 128
 #define KMC_RCCL_ID_BYTES 128
@@ -190,7 +203,15 @@ typedef struct kmc_config {
     kmc_host_accepted_fn host_accepted; /* KMC_HOST_DENSITY: per-half-step accept outcomes, or NULL */
     int32_t  deal_rank;     /* DEALT SUB-ENSEMBLES (opt-in, not the reference's partner rule; see kmc_sampler_deal_pack): this sampler is */
     int32_t  deal_count;    /* sub-ensemble deal_rank of deal_count; 0 = off.  nwalkers is then THIS sub-ensemble's size */
-    int32_t  move;          /* KMC_MOVE_STRETCH (0, the reference's move) or KMC_MOVE_DE */
+    /* (the snooker and mixture fields stand in front of `move`: the four fields from `move` on stay the struct's tail) */
+    double   snooker_gamma; /* KMC_MOVE_SNOOKER: gamma of the proposal; 0 -> 1.7 */
+    int32_t  mix_count;     /* KMC_MOVE_MIX: members, 2 .. KMC_MIX_MAX */
+    int32_t  mix_move[KMC_MIX_MAX];   /* ... each KMC_MOVE_DE or KMC_MOVE_SNOOKER */
+    int32_t  mix_pad_[3];
+    double   mix_weight[KMC_MIX_MAX]; /* ... its weight: finite, > 0; normalised by the library */
+    double   mix_gamma[KMC_MIX_MAX];  /* ... its gamma0 (DE; 0 -> 2.38 / sqrt(2 ndim)) or gamma (snooker; 0 -> 1.7) */
+    double   mix_sigma[KMC_MIX_MAX];  /* ... its sigma (DE members; 0 for snooker members) */
+    int32_t  move;          /* KMC_MOVE_STRETCH (0, the reference's move), KMC_MOVE_DE, KMC_MOVE_SNOOKER or KMC_MOVE_MIX */
     int32_t  move_pad_;
     double   de_gamma0;     /* KMC_MOVE_DE: gamma0 of the proposal; 0 -> 2.38 / sqrt(2 ndim) */
     double   de_sigma;      /* KMC_MOVE_DE: relative jitter of gamma, in [0, 1); 0 = none */

@@ -13,14 +13,14 @@ from .api import emcee, emcee_counts, make_theta0s, squash_walkers
 from .densities import (CDensity, DataDensity, DeviceLogPdf, Exponential, ExprDensity, GaussianIso, HostLogPdf, LogNormal, MvNormal2,
                         Rosenbrock)
 from .diagnostics import eff_samples, int_acorr
-from .moves import DEMove
+from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
 from .sampler import Sampler
 
 __all__ = [
     "emcee", "make_theta0s", "squash_walkers", "emcee_counts", "Sampler", "KmcError",
     "DeviceLogPdf", "GaussianIso", "Exponential", "Rosenbrock", "LogNormal", "MvNormal2", "ExprDensity", "CDensity", "DataDensity", "HostLogPdf",
-    "DEMove", "cdf_g_inv", "g_pdf", "metropolis", "metropolis_chains", "GaussianStep", "HostProposal", "int_acorr", "eff_samples",
+    "DEMove", "DESnookerMove", "cdf_g_inv", "g_pdf", "metropolis", "metropolis_chains", "GaussianStep", "HostProposal", "int_acorr", "eff_samples",
 ]
 
 

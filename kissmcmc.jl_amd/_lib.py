@@ -30,7 +30,8 @@ STREAM_CHAIN = 2048
 CHAIN_BY_WALKER = 4096
 STORE_BLOBS = 8192
 # kmc_config.move
-MOVE_STRETCH, MOVE_DE = 0, 1
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_MIX = 0, 1, 3, 4
+MIX_MAX = 4
 P2P_HANDLE_BYTES = 128
 RCCL_ID_BYTES = 128
 
@@ -77,6 +78,14 @@ class Config(C.Structure):
         ("host_accepted", C.c_void_p),
         ("deal_rank", C.c_int32),
         ("deal_count", C.c_int32),
+        ("snooker_gamma", C.c_double),
+        ("mix_count", C.c_int32),
+        # (the header's mix_move[4] ... mix_sigma[4], spelled out member by member like the Julia mirror)
+        ("mix_move0", C.c_int32), ("mix_move1", C.c_int32), ("mix_move2", C.c_int32), ("mix_move3", C.c_int32),
+        ("mix_pad0_", C.c_int32), ("mix_pad1_", C.c_int32), ("mix_pad2_", C.c_int32),
+        ("mix_weight0", C.c_double), ("mix_weight1", C.c_double), ("mix_weight2", C.c_double), ("mix_weight3", C.c_double),
+        ("mix_gamma0", C.c_double), ("mix_gamma1", C.c_double), ("mix_gamma2", C.c_double), ("mix_gamma3", C.c_double),
+        ("mix_sigma0", C.c_double), ("mix_sigma1", C.c_double), ("mix_sigma2", C.c_double), ("mix_sigma3", C.c_double),
         ("move", C.c_int32),
         ("move_pad_", C.c_int32),
         ("de_gamma0", C.c_double),

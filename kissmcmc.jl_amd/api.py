@@ -64,7 +64,9 @@ def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_sc
     as downloading a chain that does fit).
 
     ``move``: ``None`` is the reference's stretch move with ``a_scale``; ``DEMove(gamma0=None, sigma=1e-5)`` the opt-in
-    differential-evolution move (two partners, no ``a_scale``; README "Differential-evolution move").
+    differential-evolution move (two partners, no ``a_scale``; README "Differential-evolution move"); ``DESnookerMove(gamma=1.7)``
+    the DE snooker update, and a list of 2 to 4 ``(move, weight)`` pairs of the two a mixture, one member per half-step
+    (``[(DEMove(), 0.8), (DESnookerMove(), 0.2)]`` for multimodal targets; README "Snooker move and move mixtures").
 
     ``hasblob=True`` (``:150-151, :194-196``): ``pdf`` is a host callable returning ``(p, blob)``; the blobs
     stay on the host and follow the device's accept decisions.  ``blobs[w] = init_blobs(blob0s[w],

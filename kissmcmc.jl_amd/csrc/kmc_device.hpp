@@ -145,8 +145,10 @@ __device__ __forceinline__ bool accept_test(const Draw& d, double p1, double p0)
 }
 
 // The move a half-step kernel makes: the stretch move (the reference's, the default) or differential evolution
-// (KMC_MOVE_DE, opt-in; ter Braak 2006, emcee's DEMove): y = x + g (x_j - x_k), two distinct partners from the complementary half.
-enum class Move { Stretch, DE };
+// (KMC_MOVE_DE, opt-in; ter Braak 2006, emcee's DEMove): y = x + g (x_j - x_k), two distinct partners from the complementary half;
+// the DE snooker update (KMC_MOVE_SNOOKER; ter Braak & Vrugt 2008, emcee's DESnookerMove): three distinct partners z, z1, z2 and a step
+// along x - z; Mix (KMC_MOVE_MIX) names the kernels that pick DE or snooker per half-step and is never a move of the bodies themselves.
+enum class Move { Stretch, DE, Snooker, Mix };
 
 // Differential-evolution move: its own Philox stream, key {seed_lo ^ "DEMV", seed_hi},
 // counter {step_lo, step_hi, walker, block}.  Block 0: partners j, k (distinct, uniform over the complementary half) and the accept
@@ -190,6 +192,99 @@ __device__ __forceinline__ Draw de_draw(const DrawConsts& dc, uint64_t step, uin
 __device__ __forceinline__ bool de_accept_test(const Draw& d, double p1, double p0)
 {
     return (p1 - p0) >= d.lu;
+}
+
+// Snooker move: the DE key family and counter, blocks 2 and 3.  Block 2: the three partners, distinct and
+// uniform over the complementary half (z from h, z1 from the h - 1 others, z2 from the h - 2 others); block 3: the accept uniform.
+// The kernels reuse Draw: partner = z, z = gamma (DrawConsts::c0; nm1 = ndim - 1), lu = log u; t1 = (ndim - 1) log|1 + s| once the
+// proposal's s is known.
+__device__ __forceinline__ void snooker_partners(const U4& w, uint32_t nhalf, uint32_t* z, uint32_t* z1, uint32_t* z2)
+{
+    const uint32_t a = __umulhi(w.x, nhalf);
+    uint32_t b = __umulhi(w.y, nhalf - 1u);
+    b += (b >= a ? 1u : 0u);
+    const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+    uint32_t c = __umulhi(w.z, nhalf - 2u);
+    c += (c >= lo ? 1u : 0u);
+    c += (c >= hi ? 1u : 0u);
+    *z = a; *z1 = b; *z2 = c;
+}
+// s = gamma (q / n2), separately rounded.  n2 == 0 or anything non-finite rejects; so does |1 + s| == 0 (log = -inf).
+__device__ __forceinline__ double snooker_s(double gamma, double q, double n2) { return gamma * (q / n2); }
+// (ndim - 1) log|1 + s| into d.t1; false: the proposal is rejected whatever its density
+__device__ __forceinline__ bool snooker_hastings(Draw& d, double nm1, double s)
+{
+    const double a1 = fabs(1.0 + s);
+    const bool ok = isfinite(s) && isfinite(a1) && a1 > 0.0;
+    d.t1 = nm1 * log_pos_normal(ok ? a1 : 1.0);
+    return ok;
+}
+__device__ __forceinline__ Draw snooker_draw(const DrawConsts& dc, uint64_t step, uint32_t walker, uint32_t* z1, uint32_t* z2)
+{
+    const U4 w = de_bits(dc.seed_lo, dc.seed_hi, step, walker, 2u);
+    const U4 v = de_bits(dc.seed_lo, dc.seed_hi, step, walker, 3u);
+    Draw d;
+    snooker_partners(w, dc.nhalf, &d.partner, z1, z2);
+    d.z = dc.c0;
+    d.t1 = 0.0;
+    d.lu = log_pos_normal(de_accept_u(v));
+    return d;
+}
+
+// The reduction order T of the snooker move's two sums: the pairwise tree over the terms t_0 .. t_{ndim-1}
+// in index order, padded with +0.0 to a power of two, and + 0.0 at the root.  The root's + 0.0 makes the value independent of HOW
+// FAR the row is padded (a zero subtree only ever adds +0.0 to a finished node, which changes nothing but the sign of a zero sum),
+// so every geometry of the vector kernel and the one-walker-per-lane kernel give the same bits.
+// One walker per lane: pair nodes t_{2i} + t_{2i+1} go through a binary counter (node i merges upwards while the bits of i below
+// the level are set; i is wave-uniform, so the branches are scalar).  Template recursion keeps the stack in registers (kmc_data.hpp).
+constexpr int kTreeLevels = 24;          // pair nodes: rows of up to 2^25 elements
+struct TreeStack2 {                      // two sums at once
+    double a[kTreeLevels], b[kTreeLevels];
+    template <int LV>
+    __device__ __forceinline__ void push_at(double va, double vb, uint32_t i)
+    {
+        if constexpr (LV < kTreeLevels) {
+            if ((i >> LV) & 1u) push_at<LV + 1>(a[LV] + va, b[LV] + vb, i);
+            else { a[LV] = va; b[LV] = vb; }
+        }
+    }
+    __device__ __forceinline__ void push(double va, double vb, uint32_t i) { push_at<0>(va, vb, i); }
+    template <int LV>
+    __device__ __forceinline__ void finish_at(uint32_t n, double& ra, double& rb, bool& have) const
+    {
+        if ((n >> LV) & 1u) { ra = have ? a[LV] + ra : a[LV]; rb = have ? b[LV] + rb : b[LV]; have = true; }
+        if constexpr (LV + 1 < kTreeLevels) finish_at<LV + 1>(n, ra, rb, have);
+    }
+    // the tree over the n >= 1 nodes pushed: the nodes at the set bits of n, folded from the lowest level up
+    __device__ __forceinline__ void finish(uint32_t n, double* ra, double* rb) const
+    {
+        double x = 0.0, y = 0.0; bool have = false;
+        finish_at<0>(n, x, y, have);
+        *ra = x + 0.0; *rb = y + 0.0;
+    }
+};
+
+// Mixtures (KMC_MOVE_MIX): every half-step uses ONE member for all its walkers, chosen by u_mix = (w0 + 1/2) 2^-32 from Philox key
+// {seed_lo ^ "MIXV", seed_hi}, counter {step_lo, step_hi, 0, 0}: the first member whose cumulative weight exceeds u_mix.  The table
+// lives in device memory (kmc_launch.hip: make_args); cum[i] of the last member and beyond is 2.0, so the last member catches rounding.
+constexpr uint32_t kMixKey = 0x4D495856u;   // "MIXV"
+constexpr int kMoveIdDE = 1, kMoveIdSnooker = 3;   // KMC_MOVE_DE, KMC_MOVE_SNOOKER (include/kissmcmc_hip.h; checked in kmc_host.hpp)
+struct MixTable {
+    int32_t count;
+    int32_t move[4];       // kMoveIdDE or kMoveIdSnooker
+    int32_t pad_[3];
+    double  cum[4];        // cumulative normalised weights
+    double  c0[4], c1[4];  // the member's DrawConsts::c0, c1 (DE: gamma0, sigma; snooker: gamma, 0)
+};
+__device__ __forceinline__ int mix_member(const MixTable* t, uint32_t seed_lo, uint32_t seed_hi, uint64_t step)
+{
+    const U4 w = philox4x32_10((uint32_t)step, (uint32_t)(step >> 32), 0u, 0u, seed_lo ^ kMixKey, seed_hi);
+    const double u = ((double)w.x + 0.5) * 0x1.0p-32;
+    int i = 3;
+    if (t->cum[2] > u) i = 2;
+    if (t->cum[1] > u) i = 1;
+    if (t->cum[0] > u) i = 0;
+    return __builtin_amdgcn_readfirstlane(i);
 }
 
 // ------------------------------------------------------------------------------------------

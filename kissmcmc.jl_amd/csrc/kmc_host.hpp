@@ -90,7 +90,36 @@ R with_density(int density, R none, F&& f)
 bool lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
 // KMC_MOVE_DE: gamma0 as the kernels use it (kmc_config.de_gamma0, or 2.38 / sqrt(2 ndim) when that is 0)
 inline double de_gamma0_of(const kmc_config& c) { return c.de_gamma0 > 0.0 ? c.de_gamma0 : 2.38 / std::sqrt(2.0 * (double)c.ndim); }
-bool lookup_de(int density, int L, int K, int iter, bool ragged, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
+inline double de_gamma0_of(double gamma0, int64_t ndim) { return gamma0 > 0.0 ? gamma0 : 2.38 / std::sqrt(2.0 * (double)ndim); }
+// KMC_MOVE_SNOOKER: gamma as the kernels use it (0 -> 1.7)
+inline double snooker_gamma_of(double gamma) { return gamma > 0.0 ? gamma : 1.7; }
+// a move with its own stream and the two-launch kernels only (DE, snooker, their mixtures)
+inline bool own_stream_move(const kmc_config& c) { return c.move != KMC_MOVE_STRETCH; }
+inline const char* move_name(int move) { return move == KMC_MOVE_DE ? "KMC_MOVE_DE" : move == KMC_MOVE_SNOOKER ? "KMC_MOVE_SNOOKER" : move == KMC_MOVE_MIX ? "KMC_MOVE_MIX" : "KMC_MOVE_STRETCH"; }
+// KMC_MOVE_MIX: the table the mixture kernels read -- weights normalised in double, in member order (weights_out[i], optional), cumulated
+// in the same order; the last member's cumulative weight and every one beyond is 2.0 (it catches rounding)
+static_assert(kmc::kMoveIdDE == KMC_MOVE_DE && kmc::kMoveIdSnooker == KMC_MOVE_SNOOKER, "the mixture table carries kmc_config's move ids");
+inline kmc::MixTable mix_table_of(const kmc_config& c, double* weights_out = nullptr)
+{
+    kmc::MixTable t{};
+    t.count = c.mix_count;
+    double sum = 0.0, cum = 0.0;
+    for (int i = 0; i < c.mix_count; ++i) sum += c.mix_weight[i];
+    for (int i = 0; i < KMC_MIX_MAX; ++i) {
+        t.cum[i] = 2.0;
+        if (i >= c.mix_count) continue;
+        const double w = c.mix_weight[i] / sum;
+        cum += w;
+        if (weights_out) weights_out[i] = w;
+        if (i < c.mix_count - 1) t.cum[i] = cum;
+        t.move[i] = c.mix_move[i];
+        t.c0[i] = c.mix_move[i] == KMC_MOVE_DE ? de_gamma0_of(c.mix_gamma[i], c.ndim) : snooker_gamma_of(c.mix_gamma[i]);
+        t.c1[i] = c.mix_move[i] == KMC_MOVE_DE ? c.mix_sigma[i] : 0.0;
+    }
+    return t;
+}
+// the kernels of KMC_MOVE_DE (PART 3), KMC_MOVE_SNOOKER (4) and KMC_MOVE_MIX (5)
+bool lookup_move(int move, int density, int L, int K, int iter, bool ragged, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
 kmc::LogpdfFn logpdf_fn(int density);
 kmc_status check_ndim(int density, int64_t ndim);
 kmc_status digest_params(const kmc_config& c, kmc::DensityParams* dp);

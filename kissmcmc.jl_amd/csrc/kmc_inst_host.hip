@@ -6,4 +6,6 @@
 namespace kmc {
 HalfStepFn half_step_host() { return half_step_generic<HostEval, false>; }
 HalfStepFn half_step_host_de() { return half_step_de_generic<HostEval>; }
+HalfStepFn half_step_host_snooker() { return half_step_snooker_generic<HostEval>; }
+HalfStepFn half_step_host_mix() { return half_step_mix_generic<HostEval>; }
 }  // namespace kmc

@@ -433,13 +433,19 @@ static __device__ unsigned long long g_probe[2][8192][8];
 // RAGGED = true : ndim < 2*L*K, runtime ndim and row stride (preloaded, see the body), tail chunks folded onto the row's last chunk.
 // M = Move::DE: the differential-evolution move -- block 0 of its Philox stream and a second partner row (xk)
 // in front of the first scheduling barrier, block 1 behind it; no draw ring; one GPU, double rows, no blobs.
+// M = Move::Snooker: block 2 and THREE partner rows (xo: z, then x - z, then the proposal; xk: z1; xl: z2), all loaded in front of
+// block 3 (the accept uniform); the two sums over the row in the fixed order T (kmc_device.hpp); otherwise as DE.
+// over != nullptr (the mixture kernels): c0 and c1 of the half-step's member instead of the argument struct's.
 template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double, Move M = Move::Stretch>
-__device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const HalfStepArgs& a)
+__device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const HalfStepArgs& a, const DrawConsts* over = nullptr)
 {
+    static_assert(M != Move::Mix, "a mixture picks its member in front of the body (half_step_mix_vec_body)");
     static_assert(L >= 1 && L <= 64 && (L & (L - 1)) == 0, "L must be a power of two <= 64");
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
     constexpr bool kDE = M == Move::DE;
-    static_assert(!kDE || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "the DE move: one GPU, double rows, no blobs (kmc_validate)");
+    constexpr bool kSnk = M == Move::Snooker;
+    constexpr bool kOwn = kDE || kSnk;                  // a move with its own stream
+    static_assert(!kOwn || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "the DE move: one GPU, double rows, no blobs (kmc_validate)");
     using V2 = typename RowOf<T>::V2;                   // one chunk = two consecutive elements of a row
     T* const posT = reinterpret_cast<T*>(f.pos);
     static_assert(ITER >= 1 && ITER <= L, "a group's scalar lanes must cover its iterations");
@@ -488,11 +494,11 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     // (round 2, one more bounded try for L = 8 -- C2 -- in both launch modes: 4.83 against 4.27 us per half-step under the table
     //  graph, 4.70 against 3.99 with the step preloaded: the ring entry is one more dependent load in front of the partner
     //  row, and at 16 walkers per wave the Philox it replaces was already hidden.  Dropped; profiles/NOTES.md.)
-    constexpr bool kRing = !kDE && Q >= 2 && L >= 16 && L <= 32;        // (DE: nothing to park -- it has no log z)
+    constexpr bool kRing = !kOwn && Q >= 2 && L >= 16 && L <= 32;       // (DE: nothing to park -- it has no log z)
     const int64_t oth_row0 = (int64_t)(1 - half) * (int64_t)(P2P ? (uint32_t)nact : f.nhalf);
     const int  jq     = j / ITER, js = j - jq * ITER;
     const bool useA   = jq == 0;
-    const int  iA     = w0 + (kDE || jq < Q ? js : 0) * G + g;
+    const int  iA     = w0 + (kOwn || jq < Q ? js : 0) * G + g;
     const bool validA = useA && (iA < nact);
     const int      iAc = iA < nact ? iA : nact - 1;
     const int64_t  rowA = own_row0 + iAc;                                // row in pos / index in logp, naccept
@@ -506,6 +512,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     bool    validB[ITER];
     double2 xc[ITER][K], xo[ITER][K];
     double2 xk[ITER][K];                                                // DE: the second partner's rows (xo: the first's, then the proposal)
+    double2 xl[ITER][K];                                                // snooker: the third partner's rows
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int i = w0 + it * G + g;
@@ -538,7 +545,11 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     U4 bits{0u, 0u, 0u, 0u};
     uint32_t partnerA = e1y_lo;                                         // :250
     uint32_t partnerK = 0u;                                             // DE: the second partner
-    if constexpr (kDE) {                                                // block 0: both partners and the accept uniform
+    uint32_t partnerL = 0u;                                             // snooker: the third
+    if constexpr (kSnk) {                                               // block 2: the three partners
+        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 2u);
+        snooker_partners(bits, f.nhalf, &partnerA, &partnerK, &partnerL);
+    } else if constexpr (kDE) {                                                // block 0: both partners and the accept uniform
         bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 0u);
         partnerA = __umulhi(bits.x, f.nhalf);
         partnerK = de_partner_k(bits.y, f.nhalf, partnerA);
@@ -547,7 +558,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         partnerA = draw_partner(dcf, bits);
     }
 #if KMC_PROBE_PINS
-    if constexpr (!kDE) asm volatile("" :: "v"(partnerA));
+    if constexpr (!kOwn) asm volatile("" :: "v"(partnerA));
 #endif
     KMC_STAMP(1);                                       // Philox done: the partner index is known
 
@@ -562,11 +573,16 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     auto load_partner_rows = [&](int it) {
         const V2* oth;
         const V2* othk = nullptr;                                       // DE: x_k
+        const V2* othl = nullptr;                                       // snooker: z2 (oth: z, othk: z1)
         if constexpr (!P2P) {
             const uint32_t partner = (uint32_t)__builtin_amdgcn_ds_bpermute((gbase + it) * 4, (int)partnerA);
-            const uint32_t pk = kDE ? (uint32_t)__builtin_amdgcn_ds_bpermute((gbase + it) * 4, (int)partnerK) : 0u;
+            const uint32_t pk = kOwn ? (uint32_t)__builtin_amdgcn_ds_bpermute((gbase + it) * 4, (int)partnerK) : 0u;
             oth = reinterpret_cast<const V2*>(posT + row_off(oth_row0 + partner));
-            if constexpr (kDE) othk = reinterpret_cast<const V2*>(posT + row_off(oth_row0 + pk));
+            if constexpr (kOwn) othk = reinterpret_cast<const V2*>(posT + row_off(oth_row0 + pk));
+            if constexpr (kSnk) {
+                const uint32_t pl = (uint32_t)__builtin_amdgcn_ds_bpermute((gbase + it) * 4, (int)partnerL);
+                othl = reinterpret_cast<const V2*>(posT + row_off(oth_row0 + pl));
+            }
         } else {
             const int src = (gbase + it) * 4;
             const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(src, (int)(unsigned)addrA);
@@ -585,9 +601,13 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) xo[it][k] = load_row(&oth[ck[k]]);
-        if constexpr (kDE) {
+        if constexpr (kOwn) {
 #pragma unroll
             for (int k = 0; k < K; ++k) xk[it][k] = load_row(&othk[ck[k]]);
+        }
+        if constexpr (kSnk) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) xl[it][k] = load_row(&othl[ck[k]]);
         }
     };
     if constexpr (P2P) {
@@ -606,7 +626,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
             __syncthreads();
         }
     }
-    constexpr int kFirst = ITER >= 2 ? ITER / 2 : ITER;                 // iterations whose loads precede the first logarithm
+    constexpr int kFirst = ITER >= 2 && !kSnk ? ITER / 2 : ITER;        // iterations whose loads precede the first logarithm (snooker: every load precedes block 3)
 #pragma unroll
     for (int it = 0; it < kFirst; ++it) load_partner_rows(it);
     __builtin_amdgcn_sched_barrier(0);
@@ -628,6 +648,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     const bool sample = (sch.flags & kSample) != 0;
     DrawConsts dc = a.dc;                                               // seed and nhalf from the front parameters (DE: gamma0 in c0, sigma in c1)
     dc.seed_lo = f.seed_lo; dc.seed_hi = f.seed_hi; dc.nhalf = f.nhalf;
+    if (over != nullptr) { dc.c0 = over->c0; dc.c1 = over->c1; }       // (a mixture's member; folds away everywhere else)
     // Streaming moments are sojourn-weighted: a walker's value is credited, times the number of
     // samples it stood for, when it is replaced (and by flush_moments_vec at read-out).  Only waves
     // with an accepted move touch their accumulators -- at low acceptance (large ndim) almost none.
@@ -665,13 +686,17 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         if (do_mom && a.mring != nullptr) { ring_posted = a.mcnt[tid >> 6]; ring_swept = a.mswept[tid >> 6]; }
     }
 #if KMC_PROBE_PINS
-    if constexpr (!kDE) asm volatile("" :: "s"(count ? 1 : 0), "s"(a.dc.c0));
+    if constexpr (!kOwn) asm volatile("" :: "s"(count ? 1 : 0), "s"(a.dc.c0));
 #endif
     KMC_STAMP(3);                                       // the argument struct has arrived (schedule entry, constants)
     Draw dr;
     dr.partner = partnerA; dr.z = e1.x; dr.t1 = e0.x; dr.lu = e0.y;
     double ua = 0.5;
-    if constexpr (kDE) {                                                // block 1: the jitter of gamma; z = gamma, t1 unused
+    if constexpr (kSnk) {                                               // block 3: the accept uniform; z = gamma, t1 once s is known
+        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 3u);
+        dr.z = dc.c0;
+        dr.t1 = 0.0;
+    } else if constexpr (kDE) {                                         // block 1: the jitter of gamma; z = gamma, t1 unused
         const U4 b1 = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 1u);
         dr.z = de_gamma(dc, b1.x);
         dr.t1 = 0.0;
@@ -687,7 +712,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
 #pragma unroll
     for (int it = kFirst; it < ITER; ++it) load_partner_rows(it);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (kDE) {
+    if constexpr (kOwn) {
         dr.lu = log_pos_normal(de_accept_u(bits));
     } else if (!fresh) {
         dr.lu = log_pos_normal(ua);                                     // :260
@@ -700,22 +725,48 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
         }
     }
 #if KMC_PROBE_PINS
-    if constexpr (!kDE) asm volatile("" :: "v"(dr.lu), "v"(dr.t1));
+    if constexpr (!kOwn) asm volatile("" :: "v"(dr.lu), "v"(dr.t1));
 #endif
     KMC_STAMP(4);                                       // both logarithms done, every partner-row load issued
     double zB[ITER];
 #pragma unroll
-    for (int it = 0; it < ITER; ++it) zB[it] = bperm_f64((gbase + it) * 4, dr.z);
+    for (int it = 0; it < ITER; ++it) zB[it] = kSnk ? dc.c0 : bperm_f64((gbase + it) * 4, dr.z);   // (snooker: gamma is the same for every walker)
 
     // ---- stretch or DE move + log-pdf; xo becomes the proposal ------------------------------
     double myp1 = 0.0;
+    double mys = 0.0;                                                   // snooker: s of this lane's walker (scalar layout)
     constexpr int kRowND = RowEvalTrait<Dens>::n;                       // > 0: a function body over the whole proposal (see below)
     double blob1[BlobTrait<Dens>::n > 0 ? BlobTrait<Dens>::n : 1];      // ... and the blob it returned (blob1 of src/samplers.jl:257), scalar layout
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
+        if constexpr (kSnk) {
+            // n2 = T(d . d), q = T(d . (z1 - z2)) with d = x - z: the in-chunk pair, the lane butterfly per chunk, the tree over the chunks
+            double vn[K], vq[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int e0 = 2 * (k * L + j);
+                const double dx = xc[it][k].x - xo[it][k].x, dy = xc[it][k].y - xo[it][k].y;
+                const double nx = dx * dx, ny = dy * dy;
+                const double qx = dx * (xk[it][k].x - xl[it][k].x), qy = dy * (xk[it][k].y - xl[it][k].y);
+                vn[k] = group_sum<L>(((e0 < ndim) ? nx : 0.0) + ((e0 + 1 < ndim) ? ny : 0.0));   // elements >= ndim are padding: +0.0
+                vq[k] = group_sum<L>(((e0 < ndim) ? qx : 0.0) + ((e0 + 1 < ndim) ? qy : 0.0));
+                xo[it][k] = make_double2(dx, dy);
+            }
+#pragma unroll
+            for (int w = 1; w < K; w *= 2) {
+#pragma unroll
+                for (int k = 0; k + w < K; k += 2 * w) { vn[k] = vn[k] + vn[k + w]; vq[k] = vq[k] + vq[k + w]; }
+            }
+            const double sB = snooker_s(zB[it], vq[0] + 0.0, vn[0] + 0.0);
+            mys = (j == it) ? sB : mys;
+            zB[it] = sB;
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {                                   // :255
-            if constexpr (kDE) {                                        // y = x + g (x_j - x_k), separately rounded
+            if constexpr (kSnk) {                                       // y = x + (x - z) s, separately rounded
+                xo[it][k].x = xc[it][k].x + xo[it][k].x * zB[it];
+                xo[it][k].y = xc[it][k].y + xo[it][k].y * zB[it];
+            } else if constexpr (kDE) {                                        // y = x + g (x_j - x_k), separately rounded
                 xo[it][k].x = xc[it][k].x + zB[it] * (xo[it][k].x - xk[it][k].x);
                 xo[it][k].y = xc[it][k].y + zB[it] * (xo[it][k].y - xk[it][k].y);
             } else {
@@ -766,11 +817,13 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     }
 
 #if KMC_PROBE_PINS
-    if constexpr (!kDE) asm volatile("" :: "v"(myp1));
+    if constexpr (!kOwn) asm volatile("" :: "v"(myp1));
 #endif
     KMC_STAMP(5);                                       // both rows have arrived, the proposal's log-pdf is reduced
     // ---- accept test in the scalar layout ---------------------------------------------------
-    const bool acc = validA && (kDE ? de_accept_test(dr, myp1, p0) : accept_test(dr, myp1, p0));   // :260
+    bool snk_ok = true;
+    if constexpr (kSnk) snk_ok = snooker_hastings(dr, dc.nm1, mys);    // (ndim - 1) log|1 + s| + p1 - p0 >= log u
+    const bool acc = validA && snk_ok && (kDE ? de_accept_test(dr, myp1, p0) : accept_test(dr, myp1, p0));   // :260
     const unsigned long long accmask = __ballot(acc);
     if (acc) {
         store_wt(&logp_p[rowA], myp1);                                  // :262
@@ -882,7 +935,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     }
     KMC_STAMP(7);                                       // the last store is issued
 #ifdef KMC_PROBE
-    if constexpr (!kDE) {                               // (the DE kernels stamp, but keep no record)
+    if constexpr (!kOwn) {                              // (the DE kernels stamp, but keep no record)
         unsigned long long st[8];
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         KMC_STAMP_READ(st[0], 80, 81); KMC_STAMP_READ(st[1], 82, 83); KMC_STAMP_READ(st[2], 84, 85); KMC_STAMP_READ(st[3], 86, 87);
@@ -901,6 +954,38 @@ template <class Dens, int L, int K, int ITER, bool RAGGED>
 __global__ __launch_bounds__(vec_tpb(L)) void half_step_de_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::DE>(KMC_FRONT_PACK, a);
+}
+template <class Dens, int L, int K, int ITER, bool RAGGED>
+__global__ __launch_bounds__(vec_tpb(L)) void half_step_snooker_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::Snooker>(KMC_FRONT_PACK, a);
+}
+// A mixture of DE and snooker members (KMC_MOVE_MIX): the member of this half-step is a pure function of (seed, step), the same for
+// every wave of the launch -- one scalar branch in front of the two bodies.  The table's address travels in HalfStepArgs::peer_pos[0]
+// (these moves run on one GPU; the struct every half-step kernel takes keeps its length).
+__device__ __forceinline__ const MixTable* mix_table(const HalfStepArgs& a) { return reinterpret_cast<const MixTable*>(a.peer_pos[0]); }
+__device__ __forceinline__ bool mix_pick(const HalfStepArgs& a, uint32_t seed_lo, uint32_t seed_hi, uint64_t step, DrawConsts* dc)
+{
+    const MixTable* t = mix_table(a);
+    const int i = mix_member(t, seed_lo, seed_hi, step);
+    *dc = a.dc;
+    dc->c0 = i == 0 ? t->c0[0] : i == 1 ? t->c0[1] : i == 2 ? t->c0[2] : t->c0[3];
+    dc->c1 = i == 0 ? t->c1[0] : i == 1 ? t->c1[1] : i == 2 ? t->c1[2] : t->c1[3];
+    const int mv = i == 0 ? t->move[0] : i == 1 ? t->move[1] : i == 2 ? t->move[2] : t->move[3];
+    return mv == kMoveIdSnooker;
+}
+template <class Dens, int L, int K, int ITER, bool RAGGED>
+__device__ __forceinline__ void half_step_mix_vec_body(const HalfStepFront& f, const HalfStepArgs& a)
+{
+    const uint64_t step = f.sched == nullptr ? (uint64_t)f.step : 2ull * (uint64_t)schedule_entry(f).gen + (uint64_t)f.half();
+    DrawConsts dc;
+    if (mix_pick(a, f.seed_lo, f.seed_hi, step, &dc)) half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::Snooker>(f, a, &dc);
+    else half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::DE>(f, a, &dc);
+}
+template <class Dens, int L, int K, int ITER, bool RAGGED>
+__global__ __launch_bounds__(vec_tpb(L)) void half_step_mix_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_mix_vec_body<Dens, L, K, ITER, RAGGED>(KMC_FRONT_PACK, a);
 }
 
 // Moment read-out: credit every walker's current value with the samples it has stood for since it
@@ -961,11 +1046,14 @@ __global__ __launch_bounds__(vec_tpb(L)) void flush_moments_vec(const FlushArgs 
 // Generic kernel: one walker per lane, any ndim.
 // ------------------------------------------------------------------------------------------
 template <class Dens, bool P2P, class T = double, Move M = Move::Stretch>
-__device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, const HalfStepArgs& a)
+__device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, const HalfStepArgs& a, const DrawConsts* over = nullptr)
 {
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
+    static_assert(M != Move::Mix, "a mixture picks its member in front of the body (half_step_mix_generic_body)");
     constexpr bool kDE = M == Move::DE;
-    static_assert(!kDE || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "the DE move: one GPU, double rows, no blobs (kmc_validate)");
+    constexpr bool kSnk = M == Move::Snooker;
+    constexpr bool kOwn = kDE || kSnk;
+    static_assert(!kOwn || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "the DE move: one GPU, double rows, no blobs (kmc_validate)");
     const int tid = blockIdx.x * 256 + threadIdx.x;
     const SchedEntry sch = schedule_of(f, a);
     const uint64_t step = 2ull * (uint64_t)sch.gen + (uint64_t)a.half;      // (eager: sched_inline.gen)
@@ -976,15 +1064,20 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     const bool sample = (sch.flags & kSample) != 0;
     const int64_t gw = a.own_row0 + tid;                                // row in pos / index in logp, naccept
     uint32_t partner_k = 0u;                                            // DE: the second partner
-    const Draw dr = kDE ? de_draw(a.dc, step, (uint32_t)(a.gw0 + tid), &partner_k)   // DE: partner = j, z = gamma, lu = log u
-                        : draw_step(a.dc, step, (uint64_t)(a.gw0 + tid));
+    uint32_t partner_l = 0u;                                            // snooker: the third
+    const DrawConsts& dcm = over != nullptr ? *over : a.dc;             // (a mixture's member; folds away everywhere else)
+    Draw dr = kSnk ? snooker_draw(dcm, step, (uint32_t)(a.gw0 + tid), &partner_k, &partner_l)   // snooker: partner = z, z = gamma, lu = log u
+            : kDE ? de_draw(dcm, step, (uint32_t)(a.gw0 + tid), &partner_k)   // DE: partner = j, z = gamma, lu = log u
+                  : draw_step(a.dc, step, (uint64_t)(a.gw0 + tid));
     const int64_t ld = a.ld;
     T* own = reinterpret_cast<T*>(a.pos) + gw * ld;
     const T* oth;
     const T* othk = nullptr;                                            // DE: x_k (oth: x_j)
+    const T* othl = nullptr;                                            // snooker: z2 (oth: z, othk: z1)
     if constexpr (!P2P) {
         oth = reinterpret_cast<const T*>(a.pos) + (a.oth_row0 + dr.partner) * ld;
-        if constexpr (kDE) othk = reinterpret_cast<const T*>(a.pos) + (a.oth_row0 + partner_k) * ld;
+        if constexpr (kOwn) othk = reinterpret_cast<const T*>(a.pos) + (a.oth_row0 + partner_k) * ld;
+        if constexpr (kSnk) othl = reinterpret_cast<const T*>(a.pos) + (a.oth_row0 + partner_l) * ld;
     } else {
         const uint32_t q = a.hloc_shift >= 0 ? dr.partner >> a.hloc_shift : dr.partner / a.hloc;
         const uint32_t r = dr.partner - q * a.hloc;
@@ -1003,9 +1096,27 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
         }
         return (double)oth[d];
     };
+    // snooker: s = gamma T(d . (z1 - z2)) / T(d . d), d = x - z, the two sums in the fixed order T (kmc_device.hpp)
+    double snk_s = 0.0;
+    bool snk_ok = true;
+    if constexpr (kSnk) {
+        TreeStack2 st;
+        for (int d = 0; d < ndim; d += 2) {
+            const double dx = own[d] - oth[d];
+            double nn = dx * dx, qq = dx * (othk[d] - othl[d]);
+            double ny = 0.0, qy = 0.0;
+            if (d + 1 < ndim) { const double dy = own[d + 1] - oth[d + 1]; ny = dy * dy; qy = dy * (othk[d + 1] - othl[d + 1]); }
+            st.push(nn + ny, qq + qy, (uint32_t)(d >> 1));
+        }
+        double n2, q;
+        st.finish((uint32_t)((ndim + 1) >> 1), &n2, &q);
+        snk_s = snooker_s(dr.z, q, n2);
+        snk_ok = snooker_hastings(dr, dcm.nm1, snk_s);
+    }
     // element d of the proposal
     auto y_at = [&](int d) -> double {
-        if constexpr (kDE) return own[d] + dr.z * (oth[d] - othk[d]);  // y = x + g (x_j - x_k), separately rounded
+        if constexpr (kSnk) return own[d] + (own[d] - oth[d]) * snk_s;  // y = x + (x - z) s, separately rounded
+        else if constexpr (kDE) return own[d] + dr.z * (oth[d] - othk[d]);  // y = x + g (x_j - x_k), separately rounded
         else { const double o = oth_at(d); return as_stored<T>(fma(dr.z, (double)own[d] - o, o)); }   // :255
     };
 
@@ -1021,7 +1132,7 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     for (int d = 0; d < ndim; ++d) Dens::seq_add(q, y_at(d), d, a.dp);
     double p1 = Dens::seq_finish(q, ndim, a.dp);                         // :257
     if constexpr (kHost) p1 = a.p1_in[tid];
-    const bool acc = kDE ? de_accept_test(dr, p1, p0) : accept_test(dr, p1, p0);   // :260
+    const bool acc = snk_ok && (kDE ? de_accept_test(dr, p1, p0) : accept_test(dr, p1, p0));   // :260
     if constexpr (kHost) { if (a.acc_out != nullptr) a.acc_out[tid] = acc ? 1 : 0; }
 
     const bool do_mom = sample && a.msum != nullptr;
@@ -1031,7 +1142,8 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
         for (int d = 0; d < ndim; ++d) {
             const double xcd = (double)own[d];
             double cur;
-            if constexpr (kDE) cur = acc ? xcd + dr.z * (oth[d] - othk[d]) : xcd;
+            if constexpr (kSnk) cur = acc ? xcd + (xcd - oth[d]) * snk_s : xcd;
+            else if constexpr (kDE) cur = acc ? xcd + dr.z * (oth[d] - othk[d]) : xcd;
             else { const double o = acc ? oth_at(d) : 0.0; cur = acc ? as_stored<T>(fma(dr.z, xcd - o, o)) : xcd; }
             if (acc) own[d] = (T)cur;                                   // :261
             if (do_chain) reinterpret_cast<T*>(a.chain)[row * ld + d] = (T)cur;   // :269
@@ -1071,6 +1183,24 @@ template <class Dens>
 __global__ __launch_bounds__(256) void half_step_de_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_generic_body<Dens, false, double, Move::DE>(KMC_FRONT_PACK, a);
+}
+template <class Dens>
+__global__ __launch_bounds__(256) void half_step_snooker_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_generic_body<Dens, false, double, Move::Snooker>(KMC_FRONT_PACK, a);
+}
+template <class Dens>
+__device__ __forceinline__ void half_step_mix_generic_body(const HalfStepFront& f, const HalfStepArgs& a)
+{
+    const uint64_t step = 2ull * (uint64_t)schedule_of(f, a).gen + (uint64_t)a.half;
+    DrawConsts dc;
+    if (mix_pick(a, a.dc.seed_lo, a.dc.seed_hi, step, &dc)) half_step_generic_body<Dens, false, double, Move::Snooker>(f, a, &dc);
+    else half_step_generic_body<Dens, false, double, Move::DE>(f, a, &dc);
+}
+template <class Dens>
+__global__ __launch_bounds__(256) void half_step_mix_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_mix_generic_body<Dens>(KMC_FRONT_PACK, a);
 }
 
 // ------------------------------------------------------------------------------------------

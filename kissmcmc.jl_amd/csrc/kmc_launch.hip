@@ -84,6 +84,13 @@ HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t 
         a.dc.c0 = de_gamma0_of(s->cfg);
         a.dc.c1 = s->cfg.de_sigma;
         a.dc.nm1 = 0.0;
+    } else if (s->cfg.move == KMC_MOVE_SNOOKER) {                         // gamma; nm1 stays ndim - 1 (the Hastings factor)
+        a.dc.c0 = snooker_gamma_of(s->cfg.snooker_gamma);
+        a.dc.c1 = 0.0;
+    } else if (s->cfg.move == KMC_MOVE_MIX) {                             // the member's c0, c1 come from the table (kmc_kernels.hpp: mix_pick)
+        a.dc.c0 = 0.0;
+        a.dc.c1 = 0.0;
+        a.peer_pos[0] = reinterpret_cast<double*>(s->d_mix);
     }
     a.dp = s->dp;
     a.chain = s->d_chain;

@@ -25,10 +25,15 @@ bool lookup(int density, int L, int K, int iter, bool p2p, bool ragged, bool f32
     });
 }
 
-// KMC_MOVE_DE: the differential-evolution kernels (PART 3)
-bool lookup_de(int density, int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
+// KMC_MOVE_DE: the differential-evolution kernels (PART 3); KMC_MOVE_SNOOKER: PART 4; KMC_MOVE_MIX: PART 5
+bool lookup_move(int move, int density, int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
 {
-    return with_density(density, false, [&](auto d) { density_part<decltype(d), 3>(L, K, iter, ragged, false, vec, gen); return true; });
+    return with_density(density, false, [&](auto d) {
+        if (move == KMC_MOVE_SNOOKER) density_part<decltype(d), 4>(L, K, iter, ragged, false, vec, gen);
+        else if (move == KMC_MOVE_MIX) density_part<decltype(d), 5>(L, K, iter, ragged, false, vec, gen);
+        else density_part<decltype(d), 3>(L, K, iter, ragged, false, vec, gen);
+        return true;
+    });
 }
 
 LogpdfFn logpdf_fn(int density)
@@ -131,9 +136,12 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
             while (iter >= 2 && iter * 2 <= L && iter * 2 * K <= 16 && waves1 / (iter * 2) >= 4096 && iter < 16) iter *= 2;
         }
     }
-    const bool de = c.move == KMC_MOVE_DE;
-    // (a DE kernel holds three row tiles -- own, two partners -- where the stretch kernel holds two: at most 8 chunks per lane each)
-    if (de && !env) while (iter > 1 && iter * K > 8) iter /= 2;
+    const bool de = own_stream_move(c);
+    // (a DE kernel holds three row tiles -- own, two partners -- where the stretch kernel holds two: at most 8 chunks per lane each;
+    //  a snooker or mixture kernel holds four -- at most 4 chunks each, 64 of its VGPRs, so that the two sums' butterflies and the
+    //  density still fit 128 VGPRs: four waves per SIMD, as DE has them at 8)
+    const int tile_cap = c.move == KMC_MOVE_DE ? 8 : 4;
+    if (de && (!env || c.move != KMC_MOVE_DE)) while (iter > 1 && iter * K > tile_cap) iter /= 2;
     const bool ragged = L > 0 && 2 * L * K != c.ndim;
     const bool f32 = c.dtype == KMC_F32;
     if ((ragged || f32) && iter > 4) iter = 4;
@@ -141,7 +149,7 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     p.ragged = ragged;
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY) {
         // bound by the host callback (or, for a data density, by the data kernels between the two passes): the one-walker-per-lane kernel, any ndim
-        p.fn = de ? half_step_host_de() : half_step_host(); p.vec = false; p.ragged = false; p.L = 1; p.K = 1; p.ITER = 1;
+        p.fn = c.move == KMC_MOVE_MIX ? half_step_host_mix() : c.move == KMC_MOVE_SNOOKER ? half_step_host_snooker() : de ? half_step_host_de() : half_step_host(); p.vec = false; p.ragged = false; p.L = 1; p.K = 1; p.ITER = 1;
         return p;
     }
     if (c.density == KMC_USER_DENSITY) {
@@ -160,7 +168,7 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
         }
         return p;
     }
-    if (de) lookup_de(c.density, L, K, iter, ragged, &vec, &gen);
+    if (de) lookup_move(c.move, c.density, L, K, iter, ragged, &vec, &gen);
     else lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen);
     if (!force_generic && L > 0 && 2 * L * K >= c.ndim && vec != nullptr) {
         p.fn = vec; p.vec = true; p.L = L; p.K = K; p.ITER = iter;

@@ -108,15 +108,42 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
         if (c->dtype != KMC_F64 || P != 1 || (c->flags & (KMC_P2P | KMC_ISLANDS)))
             return fail(KMC_ERR_UNSUPPORTED, "KMC_STREAM_CHAIN: KMC_F64, one GPU, without KMC_P2P / KMC_ISLANDS / sharding");
     }
-    if (c->move != KMC_MOVE_STRETCH && c->move != KMC_MOVE_DE) return fail(KMC_ERR_BAD_ARG, "kmc_config.move must be KMC_MOVE_STRETCH or KMC_MOVE_DE");
-    if (c->move == KMC_MOVE_DE) {
-        if (!std::isfinite(c->de_gamma0) || c->de_gamma0 < 0.0) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_DE: de_gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim))");
-        if (!std::isfinite(c->de_sigma) || c->de_sigma < 0.0 || c->de_sigma >= 1.0) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_DE: de_sigma must be in [0, 1)");
+    if (c->move != KMC_MOVE_STRETCH && c->move != KMC_MOVE_DE && c->move != KMC_MOVE_SNOOKER && c->move != KMC_MOVE_MIX)
+        return fail(KMC_ERR_BAD_ARG, "kmc_config.move must be KMC_MOVE_STRETCH, KMC_MOVE_DE, KMC_MOVE_SNOOKER or KMC_MOVE_MIX");
+    if (c->move != KMC_MOVE_STRETCH) {
+        const std::string name = move_name(c->move);
+        auto check_de = [&](double gamma0, double sigma) -> kmc_status {
+            if (!std::isfinite(gamma0) || gamma0 < 0.0) return fail(KMC_ERR_BAD_ARG, name + ": de_gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim))");
+            if (!std::isfinite(sigma) || sigma < 0.0 || sigma >= 1.0) return fail(KMC_ERR_BAD_ARG, name + ": de_sigma must be in [0, 1)");
+            return KMC_OK;
+        };
+        auto check_snooker = [&](double gamma) -> kmc_status {
+            if (!std::isfinite(gamma) || gamma < 0.0) return fail(KMC_ERR_BAD_ARG, name + ": snooker_gamma must be finite and >= 0 (0: 1.7)");
+            if (c->ndim < 2) return fail(KMC_ERR_BAD_ARG, name + ": the snooker move needs ndim >= 2 (it is degenerate in one dimension)");
+            if (c->nwalkers < 6) return fail(KMC_ERR_BAD_ARG, name + ": the snooker move needs nwalkers >= 6 (three distinct partners in a half)");
+            return KMC_OK;
+        };
+        if (c->move == KMC_MOVE_DE) KMC_TRY(check_de(c->de_gamma0, c->de_sigma));
+        if (c->move == KMC_MOVE_SNOOKER) KMC_TRY(check_snooker(c->snooker_gamma));
+        if (c->move == KMC_MOVE_MIX) {
+            if (c->mix_count < 2 || c->mix_count > KMC_MIX_MAX) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: mix_count must be 2 .. 4");
+            for (int i = 0; i < c->mix_count; ++i) {
+                if (c->mix_move[i] == KMC_MOVE_STRETCH)
+                    return fail(KMC_ERR_UNSUPPORTED, "KMC_MOVE_MIX: a stretch member is not supported yet (members are KMC_MOVE_DE and KMC_MOVE_SNOOKER; DESIGN.md section 8)");
+                if (c->mix_move[i] != KMC_MOVE_DE && c->mix_move[i] != KMC_MOVE_SNOOKER) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: a member must be KMC_MOVE_DE or KMC_MOVE_SNOOKER");
+                if (!std::isfinite(c->mix_weight[i]) || !(c->mix_weight[i] > 0.0)) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: weights must be finite and > 0");
+                if (c->mix_move[i] == KMC_MOVE_DE) KMC_TRY(check_de(c->mix_gamma[i], c->mix_sigma[i]));
+                else KMC_TRY(check_snooker(c->mix_gamma[i]));
+            }
+            double sum = 0.0;
+            for (int i = 0; i < c->mix_count; ++i) sum += c->mix_weight[i];
+            if (!std::isfinite(sum)) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: the weights' sum must be finite");
+        }
         const char* what = (c->flags & KMC_ISLANDS) ? "KMC_ISLANDS" : (c->flags & KMC_P2P) ? "KMC_P2P" : P > 1 ? "shard_count > 1"
                          : c->deal_count > 0 ? "dealt sub-ensembles (deal_count > 0)" : c->dtype == KMC_F32 ? "KMC_F32"
                          : (c->flags & KMC_STORE_BLOBS) ? "KMC_STORE_BLOBS" : nullptr;
         if (!what && c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) what = "a density with blobs";
-        if (what) return fail(KMC_ERR_UNSUPPORTED, std::string("KMC_MOVE_DE: two launches per generation on one GPU with double rows -- not with ") + what);
+        if (what) return fail(KMC_ERR_UNSUPPORTED, name + ": two launches per generation on one GPU with double rows -- not with " + what);
     }
     {
         const int nb = c->density == KMC_USER_DENSITY && c->user_density ? static_cast<const kmc_user_density*>(c->user_density)->nblob : 0;
@@ -296,7 +323,7 @@ int generation_wanted(const kmc_sampler* s)
 {
     const kmc_config& c = s->cfg;
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY || s->f32 || s->nblob != 0 || c.shard_count != 1 || c.deal_count != 0 ||
-        c.move == KMC_MOVE_DE ||                                                                      // (DE: the two-launch kernels only)
+        own_stream_move(c) ||                                                                         // (DE, snooker, mixtures: the two-launch kernels only)
         (c.flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) || std::getenv("KMC_PLAN") != nullptr)      // (KMC_PLAN: a geometry of the two-launch kernels was asked for)
         return 0;
     // lane-striped forms need a lane-striped density (menu, term / pair, a body recognised as a sum) and the vector kernels' plan
@@ -360,7 +387,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         const bool lane2 = cfg->nwalkers > 1024 && cfg->nwalkers <= 2048 && !s->f32 && cfg->ndim <= 8 && s->user->nblob == 0 && resident_lane_wanted(cfg->ndim);
         if (lane2) rlds = ((size_t)cfg->nwalkers * (size_t)((cfg->ndim | 1) + 1)) * sizeof(double);
         if ((!s->f32 || s->user->is_body || expr_lane) && (cfg->nwalkers <= ((s->user->is_body || expr_lane) ? 1024 : 256) || lane2) && cfg->ndim <= 32 && s->cfg.shard_count == 1 && !(s->user->is_body && cfg->deal_count > 0) &&
-            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && cfg->move != KMC_MOVE_DE &&
+            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && !own_stream_move(*cfg) &&
             rlds <= 156 * 1024 && !debug_opt("no-resident"))    // (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
             rK = rK0;
         int iS = 0;
@@ -395,7 +422,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
             set_offline_compiler_hint(s->h_loc >= 8192 && rK == 0 && iS == 0);
             const kmc_status lst = load_user(s->user, s->plan.vec, s->plan.L, s->plan.K, s->plan.ITER, s->plan.ragged, &s->uk, rcode, 4 * rK != cfg->ndim, iS, s->f32,
                                              cfg->ndim, (cfg->flags & KMC_P2P) != 0, (rK != 0 || iS != 0) ? 0 : generation_wanted(s) == 1 ? (int)cfg->ndim : generation_wanted(s) == 2 ? -(100 * s->plan.L + s->plan.K) : generation_wanted(s) == 3 ? -401 : 0,
-                                             cfg->move == KMC_MOVE_DE);
+                                             (int)cfg->move);
             set_offline_compiler_hint(false);
             return lst;
         };
@@ -459,7 +486,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         if (ea != hipSuccess) { (void)hipGetLastError(); kmc_sampler_destroy(s); return fail(KMC_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
     }
     if (!s->islands && cfg->density != KMC_USER_DENSITY && !s->host_eval && cfg->nwalkers <= 2048 && cfg->ndim <= 32 &&
-        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && cfg->move != KMC_MOVE_DE && !debug_opt("no-resident")) {
+        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && !own_stream_move(*cfg) && !debug_opt("no-resident")) {
         const int64_t chunks = s->ld / 2;
         int K = 1;
         while (2 * K < chunks) K *= 2;
@@ -557,6 +584,11 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     s->p2p = (cfg->flags & KMC_P2P) != 0;
     s->nrows = s->p2p ? s->nlocal : cfg->nwalkers;
     const size_t nw = (size_t)s->nrows;
+    if (cfg->move == KMC_MOVE_MIX) {
+        const MixTable mt = mix_table_of(*cfg);
+        CREATE_TRY(dev_alloc(s, (void**)&s->d_mix, sizeof(MixTable)));
+        CREATE_TRY(copy_sync(s->d_mix, &mt, sizeof(MixTable), hipMemcpyHostToDevice, s->stream));
+    }
     if (s->p2p) {
         CREATE_TRY(hipExtMallocWithFlags((void**)&s->d_flags, 4096, hipDeviceMallocFinegrained));
         CREATE_TRY(hipMemsetAsync(s->d_flags, 0, 4096, s->stream));
@@ -597,7 +629,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     // kernels gained 6-10 % from it only while their loads sat behind exec-mask regions and scalar waits; without those they behave like the exact-size ones), and
     // 6-14 % in the large-ensemble geometries (ITER >= 4: bandwidth-bound, the ring is bytes); L = 16, ITER = 1 (C3's geometry) is +-1 % exact-size, -1..2 % ragged, and keeps it.
     // KMC_DEBUG=ring=0|1 forces it off / on wherever the kernel has one.
-    bool want_ring = s->plan.vec && cfg->move != KMC_MOVE_DE && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
+    bool want_ring = s->plan.vec && !own_stream_move(*cfg) && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
     {
         std::string forced;
         if (want_ring && debug_opt("ring", &forced)) want_ring = forced != "0";
@@ -774,6 +806,7 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
         cache_free(s->d_flags);
         cache_free(s->d_err);
     }
+    cache_free(s->d_mix);
     if (s->comm) { rccl_comm_destroy(s->comm); s->comm = nullptr; }
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     for (int i = 0; i < 3; ++i) {
@@ -921,6 +954,24 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
         std::snprintf(b, sizeof(b), "; differential-evolution move (KMC_MOVE_DE): gamma0 %.6g, sigma %.3g, kernel %s", de_gamma0_of(s->cfg), s->cfg.de_sigma,
                       s->host_eval ? "half_step_de_generic (propose / accept passes)" : s->plan.vec ? "half_step_de_vec" : "half_step_de_generic");
         o << b;
+    }
+    if (s->cfg.move == KMC_MOVE_SNOOKER) {
+        char b[160];
+        std::snprintf(b, sizeof(b), "; snooker move (KMC_MOVE_SNOOKER): gamma %.6g, kernel %s", snooker_gamma_of(s->cfg.snooker_gamma),
+                      s->host_eval ? "half_step_snooker_generic (propose / accept passes)" : s->plan.vec ? "half_step_snooker_vec" : "half_step_snooker_generic");
+        o << b;
+    }
+    if (s->cfg.move == KMC_MOVE_MIX) {
+        double w[KMC_MIX_MAX] = {0.0, 0.0, 0.0, 0.0};
+        const MixTable mt = mix_table_of(s->cfg, w);
+        o << "; move mixture (KMC_MOVE_MIX), one member per half-step:";
+        for (int i = 0; i < mt.count; ++i) {
+            char b[160];
+            if (mt.move[i] == KMC_MOVE_DE) std::snprintf(b, sizeof(b), " %.6g x DE (gamma0 %.6g, sigma %.3g)", w[i], mt.c0[i], mt.c1[i]);
+            else std::snprintf(b, sizeof(b), " %.6g x snooker (gamma %.6g)", w[i], mt.c0[i]);
+            o << (i ? "," : "") << b;
+        }
+        o << ", kernel " << (s->host_eval ? "half_step_mix_generic (propose / accept passes)" : s->plan.vec ? "half_step_mix_vec" : "half_step_mix_generic");
     }
     if (s->budget_fallback) o << "; updated-graph budget of the process spent (kmc_set_updated_budget_mb): fell back to " << (s->launch_mode == 2 ? "eager launches" : "the table graph");
     if (s->push) o << "; accepted rows pushed into the peers' local copies (KMC_P2P_PUSH)";

@@ -190,6 +190,7 @@ struct kmc_sampler {
     int64_t nrows = 0;                                   // rows held by this sampler (nwalkers, or nlocal for P2P)
     unsigned long long* d_flags = nullptr;               // fine-grained progress flags [shard_count]
     unsigned long long* d_err = nullptr;
+    kmc::MixTable* d_mix = nullptr;                                     // KMC_MOVE_MIX: the members' table (kmc_host.hpp: mix_table_of)
     bool stream_by_walker = false;                       // KMC_STREAM_CHAIN | KMC_CHAIN_BY_WALKER: host buffers are [walker][nsamples][..]
     double *bw_scratch = nullptr, *bw_scratch_logp = nullptr;   // ... one transposed block on the device, copied out as a 2-D window (also: rows_compact of odd ndim)
     std::vector<double> bw_host;                         // ... (host buffers that could not be page-locked: a block lands here, then is scattered by memcpy)
@@ -232,7 +233,7 @@ void chain_unregister(kmc_sampler* s);
 // kmc_rtc.hip
 kmc_status load_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged, UserKernels* uk,
                      int resident_K = 0, bool resident_ragged = false, int island_S = 0, bool f32 = false, int64_t ndim = 0, bool p2p = false,
-                     int generation_nd = 0, bool de = false);
+                     int generation_nd = 0, int move = 0);
 void drop_updated_graph(kmc_sampler* s);                               // the updated-graph mode's executables, events and template graph (kmc_launch.hip)
 kmc_status unfuse(kmc_sampler* s);                                     // back to the two-launch kernels, in place (kmc_launch.hip)
 void set_offline_compiler_hint(bool wanted);                          // runtime-compiled kernels of this thread: hipcc as a child process instead of hiprtc (kmc_rtc.hip)

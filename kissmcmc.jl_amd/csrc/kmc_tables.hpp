@@ -1,14 +1,15 @@
 // kmc_tables.hpp -- kernel instantiation tables.  The lookup templates below map a launch geometry to a kernel of density D.
 // Every translation unit sees their declarations.  Only the kmc_inst_<density>*.hip files define KMC_TABLES_IMPL: they see the
 // definitions and instantiate them explicitly for their density (KMC_INSTANTIATE_*).  So the host driver names them without
-// instantiating a kernel, and the build compiles a density's kernels in parallel, five translation units per density:
+// instantiating a kernel, and the build compiles a density's kernels in parallel, six translation units per density:
 //   kmc_inst_<density>.hip       density_part PART 0: double rows of exact size, one GPU (incl. the tuning geometries); the
 //                                log-pdf and initial-ball kernels
 //   kmc_inst_<density>_var.hip   density_part PART 1: ragged sizes and KMC_F32 rows, one GPU
 //   kmc_inst_<density>_p2p.hip   density_part PART 2: the peer-to-peer kernels (KMC_P2P)
 //   kmc_inst_<density>_de.hip    density_part PART 3: the differential-evolution move (KMC_MOVE_DE: exact and ragged double rows, one GPU)
+//   kmc_inst_<density>_snooker.hip  density_part PART 4 and 5: the snooker move (KMC_MOVE_SNOOKER) and the DE / snooker mixtures (KMC_MOVE_MIX), as PART 3
 //   kmc_inst_<density>_lds.hip   the LDS-resident (islands, resident mode), one-launch-per-generation and many-chain Metropolis kernels
-// Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_de).
+// Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_move).
 #pragma once
 #include <type_traits>
 #include "kmc_islands.hpp"
@@ -41,13 +42,18 @@ template <class D> MetropolisFn metropolis_lookup(int ndim);
 template <class D> MetropolisTabledFn metropolis_tabled_lookup(int ndim);
 HalfStepFn half_step_host();         // kmc_inst_host.hip
 HalfStepFn half_step_host_de();      // KMC_MOVE_DE
+HalfStepFn half_step_host_snooker(); // KMC_MOVE_SNOOKER
+HalfStepFn half_step_host_mix();     // KMC_MOVE_MIX
 
 #ifdef KMC_TABLES_IMPL
 template <class D, int L, int K, int ITER, bool P2P, bool RAGGED, class T, Move M>
 HalfStepFn vec_one()
 {
     // a group's ITER scalar lanes must fit in its L lanes; keep the register tile (ITER*K chunks) bounded
-    if constexpr (ITER > L || ITER * K > 16) return nullptr;
+    // (snooker and the mixtures hold four row tiles: the planner keeps ITER * K <= 4 for them, kmc_plan.hip)
+    if constexpr (ITER > L || ITER * K > 16 || ((M == Move::Snooker || M == Move::Mix) && ITER > 1 && ITER * K > 4)) return nullptr;
+    else if constexpr (M == Move::Snooker) return half_step_snooker_vec<D, L, K, ITER, RAGGED>;
+    else if constexpr (M == Move::Mix) return half_step_mix_vec<D, L, K, ITER, RAGGED>;
     else if constexpr (M == Move::DE) return half_step_de_vec<D, L, K, ITER, RAGGED>;
     else return half_step_vec<D, L, K, ITER, P2P, RAGGED, T>;
 }
@@ -67,7 +73,7 @@ HalfStepFn vec_iter(int iter)
     }
 }
 
-// PART 0 .. 3 of density_part (see the top of this file); each part only names -- and therefore only compiles -- its own instantiations
+// PART 0 .. 5 of density_part (see the top of this file); each part only names -- and therefore only compiles -- its own instantiations
 template <class D, int L, int K, int PART>
 HalfStepFn vec_pick(int iter, bool ragged, bool f32)
 {
@@ -76,7 +82,9 @@ HalfStepFn vec_pick(int iter, bool ragged, bool f32)
         if (f32) return ragged ? vec_iter<D, L, K, false, true, float>(iter) : vec_iter<D, L, K, false, false, float>(iter);   // KMC_F32: single rows, one GPU
         return vec_iter<D, L, K, false, true, double>(iter);
     } else if constexpr (PART == 2) return ragged ? vec_iter<D, L, K, true, true, double>(iter) : vec_iter<D, L, K, true, false, double>(iter);
-    else return ragged ? vec_iter<D, L, K, false, true, double, Move::DE>(iter) : vec_iter<D, L, K, false, false, double, Move::DE>(iter);
+    else if constexpr (PART == 3) return ragged ? vec_iter<D, L, K, false, true, double, Move::DE>(iter) : vec_iter<D, L, K, false, false, double, Move::DE>(iter);
+    else if constexpr (PART == 4) return ragged ? vec_iter<D, L, K, false, true, double, Move::Snooker>(iter) : vec_iter<D, L, K, false, false, double, Move::Snooker>(iter);
+    else return ragged ? vec_iter<D, L, K, false, true, double, Move::Mix>(iter) : vec_iter<D, L, K, false, false, double, Move::Mix>(iter);
 }
 
 // geometries make_plan can pick: exact + ragged, single-GPU + P2P; the extra exact single-GPU ones
@@ -107,7 +115,9 @@ void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec
     if constexpr (PART == 0) *gen = half_step_generic<D, false, double>;
     else if constexpr (PART == 1) *gen = f32 ? half_step_generic<D, false, float> : half_step_generic<D, false, double>;
     else if constexpr (PART == 2) *gen = half_step_generic<D, true, double>;
-    else *gen = half_step_de_generic<D>;
+    else if constexpr (PART == 3) *gen = half_step_de_generic<D>;
+    else if constexpr (PART == 4) *gen = half_step_snooker_generic<D>;
+    else *gen = half_step_mix_generic<D>;
 }
 
 template <class D>

@@ -51,6 +51,27 @@ Base.@kwdef struct KmcConfig
     host_accepted::Ptr{Cvoid} = C_NULL                # KMC_HOST_DENSITY: accept outcomes per half-step (blobs), or NULL
     deal_rank::Int32 = 0                              # dealt sub-ensembles (multi-GPU, opt-in); deal_count = 0: off
     deal_count::Int32 = 0
+    snooker_gamma::Float64 = 0.0                      # KMC_MOVE_SNOOKER: 0 -> 1.7
+    mix_count::Int32 = 0                              # KMC_MOVE_MIX: 2 .. 4 members (the header's mix_move[4] ... mix_sigma[4], member by member)
+    mix_move0::Int32 = 0
+    mix_move1::Int32 = 0
+    mix_move2::Int32 = 0
+    mix_move3::Int32 = 0
+    mix_pad0_::Int32 = 0
+    mix_pad1_::Int32 = 0
+    mix_pad2_::Int32 = 0
+    mix_weight0::Float64 = 0.0
+    mix_weight1::Float64 = 0.0
+    mix_weight2::Float64 = 0.0
+    mix_weight3::Float64 = 0.0
+    mix_gamma0::Float64 = 0.0                         # a member's gamma0 (DE; 0 -> 2.38 / sqrt(2 ndim)) or gamma (snooker; 0 -> 1.7)
+    mix_gamma1::Float64 = 0.0
+    mix_gamma2::Float64 = 0.0
+    mix_gamma3::Float64 = 0.0
+    mix_sigma0::Float64 = 0.0                         # a DE member's sigma
+    mix_sigma1::Float64 = 0.0
+    mix_sigma2::Float64 = 0.0
+    mix_sigma3::Float64 = 0.0
     move::Int32 = 0                                   # KMC_MOVE_STRETCH = 0 (the reference's move), KMC_MOVE_DE = 1 (opt-in)
     move_pad_::Int32 = 0
     de_gamma0::Float64 = 0.0                          # KMC_MOVE_DE: 0 -> 2.38 / sqrt(2 ndim)
@@ -77,6 +98,7 @@ const KMC_STORE_LOGP = UInt32(1) << 1
 const KMC_CHAIN_BY_WALKER = UInt32(1) << 12     # chain delivered as [walker][sample][dim]: thetas[w][k] are contiguous
 const KMC_MOVE_STRETCH = Int32(0)              # kmc_config.move: the reference's stretch move (default)
 const KMC_MOVE_DE = Int32(1)                   # ... the opt-in differential-evolution move (one GPU, double rows)
+const KMC_MOVE_SNOOKER, KMC_MOVE_MIX = Int32(3), Int32(4)   # ... the opt-in DE snooker update (ndim >= 2), and a weighted mixture of DE / snooker members
 const KMC_STORE_BLOBS = UInt32(1) << 13         # a CDensity(body; nblob=m): the blob of every stored sample (src/samplers.jl:270, :117)
 
 last_error() = unsafe_string(ccall((:kmc_last_error, LIB), Cstring, ()))
@@ -226,22 +248,35 @@ end
 """
     emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter÷2, nthin=1, a_scale=2.0,
           use_progress_meter=true, hasblob=false, init_blobs, reduce_blob!, seed=rand(UInt64), device=0, dtype=:f64,
-          move=:stretch, de_gamma0=0.0, de_sigma=1e-5)
+          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7)
 
 Same meaning as KissMCMC.emcee (src/samplers.jl:188-197); returns
 `(thetas, accept_ratio, logdensities, blobs)` with `thetas[w][k]` (src/samplers.jl:292).
 `hasblob=true` needs a `pdf` that returns a blob: a host closure (`HostLogPdf(f; hasblob=true)`, blobs of any type, kept on
 the host) or a `CDensity(body; nblob=m)` (m doubles computed and carried on the device; `blobs[w][k]::Vector{Float64}`).
 `move=:de` selects the opt-in differential-evolution move (KMC_MOVE_DE; `de_gamma0=0` is 2.38/sqrt(2 ndim), `de_sigma` the
-relative jitter of gamma); `:stretch` is the reference's move with `a_scale`.
+relative jitter of gamma); `:stretch` is the reference's move with `a_scale`.  `move=:snooker` is the DE snooker update
+(KMC_MOVE_SNOOKER, `snooker_gamma`); `move=[(:de, 0.8), (:snooker, 0.2)]` a mixture of 2 to 4 weighted members (KMC_MOVE_MIX:
+one member per half-step, each with `de_gamma0` / `de_sigma` or `snooker_gamma`).
 """
 function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1, a_scale=2.0,
                use_progress_meter=true, hasblob=false,
                init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),      # init_output_vector :80-85
                reduce_blob! =(blobs, blob) -> push!(blobs, blob),                         # :196
                seed=rand(UInt64), device=0, dtype=:f64,     # dtype=:f32: float rows on the device (KMC_F32), built-in densities
-               move=:stretch, de_gamma0=0.0, de_sigma=1e-5)
-    move in (:stretch, :de) || error("move must be :stretch or :de")
+               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7)
+    mix = move isa AbstractVector ? collect(move) : Tuple{Symbol,Float64}[]
+    if move isa AbstractVector
+        2 <= length(mix) <= 4 || error("a move mixture has 2 to 4 (move, weight) pairs")
+        all(m -> m[1] in (:de, :snooker), mix) || error("mixture members are :de and :snooker (a :stretch member is not supported yet)")
+        all(m -> isfinite(m[2]) && m[2] > 0, mix) || error("mixture weights must be finite and > 0")
+    else
+        move in (:stretch, :de, :snooker) || error("move must be :stretch, :de, :snooker or a vector of (move, weight) pairs")
+    end
+    mix_id(i) = i <= length(mix) ? (mix[i][1] == :de ? KMC_MOVE_DE : KMC_MOVE_SNOOKER) : Int32(0)
+    mix_w(i) = i <= length(mix) ? Float64(mix[i][2]) : 0.0
+    mix_g(i) = i <= length(mix) ? (mix[i][1] == :de ? Float64(de_gamma0) : Float64(snooker_gamma)) : 0.0
+    mix_s(i) = i <= length(mix) && mix[i][1] == :de ? Float64(de_sigma) : 0.0
     device_blobs = hasblob && pdf isa ExprDensity && pdf.nblob > 0
     hasblob && !device_blobs && !(pdf isa HostLogPdf && pdf.hasblob) &&
         error("hasblob=true needs a pdf that returns a blob: HostLogPdf(f; hasblob=true) or CDensity(body; nblob=m)")
@@ -291,7 +326,12 @@ function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin
                             ngenerations=niter_walker, nburnin=nburnin_walker, nthin=nthin, a_scale=a_scale, seed=UInt64(seed),
                             flags=KMC_STORE_CHAIN | KMC_STORE_LOGP | flag, device=Int32(device), user_density=user_handle(pdf),
                             host_logpdf=host_fn, host_user=host_ctx, host_accepted=acc_fn,
-                            move=(move == :de ? KMC_MOVE_DE : KMC_MOVE_STRETCH), de_gamma0=Float64(de_gamma0), de_sigma=Float64(de_sigma)))
+                            move=(move isa AbstractVector ? KMC_MOVE_MIX : move == :de ? KMC_MOVE_DE : move == :snooker ? KMC_MOVE_SNOOKER : KMC_MOVE_STRETCH),
+                            de_gamma0=Float64(de_gamma0), de_sigma=Float64(de_sigma), snooker_gamma=Float64(snooker_gamma), mix_count=Int32(length(mix)),
+                            mix_move0=mix_id(1), mix_move1=mix_id(2), mix_move2=mix_id(3), mix_move3=mix_id(4),
+                            mix_weight0=mix_w(1), mix_weight1=mix_w(2), mix_weight2=mix_w(3), mix_weight3=mix_w(4),
+                            mix_gamma0=mix_g(1), mix_gamma1=mix_g(2), mix_gamma2=mix_g(3), mix_gamma3=mix_g(4),
+                            mix_sigma0=mix_s(1), mix_sigma1=mix_s(2), mix_sigma2=mix_s(3), mix_sigma3=mix_s(4)))
         st = GC.@preserve pdf theta chain clogp acc bl ccall((:kmc_emcee_run, LIB), Cint,
                                                        (Ref{KmcConfig}, Ptr{Float64}, Ref{KmcOutputs}), cfg, theta, out)
         (st == 9 && by_walker && occursin("KMC_CHAIN_BY_WALKER", last_error())) || break

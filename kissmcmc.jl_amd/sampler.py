@@ -79,7 +79,7 @@ class Sampler:
         cfg.device = int(device)
         cfg.shard_rank, cfg.shard_count = int(shard_rank), int(shard_count)
         cfg.deal_rank, cfg.deal_count = int(deal_rank), int(deal_count)   # dealt sub-ensembles (distributed.DealtEmcee)
-        apply_move(move, cfg)                  # None: the stretch move; DEMove: differential evolution (opt-in)
+        apply_move(move, cfg)                  # None: the stretch move; DEMove, DESnookerMove or a weighted list of them (opt-in)
         self.move = move
         cfg.user_density = pdf.user_handle     # runtime-compiled density (ExprDensity) or None
         cb = getattr(pdf, "c_callback", None)  # host-evaluated density (HostLogPdf) or None
