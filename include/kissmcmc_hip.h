@@ -176,6 +176,7 @@ enum {
     KMC_MOVE_MIX     = 4
 };
 #define KMC_MIX_MAX 4
+#define KMC_TEMPS_MAX 64
 
 #define KMC_P2P_HANDLE_BYTES 128
 #define KMC_RCCL_ID_BYTES 128
@@ -211,6 +212,10 @@ typedef struct kmc_config {
     double   mix_weight[KMC_MIX_MAX]; /* ... its weight: finite, > 0; normalised by the library */
     double   mix_gamma[KMC_MIX_MAX];  /* ... its gamma0 (DE; 0 -> 2.38 / sqrt(2 ndim)) or gamma (snooker; 0 -> 1.7) */
     double   mix_sigma[KMC_MIX_MAX];  /* ... its sigma (DE members; 0 for snooker members) */
+    /* PARALLEL TEMPERING (opt-in; see the comment above kmc_sampler_get_rung_state).  Zeroed: off. */
+    const double* betas;    /* [ntemps] inverse temperatures, copied at creation: betas[0] == 1, strictly decreasing, finite, > 0 */
+    int32_t  ntemps;        /* rungs of the ladder: 0 or 1 = off, else 2 .. KMC_TEMPS_MAX */
+    int32_t  swap_every;    /* generations between swap sweeps; 0 = never */
     int32_t  move;          /* KMC_MOVE_STRETCH (0, the reference's move), KMC_MOVE_DE, KMC_MOVE_SNOOKER or KMC_MOVE_MIX */
     int32_t  move_pad_;
     double   de_gamma0;     /* KMC_MOVE_DE: gamma0 of the proposal; 0 -> 2.38 / sqrt(2 ndim) */
@@ -472,6 +477,27 @@ void*       kmc_sampler_device_ptr(kmc_sampler* s, int which);
 kmc_status  kmc_sampler_get_positions(kmc_sampler* s, double* host /* [nwalkers][ndim] */);
 kmc_status  kmc_sampler_get_logp(kmc_sampler* s, double* host /* [nwalkers] */);
 kmc_status  kmc_sampler_get_naccept(kmc_sampler* s, int64_t* host /* [nwalkers] */);
+
+/* Parallel tempering (kmc_config.ntemps >= 2).  The sampler holds ntemps ensembles of nwalkers walkers; rung t
+ * samples exp(betas[t] * logpdf) with the configured move, partners from the complementary half of the SAME rung, its draws keyed by
+ * the walker word t * nwalkers + w (rung 0 draws what the untempered sampler draws).  Stored log-densities are UNTEMPERED on every
+ * rung.  After generation g, when swap_every > 0 and (g + 1) % swap_every == 0, sweep n = (g + 1) / swap_every - 1 exchanges walker w
+ * of rung t with walker w of rung t + 1 for every t == n (mod 2), when (beta_t - beta_{t+1}) (logp_{t+1,w} - logp_{t,w}) >= log u,
+ * u from Philox key {seed_lo ^ 0x54454D50 ("TEMP"), seed_hi}, counter {n_lo, n_hi, w, t}.  Every existing read-out (positions,
+ * log-pdfs, counters, chain, moments) is rung 0's; a stored sample of generation g is the state BEFORE that generation's sweep.
+ * One GPU, double rows, two launches per generation (+ the sweep): KMC_ERR_UNSUPPORTED with KMC_HOST_DENSITY, KMC_DATA_DENSITY,
+ * blobs, KMC_F32, KMC_ISLANDS, KMC_P2P, sharding, dealt sub-ensembles, kmc_sampler_init_ball, kmc_sampler_bind_positions and
+ * kmc_sampler_rccl_init.  kmc_sampler_set_positions copies the ensemble to every rung.
+ *   kmc_sampler_get_rung_state  any pointer may be NULL: positions [ntemps][nwalkers][ndim], log-pdfs and acceptance counters
+ *                               [ntemps][nwalkers], logp_sum [ntemps] = the sum over stored generations and walkers of the untempered
+ *                               log-density of the stored state
+ *   kmc_sampler_set_rung_state  all rungs at once: logp NULL = evaluate; naccept, nswap, logp_sum NULL = zero; generation > 0 is a
+ *                               checkpoint restore (as kmc_sampler_set_state, which a tempered sampler refuses)
+ *   kmc_sampler_get_swaps       accepted exchanges per neighbouring pair [ntemps - 1], counted from the end of burn-in */
+kmc_status  kmc_sampler_get_rung_state(kmc_sampler* s, double* pos_host, double* logp_host, int64_t* naccept_host, double* logp_sum_host);
+kmc_status  kmc_sampler_set_rung_state(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host,
+                                       const uint64_t* nswap_host, const double* logp_sum_host, int64_t generation);
+kmc_status  kmc_sampler_get_swaps(kmc_sampler* s, uint64_t* nswap_host);
 kmc_status  kmc_sampler_get_accept_ratio(kmc_sampler* s, double* host /* [nwalkers] */);
 kmc_status  kmc_sampler_get_moments(kmc_sampler* s, double* sum, double* sumsq /* [ndim] */, int64_t* n);
 /* Chain of this shard: [nsamples][nlocal][ndim] and [nsamples][nlocal]; nlocal = nwalkers /

@@ -32,6 +32,7 @@ STORE_BLOBS = 8192
 # kmc_config.move
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_MIX = 0, 1, 3, 4
 MIX_MAX = 4
+TEMPS_MAX = 64  # parallel tempering: most rungs of a ladder (kmc_config.ntemps)
 P2P_HANDLE_BYTES = 128
 RCCL_ID_BYTES = 128
 
@@ -51,6 +52,7 @@ SYMBOLS = [
     "kmc_sampler_launch_mode", "kmc_updated_budget", "kmc_set_updated_budget_mb", "kmc_debug_accept_terms",
     "kmc_user_density_create_body_blob", "kmc_user_density_nblob", "kmc_logpdf_blob_eval_host", "kmc_sampler_get_blobs",
     "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault", "kmc_data_density_create",
+    "kmc_sampler_get_rung_state", "kmc_sampler_set_rung_state", "kmc_sampler_get_swaps",
 ]
 
 
@@ -86,6 +88,9 @@ class Config(C.Structure):
         ("mix_weight0", C.c_double), ("mix_weight1", C.c_double), ("mix_weight2", C.c_double), ("mix_weight3", C.c_double),
         ("mix_gamma0", C.c_double), ("mix_gamma1", C.c_double), ("mix_gamma2", C.c_double), ("mix_gamma3", C.c_double),
         ("mix_sigma0", C.c_double), ("mix_sigma1", C.c_double), ("mix_sigma2", C.c_double), ("mix_sigma3", C.c_double),
+        ("betas", C.c_void_p),          # parallel tempering: const double* [ntemps], copied at creation
+        ("ntemps", C.c_int32),
+        ("swap_every", C.c_int32),
         ("move", C.c_int32),
         ("move_pad_", C.c_int32),
         ("de_gamma0", C.c_double),
@@ -204,6 +209,9 @@ def lib() -> C.CDLL:
     L.kmc_sampler_set_positions.argtypes = [vp, dp]
     L.kmc_sampler_init_ball.argtypes = [vp, dp, dp, C.c_uint64, C.c_int, C.c_int]
     L.kmc_sampler_set_state.argtypes = [vp, dp, dp, ip, C.c_int64]
+    L.kmc_sampler_get_rung_state.argtypes = [vp, dp, dp, ip, dp]
+    L.kmc_sampler_set_rung_state.argtypes = [vp, dp, dp, ip, C.POINTER(C.c_uint64), dp, C.c_int64]
+    L.kmc_sampler_get_swaps.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.kmc_sampler_run.argtypes = [vp, C.c_int64]
     L.kmc_sampler_half_step.argtypes = [vp, C.c_int]
     L.kmc_sampler_sync.argtypes = [vp]

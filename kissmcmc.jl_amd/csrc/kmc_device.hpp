@@ -264,6 +264,22 @@ struct TreeStack2 {                      // two sums at once
     }
 };
 
+// Parallel tempering (kmc_config.ntemps >= 2): rung t samples exp(beta_t logpdf), the stored log-densities stay
+// untempered.  The accept tests with beta, each operation rounded on its own; with beta == 1.0 they are the tests above bit for bit.
+template <Move M>
+__device__ __forceinline__ bool accept_test_beta(const Draw& d, double p1, double p0, double beta)
+{
+    if constexpr (M == Move::DE) return (beta * p1 - beta * p0) >= d.lu;
+    else return ((d.t1 + beta * p1) - beta * p0) >= d.lu;          // stretch: t1 = (N-1) log z; snooker: (N-1) log|1 + s|
+}
+// The swap stream: key {seed_lo ^ "TEMP", seed_hi}, counter {sweep_lo, sweep_hi, w, t}; log u of the exchange of walker w between
+// rungs t and t + 1 in sweep n, u built from w2, w3 like every accept uniform.
+constexpr uint32_t kTemperKey = 0x54454D50u;   // "TEMP"
+__device__ __forceinline__ double temper_swap_logu(uint32_t seed_lo, uint32_t seed_hi, uint64_t sweep, uint32_t w, uint32_t t)
+{
+    return log_pos_normal(de_accept_u(philox4x32_10((uint32_t)sweep, (uint32_t)(sweep >> 32), w, t, seed_lo ^ kTemperKey, seed_hi)));
+}
+
 // Mixtures (KMC_MOVE_MIX): every half-step uses ONE member for all its walkers, chosen by u_mix = (w0 + 1/2) 2^-32 from Philox key
 // {seed_lo ^ "MIXV", seed_hi}, counter {step_lo, step_hi, 0, 0}: the first member whose cumulative weight exceeds u_mix.  The table
 // lives in device memory (kmc_launch.hip: make_args); cum[i] of the last member and beyond is 2.0, so the last member catches rounding.

@@ -95,6 +95,9 @@ inline double de_gamma0_of(double gamma0, int64_t ndim) { return gamma0 > 0.0 ? 
 inline double snooker_gamma_of(double gamma) { return gamma > 0.0 ? gamma : 1.7; }
 // a move with its own stream and the two-launch kernels only (DE, snooker, their mixtures)
 inline bool own_stream_move(const kmc_config& c) { return c.move != KMC_MOVE_STRETCH; }
+// parallel tempering (kmc_config.ntemps >= 2): a ladder of ensembles in one launch, the two-launch kernels only
+inline bool tempered(const kmc_config& c) { return c.ntemps >= 2; }
+inline bool two_launch_only(const kmc_config& c) { return own_stream_move(c) || tempered(c); }
 inline const char* move_name(int move) { return move == KMC_MOVE_DE ? "KMC_MOVE_DE" : move == KMC_MOVE_SNOOKER ? "KMC_MOVE_SNOOKER" : move == KMC_MOVE_MIX ? "KMC_MOVE_MIX" : "KMC_MOVE_STRETCH"; }
 // KMC_MOVE_MIX: the table the mixture kernels read -- weights normalised in double, in member order (weights_out[i], optional), cumulated
 // in the same order; the last member's cumulative weight and every one beyond is 2.0 (it catches rounding)
@@ -120,6 +123,8 @@ inline kmc::MixTable mix_table_of(const kmc_config& c, double* weights_out = nul
 }
 // the kernels of KMC_MOVE_DE (PART 3), KMC_MOVE_SNOOKER (4) and KMC_MOVE_MIX (5)
 bool lookup_move(int move, int density, int L, int K, int iter, bool ragged, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
+// ... and their tempered forms (kmc_tables.hpp: temper_part), for any of the four moves
+bool lookup_temper(int move, int density, int L, int K, int iter, bool ragged, kmc::HalfStepFn* vec, kmc::HalfStepFn* gen);
 kmc::LogpdfFn logpdf_fn(int density);
 kmc_status check_ndim(int density, int64_t ndim);
 kmc_status digest_params(const kmc_config& c, kmc::DensityParams* dp);
@@ -180,6 +185,15 @@ hipError_t launch_module(hipFunction_t f, unsigned grid, unsigned tpb, hipStream
     size_t size = sizeof(Args);
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     return hipModuleLaunchKernel(f, grid, 1, 1, tpb, 1, 1, lds_bytes, st, nullptr, extra);
+}
+// ... with a second grid dimension (the rungs of a tempered sampler)
+template <class Args>
+hipError_t launch_module_y(hipFunction_t f, unsigned grid, unsigned grid_y, unsigned tpb, hipStream_t st, const Args& args, unsigned lds_bytes = 0)
+{
+    Args copy = args;
+    size_t size = sizeof(Args);
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+    return hipModuleLaunchKernel(f, grid, grid_y, 1, tpb, 1, 1, lds_bytes, st, nullptr, extra);
 }
 
 // Small device allocations, cached per device (kmc_diag.hip).  A sampler of the reference's own size lives for a millisecond or

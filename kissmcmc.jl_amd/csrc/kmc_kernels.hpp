@@ -436,9 +436,15 @@ static __device__ unsigned long long g_probe[2][8192][8];
 // M = Move::Snooker: block 2 and THREE partner rows (xo: z, then x - z, then the proposal; xk: z1; xl: z2), all loaded in front of
 // block 3 (the accept uniform); the two sums over the row in the fixed order T (kmc_device.hpp); otherwise as DE.
 // over != nullptr (the mixture kernels): c0 and c1 of the half-step's member instead of the argument struct's.
-template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double, Move M = Move::Stretch>
+// TEMPER (parallel tempering): the rung is blockIdx.y.  The caller has moved f.pos and f.logp to the rung's rows and
+// per-walker block (temper_front); here the draws take the walker word t nwalkers + w, the accept test takes beta_t (one scalar load from
+// the table behind HalfStepArgs::peer_pos[1]) and only rung 0 stores samples and credits moments.
+template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double, Move M = Move::Stretch, bool TEMPER = false>
 __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const HalfStepArgs& a, const DrawConsts* over = nullptr)
 {
+    static_assert(!TEMPER || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "tempering: one GPU, double rows, no blobs (kmc_validate)");
+    const uint32_t rung = TEMPER ? (uint32_t)blockIdx.y : 0u;
+    const uint32_t rung_w0 = TEMPER ? rung * (2u * f.nhalf) : 0u;       // added to the walker word of every draw
     static_assert(M != Move::Mix, "a mixture picks its member in front of the body (half_step_mix_vec_body)");
     static_assert(L >= 1 && L <= 64 && (L & (L - 1)) == 0, "L must be a power of two <= 64");
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
@@ -547,14 +553,14 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     uint32_t partnerK = 0u;                                             // DE: the second partner
     uint32_t partnerL = 0u;                                             // snooker: the third
     if constexpr (kSnk) {                                               // block 2: the three partners
-        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 2u);
+        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc + rung_w0, 2u);
         snooker_partners(bits, f.nhalf, &partnerA, &partnerK, &partnerL);
     } else if constexpr (kDE) {                                                // block 0: both partners and the accept uniform
-        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 0u);
+        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc + rung_w0, 0u);
         partnerA = __umulhi(bits.x, f.nhalf);
         partnerK = de_partner_k(bits.y, f.nhalf, partnerA);
     } else if (!fresh) {
-        bits = draw_bits(dcf, step + 2ull * (uint64_t)jq, (uint64_t)f.gw0 + (uint64_t)iAc);   // RNG keyed by the GLOBAL walker index
+        bits = draw_bits(dcf, step + 2ull * (uint64_t)jq, (uint64_t)f.gw0 + (uint64_t)iAc + (uint64_t)rung_w0);   // RNG keyed by the GLOBAL walker index
         partnerA = draw_partner(dcf, bits);
     }
 #if KMC_PROBE_PINS
@@ -645,14 +651,16 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     SchedEntry sch = sch_t;
     if (eager_late != 0) sch = a.sched_inline;
     const bool count  = (sch.flags & kCount) != 0;
-    const bool sample = (sch.flags & kSample) != 0;
+    const bool sample = (sch.flags & kSample) != 0 && (!TEMPER || rung == 0u);      // (the chain is rung 0's)
+    double beta = 1.0;
+    if constexpr (TEMPER) beta = reinterpret_cast<const double*>(a.peer_pos[1])[rung];
     DrawConsts dc = a.dc;                                               // seed and nhalf from the front parameters (DE: gamma0 in c0, sigma in c1)
     dc.seed_lo = f.seed_lo; dc.seed_hi = f.seed_hi; dc.nhalf = f.nhalf;
     if (over != nullptr) { dc.c0 = over->c0; dc.c1 = over->c1; }       // (a mixture's member; folds away everywhere else)
     // Streaming moments are sojourn-weighted: a walker's value is credited, times the number of
     // samples it stood for, when it is replaced (and by flush_moments_vec at read-out).  Only waves
     // with an accepted move touch their accumulators -- at low acceptance (large ndim) almost none.
-    const bool do_mom = count && a.msum != nullptr;
+    const bool do_mom = count && a.msum != nullptr && (!TEMPER || rung == 0u);
     // small rows: nearly every wave has an accepted move, so fetch its accumulator slots now and
     // keep that latency off the kernel's tail; large rows: fetch only when needed
     constexpr bool kPrefetchAcc = K <= 2 && L != 64;                   // L == 64: the moment ring instead (below)
@@ -693,11 +701,11 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     dr.partner = partnerA; dr.z = e1.x; dr.t1 = e0.x; dr.lu = e0.y;
     double ua = 0.5;
     if constexpr (kSnk) {                                               // block 3: the accept uniform; z = gamma, t1 once s is known
-        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 3u);
+        bits = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc + rung_w0, 3u);
         dr.z = dc.c0;
         dr.t1 = 0.0;
     } else if constexpr (kDE) {                                         // block 1: the jitter of gamma; z = gamma, t1 unused
-        const U4 b1 = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc, 1u);
+        const U4 b1 = de_bits(f.seed_lo, f.seed_hi, step, f.gw0 + (uint32_t)iAc + rung_w0, 1u);
         dr.z = de_gamma(dc, b1.x);
         dr.t1 = 0.0;
     } else if (!fresh) {                                                // the arithmetic of draw_finish, in two parts
@@ -823,7 +831,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     // ---- accept test in the scalar layout ---------------------------------------------------
     bool snk_ok = true;
     if constexpr (kSnk) snk_ok = snooker_hastings(dr, dc.nm1, mys);    // (ndim - 1) log|1 + s| + p1 - p0 >= log u
-    const bool acc = validA && snk_ok && (kDE ? de_accept_test(dr, myp1, p0) : accept_test(dr, myp1, p0));   // :260
+    const bool acc = validA && snk_ok && (TEMPER ? accept_test_beta<M>(dr, myp1, p0, beta) : kDE ? de_accept_test(dr, myp1, p0) : accept_test(dr, myp1, p0));   // :260
     const unsigned long long accmask = __ballot(acc);
     if (acc) {
         store_wt(&logp_p[rowA], myp1);                                  // :262
@@ -974,18 +982,37 @@ __device__ __forceinline__ bool mix_pick(const HalfStepArgs& a, uint32_t seed_lo
     const int mv = i == 0 ? t->move[0] : i == 1 ? t->move[1] : i == 2 ? t->move[2] : t->move[3];
     return mv == kMoveIdSnooker;
 }
-template <class Dens, int L, int K, int ITER, bool RAGGED>
+template <class Dens, int L, int K, int ITER, bool RAGGED, bool TEMPER = false>
 __device__ __forceinline__ void half_step_mix_vec_body(const HalfStepFront& f, const HalfStepArgs& a)
 {
     const uint64_t step = f.sched == nullptr ? (uint64_t)f.step : 2ull * (uint64_t)schedule_entry(f).gen + (uint64_t)f.half();
     DrawConsts dc;
-    if (mix_pick(a, f.seed_lo, f.seed_hi, step, &dc)) half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::Snooker>(f, a, &dc);
-    else half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::DE>(f, a, &dc);
+    if (mix_pick(a, f.seed_lo, f.seed_hi, step, &dc)) half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::Snooker, TEMPER>(f, a, &dc);
+    else half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, Move::DE, TEMPER>(f, a, &dc);
 }
 template <class Dens, int L, int K, int ITER, bool RAGGED>
 __global__ __launch_bounds__(vec_tpb(L)) void half_step_mix_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_mix_vec_body<Dens, L, K, ITER, RAGGED>(KMC_FRONT_PACK, a);
+}
+// Parallel tempering: ONE launch per half-step for the whole ladder, the rung as the grid's second dimension.  Rung t's rows are
+// pos[t][nwalkers][ld]; its per-walker block {logp[nwalkers], naccept[nwalkers], klast[nwalkers]} follows rung t - 1's (16 nwalkers bytes
+// each), so rung 0's state lies where an untempered sampler's does.  (A ragged kernel's ndim tag in the upper bits of f.logp moves along.)
+template <int L, int K, bool RAGGED>
+__device__ __forceinline__ HalfStepFront temper_front(HalfStepFront f)
+{
+    const uint64_t t = blockIdx.y, nw = 2ull * f.nhalf;
+    const uint64_t ld = RAGGED ? (((reinterpret_cast<uint64_t>(f.logp) >> 48) + 1ull) & ~1ull) : (uint64_t)(2 * L * K);
+    f.pos += t * nw * ld;
+    f.logp += t * nw * 2ull;
+    return f;
+}
+template <class Dens, int L, int K, int ITER, bool RAGGED, Move M>
+__global__ __launch_bounds__(vec_tpb(L)) void half_step_temper_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    const HalfStepFront f = temper_front<L, K, RAGGED>(KMC_FRONT_PACK);
+    if constexpr (M == Move::Mix) half_step_mix_vec_body<Dens, L, K, ITER, RAGGED, true>(f, a);
+    else half_step_vec_body<Dens, L, K, ITER, false, RAGGED, double, M, true>(f, a);
 }
 
 // Moment read-out: credit every walker's current value with the samples it has stood for since it
@@ -1045,9 +1072,12 @@ __global__ __launch_bounds__(vec_tpb(L)) void flush_moments_vec(const FlushArgs 
 // ------------------------------------------------------------------------------------------
 // Generic kernel: one walker per lane, any ndim.
 // ------------------------------------------------------------------------------------------
-template <class Dens, bool P2P, class T = double, Move M = Move::Stretch>
+template <class Dens, bool P2P, class T = double, Move M = Move::Stretch, bool TEMPER = false>
 __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, const HalfStepArgs& a, const DrawConsts* over = nullptr)
 {
+    static_assert(!TEMPER || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0 && !HostEvalTrait<Dens>::value), "tempering: one GPU, double rows, device densities, no blobs");
+    // (TEMPER: `a` is the rung's own copy of the arguments -- temper_args -- with beta behind it)
+    const bool rung0 = !TEMPER || blockIdx.y == 0u;
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
     static_assert(M != Move::Mix, "a mixture picks its member in front of the body (half_step_mix_generic_body)");
     constexpr bool kDE = M == Move::DE;
@@ -1061,7 +1091,7 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     if (tid >= a.n_active) return;
     const int ndim = a.ndim;
     const bool count  = (sch.flags & kCount) != 0;
-    const bool sample = (sch.flags & kSample) != 0;
+    const bool sample = (sch.flags & kSample) != 0 && rung0;
     const int64_t gw = a.own_row0 + tid;                                // row in pos / index in logp, naccept
     uint32_t partner_k = 0u;                                            // DE: the second partner
     uint32_t partner_l = 0u;                                            // snooker: the third
@@ -1132,7 +1162,9 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     for (int d = 0; d < ndim; ++d) Dens::seq_add(q, y_at(d), d, a.dp);
     double p1 = Dens::seq_finish(q, ndim, a.dp);                         // :257
     if constexpr (kHost) p1 = a.p1_in[tid];
-    const bool acc = snk_ok && (kDE ? de_accept_test(dr, p1, p0) : accept_test(dr, p1, p0));   // :260
+    bool acc;
+    if constexpr (TEMPER) acc = snk_ok && accept_test_beta<M>(dr, p1, p0, reinterpret_cast<const double*>(a.peer_pos[1])[blockIdx.y]);
+    else acc = snk_ok && (kDE ? de_accept_test(dr, p1, p0) : accept_test(dr, p1, p0));   // :260
     if constexpr (kHost) { if (a.acc_out != nullptr) a.acc_out[tid] = acc ? 1 : 0; }
 
     const bool do_mom = sample && a.msum != nullptr;
@@ -1189,18 +1221,36 @@ __global__ __launch_bounds__(256) void half_step_snooker_generic(KMC_FRONT_PARAM
 {
     half_step_generic_body<Dens, false, double, Move::Snooker>(KMC_FRONT_PACK, a);
 }
-template <class Dens>
+template <class Dens, bool TEMPER = false>
 __device__ __forceinline__ void half_step_mix_generic_body(const HalfStepFront& f, const HalfStepArgs& a)
 {
     const uint64_t step = 2ull * (uint64_t)schedule_of(f, a).gen + (uint64_t)a.half;
     DrawConsts dc;
-    if (mix_pick(a, a.dc.seed_lo, a.dc.seed_hi, step, &dc)) half_step_generic_body<Dens, false, double, Move::Snooker>(f, a, &dc);
-    else half_step_generic_body<Dens, false, double, Move::DE>(f, a, &dc);
+    if (mix_pick(a, a.dc.seed_lo, a.dc.seed_hi, step, &dc)) half_step_generic_body<Dens, false, double, Move::Snooker, TEMPER>(f, a, &dc);
+    else half_step_generic_body<Dens, false, double, Move::DE, TEMPER>(f, a, &dc);
 }
 template <class Dens>
 __global__ __launch_bounds__(256) void half_step_mix_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_mix_generic_body<Dens>(KMC_FRONT_PACK, a);
+}
+// Parallel tempering, one walker per lane: the rung's own copy of the arguments (rows, per-walker block, walker word of the draws).
+__device__ __forceinline__ HalfStepArgs temper_args(const HalfStepArgs& a)
+{
+    HalfStepArgs b = a;
+    const int64_t t = blockIdx.y, nw = 2 * (int64_t)a.dc.nhalf;
+    b.pos = a.pos + t * nw * a.ld;
+    b.logp = a.logp + t * nw * 2;
+    b.naccept = a.naccept + t * nw * 4;
+    b.gw0 = a.gw0 + t * nw;
+    return b;
+}
+template <class Dens, Move M>
+__global__ __launch_bounds__(256) void half_step_temper_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    const HalfStepArgs b = temper_args(a);
+    if constexpr (M == Move::Mix) half_step_mix_generic_body<Dens, true>(KMC_FRONT_PACK, b);
+    else half_step_generic_body<Dens, false, double, M, true>(KMC_FRONT_PACK, b);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1549,6 +1599,21 @@ struct SweepArgs {
     int32_t        K, depth;
 };
 
+// Parallel tempering: what follows the two half-steps of a generation that stores a sample or ends in a swap sweep.
+struct TemperSweepArgs {
+    double*             pos;          // [ntemps][nwalkers][ld]
+    double*             logp;         // rung 0's per-walker block {logp, naccept, klast}; rung t's starts 2 t nwalkers doubles further
+    const double*       betas;        // [ntemps]
+    unsigned long long* nswap;        // [ntemps - 1] accepted exchanges per pair, counted like naccept
+    double*             logp_sum;     // [ntemps] sum of the stored states' untempered log-densities
+    double*             msum;         // [2][ld] moments credited when a walker of rung 0 is exchanged (KMC_MOMENTS), or nullptr
+    const SchedEntry*   sched_table;
+    SchedEntry          sched_inline; // used when sched_index < 0 (eager launches)
+    int32_t             sched_index;
+    int32_t             ntemps, nwalkers, ld, swap_every;
+    uint32_t            seed_lo, seed_hi;
+};
+
 // Non-template kernels of the host driver: each group is defined once, in the translation unit that launches it.
 #ifdef KMC_DEFINE_LAUNCH_KERNELS   // kmc_launch.hip
 // one 64-lane workgroup per (wave of the half-step grid, chunk k): sum += x w, sumsq += x^2 w over the wave's posted rows
@@ -1577,6 +1642,98 @@ __global__ __launch_bounds__(256) void moments_swept(const uint32_t* cnt, uint32
 {
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (w < nwaves) swept[w] = cnt[w];
+}
+
+// sum over the workgroup's 256 threads, valid in thread 0
+__device__ __forceinline__ double block_sum256(double v, double* lds)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    __syncthreads();                                   // (lds may still be read from an earlier call)
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
+}
+// Grid (ceil(nwalkers / 256), ntemps), 256 threads: thread w of block row t owns walker w of rung t -- and, in a sweep whose pairs start
+// at t's parity, walker w of rung t + 1 as well (that rung's own block row leaves at once), so nobody reads a value another thread
+// exchanges.  First the stored state's log-densities are added into logp_sum (block reduction, one double atomic add per block and rung);
+// then the lane decides its pair's exchange and swaps the two log-densities, and the wave swaps the rows of its accepted pairs:
+// 64 walkers x ld / 2 chunks of 16 bytes, consecutive lanes on consecutive chunks, both chunks of a pair read before either is written.
+// naccept stays with the slot.  Moments (rung 0 only) are sojourn-weighted: the walker that leaves rung 0 is credited here.
+__global__ __launch_bounds__(256) void temper_sweep(const TemperSweepArgs a)
+{
+    __shared__ double red[4];
+    const SchedEntry sch = a.sched_index >= 0 ? a.sched_table[a.sched_index] : a.sched_inline;
+    const bool stored = (sch.flags & kSample) != 0;
+    const int64_t g1 = sch.gen + 1;
+    const bool sweep = a.swap_every > 0 && g1 % a.swap_every == 0;
+    if (!stored && !sweep) return;
+    const uint64_t n = sweep ? (uint64_t)(g1 / a.swap_every - 1) : 0ull;
+    const int par = (int)(n & 1ull);
+    const int t = (int)blockIdx.y;
+    if (sweep && t >= 1 && ((t - 1) & 1) == par) return;                 // the upper rung of a pair: rung t - 1's block row has it
+    const bool lower = sweep && (t & 1) == par && t + 1 < a.ntemps;
+    const int64_t nw = a.nwalkers;
+    const int w = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool valid = w < a.nwalkers;
+    double* const lp_lo = a.logp + 2 * (int64_t)t * nw;
+    double* const lp_hi = lp_lo + 2 * nw;
+    const double p_lo = valid ? lp_lo[w] : 0.0;
+    const double p_hi = (lower && valid) ? lp_hi[w] : 0.0;
+    if (stored) {
+        const double s_lo = block_sum256(p_lo, red);
+        if (threadIdx.x == 0) atomicAdd(&a.logp_sum[t], s_lo);
+        if (lower) {
+            const double s_hi = block_sum256(p_hi, red);
+            if (threadIdx.x == 0) atomicAdd(&a.logp_sum[t + 1], s_hi);
+        }
+    }
+    if (!lower) return;
+    bool acc = false;
+    if (valid) {
+        const double lu = temper_swap_logu(a.seed_lo, a.seed_hi, n, (uint32_t)w, (uint32_t)t);
+        acc = (a.betas[t] - a.betas[t + 1]) * (p_hi - p_lo) >= lu;
+    }
+    uint32_t wgt = 0u;                                                   // samples the walker leaving rung 0 stood for
+    if (acc) {
+        lp_lo[w] = p_hi;
+        lp_hi[w] = p_lo;
+        if (t == 0 && a.msum != nullptr) {
+            uint32_t* const klast = reinterpret_cast<uint32_t*>(lp_lo + nw) + nw;
+            const uint32_t nb1 = sch.nbefore + (stored ? 1u : 0u);      // samples taken by the generations up to this one
+            wgt = nb1 - klast[w];
+            klast[w] = nb1;
+        }
+    }
+    const unsigned long long mask = __ballot(acc);
+    if ((sch.flags & kCount) != 0) {
+        const double c = block_sum256((threadIdx.x & 63) == 0 ? (double)__popcll(mask) : 0.0, red);
+        if (threadIdx.x == 0 && c != 0.0) atomicAdd(&a.nswap[t], (unsigned long long)c);
+    }
+    if (mask == 0ull) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t wbase = (int64_t)blockIdx.x * 256 + (int64_t)(threadIdx.x & ~63u);
+    const int nchunk = a.ld >> 1;
+    double2* const r_lo = reinterpret_cast<double2*>(a.pos + ((int64_t)t * nw + wbase) * a.ld);
+    double2* const r_hi = reinterpret_cast<double2*>(a.pos + ((int64_t)(t + 1) * nw + wbase) * a.ld);
+    const bool credit = t == 0 && a.msum != nullptr;
+    for (int idx = lane; idx < 64 * nchunk; idx += 64) {                 // (the same trip count in every lane)
+        const int wl = idx / nchunk;
+        const uint32_t wq = credit ? (uint32_t)__shfl((int)wgt, wl) : 0u;
+        if ((mask >> wl) & 1ull) {
+            const double2 x = r_lo[idx], y = r_hi[idx];
+            r_lo[idx] = y;
+            r_hi[idx] = x;
+            if (wq != 0u) {
+                const int d = 2 * (idx - wl * nchunk);
+                const double wd = (double)wq;
+                atomicAdd(&a.msum[d], x.x * wd);
+                atomicAdd(&a.msum[d + 1], x.y * wd);
+                atomicAdd(&a.msum[a.ld + d], (x.x * x.x) * wd);
+                atomicAdd(&a.msum[a.ld + d + 1], (x.y * x.y) * wd);
+            }
+        }
+    }
 }
 
 __global__ void p2p_signal(const SignalArgs a)

@@ -92,6 +92,7 @@ HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t 
         a.dc.c1 = 0.0;
         a.peer_pos[0] = reinterpret_cast<double*>(s->d_mix);
     }
+    if (s->temper) a.peer_pos[1] = s->d_betas;                            // the tempered kernels read beta_t there (one GPU: no peers)
     a.dp = s->dp;
     a.chain = s->d_chain;
     a.chain_logp = s->d_chain_logp;
@@ -139,10 +140,48 @@ static_assert(offsetof(HalfStepLaunch, a) == 56 && offsetof(HalfStepFront, ring_
 
 hipError_t launch_half_kernel(const kmc_sampler* s, const HalfStepArgs& a);
 
+// Parallel tempering: the node behind a generation's second half-step -- the stored state's log-densities into logp_sum, then the swap
+// sweep (kmc_kernels.hpp: temper_sweep).  Which generations store or sweep changes from one to the next, so the kernel reads that from
+// its schedule entry like the half-step kernels do: inside a graph it is a node of every generation and leaves at once when there is
+// nothing to do; launched eagerly it is launched only where it has work.
+hipError_t launch_temper_sweep(const kmc_sampler* s, const HalfStepArgs& a, bool* launched)
+{
+    *launched = false;
+    if (a.sched_index < 0) {
+        const bool stored = (a.sched_inline.flags & kSample) != 0;
+        const bool sweep = s->cfg.swap_every > 0 && (a.sched_inline.gen + 1) % s->cfg.swap_every == 0;
+        if (!stored && !sweep) return hipSuccess;
+    }
+    TemperSweepArgs t{};
+    t.pos = s->d_pos;
+    t.logp = s->d_logp;
+    t.betas = s->d_betas;
+    t.nswap = s->d_nswap;
+    t.logp_sum = s->d_rung_sum;
+    t.msum = (s->d_msum && s->plan.vec) ? s->d_tsum : nullptr;            // (the one-walker-per-lane kernel adds every sample as it is: nothing to credit)
+    t.sched_table = a.sched_table;
+    t.sched_inline = a.sched_inline;
+    t.sched_index = a.sched_index;
+    t.ntemps = s->ntemps;
+    t.nwalkers = (int32_t)s->nrows;
+    t.ld = (int32_t)s->ld;
+    t.swap_every = s->cfg.swap_every;
+    t.seed_lo = a.dc.seed_lo;
+    t.seed_hi = a.dc.seed_hi;
+    hipLaunchKernelGGL(temper_sweep, dim3((unsigned)((s->nrows + 255) / 256), (unsigned)s->ntemps), dim3(256), 0, s->stream, t);
+    *launched = true;
+    return hipGetLastError();
+}
+
 kmc_status launch_half(kmc_sampler* s, int half, bool graph_mode, int64_t gen_offset)
 {
     const HalfStepArgs a = make_args(s, half, graph_mode, gen_offset);
     HIP_TRY(launch_half_kernel(s, a));
+    if (s->temper && half == 1) {
+        bool swept = false;
+        HIP_TRY(launch_temper_sweep(s, a, &swept));
+        if (swept && !graph_mode) s->launches += 1;           // (the callers count the two half-steps; a replayed chunk counts its sweep nodes itself)
+    }
     if (s->p2p && s->cfg.shard_count > 1) {
         // the kernel boundary puts this half-step's rows in memory; then publish the progress
         SignalArgs sg{};
@@ -171,6 +210,7 @@ hipError_t launch_half_kernel(const kmc_sampler* s, const HalfStepArgs& a)
     if (s->user) {
         const HalfStepLaunch la{f, a};
         if (s->uk.staged) return launch_module(s->uk.staged, (unsigned)s->grid, (unsigned)s->tpb, s->stream, la, (unsigned)staged_lds_bytes((int)s->cfg.ndim));
+        if (s->temper) return launch_module_y(s->plan.vec ? s->uk.vec : s->uk.generic, (unsigned)s->grid, (unsigned)s->ntemps, (unsigned)s->tpb, s->stream, la, s->plan.vec ? s->vec_lds : 0u);
         return launch_module(s->plan.vec ? s->uk.vec : s->uk.generic, (unsigned)s->grid, (unsigned)s->tpb, s->stream, la, s->plan.vec ? s->vec_lds : 0u);
     }
     if (debug_opt("menu-via-module")) {
@@ -180,9 +220,9 @@ hipError_t launch_half_kernel(const kmc_sampler* s, const HalfStepArgs& a)
         const hipError_t e = hipGetFuncBySymbol(&fn, reinterpret_cast<const void*>(s->plan.fn));
         if (e != hipSuccess) return e;
         const HalfStepLaunch la{f, a};
-        return launch_module(fn, (unsigned)s->grid, (unsigned)s->tpb, s->stream, la);
+        return launch_module_y(fn, (unsigned)s->grid, (unsigned)s->ntemps, (unsigned)s->tpb, s->stream, la);
     }
-    hipLaunchKernelGGL(s->plan.fn, dim3(s->grid), dim3(s->tpb), 0, s->stream, f.pos, f.sched, f.ring_now, f.logp, f.gw0, f.nact_half,
+    hipLaunchKernelGGL(s->plan.fn, dim3((unsigned)s->grid, (unsigned)s->ntemps), dim3(s->tpb), 0, s->stream, f.pos, f.sched, f.ring_now, f.logp, f.gw0, f.nact_half,
                        f.seed_lo, f.seed_hi, f.nhalf, f.step, a);
     return hipGetLastError();
 }
@@ -413,6 +453,7 @@ hipKernelNodeParams node_params(const kmc_sampler* s, KernelParamPack* pk)
 bool updated_graph_possible(const kmc_sampler* s)
 {
     if (s->p2p || s->host_eval || s->islands || s->resident || s->comm || s->updated_refused) return false;
+    if (s->temper) return false;            // (a tempered sampler replays the table graph: the sweep node's work changes per generation -- DESIGN.md 4d)
     if (s->fused) return s->user ? s->uk.generation != nullptr : s->generation_kernel != nullptr;      // (one node per generation: the generation among the preloaded parameters)
     return s->user ? (s->plan.vec && s->uk.vec != nullptr) : s->plan.fn != nullptr;
 }
@@ -790,7 +831,7 @@ KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
         if (!s->fused) HIP_TRY(launch_sweep(s));
         s->generation += kGraphChunk;
         s->dev_gen += kGraphChunk;
-        s->launches += lpg * kGraphChunk;
+        s->launches += (lpg + (s->temper ? 1 : 0)) * kGraphChunk;          // (a tempered chunk: the sweep node of every generation)
         ngen -= kGraphChunk;
         return chain_after(s);
     };
@@ -874,6 +915,7 @@ KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
             s->updated_refused = true;
         }
     }
+    if (s->temper && updated_asked) s->temper_updated_fallback = true;    // (said by kmc_sampler_describe: the run below replays the table graph)
     if (use_graph && s->launch_mode == 0) {
         const char* env = std::getenv("KMC_LAUNCH");
         if (env && std::strcmp(env, "graph") == 0) s->launch_mode = 1;

@@ -33,6 +33,7 @@ KMC_EXPORT kmc_status kmc_rccl_unique_id(void* id_out)
 KMC_EXPORT kmc_status kmc_sampler_rccl_init(kmc_sampler* s, const void* id)
 {
     if (!s || !id) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_rccl_init: parallel tempering runs on one GPU (no replica sharding)");
     if (own_stream_move(s->cfg)) return fail(KMC_ERR_UNSUPPORTED, std::string("kmc_sampler_rccl_init: ") + move_name(s->cfg.move) + " runs on one GPU (no replica sharding)");
     if (s->p2p || s->islands || s->resident || s->host_eval || s->f32 || s->d_ids || s->stream_chain)
         return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_rccl_init: a replica-sharded double sampler with a device density (shard_rank / shard_count, no KMC_P2P)");

@@ -36,6 +36,19 @@ bool lookup_move(int move, int density, int L, int K, int iter, bool ragged, Hal
     });
 }
 
+// parallel tempering: the tempered form of the move's kernels
+bool lookup_temper(int move, int density, int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
+{
+    return with_density(density, false, [&](auto d) {
+        using D = decltype(d);
+        if (move == KMC_MOVE_SNOOKER) temper_part<D, Move::Snooker>(L, K, iter, ragged, vec, gen);
+        else if (move == KMC_MOVE_MIX) temper_part<D, Move::Mix>(L, K, iter, ragged, vec, gen);
+        else if (move == KMC_MOVE_DE) temper_part<D, Move::DE>(L, K, iter, ragged, vec, gen);
+        else temper_part<D, Move::Stretch>(L, K, iter, ragged, vec, gen);
+        return true;
+    });
+}
+
 LogpdfFn logpdf_fn(int density)
 {
     return with_density(density, LogpdfFn(nullptr), [](auto d) { return logpdf_lookup<decltype(d)>(); });
@@ -145,6 +158,7 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     const bool ragged = L > 0 && 2 * L * K != c.ndim;
     const bool f32 = c.dtype == KMC_F32;
     if ((ragged || f32) && iter > 4) iter = 4;
+    if (tempered(c) && iter > 8) iter = 8;                  // (the tempered tables: kmc_tables.hpp, temper_iter)
     if ((c.flags & KMC_P2P) && iter > 8) iter = 8;
     p.ragged = ragged;
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY) {
@@ -168,7 +182,8 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
         }
         return p;
     }
-    if (de) lookup_move(c.move, c.density, L, K, iter, ragged, &vec, &gen);
+    if (tempered(c)) lookup_temper(c.move, c.density, L, K, iter, ragged, &vec, &gen);
+    else if (de) lookup_move(c.move, c.density, L, K, iter, ragged, &vec, &gen);
     else lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen);
     if (!force_generic && L > 0 && 2 * L * K >= c.ndim && vec != nullptr) {
         p.fn = vec; p.vec = true; p.L = L; p.K = K; p.ITER = iter;

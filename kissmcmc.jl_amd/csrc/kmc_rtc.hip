@@ -354,15 +354,19 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
     if (ud->is_body && ((with_vec && !sep_routed(ud) && !body_vec_possible(ud, ndim)) || island_S > 0))
         return fail(KMC_ERR_UNSUPPORTED, "this body density runs in the one-walker-per-lane kernels only");
     // KMC_MOVE_DE / _SNOOKER: the two half-step bodies with that move; KMC_MOVE_MIX: the bodies that pick the member (no staged kernel; one GPU, double rows: kmc_validate)
-    const bool de = move_id != KMC_MOVE_STRETCH, mix = move_id == KMC_MOVE_MIX;
+    // move_id >= kTemperMoveBase: the tempered form of that move's bodies (the rung as blockIdx.y; in the key, and in the program text the disk cache hashes)
+    const bool temper = move_id >= kTemperMoveBase;
+    const int move_key = move_id;
+    if (temper) move_id -= kTemperMoveBase;
+    const bool de = move_id != KMC_MOVE_STRETCH || temper, mix = move_id == KMC_MOVE_MIX;
     const bool staged = !de && !with_vec && staged_possible(ud, f32, ndim, p2p);
     char key[128];
     std::snprintf(key, sizeof(key), "%d:%d,%d,%d,%d|%d,%d|%d|%d|%lld|%d|%d|%d|%d|%d|%d", (int)with_vec, L, K, iter, (int)ragged, resident_K,
                   (int)resident_ragged, island_S, (int)f32, ud->is_body ? (long long)ndim : 0ll, (int)staged, (int)p2p, ud->nblob, (int)sep_routed(ud) + 2 * (int)offline_compiler_wanted(),
-                  generation_nd, move_id);
+                  generation_nd, move_key);
     const char* peer = p2p ? "true" : "false";         // KMC_P2P: partner rows read from their owners (pull)
     const char* rowt = f32 ? "float" : "double";       // storage type of the walker rows (KMC_F32 / KMC_F64)
-    const char* move = move_id == KMC_MOVE_SNOOKER ? ", kmc::Move::Snooker" : de ? ", kmc::Move::DE" : "";    // the half-step bodies' move (the stretch move by default)
+    const char* move = move_id == KMC_MOVE_SNOOKER ? ", kmc::Move::Snooker" : move_id == KMC_MOVE_DE ? ", kmc::Move::DE" : temper ? ", kmc::Move::Stretch" : "";    // the half-step bodies' move (the stretch move by default)
     std::lock_guard<std::mutex> lock(ud->mu);
     auto it = ud->code.find(key);
     if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
@@ -379,7 +383,9 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
         << (ud->is_body && with_vec && sep_routed(ud) ? ud->sep_functor + (ud->sep_nacc > 1 ? "using UDV = kmc::SepDensityN<UserS>;\n" : "using UDV = kmc::SepDensity<UserS>;\n")
                                                 : std::string("using UDV = UD;\n"))
         << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_generic(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { "
-        << (mix ? std::string("kmc::half_step_mix_generic_body<UD") : std::string("kmc::half_step_generic_body<UD, ") + peer + ", " + rowt + move) << ">(KMC_FRONT_PACK, a); }\n"
+        << (temper ? "const kmc::HalfStepArgs b = kmc::temper_args(a); " : "")
+        << (mix ? std::string("kmc::half_step_mix_generic_body<UD") + (temper ? ", true" : "") : std::string("kmc::half_step_generic_body<UD, ") + peer + ", " + rowt + move + (temper ? ", true" : ""))
+        << (temper ? ">(KMC_FRONT_PACK, b); }\n" : ">(KMC_FRONT_PACK, a); }\n")
         << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
         << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_init_ball(const kmc::InitBallArgs a) { kmc::init_ball_body<UD>(a); }\n";
     if (ud->is_body && with_vec && sep_routed(ud))
@@ -387,7 +393,13 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
     if (staged)
         src << "extern \"C\" __global__ __launch_bounds__(" << kStagedTPB << ") void kmc_user_staged(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_staged_body<UD, "
             << ndim << ">(KMC_FRONT_PACK, a); }\n";
-    if (with_vec && mix)
+    if (with_vec && temper)
+        src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { const kmc::HalfStepFront f = kmc::temper_front<"
+            << L << ", " << K << ", " << (ragged ? "true" : "false") << ">(KMC_FRONT_PACK); "
+            << (mix ? std::string("kmc::half_step_mix_vec_body<UDV, ") + std::to_string(L) + ", " + std::to_string(K) + ", " + std::to_string(iter) + ", " + (ragged ? "true" : "false") + ", true"
+                    : std::string("kmc::half_step_vec_body<UDV, ") + std::to_string(L) + ", " + std::to_string(K) + ", " + std::to_string(iter) + ", false, " + (ragged ? "true" : "false") + ", double" + move + ", true")
+            << ">(f, a); }\n";
+    else if (with_vec && mix)
         src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_mix_vec_body<UDV, "
             << L << ", " << K << ", " << iter << ", " << (ragged ? "true" : "false") << ">(KMC_FRONT_PACK, a); }\n";
     else if (with_vec)
@@ -431,7 +443,7 @@ kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int i
 kmc_status load_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged, UserKernels* uk,
                      int resident_K, bool resident_ragged, int island_S, bool f32, int64_t ndim, bool p2p, int generation_nd, int move)
 {
-    const bool de = move != KMC_MOVE_STRETCH;
+    const bool de = move != KMC_MOVE_STRETCH;         // (a tempered sampler too: move >= kTemperMoveBase)
     const std::vector<char>* code = nullptr;
     KMC_TRY(compile_user(ud, with_vec, L, K, iter, ragged, resident_K, resident_ragged, island_S, f32, &code, ndim, p2p, generation_nd, move));
     {

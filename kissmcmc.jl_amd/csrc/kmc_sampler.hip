@@ -152,6 +152,24 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
         if (nb > 0 && (c->dtype != KMC_F64 || P != 1 || c->deal_count > 0 || (c->flags & (KMC_P2P | KMC_ISLANDS | KMC_STREAM_CHAIN))))
             return fail(KMC_ERR_UNSUPPORTED, "a density with blobs: KMC_F64, one GPU, without KMC_P2P / KMC_ISLANDS / KMC_STREAM_CHAIN / sharding / dealt sub-ensembles");
     }
+    if (c->ntemps < 0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps must be >= 0 (0 or 1: off)");
+    if (c->swap_every < 0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: swap_every must be >= 0 (0: never)");
+    if (c->ntemps >= 2) {
+        if (c->ntemps > KMC_TEMPS_MAX) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps must be 2 .. " + std::to_string(KMC_TEMPS_MAX));
+        if (!c->betas) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must point to ntemps inverse temperatures");
+        if (c->betas[0] != 1.0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas[0] must be 1");
+        for (int t = 0; t < c->ntemps; ++t) {
+            if (!std::isfinite(c->betas[t]) || !(c->betas[t] > 0.0)) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must be finite and > 0");
+            if (t > 0 && !(c->betas[t] < c->betas[t - 1])) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must be strictly decreasing");
+        }
+        if ((int64_t)c->ntemps * c->nwalkers >= (int64_t)1 << 31) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps * nwalkers must stay below 2^31");
+        const char* what = c->density == KMC_HOST_DENSITY ? "KMC_HOST_DENSITY" : c->density == KMC_DATA_DENSITY ? "KMC_DATA_DENSITY"
+                         : (c->flags & KMC_ISLANDS) ? "KMC_ISLANDS" : (c->flags & KMC_P2P) ? "KMC_P2P" : P > 1 ? "shard_count > 1"
+                         : c->deal_count > 0 ? "dealt sub-ensembles (deal_count > 0)" : c->dtype == KMC_F32 ? "KMC_F32"
+                         : (c->flags & KMC_STORE_BLOBS) ? "KMC_STORE_BLOBS" : nullptr;
+        if (!what && c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) what = "a density with blobs";
+        if (what) return fail(KMC_ERR_UNSUPPORTED, std::string("parallel tempering (ntemps >= 2): a ladder of ensembles on one GPU with double rows and a device density -- not with ") + what);
+    }
     if (c->deal_count < 0 || (c->deal_count > 0 && (c->deal_rank < 0 || c->deal_rank >= c->deal_count)))
         return fail(KMC_ERR_BAD_ARG, "deal_rank / deal_count out of range");
     if (c->deal_count > 0) {
@@ -323,7 +341,7 @@ int generation_wanted(const kmc_sampler* s)
 {
     const kmc_config& c = s->cfg;
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY || s->f32 || s->nblob != 0 || c.shard_count != 1 || c.deal_count != 0 ||
-        own_stream_move(c) ||                                                                         // (DE, snooker, mixtures: the two-launch kernels only)
+        two_launch_only(c) ||                                                                         // (DE, snooker, mixtures, tempered ladders: the two-launch kernels only)
         (c.flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) || std::getenv("KMC_PLAN") != nullptr)      // (KMC_PLAN: a geometry of the two-launch kernels was asked for)
         return 0;
     // lane-striped forms need a lane-striped density (menu, term / pair, a body recognised as a sum) and the vector kernels' plan
@@ -359,6 +377,10 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     kmc_sampler* s = new kmc_sampler();
     s->cfg = *cfg;
     s->user_seed = cfg->seed;
+    s->temper = tempered(*cfg);
+    s->ntemps = s->temper ? cfg->ntemps : 1;
+    if (s->temper) s->betas.assign(cfg->betas, cfg->betas + cfg->ntemps);          // (the caller's array is copied here)
+    s->cfg.betas = s->temper ? s->betas.data() : nullptr;
     if (cfg->deal_count > 0) s->cfg.seed = deal_seed(cfg->seed, cfg->deal_rank);    // this sub-ensemble's Philox key
     if (s->cfg.shard_count <= 0) s->cfg.shard_count = 1;
     s->h = cfg->nwalkers / 2;
@@ -387,7 +409,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         const bool lane2 = cfg->nwalkers > 1024 && cfg->nwalkers <= 2048 && !s->f32 && cfg->ndim <= 8 && s->user->nblob == 0 && resident_lane_wanted(cfg->ndim);
         if (lane2) rlds = ((size_t)cfg->nwalkers * (size_t)((cfg->ndim | 1) + 1)) * sizeof(double);
         if ((!s->f32 || s->user->is_body || expr_lane) && (cfg->nwalkers <= ((s->user->is_body || expr_lane) ? 1024 : 256) || lane2) && cfg->ndim <= 32 && s->cfg.shard_count == 1 && !(s->user->is_body && cfg->deal_count > 0) &&
-            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && !own_stream_move(*cfg) &&
+            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && !two_launch_only(*cfg) &&
             rlds <= 156 * 1024 && !debug_opt("no-resident"))    // (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
             rK = rK0;
         int iS = 0;
@@ -422,7 +444,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
             set_offline_compiler_hint(s->h_loc >= 8192 && rK == 0 && iS == 0);
             const kmc_status lst = load_user(s->user, s->plan.vec, s->plan.L, s->plan.K, s->plan.ITER, s->plan.ragged, &s->uk, rcode, 4 * rK != cfg->ndim, iS, s->f32,
                                              cfg->ndim, (cfg->flags & KMC_P2P) != 0, (rK != 0 || iS != 0) ? 0 : generation_wanted(s) == 1 ? (int)cfg->ndim : generation_wanted(s) == 2 ? -(100 * s->plan.L + s->plan.K) : generation_wanted(s) == 3 ? -401 : 0,
-                                             (int)cfg->move);
+                                             (int)cfg->move + (s->temper ? kTemperMoveBase : 0));
             set_offline_compiler_hint(false);
             return lst;
         };
@@ -486,7 +508,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         if (ea != hipSuccess) { (void)hipGetLastError(); kmc_sampler_destroy(s); return fail(KMC_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
     }
     if (!s->islands && cfg->density != KMC_USER_DENSITY && !s->host_eval && cfg->nwalkers <= 2048 && cfg->ndim <= 32 &&
-        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && !own_stream_move(*cfg) && !debug_opt("no-resident")) {
+        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && !two_launch_only(*cfg) && !debug_opt("no-resident")) {
         const int64_t chunks = s->ld / 2;
         int K = 1;
         while (2 * K < chunks) K *= 2;
@@ -599,16 +621,28 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         s->push = (cfg->flags & KMC_P2P_PUSH) != 0 && s->plan.vec && s->user == nullptr && !(cfg->flags & KMC_P2P_FINEGRAINED) &&
                   s->cfg.shard_count > 1;
     }
+    const size_t nt = (size_t)s->ntemps;                              // rungs: every per-walker array below holds nt ensembles
+    if (s->temper) {
+        const size_t nb = (2 * nt + 2 * (size_t)s->ld) * sizeof(double);
+        CREATE_TRY(dev_alloc(s, &s->d_betas, nb));
+        CREATE_TRY(hipMemsetAsync(s->d_betas, 0, nb, s->stream));
+        CREATE_TRY(copy_sync(s->d_betas, s->betas.data(), nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        s->d_rung_sum = s->d_betas + nt;
+        s->d_tsum = s->d_rung_sum + nt;
+        CREATE_TRY(dev_alloc(s, (void**)&s->d_nswap, nt * sizeof(unsigned long long)));
+        CREATE_TRY(hipMemsetAsync(s->d_nswap, 0, nt * sizeof(unsigned long long), s->stream));
+    }
     const size_t ldz = (size_t)s->ld;
     const size_t esz = s->f32 ? sizeof(float) : sizeof(double);      // element size of rows and chain
     if (s->p2p && (cfg->flags & KMC_P2P_FINEGRAINED))   // peers map the rows uncached: nothing of them can go stale in a reader's L2
         CREATE_TRY(hipExtMallocWithFlags((void**)&s->d_pos, nw * ldz * sizeof(double), hipDeviceMallocFinegrained));
     else
-        CREATE_TRY(dev_alloc(s, &s->d_pos, (s->push ? 1 + (size_t)s->cfg.shard_count : 1) * nw * ldz * esz ));
-    CREATE_TRY(hipMemsetAsync(s->d_pos, 0, (s->push ? 1 + (size_t)s->cfg.shard_count : 1) * nw * ldz * esz, s->stream));   // the pad column of odd ndim stays 0
+        CREATE_TRY(dev_alloc(s, &s->d_pos, (s->push ? 1 + (size_t)s->cfg.shard_count : nt) * nw * ldz * esz ));
+    CREATE_TRY(hipMemsetAsync(s->d_pos, 0, (s->push ? 1 + (size_t)s->cfg.shard_count : nt) * nw * ldz * esz, s->stream));   // the pad column of odd ndim stays 0
     // per-walker block {logp[nrows], naccept[nrows], klast[nrows]}: one allocation, so the half-step kernels reach all
     // three from one preloaded pointer (HalfStepFront::logp)
-    CREATE_TRY(dev_alloc(s, &s->d_logp, nw * (sizeof(double) + 2 * sizeof(uint32_t))));
+    CREATE_TRY(dev_alloc(s, &s->d_logp, nt * nw * (sizeof(double) + 2 * sizeof(uint32_t))));
+    if (s->temper) CREATE_TRY(hipMemsetAsync(s->d_logp, 0, nt * nw * (sizeof(double) + 2 * sizeof(uint32_t)), s->stream));   // (every rung's counters)
     s->d_naccept = reinterpret_cast<uint32_t*>(s->d_logp + nw);
     s->d_klast = s->d_naccept + nw;
     if (s->ragged_vec() && (reinterpret_cast<uint64_t>(s->d_logp) >> 48) != 0) {   // (kmc_launch.hip: front_of -- ndim rides in the 16 bits above this address)
@@ -629,7 +663,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     // kernels gained 6-10 % from it only while their loads sat behind exec-mask regions and scalar waits; without those they behave like the exact-size ones), and
     // 6-14 % in the large-ensemble geometries (ITER >= 4: bandwidth-bound, the ring is bytes); L = 16, ITER = 1 (C3's geometry) is +-1 % exact-size, -1..2 % ragged, and keeps it.
     // KMC_DEBUG=ring=0|1 forces it off / on wherever the kernel has one.
-    bool want_ring = s->plan.vec && !own_stream_move(*cfg) && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
+    bool want_ring = s->plan.vec && !two_launch_only(*cfg) && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
     {
         std::string forced;
         if (want_ring && debug_opt("ring", &forced)) want_ring = forced != "0";
@@ -807,6 +841,8 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
         cache_free(s->d_err);
     }
     cache_free(s->d_mix);
+    cache_free(s->d_betas);
+    cache_free(s->d_nswap);
     if (s->comm) { rccl_comm_destroy(s->comm); s->comm = nullptr; }
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     for (int i = 0; i < 3; ++i) {
@@ -866,6 +902,7 @@ KMC_EXPORT kmc_status kmc_sampler_bind_positions(kmc_sampler* s, void* pos_dev)
 {
     if (!s || !pos_dev) return fail(KMC_ERR_BAD_ARG, "null argument");
     if (s->p2p) return fail(KMC_ERR_UNSUPPORTED, "KMC_P2P samplers export their own position buffer");
+    if (s->temper) return fail(KMC_ERR_UNSUPPORTED, "parallel tempering: the sampler keeps every rung's rows in its own buffer (no kmc_sampler_bind_positions)");
     if (s->f32) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_bind_positions takes double rows; a KMC_F32 sampler keeps its own float rows");
     if (s->ld != s->cfg.ndim) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_bind_positions needs an even ndim (16-byte rows)");
     HIP_TRY(hipSetDevice(s->cfg.device));
@@ -972,6 +1009,14 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
             o << (i ? "," : "") << b;
         }
         o << ", kernel " << (s->host_eval ? "half_step_mix_generic (propose / accept passes)" : s->plan.vec ? "half_step_mix_vec" : "half_step_mix_generic");
+    }
+    if (s->temper) {
+        o << "; parallel tempering: ntemps " << s->ntemps << " rungs in one launch per half-step (grid y = rung), kernel "
+          << (s->plan.vec ? "half_step_temper_vec" : "half_step_temper_generic") << ", betas 1 .. ";
+        char b[64];
+        std::snprintf(b, sizeof(b), "%.6g", s->betas.back());
+        o << b << ", swap sweep " << (s->cfg.swap_every > 0 ? "every " + std::to_string(s->cfg.swap_every) + " generations (temper_sweep)" : std::string("off"));
+        if (s->temper_updated_fallback) o << "; KMC_LAUNCH=updated asked for: the updated-graph mode is not built for tempered samplers, fell back to the table graph";
     }
     if (s->budget_fallback) o << "; updated-graph budget of the process spent (kmc_set_updated_budget_mb): fell back to " << (s->launch_mode == 2 ? "eager launches" : "the table graph");
     if (s->push) o << "; accepted rows pushed into the peers' local copies (KMC_P2P_PUSH)";

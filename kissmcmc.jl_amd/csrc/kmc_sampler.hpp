@@ -18,6 +18,7 @@ constexpr int64_t kDrawTableGens = 1024;   // resident mode with a draw table: g
 constexpr int64_t kGraphChunk = 64;   // generations per hipGraph replay (128 kernel nodes + 1)
 constexpr int kUExec = 6;             // executables of the "updated graph" launch mode (kmc_sampler::uexec)
 constexpr size_t kGuardBytes = 4096;  // KMC_DEBUG=poison: guard band behind every device allocation of a sampler
+constexpr int kTemperMoveBase = 100;  // load_user's `move` of a tempered sampler: this + kmc_config.move (kmc_rtc.hip)
 constexpr int kHostPieces = 8;        // KMC_HOST_DENSITY: most pieces a half-step's proposals travel to the host in
 
 struct Plan {
@@ -190,6 +191,16 @@ struct kmc_sampler {
     int64_t nrows = 0;                                   // rows held by this sampler (nwalkers, or nlocal for P2P)
     unsigned long long* d_flags = nullptr;               // fine-grained progress flags [shard_count]
     unsigned long long* d_err = nullptr;
+    // parallel tempering (kmc_config.ntemps >= 2): ntemps ensembles in d_pos [ntemps][nrows][ld] and ntemps per-walker blocks behind d_logp
+    // (16 nrows bytes each), so everything that reads rung 0 reads what an untempered sampler holds
+    int ntemps = 1;
+    bool temper = false;
+    bool temper_updated_fallback = false;                // KMC_LAUNCH=updated was asked for: a tempered sampler replays the table graph instead
+    std::vector<double> betas;
+    double* d_betas = nullptr;                           // [ntemps], then logp_sum [ntemps], then the moments credited at exchanges [2][ld] (one allocation)
+    double* d_rung_sum = nullptr;
+    double* d_tsum = nullptr;
+    unsigned long long* d_nswap = nullptr;               // [ntemps - 1]
     kmc::MixTable* d_mix = nullptr;                                     // KMC_MOVE_MIX: the members' table (kmc_host.hpp: mix_table_of)
     bool stream_by_walker = false;                       // KMC_STREAM_CHAIN | KMC_CHAIN_BY_WALKER: host buffers are [walker][nsamples][..]
     double *bw_scratch = nullptr, *bw_scratch_logp = nullptr;   // ... one transposed block on the device, copied out as a 2-D window (also: rows_compact of odd ndim)

@@ -26,10 +26,16 @@ __global__ __launch_bounds__(256) void narrow_rows(const double* src, float* dst
     if (i < n) dst[i] = (float)src[i];
 }
 
-kmc_status eval_initial_logp(kmc_sampler* s, double* logp_out = nullptr)      // (logp_out: somewhere else than d_logp -- a caller that only wants the blobs)
+// the per-walker block {logp, naccept, klast} of rung t of a tempered sampler (16 nrows bytes per rung; rung 0: d_logp itself)
+static double* rung_logp(const kmc_sampler* s, int t) { return s->d_logp + 2 * (size_t)t * (size_t)s->nrows; }
+static uint32_t* rung_naccept(const kmc_sampler* s, int t) { return reinterpret_cast<uint32_t*>(rung_logp(s, t) + s->nrows); }
+static double* rung_pos(const kmc_sampler* s, int t) { return s->d_pos + (size_t)t * (size_t)s->nrows * (size_t)s->ld; }
+
+kmc_status eval_initial_logp(kmc_sampler* s, double* logp_out = nullptr, int rung = 0)      // (logp_out: somewhere else than d_logp -- a caller that only wants the blobs)
 {
     const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
-    double* rows = s->d_pos;
+    double* rows = rung_pos(s, rung);
+    if (rung > 0 && !logp_out) logp_out = rung_logp(s, rung);
     double* scratch = nullptr;
     if (s->f32) {
         const int64_t n = (int64_t)(nw * (size_t)s->ld);
@@ -89,6 +95,31 @@ kmc_status reset_run_state(kmc_sampler* s, bool eval_logp, int64_t generation, u
     return KMC_OK;
 }
 
+// Parallel tempering: the ladder's own counters back to zero (or to a checkpoint's values)
+kmc_status reset_temper_counters(kmc_sampler* s, const uint64_t* nswap, const double* logp_sum)
+{
+    if (!s->temper) return KMC_OK;
+    const size_t nt = (size_t)s->ntemps;
+    std::vector<unsigned long long> ns(nt, 0ull);
+    std::vector<double> ls(nt + 2 * (size_t)s->ld, 0.0);                   // logp_sum, then the moments credited at exchanges
+    if (nswap) for (size_t t = 0; t + 1 < nt; ++t) ns[t] = nswap[t];
+    if (logp_sum) for (size_t t = 0; t < nt; ++t) ls[t] = logp_sum[t];
+    HIP_TRY(copy_sync(s->d_nswap, ns.data(), nt * sizeof(unsigned long long), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(copy_sync(s->d_rung_sum, ls.data(), ls.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    return KMC_OK;
+}
+// rung 0's rows, log-pdfs and zeroed counters into every other rung (kmc_sampler_set_positions of a tempered sampler)
+kmc_status replicate_rung0(kmc_sampler* s)
+{
+    const size_t nw = (size_t)s->nrows;
+    for (int t = 1; t < s->ntemps; ++t) {
+        HIP_TRY(hipMemcpyAsync(rung_pos(s, t), s->d_pos, nw * (size_t)s->ld * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(rung_logp(s, t), s->d_logp, nw * (sizeof(double) + 2 * sizeof(uint32_t)), hipMemcpyDeviceToDevice, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return reset_temper_counters(s, nullptr, nullptr);
+}
+
 }  // namespace kmc_host
 // Device-side make_theta0s: src/samplers.jl:311-349 (see init_ball in kmc_kernels.hpp).
 KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0, const double* ball_radius,
@@ -97,6 +128,7 @@ KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0
     if (!s || !theta0 || !ball_radius || halving_steps < 1 || ntries < 1) return fail(KMC_ERR_BAD_ARG, "bad argument");
     if (s->data_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with KMC_DATA_DENSITY (build the initial ensemble on the host, e.g. make_theta0s)");
     if (s->host_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball evaluates the density on the device; with KMC_HOST_DENSITY build the ball on the host");
+    if (s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with parallel tempering (build the initial ensemble on the host, e.g. make_theta0s; kmc_sampler_set_positions copies it to every rung)");
     if (s->push) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball fills this rank's rows only; with KMC_P2P_PUSH use kmc_sampler_set_positions (the peers' copies must be filled too)");
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -168,8 +200,14 @@ KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0
 // Checkpoint / resume: restore (positions, log-pdfs, acceptance counters, generation).  The random
 // stream is a pure function of (seed, generation, walker), so the continued run is bit-identical to an
 // uninterrupted one.  Moments and the chain restart at the restored generation.
+static kmc_status set_state_rung0(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host, int64_t generation);
 KMC_EXPORT kmc_status kmc_sampler_set_state(kmc_sampler* s, const double* pos_host, const double* logp_host,
                                             const int64_t* naccept_host, int64_t generation)
+{
+    if (s && s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_set_state restores one ensemble: a sampler with parallel tempering takes every rung through kmc_sampler_set_rung_state");
+    return set_state_rung0(s, pos_host, logp_host, naccept_host, generation);
+}
+static kmc_status set_state_rung0(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host, int64_t generation)
 {
     if (!s || !pos_host || !logp_host || generation < 0) return fail(KMC_ERR_BAD_ARG, "bad argument");
     // (stored blobs are chain storage too: after a resume past burn-in kmc_sampler_get_blobs would return rows never written)
@@ -206,7 +244,14 @@ KMC_EXPORT kmc_status kmc_sampler_set_state(kmc_sampler* s, const double* pos_ho
     return reset_run_state(s, /*eval_logp=*/false, generation, (uint32_t)done);
 }
 
+// replicate: a tempered sampler copies the ensemble to every rung (kmc_sampler_set_positions); kmc_sampler_set_rung_state fills the
+// other rungs itself
+static kmc_status set_positions_rung0(kmc_sampler* s, const double* theta_host, bool replicate);
 KMC_EXPORT kmc_status kmc_sampler_set_positions(kmc_sampler* s, const double* theta_host)
+{
+    return set_positions_rung0(s, theta_host, true);
+}
+static kmc_status set_positions_rung0(kmc_sampler* s, const double* theta_host, bool replicate)
 {
     if (!s || !theta_host) return fail(KMC_ERR_BAD_ARG, "null argument");
     reinstall_abort_backtrace();                                 // (diagnostics: somebody may have replaced the handler)
@@ -281,6 +326,78 @@ KMC_EXPORT kmc_status kmc_sampler_set_positions(kmc_sampler* s, const double* th
                         "walker " + std::to_string(w) + " has a non-finite initial log-pdf");
         }
     s->positions_set = true;
+    if (s->temper && replicate) KMC_TRY(replicate_rung0(s));     // the same ensemble on every rung
+    return KMC_OK;
+}
+
+// ---- parallel tempering: every rung in and out (include/kissmcmc_hip.h) ---------------------------------------------------
+KMC_EXPORT kmc_status kmc_sampler_set_rung_state(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host,
+                                                 const uint64_t* nswap_host, const double* logp_sum_host, int64_t generation)
+{
+    if (!s || !pos_host || generation < 0) return fail(KMC_ERR_BAD_ARG, "bad argument");
+    if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_set_rung_state: the sampler was created without parallel tempering (ntemps < 2)");
+    if (generation > 0 && !logp_host) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_set_rung_state: a checkpoint (generation > 0) carries its log-pdfs");
+    const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
+    // rung 0 through the untempered entry points (initial log-pdfs, counters, moments, the finiteness check) ...
+    if (generation == 0 && !logp_host) {
+        KMC_TRY(set_positions_rung0(s, pos_host, false));
+        if (naccept_host) {
+            std::vector<uint32_t> na(nw);
+            for (size_t i = 0; i < nw; ++i) na[i] = (uint32_t)naccept_host[i];
+            HIP_TRY(copy_sync(s->d_naccept, na.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        }
+    } else {
+        KMC_TRY(set_state_rung0(s, pos_host, logp_host, naccept_host, generation));
+    }
+    // ... then the others the same way: rows, log-pdfs (given or evaluated), counters; klast as rung 0's (unused: moments are rung 0's)
+    std::vector<double> lp(nw);
+    std::vector<uint32_t> na(nw);
+    for (int t = 1; t < s->ntemps; ++t) {
+        HIP_TRY(upload_rows(s, rung_pos(s, t), pos_host + (size_t)t * nw * nd, nw));
+        if (logp_host) HIP_TRY(copy_sync(rung_logp(s, t), logp_host + (size_t)t * nw, nw * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        else KMC_TRY(eval_initial_logp(s, nullptr, t));
+        for (size_t i = 0; i < nw; ++i) na[i] = naccept_host ? (uint32_t)naccept_host[(size_t)t * nw + i] : 0u;
+        HIP_TRY(copy_sync(rung_naccept(s, t), na.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemsetAsync(rung_naccept(s, t) + nw, 0, nw * sizeof(uint32_t), s->stream));
+        HIP_TRY(copy_sync(lp.data(), rung_logp(s, t), nw * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        for (size_t w = 0; w < nw; ++w)
+            if (!std::isfinite(lp[w])) {
+                s->positions_set = false;
+                return fail(KMC_ERR_NONFINITE_LOGP, "walker " + std::to_string(w) + " of rung " + std::to_string(t) + " has a non-finite initial log-pdf");
+            }
+    }
+    return reset_temper_counters(s, nswap_host, logp_sum_host);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_get_rung_state(kmc_sampler* s, double* pos_host, double* logp_host, int64_t* naccept_host, double* logp_sum_host)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_rung_state: the sampler was created without parallel tempering (ntemps < 2)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
+    std::vector<uint32_t> na(nw);
+    for (int t = 0; t < s->ntemps; ++t) {
+        if (pos_host) HIP_TRY(download_rows(s, pos_host + (size_t)t * nw * nd, rung_pos(s, t), nw));
+        if (logp_host) HIP_TRY(copy_sync(logp_host + (size_t)t * nw, rung_logp(s, t), nw * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (naccept_host) {
+            HIP_TRY(copy_sync(na.data(), rung_naccept(s, t), nw * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+            for (size_t i = 0; i < nw; ++i) naccept_host[(size_t)t * nw + i] = (int64_t)na[i];
+        }
+    }
+    if (logp_sum_host) HIP_TRY(copy_sync(logp_sum_host, s->d_rung_sum, (size_t)s->ntemps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_get_swaps(kmc_sampler* s, uint64_t* nswap_host)
+{
+    if (!s || !nswap_host) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_swaps: the sampler was created without parallel tempering (ntemps < 2)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::vector<unsigned long long> ns((size_t)s->ntemps);
+    HIP_TRY(copy_sync(ns.data(), s->d_nswap, ns.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+    for (int t = 0; t + 1 < s->ntemps; ++t) nswap_host[t] = (uint64_t)ns[(size_t)t];
     return KMC_OK;
 }
 
@@ -446,6 +563,11 @@ KMC_EXPORT kmc_status kmc_sampler_get_moments(kmc_sampler* s, double* sum, doubl
                 S[d] += hs[d * s->macc_stride + t];
                 Q[d] += hq[d * s->macc_stride + t];
             }
+    }
+    if (s->temper && s->plan.vec) {               // what temper_sweep credited when walkers left rung 0 ([2][ld] behind logp_sum)
+        std::vector<double> ts(2 * (size_t)s->ld);
+        HIP_TRY(copy_sync(ts.data(), s->d_tsum, ts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += ts[(size_t)d]; Q[(size_t)d] += ts[(size_t)(s->ld + d)]; }
     }
     if (!s->carry_sum.empty())                    // what the sampler credited while it ran one launch per generation (unfuse)
         for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += s->carry_sum[(size_t)d]; Q[(size_t)d] += s->carry_sumsq[(size_t)d]; }

@@ -8,6 +8,8 @@
 //   kmc_inst_<density>_p2p.hip   density_part PART 2: the peer-to-peer kernels (KMC_P2P)
 //   kmc_inst_<density>_de.hip    density_part PART 3: the differential-evolution move (KMC_MOVE_DE: exact and ragged double rows, one GPU)
 //   kmc_inst_<density>_snooker.hip  density_part PART 4 and 5: the snooker move (KMC_MOVE_SNOOKER) and the DE / snooker mixtures (KMC_MOVE_MIX), as PART 3
+//   kmc_inst_<density>_temper.hip          temper_part: the tempered kernels (parallel tempering, the rung as blockIdx.y) of the stretch and DE moves
+//   kmc_inst_<density>_temper_snooker.hip  temper_part of the snooker move and the mixtures (exact and ragged double rows, one GPU, like PART 3 .. 5)
 //   kmc_inst_<density>_lds.hip   the LDS-resident (islands, resident mode), one-launch-per-generation and many-chain Metropolis kernels
 // Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_move).
 #pragma once
@@ -30,6 +32,7 @@ using MetropolisTabledFn = void (*)(const MetropolisArgs, const double*, int);
 
 // (the part's vector kernel for this geometry or nullptr, its generic kernel)
 template <class D, int PART> void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen);
+template <class D, Move M> void temper_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen);
 template <class D> LogpdfFn logpdf_lookup();
 template <class D> InitBallFn init_ball_lookup();
 template <class D> IslandFn island_lookup(int S, int K, bool ragged);
@@ -118,6 +121,37 @@ void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec
     else if constexpr (PART == 3) *gen = half_step_de_generic<D>;
     else if constexpr (PART == 4) *gen = half_step_snooker_generic<D>;
     else *gen = half_step_mix_generic<D>;
+}
+
+// parallel tempering: the same geometries with the rung as the grid's second dimension
+template <class D, int L, int K, int ITER, bool RAGGED, Move M>
+HalfStepFn temper_one()
+{
+    if constexpr (ITER > L || ITER * K > 16 || ((M == Move::Snooker || M == Move::Mix) && ITER > 1 && ITER * K > 4)) return nullptr;
+    else return half_step_temper_vec<D, L, K, ITER, RAGGED, M>;
+}
+template <class D, int L, int K, bool RAGGED, Move M>
+HalfStepFn temper_iter(int iter)
+{
+    switch (iter) {
+    case 1: return temper_one<D, L, K, 1, RAGGED, M>();
+    case 2: return temper_one<D, L, K, 2, RAGGED, M>();
+    case 4: return temper_one<D, L, K, 4, RAGGED, M>();
+    case 8: if constexpr (!RAGGED) return temper_one<D, L, K, 8, RAGGED, M>(); else return nullptr;
+    default: return nullptr;
+    }
+}
+template <class D, Move M>
+void temper_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen)
+{
+    *vec = nullptr;
+    *gen = half_step_temper_generic<D, M>;
+    if constexpr (D::kHasFrag) {
+#define KMC_LK(l, k) if (L == l && K == k) *vec = ragged ? temper_iter<D, l, k, true, M>(iter) : temper_iter<D, l, k, false, M>(iter);
+        KMC_LK(1, 1) KMC_LK(2, 1) KMC_LK(4, 1) KMC_LK(4, 2) KMC_LK(8, 2) KMC_LK(16, 2) KMC_LK(32, 2) KMC_LK(64, 2)
+        KMC_LK(64, 4) KMC_LK(64, 8)
+#undef KMC_LK
+    }
 }
 
 template <class D>
@@ -270,6 +304,7 @@ MetropolisTabledFn metropolis_tabled_lookup(int ndim)
 }
 // the explicit instantiations of one translation unit of density D (see the top of this file)
 #define KMC_INSTANTIATE_PART(D, PART) template void density_part<D, PART>(int, int, int, bool, bool, HalfStepFn*, HalfStepFn*)
+#define KMC_INSTANTIATE_TEMPER(D, M) template void temper_part<D, M>(int, int, int, bool, HalfStepFn*, HalfStepFn*)
 #define KMC_INSTANTIATE_ROWS(D) \
     template LogpdfFn logpdf_lookup<D>(); \
     template InitBallFn init_ball_lookup<D>()

@@ -72,6 +72,9 @@ Base.@kwdef struct KmcConfig
     mix_sigma1::Float64 = 0.0
     mix_sigma2::Float64 = 0.0
     mix_sigma3::Float64 = 0.0
+    betas::Ptr{Float64} = C_NULL                      # parallel tempering: [ntemps] inverse temperatures (copied at creation), betas[1] == 1, decreasing
+    ntemps::Int32 = 0                                 # rungs of the ladder; 0 or 1 = off
+    swap_every::Int32 = 0                             # generations between swap sweeps; 0 = never
     move::Int32 = 0                                   # KMC_MOVE_STRETCH = 0 (the reference's move), KMC_MOVE_DE = 1 (opt-in)
     move_pad_::Int32 = 0
     de_gamma0::Float64 = 0.0                          # KMC_MOVE_DE: 0 -> 2.38 / sqrt(2 ndim)
@@ -248,7 +251,7 @@ end
 """
     emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter÷2, nthin=1, a_scale=2.0,
           use_progress_meter=true, hasblob=false, init_blobs, reduce_blob!, seed=rand(UInt64), device=0, dtype=:f64,
-          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7)
+          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1)
 
 Same meaning as KissMCMC.emcee (src/samplers.jl:188-197); returns
 `(thetas, accept_ratio, logdensities, blobs)` with `thetas[w][k]` (src/samplers.jl:292).
@@ -258,13 +261,19 @@ the host) or a `CDensity(body; nblob=m)` (m doubles computed and carried on the 
 relative jitter of gamma); `:stretch` is the reference's move with `a_scale`.  `move=:snooker` is the DE snooker update
 (KMC_MOVE_SNOOKER, `snooker_gamma`); `move=[(:de, 0.8), (:snooker, 0.2)]` a mixture of 2 to 4 weighted members (KMC_MOVE_MIX:
 one member per half-step, each with `de_gamma0` / `de_sigma` or `snooker_gamma`).
+`betas=[1.0, ...]` (strictly decreasing inverse temperatures) switches parallel tempering on: a ladder of ensembles, rung t sampling
+`exp(betas[t] * logpdf)`, neighbouring rungs exchanging walkers every `swap_every` generations; `theta0s` starts every rung and
+the returned tuple is rung 1's (`betas[1] == 1`, the target itself).
 """
 function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1, a_scale=2.0,
                use_progress_meter=true, hasblob=false,
                init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),      # init_output_vector :80-85
                reduce_blob! =(blobs, blob) -> push!(blobs, blob),                         # :196
                seed=rand(UInt64), device=0, dtype=:f64,     # dtype=:f32: float rows on the device (KMC_F32), built-in densities
-               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7)
+               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1)
+    ladder = collect(Float64, betas)                      # (kept alive across the call: GC.@preserve below)
+    isempty(ladder) || (length(ladder) >= 2 && ladder[1] == 1.0 && all(diff(ladder) .< 0) && all(isfinite, ladder) && ladder[end] > 0) ||
+        error("betas must start at 1 and decrease strictly, finite and > 0")
     mix = move isa AbstractVector ? collect(move) : Tuple{Symbol,Float64}[]
     if move isa AbstractVector
         2 <= length(mix) <= 4 || error("a move mixture has 2 to 4 (move, weight) pairs")
@@ -331,8 +340,10 @@ function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin
                             mix_move0=mix_id(1), mix_move1=mix_id(2), mix_move2=mix_id(3), mix_move3=mix_id(4),
                             mix_weight0=mix_w(1), mix_weight1=mix_w(2), mix_weight2=mix_w(3), mix_weight3=mix_w(4),
                             mix_gamma0=mix_g(1), mix_gamma1=mix_g(2), mix_gamma2=mix_g(3), mix_gamma3=mix_g(4),
-                            mix_sigma0=mix_s(1), mix_sigma1=mix_s(2), mix_sigma2=mix_s(3), mix_sigma3=mix_s(4)))
-        st = GC.@preserve pdf theta chain clogp acc bl ccall((:kmc_emcee_run, LIB), Cint,
+                            mix_sigma0=mix_s(1), mix_sigma1=mix_s(2), mix_sigma2=mix_s(3), mix_sigma3=mix_s(4),
+                            betas=(isempty(ladder) ? Ptr{Float64}(C_NULL) : pointer(ladder)), ntemps=Int32(length(ladder)),
+                            swap_every=Int32(isempty(ladder) ? 0 : swap_every)))
+        st = GC.@preserve pdf theta chain clogp acc bl ladder ccall((:kmc_emcee_run, LIB), Cint,
                                                        (Ref{KmcConfig}, Ptr{Float64}, Ref{KmcOutputs}), cfg, theta, out)
         (st == 9 && by_walker && occursin("KMC_CHAIN_BY_WALKER", last_error())) || break
     end

@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from .densities import DeviceLogPdf
 from .moves import apply_move
+from .tempering import apply_tempering
 
 
 def _dp(a):
@@ -25,7 +26,8 @@ class Sampler:
                  device: int = 0, shard_rank: int = 0, shard_count: int = 1, p2p: bool = False,
                  island_gens: int = 0, island_size: int = 0, p2p_finegrained: bool = False, p2p_push: bool = False,
                  dtype: str = "f64", deal_rank: int = 0, deal_count: int = 0,
-                 stream_chain: bool = False, chain_by_walker: bool = False, store_blobs: bool = False, move=None):
+                 stream_chain: bool = False, chain_by_walker: bool = False, store_blobs: bool = False, move=None,
+                 betas=None, ntemps=None, beta_min=None, swap_every: int = 1):
         if not isinstance(pdf, DeviceLogPdf):
             raise TypeError(
                 "pdf must be a menu log-density (GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2), "
@@ -81,6 +83,10 @@ class Sampler:
         cfg.deal_rank, cfg.deal_count = int(deal_rank), int(deal_count)   # dealt sub-ensembles (distributed.DealtEmcee)
         apply_move(move, cfg)                  # None: the stretch move; DEMove, DESnookerMove or a weighted list of them (opt-in)
         self.move = move
+        # parallel tempering (opt-in): betas=[1, ...], or ntemps= and beta_min= for geometric_betas(ntemps, beta_min); every read-out
+        # below stays rung 0's, the rung_* methods return the whole ladder
+        self.betas = apply_tempering(cfg, betas, ntemps, beta_min, swap_every)
+        self.ntemps = 1 if self.betas is None else int(self.betas.size)
         cfg.user_density = pdf.user_handle     # runtime-compiled density (ExprDensity) or None
         cb = getattr(pdf, "c_callback", None)  # host-evaluated density (HostLogPdf) or None
         if cb is not None:
@@ -224,8 +230,80 @@ class Sampler:
         _lib.check(self._L.kmc_sampler_set_walker_ids(self._h, ids.ctypes.data_as(C.POINTER(C.c_int64))))
 
     def set_positions(self, theta):
-        theta = np.ascontiguousarray(np.asarray(theta, dtype=np.float64).reshape(self.nwalkers, self.ndim))
+        """``[nwalkers, ndim]``; a tempered sampler copies it to every rung, or takes ``[ntemps, nwalkers, ndim]``."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if self.betas is not None and theta.ndim == 3:
+            theta = np.ascontiguousarray(theta.reshape(self.ntemps, self.nwalkers, self.ndim))
+            _lib.check(self._L.kmc_sampler_set_rung_state(self._h, _dp(theta), None, None, None, None, 0))
+            return
+        theta = np.ascontiguousarray(theta.reshape(self.nwalkers, self.ndim))
         self._check_host(self._L.kmc_sampler_set_positions(self._h, _dp(theta)))
+
+    # -- parallel tempering: the whole ladder (leading axis: the rung) -------------------------
+    def _need_ladder(self):
+        if self.betas is None:
+            raise ValueError("this sampler was created without parallel tempering (betas= / ntemps=)")
+
+    def _rung_state(self, pos=False, logp=False, naccept=False, logp_sum=False):
+        self._need_ladder()
+        T, nw = self.ntemps, self.nwalkers
+        p = np.empty((T, nw, self.ndim)) if pos else None
+        lp = np.empty((T, nw)) if logp else None
+        na = np.empty((T, nw), dtype=np.int64) if naccept else None
+        ls = np.empty(T) if logp_sum else None
+        _lib.check(self._L.kmc_sampler_get_rung_state(self._h, None if p is None else _dp(p), None if lp is None else _dp(lp),
+                                                      None if na is None else na.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      None if ls is None else _dp(ls)))
+        return p, lp, na, ls
+
+    def rung_positions(self) -> np.ndarray:
+        """``[ntemps, nwalkers, ndim]``: every rung's ensemble (rung 0 is :meth:`positions`)."""
+        return self._rung_state(pos=True)[0]
+
+    def rung_logp(self) -> np.ndarray:
+        """``[ntemps, nwalkers]``: the UNTEMPERED log-density of every walker of every rung."""
+        return self._rung_state(logp=True)[1]
+
+    def rung_naccept(self) -> np.ndarray:
+        """``[ntemps, nwalkers]`` accepted moves per slot since the end of burn-in (a swap leaves the counter with its slot)."""
+        return self._rung_state(naccept=True)[2]
+
+    def nswap(self) -> np.ndarray:
+        """``[ntemps - 1]`` accepted exchanges between rungs ``t`` and ``t + 1`` since the end of burn-in."""
+        self._need_ladder()
+        out = np.zeros(self.ntemps - 1, dtype=np.uint64)
+        _lib.check(self._L.kmc_sampler_get_swaps(self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def swap_attempts(self) -> np.ndarray:
+        """``[ntemps - 1]`` exchanges attempted per pair since the end of burn-in: it follows from the schedule (sweep ``n`` after
+        generation ``g`` when ``(g + 1) % swap_every == 0``, pairs ``(t, t + 1)`` with ``t == n (mod 2)``, every walker index once)."""
+        self._need_ladder()
+        se, out = int(self.cfg.swap_every), np.zeros(self.ntemps - 1, dtype=np.int64)
+        if se > 0:
+            n_all = self.generation // se                               # sweeps so far: n = 0 .. n_all - 1, after generation (n + 1) se - 1
+            n_burn = min(n_all, int(self.cfg.nburnin) // se)            # ... of which these came before counting began (g < nburnin)
+            for par in (0, 1):
+                cnt = (n_all + 1 - par) // 2 - (n_burn + 1 - par) // 2  # sweeps n in [n_burn, n_all) with n % 2 == par
+                out[par::2] = cnt * self.nwalkers
+        return out
+
+    def swap_rates(self) -> np.ndarray:
+        """``[ntemps - 1]`` accepted / attempted exchanges per neighbouring pair (``nan`` where nothing was attempted)."""
+        att = self.swap_attempts().astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.nswap().astype(np.float64) / att
+
+    def rung_logp_sum(self) -> np.ndarray:
+        """``[ntemps]``: sum over stored generations and walkers of the untempered log-density of the stored state."""
+        return self._rung_state(logp_sum=True)[3]
+
+    def rung_logp_mean(self) -> np.ndarray:
+        """``[ntemps]``: mean untempered log-density per rung over the stored generations -- what thermodynamic integration reads."""
+        post = self.generation - self.cfg.nburnin
+        done = 0 if post <= 0 else min(self.nsamples, post // self.cfg.nthin)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.rung_logp_sum() / float(done * self.nwalkers)
 
     def init_ball(self, theta0, ball_radius, seed: int = 0, ball_radius_halfing_steps: int = 7, ntries: int = 100):
         """Device-side ``make_theta0s`` (reference ``src/samplers.jl:311-349``): seeded Gaussian ball
@@ -249,11 +327,24 @@ class Sampler:
 
     def state(self):
         """Checkpoint: ``dict(positions, logp, naccept, generation)`` (synchronises)."""
+        if self.betas is not None:            # every rung, the swap counters and the log-density sums
+            p, lp, na, ls = self._rung_state(True, True, True, True)
+            return dict(positions=p, logp=lp, naccept=na, generation=self.generation, nswap=self.nswap(), rung_logp_sum=ls)
         return dict(positions=self.positions(), logp=self.logp(), naccept=self.naccept(), generation=self.generation)
 
     def restore(self, state):
         """Resume from :meth:`state` of a sampler with the same configuration and seed: the continued
         run is bit-identical to an uninterrupted one (moments restart at the restored generation)."""
+        if self.betas is not None:
+            T = self.ntemps
+            pos = np.ascontiguousarray(np.asarray(state["positions"], dtype=np.float64).reshape(T, self.nwalkers, self.ndim))
+            lp = np.ascontiguousarray(np.asarray(state["logp"], dtype=np.float64).reshape(T, self.nwalkers))
+            na = np.ascontiguousarray(np.asarray(state["naccept"], dtype=np.int64).reshape(T, self.nwalkers))
+            ns = np.ascontiguousarray(np.asarray(state["nswap"], dtype=np.uint64).reshape(T - 1))
+            ls = np.ascontiguousarray(np.asarray(state["rung_logp_sum"], dtype=np.float64).reshape(T))
+            _lib.check(self._L.kmc_sampler_set_rung_state(self._h, _dp(pos), _dp(lp), na.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                          ns.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(ls), int(state["generation"])))
+            return
         pos = np.ascontiguousarray(np.asarray(state["positions"], dtype=np.float64).reshape(self.nrows, self.ndim))
         lp = np.ascontiguousarray(np.asarray(state["logp"], dtype=np.float64))
         na = np.ascontiguousarray(np.asarray(state["naccept"], dtype=np.int64))
