@@ -177,6 +177,14 @@ enum {
 };
 #define KMC_MIX_MAX 4
 #define KMC_TEMPS_MAX 64
+/* kmc_config.temper_mode: what a ladder tempers.
+ *   KMC_TEMPER_WHOLE       rung t samples exp(betas[t] * logpdf): the whole log-density (the default)
+ *   KMC_TEMPER_LIKELIHOOD  KMC_DATA_DENSITY only: rung t samples prior(x) + betas[t] * S(x), the two values of the data-density value
+ *                          contract; the last beta may be 0 (the prior itself).  See kmc_sampler_get_rung_loglike. */
+enum {
+    KMC_TEMPER_WHOLE      = 0,
+    KMC_TEMPER_LIKELIHOOD = 1
+};
 
 #define KMC_P2P_HANDLE_BYTES 128
 #define KMC_RCCL_ID_BYTES 128
@@ -204,6 +212,8 @@ typedef struct kmc_config {
     kmc_host_accepted_fn host_accepted; /* KMC_HOST_DENSITY: per-half-step accept outcomes, or NULL */
     int32_t  deal_rank;     /* DEALT SUB-ENSEMBLES (opt-in, not the reference's partner rule; see kmc_sampler_deal_pack): this sampler is */
     int32_t  deal_count;    /* sub-ensemble deal_rank of deal_count; 0 = off.  nwalkers is then THIS sub-ensemble's size */
+    int32_t  temper_mode;   /* what a ladder tempers: KMC_TEMPER_WHOLE (0, the default) or KMC_TEMPER_LIKELIHOOD (needs ntemps >= 2, KMC_DATA_DENSITY) */
+    int32_t  temper_pad_;
     /* (the snooker and mixture fields stand in front of `move`: the four fields from `move` on stay the struct's tail) */
     double   snooker_gamma; /* KMC_MOVE_SNOOKER: gamma of the proposal; 0 -> 1.7 */
     int32_t  mix_count;     /* KMC_MOVE_MIX: members, 2 .. KMC_MIX_MAX */
@@ -213,7 +223,8 @@ typedef struct kmc_config {
     double   mix_gamma[KMC_MIX_MAX];  /* ... its gamma0 (DE; 0 -> 2.38 / sqrt(2 ndim)) or gamma (snooker; 0 -> 1.7) */
     double   mix_sigma[KMC_MIX_MAX];  /* ... its sigma (DE members; 0 for snooker members) */
     /* PARALLEL TEMPERING (opt-in; see the comment above kmc_sampler_get_rung_state).  Zeroed: off. */
-    const double* betas;    /* [ntemps] inverse temperatures, copied at creation: betas[0] == 1, strictly decreasing, finite, > 0 */
+    const double* betas;    /* [ntemps] inverse temperatures, copied at creation: betas[0] == 1, strictly decreasing, finite, > 0
+                             * (KMC_TEMPER_LIKELIHOOD: the last one may be 0) */
     int32_t  ntemps;        /* rungs of the ladder: 0 or 1 = off, else 2 .. KMC_TEMPS_MAX */
     int32_t  swap_every;    /* generations between swap sweeps; 0 = never */
     int32_t  move;          /* KMC_MOVE_STRETCH (0, the reference's move), KMC_MOVE_DE, KMC_MOVE_SNOOKER or KMC_MOVE_MIX */
@@ -485,7 +496,8 @@ kmc_status  kmc_sampler_get_naccept(kmc_sampler* s, int64_t* host /* [nwalkers] 
  * of rung t with walker w of rung t + 1 for every t == n (mod 2), when (beta_t - beta_{t+1}) (logp_{t+1,w} - logp_{t,w}) >= log u,
  * u from Philox key {seed_lo ^ 0x54454D50 ("TEMP"), seed_hi}, counter {n_lo, n_hi, w, t}.  Every existing read-out (positions,
  * log-pdfs, counters, chain, moments) is rung 0's; a stored sample of generation g is the state BEFORE that generation's sweep.
- * One GPU, double rows, two launches per generation (+ the sweep): KMC_ERR_UNSUPPORTED with KMC_HOST_DENSITY, KMC_DATA_DENSITY,
+ * One GPU, double rows, two launches per generation (+ the sweep): KMC_ERR_UNSUPPORTED with KMC_HOST_DENSITY, KMC_DATA_DENSITY (unless
+ * temper_mode is KMC_TEMPER_LIKELIHOOD, below),
  * blobs, KMC_F32, KMC_ISLANDS, KMC_P2P, sharding, dealt sub-ensembles, kmc_sampler_init_ball, kmc_sampler_bind_positions and
  * kmc_sampler_rccl_init.  kmc_sampler_set_positions copies the ensemble to every rung.
  *   kmc_sampler_get_rung_state  any pointer may be NULL: positions [ntemps][nwalkers][ndim], log-pdfs and acceptance counters
@@ -498,6 +510,26 @@ kmc_status  kmc_sampler_get_rung_state(kmc_sampler* s, double* pos_host, double*
 kmc_status  kmc_sampler_set_rung_state(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host,
                                        const uint64_t* nswap_host, const double* logp_sum_host, int64_t generation);
 kmc_status  kmc_sampler_get_swaps(kmc_sampler* s, uint64_t* nswap_host);
+/* Likelihood tempering (kmc_config.temper_mode = KMC_TEMPER_LIKELIHOOD; KMC_DATA_DENSITY with ntemps >= 2).
+ * Rung t samples prior(x) + betas[t] * S(x).  The tempered value is q = pri + (beta * S): the product is rounded, then the sum, no
+ * fused multiply-add.  Accept tests: stretch and snooker (t1 + q1) - q0 >= log u, DE q1 - q0 >= log u; a proposal whose prior is
+ * -inf is never accepted; draws, partners, walker words and the mixture choice as above.  With beta = 1.0 q has the bits of
+ * pri + S: rung 0 of a ladder that never swaps is the plain KMC_DATA_DENSITY sampler bit for bit.  The sweep keeps its schedule,
+ * pairing and stream; its test is (beta_t - beta_{t+1}) (S_{t+1,w} - S_{t,w}) >= log u (the priors cancel).  The stored log-pdf of
+ * every rung stays the untempered posterior pri + S, so every read-out above keeps its meaning; S and the prior are kept next to
+ * it per walker and rung and travel with their row in an exchange.  betas[ntemps - 1] may be 0: the prior rung, which closes the
+ * thermodynamic integral  log Z = int_0^1 <S>_beta dbeta  (Z is the evidence when the prior body is normalised).  A half-step of the
+ * whole ladder is four launches: every rung's proposals go through one pass of the data kernels.
+ * KMC_ERR_UNSUPPORTED with any density but KMC_DATA_DENSITY, and with everything KMC_DATA_DENSITY or parallel tempering refuses.
+ *   kmc_sampler_get_rung_loglike      any pointer may be NULL: S and the log-prior of every walker [ntemps][nwalkers], loglike_sum
+ *                                     [ntemps] = the sum over stored generations and walkers of S of the stored state (taken before
+ *                                     that generation's sweep, like logp_sum)
+ *   kmc_sampler_set_rung_loglike_sum  a checkpoint's sums back in (NULL: zero).  The per-walker S and priors are NOT part of a
+ *                                     checkpoint: kmc_sampler_set_positions and kmc_sampler_set_rung_state evaluate them again from
+ *                                     the positions on the device, and the value contract makes that the same bits;
+ *                                     kmc_sampler_set_rung_state zeroes the sums, so call this after it */
+kmc_status  kmc_sampler_get_rung_loglike(kmc_sampler* s, double* loglike_host, double* logprior_host, double* loglike_sum_host);
+kmc_status  kmc_sampler_set_rung_loglike_sum(kmc_sampler* s, const double* loglike_sum_host);
 kmc_status  kmc_sampler_get_accept_ratio(kmc_sampler* s, double* host /* [nwalkers] */);
 kmc_status  kmc_sampler_get_moments(kmc_sampler* s, double* sum, double* sumsq /* [ndim] */, int64_t* n);
 /* Chain of this shard: [nsamples][nlocal][ndim] and [nsamples][nlocal]; nlocal = nwalkers /

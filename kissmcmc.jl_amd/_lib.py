@@ -33,6 +33,7 @@ STORE_BLOBS = 8192
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_MIX = 0, 1, 3, 4
 MIX_MAX = 4
 TEMPS_MAX = 64  # parallel tempering: most rungs of a ladder (kmc_config.ntemps)
+TEMPER_WHOLE, TEMPER_LIKELIHOOD = 0, 1  # kmc_config.temper_mode
 P2P_HANDLE_BYTES = 128
 RCCL_ID_BYTES = 128
 
@@ -53,6 +54,7 @@ SYMBOLS = [
     "kmc_user_density_create_body_blob", "kmc_user_density_nblob", "kmc_logpdf_blob_eval_host", "kmc_sampler_get_blobs",
     "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault", "kmc_data_density_create",
     "kmc_sampler_get_rung_state", "kmc_sampler_set_rung_state", "kmc_sampler_get_swaps",
+    "kmc_sampler_get_rung_loglike", "kmc_sampler_set_rung_loglike_sum",
 ]
 
 
@@ -80,6 +82,8 @@ class Config(C.Structure):
         ("host_accepted", C.c_void_p),
         ("deal_rank", C.c_int32),
         ("deal_count", C.c_int32),
+        ("temper_mode", C.c_int32),     # TEMPER_WHOLE or TEMPER_LIKELIHOOD (a DataDensity with a ladder)
+        ("temper_pad_", C.c_int32),
         ("snooker_gamma", C.c_double),
         ("mix_count", C.c_int32),
         # (the header's mix_move[4] ... mix_sigma[4], spelled out member by member like the Julia mirror)
@@ -212,6 +216,8 @@ def lib() -> C.CDLL:
     L.kmc_sampler_get_rung_state.argtypes = [vp, dp, dp, ip, dp]
     L.kmc_sampler_set_rung_state.argtypes = [vp, dp, dp, ip, C.POINTER(C.c_uint64), dp, C.c_int64]
     L.kmc_sampler_get_swaps.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.kmc_sampler_get_rung_loglike.argtypes = [vp, dp, dp, dp]
+    L.kmc_sampler_set_rung_loglike_sum.argtypes = [vp, dp]
     L.kmc_sampler_run.argtypes = [vp, C.c_int64]
     L.kmc_sampler_half_step.argtypes = [vp, C.c_int]
     L.kmc_sampler_sync.argtypes = [vp]

@@ -41,7 +41,8 @@ kmc_status compile_data(kmc_user_density* ud, int64_t ndim, const std::vector<ch
     src << "#include \"kmc_data.hpp\"\n" << data_functor_source(ud)
         << "extern \"C\" __global__ __launch_bounds__(" << kDataTPB << ") void kmc_data_lane(const kmc_data::DataArgs a) { kmc_data::data_partial_lane_body<UserData, " << nd << ", " << nc << ">(a); }\n"
         << "extern \"C\" __global__ __launch_bounds__(" << kDataTPB << ") void kmc_data_obs(const kmc_data::DataArgs a) { kmc_data::data_partial_obs_body<UserData, " << nd << ", " << nc << ">(a); }\n"
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold(const kmc_data::DataArgs a) { kmc_data::data_fold_body<UserData, " << nd << ">(a); }\n";
+        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold(const kmc_data::DataArgs a) { kmc_data::data_fold_body<UserData, " << nd << ">(a); }\n"
+        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold_split(const kmc_data::DataArgs a) { kmc_data::data_fold_split_body<UserData, " << nd << ">(a); }\n";
     const char* headers[2] = {h_dev.c_str(), h_data.c_str()};
     const char* names[2] = {"kmc_device.hpp", "kmc_data.hpp"};
     const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
@@ -92,6 +93,7 @@ kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk)
     HIP_TRY(hipModuleGetFunction(&dk->lane, mod, "kmc_data_lane"));
     HIP_TRY(hipModuleGetFunction(&dk->obs, mod, "kmc_data_obs"));
     HIP_TRY(hipModuleGetFunction(&dk->fold, mod, "kmc_data_fold"));
+    HIP_TRY(hipModuleGetFunction(&dk->fold_split, mod, "kmc_data_fold_split"));
     return KMC_OK;
 }
 
@@ -117,7 +119,7 @@ DataPlan data_plan(const kmc_user_density* ud, int64_t nprop)
 }
 
 hipError_t launch_data_eval(const DataKernels& dk, const kmc_user_density* ud, const DataPlan& p, const double* prop, int64_t nprop, int32_t ld,
-                            const double* params, double* part, size_t part_doubles, double* out, hipStream_t st)
+                            const double* params, double* part, size_t part_doubles, double* out, hipStream_t st, bool split)
 {
     if (nprop <= 0) return hipSuccess;
     if ((size_t)p.nblocks * (size_t)nprop > part_doubles) return hipErrorInvalidValue;     // (never launched past the scratch buffer)
@@ -134,7 +136,7 @@ hipError_t launch_data_eval(const DataKernels& dk, const kmc_user_density* ud, c
         const hipError_t e = hipModuleLaunchKernel(p.obs ? dk.obs : dk.lane, gx, (unsigned)p.nblocks, 1, kDataTPB, 1, 1, 0, st, nullptr, extra);
         if (e != hipSuccess) return e;
     }
-    return launch_module(dk.fold, (unsigned)((nprop + 255) / 256), 256u, st, a);
+    return launch_module(split ? dk.fold_split : dk.fold, (unsigned)((nprop + 255) / 256), 256u, st, a);
 }
 
 }  // namespace kmc_host

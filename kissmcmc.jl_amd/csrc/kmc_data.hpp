@@ -19,6 +19,8 @@
 //   data_partial_obs  -- one proposal per workgroup, one observation per lane: 64 terms reduced by the fixed DPP / v_permlane
 //                        butterfly (group_sum<64>), then the same stack and LDS fold.  Node of kWaves * 64 * rounds observations.
 //   data_fold         -- one proposal per thread: the tree over the blocks' nodes, the prior, the log-pdf.
+//   data_fold_split   -- the same tree and prior, written separately: S to out[prop], the prior to out[nprop + prop] (likelihood
+//                        tempering, DESIGN.md section 4d: a rung samples prior + beta S).
 #pragma once
 #include "kmc_device.hpp"
 
@@ -179,6 +181,21 @@ __device__ __forceinline__ void data_fold_body(const DataArgs& a)
     const double s = st.finish((uint32_t)a.nblocks);
     const double pri = F::prior(x, ND, a.p);
     a.out[prop] = pri == -INFINITY ? -INFINITY : pri + s;
+}
+
+// ... S and the prior as they are ([2][nprop]); what data_fold adds up, bit for bit
+template <class F, int ND>
+__device__ __forceinline__ void data_fold_split_body(const DataArgs& a)
+{
+    const int64_t prop = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (prop >= a.nprop) return;
+    double x[ND];
+#pragma unroll
+    for (int k = 0; k < ND; ++k) x[k] = a.prop[prop * a.ld + k];
+    Stack st;
+    for (int b = 0; b < a.nblocks; ++b) st.push(a.part[(int64_t)b * a.nprop + prop], (uint32_t)b);
+    a.out[prop] = st.finish((uint32_t)a.nblocks);
+    a.out[a.nprop + prop] = F::prior(x, ND, a.p);
 }
 
 }  // namespace kmc_data

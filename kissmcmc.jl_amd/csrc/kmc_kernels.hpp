@@ -1075,8 +1075,10 @@ __global__ __launch_bounds__(vec_tpb(L)) void flush_moments_vec(const FlushArgs 
 template <class Dens, bool P2P, class T = double, Move M = Move::Stretch, bool TEMPER = false>
 __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, const HalfStepArgs& a, const DrawConsts* over = nullptr)
 {
-    static_assert(!TEMPER || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0 && !HostEvalTrait<Dens>::value), "tempering: one GPU, double rows, device densities, no blobs");
-    // (TEMPER: `a` is the rung's own copy of the arguments -- temper_args -- with beta behind it)
+    static_assert(!TEMPER || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "tempering: one GPU, double rows, no blobs");
+    // (TEMPER: `a` is the rung's own copy of the arguments -- temper_args -- with beta behind it.  TEMPER with HostEval is LIKELIHOOD
+    //  tempering of a data density, DESIGN.md section 4d: the ACCEPT pass reads the proposal's tree sum S1 from p1_in and its prior from
+    //  peer_pos[4], the walker's stored S0 / prior from peer_pos[2] / peer_pos[3], and tests q = pri + (beta S); logp stays pri + S)
     const bool rung0 = !TEMPER || blockIdx.y == 0u;
     static_assert(!P2P || sizeof(T) == 8, "the peer-to-peer kernels keep double rows");
     static_assert(M != Move::Mix, "a mixture picks its member in front of the body (half_step_mix_generic_body)");
@@ -1163,7 +1165,16 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     double p1 = Dens::seq_finish(q, ndim, a.dp);                         // :257
     if constexpr (kHost) p1 = a.p1_in[tid];
     bool acc;
-    if constexpr (TEMPER) acc = snk_ok && accept_test_beta<M>(dr, p1, p0, reinterpret_cast<const double*>(a.peer_pos[1])[blockIdx.y]);
+    [[maybe_unused]] double like1 = 0.0, pri1 = 0.0;
+    if constexpr (TEMPER && kHost) {
+        like1 = p1;
+        pri1 = a.peer_pos[4][tid];
+        const double beta = reinterpret_cast<const double*>(a.peer_pos[1])[blockIdx.y];
+        const double q1 = pri1 + beta * like1;                           // (the product is rounded, then the sum: -ffp-contract=off)
+        const double q0 = a.peer_pos[3][gw] + beta * a.peer_pos[2][gw];
+        p1 = pri1 + like1;                                               // what is stored: the untempered posterior
+        acc = snk_ok && pri1 != -INFINITY && (kDE ? de_accept_test(dr, q1, q0) : accept_test(dr, q1, q0));
+    } else if constexpr (TEMPER) acc = snk_ok && accept_test_beta<M>(dr, p1, p0, reinterpret_cast<const double*>(a.peer_pos[1])[blockIdx.y]);
     else acc = snk_ok && (kDE ? de_accept_test(dr, p1, p0) : accept_test(dr, p1, p0));   // :260
     if constexpr (kHost) { if (a.acc_out != nullptr) a.acc_out[tid] = acc ? 1 : 0; }
 
@@ -1188,6 +1199,7 @@ __device__ __forceinline__ void half_step_generic_body(const HalfStepFront& f, c
     }
     if (acc) {
         a.logp[gw] = p1;                                                // :262
+        if constexpr (TEMPER && kHost) { a.peer_pos[2][gw] = like1; a.peer_pos[3][gw] = pri1; }
         if (count) a.naccept[gw] += 1u;                                 // :265
     }
     if (sample && a.chain_logp != nullptr) a.chain_logp[row] = acc ? p1 : p0;   // :271
@@ -1245,10 +1257,29 @@ __device__ __forceinline__ HalfStepArgs temper_args(const HalfStepArgs& a)
     b.gw0 = a.gw0 + t * nw;
     return b;
 }
+// ... of a likelihood-tempered data density as well: rung t's h proposals are rows t h .. of prop_out, their tree sums and priors
+// entries t h .. of p1_in / peer_pos[4] (one pass of the data kernels serves every rung), the stored S and prior [ntemps][nwalkers]
+__device__ __forceinline__ HalfStepArgs temper_args_like(const HalfStepArgs& a)
+{
+    HalfStepArgs b = temper_args(a);
+    const int64_t t = blockIdx.y, nw = 2 * (int64_t)a.dc.nhalf, h = a.n_active;
+    if (a.prop_out != nullptr) b.prop_out = a.prop_out + t * h * a.prop_ld;
+    b.p1_in = a.p1_in + t * h;
+    b.peer_pos[4] = a.peer_pos[4] + t * h;
+    b.peer_pos[2] = a.peer_pos[2] + t * nw;
+    b.peer_pos[3] = a.peer_pos[3] + t * nw;
+    return b;
+}
+template <class Dens>
+__device__ __forceinline__ HalfStepArgs temper_args_of(const HalfStepArgs& a)
+{
+    if constexpr (HostEvalTrait<Dens>::value) return temper_args_like(a);
+    else return temper_args(a);
+}
 template <class Dens, Move M>
 __global__ __launch_bounds__(256) void half_step_temper_generic(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
-    const HalfStepArgs b = temper_args(a);
+    const HalfStepArgs b = temper_args_of<Dens>(a);
     if constexpr (M == Move::Mix) half_step_mix_generic_body<Dens, true>(KMC_FRONT_PACK, b);
     else half_step_generic_body<Dens, false, double, M, true>(KMC_FRONT_PACK, b);
 }
@@ -1613,6 +1644,14 @@ struct TemperSweepArgs {
     int32_t             ntemps, nwalkers, ld, swap_every;
     uint32_t            seed_lo, seed_hi;
 };
+// ... of a likelihood-tempered data density (kmc_config.temper_mode = KMC_TEMPER_LIKELIHOOD): the whole-mode arguments, then the
+// per-walker tree sums S and priors, which travel with their row
+struct TemperSweepLikeArgs {
+    TemperSweepArgs a;
+    double*         like;         // [ntemps][nwalkers] S of every walker's current position
+    double*         prior;        // [ntemps][nwalkers] its log-prior
+    double*         like_sum;     // [ntemps] sum of the stored states' S
+};
 
 // Non-template kernels of the host driver: each group is defined once, in the translation unit that launches it.
 #ifdef KMC_DEFINE_LAUNCH_KERNELS   // kmc_launch.hip
@@ -1698,6 +1737,106 @@ __global__ __launch_bounds__(256) void temper_sweep(const TemperSweepArgs a)
     if (acc) {
         lp_lo[w] = p_hi;
         lp_hi[w] = p_lo;
+        if (t == 0 && a.msum != nullptr) {
+            uint32_t* const klast = reinterpret_cast<uint32_t*>(lp_lo + nw) + nw;
+            const uint32_t nb1 = sch.nbefore + (stored ? 1u : 0u);      // samples taken by the generations up to this one
+            wgt = nb1 - klast[w];
+            klast[w] = nb1;
+        }
+    }
+    const unsigned long long mask = __ballot(acc);
+    if ((sch.flags & kCount) != 0) {
+        const double c = block_sum256((threadIdx.x & 63) == 0 ? (double)__popcll(mask) : 0.0, red);
+        if (threadIdx.x == 0 && c != 0.0) atomicAdd(&a.nswap[t], (unsigned long long)c);
+    }
+    if (mask == 0ull) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t wbase = (int64_t)blockIdx.x * 256 + (int64_t)(threadIdx.x & ~63u);
+    const int nchunk = a.ld >> 1;
+    double2* const r_lo = reinterpret_cast<double2*>(a.pos + ((int64_t)t * nw + wbase) * a.ld);
+    double2* const r_hi = reinterpret_cast<double2*>(a.pos + ((int64_t)(t + 1) * nw + wbase) * a.ld);
+    const bool credit = t == 0 && a.msum != nullptr;
+    for (int idx = lane; idx < 64 * nchunk; idx += 64) {                 // (the same trip count in every lane)
+        const int wl = idx / nchunk;
+        const uint32_t wq = credit ? (uint32_t)__shfl((int)wgt, wl) : 0u;
+        if ((mask >> wl) & 1ull) {
+            const double2 x = r_lo[idx], y = r_hi[idx];
+            r_lo[idx] = y;
+            r_hi[idx] = x;
+            if (wq != 0u) {
+                const int d = 2 * (idx - wl * nchunk);
+                const double wd = (double)wq;
+                atomicAdd(&a.msum[d], x.x * wd);
+                atomicAdd(&a.msum[d + 1], x.y * wd);
+                atomicAdd(&a.msum[a.ld + d], (x.x * x.x) * wd);
+                atomicAdd(&a.msum[a.ld + d + 1], (x.y * x.y) * wd);
+            }
+        }
+    }
+}
+// The likelihood form (KMC_TEMPER_LIKELIHOOD): the same schedule, pairing, stream and row exchange; the exchange is decided on S -- the
+// priors cancel --, the stored states' S are added into like_sum as well, and S and the prior are exchanged with the log-density.  A kernel
+// of its own, so that temper_sweep stays the code it was.
+__global__ __launch_bounds__(256) void temper_sweep_like(const TemperSweepLikeArgs la)
+{
+    const TemperSweepArgs& a = la.a;
+    double* const like = la.like;
+    double* const prior = la.prior;
+    double* const like_sum = la.like_sum;
+    __shared__ double red[4];
+    const SchedEntry sch = a.sched_index >= 0 ? a.sched_table[a.sched_index] : a.sched_inline;
+    const bool stored = (sch.flags & kSample) != 0;
+    const int64_t g1 = sch.gen + 1;
+    const bool sweep = a.swap_every > 0 && g1 % a.swap_every == 0;
+    if (!stored && !sweep) return;
+    const uint64_t n = sweep ? (uint64_t)(g1 / a.swap_every - 1) : 0ull;
+    const int par = (int)(n & 1ull);
+    const int t = (int)blockIdx.y;
+    if (sweep && t >= 1 && ((t - 1) & 1) == par) return;                 // the upper rung of a pair: rung t - 1's block row has it
+    const bool lower = sweep && (t & 1) == par && t + 1 < a.ntemps;
+    const int64_t nw = a.nwalkers;
+    const int w = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool valid = w < a.nwalkers;
+    double* const lp_lo = a.logp + 2 * (int64_t)t * nw;
+    double* const lp_hi = lp_lo + 2 * nw;
+    const double p_lo = valid ? lp_lo[w] : 0.0;
+    const double p_hi = (lower && valid) ? lp_hi[w] : 0.0;
+    const double l_lo = valid ? like[(int64_t)t * nw + w] : 0.0;
+    const double l_hi = (lower && valid) ? like[(int64_t)(t + 1) * nw + w] : 0.0;
+    if (stored) {
+        const double s_lo = block_sum256(p_lo, red);
+        if (threadIdx.x == 0) atomicAdd(&a.logp_sum[t], s_lo);
+        if (lower) {
+            const double s_hi = block_sum256(p_hi, red);
+            if (threadIdx.x == 0) atomicAdd(&a.logp_sum[t + 1], s_hi);
+        }
+        {
+            const double ls_lo = block_sum256(l_lo, red);
+            if (threadIdx.x == 0) atomicAdd(&like_sum[t], ls_lo);
+            if (lower) {
+                const double ls_hi = block_sum256(l_hi, red);
+                if (threadIdx.x == 0) atomicAdd(&like_sum[t + 1], ls_hi);
+            }
+        }
+    }
+    if (!lower) return;
+    bool acc = false;
+    if (valid) {
+        const double lu = temper_swap_logu(a.seed_lo, a.seed_hi, n, (uint32_t)w, (uint32_t)t);
+        acc = (a.betas[t] - a.betas[t + 1]) * (l_hi - l_lo) >= lu;            // (the priors cancel)
+    }
+    uint32_t wgt = 0u;                                                   // samples the walker leaving rung 0 stood for
+    if (acc) {
+        lp_lo[w] = p_hi;
+        lp_hi[w] = p_lo;
+        {
+            double* const pr_lo = prior + (int64_t)t * nw;
+            const double r_lo = pr_lo[w], r_hi = pr_lo[nw + w];
+            pr_lo[w] = r_hi;
+            pr_lo[nw + w] = r_lo;
+            like[(int64_t)t * nw + w] = l_hi;
+            like[(int64_t)(t + 1) * nw + w] = l_lo;
+        }
         if (t == 0 && a.msum != nullptr) {
             uint32_t* const klast = reinterpret_cast<uint32_t*>(lp_lo + nw) + nw;
             const uint32_t nb1 = sch.nbefore + (stored ? 1u : 0u);      // samples taken by the generations up to this one

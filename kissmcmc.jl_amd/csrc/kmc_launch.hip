@@ -93,6 +93,11 @@ HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t 
         a.peer_pos[0] = reinterpret_cast<double*>(s->d_mix);
     }
     if (s->temper) a.peer_pos[1] = s->d_betas;                            // the tempered kernels read beta_t there (one GPU: no peers)
+    if (s->temper_like) {                                                 // likelihood tempering: the walkers' S and priors, the proposals' priors behind their S
+        a.peer_pos[2] = s->d_like;
+        a.peer_pos[3] = s->d_prior;
+        a.peer_pos[4] = s->d_p1 + (int64_t)s->ntemps * s->h;
+    }
     a.dp = s->dp;
     a.chain = s->d_chain;
     a.chain_logp = s->d_chain_logp;
@@ -168,7 +173,9 @@ hipError_t launch_temper_sweep(const kmc_sampler* s, const HalfStepArgs& a, bool
     t.swap_every = s->cfg.swap_every;
     t.seed_lo = a.dc.seed_lo;
     t.seed_hi = a.dc.seed_hi;
-    hipLaunchKernelGGL(temper_sweep, dim3((unsigned)((s->nrows + 255) / 256), (unsigned)s->ntemps), dim3(256), 0, s->stream, t);
+    const dim3 grid((unsigned)((s->nrows + 255) / 256), (unsigned)s->ntemps);
+    if (s->temper_like) hipLaunchKernelGGL(temper_sweep_like, grid, dim3(256), 0, s->stream, TemperSweepLikeArgs{t, s->d_like, s->d_prior, s->d_like_sum});
+    else hipLaunchKernelGGL(temper_sweep, grid, dim3(256), 0, s->stream, t);
     *launched = true;
     return hipGetLastError();
 }
@@ -710,7 +717,10 @@ KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
         return KMC_OK;
     }
     if (s->data_eval) {
-        // per half-step: PROPOSE (the host route's first pass) -> partial sums -> fold -> ACCEPT, all on the sampler's stream
+        // per half-step: PROPOSE (the host route's first pass) -> partial sums -> fold -> ACCEPT, all on the sampler's stream.  A likelihood-tempered
+        // ladder does the same four launches for every rung at once (the rung as the grid's second dimension in PROPOSE and ACCEPT, ntemps h proposals
+        // in one pass of the data kernels -- S does not depend on beta), then the sweep where it has work
+        const int64_t nprop = (int64_t)s->ntemps * s->h;
         for (; ngen > 0; --ngen) {
             KMC_TRY(chain_before(s, s->generation + 1));
             for (int half = 0; half < 2; ++half) {
@@ -718,11 +728,16 @@ KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
                 a.prop_out = s->d_prop;
                 a.prop_ld = (int32_t)s->ld;
                 HIP_TRY(launch_half_kernel(s, a));
-                HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_half, s->d_prop, s->h, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_p1, s->stream));
+                HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_half, s->d_prop, nprop, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_p1, s->stream, s->temper_like));
                 a.prop_out = nullptr;
                 a.p1_in = s->d_p1;
                 HIP_TRY(launch_half_kernel(s, a));
                 s->launches += 4;
+                if (s->temper && half == 1) {
+                    bool swept = false;
+                    HIP_TRY(launch_temper_sweep(s, a, &swept));
+                    if (swept) s->launches += 1;
+                }
             }
             s->generation += 1;
             KMC_TRY(chain_after(s));

@@ -164,6 +164,12 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     if (c.density == KMC_HOST_DENSITY || c.density == KMC_DATA_DENSITY) {
         // bound by the host callback (or, for a data density, by the data kernels between the two passes): the one-walker-per-lane kernel, any ndim
         p.fn = c.move == KMC_MOVE_MIX ? half_step_host_mix() : c.move == KMC_MOVE_SNOOKER ? half_step_host_snooker() : de ? half_step_host_de() : half_step_host(); p.vec = false; p.ragged = false; p.L = 1; p.K = 1; p.ITER = 1;
+        if (tempered(c)) {                                  // (a likelihood-tempered data density: kmc_inst_host_temper*.hip)
+            if (c.move == KMC_MOVE_SNOOKER) temper_part<HostEval, Move::Snooker>(1, 1, 1, false, &vec, &p.fn);
+            else if (c.move == KMC_MOVE_MIX) temper_part<HostEval, Move::Mix>(1, 1, 1, false, &vec, &p.fn);
+            else if (c.move == KMC_MOVE_DE) temper_part<HostEval, Move::DE>(1, 1, 1, false, &vec, &p.fn);
+            else temper_part<HostEval, Move::Stretch>(1, 1, 1, false, &vec, &p.fn);
+        }
         return p;
     }
     if (c.density == KMC_USER_DENSITY) {

@@ -154,16 +154,25 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
     }
     if (c->ntemps < 0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps must be >= 0 (0 or 1: off)");
     if (c->swap_every < 0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: swap_every must be >= 0 (0: never)");
+    if (c->temper_mode != KMC_TEMPER_WHOLE && c->temper_mode != KMC_TEMPER_LIKELIHOOD)
+        return fail(KMC_ERR_BAD_ARG, "parallel tempering: temper_mode must be KMC_TEMPER_WHOLE or KMC_TEMPER_LIKELIHOOD");
+    const bool like = c->temper_mode == KMC_TEMPER_LIKELIHOOD;
+    if (like && c->ntemps < 2) return fail(KMC_ERR_BAD_ARG, "parallel tempering: KMC_TEMPER_LIKELIHOOD needs a ladder (ntemps >= 2)");
     if (c->ntemps >= 2) {
         if (c->ntemps > KMC_TEMPS_MAX) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps must be 2 .. " + std::to_string(KMC_TEMPS_MAX));
         if (!c->betas) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must point to ntemps inverse temperatures");
         if (c->betas[0] != 1.0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas[0] must be 1");
         for (int t = 0; t < c->ntemps; ++t) {
-            if (!std::isfinite(c->betas[t]) || !(c->betas[t] > 0.0)) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must be finite and > 0");
+            const bool prior_rung = like && t == c->ntemps - 1 && c->betas[t] == 0.0;      // (the rung that samples the prior closes the thermodynamic integral)
+            if (!std::isfinite(c->betas[t]) || !(c->betas[t] > 0.0 || prior_rung))
+                return fail(KMC_ERR_BAD_ARG, like ? "parallel tempering: betas must be finite and > 0 (KMC_TEMPER_LIKELIHOOD: the last one may be 0)" : "parallel tempering: betas must be finite and > 0");
             if (t > 0 && !(c->betas[t] < c->betas[t - 1])) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must be strictly decreasing");
         }
         if ((int64_t)c->ntemps * c->nwalkers >= (int64_t)1 << 31) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps * nwalkers must stay below 2^31");
-        const char* what = c->density == KMC_HOST_DENSITY ? "KMC_HOST_DENSITY" : c->density == KMC_DATA_DENSITY ? "KMC_DATA_DENSITY"
+        if (like && c->density != KMC_DATA_DENSITY)
+            return fail(KMC_ERR_UNSUPPORTED, "parallel tempering: KMC_TEMPER_LIKELIHOOD needs KMC_DATA_DENSITY (prior + beta * S): nothing says where another density's prior ends");
+        const char* what = c->density == KMC_HOST_DENSITY ? "KMC_HOST_DENSITY"
+                         : (c->density == KMC_DATA_DENSITY && !like) ? "KMC_DATA_DENSITY in the default temper_mode (temper_mode = KMC_TEMPER_LIKELIHOOD, temper=\"likelihood\", tempers its likelihood)"
                          : (c->flags & KMC_ISLANDS) ? "KMC_ISLANDS" : (c->flags & KMC_P2P) ? "KMC_P2P" : P > 1 ? "shard_count > 1"
                          : c->deal_count > 0 ? "dealt sub-ensembles (deal_count > 0)" : c->dtype == KMC_F32 ? "KMC_F32"
                          : (c->flags & KMC_STORE_BLOBS) ? "KMC_STORE_BLOBS" : nullptr;
@@ -381,6 +390,7 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     s->ntemps = s->temper ? cfg->ntemps : 1;
     if (s->temper) s->betas.assign(cfg->betas, cfg->betas + cfg->ntemps);          // (the caller's array is copied here)
     s->cfg.betas = s->temper ? s->betas.data() : nullptr;
+    s->temper_like = s->temper && cfg->temper_mode == KMC_TEMPER_LIKELIHOOD;
     if (cfg->deal_count > 0) s->cfg.seed = deal_seed(cfg->seed, cfg->deal_rank);    // this sub-ensemble's Philox key
     if (s->cfg.shard_count <= 0) s->cfg.shard_count = 1;
     s->h = cfg->nwalkers / 2;
@@ -717,13 +727,22 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         }
     }
     if (s->data_eval) {
-        CREATE_TRY(dev_alloc(s, &s->d_prop, (size_t)s->h * ldz * sizeof(double)));
-        CREATE_TRY(dev_alloc(s, &s->d_p1, (size_t)s->h * sizeof(double)));
+        // (a likelihood-tempered ladder: every rung's proposals in one pass -- nt h rows, S and the prior apart -- and every rung's rows at set_positions)
+        const size_t np_half = nt * (size_t)s->h, np_all = nt * nw;
+        CREATE_TRY(dev_alloc(s, &s->d_prop, np_half * ldz * sizeof(double)));
+        CREATE_TRY(dev_alloc(s, &s->d_p1, (s->temper_like ? 2 : 1) * np_half * sizeof(double)));
         // the plans are decided here, once (KMC_DEBUG=data-map may change later in the process: the kernels keep the geometry d_part was sized for)
-        s->plan_half = data_plan(s->data_ud, s->h);
-        s->plan_all = data_plan(s->data_ud, s->nrows);
-        s->part_doubles = std::max((size_t)s->plan_half.nblocks * (size_t)s->h, (size_t)s->plan_all.nblocks * (size_t)s->nrows);
+        s->plan_half = data_plan(s->data_ud, (int64_t)np_half);
+        s->plan_all = data_plan(s->data_ud, (int64_t)np_all);
+        s->part_doubles = std::max((size_t)s->plan_half.nblocks * np_half, (size_t)s->plan_all.nblocks * np_all);
         CREATE_TRY(dev_alloc(s, &s->d_part, s->part_doubles * sizeof(double)));
+        if (s->temper_like) {
+            const size_t nb = (2 * np_all + nt) * sizeof(double);
+            CREATE_TRY(dev_alloc(s, &s->d_like, nb));
+            CREATE_TRY(hipMemsetAsync(s->d_like, 0, nb, s->stream));
+            s->d_prior = s->d_like + np_all;
+            s->d_like_sum = s->d_prior + np_all;
+        }
     } else if (s->host_eval) {
         CREATE_TRY(dev_alloc(s, &s->d_prop, (size_t)s->h * ldz * sizeof(double)));
         CREATE_TRY(dev_alloc(s, &s->d_p1, (size_t)s->h * sizeof(double)));
@@ -876,6 +895,7 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
     cache_free(s->d_prop);
     cache_free(s->d_p1);
     cache_free(s->d_part);
+    cache_free(s->d_like);
     if (s->h_prop) (void)hipHostFree(s->h_prop);
     if (s->h_p1) (void)hipHostFree(s->h_p1);
     cache_free(s->d_acc);
@@ -965,11 +985,12 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
         o << launch_mode_text(s, "generation");
     } else if (s->data_eval) {
         const DataPlan& ph = s->plan_half;
-        o << "data density (exact): per half-step propose kernel -> " << (ph.obs ? "data_partial_obs (one observation per lane, grid " + std::to_string(s->h)
-                                                                                 : "data_partial_lane (one proposal per lane, grid " + std::to_string((s->h + 63) / 64))
-          << " x " << ph.nblocks << " workgroups of 256, " << ph.rounds << " rounds per wave) -> data_fold -> accept kernel, eager launches; "
-          << s->data_ud->ndata << " observations of " << s->data_ud->ncols << " doubles; scratch " << ph.nblocks << " x " << s->h
-          << " tree nodes (at most 4096 x nwalkers doubles)";
+        const int64_t np = (int64_t)s->ntemps * s->h;                      // (a likelihood-tempered ladder: every rung's proposals in one pass)
+        o << "data density (exact): per half-step propose kernel -> " << (ph.obs ? "data_partial_obs (one observation per lane, grid " + std::to_string(np)
+                                                                                 : "data_partial_lane (one proposal per lane, grid " + std::to_string((np + 63) / 64))
+          << " x " << ph.nblocks << " workgroups of 256, " << ph.rounds << " rounds per wave) -> " << (s->temper_like ? "data_fold_split" : "data_fold") << " -> accept kernel, eager launches; "
+          << s->data_ud->ndata << " observations of " << s->data_ud->ncols << " doubles; scratch " << ph.nblocks << " x " << np
+          << " tree nodes (at most 4096 x " << (s->temper_like ? "ntemps x " : "") << "nwalkers doubles)";
     } else if (s->host_eval)
         o << "host-evaluated density (exact): per half-step propose kernel -> D2H -> callback -> H2D -> accept kernel, grid "
           << s->grid << " x 256";
@@ -1015,7 +1036,8 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
           << (s->plan.vec ? "half_step_temper_vec" : "half_step_temper_generic") << ", betas 1 .. ";
         char b[64];
         std::snprintf(b, sizeof(b), "%.6g", s->betas.back());
-        o << b << ", swap sweep " << (s->cfg.swap_every > 0 ? "every " + std::to_string(s->cfg.swap_every) + " generations (temper_sweep)" : std::string("off"));
+        o << b << ", swap sweep " << (s->cfg.swap_every > 0 ? "every " + std::to_string(s->cfg.swap_every) + " generations (" + (s->temper_like ? "temper_sweep_like" : "temper_sweep") + ")" : std::string("off"));
+        if (s->temper_like) o << "; likelihood tempering: rung t samples prior + beta_t S, four launches per half-step for the whole ladder";
         if (s->temper_updated_fallback) o << "; KMC_LAUNCH=updated asked for: the updated-graph mode is not built for tempered samplers, fell back to the table graph";
     }
     if (s->budget_fallback) o << "; updated-graph budget of the process spent (kmc_set_updated_budget_mb): fell back to " << (s->launch_mode == 2 ? "eager launches" : "the table graph");

@@ -41,7 +41,7 @@ struct UserKernels {
 // kernels and device data of a data density (kmc_data.hip), and how one evaluation over `nprop` rows is cut
 struct DataKernels {
     std::shared_ptr<void> keep, keep_data;   // the module and the device copy of the observations (shared with the density)
-    hipFunction_t lane = nullptr, obs = nullptr, fold = nullptr;
+    hipFunction_t lane = nullptr, obs = nullptr, fold = nullptr, fold_split = nullptr;
     const double* data = nullptr;
 };
 struct DataPlan {
@@ -154,6 +154,12 @@ struct kmc_sampler {
     double* d_part = nullptr;          // tree nodes of the partial kernels, [nblocks][rows] (<= 4096 x nwalkers doubles)
     size_t part_doubles = 0;           //   its size
     kmc_host::DataPlan plan_half{}, plan_all{};   // how a half-step's proposals / the whole ensemble are cut: fixed at creation, d_part sized for both
+    // likelihood tempering (kmc_config.temper_mode = KMC_TEMPER_LIKELIHOOD, a data density with a ladder): rung t samples prior + beta_t S.  plan_half / plan_all,
+    // d_prop and d_p1 ([2][ntemps h]: S, then the priors) are then sized for every rung's proposals at once: one pass of the data kernels per half-step
+    bool temper_like = false;
+    double* d_like = nullptr;          // [ntemps][nrows] S of every walker, then the priors [ntemps][nrows], then like_sum [ntemps] (one allocation)
+    double* d_prior = nullptr;
+    double* d_like_sum = nullptr;
     // resident mode: exact sampler, whole (small) ensemble in one workgroup's LDS, many generations per launch
     bool resident = false;
     kmc::ResidentFn resident_kernel = nullptr;
@@ -253,9 +259,10 @@ bool body_vec_possible(const kmc_user_density* ud, int64_t ndim);     // a funct
 // kmc_data.hip
 kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk);       // compile (cached) + module + device copy of the data
 DataPlan data_plan(const kmc_user_density* ud, int64_t nprop);                   // reads KMC_DEBUG=data-map: call it once per evaluation size, keep the result
-// one evaluation of nprop rows cut as `p` says; `part` holds part_doubles doubles (p.nblocks * nprop are written: refused beyond that)
+// one evaluation of nprop rows cut as `p` says; `part` holds part_doubles doubles (p.nblocks * nprop are written: refused beyond that).
+// split: `out` takes the tree sums S [nprop] and then the priors [nprop] instead of the log-pdfs (data_fold_split)
 hipError_t launch_data_eval(const DataKernels& dk, const kmc_user_density* ud, const DataPlan& p, const double* prop, int64_t nprop, int32_t ld,
-                            const double* params, double* part, size_t part_doubles, double* out, hipStream_t st);
+                            const double* params, double* part, size_t part_doubles, double* out, hipStream_t st, bool split = false);
 
 // kmc_p2p.hip
 kmc_status check_p2p_err(kmc_sampler* s);                // a peer wait that timed out invalidates everything after it

@@ -106,6 +106,26 @@ kmc_status reset_temper_counters(kmc_sampler* s, const uint64_t* nswap, const do
     if (logp_sum) for (size_t t = 0; t < nt; ++t) ls[t] = logp_sum[t];
     HIP_TRY(copy_sync(s->d_nswap, ns.data(), nt * sizeof(unsigned long long), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(copy_sync(s->d_rung_sum, ls.data(), ls.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    if (s->temper_like) HIP_TRY(fill_sync(s->d_like_sum, 0, nt * sizeof(double), s->stream));      // (a checkpoint's: kmc_sampler_set_rung_loglike_sum)
+    return KMC_OK;
+}
+// Likelihood tempering: S and the prior of every walker of every rung from the rows in place -- one pass of the data kernels over
+// ntemps x nwalkers rows, the value contract's bits whatever the cut.  fill_logp: the rungs above 0 get their log-pdfs from them
+// (pri + S as data_fold adds them; rung 0's came from data_fold itself), and a non-finite one is refused like rung 0's.
+kmc_status eval_like_all(kmc_sampler* s, bool fill_logp)
+{
+    const size_t nw = (size_t)s->nrows, nt = (size_t)s->ntemps;
+    HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_all, s->d_pos, (int64_t)(nt * nw), (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_like, s->stream, true));
+    if (!fill_logp) { HIP_TRY(hipStreamSynchronize(s->stream)); return KMC_OK; }
+    std::vector<double> sp(2 * nt * nw), lp(nw);
+    HIP_TRY(copy_sync(sp.data(), s->d_like, sp.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    for (size_t t = 1; t < nt; ++t) {
+        for (size_t w = 0; w < nw; ++w) {
+            const double like = sp[t * nw + w], pri = sp[(nt + t) * nw + w];
+            lp[w] = pri == -INFINITY ? -INFINITY : pri + like;
+        }
+        HIP_TRY(copy_sync(rung_logp(s, (int)t), lp.data(), nw * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    }
     return KMC_OK;
 }
 // rung 0's rows, log-pdfs and zeroed counters into every other rung (kmc_sampler_set_positions of a tempered sampler)
@@ -117,6 +137,7 @@ kmc_status replicate_rung0(kmc_sampler* s)
         HIP_TRY(hipMemcpyAsync(rung_logp(s, t), s->d_logp, nw * (sizeof(double) + 2 * sizeof(uint32_t)), hipMemcpyDeviceToDevice, s->stream));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->temper_like) KMC_TRY(eval_like_all(s, false));
     return reset_temper_counters(s, nullptr, nullptr);
 }
 
@@ -352,10 +373,14 @@ KMC_EXPORT kmc_status kmc_sampler_set_rung_state(kmc_sampler* s, const double* p
     // ... then the others the same way: rows, log-pdfs (given or evaluated), counters; klast as rung 0's (unused: moments are rung 0's)
     std::vector<double> lp(nw);
     std::vector<uint32_t> na(nw);
+    if (s->temper_like) {                  // every rung's S and prior again from the rows (and the log-pdfs, unless given): the same bits
+        for (int t = 1; t < s->ntemps; ++t) HIP_TRY(upload_rows(s, rung_pos(s, t), pos_host + (size_t)t * nw * nd, nw));
+        KMC_TRY(eval_like_all(s, logp_host == nullptr));
+    }
     for (int t = 1; t < s->ntemps; ++t) {
         HIP_TRY(upload_rows(s, rung_pos(s, t), pos_host + (size_t)t * nw * nd, nw));
         if (logp_host) HIP_TRY(copy_sync(rung_logp(s, t), logp_host + (size_t)t * nw, nw * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        else KMC_TRY(eval_initial_logp(s, nullptr, t));
+        else if (!s->temper_like) KMC_TRY(eval_initial_logp(s, nullptr, t));
         for (size_t i = 0; i < nw; ++i) na[i] = naccept_host ? (uint32_t)naccept_host[(size_t)t * nw + i] : 0u;
         HIP_TRY(copy_sync(rung_naccept(s, t), na.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipMemsetAsync(rung_naccept(s, t) + nw, 0, nw * sizeof(uint32_t), s->stream));
@@ -386,6 +411,30 @@ KMC_EXPORT kmc_status kmc_sampler_get_rung_state(kmc_sampler* s, double* pos_hos
         }
     }
     if (logp_sum_host) HIP_TRY(copy_sync(logp_sum_host, s->d_rung_sum, (size_t)s->ntemps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_get_rung_loglike(kmc_sampler* s, double* loglike_host, double* logprior_host, double* loglike_sum_host)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    if (!s->temper_like) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_rung_loglike: the sampler was created without likelihood tempering (temper_mode = KMC_TEMPER_LIKELIHOOD)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t n = (size_t)s->ntemps * (size_t)s->nrows;
+    if (loglike_host) HIP_TRY(copy_sync(loglike_host, s->d_like, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (logprior_host) HIP_TRY(copy_sync(logprior_host, s->d_prior, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (loglike_sum_host) HIP_TRY(copy_sync(loglike_sum_host, s->d_like_sum, (size_t)s->ntemps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_set_rung_loglike_sum(kmc_sampler* s, const double* loglike_sum_host)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    if (!s->temper_like) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_set_rung_loglike_sum: the sampler was created without likelihood tempering (temper_mode = KMC_TEMPER_LIKELIHOOD)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (loglike_sum_host) HIP_TRY(copy_sync(s->d_like_sum, loglike_sum_host, (size_t)s->ntemps * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    else HIP_TRY(fill_sync(s->d_like_sum, 0, (size_t)s->ntemps * sizeof(double), s->stream));
     return KMC_OK;
 }
 

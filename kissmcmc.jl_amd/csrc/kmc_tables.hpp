@@ -10,6 +10,7 @@
 //   kmc_inst_<density>_snooker.hip  density_part PART 4 and 5: the snooker move (KMC_MOVE_SNOOKER) and the DE / snooker mixtures (KMC_MOVE_MIX), as PART 3
 //   kmc_inst_<density>_temper.hip          temper_part: the tempered kernels (parallel tempering, the rung as blockIdx.y) of the stretch and DE moves
 //   kmc_inst_<density>_temper_snooker.hip  temper_part of the snooker move and the mixtures (exact and ragged double rows, one GPU, like PART 3 .. 5)
+//   kmc_inst_host_temper*.hip    temper_part of the host-evaluated density: likelihood tempering of a data density (generic kernels only)
 //   kmc_inst_<density>_lds.hip   the LDS-resident (islands, resident mode), one-launch-per-generation and many-chain Metropolis kernels
 // Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_move).
 #pragma once

@@ -51,6 +51,8 @@ Base.@kwdef struct KmcConfig
     host_accepted::Ptr{Cvoid} = C_NULL                # KMC_HOST_DENSITY: accept outcomes per half-step (blobs), or NULL
     deal_rank::Int32 = 0                              # dealt sub-ensembles (multi-GPU, opt-in); deal_count = 0: off
     deal_count::Int32 = 0
+    temper_mode::Int32 = 0                            # what a ladder tempers: KMC_TEMPER_WHOLE = 0, KMC_TEMPER_LIKELIHOOD = 1 (data densities)
+    temper_pad_::Int32 = 0
     snooker_gamma::Float64 = 0.0                      # KMC_MOVE_SNOOKER: 0 -> 1.7
     mix_count::Int32 = 0                              # KMC_MOVE_MIX: 2 .. 4 members (the header's mix_move[4] ... mix_sigma[4], member by member)
     mix_move0::Int32 = 0
@@ -101,6 +103,7 @@ const KMC_STORE_LOGP = UInt32(1) << 1
 const KMC_CHAIN_BY_WALKER = UInt32(1) << 12     # chain delivered as [walker][sample][dim]: thetas[w][k] are contiguous
 const KMC_MOVE_STRETCH = Int32(0)              # kmc_config.move: the reference's stretch move (default)
 const KMC_MOVE_DE = Int32(1)                   # ... the opt-in differential-evolution move (one GPU, double rows)
+const KMC_TEMPER_WHOLE, KMC_TEMPER_LIKELIHOOD = Int32(0), Int32(1)   # kmc_config.temper_mode: what a ladder tempers (the likelihood only: data densities)
 const KMC_MOVE_SNOOKER, KMC_MOVE_MIX = Int32(3), Int32(4)   # ... the opt-in DE snooker update (ndim >= 2), and a weighted mixture of DE / snooker members
 const KMC_STORE_BLOBS = UInt32(1) << 13         # a CDensity(body; nblob=m): the blob of every stored sample (src/samplers.jl:270, :117)
 
@@ -251,7 +254,7 @@ end
 """
     emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter÷2, nthin=1, a_scale=2.0,
           use_progress_meter=true, hasblob=false, init_blobs, reduce_blob!, seed=rand(UInt64), device=0, dtype=:f64,
-          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1)
+          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1, temper=:whole)
 
 Same meaning as KissMCMC.emcee (src/samplers.jl:188-197); returns
 `(thetas, accept_ratio, logdensities, blobs)` with `thetas[w][k]` (src/samplers.jl:292).
@@ -263,17 +266,22 @@ relative jitter of gamma); `:stretch` is the reference's move with `a_scale`.  `
 one member per half-step, each with `de_gamma0` / `de_sigma` or `snooker_gamma`).
 `betas=[1.0, ...]` (strictly decreasing inverse temperatures) switches parallel tempering on: a ladder of ensembles, rung t sampling
 `exp(betas[t] * logpdf)`, neighbouring rungs exchanging walkers every `swap_every` generations; `theta0s` starts every rung and
-the returned tuple is rung 1's (`betas[1] == 1`, the target itself).
+the returned tuple is rung 1's (`betas[1] == 1`, the target itself).  `temper=:likelihood` (KMC_TEMPER_LIKELIHOOD) tempers only the
+likelihood of a data density -- rung t samples `prior + betas[t] * S`, and the last beta may be 0 --; the library refuses it for
+every other density.
 """
 function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1, a_scale=2.0,
                use_progress_meter=true, hasblob=false,
                init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),      # init_output_vector :80-85
                reduce_blob! =(blobs, blob) -> push!(blobs, blob),                         # :196
                seed=rand(UInt64), device=0, dtype=:f64,     # dtype=:f32: float rows on the device (KMC_F32), built-in densities
-               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1)
+               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1, temper=:whole)
     ladder = collect(Float64, betas)                      # (kept alive across the call: GC.@preserve below)
-    isempty(ladder) || (length(ladder) >= 2 && ladder[1] == 1.0 && all(diff(ladder) .< 0) && all(isfinite, ladder) && ladder[end] > 0) ||
-        error("betas must start at 1 and decrease strictly, finite and > 0")
+    temper in (:whole, :likelihood) || error("temper must be :whole or :likelihood")
+    temper == :whole || !isempty(ladder) || error("temper=:likelihood needs a ladder (betas)")
+    isempty(ladder) || (length(ladder) >= 2 && ladder[1] == 1.0 && all(diff(ladder) .< 0) && all(isfinite, ladder) &&
+                        (ladder[end] > 0 || (temper == :likelihood && ladder[end] == 0))) ||
+        error("betas must start at 1 and decrease strictly, finite and > 0 (temper=:likelihood: the last one may be 0)")
     mix = move isa AbstractVector ? collect(move) : Tuple{Symbol,Float64}[]
     if move isa AbstractVector
         2 <= length(mix) <= 4 || error("a move mixture has 2 to 4 (move, weight) pairs")
@@ -342,7 +350,7 @@ function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin
                             mix_gamma0=mix_g(1), mix_gamma1=mix_g(2), mix_gamma2=mix_g(3), mix_gamma3=mix_g(4),
                             mix_sigma0=mix_s(1), mix_sigma1=mix_s(2), mix_sigma2=mix_s(3), mix_sigma3=mix_s(4),
                             betas=(isempty(ladder) ? Ptr{Float64}(C_NULL) : pointer(ladder)), ntemps=Int32(length(ladder)),
-                            swap_every=Int32(isempty(ladder) ? 0 : swap_every)))
+                            swap_every=Int32(isempty(ladder) ? 0 : swap_every), temper_mode=(temper == :likelihood ? KMC_TEMPER_LIKELIHOOD : KMC_TEMPER_WHOLE)))
         st = GC.@preserve pdf theta chain clogp acc bl ladder ccall((:kmc_emcee_run, LIB), Cint,
                                                        (Ref{KmcConfig}, Ptr{Float64}, Ref{KmcOutputs}), cfg, theta, out)
         (st == 9 && by_walker && occursin("KMC_CHAIN_BY_WALKER", last_error())) || break

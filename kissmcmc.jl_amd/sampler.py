@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from .densities import DeviceLogPdf
 from .moves import apply_move
-from .tempering import apply_tempering
+from .tempering import apply_tempering, thermodynamic_integration
 
 
 def _dp(a):
@@ -27,7 +27,7 @@ class Sampler:
                  island_gens: int = 0, island_size: int = 0, p2p_finegrained: bool = False, p2p_push: bool = False,
                  dtype: str = "f64", deal_rank: int = 0, deal_count: int = 0,
                  stream_chain: bool = False, chain_by_walker: bool = False, store_blobs: bool = False, move=None,
-                 betas=None, ntemps=None, beta_min=None, swap_every: int = 1):
+                 betas=None, ntemps=None, beta_min=None, swap_every: int = 1, temper=None):
         if not isinstance(pdf, DeviceLogPdf):
             raise TypeError(
                 "pdf must be a menu log-density (GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2), "
@@ -85,7 +85,9 @@ class Sampler:
         self.move = move
         # parallel tempering (opt-in): betas=[1, ...], or ntemps= and beta_min= for geometric_betas(ntemps, beta_min); every read-out
         # below stays rung 0's, the rung_* methods return the whole ladder
-        self.betas = apply_tempering(cfg, betas, ntemps, beta_min, swap_every)
+        # temper="likelihood" (a DataDensity): rung t samples prior + betas[t] * S, the last beta may be 0; rung_loglike*, log_evidence
+        self.betas = apply_tempering(cfg, betas, ntemps, beta_min, swap_every, temper)
+        self.temper = "likelihood" if cfg.temper_mode == _lib.TEMPER_LIKELIHOOD else ("whole" if self.betas is not None else None)
         self.ntemps = 1 if self.betas is None else int(self.betas.size)
         cfg.user_density = pdf.user_handle     # runtime-compiled density (ExprDensity) or None
         cb = getattr(pdf, "c_callback", None)  # host-evaluated density (HostLogPdf) or None
@@ -305,6 +307,53 @@ class Sampler:
         with np.errstate(invalid="ignore", divide="ignore"):
             return self.rung_logp_sum() / float(done * self.nwalkers)
 
+    # -- likelihood tempering (temper="likelihood"): S, the prior, and the evidence -------------
+    def _need_likelihood(self):
+        if self.temper != "likelihood":
+            raise ValueError("this sampler was created without likelihood tempering (a DataDensity with betas= and temper=\"likelihood\")")
+
+    def _rung_loglike(self, like=False, prior=False, like_sum=False):
+        self._need_likelihood()
+        T, nw = self.ntemps, self.nwalkers
+        ll = np.empty((T, nw)) if like else None
+        pr = np.empty((T, nw)) if prior else None
+        ls = np.empty(T) if like_sum else None
+        _lib.check(self._L.kmc_sampler_get_rung_loglike(self._h, None if ll is None else _dp(ll), None if pr is None else _dp(pr),
+                                                        None if ls is None else _dp(ls)))
+        return ll, pr, ls
+
+    def rung_loglike(self) -> np.ndarray:
+        """``[ntemps, nwalkers]``: the log-likelihood ``S`` (the tree sum of the data terms) of every walker of every rung."""
+        return self._rung_loglike(like=True)[0]
+
+    def rung_logprior(self) -> np.ndarray:
+        """``[ntemps, nwalkers]``: the log-prior of every walker of every rung; ``rung_logp() == rung_logprior() + rung_loglike()``."""
+        return self._rung_loglike(prior=True)[1]
+
+    def rung_loglike_sum(self) -> np.ndarray:
+        """``[ntemps]``: sum over stored generations and walkers of ``S`` of the stored state (taken before that generation's sweep)."""
+        return self._rung_loglike(like_sum=True)[2]
+
+    def rung_loglike_mean(self) -> np.ndarray:
+        """``[ntemps]``: ``<S>`` per rung over the stored generations -- the integrand of thermodynamic integration."""
+        post = self.generation - self.cfg.nburnin
+        done = 0 if post <= 0 else min(self.nsamples, post // self.cfg.nthin)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.rung_loglike_sum() / float(done * self.nwalkers)
+
+    def log_evidence(self):
+        """``(logZ, err)`` = :func:`thermodynamic_integration` of ``rung_loglike_mean()`` over the ladder: the trapezoid of ``<S>_beta``
+        and its every-second-rung discretisation estimate.  ``logZ`` is the log-evidence of the model only when the prior body is
+        NORMALISED (a log-density that integrates to one, constants included) and the ladder ends in ``beta = 0``; a ladder that stops
+        at ``beta_min > 0`` leaves out the integral from 0 to ``beta_min`` (a warning says so).  ``err`` does not include the
+        Monte-Carlo error of the means.  Raises unless the sampler is likelihood-tempered."""
+        self._need_likelihood()
+        if self.betas[-1] != 0.0:
+            import warnings
+            warnings.warn(f"log_evidence: the ladder ends at beta = {self.betas[-1]:g}, not 0: the thermodynamic integral starts there "
+                          "(add a prior rung: betas=[..., 0.0])", stacklevel=2)
+        return thermodynamic_integration(self.betas, self.rung_loglike_mean())
+
     def init_ball(self, theta0, ball_radius, seed: int = 0, ball_radius_halfing_steps: int = 7, ntries: int = 100):
         """Device-side ``make_theta0s`` (reference ``src/samplers.jl:311-349``): seeded Gaussian ball
         around ``theta0`` with ``pdf > -Inf``, generated and checked on the GPU; the sampler is then
@@ -329,7 +378,10 @@ class Sampler:
         """Checkpoint: ``dict(positions, logp, naccept, generation)`` (synchronises)."""
         if self.betas is not None:            # every rung, the swap counters and the log-density sums
             p, lp, na, ls = self._rung_state(True, True, True, True)
-            return dict(positions=p, logp=lp, naccept=na, generation=self.generation, nswap=self.nswap(), rung_logp_sum=ls)
+            st = dict(positions=p, logp=lp, naccept=na, generation=self.generation, nswap=self.nswap(), rung_logp_sum=ls)
+            if self.temper == "likelihood":   # (S and the prior per walker are evaluated again from the positions at restore: the same bits)
+                st["rung_loglike_sum"] = self.rung_loglike_sum()
+            return st
         return dict(positions=self.positions(), logp=self.logp(), naccept=self.naccept(), generation=self.generation)
 
     def restore(self, state):
@@ -344,6 +396,9 @@ class Sampler:
             ls = np.ascontiguousarray(np.asarray(state["rung_logp_sum"], dtype=np.float64).reshape(T))
             _lib.check(self._L.kmc_sampler_set_rung_state(self._h, _dp(pos), _dp(lp), na.ctypes.data_as(C.POINTER(C.c_int64)),
                                                           ns.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(ls), int(state["generation"])))
+            if self.temper == "likelihood":
+                lls = np.ascontiguousarray(np.asarray(state["rung_loglike_sum"], dtype=np.float64).reshape(T))
+                _lib.check(self._L.kmc_sampler_set_rung_loglike_sum(self._h, _dp(lls)))
             return
         pos = np.ascontiguousarray(np.asarray(state["positions"], dtype=np.float64).reshape(self.nrows, self.ndim))
         lp = np.ascontiguousarray(np.asarray(state["logp"], dtype=np.float64))

@@ -25,13 +25,19 @@ def geometric_betas(ntemps: int, beta_min: float) -> np.ndarray:
     return b
 
 
-def check_betas(betas) -> np.ndarray:
-    """The ladder as a contiguous float64 array, or ``ValueError`` naming what is wrong with it (the library checks the same)."""
+TEMPER_MODES = {None: _lib.TEMPER_WHOLE, "whole": _lib.TEMPER_WHOLE, "likelihood": _lib.TEMPER_LIKELIHOOD}
+
+
+def check_betas(betas, prior_rung: bool = False) -> np.ndarray:
+    """The ladder as a contiguous float64 array, or ``ValueError`` naming what is wrong with it (the library checks the same).
+    ``prior_rung`` (``temper="likelihood"``): the last beta may be 0, the rung that samples the prior."""
     b = np.ascontiguousarray(np.asarray(betas, dtype=np.float64))
     if b.ndim != 1 or not 2 <= b.size <= _lib.TEMPS_MAX:
         raise ValueError(f"betas must be a 1-D sequence of 2 .. {_lib.TEMPS_MAX} inverse temperatures")
-    if not np.all(np.isfinite(b)) or not np.all(b > 0):
-        raise ValueError("betas must be finite and > 0")
+    positive = b[:-1] if (prior_rung and b[-1] == 0.0) else b
+    if not np.all(np.isfinite(b)) or not np.all(positive > 0):
+        raise ValueError("betas must be finite and > 0" + (" (only the last one may be 0)" if prior_rung else
+                                                           " (a rung with beta = 0 needs temper=\"likelihood\")"))
     if b[0] != 1.0:
         raise ValueError("betas[0] must be 1 (rung 0 samples the target itself)")
     if not np.all(np.diff(b) < 0):
@@ -39,12 +45,18 @@ def check_betas(betas) -> np.ndarray:
     return b
 
 
-def apply_tempering(cfg, betas=None, ntemps=None, beta_min=None, swap_every=1):
-    """Fill ``cfg.betas / ntemps / swap_every``; returns the array ``cfg.betas`` points into (keep it alive until the sampler
-    exists: the library copies it at creation), or ``None`` when tempering is off."""
+def apply_tempering(cfg, betas=None, ntemps=None, beta_min=None, swap_every=1, temper=None):
+    """Fill ``cfg.betas / ntemps / swap_every / temper_mode``; returns the array ``cfg.betas`` points into (keep it alive until the
+    sampler exists: the library copies it at creation), or ``None`` when tempering is off.  ``temper``: ``None`` / ``"whole"`` (rung
+    ``t`` samples ``exp(betas[t] * logpdf)``) or ``"likelihood"`` (a :class:`DataDensity`: ``prior + betas[t] * S``)."""
+    if temper not in TEMPER_MODES:
+        raise ValueError("temper must be None, \"whole\" or \"likelihood\"")
+    cfg.temper_mode = TEMPER_MODES[temper]
     if betas is None and not ntemps:
         if beta_min is not None:
             raise ValueError("beta_min needs ntemps")
+        if temper == "likelihood":
+            raise ValueError("temper=\"likelihood\" needs a ladder: betas=, or ntemps= and beta_min=")
         cfg.betas, cfg.ntemps, cfg.swap_every = None, 0, 0
         return None
     if betas is None:
@@ -52,7 +64,7 @@ def apply_tempering(cfg, betas=None, ntemps=None, beta_min=None, swap_every=1):
             raise ValueError("ntemps needs beta_min (the ladder is geometric_betas(ntemps, beta_min)), or pass betas")
         b = geometric_betas(ntemps, beta_min)
     else:
-        b = check_betas(betas)
+        b = check_betas(betas, prior_rung=temper == "likelihood")
         if ntemps and int(ntemps) != b.size:
             raise ValueError("ntemps does not match len(betas)")
     if int(swap_every) != swap_every or int(swap_every) < 0:
@@ -61,3 +73,29 @@ def apply_tempering(cfg, betas=None, ntemps=None, beta_min=None, swap_every=1):
     cfg.ntemps = int(b.size)
     cfg.swap_every = int(swap_every)
     return b
+
+
+def thermodynamic_integration(betas, mean_loglike):
+    """``(logZ, err)``: the trapezoid of ``mean_loglike`` = ``<S>_beta`` over the ladder ``betas``, in ascending beta -- the
+    thermodynamic integral ``log Z = int_0^1 <S>_beta dbeta`` of a likelihood-tempered ladder (``Sampler.rung_loglike_mean()``) --
+    and ``|logZ - logZ of every second rung|`` (counted from ``beta = 1`` down), ptemcee's estimate of the discretisation error.
+    ``Z`` is the evidence when the prior is normalised and the ladder reaches ``beta = 0``; a ladder that stops at ``beta_min``
+    gives the integral from there.  Pure numpy: no device."""
+    b = np.asarray(betas, dtype=np.float64)
+    m = np.asarray(mean_loglike, dtype=np.float64)
+    if b.ndim != 1 or b.shape != m.shape or b.size < 2:
+        raise ValueError("betas and mean_loglike must be 1-D sequences of the same length (>= 2)")
+    order = np.argsort(-b, kind="stable")                  # from beta = 1 down, whatever order the ladder was given in
+    b, m = b[order], m[order]
+    if np.any(np.diff(b) >= 0):
+        raise ValueError("betas must be distinct")
+
+    def trapezoid(x, y):
+        x, y = x[::-1], y[::-1]                            # ascending beta
+        return float(np.sum(0.5 * (y[1:] + y[:-1]) * np.diff(x)))
+
+    b2, m2 = b[::2], m[::2]
+    if b2[-1] != b[-1]:                                    # every second rung, and the lowest one: the same interval
+        b2, m2 = np.append(b2, b[-1]), np.append(m2, m[-1])
+    logz = trapezoid(b, m)
+    return logz, abs(logz - trapezoid(b2, m2))
