@@ -214,6 +214,12 @@ typedef struct kmc_config {
     int32_t  deal_count;    /* sub-ensemble deal_rank of deal_count; 0 = off.  nwalkers is then THIS sub-ensemble's size */
     int32_t  temper_mode;   /* what a ladder tempers: KMC_TEMPER_WHOLE (0, the default) or KMC_TEMPER_LIKELIHOOD (needs ntemps >= 2, KMC_DATA_DENSITY) */
     int32_t  temper_pad_;
+    /* ADAPTIVE LADDER (opt-in; see the comment above kmc_sampler_get_ladder).  Zeroed: off.  (Here, in front of `move`: the struct's tail from `betas` on stays as it is.) */
+    int64_t  adapt_until;   /* the sweeps of generations g < adapt_until adapt the ladder; 0 -> nburnin; 0 .. nburnin */
+    double   adapt_lag;     /* ptemcee's adaptation_lag, in rounds: finite, > 0 (the bindings' default: 10000) */
+    double   adapt_time;    /* ptemcee's adaptation_time: finite, > 0 (the bindings' default: 100) */
+    int32_t  adapt;         /* 1: adapt the interior rungs during burn-in (needs ntemps >= 3, swap_every >= 1); 0: the ladder stays as given */
+    int32_t  adapt_pad_;
     /* (the snooker and mixture fields stand in front of `move`: the four fields from `move` on stay the struct's tail) */
     double   snooker_gamma; /* KMC_MOVE_SNOOKER: gamma of the proposal; 0 -> 1.7 */
     int32_t  mix_count;     /* KMC_MOVE_MIX: members, 2 .. KMC_MIX_MAX */
@@ -530,6 +536,29 @@ kmc_status  kmc_sampler_get_swaps(kmc_sampler* s, uint64_t* nswap_host);
  *                                     kmc_sampler_set_rung_state zeroes the sums, so call this after it */
 kmc_status  kmc_sampler_get_rung_loglike(kmc_sampler* s, double* loglike_host, double* logprior_host, double* loglike_sum_host);
 kmc_status  kmc_sampler_set_rung_loglike_sum(kmc_sampler* s, const double* loglike_sum_host);
+
+/* Adaptive ladder (kmc_config.adapt = 1; ntemps >= 3, swap_every >= 1; both temper modes, every move; DESIGN.md sections 2 and 4d).
+ * The sweep kernels move the interior rungs towards equal swap acceptance between all neighbouring pairs (Vousden, Farr & Mandel
+ * 2016, ptemcee's ladder dynamics) while the generation g of a sweep is < adapt_until; from adapt_until <= nburnin on the ladder is
+ * frozen, so every stored sample, moment and rung sum comes from one fixed ladder.  Sweeps alternate pair parity, so a ROUND is sweep n
+ * even followed by sweep n + 1, and tries every pair once.  A sweep with g < adapt_until adds its accepted exchanges per pair into
+ * round_acc; after the odd sweep n of round k = (n - 1) / 2 with g < adapt_until, with A_i = (double)round_acc[i] / (double)nwalkers,
+ * each operation rounded on its own:
+ *     kappa = (lag / ((double)k + lag)) / time
+ *     S'_j  = S_j + kappa * (A_{j-1} - A_j)                         j = 1 .. ntemps - 2
+ *     tau_0 = 1,  tau_j = tau_{j-1} + exp(S'_j),  beta'_j = 1 / tau_j
+ * S and the interior betas are replaced when every beta'_j is finite and 1 > beta'_1 > ... > beta'_{T-2} > beta_{T-1}; otherwise
+ * nothing is and `skipped` counts the round.  round_acc is zeroed either way.  beta_0 and beta_{T-1} never move.  S_j =
+ * log(1 / beta_j - 1 / beta_{j-1}) is state: computed once at creation from the caller's ladder, never derived from the betas again.
+ * The round number follows from the sweep number alone: the same run in every launch mode and across a checkpoint.
+ * kmc_sampler_set_positions starts the ladder again from the caller's.
+ *   kmc_sampler_get_ladder  any tempered sampler; any pointer may be NULL: the current betas [ntemps], S [ntemps - 2] (rung j's at
+ *                           j - 1), round_acc [ntemps - 1] and the rounds skipped
+ *   kmc_sampler_set_ladder  an adaptive sampler: a checkpoint's four values back in (all four are required; betas[0] and
+ *                           betas[ntemps - 1] must be the sampler's own).  kmc_sampler_set_rung_state starts the ladder again: call
+ *                           this after it */
+kmc_status  kmc_sampler_get_ladder(kmc_sampler* s, double* betas_host, double* S_host, uint64_t* round_acc_host, uint64_t* skipped_host);
+kmc_status  kmc_sampler_set_ladder(kmc_sampler* s, const double* betas_host, const double* S_host, const uint64_t* round_acc_host, const uint64_t* skipped_host);
 kmc_status  kmc_sampler_get_accept_ratio(kmc_sampler* s, double* host /* [nwalkers] */);
 kmc_status  kmc_sampler_get_moments(kmc_sampler* s, double* sum, double* sumsq /* [ndim] */, int64_t* n);
 /* Chain of this shard: [nsamples][nlocal][ndim] and [nsamples][nlocal]; nlocal = nwalkers /

@@ -54,7 +54,7 @@ SYMBOLS = [
     "kmc_user_density_create_body_blob", "kmc_user_density_nblob", "kmc_logpdf_blob_eval_host", "kmc_sampler_get_blobs",
     "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault", "kmc_data_density_create",
     "kmc_sampler_get_rung_state", "kmc_sampler_set_rung_state", "kmc_sampler_get_swaps",
-    "kmc_sampler_get_rung_loglike", "kmc_sampler_set_rung_loglike_sum",
+    "kmc_sampler_get_rung_loglike", "kmc_sampler_set_rung_loglike_sum", "kmc_sampler_get_ladder", "kmc_sampler_set_ladder",
 ]
 
 
@@ -84,6 +84,11 @@ class Config(C.Structure):
         ("deal_count", C.c_int32),
         ("temper_mode", C.c_int32),     # TEMPER_WHOLE or TEMPER_LIKELIHOOD (a DataDensity with a ladder)
         ("temper_pad_", C.c_int32),
+        ("adapt_until", C.c_int64),     # adaptive ladder: the sweeps of generations < adapt_until adapt it (0: nburnin)
+        ("adapt_lag", C.c_double),
+        ("adapt_time", C.c_double),
+        ("adapt", C.c_int32),           # 1: on
+        ("adapt_pad_", C.c_int32),
         ("snooker_gamma", C.c_double),
         ("mix_count", C.c_int32),
         # (the header's mix_move[4] ... mix_sigma[4], spelled out member by member like the Julia mirror)
@@ -218,6 +223,8 @@ def lib() -> C.CDLL:
     L.kmc_sampler_get_swaps.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.kmc_sampler_get_rung_loglike.argtypes = [vp, dp, dp, dp]
     L.kmc_sampler_set_rung_loglike_sum.argtypes = [vp, dp]
+    L.kmc_sampler_get_ladder.argtypes = [vp, dp, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.kmc_sampler_set_ladder.argtypes = [vp, dp, dp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.kmc_sampler_run.argtypes = [vp, C.c_int64]
     L.kmc_sampler_half_step.argtypes = [vp, C.c_int]
     L.kmc_sampler_sync.argtypes = [vp]

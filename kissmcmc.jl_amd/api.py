@@ -49,7 +49,7 @@ def emcee_counts(niter: int, nwalkers: int, nburnin=None, nthin: int = 1):
 def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_scale: float = 2.0,
           use_progress_meter: bool = True, hasblob: bool = False, init_blobs=None, reduce_blob=None,
           seed=None, device: int = 0, dtype: str = "f64", stream_chain=None, move=None,
-          betas=None, ntemps=None, beta_min=None, swap_every: int = 1, temper=None):
+          betas=None, ntemps=None, beta_min=None, swap_every: int = 1, temper=None, adapt=None):
     """The affine-invariant ensemble sampler, on one MI355X.  ``dtype="f32"`` keeps the walkers in single
     precision on the device (a throughput option, device densities; everything returned is still float64).
 
@@ -74,7 +74,9 @@ def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_sc
     generations; ``theta0s`` starts every rung and the returned tuple is rung 0's, the target itself (README "Parallel
     tempering"; device densities without blobs, ``dtype="f64"``).  ``temper="likelihood"`` (a ``DataDensity``) tempers only the
     likelihood -- rung ``t`` samples ``prior + betas[t] * S``, the last beta may be 0 (README "Likelihood tempering and the evidence";
-    the evidence itself comes from a ``Sampler``'s ``log_evidence()``).
+    the evidence itself comes from a ``Sampler``'s ``log_evidence()``).  ``adapt=True`` (or ``dict(lag=, time=, until=)``) lets the
+    sweeps of burn-in move the interior rungs towards equal swap acceptance between all pairs; the ladder is frozen before the first
+    stored sample (README "Adaptive ladder"; ``ntemps >= 3``, ``swap_every >= 1``).
 
     ``hasblob=True`` (``:150-151, :194-196``): ``pdf`` is a host callable returning ``(p, blob)``; the blobs
     stay on the host and follow the device's accept decisions.  ``blobs[w] = init_blobs(blob0s[w],
@@ -142,7 +144,7 @@ def emcee(pdf, theta0s, niter: int = 10 ** 5, nburnin=None, nthin: int = 1, a_sc
     # (host arrays that cannot be page-locked are no reason to fail: the library then stages the by-walker blocks itself)
     with Sampler(pdf, nwalkers, ndim, niter_walker, nburnin_walker, nthin, a_scale, seed, store_chain=True, store_logp=True,
                  device=device, dtype=dtype, stream_chain=bool(stream_chain), chain_by_walker=True, store_blobs=device_blobs, move=move,
-                 betas=betas, ntemps=ntemps, beta_min=beta_min, swap_every=swap_every, temper=temper) as s:
+                 betas=betas, ntemps=ntemps, beta_min=beta_min, swap_every=swap_every, temper=temper, adapt=adapt) as s:
         try:
             s.set_positions(theta0s)
         except _lib.KmcError as e:

@@ -1652,6 +1652,18 @@ struct TemperSweepLikeArgs {
     double*         prior;        // [ntemps][nwalkers] its log-prior
     double*         like_sum;     // [ntemps] sum of the stored states' S
 };
+// ... of an adaptive ladder (kmc_config.adapt): either form's arguments (like == nullptr: the whole mode), then the ladder's state
+struct TemperSweepAdaptArgs {
+    TemperSweepLikeArgs la;
+    double*             betas;        // [ntemps] the table the half-step kernels read; la.a.betas, writable
+    double*             S;            // [ntemps - 2] S_j = log(1 / beta_j - 1 / beta_{j-1}) of rung j at j - 1
+    double*             stage;        // [2][ntemps] a round's candidate S' and betas until they have passed the check
+    unsigned long long* round_acc;    // [ntemps - 1] accepted exchanges per pair in the round under way
+    unsigned int*       ticket;       // blocks of this sweep that have decided their pair
+    unsigned long long* skipped;      // rounds whose update was not committed
+    int64_t             adapt_until;
+    double              lag, time;
+};
 
 // Non-template kernels of the host driver: each group is defined once, in the translation unit that launches it.
 #ifdef KMC_DEFINE_LAUNCH_KERNELS   // kmc_launch.hip
@@ -1848,6 +1860,165 @@ __global__ __launch_bounds__(256) void temper_sweep_like(const TemperSweepLikeAr
     if ((sch.flags & kCount) != 0) {
         const double c = block_sum256((threadIdx.x & 63) == 0 ? (double)__popcll(mask) : 0.0, red);
         if (threadIdx.x == 0 && c != 0.0) atomicAdd(&a.nswap[t], (unsigned long long)c);
+    }
+    if (mask == 0ull) return;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t wbase = (int64_t)blockIdx.x * 256 + (int64_t)(threadIdx.x & ~63u);
+    const int nchunk = a.ld >> 1;
+    double2* const r_lo = reinterpret_cast<double2*>(a.pos + ((int64_t)t * nw + wbase) * a.ld);
+    double2* const r_hi = reinterpret_cast<double2*>(a.pos + ((int64_t)(t + 1) * nw + wbase) * a.ld);
+    const bool credit = t == 0 && a.msum != nullptr;
+    for (int idx = lane; idx < 64 * nchunk; idx += 64) {                 // (the same trip count in every lane)
+        const int wl = idx / nchunk;
+        const uint32_t wq = credit ? (uint32_t)__shfl((int)wgt, wl) : 0u;
+        if ((mask >> wl) & 1ull) {
+            const double2 x = r_lo[idx], y = r_hi[idx];
+            r_lo[idx] = y;
+            r_hi[idx] = x;
+            if (wq != 0u) {
+                const int d = 2 * (idx - wl * nchunk);
+                const double wd = (double)wq;
+                atomicAdd(&a.msum[d], x.x * wd);
+                atomicAdd(&a.msum[d + 1], x.y * wd);
+                atomicAdd(&a.msum[a.ld + d], (x.x * x.x) * wd);
+                atomicAdd(&a.msum[a.ld + d + 1], (x.y * x.y) * wd);
+            }
+        }
+    }
+}
+
+// The adaptive ladder's rule (include/kissmcmc_hip.h above kmc_sampler_get_ladder), after the odd sweep n: one
+// lane, ONE serial pass of at most 62 steps (a load of round_acc, an exp and a division each).  The candidate ladder goes into a staging
+// area behind S in global memory (no array of the lane's own: no scratch memory); where it passes the check, a second loop without any
+// dependent arithmetic copies it over S and the betas.  round_acc was summed by agent-scope atomics and is read (once per rung) and
+// zeroed the same way; S, the staging area, the betas and the skip counter are this lane's alone until the kernel ends.
+__device__ __forceinline__ void adapt_ladder_update(const TemperSweepAdaptArgs& ad, int ntemps, int nwalkers, uint64_t n)
+{
+    const double kappa = (ad.lag / ((double)((n - 1ull) >> 1) + ad.lag)) / ad.time;
+    const double nwd = (double)nwalkers;
+    double* const S_new = ad.stage;
+    double* const b_new = ad.stage + ntemps;
+    bool ok = true;
+    double tau = 1.0, b_prev = 1.0;
+    double a_prev = (double)__hip_atomic_load(&ad.round_acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / nwd;
+    __hip_atomic_store(&ad.round_acc[0], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll 1
+    for (int j = 1; j + 1 < ntemps; ++j) {
+        const double a_j = (double)__hip_atomic_load(&ad.round_acc[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / nwd;
+        __hip_atomic_store(&ad.round_acc[j], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double s = ad.S[j - 1] + kappa * (a_prev - a_j);
+        tau = tau + exp(s);
+        const double b = 1.0 / tau;
+        ok = ok && isfinite(b) && b < b_prev;
+        S_new[j - 1] = s;
+        b_new[j] = b;
+        b_prev = b;
+        a_prev = a_j;
+    }
+    ok = ok && b_prev > ad.betas[ntemps - 1];
+    if (!ok) { *ad.skipped += 1ull; return; }
+#pragma unroll 1
+    for (int j = 1; j + 1 < ntemps; ++j) {
+        ad.S[j - 1] = S_new[j - 1];
+        ad.betas[j] = b_new[j];
+    }
+}
+
+// The sweep of an adaptive ladder (kmc_config.adapt), both forms: temper_sweep / temper_sweep_like statement for statement, plus, while
+// the sweep's generation is < adapt_until: every block that decides a pair adds its accepted count into round_acc[t] (one integer atomic:
+// exact and order-free), fences, and draws a ticket; the block that draws the last one, gridDim.x * npairs(parity) - 1, resets the ticket
+// and, on an odd sweep, runs the rule in one lane.  Every block has read its two betas before its ticket, so nobody reads a half-written
+// table; the next half-step's kernels follow in stream order.  From adapt_until on it does what the plain kernels do.
+template <bool LIKE>
+__global__ __launch_bounds__(256) void temper_sweep_adapt(const TemperSweepAdaptArgs ad)
+{
+    const TemperSweepArgs& a = ad.la.a;
+    double* const like = ad.la.like;
+    double* const prior = ad.la.prior;
+    double* const like_sum = ad.la.like_sum;
+    __shared__ double red[4];
+    const SchedEntry sch = a.sched_index >= 0 ? a.sched_table[a.sched_index] : a.sched_inline;
+    const bool stored = (sch.flags & kSample) != 0;
+    const int64_t g1 = sch.gen + 1;
+    const bool sweep = a.swap_every > 0 && g1 % a.swap_every == 0;
+    if (!stored && !sweep) return;
+    const uint64_t n = sweep ? (uint64_t)(g1 / a.swap_every - 1) : 0ull;
+    const int par = (int)(n & 1ull);
+    const int t = (int)blockIdx.y;
+    if (sweep && t >= 1 && ((t - 1) & 1) == par) return;                 // the upper rung of a pair: rung t - 1's block row has it
+    const bool lower = sweep && (t & 1) == par && t + 1 < a.ntemps;
+    const bool adapting = (int64_t)sch.gen < ad.adapt_until;
+    const int64_t nw = a.nwalkers;
+    const int w = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool valid = w < a.nwalkers;
+    double* const lp_lo = a.logp + 2 * (int64_t)t * nw;
+    double* const lp_hi = lp_lo + 2 * nw;
+    const double p_lo = valid ? lp_lo[w] : 0.0;
+    const double p_hi = (lower && valid) ? lp_hi[w] : 0.0;
+    double l_lo = 0.0, l_hi = 0.0;
+    if constexpr (LIKE) {
+        l_lo = valid ? like[(int64_t)t * nw + w] : 0.0;
+        l_hi = (lower && valid) ? like[(int64_t)(t + 1) * nw + w] : 0.0;
+    }
+    if (stored) {
+        const double s_lo = block_sum256(p_lo, red);
+        if (threadIdx.x == 0) atomicAdd(&a.logp_sum[t], s_lo);
+        if (lower) {
+            const double s_hi = block_sum256(p_hi, red);
+            if (threadIdx.x == 0) atomicAdd(&a.logp_sum[t + 1], s_hi);
+        }
+        if constexpr (LIKE) {
+            const double ls_lo = block_sum256(l_lo, red);
+            if (threadIdx.x == 0) atomicAdd(&like_sum[t], ls_lo);
+            if (lower) {
+                const double ls_hi = block_sum256(l_hi, red);
+                if (threadIdx.x == 0) atomicAdd(&like_sum[t + 1], ls_hi);
+            }
+        }
+    }
+    if (!lower) return;
+    bool acc = false;
+    if (valid) {
+        const double lu = temper_swap_logu(a.seed_lo, a.seed_hi, n, (uint32_t)w, (uint32_t)t);
+        if constexpr (LIKE) acc = (a.betas[t] - a.betas[t + 1]) * (l_hi - l_lo) >= lu;            // (the priors cancel)
+        else acc = (a.betas[t] - a.betas[t + 1]) * (p_hi - p_lo) >= lu;
+    }
+    uint32_t wgt = 0u;                                                   // samples the walker leaving rung 0 stood for
+    if (acc) {
+        lp_lo[w] = p_hi;
+        lp_hi[w] = p_lo;
+        if constexpr (LIKE) {
+            double* const pr_lo = prior + (int64_t)t * nw;
+            const double r_lo = pr_lo[w], r_hi = pr_lo[nw + w];
+            pr_lo[w] = r_hi;
+            pr_lo[nw + w] = r_lo;
+            like[(int64_t)t * nw + w] = l_hi;
+            like[(int64_t)(t + 1) * nw + w] = l_lo;
+        }
+        if (t == 0 && a.msum != nullptr) {
+            uint32_t* const klast = reinterpret_cast<uint32_t*>(lp_lo + nw) + nw;
+            const uint32_t nb1 = sch.nbefore + (stored ? 1u : 0u);      // samples taken by the generations up to this one
+            wgt = nb1 - klast[w];
+            klast[w] = nb1;
+        }
+    }
+    const unsigned long long mask = __ballot(acc);
+    const bool count = (sch.flags & kCount) != 0;
+    if (count || adapting) {
+        const double c = block_sum256((threadIdx.x & 63) == 0 ? (double)__popcll(mask) : 0.0, red);
+        if (threadIdx.x == 0) {
+            if (count && c != 0.0) atomicAdd(&a.nswap[t], (unsigned long long)c);
+            if (adapting) {
+                if (c != 0.0) atomicAdd(&ad.round_acc[t], (unsigned long long)c);
+                __threadfence();
+                const unsigned int last = gridDim.x * (unsigned int)((a.ntemps - par) >> 1) - 1u;      // blocks that decide a pair of this parity
+                if (atomicAdd(ad.ticket, 1u) == last) {
+                    __threadfence();                                     // (the acquire side of the fence above: every block's count is in round_acc)
+                    __hip_atomic_store(ad.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (par == 1) adapt_ladder_update(ad, a.ntemps, a.nwalkers, n);
+                }
+            }
+        }
     }
     if (mask == 0ull) return;
     const int lane = (int)(threadIdx.x & 63);

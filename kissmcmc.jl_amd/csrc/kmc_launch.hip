@@ -174,7 +174,22 @@ hipError_t launch_temper_sweep(const kmc_sampler* s, const HalfStepArgs& a, bool
     t.seed_lo = a.dc.seed_lo;
     t.seed_hi = a.dc.seed_hi;
     const dim3 grid((unsigned)((s->nrows + 255) / 256), (unsigned)s->ntemps);
-    if (s->temper_like) hipLaunchKernelGGL(temper_sweep_like, grid, dim3(256), 0, s->stream, TemperSweepLikeArgs{t, s->d_like, s->d_prior, s->d_like_sum});
+    if (s->adapt) {                                                      // the adaptive ladder's forms: the same sweep, and the rule in its tail
+        TemperSweepAdaptArgs ad{};
+        ad.la = TemperSweepLikeArgs{t, s->d_like, s->d_prior, s->d_like_sum};
+        ad.betas = s->d_betas;
+        ad.S = s->d_S;
+        ad.stage = s->d_stage;
+        ad.round_acc = s->d_round_acc;
+        ad.ticket = s->d_ticket;
+        ad.skipped = s->d_skipped;
+        ad.adapt_until = s->cfg.adapt_until;
+        ad.lag = s->cfg.adapt_lag;
+        ad.time = s->cfg.adapt_time;
+        if (s->temper_like) hipLaunchKernelGGL(temper_sweep_adapt<true>, grid, dim3(256), 0, s->stream, ad);
+        else hipLaunchKernelGGL(temper_sweep_adapt<false>, grid, dim3(256), 0, s->stream, ad);
+    }
+    else if (s->temper_like) hipLaunchKernelGGL(temper_sweep_like, grid, dim3(256), 0, s->stream, TemperSweepLikeArgs{t, s->d_like, s->d_prior, s->d_like_sum});
     else hipLaunchKernelGGL(temper_sweep, grid, dim3(256), 0, s->stream, t);
     *launched = true;
     return hipGetLastError();

@@ -179,6 +179,16 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
         if (!what && c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) what = "a density with blobs";
         if (what) return fail(KMC_ERR_UNSUPPORTED, std::string("parallel tempering (ntemps >= 2): a ladder of ensembles on one GPU with double rows and a device density -- not with ") + what);
     }
+    if (c->adapt != 0) {
+        if (c->adapt != 1) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt must be 0 or 1");
+        if (c->ntemps < 2) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt needs a ladder (parallel tempering: betas, ntemps)");
+        if (c->ntemps < 3) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: ntemps must be >= 3 (the first and the last rung never move)");
+        if (c->swap_every == 0) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: swap_every must be >= 1 (the ladder adapts to the swap sweeps' acceptance)");
+        if (c->adapt_until < 0 || c->adapt_until > c->nburnin)
+            return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt_until must be 0 .. nburnin (0: nburnin) -- every stored sample comes from the frozen ladder");
+        if (!std::isfinite(c->adapt_lag) || !(c->adapt_lag > 0.0)) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt_lag must be finite and > 0");
+        if (!std::isfinite(c->adapt_time) || !(c->adapt_time > 0.0)) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt_time must be finite and > 0");
+    }
     if (c->deal_count < 0 || (c->deal_count > 0 && (c->deal_rank < 0 || c->deal_rank >= c->deal_count)))
         return fail(KMC_ERR_BAD_ARG, "deal_rank / deal_count out of range");
     if (c->deal_count > 0) {
@@ -391,6 +401,10 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     if (s->temper) s->betas.assign(cfg->betas, cfg->betas + cfg->ntemps);          // (the caller's array is copied here)
     s->cfg.betas = s->temper ? s->betas.data() : nullptr;
     s->temper_like = s->temper && cfg->temper_mode == KMC_TEMPER_LIKELIHOOD;
+    s->adapt = s->temper && cfg->adapt != 0;
+    if (s->adapt && s->cfg.adapt_until == 0) s->cfg.adapt_until = cfg->nburnin;
+    for (int j = 1; s->temper && j + 1 < s->ntemps; ++j)                             // (state from here on: never derived from the betas again)
+        s->S0.push_back(std::log(1.0 / s->betas[(size_t)j] - 1.0 / s->betas[(size_t)j - 1]));
     if (cfg->deal_count > 0) s->cfg.seed = deal_seed(cfg->seed, cfg->deal_rank);    // this sub-ensemble's Philox key
     if (s->cfg.shard_count <= 0) s->cfg.shard_count = 1;
     s->h = cfg->nwalkers / 2;
@@ -633,12 +647,18 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     }
     const size_t nt = (size_t)s->ntemps;                              // rungs: every per-walker array below holds nt ensembles
     if (s->temper) {
-        const size_t nb = (2 * nt + 2 * (size_t)s->ld) * sizeof(double);
+        const size_t nb = (2 * nt + 2 * (size_t)s->ld + 2 * nt + 2 + 2 * nt) * sizeof(double);
         CREATE_TRY(dev_alloc(s, &s->d_betas, nb));
         CREATE_TRY(hipMemsetAsync(s->d_betas, 0, nb, s->stream));
         CREATE_TRY(copy_sync(s->d_betas, s->betas.data(), nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
         s->d_rung_sum = s->d_betas + nt;
         s->d_tsum = s->d_rung_sum + nt;
+        s->d_S = s->d_tsum + 2 * (size_t)s->ld;
+        s->d_round_acc = reinterpret_cast<unsigned long long*>(s->d_S + nt);
+        s->d_ticket = reinterpret_cast<unsigned int*>(s->d_round_acc + nt);
+        s->d_skipped = s->d_round_acc + nt + 1;
+        s->d_stage = reinterpret_cast<double*>(s->d_skipped + 1);
+        if (!s->S0.empty()) CREATE_TRY(copy_sync(s->d_S, s->S0.data(), s->S0.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
         CREATE_TRY(dev_alloc(s, (void**)&s->d_nswap, nt * sizeof(unsigned long long)));
         CREATE_TRY(hipMemsetAsync(s->d_nswap, 0, nt * sizeof(unsigned long long), s->stream));
     }
@@ -1036,7 +1056,12 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
           << (s->plan.vec ? "half_step_temper_vec" : "half_step_temper_generic") << ", betas 1 .. ";
         char b[64];
         std::snprintf(b, sizeof(b), "%.6g", s->betas.back());
-        o << b << ", swap sweep " << (s->cfg.swap_every > 0 ? "every " + std::to_string(s->cfg.swap_every) + " generations (" + (s->temper_like ? "temper_sweep_like" : "temper_sweep") + ")" : std::string("off"));
+        o << b << ", swap sweep " << (s->cfg.swap_every > 0 ? "every " + std::to_string(s->cfg.swap_every) + " generations (" + (s->adapt ? (s->temper_like ? "temper_sweep_adapt<like>" : "temper_sweep_adapt<whole>") : s->temper_like ? "temper_sweep_like" : "temper_sweep") + ")" : std::string("off"));
+        if (s->adapt) {
+            char ab[96];
+            std::snprintf(ab, sizeof(ab), ", lag %.6g, time %.6g", s->cfg.adapt_lag, s->cfg.adapt_time);
+            o << "; adaptive ladder: until generation " << s->cfg.adapt_until << ab << " (betas above: the initial ladder)";
+        }
         if (s->temper_like) o << "; likelihood tempering: rung t samples prior + beta_t S, four launches per half-step for the whole ladder";
         if (s->temper_updated_fallback) o << "; KMC_LAUNCH=updated asked for: the updated-graph mode is not built for tempered samplers, fell back to the table graph";
     }

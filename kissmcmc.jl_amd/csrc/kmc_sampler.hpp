@@ -203,9 +203,17 @@ struct kmc_sampler {
     bool temper = false;
     bool temper_updated_fallback = false;                // KMC_LAUNCH=updated was asked for: a tempered sampler replays the table graph instead
     std::vector<double> betas;
-    double* d_betas = nullptr;                           // [ntemps], then logp_sum [ntemps], then the moments credited at exchanges [2][ld] (one allocation)
+    double* d_betas = nullptr;                           // [ntemps], then logp_sum [ntemps], then the moments credited at exchanges [2][ld], then the ladder's state (one allocation)
     double* d_rung_sum = nullptr;
     double* d_tsum = nullptr;
+    // adaptive ladder (kmc_config.adapt): behind d_tsum, 8 bytes each -- S [ntemps], round_acc [ntemps], the ticket, the rounds skipped, the staging area [2][ntemps]
+    bool adapt = false;
+    std::vector<double> S0;                              // [ntemps - 2] S_j = log(1 / beta_j - 1 / beta_{j-1}) of the caller's ladder (`betas` above keeps that ladder)
+    double* d_S = nullptr;
+    unsigned long long* d_round_acc = nullptr;
+    unsigned int* d_ticket = nullptr;
+    unsigned long long* d_skipped = nullptr;
+    double* d_stage = nullptr;
     unsigned long long* d_nswap = nullptr;               // [ntemps - 1]
     kmc::MixTable* d_mix = nullptr;                                     // KMC_MOVE_MIX: the members' table (kmc_host.hpp: mix_table_of)
     bool stream_by_walker = false;                       // KMC_STREAM_CHAIN | KMC_CHAIN_BY_WALKER: host buffers are [walker][nsamples][..]

@@ -107,6 +107,12 @@ kmc_status reset_temper_counters(kmc_sampler* s, const uint64_t* nswap, const do
     HIP_TRY(copy_sync(s->d_nswap, ns.data(), nt * sizeof(unsigned long long), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(copy_sync(s->d_rung_sum, ls.data(), ls.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
     if (s->temper_like) HIP_TRY(fill_sync(s->d_like_sum, 0, nt * sizeof(double), s->stream));      // (a checkpoint's: kmc_sampler_set_rung_loglike_sum)
+    if (s->adapt) {                                                        // the ladder starts again from the caller's (a checkpoint's: kmc_sampler_set_ladder)
+        std::vector<double> z(2 * nt + 2, 0.0);                            // S, then round_acc, the ticket and the rounds skipped: zero
+        for (size_t j = 0; j < s->S0.size(); ++j) z[j] = s->S0[j];
+        HIP_TRY(copy_sync(s->d_betas, s->betas.data(), nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(copy_sync(s->d_S, z.data(), z.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    }
     return KMC_OK;
 }
 // Likelihood tempering: S and the prior of every walker of every rung from the rows in place -- one pass of the data kernels over
@@ -447,6 +453,53 @@ KMC_EXPORT kmc_status kmc_sampler_get_swaps(kmc_sampler* s, uint64_t* nswap_host
     std::vector<unsigned long long> ns((size_t)s->ntemps);
     HIP_TRY(copy_sync(ns.data(), s->d_nswap, ns.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
     for (int t = 0; t + 1 < s->ntemps; ++t) nswap_host[t] = (uint64_t)ns[(size_t)t];
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_get_ladder(kmc_sampler* s, double* betas_host, double* S_host, uint64_t* round_acc_host, uint64_t* skipped_host)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_ladder: the sampler was created without parallel tempering (ntemps < 2)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const size_t nt = (size_t)s->ntemps;
+    if (betas_host) HIP_TRY(copy_sync(betas_host, s->d_betas, nt * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (S_host && nt > 2) HIP_TRY(copy_sync(S_host, s->d_S, (nt - 2) * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (round_acc_host) {
+        std::vector<unsigned long long> ra(nt);
+        HIP_TRY(copy_sync(ra.data(), s->d_round_acc, nt * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
+        for (size_t t = 0; t + 1 < nt; ++t) round_acc_host[t] = (uint64_t)ra[t];
+    }
+    if (skipped_host) {
+        unsigned long long sk = 0ull;
+        HIP_TRY(copy_sync(&sk, s->d_skipped, sizeof(sk), hipMemcpyDeviceToHost, s->stream));
+        *skipped_host = (uint64_t)sk;
+    }
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_set_ladder(kmc_sampler* s, const double* betas_host, const double* S_host, const uint64_t* round_acc_host, const uint64_t* skipped_host)
+{
+    if (!s || !betas_host || !S_host || !round_acc_host || !skipped_host) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (!s->adapt) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_set_ladder: the sampler was created without an adaptive ladder (kmc_config.adapt); a fixed ladder is set at creation");
+    const size_t nt = (size_t)s->ntemps;
+    if (betas_host[0] != 1.0 || betas_host[nt - 1] != s->betas[nt - 1])
+        return fail(KMC_ERR_BAD_ARG, "adaptive ladder: kmc_sampler_set_ladder: the first and the last beta never move -- they must be the sampler's own");
+    for (size_t t = 1; t < nt; ++t)
+        if (!std::isfinite(betas_host[t]) || !(betas_host[t] < betas_host[t - 1]))
+            return fail(KMC_ERR_BAD_ARG, "adaptive ladder: kmc_sampler_set_ladder: betas must be finite and strictly decreasing");
+    for (size_t j = 0; j + 2 < nt; ++j)
+        if (std::isnan(S_host[j])) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: kmc_sampler_set_ladder: S must not be NaN");
+    for (size_t t = 0; t + 1 < nt; ++t)
+        if (round_acc_host[t] > (uint64_t)s->nrows) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: kmc_sampler_set_ladder: round_acc counts at most nwalkers exchanges per pair");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::vector<unsigned long long> tail(nt + 2, 0ull);                    // round_acc, then the ticket (0: between sweeps) and the rounds skipped
+    for (size_t t = 0; t + 1 < nt; ++t) tail[t] = (unsigned long long)round_acc_host[t];
+    tail[nt + 1] = (unsigned long long)*skipped_host;
+    HIP_TRY(copy_sync(s->d_betas, betas_host, nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(copy_sync(s->d_S, S_host, (nt - 2) * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(copy_sync(s->d_round_acc, tail.data(), tail.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s->stream));
     return KMC_OK;
 }
 

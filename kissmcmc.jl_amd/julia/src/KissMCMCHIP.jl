@@ -53,6 +53,11 @@ Base.@kwdef struct KmcConfig
     deal_count::Int32 = 0
     temper_mode::Int32 = 0                            # what a ladder tempers: KMC_TEMPER_WHOLE = 0, KMC_TEMPER_LIKELIHOOD = 1 (data densities)
     temper_pad_::Int32 = 0
+    adapt_until::Int64 = 0                            # adaptive ladder: the sweeps of generations < adapt_until adapt it; 0 -> nburnin
+    adapt_lag::Float64 = 0.0                          # ptemcee's adaptation_lag (rounds): finite, > 0
+    adapt_time::Float64 = 0.0                         # ptemcee's adaptation_time: finite, > 0
+    adapt::Int32 = 0                                  # 1: adapt the interior rungs during burn-in (ntemps >= 3, swap_every >= 1)
+    adapt_pad_::Int32 = 0
     snooker_gamma::Float64 = 0.0                      # KMC_MOVE_SNOOKER: 0 -> 1.7
     mix_count::Int32 = 0                              # KMC_MOVE_MIX: 2 .. 4 members (the header's mix_move[4] ... mix_sigma[4], member by member)
     mix_move0::Int32 = 0
@@ -254,7 +259,8 @@ end
 """
     emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter÷2, nthin=1, a_scale=2.0,
           use_progress_meter=true, hasblob=false, init_blobs, reduce_blob!, seed=rand(UInt64), device=0, dtype=:f64,
-          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1, temper=:whole)
+          move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1, temper=:whole,
+          adapt=false, adapt_lag=10000.0, adapt_time=100.0, adapt_until=0)
 
 Same meaning as KissMCMC.emcee (src/samplers.jl:188-197); returns
 `(thetas, accept_ratio, logdensities, blobs)` with `thetas[w][k]` (src/samplers.jl:292).
@@ -268,17 +274,21 @@ one member per half-step, each with `de_gamma0` / `de_sigma` or `snooker_gamma`)
 `exp(betas[t] * logpdf)`, neighbouring rungs exchanging walkers every `swap_every` generations; `theta0s` starts every rung and
 the returned tuple is rung 1's (`betas[1] == 1`, the target itself).  `temper=:likelihood` (KMC_TEMPER_LIKELIHOOD) tempers only the
 likelihood of a data density -- rung t samples `prior + betas[t] * S`, and the last beta may be 0 --; the library refuses it for
-every other density.
+every other density.  `adapt=true` (KMC's adaptive ladder; `length(betas) >= 3`, `swap_every >= 1`) lets the swap sweeps of burn-in move
+the interior rungs towards equal swap acceptance between all neighbouring pairs (ptemcee's dynamics with `adapt_lag`, `adapt_time`)
+until generation `adapt_until` (0: `nburnin ÷ nwalkers`, the end of burn-in); every stored sample comes from the frozen ladder.
 """
 function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1, a_scale=2.0,
                use_progress_meter=true, hasblob=false,
                init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),      # init_output_vector :80-85
                reduce_blob! =(blobs, blob) -> push!(blobs, blob),                         # :196
                seed=rand(UInt64), device=0, dtype=:f64,     # dtype=:f32: float rows on the device (KMC_F32), built-in densities
-               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1, temper=:whole)
+               move=:stretch, de_gamma0=0.0, de_sigma=1e-5, snooker_gamma=1.7, betas=Float64[], swap_every=1, temper=:whole,
+               adapt=false, adapt_lag=10000.0, adapt_time=100.0, adapt_until=0)
     ladder = collect(Float64, betas)                      # (kept alive across the call: GC.@preserve below)
     temper in (:whole, :likelihood) || error("temper must be :whole or :likelihood")
     temper == :whole || !isempty(ladder) || error("temper=:likelihood needs a ladder (betas)")
+    !adapt || length(ladder) >= 3 || error("adapt=true needs a ladder of at least 3 rungs (betas)")
     isempty(ladder) || (length(ladder) >= 2 && ladder[1] == 1.0 && all(diff(ladder) .< 0) && all(isfinite, ladder) &&
                         (ladder[end] > 0 || (temper == :likelihood && ladder[end] == 0))) ||
         error("betas must start at 1 and decrease strictly, finite and > 0 (temper=:likelihood: the last one may be 0)")
@@ -350,7 +360,9 @@ function emcee(pdf::DeviceLogPdf, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin
                             mix_gamma0=mix_g(1), mix_gamma1=mix_g(2), mix_gamma2=mix_g(3), mix_gamma3=mix_g(4),
                             mix_sigma0=mix_s(1), mix_sigma1=mix_s(2), mix_sigma2=mix_s(3), mix_sigma3=mix_s(4),
                             betas=(isempty(ladder) ? Ptr{Float64}(C_NULL) : pointer(ladder)), ntemps=Int32(length(ladder)),
-                            swap_every=Int32(isempty(ladder) ? 0 : swap_every), temper_mode=(temper == :likelihood ? KMC_TEMPER_LIKELIHOOD : KMC_TEMPER_WHOLE)))
+                            swap_every=Int32(isempty(ladder) ? 0 : swap_every), temper_mode=(temper == :likelihood ? KMC_TEMPER_LIKELIHOOD : KMC_TEMPER_WHOLE),
+                            adapt=Int32(adapt ? 1 : 0), adapt_until=Int64(adapt ? adapt_until : 0), adapt_lag=Float64(adapt ? adapt_lag : 0.0),
+                            adapt_time=Float64(adapt ? adapt_time : 0.0)))
         st = GC.@preserve pdf theta chain clogp acc bl ladder ccall((:kmc_emcee_run, LIB), Cint,
                                                        (Ref{KmcConfig}, Ptr{Float64}, Ref{KmcOutputs}), cfg, theta, out)
         (st == 9 && by_walker && occursin("KMC_CHAIN_BY_WALKER", last_error())) || break

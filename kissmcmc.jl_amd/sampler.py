@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from .densities import DeviceLogPdf
 from .moves import apply_move
-from .tempering import apply_tempering, thermodynamic_integration
+from .tempering import apply_adapt, apply_tempering, thermodynamic_integration
 
 
 def _dp(a):
@@ -27,7 +27,7 @@ class Sampler:
                  island_gens: int = 0, island_size: int = 0, p2p_finegrained: bool = False, p2p_push: bool = False,
                  dtype: str = "f64", deal_rank: int = 0, deal_count: int = 0,
                  stream_chain: bool = False, chain_by_walker: bool = False, store_blobs: bool = False, move=None,
-                 betas=None, ntemps=None, beta_min=None, swap_every: int = 1, temper=None):
+                 betas=None, ntemps=None, beta_min=None, swap_every: int = 1, temper=None, adapt=None):
         if not isinstance(pdf, DeviceLogPdf):
             raise TypeError(
                 "pdf must be a menu log-density (GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2), "
@@ -86,9 +86,12 @@ class Sampler:
         # parallel tempering (opt-in): betas=[1, ...], or ntemps= and beta_min= for geometric_betas(ntemps, beta_min); every read-out
         # below stays rung 0's, the rung_* methods return the whole ladder
         # temper="likelihood" (a DataDensity): rung t samples prior + betas[t] * S, the last beta may be 0; rung_loglike*, log_evidence
-        self.betas = apply_tempering(cfg, betas, ntemps, beta_min, swap_every, temper)
-        self.temper = "likelihood" if cfg.temper_mode == _lib.TEMPER_LIKELIHOOD else ("whole" if self.betas is not None else None)
-        self.ntemps = 1 if self.betas is None else int(self.betas.size)
+        # adapt=True or dict(lag=, time=, until=): the sweeps of burn-in move the interior rungs towards equal swap acceptance (README
+        # "Adaptive ladder"); `betas` is then the current ladder, `betas0` the one given here
+        self.betas0 = apply_tempering(cfg, betas, ntemps, beta_min, swap_every, temper)
+        self.adapt = apply_adapt(cfg, adapt)
+        self.temper = "likelihood" if cfg.temper_mode == _lib.TEMPER_LIKELIHOOD else ("whole" if self.betas0 is not None else None)
+        self.ntemps = 1 if self.betas0 is None else int(self.betas0.size)
         cfg.user_density = pdf.user_handle     # runtime-compiled density (ExprDensity) or None
         cb = getattr(pdf, "c_callback", None)  # host-evaluated density (HostLogPdf) or None
         if cb is not None:
@@ -234,7 +237,7 @@ class Sampler:
     def set_positions(self, theta):
         """``[nwalkers, ndim]``; a tempered sampler copies it to every rung, or takes ``[ntemps, nwalkers, ndim]``."""
         theta = np.asarray(theta, dtype=np.float64)
-        if self.betas is not None and theta.ndim == 3:
+        if self.betas0 is not None and theta.ndim == 3:
             theta = np.ascontiguousarray(theta.reshape(self.ntemps, self.nwalkers, self.ndim))
             _lib.check(self._L.kmc_sampler_set_rung_state(self._h, _dp(theta), None, None, None, None, 0))
             return
@@ -243,7 +246,7 @@ class Sampler:
 
     # -- parallel tempering: the whole ladder (leading axis: the rung) -------------------------
     def _need_ladder(self):
-        if self.betas is None:
+        if self.betas0 is None:
             raise ValueError("this sampler was created without parallel tempering (betas= / ntemps=)")
 
     def _rung_state(self, pos=False, logp=False, naccept=False, logp_sum=False):
@@ -257,6 +260,28 @@ class Sampler:
                                                       None if na is None else na.ctypes.data_as(C.POINTER(C.c_int64)),
                                                       None if ls is None else _dp(ls)))
         return p, lp, na, ls
+
+    def _ladder(self):
+        """``(betas [T], S [T - 2], round_acc [T - 1], skipped)`` as the device holds them (kmc_sampler_get_ladder)."""
+        self._need_ladder()
+        T = self.ntemps
+        b, S = np.zeros(T), np.zeros(max(T - 2, 0))
+        ra, sk = np.zeros(T - 1, dtype=np.uint64), C.c_uint64(0)
+        _lib.check(self._L.kmc_sampler_get_ladder(self._h, _dp(b), _dp(S) if T > 2 else None, ra.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(sk)))
+        return b, S, ra, int(sk.value)
+
+    @property
+    def betas(self):
+        """The ladder: the array given at creation, or, with ``adapt=``, the current one read from the device (frozen from
+        ``adapt_until`` on; :attr:`betas0` stays the initial ladder).  ``None`` without tempering."""
+        if not self.adapt or self._h is None:
+            return self.betas0
+        return self._ladder()[0]
+
+    @property
+    def adapt_skipped(self) -> int:
+        """Rounds whose ladder update was not committed (it would not have left the ladder strictly decreasing)."""
+        return self._ladder()[3]
 
     def rung_positions(self) -> np.ndarray:
         """``[ntemps, nwalkers, ndim]``: every rung's ensemble (rung 0 is :meth:`positions`)."""
@@ -376,18 +401,20 @@ class Sampler:
 
     def state(self):
         """Checkpoint: ``dict(positions, logp, naccept, generation)`` (synchronises)."""
-        if self.betas is not None:            # every rung, the swap counters and the log-density sums
+        if self.betas0 is not None:            # every rung, the swap counters and the log-density sums
             p, lp, na, ls = self._rung_state(True, True, True, True)
             st = dict(positions=p, logp=lp, naccept=na, generation=self.generation, nswap=self.nswap(), rung_logp_sum=ls)
             if self.temper == "likelihood":   # (S and the prior per walker are evaluated again from the positions at restore: the same bits)
                 st["rung_loglike_sum"] = self.rung_loglike_sum()
+            if self.adapt:                    # the ladder as it stands, a half-finished round's counts included
+                st["betas"], st["S"], st["round_acc"], st["skipped"] = self._ladder()
             return st
         return dict(positions=self.positions(), logp=self.logp(), naccept=self.naccept(), generation=self.generation)
 
     def restore(self, state):
         """Resume from :meth:`state` of a sampler with the same configuration and seed: the continued
         run is bit-identical to an uninterrupted one (moments restart at the restored generation)."""
-        if self.betas is not None:
+        if self.betas0 is not None:
             T = self.ntemps
             pos = np.ascontiguousarray(np.asarray(state["positions"], dtype=np.float64).reshape(T, self.nwalkers, self.ndim))
             lp = np.ascontiguousarray(np.asarray(state["logp"], dtype=np.float64).reshape(T, self.nwalkers))
@@ -399,6 +426,14 @@ class Sampler:
             if self.temper == "likelihood":
                 lls = np.ascontiguousarray(np.asarray(state["rung_loglike_sum"], dtype=np.float64).reshape(T))
                 _lib.check(self._L.kmc_sampler_set_rung_loglike_sum(self._h, _dp(lls)))
+            if self.adapt:                    # (after set_rung_state, which starts the ladder again)
+                if "S" not in state:
+                    raise ValueError("restore: the state was not taken from a sampler with adapt= (it has no ladder state)")
+                b = np.ascontiguousarray(np.asarray(state["betas"], dtype=np.float64).reshape(T))
+                S = np.ascontiguousarray(np.asarray(state["S"], dtype=np.float64).reshape(T - 2))
+                ra = np.ascontiguousarray(np.asarray(state["round_acc"], dtype=np.uint64).reshape(T - 1))
+                sk = C.c_uint64(int(state["skipped"]))
+                _lib.check(self._L.kmc_sampler_set_ladder(self._h, _dp(b), _dp(S), ra.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(sk)))
             return
         pos = np.ascontiguousarray(np.asarray(state["positions"], dtype=np.float64).reshape(self.nrows, self.ndim))
         lp = np.ascontiguousarray(np.asarray(state["logp"], dtype=np.float64))

@@ -75,6 +75,58 @@ def apply_tempering(cfg, betas=None, ntemps=None, beta_min=None, swap_every=1, t
     return b
 
 
+ADAPT_LAG, ADAPT_TIME = 10000.0, 100.0     # ptemcee's adaptation_lag and adaptation_time
+
+
+def apply_adapt(cfg, adapt=None):
+    """Fill ``cfg.adapt / adapt_until / adapt_lag / adapt_time`` from ``adapt``: ``None`` / ``False`` (off), ``True`` (the defaults:
+    ``lag=10000``, ``time=100``, until the end of burn-in) or a dict with any of ``lag``, ``time``, ``until`` (``None`` or 0: ``nburnin``).  Returns the dict in
+    force, or ``None`` when off.  The library checks the values (``KMC_ERR_BAD_ARG``, "adaptive ladder: ...")."""
+    cfg.adapt, cfg.adapt_until, cfg.adapt_lag, cfg.adapt_time = 0, 0, 0.0, 0.0
+    if adapt is None or adapt is False:
+        return None
+    if adapt is True:
+        adapt = {}
+    if not isinstance(adapt, dict) or not set(adapt) <= {"lag", "time", "until"}:
+        raise ValueError("adapt must be None, True or a dict with any of lag=, time=, until=")
+    out = dict(lag=float(adapt.get("lag", ADAPT_LAG)), time=float(adapt.get("time", ADAPT_TIME)),
+               until=None if adapt.get("until") is None else int(adapt["until"]))
+    if out["until"] == 0:                  # (kmc_config.adapt_until == 0 means nburnin, in every binding)
+        out["until"] = None
+    cfg.adapt, cfg.adapt_lag, cfg.adapt_time = 1, out["lag"], out["time"]
+    cfg.adapt_until = 0 if out["until"] is None else out["until"]
+    return out
+
+
+def adapt_ladder(betas, S, A, k, lag=ADAPT_LAG, time=ADAPT_TIME):
+    """One update of the adaptive ladder's rule, restated in numpy (``include/kissmcmc_hip.h`` above ``kmc_sampler_get_ladder``):
+    ``betas`` [T >= 3], the state ``S`` [T - 2] (``S[j - 1] = log(1 / betas[j] - 1 / betas[j - 1])`` when the ladder was created),
+    the round's swap acceptance ``A`` [T - 1] per neighbouring pair and the round number ``k``.  Returns ``(betas', S', skipped)``:
+    new arrays, equal to the old ones with ``skipped = 1`` when the candidate ladder is not finite and strictly decreasing between
+    ``betas[0] = 1`` and ``betas[-1]``, which never move.  The operations and their order are the device's; only ``exp`` is to
+    rounding, once per rung, and that difference does not accumulate because ``S`` is never derived from the betas again."""
+    b = np.array(betas, dtype=np.float64)
+    S = np.array(S, dtype=np.float64)
+    A = np.asarray(A, dtype=np.float64)
+    T = b.size
+    if b.ndim != 1 or T < 3 or S.shape != (T - 2,) or A.shape != (T - 1,):
+        raise ValueError("adapt_ladder: betas [T >= 3], S [T - 2] and A [T - 1]")
+    lag, time = float(lag), float(time)
+    kappa = (lag / (float(k) + lag)) / time
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        S1 = S + kappa * (A[:-1] - A[1:])
+        tau, b1 = 1.0, np.empty(T - 2)
+        for j in range(T - 2):
+            tau = tau + np.exp(S1[j])
+            b1[j] = 1.0 / tau
+        full = np.concatenate(([1.0], b1, [b[-1]]))
+        ok = bool(np.all(np.isfinite(b1)) and np.all(full[1:] < full[:-1]))
+    if not ok:
+        return b, S, 1
+    b[1:-1] = b1
+    return b, S1, 0
+
+
 def thermodynamic_integration(betas, mean_loglike):
     """``(logZ, err)``: the trapezoid of ``mean_loglike`` = ``<S>_beta`` over the ladder ``betas``, in ascending beta -- the
     thermodynamic integral ``log Z = int_0^1 <S>_beta dbeta`` of a likelihood-tempered ladder (``Sampler.rung_loglike_mean()``) --

@@ -3,7 +3,13 @@ after the other (what the library offered before), at S1 (100 x 3 over 10^3 obse
 sweep node's period.  Writes profiles/data_tempering.json.
 
     python scripts/data_tempering_bench.py [--parent-root DIR] [--out profiles/data_tempering.json]
-    python scripts/data_tempering_bench.py --one ladder|plain|sweep --shape S1|S2        (one figure as a JSON line: the child mode)
+    python scripts/data_tempering_bench.py --one ladder|plain|sweep|adapt --shape S1|S2|W1|W2   (one figure as a JSON line: the child mode)
+    python scripts/data_tempering_bench.py --adapt [--parent-root DIR] [--out profiles/adaptive_ladder.json]
+
+--adapt: the adaptive ladder's price (README "Adaptive ladder").  Per shape -- S1, S2 in the likelihood mode and W1 (100 x 3), W2 (4 096 x 8)
+in whole mode on GaussianIso, 8 rungs, a sweep after every generation -- the period with the ladder fixed (`off`) and adapting all the way
+(`on`: nburnin = ngenerations), and with --parent-root `off` on the parent commit's build too: each a median of three child processes of
+the same session, with its spread (max - min).
 
 --parent-root: a checkout of the parent commit with its library built; the plain samplers are then ALSO timed there, in child
 processes of the same session, three repetitions (their spread is the run-to-run spread the comparison is read against).  Kernel
@@ -19,6 +25,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = {"S1": dict(nw=100, nd=3, ndata=1000, G=400), "S2": dict(nw=4096, nd=8, ndata=100000, G=40)}
+WHOLE = {"W1": dict(nw=100, nd=3, G=1024), "W2": dict(nw=4096, nd=8, G=1024)}      # --adapt only: whole mode, GaussianIso
 NTEMPS = 8
 TERM = "double mu = x[0]; for (int k = 1; k < n; ++k) mu += x[k] * d[k - 1]; double r = d[n - 1] - mu; return -0.5 * p[0] * r * r;"
 PRIOR = "double s = 0.0; for (int k = 0; k < n; ++k) s += x[k] * x[k]; return -0.5 * s;"
@@ -45,6 +52,12 @@ def timed(s, th, G):
 def one(kind, shape):
     sys.path.insert(0, ROOT)
     import kissmcmc_jl_amd as kmc
+    kw = dict(adapt=True) if kind == "adapt" else {}          # (the parent commit's package is only asked for the other kinds)
+    if shape in WHOLE:
+        sh = WHOLE[shape]
+        G, th = sh["G"], np.random.default_rng(0).standard_normal((sh["nw"], sh["nd"]))
+        with kmc.Sampler(kmc.GaussianIso(), sh["nw"], sh["nd"], 3 * G, 3 * G, 1, 2.0, 5, betas=kmc.geometric_betas(NTEMPS, 0.05), swap_every=1, **kw) as s:
+            return dict(kind=kind, shape=shape, us_per_half_step=timed(s, th, G), describe=s.describe())
     sh = SHAPES[shape]
     dd, th = problem(kmc, sh)
     G = sh["G"]
@@ -56,7 +69,7 @@ def one(kind, shape):
         return dict(kind=kind, shape=shape, us_per_half_step=us, one_sampler_us=us / NTEMPS)
     betas = kmc.geometric_betas(NTEMPS, 1e-3)
     # swap_every 0 and no stored samples: no sweep node; "sweep": a sweep after every generation, the difference is the node's period
-    with kmc.Sampler(dd, sh["nw"], sh["nd"], 3 * G, 3 * G, 1, 2.0, 5, betas=betas, swap_every=1 if kind == "sweep" else 0, temper="likelihood") as s:
+    with kmc.Sampler(dd, sh["nw"], sh["nd"], 3 * G, 3 * G, 1, 2.0, 5, betas=betas, swap_every=1 if kind in ("sweep", "adapt") else 0, temper="likelihood", **kw) as s:
         us = timed(s, th, G)
         return dict(kind=kind, shape=shape, us_per_half_step=us, describe=s.describe())
 
@@ -76,11 +89,30 @@ def main():
     ap.add_argument("--shape", default="S1")
     ap.add_argument("--root", default=ROOT)
     ap.add_argument("--parent-root")
+    ap.add_argument("--adapt", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "data_tempering.json"))
     a = ap.parse_args()
     if a.one:
-        ROOT = a.root                                          # (the package under test: this checkout, or the parent's)
+        ROOT = os.path.abspath(a.root)                         # (the package under test: this checkout, or the parent's)
         print(json.dumps(one(a.one, a.shape)))
+        return
+    if a.adapt:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "adaptive_ladder.json")
+        rec = dict(device="MI355X", ntemps=NTEMPS, shapes={**SHAPES, **WHOLE}, swap_every=1,
+                   unit="us per half-step (HIP events over run(), launch gaps included); median of three child processes, spread = max - min", results={})
+        stat = lambda v: dict(median=float(np.median(v)), spread=float(max(v) - min(v)), runs=v)
+        for shape in list(WHOLE) + list(SHAPES):
+            r = dict(off=stat([child(ROOT, "sweep", shape)["us_per_half_step"] for _ in range(3)]),
+                     on=stat([child(ROOT, "adapt", shape)["us_per_half_step"] for _ in range(3)]))
+            if a.parent_root:
+                r["off_parent"] = stat([child(a.parent_root, "sweep", shape)["us_per_half_step"] for _ in range(3)])
+                r["off_minus_parent"] = r["off"]["median"] - r["off_parent"]["median"]
+            r["on_minus_off_us_per_generation"] = 2.0 * (r["on"]["median"] - r["off"]["median"])
+            rec["results"][shape] = r
+            print(shape, json.dumps(r), flush=True)
+        if not a.parent_root:
+            rec["not_measured"] = ["off on the parent commit's build (--parent-root)"]
+        json.dump(rec, open(out, "w"), indent=1)
         return
     rec = dict(ntemps=NTEMPS, shapes=SHAPES, unit="us per half-step (HIP events over run(), launch gaps included)", results={})
     for shape in SHAPES:

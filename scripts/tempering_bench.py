@@ -99,13 +99,47 @@ def two_mode_mixing(kmc, betas, gens, nburn, nw=256, d=10.0):
                 ess_per_s_first_coordinate=nw * (gens - nburn) / float(tau[0]) / (ms * 1e-3 * (gens - nburn) / gens))
 
 
+def adapt_figures(kmc, gens, shapes=((100, 3), (4096, 8)), T=8):
+    """--adapt: HIP-event time per half-step of run() with 8 rungs, a sweep after every generation, the ladder fixed (`off`) and adapting
+    all the way (`on`: nburnin = ngenerations, lag and time at their defaults): each a median of three runs with its spread.  The price of
+    the counters and the ticket is on - off; `off` against the same figure of the parent commit's build says what the feature costs unused."""
+    rows = []
+    for nw, nd in shapes:
+        row = dict(ntemps=T, nwalkers=nw, ndim=nd)
+        for name, kw in (("off", {}), ("on", dict(adapt=True))):
+            th = np.random.default_rng(0).standard_normal((nw, nd))
+            G = gens // 4 + 3 * gens
+            with kmc.Sampler(kmc.GaussianIso(), nw, nd, G, G, 1, 2.0, 1, betas=kmc.geometric_betas(T, 0.05), swap_every=1, **kw) as s:
+                s.set_positions(th)
+                s.run(gens // 4)
+                s.sync()
+                us = []
+                for _ in range(3):
+                    s.run(gens)
+                    s.sync()
+                    us.append(s.last_run_ms() * 1e3 / (2 * gens))
+                row[name] = dict(us_per_half_step_median=float(np.median(us)), spread=float(max(us) - min(us)), runs=us, describe=s.describe())
+        row["on_minus_off_us_per_generation"] = 2 * (row["on"]["us_per_half_step_median"] - row["off"]["us_per_half_step_median"])
+        rows.append(row)
+        print(json.dumps({k: (v if not isinstance(v, dict) else {kk: vv for kk, vv in v.items() if kk != "describe"}) for k, v in row.items()}), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--adapt", action="store_true", help="only the adaptive ladder's figures (README \"Adaptive ladder\"); --out profiles/adaptive_ladder.json")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tempering.json"))
     ap.add_argument("--gens", type=int, default=1024)
     ap.add_argument("--mix-gens", type=int, default=20000)
     a = ap.parse_args()
     import kissmcmc_jl_amd as kmc
+    if a.adapt:
+        rec = dict(device="MI355X", density="GaussianIso(0, 1)", ladder="geometric_betas(8, 0.05), swap_every=1", whole_mode=adapt_figures(kmc, a.gens))
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        print("wrote", a.out)
+        return
     rec = dict(device="MI355X", density="GaussianIso(0, 1)", ladder="geometric_betas(ntemps, 0.05)", shapes=[])
     for T, nw, nd in SHAPES:
         betas = kmc.geometric_betas(T, 0.05)
