@@ -704,6 +704,19 @@ kmc_status  kmc_sampler_int_acorr(kmc_sampler* s, double c, double* tau, double*
  * and the probability that it flips an accept decision (tests/test_gpu_accept_margin.py). */
 kmc_status  kmc_debug_accept_terms(uint64_t seed, uint64_t step, uint64_t walker0, int64_t n, int64_t nhalf, double a_scale,
                                    int64_t ndim, int device, int64_t* partner_host, double* z_host, double* t1_host, double* lu_host);
+/* The chain read-out kernels on the caller's data, through the launch code the library itself uses, so that a test can compare
+ * them element by element with a host transposition at row lengths no sampler of a testable size reaches
+ * (tests/test_gpu_readout_kernels.py).  src_host is a chain [K][nl][ld] of float (is_float = 1) or double, nd <= ld of every row
+ * meaningful; dst_host [dst_len] is uploaded as the initial content of the destination, then walkers [w0, w0 + nw) are written as
+ * dst[w * dst_stride + k * nd + c] = src[k][w0 + w][c], and all dst_len doubles come back: what the kernel must not touch keeps
+ * the caller's values.  KMC_ERR_BAD_ARG, before the device is touched, unless K, nl, nw, nd >= 1, ld >= nd, 0 <= w0,
+ * w0 + nw <= nl, dst_stride >= K * nd, dst_len >= (nw - 1) * dst_stride + K * nd, and nl, ld < 2^31. */
+kmc_status  kmc_debug_chain_by_walker(const void* src_host, int is_float, int64_t K, int64_t nl, int64_t ld, int64_t nd, int64_t w0,
+                                      int64_t nw, int64_t dst_stride, double* dst_host, int64_t dst_len, int device);
+/* The same for the compaction of padded rows (a streamed chain of odd ndim): src_host [rows][ld] -> dst[r * nd + c] = src[r][c],
+ * c < nd; needs dst_len >= rows * nd. */
+kmc_status  kmc_debug_rows_compact(const double* src_host, int64_t rows, int64_t ld, int64_t nd, double* dst_host, int64_t dst_len,
+                                   int device);
 
 #ifdef __cplusplus
 }

@@ -244,6 +244,16 @@ hipError_t launch_by_walker(const void* src, bool is_float, double* dst, int64_t
     return hipGetLastError();
 }
 
+// padded rows [rows][ld] -> dense rows [rows][nd] (kmc_copy_kernels.hpp: rows_compact): a thread per element, at most 8 192
+// workgroups (the kernel strides over the rest)
+hipError_t launch_rows_compact(const double* src, double* dst, int64_t rows, int64_t ld, int64_t nd, hipStream_t st)
+{
+    if (rows <= 0) return hipSuccess;
+    const int64_t grid = std::min<int64_t>((rows * nd + 255) / 256, 8192);
+    hipLaunchKernelGGL(rows_compact, dim3((unsigned)grid), dim3(256), 0, st, src, dst, rows, (int32_t)ld, (int32_t)nd);
+    return hipGetLastError();
+}
+
 // ---- KMC_STREAM_CHAIN ---------------------------------------------------------------------------------------
 int64_t samples_done_at(const kmc_sampler* s, int64_t generation)
 {
@@ -303,10 +313,7 @@ kmc_status chain_copy_range(kmc_sampler* s, int64_t k0, int64_t k1)
             if (locked) HIP_TRY(hipMemcpyAsync(dst, src, n * nl * nd * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
             else HIP_TRY(copy_sync(dst, src, n * nl * nd * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
         } else {                                         // padded rows: compacted into the scratch block, then one contiguous copy
-            int64_t grid = (int64_t)((n * nl * nd + 255) / 256);
-            if (grid > 8192) grid = 8192;
-            hipLaunchKernelGGL(rows_compact, dim3((unsigned)grid), dim3(256), 0, s->copy_stream, src, s->bw_scratch, (int64_t)(n * nl), (int32_t)ld, (int32_t)nd);
-            HIP_TRY(hipGetLastError());
+            HIP_TRY(launch_rows_compact(src, s->bw_scratch, (int64_t)(n * nl), (int64_t)ld, (int64_t)nd, s->copy_stream));
             if (locked) HIP_TRY(hipMemcpyAsync(dst, s->bw_scratch, n * nl * nd * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
             else HIP_TRY(copy_sync(dst, s->bw_scratch, n * nl * nd * sizeof(double), hipMemcpyDeviceToHost, s->copy_stream));
         }
@@ -496,5 +503,74 @@ KMC_EXPORT kmc_status kmc_sampler_get_chain_by_walker(kmc_sampler* s, double* ch
     if (chain) KMC_TRY(download_by_walker(s->d_chain, s->f32, nl, s->ld, nd, K, chain, s->stream));
     if (chain_logp) KMC_TRY(download_by_walker(s->d_chain_logp, false, nl, 1, 1, K, chain_logp, s->stream));
     return KMC_OK;
+}
+
+// ---- diagnostics: the read-out kernels on the caller's data (tests/test_gpu_readout_kernels.py) ---------------------------
+namespace {
+// *r = a * b; false when that does not fit int64
+bool mul_fits(int64_t a, int64_t b, int64_t* r) { return !__builtin_mul_overflow(a, b, r); }
+
+// host -> a fresh device block -> `run` -> the whole destination back to the host, on a stream of the call's own
+template <class Run>
+kmc_status debug_copy_run(const void* src_host, size_t src_bytes, double* dst_host, int64_t dst_len, int device, Run&& run)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(KMC_ERR_NO_DEVICE, "no HIP device visible"); }
+    if (device < 0 || device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    const size_t dst_bytes = (size_t)dst_len * sizeof(double);
+    KMC_TRY(check_device_room(src_bytes + dst_bytes + 512, "the read-out diagnostic"));
+    ScopedStream ss;
+    HIP_TRY(ss.create());
+    char* buf = nullptr;                                                 // [source | destination], the destination 256-byte aligned
+    const size_t dst_off = (src_bytes + 255) & ~(size_t)255;
+    HIP_TRY(hipMalloc((void**)&buf, dst_off + dst_bytes));
+    double* dst = reinterpret_cast<double*>(buf + dst_off);
+    hipError_t e = copy_sync(buf, src_host, src_bytes, hipMemcpyHostToDevice, ss.st);
+    if (e == hipSuccess) e = copy_sync(dst, dst_host, dst_bytes, hipMemcpyHostToDevice, ss.st);
+    if (e == hipSuccess) e = run(static_cast<const void*>(buf), dst, ss.st);
+    if (e == hipSuccess) e = copy_sync(dst_host, dst, dst_bytes, hipMemcpyDeviceToHost, ss.st);
+    if (e != hipSuccess) (void)hipStreamSynchronize(ss.st);
+    (void)hipFree(buf);
+    HIP_TRY(e);
+    return KMC_OK;
+}
+}  // namespace
+
+KMC_EXPORT kmc_status kmc_debug_chain_by_walker(const void* src_host, int is_float, int64_t K, int64_t nl, int64_t ld, int64_t nd, int64_t w0,
+                                                int64_t nw, int64_t dst_stride, double* dst_host, int64_t dst_len, int device)
+{
+    const int64_t lim = (int64_t)1 << 31;
+    if (!src_host || !dst_host) return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: null source or destination");
+    if (is_float != 0 && is_float != 1) return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: is_float is 0 or 1");
+    if (K < 1 || nl < 1 || nw < 1 || nd < 1) return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: K, nl, nw and nd are at least 1");
+    if (ld < nd) return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: ld < nd");
+    // (the kernel holds ld, nd and its tile indices in int; the grid has one x entry per walker tile, 4 096 columns per z entry)
+    if (ld >= lim || nl >= lim || (nd + 4095) / 4096 > 65535)
+        return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: nl and ld are below 2^31, nd at most 65535 * 4096");
+    if (w0 < 0 || nw > nl || w0 > nl - nw) return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: walkers [w0, w0 + nw) outside [0, nl)");
+    int64_t run = 0, rows = 0, src_n = 0, src_bytes = 0, span = 0, dst_bytes = 0;
+    if (!mul_fits(K, nd, &run) || !mul_fits(K, nl, &rows) || !mul_fits(rows, ld, &src_n) || !mul_fits(src_n, is_float ? 4 : 8, &src_bytes))
+        return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: the source does not fit 2^63 bytes");
+    if (dst_stride < run) return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: dst_stride < K * nd");
+    if (dst_len < 1 || !mul_fits(dst_len, 8, &dst_bytes) || !mul_fits(nw - 1, dst_stride, &span) || span > dst_len - run)
+        return fail(KMC_ERR_BAD_ARG, "kmc_debug_chain_by_walker: dst_len < (nw - 1) * dst_stride + K * nd");
+    return debug_copy_run(src_host, (size_t)src_bytes, dst_host, dst_len, device, [&](const void* src, double* dst, hipStream_t st) {
+        return launch_by_walker(src, is_float != 0, dst, nl, ld, nd, K, w0, nw, dst_stride, st);
+    });
+}
+
+KMC_EXPORT kmc_status kmc_debug_rows_compact(const double* src_host, int64_t rows, int64_t ld, int64_t nd, double* dst_host, int64_t dst_len, int device)
+{
+    if (!src_host || !dst_host) return fail(KMC_ERR_BAD_ARG, "kmc_debug_rows_compact: null source or destination");
+    if (rows < 1 || nd < 1) return fail(KMC_ERR_BAD_ARG, "kmc_debug_rows_compact: rows and nd are at least 1");
+    if (ld < nd) return fail(KMC_ERR_BAD_ARG, "kmc_debug_rows_compact: ld < nd");
+    if (ld >= (int64_t)1 << 31) return fail(KMC_ERR_BAD_ARG, "kmc_debug_rows_compact: ld is below 2^31");      // (int in the kernel)
+    int64_t src_n = 0, src_bytes = 0, out_n = 0, dst_bytes = 0;
+    if (!mul_fits(rows, ld, &src_n) || !mul_fits(src_n, 8, &src_bytes)) return fail(KMC_ERR_BAD_ARG, "kmc_debug_rows_compact: the source does not fit 2^63 bytes");
+    if (!mul_fits(rows, nd, &out_n) || dst_len < out_n || !mul_fits(dst_len, 8, &dst_bytes)) return fail(KMC_ERR_BAD_ARG, "kmc_debug_rows_compact: dst_len < rows * nd");
+    return debug_copy_run(src_host, (size_t)src_bytes, dst_host, dst_len, device, [&](const void* src, double* dst, hipStream_t st) {
+        return launch_rows_compact(static_cast<const double*>(src), dst, rows, ld, nd, st);
+    });
 }
 

@@ -15,6 +15,14 @@ namespace kmc {
 // samples, 39 ms for 1 GB of 32-double rows, most of the drop-in call's wall time (profiles/r04_readout.txt).
 // LDS: [TW][TK * nd + 1] doubles (the odd stride keeps a sample's TW rows off one bank).
 // Rows longer than 4 096 elements go in column windows of that many (blockIdx.z), one row per tile.
+// The regimes of by_walker_tile (tests/test_gpu_readout_kernels.py runs every one, with a ragged tile in walkers and in samples):
+//      nd            TK                         TW
+//      <= 200        32                         64 (nd = 1), 34 (nd = 7), 7 (nd = 32), 1 (nd = 200)
+//      201 .. 3000   6000 / nd: 29 down to 2    1
+//      3001 .. 3839  1                          2
+//      3840 .. 4096  1                          1      still the tiled branch (NC == nd)
+//      > 4096        1                          1      the other branch: column windows of 4 096 on blockIdx.z, a short last one
+// (launch_by_walker, kmc_copy.hip, also cuts runs of more than 65 535 sample tiles -- gridDim.y -- into several launches.)
 struct ByWalkerTile { int32_t TW, TK, NC; uint32_t lds_bytes; };
 __host__ __device__ inline ByWalkerTile by_walker_tile(int32_t nd)
 {

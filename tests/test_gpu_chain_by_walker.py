@@ -14,6 +14,8 @@ pytestmark = pytest.mark.gpu
     (2048, 32, 150, 22, 4, dict(dtype="f32")),      # float rows on the device, double on the host
     (600, 200, 40, 10, 2, {}),
     (4096, 8, 70, 0, 1, dict(use_graph=False)),
+    (336, 333, 12, 2, 2, {}),                       # an odd ndim above 200: tiles of 18 samples x 1 walker
+    (336, 333, 12, 2, 2, dict(dtype="f32")),
 ])
 def test_by_walker_equals_reordered_sample_major(kmc, nw, nd, G, nburn, nthin, kw):
     th = np.random.default_rng(nd).standard_normal((nw, nd))
