@@ -696,6 +696,39 @@ kmc_status  kmc_int_acorr(const double* chain_host, int64_t nsamples, int64_t nw
 /* The same on the chain a sampler holds on the device (KMC_STORE_CHAIN, the samples stored so far; even ndim). */
 kmc_status  kmc_sampler_int_acorr(kmc_sampler* s, double c, double* tau, double* converged);
 
+/* ---- posterior summaries: exact order statistics and the MAP sample of a stored chain, on the device ----
+ * What the summarize_run of reference src/analysis.jl:9-42 (commented out there) needs -- medians, and with them any quantile or
+ * credible interval -- without moving the chain to the host.
+ *
+ * Order statistics.  The selection is the stored samples k >= first_sample of the walkers w with walker_mask[w] != 0 (all walkers when
+ * walker_mask is NULL): N = (samples stored - first_sample) * popcount(mask) values per dimension, *n_out (may be NULL).  For each of
+ * the nranks <= 16 ranks r (0-based, in [0, N), repeats allowed), theta_out[i][d] is the element of rank r_i of dimension d in
+ * ascending order -- every dimension on its own, as np.sort(chain, axis=0)[r] -- and logp_out[i] (may be NULL; needs KMC_STORE_LOGP)
+ * the same of the stored log-densities.  The results are elements of the chain, bit for bit (a KMC_F32 chain: its floats widened).
+ * Order: a double maps to a 64-bit key, all bits flipped when its sign bit is set, else the sign bit flipped, and keys compare as unsigned
+ * integers: -inf < ... < -0.0 < +0.0 < ... < +inf.  NaNs are ordered by bit pattern (a NaN with the sign bit clear above +inf, with
+ * it set below -inf); a stored chain holds none.  Algorithm: most-significant-digit radix select, 8 passes of 8 bits over the selection,
+ * every pass one read of it for all dimensions and ranks, integer atomics only.
+ * KMC_ERR_BAD_ARG: no KMC_STORE_CHAIN; logp_out without KMC_STORE_LOGP; nranks outside 1..16; a rank outside [0, N); N = 0;
+ * first_sample outside [0, samples stored].  KMC_ERR_UNSUPPORTED: KMC_STREAM_CHAIN (the chain is on the host: kmc_chain_order_stats);
+ * shard_count > 1 or KMC_P2P (a shard holds only its own walkers; a select across GPUs is not built). */
+kmc_status  kmc_sampler_order_stats(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */,
+                                    const int64_t* ranks, int32_t nranks,
+                                    double* theta_out /* [nranks][ndim] */, double* logp_out /* [nranks] or NULL */, int64_t* n_out);
+/* The MAP sample: (sample, walker) of the largest stored log-density of the same selection (needs KMC_STORE_LOGP), ties to the
+ * smallest sample, then the smallest walker; NaN entries are ignored (all NaN: KMC_ERR_BAD_ARG).  theta gets that sample's row,
+ * logp its log-density.  Refusals as above. */
+kmc_status  kmc_sampler_chain_argmax(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask,
+                                     int64_t* sample, int64_t* walker, double* theta /* [ndim] */, double* logp);
+/* The same two on a chain in host memory, uploaded to `device` first (a streamed chain, Metropolis output).  logp_host may be NULL
+ * when logp_out is.  KMC_ERR_UNSUPPORTED when the chain does not fit the device's free memory. */
+kmc_status  kmc_chain_order_stats(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                                  int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                                  const int64_t* ranks, int32_t nranks, int device, double* theta_out, double* logp_out, int64_t* n_out);
+kmc_status  kmc_chain_argmax(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
+                             int64_t first_sample, const uint8_t* walker_mask, int device,
+                             int64_t* sample, int64_t* walker, double* theta, double* logp);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

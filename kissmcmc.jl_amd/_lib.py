@@ -56,6 +56,7 @@ SYMBOLS = [
     "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault", "kmc_data_density_create",
     "kmc_sampler_get_rung_state", "kmc_sampler_set_rung_state", "kmc_sampler_get_swaps",
     "kmc_sampler_get_rung_loglike", "kmc_sampler_set_rung_loglike_sum", "kmc_sampler_get_ladder", "kmc_sampler_set_ladder",
+    "kmc_sampler_order_stats", "kmc_sampler_chain_argmax", "kmc_chain_order_stats", "kmc_chain_argmax",
 ]
 
 
@@ -264,6 +265,11 @@ def lib() -> C.CDLL:
     L.kmc_metropolis_run.argtypes = [C.POINTER(MetropolisConfig), dp, C.POINTER(MetropolisOutputs)]
     L.kmc_int_acorr.argtypes = [dp, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int, dp, dp]
     L.kmc_sampler_int_acorr.argtypes = [vp, C.c_double, dp, dp]
+    bp = C.POINTER(C.c_uint8)
+    L.kmc_sampler_order_stats.argtypes = [vp, C.c_int64, bp, ip, C.c_int32, dp, dp, ip]
+    L.kmc_sampler_chain_argmax.argtypes = [vp, C.c_int64, bp, ip, ip, dp, dp]
+    L.kmc_chain_order_stats.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, ip, C.c_int32, C.c_int, dp, dp, ip]
+    L.kmc_chain_argmax.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int, ip, ip, dp, dp]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

@@ -1,0 +1,253 @@
+// kmc_summary.hip -- posterior summaries of a stored chain on the device: exact order statistics (kmc_sampler_order_stats,
+// kmc_chain_order_stats) and the MAP sample (kmc_sampler_chain_argmax, kmc_chain_argmax).  Kernels: kmc_summary_kernels.hpp.
+#include <vector>
+
+#include "kmc_host.hpp"
+#include "kmc_sampler.hpp"
+#include "kmc_summary_kernels.hpp"
+
+using namespace kmc_host;
+using namespace kmc_summary;
+
+// ------------------------------------------------------------------------------------------
+// The median, the 16 / 84 % quantiles and the best sample of a run (the summarize_run of reference src/analysis.jl:9-42, commented out
+// there) without moving the chain to the host.  Order statistics: a most-significant-digit radix select over the 64-bit keys of
+// kmc_summary_kernels.hpp, kSelectPasses passes of {clear the table, count the next digit per slot, scan per slot} enqueued on one
+// private stream with no host synchronisation between them, then one copy of the result.  Every pass reads the selected part of the
+// chain once for all requested ranks; the columns are cut into groups so that one workgroup's counters (columns x ranks x 256 x 4 B) fit
+// 64 KiB of LDS, and the log-densities are one more column.
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+struct ChainView {
+    const void* chain = nullptr;       // device [nsamples][nl][ld], float or double
+    bool is_float = false;
+    int64_t ld = 0, ndim = 0;
+    const double* logp = nullptr;      // device [nsamples][nl] or nullptr
+    int64_t nsamples = 0, nl = 0;
+};
+
+struct SummaryBuffers {
+    uint8_t* mask = nullptr;
+    unsigned long long* hist = nullptr;
+    uint64_t* prefix = nullptr;
+    int64_t* krem = nullptr;
+    double* out = nullptr;
+    double* pv = nullptr;
+    int64_t* pi = nullptr;
+    double *chain = nullptr, *logp = nullptr;          // kmc_chain_*: the uploaded copies
+    ~SummaryBuffers()
+    {
+        (void)hipFree(mask); (void)hipFree(hist); (void)hipFree(prefix); (void)hipFree(krem); (void)hipFree(out);
+        (void)hipFree(pv); (void)hipFree(pi); (void)hipFree(chain); (void)hipFree(logp);
+    }
+};
+
+// N = (nsamples - first_sample) * popcount(mask): what the ranks index
+kmc_status selection_size(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, int64_t* n)
+{
+    if (v.nsamples < 0 || v.nl <= 0 || v.ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples >= 0, nwalkers, ndim > 0");
+    if (v.nl >= ((int64_t)1 << 31) || v.ndim >= ((int64_t)1 << 24)) return fail(KMC_ERR_UNSUPPORTED, "chain too large: walkers < 2^31, ndim < 2^24");
+    if (first_sample < 0 || first_sample > v.nsamples) return fail(KMC_ERR_BAD_ARG, "first_sample must lie in [0, samples stored]");
+    int64_t nw = v.nl;
+    if (mask_host) {
+        nw = 0;
+        for (int64_t w = 0; w < v.nl; ++w) nw += mask_host[w] != 0;
+    }
+    *n = (v.nsamples - first_sample) * nw;
+    if (*n <= 0) return fail(KMC_ERR_BAD_ARG, "the selection is empty: no stored sample at or after first_sample, or no walker in the mask");
+    return KMC_OK;
+}
+
+kmc_status upload_mask(SummaryBuffers& b, const uint8_t* mask_host, int64_t nl, hipStream_t st)
+{
+    if (!mask_host) return KMC_OK;
+    HIP_TRY(hipMalloc((void**)&b.mask, (size_t)nl));
+    HIP_TRY(copy_sync(b.mask, mask_host, (size_t)nl, hipMemcpyHostToDevice, st));
+    return KMC_OK;
+}
+
+kmc_status order_stats_device(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, const int64_t* ranks, int32_t nranks,
+                              double* theta_out, double* logp_out, int64_t* n_out)
+{
+    if (!ranks || !theta_out) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (nranks < 1 || nranks > kMaxRanks) return fail(KMC_ERR_BAD_ARG, "between 1 and 16 ranks per call");
+    int64_t N = 0;
+    KMC_TRY(selection_size(v, first_sample, mask_host, &N));
+    if (n_out) *n_out = N;
+    for (int r = 0; r < nranks; ++r)
+        if (ranks[r] < 0 || ranks[r] >= N) return fail(KMC_ERR_BAD_ARG, "rank " + std::to_string(ranks[r]) + " outside [0, " + std::to_string(N) + ")");
+    const bool with_logp = logp_out != nullptr;
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0), nslots = ncols * nranks;
+    int cg_shift = 0;                                   // columns per group: the largest power of two with columns x ranks <= kSelectSlots ...
+    while ((2 << cg_shift) * nranks <= kSelectSlots) ++cg_shift;
+    while (cg_shift > 0 && (1 << (cg_shift - 1)) >= v.ndim) --cg_shift;                 // ... and no wider than the row needs
+    const int64_t ngroups_chain = (v.ndim + (1 << cg_shift) - 1) >> cg_shift, ngroups = ngroups_chain + (with_logp ? 1 : 0);
+    const int64_t nrows = (v.nsamples - first_sample) * v.nl;
+    // workgroups per group: enough to fill the device, few enough that their flushes stay small next to their reads, and so many that no
+    // workgroup's 32-bit counters can wrap (fewer than 2^24 steps of at most 256 elements each)
+    const int64_t steps_min = (nrows + 255) / 256, steps_max = (nrows + (256 >> cg_shift) - 1) / (256 >> cg_shift);
+    int64_t nwg = steps_min < 512 ? steps_min : 512;
+    const int64_t need = (steps_max >> 23) + 1;
+    if (nwg < need) nwg = need;
+    if (nwg < 1) nwg = 1;
+    if (ngroups * nwg >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one select");
+
+    ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
+    HIP_TRY(ss.create());
+    const hipStream_t st = ss.st;
+    SummaryBuffers b;
+    KMC_TRY(upload_mask(b, mask_host, v.nl, st));
+    const size_t hist_bytes = (size_t)nslots * kSelectBins * sizeof(unsigned long long);
+    HIP_TRY(hipMalloc((void**)&b.hist, hist_bytes));
+    HIP_TRY(hipMalloc((void**)&b.prefix, (size_t)nslots * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc((void**)&b.krem, (size_t)nslots * sizeof(int64_t)));
+    HIP_TRY(hipMalloc((void**)&b.out, (size_t)nslots * sizeof(double)));
+    std::vector<int64_t> k0((size_t)nslots);
+    for (int64_t s = 0; s < nslots; ++s) k0[(size_t)s] = ranks[s % nranks];
+    HIP_TRY(copy_sync(b.krem, k0.data(), k0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(b.prefix, 0, (size_t)nslots * sizeof(uint64_t), st));
+
+    SelectArgs a{};
+    a.chain = v.chain; a.logp = with_logp ? v.logp : nullptr; a.mask = b.mask; a.prefix = b.prefix; a.hist = b.hist;
+    a.row0 = first_sample * v.nl; a.nrows = nrows; a.nl = v.nl; a.ld = v.ld;
+    a.ndim = (int32_t)v.ndim; a.is_float = v.is_float ? 1 : 0; a.nranks = nranks; a.cg_shift = cg_shift;
+    a.ngroups_chain = (int32_t)ngroups_chain; a.nwg = (int32_t)nwg;
+    const int64_t cols_g = v.ndim < (1 << cg_shift) ? v.ndim : (1 << cg_shift);
+    const unsigned lds = (unsigned)(cols_g * nranks * kSelectBins * sizeof(uint32_t));
+    for (int pass = 0; pass < kSelectPasses; ++pass) {
+        a.pass = pass;
+        HIP_TRY(hipMemsetAsync(b.hist, 0, hist_bytes, st));
+        hipLaunchKernelGGL(select_hist, dim3((unsigned)(ngroups * nwg)), dim3(256), lds, st, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(select_scan, dim3((unsigned)nslots), dim3(kSelectBins), 0, st, b.hist, b.prefix, b.krem, b.out, (int)nranks, pass);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<double> out((size_t)nslots);
+    HIP_TRY(copy_sync(out.data(), b.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    for (int r = 0; r < nranks; ++r) {                  // slot = column * nranks + rank
+        for (int64_t d = 0; d < v.ndim; ++d) theta_out[(int64_t)r * v.ndim + d] = out[(size_t)(d * nranks + r)];
+        if (with_logp) logp_out[r] = out[(size_t)(v.ndim * nranks + r)];
+    }
+    return KMC_OK;
+}
+
+kmc_status argmax_device(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, int64_t* sample, int64_t* walker, double* theta, double* logp)
+{
+    if (!sample || !walker || !theta || !logp) return fail(KMC_ERR_BAD_ARG, "null argument");
+    int64_t N = 0;
+    KMC_TRY(selection_size(v, first_sample, mask_host, &N));
+    const int64_t nrows = (v.nsamples - first_sample) * v.nl;
+    int64_t np = (nrows + 2047) / 2048;
+    if (np > 1024) np = 1024;
+    ScopedStream ss;
+    HIP_TRY(ss.create());
+    const hipStream_t st = ss.st;
+    SummaryBuffers b;
+    KMC_TRY(upload_mask(b, mask_host, v.nl, st));
+    HIP_TRY(hipMalloc((void**)&b.pv, (size_t)np * sizeof(double)));
+    HIP_TRY(hipMalloc((void**)&b.pi, (size_t)np * sizeof(int64_t)));
+    HIP_TRY(hipMalloc((void**)&b.out, (size_t)(v.ndim + 2) * sizeof(double)));
+    hipLaunchKernelGGL(argmax_partial, dim3((unsigned)np), dim3(256), 0, st, v.logp, (const uint8_t*)b.mask, first_sample * v.nl, nrows, v.nl, b.pv, b.pi);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(argmax_final, dim3(1), dim3(256), 0, st, (const double*)b.pv, (const int64_t*)b.pi, (int)np, v.chain, v.is_float ? 1 : 0, v.ld, (int)v.ndim, b.out);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> res((size_t)v.ndim + 2);
+    HIP_TRY(copy_sync(res.data(), b.out, res.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    int64_t idx;
+    std::memcpy(&idx, &res[(size_t)v.ndim + 1], sizeof(idx));
+    if (idx < 0) return fail(KMC_ERR_BAD_ARG, "every selected log-density is NaN");
+    std::memcpy(theta, res.data(), (size_t)v.ndim * sizeof(double));
+    *logp = res[(size_t)v.ndim];
+    *sample = idx / v.nl;
+    *walker = idx % v.nl;
+    return KMC_OK;
+}
+
+// the checks the two sampler calls share; `what` names the call in the messages
+kmc_status sampler_view(kmc_sampler* s, bool need_logp, const char* host_call, ChainView* v)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    if (!s->d_chain) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_CHAIN");
+    if (need_logp && !s->d_chain_logp) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_LOGP");
+    if (s->stream_chain) return fail(KMC_ERR_UNSUPPORTED, std::string("KMC_STREAM_CHAIN: the chain is on the host; use ") + host_call + " on it");
+    if (s->cfg.shard_count > 1 || s->p2p)
+        return fail(KMC_ERR_UNSUPPORTED, std::string("sharded sampler: a shard holds only its own walkers and a select across GPUs is not built; gather the chain and use ") + host_call);
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    v->chain = s->d_chain; v->is_float = s->f32; v->ld = s->ld; v->ndim = s->cfg.ndim;
+    v->logp = s->d_chain_logp; v->nsamples = samples_done(s); v->nl = s->nlocal;
+    return KMC_OK;
+}
+
+// kmc_chain_*: a dense host chain on the device (its checks first: nothing is read before they pass)
+kmc_status host_view(SummaryBuffers& b, const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim, int device, ChainView* v)
+{
+    if (!chain_host) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (nsamples <= 0 || nwalkers <= 0 || ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples, nwalkers, ndim > 0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(KMC_ERR_NO_DEVICE, "no HIP device visible");
+    }
+    if (device < 0 || device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const double need = (double)nsamples * (double)nwalkers * ((double)ndim + 1.0) * 8.0 + 64.0 * 1048576.0;
+    if (need > (double)free_b)
+        return fail(KMC_ERR_UNSUPPORTED, "the chain (" + std::to_string((int64_t)(need / 1048576.0)) + " MiB with its work space) does not fit the device (" +
+                                             std::to_string(free_b >> 20) + " MiB free); streaming a host chain through the device is not built");
+    const size_t rows = (size_t)nsamples * (size_t)nwalkers;
+    ScopedStream up;
+    HIP_TRY(up.create());
+    HIP_TRY(hipMalloc((void**)&b.chain, rows * (size_t)ndim * sizeof(double)));
+    HIP_TRY(copy_sync(b.chain, chain_host, rows * (size_t)ndim * sizeof(double), hipMemcpyHostToDevice, up.st));
+    if (logp_host) {
+        HIP_TRY(hipMalloc((void**)&b.logp, rows * sizeof(double)));
+        HIP_TRY(copy_sync(b.logp, logp_host, rows * sizeof(double), hipMemcpyHostToDevice, up.st));
+    }
+    v->chain = b.chain; v->is_float = false; v->ld = ndim; v->ndim = ndim; v->logp = b.logp; v->nsamples = nsamples; v->nl = nwalkers;
+    return KMC_OK;
+}
+
+}  // namespace
+
+KMC_EXPORT kmc_status kmc_sampler_order_stats(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, const int64_t* ranks, int32_t nranks,
+                                              double* theta_out, double* logp_out, int64_t* n_out)
+{
+    ChainView v;
+    KMC_TRY(sampler_view(s, logp_out != nullptr, "kmc_chain_order_stats", &v));
+    return order_stats_device(v, first_sample, walker_mask, ranks, nranks, theta_out, logp_out, n_out);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_chain_argmax(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t* sample, int64_t* walker,
+                                               double* theta, double* logp)
+{
+    ChainView v;
+    KMC_TRY(sampler_view(s, true, "kmc_chain_argmax", &v));
+    return argmax_device(v, first_sample, walker_mask, sample, walker, theta, logp);
+}
+
+KMC_EXPORT kmc_status kmc_chain_order_stats(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
+                                            int64_t first_sample, const uint8_t* walker_mask, const int64_t* ranks, int32_t nranks, int device,
+                                            double* theta_out, double* logp_out, int64_t* n_out)
+{
+    if (logp_out && !logp_host) return fail(KMC_ERR_BAD_ARG, "logp_out without logp_host");
+    SummaryBuffers b;
+    ChainView v;
+    KMC_TRY(host_view(b, chain_host, logp_out ? logp_host : nullptr, nsamples, nwalkers, ndim, device, &v));
+    return order_stats_device(v, first_sample, walker_mask, ranks, nranks, theta_out, logp_out, n_out);
+}
+
+KMC_EXPORT kmc_status kmc_chain_argmax(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
+                                       int64_t first_sample, const uint8_t* walker_mask, int device, int64_t* sample, int64_t* walker, double* theta,
+                                       double* logp)
+{
+    if (!logp_host) return fail(KMC_ERR_BAD_ARG, "null argument");
+    SummaryBuffers b;
+    ChainView v;
+    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
+    return argmax_device(v, first_sample, walker_mask, sample, walker, theta, logp);
+}

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -560,6 +560,67 @@ function int_acorr(thetas; c=5, device=0)
                chain, ns, nw, nd, Float64(c), Cint(device), tau, conv)
     st == 0 || error("kmc_int_acorr failed ($st): $(last_error())")
     return tau, conv
+end
+
+# thetas[walker][sample](dim) -> column-major (dim, walker, sample) == C [sample][walker][dim]; logdensities[walker][sample] likewise
+function _summary_chain(thetas, logdensities)
+    nw = length(thetas); ns = length(thetas[1]); nd = length(thetas[1][1])
+    chain = Array{Float64}(undef, nd, nw, ns)
+    for w in 1:nw, k in 1:ns, d in 1:nd
+        chain[d, w, k] = nd == 1 ? thetas[w][k][1] : thetas[w][k][d]
+    end
+    logp = logdensities === nothing ? nothing : Float64[logdensities[w][k] for w in 1:nw, k in 1:ns]
+    return chain, logp, ns, nw, nd
+end
+_summary_mask(walkers, nw) = walkers === nothing ? nothing : (m = zeros(UInt8, nw); m[walkers] .= 1; m)
+
+"""
+    quantiles(thetas, q; logdensities=nothing, first_sample=0, walkers=nothing, device=0)
+
+Quantiles `q` (in [0, 1]) per dimension of `thetas[walker][sample]` as `emcee` / `metropolis_chains` return it, over the samples
+after the first `first_sample` of the walkers `walkers` (indices or a Bool mask; all by default): a `length(q) x ndim` matrix, and
+with `logdensities` also the vector of their quantiles.  The two order statistics of every quantile are selected exactly on the GPU
+(`kmc_chain_order_stats`); the value is `x_lo + frac (x_hi - x_lo)` with `h = q (n - 1)`, `lo = floor(h)`, `frac = h - lo`.
+"""
+function quantiles(thetas, q; logdensities=nothing, first_sample=0, walkers=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    n = (ns - first_sample) * (mask === nothing ? nw : count(!iszero, mask))
+    n >= 1 || error("the selection is empty")
+    out = Matrix{Float64}(undef, length(q), nd); outlp = Vector{Float64}(undef, length(q))
+    for (i, qi) in enumerate(q)
+        @assert 0 <= qi <= 1
+        h = qi * (n - 1); lo = floor(Int64, h); hi = min(lo + 1, n - 1); frac = h - lo
+        ranks = Int64[lo, hi]
+        th = Matrix{Float64}(undef, nd, 2); lp = Vector{Float64}(undef, 2); nout = Ref{Int64}(0)
+        st = ccall((:kmc_chain_order_stats, LIB), Cint,
+                   (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Ptr{Int64}, Int32, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                   chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, ranks, Int32(2), Cint(device),
+                   th, logp === nothing ? C_NULL : lp, nout)
+        st == 0 || error("kmc_chain_order_stats failed ($st): $(last_error())")
+        for d in 1:nd
+            out[i, d] = frac == 0 ? th[d, 1] : th[d, 1] + frac * (th[d, 2] - th[d, 1])
+        end
+        logp === nothing || (outlp[i] = frac == 0 ? lp[1] : lp[1] + frac * (lp[2] - lp[1]))
+    end
+    return logdensities === nothing ? out : (out, outlp)
+end
+
+"""
+    map_sample(thetas, logdensities; first_sample=0, walkers=nothing, device=0)
+
+The stored sample of the largest log-density (`kmc_chain_argmax`): `(theta, logdensity, sample, walker)`, 1-based; ties go to the
+smallest sample, then the smallest walker.
+"""
+function map_sample(thetas, logdensities; first_sample=0, walkers=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    k = Ref{Int64}(0); w = Ref{Int64}(0); lp = Ref{Float64}(0.0); theta = Vector{Float64}(undef, nd)
+    st = ccall((:kmc_chain_argmax, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+               chain, logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Cint(device), k, w, theta, lp)
+    st == 0 || error("kmc_chain_argmax failed ($st): $(last_error())")
+    return theta, lp[], k[] + 1, w[] + 1
 end
 
 # make_theta0s (src/samplers.jl:311-349) and squash_walkers (src/samplers.jl:372-428): KissMCMC's own, imported above.

@@ -493,6 +493,53 @@ class Sampler:
         _lib.check(self._L.kmc_sampler_int_acorr(self._h, float(c), tau.ctypes.data_as(dp), conv.ctypes.data_as(dp)))
         return tau, conv
 
+    # -- posterior summaries of the device chain (summary.py; README "Posterior summaries") ------
+    @property
+    def samples_done(self) -> int:
+        """Samples stored so far."""
+        post = self.generation - self.cfg.nburnin
+        return 0 if post <= 0 else min(self.nsamples, post // self.cfg.nthin)
+
+    def order_stats(self, ranks, first_sample: int = 0, walkers=None, logp: bool = False):
+        """Exact order statistics of the stored chain, selected on the device (``kmc_sampler_order_stats``): for each of up to 16
+        0-based ``ranks`` into the ``N = (samples_done - first_sample) * len(walkers)`` selected values of every dimension, the
+        element of that rank -- ``np.sort(chain[first_sample:, walkers], axis=(0, 1))[rank]`` per dimension.  Returns
+        ``(theta[len(ranks), ndim], logp[len(ranks)] | None, N)``.  ``walkers``: a boolean mask or an index array (None: all)."""
+        from .summary import _SamplerProvider
+        p = _SamplerProvider(self, first_sample, walkers)
+        th, lp = p.order_stats(np.atleast_1d(ranks), logp)
+        return th, lp, p.n
+
+    def quantiles(self, q, first_sample: int = 0, walkers=None, logp: bool = False):
+        """Quantiles ``q`` per dimension of the stored chain: ``[len(q), ndim]``, with ``logp=True`` also those of the stored
+        log-densities, ``[len(q)]``.  ``x_lo + frac (x_hi - x_lo)`` (:func:`kissmcmc_jl_amd.quantile_ranks`; exactly ``x_lo`` when
+        ``frac == 0``) on the host from the device's two order statistics per quantile: numpy's ``linear`` method in value."""
+        from .summary import _SamplerProvider, quantiles_from
+        return quantiles_from(_SamplerProvider(self, first_sample, walkers), q, logp=logp)
+
+    def map_sample(self, first_sample: int = 0, walkers=None):
+        """The stored sample of the largest log-density (needs ``store_logp``): ``(theta[ndim], logp, sample, walker)``; ties go to
+        the smallest sample, then the smallest walker."""
+        from .summary import _SamplerProvider
+        return _SamplerProvider(self, first_sample, walkers).argmax()
+
+    def summary(self, theta_true=None, names=None, eff_samples=None):
+        """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
+        from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain."""
+        from .summary import _SamplerProvider, quantiles_from, summary_columns
+        p = _SamplerProvider(self)
+        median = quantiles_from(p, [0.5])[0]
+        mode = p.argmax()[0] if self.cfg.flags & _lib.STORE_LOGP else None
+        if self.cfg.flags & _lib.MOMENTS:
+            sm, sq, n = self.moments()
+            mean = sm / n
+            std = np.sqrt(np.maximum(sq - sm * sm / n, 0.0) / (n - 1)) if n > 1 else np.full(self.ndim, np.nan)
+        else:
+            flat = self.chain(logp=False)[0].reshape(-1, self.ndim)
+            mean = flat.mean(axis=0)
+            std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(self.ndim, np.nan)
+        return summary_columns(names, median, mean, std, mode, theta_true, eff_samples)
+
     def device_ptr(self, which: int) -> int:
         return int(self._L.kmc_sampler_device_ptr(self._h, int(which)) or 0)
 
