@@ -729,6 +729,37 @@ kmc_status  kmc_chain_argmax(const double* chain_host, const double* logp_host, 
                              int64_t first_sample, const uint8_t* walker_mask, int device,
                              int64_t* sample, int64_t* walker, double* theta, double* logp);
 
+/* ---- marginal histograms of a stored chain, on the device: every selected column's 1-D histogram and all pairs' 2-D histograms ----
+ * The numbers of a corner plot without moving the chain to the host.  The selection (first_sample, walker_mask, N in *n_out) is that of
+ * the order statistics above.  dims lists ndims distinct chain columns in the caller's order (NULL / 0: every dimension, in order); the
+ * output columns are those, and with with_logp = 1 (needs KMC_STORE_LOGP) the stored log-densities as one more, last, column: ncols.
+ * The rule.  edges[c] is column c's B + 1 = nbins + 1 finite, strictly increasing bin edges e[0..B].  An element x falls in bin i iff
+ * e[i] <= x < e[i+1]; the last bin is closed, x == e[B] goes to bin B - 1.  x < e[0] counts in outside[c][0] (below), x > e[B] in
+ * outside[c][1] (above), a NaN in outside[c][2]; -inf and +inf are ordinary values under these comparisons.  The bin is decided by
+ * comparisons against the edges alone (a binary search), never by float arithmetic, so counts1[c] is np.histogram(x, bins=e)[0] for any
+ * edges, and counts1[c] and outside[c] sum to N.  A KMC_F32 chain is widened first, which is exact.
+ * counts2 (may be NULL) gets, for every pair (a, b), a < b, of positions in the dims list, in the order (0,1), (0,2), ..., (1,2), ...,
+ * the 2-D histogram [bin of dims[a]][bin of dims[b]] of the rows whose two coordinates both lie inside their ranges:
+ * np.histogram2d(x_a, x_b, bins=[e_a, e_b])[0].  Chain columns only (never the log-densities); it needs 2..16 selected dimensions and
+ * nbins <= 64.  Counts are exact integers (integer atomics only) and do not depend on the launch geometry.
+ * KMC_ERR_BAD_ARG: no KMC_STORE_CHAIN; with_logp without KMC_STORE_LOGP; nbins outside 1..256, or outside 1..64 with counts2; with
+ * counts2 fewer than 2 or more than 16 selected dimensions; a dimension outside [0, ndim) or listed twice; edges that are not finite
+ * and strictly increasing; N = 0; first_sample outside [0, samples stored].  KMC_ERR_UNSUPPORTED: as for the order statistics. */
+kmc_status  kmc_sampler_histograms(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */,
+                                   const int32_t* dims, int32_t ndims, const double* edges /* [ncols][nbins + 1] */, int32_t nbins,
+                                   int32_t with_logp, int64_t* counts1 /* [ncols][nbins] */, int64_t* outside /* [ncols][3] */,
+                                   int64_t* counts2 /* NULL or [npairs][nbins][nbins] */, int64_t* n_out);
+/* The same on a chain in host memory, uploaded to `device` first; every argument is checked before the device is touched.  The
+ * log-densities are the last 1-D column exactly when logp_host is not NULL. */
+kmc_status  kmc_chain_histograms(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                                 int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                                 const int32_t* dims, int32_t ndims, const double* edges, int32_t nbins, int device,
+                                 int64_t* counts1, int64_t* outside, int64_t* counts2, int64_t* n_out);
+/* How the 2-D kernel cuts the ndims (ndims - 1) / 2 pairs into groups whose counters (nbins^2 x 4 bytes a pair) share one workgroup's
+ * LDS next to the edges and a tile of bin indices: the selection is read once per group.  *lds_budget: the bytes a workgroup may use.
+ * Needs no device.  KMC_ERR_BAD_ARG unless 2 <= ndims <= 16 and 1 <= nbins <= 64. */
+kmc_status  kmc_hist_pair_plan(int32_t ndims, int32_t nbins, int32_t* pairs_per_group, int32_t* ngroups, int32_t* lds_budget);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

@@ -16,14 +16,14 @@ from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
 from .sampler import Sampler
-from .summary import map_sample, quantile_ranks, quantiles, summarize_run
+from .summary import corner, credible_levels, hist_mode, histogram, map_sample, quantile_ranks, quantiles, summarize_run
 from .tempering import geometric_betas, thermodynamic_integration
 
 __all__ = [
     "emcee", "make_theta0s", "squash_walkers", "emcee_counts", "Sampler", "KmcError",
     "DeviceLogPdf", "GaussianIso", "Exponential", "Rosenbrock", "LogNormal", "MvNormal2", "ExprDensity", "CDensity", "DataDensity", "HostLogPdf",
     "DEMove", "DESnookerMove", "geometric_betas", "thermodynamic_integration", "cdf_g_inv", "g_pdf", "metropolis", "metropolis_chains", "GaussianStep", "HostProposal", "int_acorr", "eff_samples",
-    "quantiles", "quantile_ranks", "map_sample", "summarize_run",
+    "quantiles", "quantile_ranks", "map_sample", "summarize_run", "histogram", "corner", "hist_mode", "credible_levels",
 ]
 
 

@@ -57,6 +57,7 @@ SYMBOLS = [
     "kmc_sampler_get_rung_state", "kmc_sampler_set_rung_state", "kmc_sampler_get_swaps",
     "kmc_sampler_get_rung_loglike", "kmc_sampler_set_rung_loglike_sum", "kmc_sampler_get_ladder", "kmc_sampler_set_ladder",
     "kmc_sampler_order_stats", "kmc_sampler_chain_argmax", "kmc_chain_order_stats", "kmc_chain_argmax",
+    "kmc_sampler_histograms", "kmc_chain_histograms", "kmc_hist_pair_plan",
 ]
 
 
@@ -270,6 +271,10 @@ def lib() -> C.CDLL:
     L.kmc_sampler_chain_argmax.argtypes = [vp, C.c_int64, bp, ip, ip, dp, dp]
     L.kmc_chain_order_stats.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, ip, C.c_int32, C.c_int, dp, dp, ip]
     L.kmc_chain_argmax.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int, ip, ip, dp, dp]
+    i32p = C.POINTER(C.c_int32)
+    L.kmc_sampler_histograms.argtypes = [vp, C.c_int64, bp, i32p, C.c_int32, dp, C.c_int32, C.c_int32, ip, ip, ip, ip]
+    L.kmc_chain_histograms.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, i32p, C.c_int32, dp, C.c_int32, C.c_int, ip, ip, ip, ip]
+    L.kmc_hist_pair_plan.argtypes = [C.c_int32, C.c_int32, i32p, i32p, i32p]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

@@ -1,0 +1,98 @@
+// kmc_chain_view.hpp -- what the calls that read a stored chain where it lies share on the host side (kmc_summary.hip: order statistics and
+// arg-max; kmc_hist.hip: histograms): the view of a chain on the device, the selection (first_sample, walker mask) and the two ways to
+// such a view -- the chain a sampler holds, or a dense host chain uploaded for the call.  Internal.
+#pragma once
+#include "kmc_host.hpp"
+#include "kmc_sampler.hpp"
+
+namespace kmc_chain_view {
+
+using namespace kmc_host;
+
+struct ChainView {
+    const void* chain = nullptr;       // device [nsamples][nl][ld], float or double
+    bool is_float = false;
+    int64_t ld = 0, ndim = 0;
+    const double* logp = nullptr;      // device [nsamples][nl] or nullptr
+    int64_t nsamples = 0, nl = 0;
+};
+
+// the device copies one call owns: the walker mask, and for kmc_chain_* the uploaded chain and log-densities
+struct ChainUpload {
+    uint8_t* mask = nullptr;
+    double *chain = nullptr, *logp = nullptr;
+    ~ChainUpload() { (void)hipFree(mask); (void)hipFree(chain); (void)hipFree(logp); }
+};
+
+// N = (nsamples - first_sample) * popcount(mask): what the ranks index
+inline kmc_status selection_size(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, int64_t* n)
+{
+    if (v.nsamples < 0 || v.nl <= 0 || v.ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples >= 0, nwalkers, ndim > 0");
+    if (v.nl >= ((int64_t)1 << 31) || v.ndim >= ((int64_t)1 << 24)) return fail(KMC_ERR_UNSUPPORTED, "chain too large: walkers < 2^31, ndim < 2^24");
+    if (first_sample < 0 || first_sample > v.nsamples) return fail(KMC_ERR_BAD_ARG, "first_sample must lie in [0, samples stored]");
+    int64_t nw = v.nl;
+    if (mask_host) {
+        nw = 0;
+        for (int64_t w = 0; w < v.nl; ++w) nw += mask_host[w] != 0;
+    }
+    *n = (v.nsamples - first_sample) * nw;
+    if (*n <= 0) return fail(KMC_ERR_BAD_ARG, "the selection is empty: no stored sample at or after first_sample, or no walker in the mask");
+    return KMC_OK;
+}
+
+inline kmc_status upload_mask(ChainUpload& b, const uint8_t* mask_host, int64_t nl, hipStream_t st)
+{
+    if (!mask_host) return KMC_OK;
+    HIP_TRY(hipMalloc((void**)&b.mask, (size_t)nl));
+    HIP_TRY(copy_sync(b.mask, mask_host, (size_t)nl, hipMemcpyHostToDevice, st));
+    return KMC_OK;
+}
+
+// the checks the sampler calls share; `host_call` names the call for a chain in host memory in the messages
+inline kmc_status sampler_view(kmc_sampler* s, bool need_logp, const char* host_call, ChainView* v)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    if (!s->d_chain) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_CHAIN");
+    if (need_logp && !s->d_chain_logp) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_LOGP");
+    if (s->stream_chain) return fail(KMC_ERR_UNSUPPORTED, std::string("KMC_STREAM_CHAIN: the chain is on the host; use ") + host_call + " on it");
+    if (s->cfg.shard_count > 1 || s->p2p)
+        return fail(KMC_ERR_UNSUPPORTED, std::string("sharded sampler: a shard holds only its own walkers and a select across GPUs is not built; gather the chain and use ") + host_call);
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    v->chain = s->d_chain; v->is_float = s->f32; v->ld = s->ld; v->ndim = s->cfg.ndim;
+    v->logp = s->d_chain_logp; v->nsamples = samples_done(s); v->nl = s->nlocal;
+    return KMC_OK;
+}
+
+// kmc_chain_*: a dense host chain on the device (its checks first: nothing is read before they pass)
+inline kmc_status host_view(ChainUpload& b, const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim, int device, ChainView* v)
+{
+    if (!chain_host) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (nsamples <= 0 || nwalkers <= 0 || ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples, nwalkers, ndim > 0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(KMC_ERR_NO_DEVICE, "no HIP device visible");
+    }
+    if (device < 0 || device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(device));
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const double need = (double)nsamples * (double)nwalkers * ((double)ndim + 1.0) * 8.0 + 64.0 * 1048576.0;
+    if (need > (double)free_b)
+        return fail(KMC_ERR_UNSUPPORTED, "the chain (" + std::to_string((int64_t)(need / 1048576.0)) + " MiB with its work space) does not fit the device (" +
+                                             std::to_string(free_b >> 20) + " MiB free); streaming a host chain through the device is not built");
+    const size_t rows = (size_t)nsamples * (size_t)nwalkers;
+    ScopedStream up;
+    HIP_TRY(up.create());
+    HIP_TRY(hipMalloc((void**)&b.chain, rows * (size_t)ndim * sizeof(double)));
+    HIP_TRY(copy_sync(b.chain, chain_host, rows * (size_t)ndim * sizeof(double), hipMemcpyHostToDevice, up.st));
+    if (logp_host) {
+        HIP_TRY(hipMalloc((void**)&b.logp, rows * sizeof(double)));
+        HIP_TRY(copy_sync(b.logp, logp_host, rows * sizeof(double), hipMemcpyHostToDevice, up.st));
+    }
+    v->chain = b.chain; v->is_float = false; v->ld = ndim; v->ndim = ndim; v->logp = b.logp; v->nsamples = nsamples; v->nl = nwalkers;
+    return KMC_OK;
+}
+
+}  // namespace kmc_chain_view

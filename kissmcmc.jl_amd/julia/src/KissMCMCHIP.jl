@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -621,6 +621,70 @@ function map_sample(thetas, logdensities; first_sample=0, walkers=nothing, devic
                chain, logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Cint(device), k, w, theta, lp)
     st == 0 || error("kmc_chain_argmax failed ($st): $(last_error())")
     return theta, lp[], k[] + 1, w[] + 1
+end
+
+"""
+    histograms(thetas, edges; dims=nothing, logdensities=nothing, pairs=false, first_sample=0, walkers=nothing, device=0)
+
+Marginal histograms of `thetas[walker][sample]` as `emcee` / `metropolis_chains` return it, counted on the GPU
+(`kmc_chain_histograms`).  `dims`: the dimensions (1-based; all by default), in the order wanted; `edges`: a `(nbins + 1) x ncols` matrix
+of strictly increasing bin edges, one column per selected dimension and, with `logdensities`, one more for them.  An element `x` is
+in bin `i` iff `e[i] <= x < e[i+1]`, the last bin closed.  Returns `(counts1, outside, counts2, n)`: `counts1` is `nbins x ncols`,
+`outside` is `3 x ncols` (below the first edge, above the last, NaN), `counts2` -- with `pairs=true`, else `nothing` -- is
+`nbins x nbins x npairs` over the pairs `(a, b)`, `a < b`, of positions in `dims`, `counts2[ib, ia, p]` counting bin `ia` of the pair's
+first dimension and `ib` of its second (2 to 16 dimensions, `nbins <= 64`), and `n` the number of selected samples.
+"""
+function histograms(thetas, edges; dims=nothing, logdensities=nothing, pairs=false, first_sample=0, walkers=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    sel = dims === nothing ? collect(Int32, 0:nd-1) : Int32[d - 1 for d in dims]
+    ncols = length(sel) + (logp === nothing ? 0 : 1)
+    e = Matrix{Float64}(edges)                               # column-major (nbins + 1, ncols) == C [ncols][nbins + 1]
+    size(e, 2) == ncols || error("edges must have one column per selected dimension (and one for the log-densities)")
+    nbins = size(e, 1) - 1
+    npairs = length(sel) * (length(sel) - 1) ÷ 2
+    counts1 = zeros(Int64, nbins, ncols); outside = zeros(Int64, 3, ncols)
+    counts2 = pairs ? zeros(Int64, nbins, nbins, npairs) : nothing
+    nout = Ref{Int64}(0)
+    st = ccall((:kmc_chain_histograms, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Ptr{Int32}, Int32, Ptr{Float64}, Int32, Cint,
+                Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, sel, Int32(length(sel)),
+               e, Int32(nbins), Cint(device), counts1, outside, counts2 === nothing ? C_NULL : counts2, nout)
+    st == 0 || error("kmc_chain_histograms failed ($st): $(last_error())")
+    return counts1, outside, counts2, nout[]
+end
+
+"""
+    corner(thetas; bins=32, range=nothing, dims=nothing, first_sample=0, walkers=nothing, device=0)
+
+The numbers of a corner plot: `(dims, pairs, edges, hist1d, outside, hist2d, n)` as a named tuple, over `bins` equal bins between
+`range = (lo, hi)` (one for all dimensions, or a vector of them), by default each dimension's minimum and maximum over the selection,
+taken on the GPU (`kmc_chain_order_stats`; equal limits widened by 0.5 either way).  See `histograms` for the layouts.
+"""
+function corner(thetas; bins=32, range=nothing, dims=nothing, first_sample=0, walkers=nothing, device=0)
+    chain, _, ns, nw, nd = _summary_chain(thetas, nothing)
+    sel = dims === nothing ? collect(1:nd) : collect(dims)
+    ext = Matrix{Float64}(undef, nd, 2)                      # every dimension's minimum and maximum over the selection: exact, on the device
+    if range === nothing
+        mask = _summary_mask(walkers, nw)
+        n = (ns - first_sample) * (mask === nothing ? nw : count(!iszero, mask))
+        n >= 1 || error("the selection is empty")
+        nout = Ref{Int64}(0)
+        st = ccall((:kmc_chain_order_stats, LIB), Cint,
+                   (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Ptr{Int64}, Int32, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+                   chain, C_NULL, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Int64[0, n - 1], Int32(2), Cint(device), ext, C_NULL, nout)
+        st == 0 || error("kmc_chain_order_stats failed ($st): $(last_error())")
+    end
+    edges = Matrix{Float64}(undef, bins + 1, length(sel))
+    for (j, d) in enumerate(sel)
+        lo, hi = range === nothing ? (ext[d, 1], ext[d, 2]) : (range isa Tuple ? range : range[j])
+        lo == hi && ((lo, hi) = (lo - 0.5, hi + 0.5))
+        edges[:, j] = collect(Base.range(lo, hi; length=bins + 1))
+    end
+    counts1, outside, counts2, n = histograms(thetas, edges; dims=sel, pairs=true, first_sample=first_sample, walkers=walkers, device=device)
+    pairs = [(sel[a], sel[b]) for a in 1:length(sel) for b in a+1:length(sel)]
+    return (dims=sel, pairs=pairs, edges=edges, hist1d=counts1, outside=outside, hist2d=counts2, n=n)
 end
 
 # make_theta0s (src/samplers.jl:311-349) and squash_walkers (src/samplers.jl:372-428): KissMCMC's own, imported above.

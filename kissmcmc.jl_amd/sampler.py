@@ -523,6 +523,22 @@ class Sampler:
         from .summary import _SamplerProvider
         return _SamplerProvider(self, first_sample, walkers).argmax()
 
+    def histogram(self, bins=40, range=None, dims=None, first_sample: int = 0, walkers=None, logp: bool = False, quantile_range=None):
+        """1-D marginal histograms of the stored chain, counted on the device in one read of it (``kmc_sampler_histograms``):
+        ``(counts[ncols, B], edges[ncols, B + 1], outside[ncols, 3])`` for the dimensions ``dims`` (all; in the order given) and, with
+        ``logp=True``, the stored log-densities as the last column.  ``bins``: a count, an edge array ``[B + 1]`` or ``[ncols, B + 1]``
+        (``B <= 256``); with a count the limits are ``range`` (``(lo, hi)`` or ``[ncols, 2]``), else the quantiles ``quantile_range``,
+        else each column's exact minimum and maximum, and ``s.histogram(bins=B)`` is ``np.histogram(column, bins=B)``, counts and
+        edges.  ``outside``: the elements below the first edge, above the last, and the NaNs.  See :func:`kissmcmc_jl_amd.histogram`."""
+        from .summary import _SamplerProvider, histogram_from
+        return histogram_from(_SamplerProvider(self, first_sample, walkers), bins, range, quantile_range, dims, logp)
+
+    def corner(self, bins=32, range=None, quantile_range=None, dims=None, first_sample: int = 0, walkers=None):
+        """The numbers of a corner plot from the device chain: a dict ``dims, pairs, edges, hist1d, outside, hist2d[npairs, B, B], n``
+        over 2 to 16 dimensions ``dims`` (all by default) with ``B <= 64`` bins; see :func:`kissmcmc_jl_amd.corner`."""
+        from .summary import _SamplerProvider, corner_from
+        return corner_from(_SamplerProvider(self, first_sample, walkers), bins, range, quantile_range, dims)
+
     def summary(self, theta_true=None, names=None, eff_samples=None):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
         from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain."""

@@ -5,6 +5,10 @@ to be bit-compatible with.  The order statistics (and with them every quantile) 
 on the GPU where the chain lies (``kmc_sampler_order_stats`` / ``kmc_sampler_chain_argmax``; ``kmc_chain_*`` for a chain in host
 memory): exact, by radix select over the keys described in ``include/kissmcmc_hip.h``; the chain does not cross to the host.
 
+So are the marginal histograms of a corner plot (:func:`histogram`, :func:`corner`; ``kmc_sampler_histograms`` /
+``kmc_chain_histograms``): every selected column's 1-D histogram and every pair's 2-D histogram, exact integer counts by numpy's
+binning rule.
+
 Input layout of the module-level functions: what ``emcee`` / ``metropolis_chains`` return, ``thetas[walker][sample]`` (scalar
 walkers) or ``thetas[walker][sample][dim]``, and ``logdensities[walker][sample]``.
 """
@@ -17,6 +21,7 @@ import numpy as np
 from . import _lib
 
 MAX_RANKS = 16          # per call of the library (kmc_sampler_order_stats)
+MAX_BINS, MAX_BINS_2D, MAX_DIMS_2D = 256, 64, 16       # kmc_sampler_histograms
 
 
 def quantile_ranks(q, n: int):
@@ -64,6 +69,18 @@ def _p(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
 
 
+def _hist_buffers(dims, edges, logp, pairs):
+    """The arrays one histogram call of the library takes and fills."""
+    dims = np.ascontiguousarray(dims, dtype=np.int32)
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    ncols = dims.size + (1 if logp else 0)
+    if edges.ndim != 2 or edges.shape[0] != ncols or edges.shape[1] < 2:
+        raise ValueError(f"edges must be [{ncols}, nbins + 1]")
+    B = edges.shape[1] - 1
+    c2 = np.zeros((dims.size * (dims.size - 1) // 2, B, B), dtype=np.int64) if pairs else None
+    return dims, edges, np.zeros((ncols, B), dtype=np.int64), np.zeros((ncols, 3), dtype=np.int64), c2
+
+
 class _SamplerProvider:
     """Order statistics and arg-max of the chain a :class:`Sampler` holds on the device."""
 
@@ -90,6 +107,17 @@ class _SamplerProvider:
         _lib.check(self.s._L.kmc_sampler_chain_argmax(self.s._h, self.first, _p(self.mask, C.c_uint8), C.byref(k), C.byref(w),
                                                       _p(th, C.c_double), C.byref(lp)))
         return th, lp.value, k.value, w.value
+
+    def histograms(self, dims, edges, logp=False, pairs=False):
+        """``(counts1[ncols, B], outside[ncols, 3], counts2[npairs, B, B] | None)`` for the chain columns ``dims`` (and the
+        log-densities as the last column with ``logp``) and ``edges[ncols, B + 1]``."""
+        dims, edges, c1, out, c2 = _hist_buffers(dims, edges, logp, pairs)
+        n = C.c_int64()
+        _lib.check(self.s._L.kmc_sampler_histograms(self.s._h, self.first, _p(self.mask, C.c_uint8), _p(dims, C.c_int32), dims.size,
+                                                    _p(edges, C.c_double), edges.shape[1] - 1, int(bool(logp)), _p(c1, C.c_int64),
+                                                    _p(out, C.c_int64), _p(c2, C.c_int64), C.byref(n)))
+        self.n = n.value
+        return c1, out, c2
 
 
 class _HostProvider:
@@ -137,6 +165,18 @@ class _HostProvider:
                                                C.byref(lp)))
         return th, lp.value, k.value, w.value
 
+    def histograms(self, dims, edges, logp=False, pairs=False):
+        if logp and self.logp is None:
+            raise ValueError("no logdensities were given")
+        dims, edges, c1, out, c2 = _hist_buffers(dims, edges, logp, pairs)
+        n = C.c_int64()
+        _lib.check(_lib.lib().kmc_chain_histograms(_p(self.chain, C.c_double), _p(self.logp if logp else None, C.c_double), self.nsamples,
+                                                   self.nwalkers, self.ndim, self.first, _p(self.mask, C.c_uint8), _p(dims, C.c_int32), dims.size,
+                                                   _p(edges, C.c_double), edges.shape[1] - 1, self.device, _p(c1, C.c_int64), _p(out, C.c_int64),
+                                                   _p(c2, C.c_int64), C.byref(n)))
+        self.n = n.value
+        return c1, out, c2
+
 
 def quantiles_from(provider, q, logp=False):
     """Quantiles ``q`` from a provider of order statistics (``.n``, ``.ndim``, ``.order_stats(ranks, logp)``): the two order
@@ -171,6 +211,127 @@ def map_sample(thetas, logdensities, first_sample: int = 0, walkers=None, device
     """The stored sample of the largest log-density: ``(theta[ndim], logp, sample, walker)``; ties go to the smallest sample, then the
     smallest walker; NaN log-densities are ignored."""
     return _HostProvider(thetas, logdensities, first_sample, walkers, device).argmax()
+
+
+# ---- marginal histograms and the corner table ------------------------------------------------------------------------------------
+
+def pair_list(ndims: int):
+    """The pairs ``(a, b)``, ``a < b``, of positions in a list of ``ndims`` dimensions, in the library's order:
+    ``(0, 1), (0, 2), ..., (1, 2), ...``."""
+    return [(a, b) for a in range(ndims) for b in range(a + 1, ndims)]
+
+
+def hist_edges(provider, bins, range=None, quantile_range=None, dims=None, logp=False):
+    """``(dims, edges[ncols, B + 1])`` for a histogram call: the selected chain columns (all by default) and, with ``logp``, the
+    log-densities as the last column.  ``bins``: a bin count, an edge array ``[B + 1]`` shared by all columns, or ``[ncols, B + 1]``.
+    With a count the limits are ``range`` (``(lo, hi)`` or ``[ncols, 2]``), else the quantiles ``quantile_range = (q_lo, q_hi)``, else
+    each column's minimum and maximum, both exact, from the provider's order statistics; equal limits are widened by 0.5 either way
+    and ``edges = np.linspace(lo, hi, B + 1)``, as ``np.histogram`` does."""
+    dims = np.arange(provider.ndim) if dims is None else np.atleast_1d(np.asarray(dims, dtype=np.int64))
+    if dims.ndim != 1 or dims.size == 0:
+        raise ValueError("dims must be a non-empty list of dimensions")
+    if np.any(dims < 0) or np.any(dims >= provider.ndim):
+        raise IndexError(f"dimension outside [0, {provider.ndim})")
+    ncols = dims.size + (1 if logp else 0)
+    if np.ndim(bins) > 0:
+        e = np.asarray(bins, dtype=np.float64)
+        if e.ndim == 1:
+            e = np.broadcast_to(e, (ncols, e.size))
+        if e.ndim != 2 or e.shape[0] != ncols or e.shape[1] < 2:
+            raise ValueError(f"bin edges must be [nbins + 1] or [{ncols}, nbins + 1]")
+        return dims, np.ascontiguousarray(e)
+    B = int(bins)
+    if B < 1:
+        raise ValueError("bins must be at least 1")
+    if range is not None:
+        lim = np.asarray(range, dtype=np.float64)
+        lim = np.broadcast_to(lim, (ncols, 2)) if lim.shape == (2,) else lim
+        if lim.shape != (ncols, 2):
+            raise ValueError(f"range must be (lo, hi) or [{ncols}, 2]")
+        lo, hi = lim[:, 0].copy(), lim[:, 1].copy()
+    else:
+        if quantile_range is not None:
+            if len(quantile_range) != 2:
+                raise ValueError("quantile_range must be (q_lo, q_hi)")
+            got = quantiles_from(provider, list(quantile_range), logp=logp)
+            th, lp = got if logp else (got, None)
+        else:
+            if provider.n < 1:
+                provider.order_stats(np.zeros(1, dtype=np.int64), logp)      # the library's own refusal of an empty selection
+                raise ValueError("the selection is empty")
+            th, lp = provider.order_stats(np.array([0, provider.n - 1], dtype=np.int64), logp)
+        lo, hi = th[0, dims], th[1, dims]
+        if logp:
+            lo, hi = np.append(lo, lp[0]), np.append(hi, lp[1])
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("the range of a column is not finite")            # (np.histogram: "autodetected range ... is not finite")
+    if np.any(lo > hi):
+        raise ValueError("max must be larger than min in range")
+    same = lo == hi
+    lo, hi = np.where(same, lo - 0.5, lo), np.where(same, hi + 0.5, hi)        # numpy's _get_outer_edges
+    return dims, np.stack([np.linspace(l, h, B + 1) for l, h in zip(lo.tolist(), hi.tolist())])
+
+
+def histogram_from(provider, bins=40, range=None, quantile_range=None, dims=None, logp=False):
+    """:func:`histogram` from a provider (``.n``, ``.ndim``, ``.order_stats(ranks, logp)``, ``.histograms(dims, edges, logp, pairs)``)."""
+    dims, edges = hist_edges(provider, bins, range, quantile_range, dims, logp)
+    counts, outside, _ = provider.histograms(dims, edges, logp, False)
+    return counts, edges, outside
+
+
+def corner_from(provider, bins=32, range=None, quantile_range=None, dims=None):
+    """:func:`corner` from a provider."""
+    dims, edges = hist_edges(provider, bins, range, quantile_range, dims, False)
+    counts, outside, h2 = provider.histograms(dims, edges, False, True)
+    pairs = [(int(dims[a]), int(dims[b])) for a, b in pair_list(dims.size)]
+    return {"dims": dims.tolist(), "pairs": pairs, "edges": edges, "hist1d": counts, "outside": outside, "hist2d": h2, "n": provider.n}
+
+
+def histogram(thetas, bins=40, range=None, quantile_range=None, dims=None, logdensities=None, first_sample: int = 0, walkers=None,
+              device: int = 0):
+    """1-D marginal histograms of ``thetas[walker][sample](dim)``, counted on the GPU in one read of the chain:
+    ``(counts[ncols, B], edges[ncols, B + 1], outside[ncols, 3])``, ``int64`` counts, one row per dimension of ``dims`` (all by
+    default, in the order given) and, with ``logdensities``, one more for them.  An element ``x`` is in bin ``i`` iff
+    ``e[i] <= x < e[i + 1]``, the last bin closed; ``outside`` counts what lies below ``e[0]``, above ``e[B]`` and the NaNs.
+    With a bin count and no range the result is ``np.histogram(column, bins=B)``, counts and edges; see :func:`hist_edges` for
+    ``bins``, ``range`` and ``quantile_range``.  The selection is that of :func:`quantiles`."""
+    p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
+    return histogram_from(p, bins, range, quantile_range, dims, logp=logdensities is not None)
+
+
+def corner(thetas, bins=32, range=None, quantile_range=None, dims=None, first_sample: int = 0, walkers=None, device: int = 0):
+    """The numbers of a corner plot, counted on the GPU: a dict ``dims`` (the selected dimensions, 2 to 16), ``pairs`` (the pairs of
+    dimensions ``(a, b)`` in list order: first with second, first with third, ...), ``edges[ndims, B + 1]``, ``hist1d[ndims, B]``,
+    ``outside[ndims, 3]``, ``hist2d[npairs, B, B]`` (``np.histogram2d(x_a, x_b, bins=[e_a, e_b])``, ``B <= 64``) and ``n``, the number
+    of selected samples.  ``bins``, ``range`` and ``quantile_range`` as in :func:`histogram`."""
+    return corner_from(_HostProvider(thetas, None, first_sample, walkers, device), bins, range, quantile_range, dims)
+
+
+def hist_mode(counts, edges):
+    """The centre of the fullest bin, the first one on ties: a scalar for ``counts[B]``, ``edges[B + 1]``; one value per row for
+    ``counts[ncols, B]``, ``edges[ncols, B + 1]``."""
+    c, e = np.asarray(counts), np.asarray(edges, dtype=np.float64)
+    if c.ndim == 1:
+        i = int(np.argmax(c))
+        return 0.5 * (e[i] + e[i + 1])
+    i = np.argmax(c, axis=1)
+    r = np.arange(c.shape[0])
+    return 0.5 * (e[r, i] + e[r, i + 1])
+
+
+def credible_levels(hist2d, levels=(0.393, 0.865)):
+    """For contour drawing: per level ``p`` the largest count ``t`` such that the bins with at least ``t`` counts -- the super-level
+    set -- hold at least the share ``p`` of the histogram's mass (0.393 and 0.865: the 1- and 2-sigma contours of a 2-D Gaussian).
+    Returns an array like ``levels``."""
+    h = np.sort(np.asarray(hist2d).ravel())[::-1]
+    cum = np.cumsum(h)
+    if h.size == 0 or cum[-1] <= 0:
+        raise ValueError("the histogram is empty")
+    p = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if np.any(~((p > 0.0) & (p <= 1.0))):
+        raise ValueError("levels must lie in (0, 1]")
+    idx = np.minimum(np.searchsorted(cum, p * cum[-1], side="left"), h.size - 1)
+    return h[idx]
 
 
 def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_samples=None):
