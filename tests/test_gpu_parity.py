@@ -51,7 +51,15 @@ def _run_both(kmc, oracle, name, nw, nd, G, nburn, nthin, seed, use_graph=True, 
                    accept_ratio=s.accept_ratio())
         got["chain"], got["chain_logp"] = s.chain()
         got["sum"], got["sumsq"], got["nmoment"] = s.moments()
+        got["desc"] = s.describe()
     return ref, got
+
+
+def _ran(got, plan):
+    """describe() names the forced geometry: a plan without an instantiation falls back to the one-walker-per-lane kernel, and a small
+    ensemble leaves for the LDS-resident kernel whatever KMC_PLAN says -- both without a word."""
+    want = "half_step_generic" if plan == "generic" else "half_step_vec L=%s K=%s ITER=%s " % tuple(plan.split(","))
+    assert want in got["desc"], (plan, got["desc"])
 
 
 def _compare(ref, got):
@@ -118,13 +126,17 @@ def test_moments_folded_per_workgroup(kmc, oracle, name, nw, nd, plan, monkeypat
     """ITER >= 4 (the planner's geometries for ensembles that live in HBM) with several waves per workgroup: the waves' moment sums are added up through
     LDS and one wave per workgroup rewrites its accumulator slots (kmc_kernels.hpp: kWgFold) -- same chain, moments to 1e-11, partly idle last workgroups."""
     ref, got = _run_both(kmc, oracle, name, nw, nd, 70, 20, 3, seed=7, plan=plan, monkeypatch=monkeypatch)
+    _ran(got, plan)
     _compare(ref, got)
 
 
-@pytest.mark.parametrize("plan", ["generic", "16,1,1", "16,1,2", "16,1,4", "16,1,8", "16,1,16", "8,2,1", "8,2,4", "8,2,8", "4,4,1", "4,4,4", "4,2,2"])
+@pytest.mark.parametrize("plan", ["generic", "16,1,1", "16,1,2", "16,1,4", "16,1,8", "16,1,16", "8,2,1", "8,2,4", "8,2,8", "4,4,1", "4,4,4", "4,4,2"])
 def test_every_geometry_gives_the_same_chain(kmc, oracle, plan, monkeypatch):
-    """The result is a pure function of (seed, inputs): launch geometry must not matter."""
+    """The result is a pure function of (seed, inputs): launch geometry must not matter.  (512 x 32 fits the LDS-resident kernel, which
+    does not look at KMC_PLAN: kept in the multi-launch kernels, or every plan would run the same resident kernel.)"""
+    kmcenv.no_resident(monkeypatch)
     ref, got = _run_both(kmc, oracle, "gauss", 512, 32, 70, 20, 1, seed=99, plan=plan, monkeypatch=monkeypatch)
+    _ran(got, plan)
     _compare(ref, got)
 
 
