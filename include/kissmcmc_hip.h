@@ -760,6 +760,70 @@ kmc_status  kmc_chain_histograms(const double* chain_host /* [nsamples][nwalkers
  * Needs no device.  KMC_ERR_BAD_ARG unless 2 <= ndims <= 16 and 1 <= nbins <= 64. */
 kmc_status  kmc_hist_pair_plan(int32_t ndims, int32_t nbins, int32_t* pairs_per_group, int32_t* ngroups, int32_t* lds_budget);
 
+/* ---- convergence across chains of a stored chain, on the device: split-R^, effective sample size, Monte-Carlo standard error ----
+ * The two columns of a summary table that ask whether the chains agree and how much the mean is worth (the evaluate_convergence and
+ * error_of_estimated_mean that reference src/analysis.jl:79-95, :242-248 sketches, commented out, over MCMCDiagnostics.jl).  The
+ * formulas below are the definition (BDA3: Gelman et al. 2014, pp. 284-287); no other implementation is followed.
+ *
+ * Chains.  The selection is that of the order statistics: the stored samples k >= first_sample of the walkers in the mask, nw walkers
+ * and n samples.  Every selected walker is a chain; with split != 0 it is cut into halves of h = n / 2 samples, [first, first + h) and
+ * [first + n - h, first + n) (an odd n leaves the middle sample out), chain j = half * nw + k for the k-th selected walker in ascending
+ * order, m = 2 nw chains.  Without split h = n, m = nw.  h >= 4 and m >= 2, else KMC_ERR_BAD_ARG.
+ * Columns: every dimension and, when asked (needs KMC_STORE_LOGP), the log-densities as the last: ncols.  Per column, with x[i][j]
+ * sample i of chain j:
+ *   mu_j, s2_j   chain means and variances; two passes, squares of x - mu_j, h - 1 in the denominator
+ *   W = mean_j s2_j;  B / h = var_j(mu_j), m - 1 in the denominator;  var+ = ((h - 1) / h) W + B / h;  R^ = sqrt(var+ / W)
+ *   D_t = sum_j sum_{i = t}^{h - 1} (x[i][j] - x[i - t][j])^2     (a pair never straddles the halves of a walker or reaches before
+ *                                                                   first_sample)
+ *   V_t = D_t / (m (h - t));  rho_t = 1 - V_t / (2 var+)
+ *   T: walking T = 1, 3, 5, ...: stop with KMC_CONV_TRUNCATED if T + 2 > max_lag; else stop if rho_(T+1) + rho_(T+2) < 0; else T += 2
+ *   ess = m h / (1 + 2 sum_{t = 1}^{T} rho_t), NaN unless the denominator is > 0;  mcse = sqrt(var+ / ess)
+ *   mean = mean_j mu_j;  the standard deviation of the table is sqrt(var+)
+ * NaN and +-inf in the chain propagate.  W == 0 (a constant chain) gives rhat = ess = mcse = NaN, T = 0, and no error.
+ *
+ * The device stage.  chain_mean and chain_var [ncols][m] (both or neither may be NULL) and lagsum[c][k] = D_(lag0 + k), k = 0 ..
+ * nlags - 1, with 1 <= lag0 and lag0 + nlags - 1 <= h - 1 (nlags may be 0).  The chain is read where it lies: for each block of 32 lags
+ * an element is loaded into a window in LDS once per tile as the leading sample of its pairs and at most twice as the trailing one,
+ * not once per lag.  No floating-point atomics: workgroups write partial sums and a second kernel adds them in a
+ * fixed order, so two identical calls return the same bits; each number is the sum of its terms, formed in double as written above, in
+ * an order the library chooses.  Refusals as for the order statistics. */
+#define KMC_CONV_NEED_LAGS 1   /* flags bit 0: the rule has not fired within the lags given (call again with more) */
+#define KMC_CONV_TRUNCATED 2   /* flags bit 1: the rule has not fired up to max_lag */
+kmc_status  kmc_sampler_lag_sums(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int32_t split,
+                                 int32_t with_logp, int64_t lag0, int64_t nlags, double* chain_mean, double* chain_var, double* lagsum,
+                                 int64_t* m_out, int64_t* h_out);
+/* The same on a chain in host memory, uploaded to `device` first; every argument is checked before the device is touched.  The
+ * log-densities are the last column exactly when logp_host is not NULL. */
+kmc_status  kmc_chain_lag_sums(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                               int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                               int32_t split, int64_t lag0, int64_t nlags, int device, double* chain_mean, double* chain_var,
+                               double* lagsum, int64_t* m_out, int64_t* h_out);
+/* The host stage; needs no device.  chain_mean, chain_var [ncols][m]; lagsum [ncols][nlags] holds D_1 .. D_nlags (0 <= nlags <= h - 1);
+ * max_lag in [3, h - 1].  Fills, per column, mean, W, B, var_plus, rhat, ess, mcse, T and flags.  When the walk needs rho beyond
+ * nlags, flags gets KMC_CONV_NEED_LAGS and ess, mcse are taken with the T reached so far: call again with more lags.  Every sum is
+ * sequential in index order (j, then t) and (double)(h - 1) / (double)h is formed before the product with W, so a
+ * restatement in another language gives the same bits.  KMC_ERR_BAD_ARG: a null pointer, ncols < 1, h < 4, m < 2, max_lag or nlags
+ * outside their ranges. */
+kmc_status  kmc_convergence_stats(int64_t m, int64_t h, int64_t ncols, const double* chain_mean, const double* chain_var,
+                                  const double* lagsum, int64_t nlags, int64_t max_lag, double* mean, double* W, double* B,
+                                  double* var_plus, double* rhat, double* ess, double* mcse, int64_t* T, int32_t* flags);
+/* The whole thing in one call: the chain moments once, then 32, 64, 128, ... lags in all until every column's rule has fired or max_lag
+ * (0: min(h - 1, 1024); else in [3, h - 1]) is reached.  Outputs [ncols] as above; info (may be NULL) gets 4 numbers for benchmarks: the
+ * lags computed, the blocks of 32 lags run, the bytes of the chain the lag kernel loaded and those the moment kernels loaded. */
+kmc_status  kmc_sampler_convergence(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
+                                    int64_t max_lag, double* mean, double* W, double* B, double* var_plus, double* rhat, double* ess,
+                                    double* mcse, int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
+/* The tile of the lag kernel: lags per block (32), leading samples per tile (32), lanes along the (walker, column) axis (64) and the
+ * bytes of LDS one workgroup uses.  D_t has the same bits however its lags are cut into calls.  Needs no device; pointers may be NULL. */
+kmc_status  kmc_convergence_plan(int32_t* lag_block, int32_t* tile_samples, int32_t* lanes, int32_t* lds_bytes);
+kmc_status  kmc_chain_convergence(const double* chain_host, const double* logp_host /* or NULL */, int64_t nsamples, int64_t nwalkers,
+                                  int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag,
+                                  int device, double* mean, double* W, double* B, double* var_plus, double* rhat, double* ess,
+                                  double* mcse, int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
+/* The tile of the lag kernel: lags per block (32), leading samples per tile (32), lanes along the (walker, column) axis (64) and the
+ * bytes of LDS one workgroup uses.  D_t has the same bits however its lags are cut into calls.  Needs no device; pointers may be NULL. */
+kmc_status  kmc_convergence_plan(int32_t* lag_block, int32_t* tile_samples, int32_t* lanes, int32_t* lds_bytes);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

@@ -33,6 +33,7 @@ STORE_BLOBS = 8192
 MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_MIX = 0, 1, 3, 4
 MIX_MAX = 4
 TEMPS_MAX = 64  # parallel tempering: most rungs of a ladder (kmc_config.ntemps)
+CONV_NEED_LAGS, CONV_TRUNCATED = 1, 2  # flags of kmc_convergence_stats
 TEMPER_WHOLE, TEMPER_LIKELIHOOD = 0, 1  # kmc_config.temper_mode
 P2P_HANDLE_BYTES = 128
 RCCL_ID_BYTES = 128
@@ -58,6 +59,8 @@ SYMBOLS = [
     "kmc_sampler_get_rung_loglike", "kmc_sampler_set_rung_loglike_sum", "kmc_sampler_get_ladder", "kmc_sampler_set_ladder",
     "kmc_sampler_order_stats", "kmc_sampler_chain_argmax", "kmc_chain_order_stats", "kmc_chain_argmax",
     "kmc_sampler_histograms", "kmc_chain_histograms", "kmc_hist_pair_plan",
+    "kmc_sampler_lag_sums", "kmc_chain_lag_sums", "kmc_convergence_stats", "kmc_sampler_convergence", "kmc_chain_convergence",
+    "kmc_convergence_plan",
 ]
 
 
@@ -275,6 +278,12 @@ def lib() -> C.CDLL:
     L.kmc_sampler_histograms.argtypes = [vp, C.c_int64, bp, i32p, C.c_int32, dp, C.c_int32, C.c_int32, ip, ip, ip, ip]
     L.kmc_chain_histograms.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, i32p, C.c_int32, dp, C.c_int32, C.c_int, ip, ip, ip, ip]
     L.kmc_hist_pair_plan.argtypes = [C.c_int32, C.c_int32, i32p, i32p, i32p]
+    L.kmc_sampler_lag_sums.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, dp, dp, dp, ip, ip]
+    L.kmc_chain_lag_sums.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int64, C.c_int, dp, dp, dp, ip, ip]
+    L.kmc_convergence_stats.argtypes = [C.c_int64, C.c_int64, C.c_int64, dp, dp, dp, C.c_int64, C.c_int64, dp, dp, dp, dp, dp, dp, dp, ip, i32p]
+    L.kmc_sampler_convergence.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, ip, i32p, ip, ip, ip]
+    L.kmc_chain_convergence.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int, dp, dp, dp, dp, dp, dp, dp, ip, i32p, ip, ip, ip]
+    L.kmc_convergence_plan.argtypes = [i32p, i32p, i32p, i32p]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -685,6 +685,34 @@ function corner(thetas; bins=32, range=nothing, dims=nothing, first_sample=0, wa
     counts1, outside, counts2, n = histograms(thetas, edges; dims=sel, pairs=true, first_sample=first_sample, walkers=walkers, device=device)
     pairs = [(sel[a], sel[b]) for a in 1:length(sel) for b in a+1:length(sel)]
     return (dims=sel, pairs=pairs, edges=edges, hist1d=counts1, outside=outside, hist2d=counts2, n=n)
+end
+
+"""
+    convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+
+Split-R-hat, effective sample size and Monte-Carlo standard error per dimension of `thetas[walker][sample]` as `emcee` /
+`metropolis_chains` return it (and of `logdensities`, as a last column, when given), computed on the GPU (`kmc_chain_convergence`; the
+definitions are in include/kissmcmc_hip.h: BDA3, Gelman et al. 2014, pp. 284-287).  Every selected walker is a chain, cut into halves
+with `split`.  Returns a named tuple `(mean, std, rhat, ess, mcse, lag, truncated, m, h)`.  The walkers of ONE emcee ensemble are not
+independent, so R-hat over them is optimistic (src/analysis.jl:69-71): pass the concatenated walkers of separate runs, or Metropolis chains.
+"""
+function convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    ncols = nd + (logp === nothing ? 0 : 1)
+    mean = Vector{Float64}(undef, ncols); W = similar(mean); B = similar(mean); var_plus = similar(mean)
+    rhat = similar(mean); ess = similar(mean); mcse = similar(mean)
+    T = Vector{Int64}(undef, ncols); flags = Vector{Int32}(undef, ncols)
+    m = Ref{Int64}(0); h = Ref{Int64}(0)
+    st = ccall((:kmc_chain_convergence, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int32, Int64, Cint,
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32},
+                Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Int32(split ? 1 : 0),
+               max_lag === nothing ? 0 : (max_lag == 0 ? -1 : max_lag), Cint(device),
+               mean, W, B, var_plus, rhat, ess, mcse, T, flags, m, h, C_NULL)
+    st == 0 || error("kmc_chain_convergence failed ($st): $(last_error())")
+    return (mean=mean, std=sqrt.(var_plus), rhat=rhat, ess=ess, mcse=mcse, lag=T, truncated=(flags .& Int32(2)) .!= 0, m=m[], h=h[])
 end
 
 # make_theta0s (src/samplers.jl:311-349) and squash_walkers (src/samplers.jl:372-428): KissMCMC's own, imported above.

@@ -539,9 +539,26 @@ class Sampler:
         from .summary import _SamplerProvider, corner_from
         return corner_from(_SamplerProvider(self, first_sample, walkers), bins, range, quantile_range, dims)
 
-    def summary(self, theta_true=None, names=None, eff_samples=None):
+    def lag_sums(self, lag0: int = 1, nlags: int = 0, first_sample: int = 0, walkers=None, split: bool = True, logp: bool = False,
+                 moments: bool = True):
+        """The device stage of the convergence diagnostics on the stored chain (``kmc_sampler_lag_sums``): a dict
+        ``chain_mean[ncols, m], chain_var[ncols, m], lagsum[ncols, nlags], m, h``; see :func:`kissmcmc_jl_amd.lag_sums`."""
+        from .chain_convergence import sampler_lag_sums
+        return sampler_lag_sums(self, lag0, nlags, first_sample, walkers, split, logp, moments)
+
+    def convergence(self, first_sample: int = 0, walkers=None, split: bool = True, logp: bool = False, max_lag=None):
+        """Split-R-hat, effective sample size and Monte-Carlo standard error per dimension of the stored chain (with ``logp=True``
+        also of the stored log-densities, as the last column), read on the device where it lies (``kmc_sampler_convergence``): a dict
+        of columns ``mean, std, rhat, ess, mcse, lag, truncated`` and ``m``, ``h``.  Every walker is a chain (cut in two with
+        ``split``); the walkers of one ensemble are not independent, so ``rhat`` over them is optimistic -- see
+        :func:`kissmcmc_jl_amd.convergence` and :func:`kissmcmc_jl_amd.evaluate_convergence`."""
+        from .chain_convergence import columns, sampler_convergence_raw
+        return columns(sampler_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
+
+    def summary(self, theta_true=None, names=None, eff_samples=None, convergence: bool = False):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
-        from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain."""
+        from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain;
+        ``convergence=True`` adds the columns ``rhat, ess, mcse`` of :meth:`convergence`."""
         from .summary import _SamplerProvider, quantiles_from, summary_columns
         p = _SamplerProvider(self)
         median = quantiles_from(p, [0.5])[0]
@@ -554,7 +571,7 @@ class Sampler:
             flat = self.chain(logp=False)[0].reshape(-1, self.ndim)
             mean = flat.mean(axis=0)
             std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(self.ndim, np.nan)
-        return summary_columns(names, median, mean, std, mode, theta_true, eff_samples)
+        return summary_columns(names, median, mean, std, mode, theta_true, eff_samples, self.convergence() if convergence else None)
 
     def device_ptr(self, which: int) -> int:
         return int(self._L.kmc_sampler_device_ptr(self._h, int(which)) or 0)

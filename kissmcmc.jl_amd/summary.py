@@ -334,9 +334,10 @@ def credible_levels(hist2d, levels=(0.393, 0.865)):
     return h[idx]
 
 
-def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_samples=None):
+def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_samples=None, convergence=None):
     """The table of ``summarize_run`` (reference ``src/analysis.jl:14-38``) as a dict of columns, in the reference's order:
-    ``var, [err,] median, mean, mode, std[, eff_samples]``."""
+    ``var, [err,] median, mean, mode, std[, eff_samples]``; then ``rhat, ess, mcse`` when ``convergence`` (the dict of
+    :func:`kissmcmc_jl_amd.convergence`) is given."""
     median, mean, std = (np.asarray(a, dtype=np.float64) for a in (median, mean, std))
     nt = median.size
     names = [str(i + 1) for i in range(nt)] if names is None else [str(v) for v in names]          # :9 names=["$i" for i=1:nt]
@@ -354,10 +355,14 @@ def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_sa
     cols["std"] = std
     if eff_samples is not None:
         cols["eff_samples"] = np.asarray(eff_samples)                                              # :26, :37
+    if convergence is not None:
+        for k in ("rhat", "ess", "mcse"):
+            cols[k] = np.asarray(convergence[k], dtype=np.float64)[:nt]
     return cols
 
 
-def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_samples=None, provider=None, device: int = 0):
+def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_samples=None, provider=None, device: int = 0,
+                  convergence: bool = False):
     """Summary statistics of a run, reference ``src/analysis.jl:9-42`` (commented out there; followed as written): a dict of columns
     ``var`` (the names, ``"1" .. "ndim"`` by default), ``err = |theta_true - median|`` (only with ``theta_true``), ``median``,
     ``mean``, ``mode``, ``std`` (Julia's: n - 1 in the denominator) and ``eff_samples`` (only when given, passed through).
@@ -365,7 +370,10 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     ``mode`` is the MAP sample -- the stored sample of the largest log-density -- when ``logdensities`` are given, else None.  (The
     reference takes ``mode`` as an argument; its line 24 tests ``mod==nothing``, the function ``mod``, where line 35 tests
     ``mode==nothing``: read as ``mode``.)  The median and the MAP sample come from the device; ``provider`` replaces the device as
-    the source of order statistics and arg-max (tests)."""
+    the source of order statistics and arg-max (tests).
+
+    ``convergence=True`` adds the columns ``rhat``, ``ess`` and ``mcse`` of :func:`kissmcmc_jl_amd.convergence` (split chains, every
+    walker a chain; computed on the device)."""
     th = np.asarray(thetas, dtype=np.float64)
     if th.ndim == 2:
         th = th[:, :, None]
@@ -377,4 +385,8 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     median = quantiles_from(provider, [0.5])[0]
     mode = provider.argmax()[0] if logdensities is not None else None
     std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(flat.shape[1], np.nan)
-    return summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples)
+    conv = None
+    if convergence:
+        from .chain_convergence import convergence as _convergence
+        conv = _convergence(th, device=device)
+    return summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv)
