@@ -824,6 +824,69 @@ kmc_status  kmc_chain_convergence(const double* chain_host, const double* logp_h
  * bytes of LDS one workgroup uses.  D_t has the same bits however its lags are cut into calls.  Needs no device; pointers may be NULL. */
 kmc_status  kmc_convergence_plan(int32_t* lag_block, int32_t* tile_samples, int32_t* lanes, int32_t* lds_bytes);
 
+/* ---- rank-normalised R^ with bulk and tail effective sample sizes, ranked on the device ----
+ * The R^ above is blind to chains that share a mean but differ in scale, is undefined for heavy tails, and its ess describes the mean
+ * only.  Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021, Bayesian Analysis 16, 667-718) replace every draw by the normal score
+ * of its rank among all draws and apply the same statistics to the scores, to the scores of the draws folded about the median, and to
+ * the indicators of the 5 % and 95 % quantiles.  The formulas below are the definition.
+ *
+ * Selection and chains: as above (first_sample, walker_mask, split, chain j = half * nw + k, m chains of h samples; columns: every
+ * dimension and, when asked, the log-densities as the last).  Everything is per column over the POOLED DRAWS, the S = m h elements that
+ * belong to a chain; the middle sample that a split with an odd n leaves out is not among them.  S < 2^31.
+ *
+ * Rank.  By value, not by bits: x + 0.0 first, so that -0.0 ties with +0.0, then the key of the order statistics above; +-inf are
+ * ordinary values.  rank2(x) = #{y < x} + #{y <= x} + 1, an int64 in [2, 2 S]; the average 1-based rank is r = rank2 / 2, and ties
+ * share it.  A column whose selection holds a NaN gets NaN in every output below (and rank2 = 0) and the flag KMC_CONV_HAS_NAN; other
+ * columns are unaffected.
+ * Normal score.  p = (r - 0.375) / (S + 0.25): one correctly rounded division, everything before it exact.  z = Phi^-1(p) is Wichura's
+ * AS 241 routine PPND16 in exactly the operation order of CPython's statistics._normal_dist_inv_cdf: q = p - 0.5;
+ * |q| <= 0.425: r = 0.180625 - q q, two Horner sums in r, z = (num q) / den; else r = sqrt(-log(min(p, 1 - p))), r - 1.6 for r <= 5 and
+ * r - 5 beyond, two Horner sums, z = -+ num / den.  No fused multiply-add on host or device: the central branch (about 85 % of the
+ * draws) has the same bits everywhere, the tails differ only as far as the two logarithms do.
+ * Transforms of a column:  bulk z(x);  folded z(|x - med|);  I05 = (x <= q05) and I95 = (x <= q95) as 0.0 / 1.0, where med, q05, q95
+ * are the quantiles 0.5, 0.05 and 0.95 of the pooled draws by the rule of the order statistics with N = S: h = q (S - 1),
+ * lo = floor(h), hi = min(lo + 1, S - 1), frac = h - lo, x_lo + frac (x_hi - x_lo) (x_lo itself where frac == 0), from two order
+ * statistics each, read out of the sorted column.  inf - inf in the fold is a NaN of the folded column only: rhat_folded and rhat are
+ * NaN and KMC_CONV_HAS_NAN is set.
+ * Statistics: those of kmc_convergence_stats applied to the transformed columns.  rhat_bulk = rhat(z), rhat_folded = rhat(z folded),
+ * rhat = max of the two (NaN if either is); ess_bulk = ess(z); ess_q05 = ess(I05), ess_q95 = ess(I95), ess_tail = min of the two (NaN
+ * if either is).  The ess stays the variogram estimator above with its truncation rule; Stan's FFT / Geyer estimator is not followed.
+ *
+ * Algorithm.  The selection's keys are gathered column-contiguous, every column is sorted on its own by a
+ * least-significant-digit radix sort (8 passes of 8 bits; digit counts per tile, an exclusive scan, a stable scatter; integer atomics in
+ * LDS only, none in the scatter), and two binary searches per draw give rank2.  The sorted column is unique, so results do not depend on
+ * the launch geometry: two identical calls return the same bits.  The transformed columns are a scratch chain on the device, read by
+ * the kernels of the section above.  Work space: 16 B of keys per pooled draw and column, plus 8 B per transformed column (four of them
+ * for the whole thing); KMC_ERR_UNSUPPORTED, naming the sizes, when that does not fit the device's free memory -- never a partial answer. */
+#define KMC_CONV_HAS_NAN 4     /* flags bit 2: a NaN among the pooled draws of the column (or inf - inf in its fold) */
+/* The shape of the sort: keys per workgroup tile, bits per digit, passes, and the bytes of LDS the scatter uses.  Needs no device. */
+kmc_status  kmc_rank_plan(int32_t* tile_keys, int32_t* digit_bits, int32_t* passes, int32_t* lds_bytes);
+/* The host form of the score: z[i] of rank2[i] among S draws, i < n.  Needs no device.  KMC_ERR_BAD_ARG: S < 1 or a rank2 outside [2, 2 S]. */
+kmc_status  kmc_rank_normal_scores(const int64_t* rank2, int64_t n, int64_t S, double* z);
+/* The device stage: rank2 and z [ncols][m][h] of the columns (folded = 0) or of the columns folded about their medians (folded = 1; then
+ * centre [ncols] gets the medians, else it is left alone), and nan_count [ncols], the NaNs among the (folded) draws -- a column without a
+ * median has none but NaNs.  Every output may be NULL.  Refusals as for kmc_sampler_lag_sums, before the device is touched. */
+kmc_status  kmc_sampler_rank_scores(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int32_t split,
+                                    int32_t with_logp, int32_t folded, int64_t* rank2, double* z, double* centre, int64_t* nan_count,
+                                    int64_t* m_out, int64_t* h_out);
+kmc_status  kmc_chain_rank_scores(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                                  int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                                  int32_t split, int32_t folded, int device, int64_t* rank2, double* z, double* centre,
+                                  int64_t* nan_count, int64_t* m_out, int64_t* h_out);
+/* The whole thing.  Per column [ncols]: rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95; T [4][ncols],
+ * the truncation lags of the four transforms (bulk, folded, I05, I95); flags [ncols], the OR of the four runs' flags and
+ * KMC_CONV_HAS_NAN.  max_lag as for kmc_sampler_convergence.  info (may be NULL) gets 4 numbers for benchmarks: the lags computed, the
+ * bytes the two sorts moved, and the bytes the lag kernel and the moment kernels loaded. */
+kmc_status  kmc_sampler_rank_convergence(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
+                                         int64_t max_lag, double* rhat, double* rhat_bulk, double* rhat_folded, double* ess_bulk,
+                                         double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
+                                         int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
+kmc_status  kmc_chain_rank_convergence(const double* chain_host, const double* logp_host /* or NULL */, int64_t nsamples, int64_t nwalkers,
+                                       int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag,
+                                       int device, double* rhat, double* rhat_bulk, double* rhat_folded, double* ess_bulk,
+                                       double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
+                                       int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

@@ -13,6 +13,7 @@ from .api import emcee, emcee_counts, make_theta0s, squash_walkers
 from .densities import (CDensity, DataDensity, DeviceLogPdf, Exponential, ExprDensity, GaussianIso, HostLogPdf, LogNormal, MvNormal2,
                         Rosenbrock)
 from .chain_convergence import convergence, convergence_stats, error_of_estimated_mean, evaluate_convergence, lag_sums, samples_vs_tau
+from .chain_convergence import normal_scores, rank_convergence, rank_plan, rank_scores
 from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
@@ -26,6 +27,7 @@ __all__ = [
     "DEMove", "DESnookerMove", "geometric_betas", "thermodynamic_integration", "cdf_g_inv", "g_pdf", "metropolis", "metropolis_chains", "GaussianStep", "HostProposal", "int_acorr", "eff_samples",
     "quantiles", "quantile_ranks", "map_sample", "summarize_run", "histogram", "corner", "hist_mode", "credible_levels",
     "convergence", "convergence_stats", "lag_sums", "evaluate_convergence", "error_of_estimated_mean", "samples_vs_tau",
+    "rank_convergence", "rank_scores", "rank_plan", "normal_scores",
 ]
 
 

@@ -34,6 +34,7 @@ MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER, MOVE_MIX = 0, 1, 3, 4
 MIX_MAX = 4
 TEMPS_MAX = 64  # parallel tempering: most rungs of a ladder (kmc_config.ntemps)
 CONV_NEED_LAGS, CONV_TRUNCATED = 1, 2  # flags of kmc_convergence_stats
+CONV_HAS_NAN = 4  # flag of kmc_*_rank_convergence: a NaN among the pooled draws of the column
 TEMPER_WHOLE, TEMPER_LIKELIHOOD = 0, 1  # kmc_config.temper_mode
 P2P_HANDLE_BYTES = 128
 RCCL_ID_BYTES = 128
@@ -61,6 +62,8 @@ SYMBOLS = [
     "kmc_sampler_histograms", "kmc_chain_histograms", "kmc_hist_pair_plan",
     "kmc_sampler_lag_sums", "kmc_chain_lag_sums", "kmc_convergence_stats", "kmc_sampler_convergence", "kmc_chain_convergence",
     "kmc_convergence_plan",
+    "kmc_rank_plan", "kmc_rank_normal_scores", "kmc_sampler_rank_scores", "kmc_chain_rank_scores", "kmc_sampler_rank_convergence",
+    "kmc_chain_rank_convergence",
 ]
 
 
@@ -284,6 +287,12 @@ def lib() -> C.CDLL:
     L.kmc_sampler_convergence.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64, dp, dp, dp, dp, dp, dp, dp, ip, i32p, ip, ip, ip]
     L.kmc_chain_convergence.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int, dp, dp, dp, dp, dp, dp, dp, ip, i32p, ip, ip, ip]
     L.kmc_convergence_plan.argtypes = [i32p, i32p, i32p, i32p]
+    L.kmc_rank_plan.argtypes = [i32p, i32p, i32p, i32p]
+    L.kmc_rank_normal_scores.argtypes = [ip, C.c_int64, C.c_int64, dp]
+    L.kmc_sampler_rank_scores.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int32, ip, dp, dp, ip, ip, ip]
+    L.kmc_chain_rank_scores.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int, ip, dp, dp, ip, ip, ip]
+    L.kmc_sampler_rank_convergence.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64] + [dp] * 10 + [ip, i32p, ip, ip, ip]
+    L.kmc_chain_rank_convergence.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int] + [dp] * 10 + [ip, i32p, ip, ip, ip]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

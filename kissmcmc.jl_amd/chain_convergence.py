@@ -10,6 +10,10 @@ order of operations (``kmc_convergence_stats``).
 Input layout of the module-level functions: what ``emcee`` / ``metropolis_chains`` return, ``thetas[walker][sample]`` (scalar walkers)
 or ``thetas[walker][sample][dim]``, and ``logdensities[walker][sample]``.  Every selected walker is a chain; with ``split`` (the
 default) each is cut into two halves.
+
+The rank-normalised form (Vehtari et al. 2021; :func:`rank_convergence`, ``convergence(..., rank=True)``) ranks every pooled draw of a
+column on the device (``kmc_sampler_rank_scores`` / ``kmc_chain_rank_scores``: a segmented radix sort and two binary searches a draw),
+turns the ranks into normal scores and applies the same statistics to them.
 """
 from __future__ import annotations
 
@@ -128,6 +132,125 @@ def chain_convergence_raw(thetas, logdensities=None, first_sample=0, walkers=Non
     return out
 
 
+RANK_COLUMNS = ("rhat", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_q05", "ess_q95", "median", "q05", "q95")
+
+
+def rank_plan():
+    """The shape of the sort behind the ranks (``kmc_rank_plan``): dict ``tile_keys, digit_bits, passes, lds_bytes``."""
+    v = [C.c_int32() for _ in range(4)]
+    _lib.check(_lib.lib().kmc_rank_plan(*[C.byref(x) for x in v]))
+    return dict(zip(("tile_keys", "digit_bits", "passes", "lds_bytes"), [x.value for x in v]))
+
+
+def normal_scores(rank2, S: int):
+    """The host form of the score (``kmc_rank_normal_scores``; needs no device): ``z = Phi^-1((rank2 / 2 - 0.375) / (S + 0.25))`` for
+    ``rank2 = #{y < x} + #{y <= x} + 1`` in ``[2, 2 S]``, by Wichura's AS 241 in the operation order of
+    ``statistics.NormalDist().inv_cdf``.  Returns an array shaped like ``rank2``."""
+    r = np.ascontiguousarray(rank2, dtype=np.int64)
+    z = np.empty(r.shape)
+    _lib.check(_lib.lib().kmc_rank_normal_scores(_p(r, C.c_int64), r.size, int(S), _p(z, C.c_double)))
+    return z
+
+
+def _score_buffers(ncols, nw, n, split, folded):
+    h = max(0, n // 2 if split else n)
+    m = (2 if split else 1) * nw
+    return (np.zeros((ncols, m, h), dtype=np.int64), np.full((ncols, m, h), np.nan), np.full(ncols, np.nan) if folded else None,
+            np.zeros(ncols, dtype=np.int64))
+
+
+def _score_result(rank2, z, centre, nan_count, m, h):
+    return {"rank2": rank2, "z": z, "centre": centre, "nan_count": nan_count, "S": m.value * h.value, "m": m.value, "h": h.value}
+
+
+def sampler_rank_scores(s, first_sample=0, walkers=None, split=True, folded=False, logp=False):
+    """:func:`rank_scores` on the chain a :class:`Sampler` holds (``kmc_sampler_rank_scores``)."""
+    mask = walker_mask(walkers, s.nlocal)
+    rank2, z, centre, nan_count = _score_buffers(s.ndim + (1 if logp else 0), _count(mask, s.nlocal), s.samples_done - int(first_sample), split, folded)
+    m, h = C.c_int64(), C.c_int64()
+    _lib.check(s._L.kmc_sampler_rank_scores(s._h, int(first_sample), _p(mask, C.c_uint8), int(bool(split)), int(bool(logp)), int(bool(folded)),
+                                            _p(rank2, C.c_int64), _p(z, C.c_double), _p(centre, C.c_double), _p(nan_count, C.c_int64),
+                                            C.byref(m), C.byref(h)))
+    return _score_result(rank2, z, centre, nan_count, m, h)
+
+
+def rank_scores(thetas, logdensities=None, first_sample: int = 0, walkers=None, split: bool = True, folded: bool = False, device: int = 0):
+    """The exact ranks of the pooled draws and their normal scores, ranked on the device (``kmc_chain_rank_scores``): a dict
+    ``rank2[ncols, m, h]`` (int64: ``#{y < x} + #{y <= x} + 1`` among the ``S = m h`` draws of the column that belong to a chain, so
+    that ``rank2 / 2`` is the average 1-based rank -- also what a rank plot needs), ``z[ncols, m, h]`` (the normal score of
+    :func:`normal_scores`), ``centre`` (with ``folded``: the medians the draws were folded about, ``|x - median|`` being what is ranked;
+    else None), ``nan_count[ncols]``, ``S``, ``m``, ``h``.  Order is by value (``-0.0`` ties with ``+0.0``, infinities are ordinary
+    values); a column that holds a NaN gets ``rank2 = 0`` and ``z = NaN``.  Chains as in :func:`convergence`."""
+    p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
+    rank2, z, centre, nan_count = _score_buffers(p.ndim + (0 if p.logp is None else 1), _count(p.mask, p.nwalkers), p.nsamples - p.first, split, folded)
+    m, h = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().kmc_chain_rank_scores(_p(p.chain, C.c_double), _p(p.logp, C.c_double), p.nsamples, p.nwalkers, p.ndim, p.first,
+                                                _p(p.mask, C.c_uint8), int(bool(split)), int(bool(folded)), p.device, _p(rank2, C.c_int64),
+                                                _p(z, C.c_double), _p(centre, C.c_double), _p(nan_count, C.c_int64), C.byref(m), C.byref(h)))
+    return _score_result(rank2, z, centre, nan_count, m, h)
+
+
+def _rank_buffers(ncols):
+    out = {k: np.empty(ncols) for k in RANK_COLUMNS}
+    out["T"] = np.zeros((4, ncols), dtype=np.int64)
+    out["flags"] = np.zeros(ncols, dtype=np.int32)
+    out["info"] = np.zeros(4, dtype=np.int64)
+    return out, [_p(out[k], C.c_double) for k in RANK_COLUMNS] + [_p(out["T"], C.c_int64), _p(out["flags"], C.c_int32)]
+
+
+def sampler_rank_convergence_raw(s, first_sample=0, walkers=None, split=True, logp=False, max_lag=None):
+    """Everything ``kmc_sampler_rank_convergence`` returns: the columns of :data:`RANK_COLUMNS`, ``T[4, ncols]``, ``flags``, ``m``,
+    ``h`` and ``info`` (lags computed, bytes the two sorts moved, bytes the lag kernel and the moment kernels loaded)."""
+    mask = walker_mask(walkers, s.nlocal)
+    out, args = _rank_buffers(s.ndim + (1 if logp else 0))
+    m, h = C.c_int64(), C.c_int64()
+    _lib.check(s._L.kmc_sampler_rank_convergence(s._h, int(first_sample), _p(mask, C.c_uint8), int(bool(split)), int(bool(logp)), _max_lag_arg(max_lag),
+                                                 *args, C.byref(m), C.byref(h), _p(out["info"], C.c_int64)))
+    out["m"], out["h"] = m.value, h.value
+    return out
+
+
+def chain_rank_convergence_raw(thetas, logdensities=None, first_sample=0, walkers=None, split=True, max_lag=None, device=0):
+    """The same for a chain in host memory (``kmc_chain_rank_convergence``)."""
+    p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
+    out, args = _rank_buffers(p.ndim + (0 if p.logp is None else 1))
+    m, h = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().kmc_chain_rank_convergence(_p(p.chain, C.c_double), _p(p.logp, C.c_double), p.nsamples, p.nwalkers, p.ndim, p.first,
+                                                     _p(p.mask, C.c_uint8), int(bool(split)), _max_lag_arg(max_lag), p.device, *args, C.byref(m),
+                                                     C.byref(h), _p(out["info"], C.c_int64)))
+    out["m"], out["h"] = m.value, h.value
+    return out
+
+
+def rank_columns(raw):
+    """The public dict of the rank-normalised diagnostics from what the library returned: the columns of :data:`RANK_COLUMNS`,
+    ``lag[4, ncols]`` (the ``T`` of the truncation rule for the bulk scores, the folded scores, ``I05`` and ``I95``), ``truncated``,
+    ``has_nan``, ``m``, ``h``."""
+    out = {k: raw[k] for k in RANK_COLUMNS}
+    out.update(lag=raw["T"], truncated=(raw["flags"] & _lib.CONV_TRUNCATED) != 0, has_nan=(raw["flags"] & _lib.CONV_HAS_NAN) != 0,
+               m=raw["m"], h=raw["h"])
+    return out
+
+
+def rank_convergence(thetas, logdensities=None, first_sample: int = 0, walkers=None, split: bool = True, max_lag=None, device: int = 0):
+    """Rank-normalised R-hat with bulk and tail effective sample sizes (Vehtari, Gelman, Simpson, Carpenter and Buerkner 2021), the
+    ranks taken on the device: a dict of per-column arrays ``rhat = max(rhat_bulk, rhat_folded)``, ``rhat_bulk`` (the R-hat of
+    :func:`convergence` on the normal scores ``z`` of the ranks of the draws), ``rhat_folded`` (the same on the scores of
+    ``|x - median|``: it sees chains that share a mean but differ in scale), ``ess_bulk`` (the ess of ``z``), ``ess_tail =
+    min(ess_q05, ess_q95)`` (the ess of the indicators ``x <= q05`` and ``x <= q95``: what the ends of a 90 % interval are worth),
+    ``median, q05, q95`` (exact, by the rule of :func:`quantile_ranks`), ``lag[4, ncols]``, ``truncated``, ``has_nan`` and ``m``,
+    ``h``.  A column that holds a NaN gets NaN throughout and ``has_nan``.  The ess is the variogram estimator of
+    :func:`convergence` with its truncation rule, not Stan's.  Chains and arguments as in :func:`convergence`."""
+    return rank_columns(chain_rank_convergence_raw(thetas, logdensities, first_sample, walkers, split, max_lag, device))
+
+
+def add_rank_columns(cols, rank):
+    """``cols`` of :func:`columns` with ``rhat_rank, ess_bulk, ess_tail`` of :func:`rank_columns` appended."""
+    cols = dict(cols)
+    cols.update(rhat_rank=rank["rhat"], ess_bulk=rank["ess_bulk"], ess_tail=rank["ess_tail"])
+    return cols
+
+
 def columns(raw):
     """The public dict of columns from what the library returned: ``mean, std = sqrt(var_plus), rhat, ess, mcse, lag`` (the ``T`` of
     the truncation rule), ``truncated`` (the rule had not fired at ``max_lag``), ``m``, ``h``."""
@@ -137,7 +260,8 @@ def columns(raw):
             "truncated": (raw["flags"] & _lib.CONV_TRUNCATED) != 0, "m": raw["m"], "h": raw["h"]}
 
 
-def convergence(thetas, logdensities=None, first_sample: int = 0, walkers=None, split: bool = True, max_lag=None, device: int = 0):
+def convergence(thetas, logdensities=None, first_sample: int = 0, walkers=None, split: bool = True, max_lag=None, device: int = 0,
+                rank: bool = False):
     """Split-R-hat, effective sample size and Monte-Carlo standard error per dimension of ``thetas[walker][sample](dim)`` (and, as a
     last column, of ``logdensities`` when given), over the samples ``>= first_sample`` of the walkers ``walkers``: a dict of columns
     ``mean, std, rhat, ess, mcse, lag, truncated`` and the numbers ``m`` (chains) and ``h`` (samples per chain).
@@ -149,8 +273,13 @@ def convergence(thetas, logdensities=None, first_sample: int = 0, walkers=None, 
 
     The walkers of ONE emcee ensemble are not independent (https://dfm.io/posts/autocorr/: "you should not compute the G-R statistic
     using multiple chains in the same emcee ensemble"), so R-hat over them is optimistic: for R-hat use separate runs
-    (:func:`evaluate_convergence`) or the independent chains of ``metropolis_chains``."""
-    return columns(chain_convergence_raw(thetas, logdensities, first_sample, walkers, split, max_lag, device))
+    (:func:`evaluate_convergence`) or the independent chains of ``metropolis_chains``.
+
+    ``rank=True`` adds the columns ``rhat_rank``, ``ess_bulk`` and ``ess_tail`` of :func:`rank_convergence`."""
+    cols = columns(chain_convergence_raw(thetas, logdensities, first_sample, walkers, split, max_lag, device))
+    if rank:
+        cols = add_rank_columns(cols, rank_convergence(thetas, logdensities, first_sample, walkers, split, max_lag, device))
+    return cols
 
 
 def _as3(thetas):
@@ -162,7 +291,7 @@ def _as3(thetas):
     return th
 
 
-def evaluate_convergence(*runs, indices=None, walkernr=None, split: bool = True, device: int = 0):
+def evaluate_convergence(*runs, indices=None, walkernr=None, split: bool = True, device: int = 0, rank: bool = False):
     """Reference ``src/analysis.jl:79-95`` (commented out there): ``(Rs, sample_size, nthin)`` -- R-hat (should be < 1.1) and the
     total effective sample size of all chains combined, per dimension of ``indices`` (all by default), and the average thinning
     factor ``round(n * nwalkers / mean(sample_size))`` (-1 when that is NaN).
@@ -170,7 +299,8 @@ def evaluate_convergence(*runs, indices=None, walkernr=None, split: bool = True,
     ``runs`` are the ``thetas`` of separate runs of one posterior; their walkers are concatenated, and with ``walkernr`` only walker
     ``walkernr`` of each run is used (the reference's choice).  The reference's warning stands: the walkers of one emcee ensemble are
     not independent, so R-hat over the walkers of a single run is optimistic -- "this needs input from two separate emcee runs", or
-    Metropolis chains.  See :func:`convergence` for the definition (the reference's MCMCDiagnostics.jl is not followed)."""
+    Metropolis chains.  See :func:`convergence` for the definition (the reference's MCMCDiagnostics.jl is not followed).  With
+    ``rank=True`` ``Rs`` is the rank-normalised R-hat and ``sample_size`` the bulk ess of :func:`rank_convergence`."""
     if not runs:
         raise ValueError("at least one run")
     ths = [_as3(t) for t in runs]
@@ -179,9 +309,13 @@ def evaluate_convergence(*runs, indices=None, walkernr=None, split: bool = True,
     if any(t.shape[1:] != ths[0].shape[1:] for t in ths):
         raise ValueError("the runs must have the same number of samples and dimensions")
     th = np.concatenate(ths, axis=0)
-    out = convergence(th, split=split, device=device)
     idx = np.arange(th.shape[2]) if indices is None else np.atleast_1d(np.asarray(indices, dtype=np.int64))
-    Rs, sample_size = out["rhat"][idx], out["ess"][idx]
+    if rank:
+        out = rank_convergence(th, split=split, device=device)
+        Rs, sample_size = out["rhat"][idx], out["ess_bulk"][idx]
+    else:
+        out = convergence(th, split=split, device=device)
+        Rs, sample_size = out["rhat"][idx], out["ess"][idx]
     nthin = th.shape[1] * th.shape[0] / np.mean(sample_size)
     return Rs, sample_size, -1 if np.isnan(nthin) else int(round(float(nthin)))
 

@@ -9,22 +9,17 @@
 #include <vector>
 
 #include "kmc_chain_view.hpp"
+#include "kmc_convergence_host.hpp"
 #include "kmc_convergence_kernels.hpp"
 
 using namespace kmc_host;
 using namespace kmc_chain_view;
 using namespace kmc_conv;
 
-namespace {
+namespace kmc_conv_host {                  // (kmc_convergence_host.hpp: kmc_rank.hip runs the same stages on its transformed columns)
 
 constexpr int64_t kConvDefaultMaxLag = 1024;
 constexpr int64_t kConvTargetWorkgroups = 2048;            // of conv_lag_partials and conv_moment_partials: 8 per compute unit
-
-// the chains of a request (include/kissmcmc_hip.h): from the sizes alone
-struct ConvShape {
-    int64_t first = 0, n = 0, nw = 0, h = 0, m = 0, half_off = 0;
-    int nhalf = 1;
-};
 
 kmc_status conv_shape(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, bool split, ConvShape* sh)
 {
@@ -57,23 +52,6 @@ kmc_status resolve_max_lag(const ConvShape& sh, int64_t* max_lag)
         return fail(KMC_ERR_BAD_ARG, "max_lag must lie in [3, h - 1] (h = " + std::to_string(sh.h) + "), or be 0 for min(h - 1, 1024)");
     return KMC_OK;
 }
-
-struct ConvBuffers : ChainUpload {
-    int32_t* rank = nullptr;
-    double *mean_p = nullptr, *part = nullptr, *out = nullptr;
-    size_t part_bytes = 0, out_bytes = 0;
-    ~ConvBuffers() { (void)hipFree(rank); (void)hipFree(mean_p); (void)hipFree(part); (void)hipFree(out); }
-    kmc_status room(double** p, size_t* have, size_t need)
-    {
-        if (need <= *have) return KMC_OK;
-        (void)hipFree(*p);
-        *p = nullptr; *have = 0;
-        KMC_TRY(check_device_room(need, "the convergence work space"));
-        HIP_TRY(hipMalloc((void**)p, need));
-        *have = need;
-        return KMC_OK;
-    }
-};
 
 // one source of columns: the chain, or the log-densities as a chain of ld = ndim = 1
 struct ConvSource {
@@ -218,12 +196,6 @@ kmc_status lags_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, 
 
 // ---- the host stage ----
 // Per column, every sum sequential in index order; no device.
-struct StatsOut {
-    double *mean, *W, *B, *var_plus, *rhat, *ess, *mcse;
-    int64_t* T;
-    int32_t* flags;
-};
-
 kmc_status stats_check(int64_t m, int64_t h, int64_t ncols, const double* chain_mean, const double* chain_var, const double* lagsum, int64_t nlags,
                        int64_t max_lag, const StatsOut& o)
 {
@@ -340,7 +312,9 @@ kmc_status host_shape(const double* chain_host, int64_t nsamples, int64_t nwalke
     return conv_shape(shape, first_sample, walker_mask, split, sh);
 }
 
-}  // namespace
+}  // namespace kmc_conv_host
+
+using namespace kmc_conv_host;
 
 KMC_EXPORT kmc_status kmc_convergence_stats(int64_t m, int64_t h, int64_t ncols, const double* chain_mean, const double* chain_var, const double* lagsum,
                                             int64_t nlags, int64_t max_lag, double* mean, double* W, double* B, double* var_plus, double* rhat,

@@ -1,0 +1,399 @@
+// kmc_rank.hip -- rank-normalised R^ with bulk and tail effective sample sizes (Vehtari, Gelman, Simpson, Carpenter and Buerkner 2021)
+// of a stored chain, ranked on the device: every pooled draw of a column gets its exact average rank among all draws of the column by
+// a segmented radix sort of the column's keys and two binary searches, the rank becomes a normal score, and the statistics are those of
+// kmc_convergence.hip applied to the transformed columns (include/kissmcmc_hip.h).
+// Kernels: kmc_rank_kernels.hpp.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <vector>
+
+#include "kmc_chain_view.hpp"
+#include "kmc_convergence_host.hpp"
+#include "kmc_rank_kernels.hpp"
+
+using namespace kmc_host;
+using namespace kmc_chain_view;
+using namespace kmc_conv_host;
+using namespace kmc_rank;
+
+namespace {
+
+constexpr int kTransforms = 4;                               // bulk z, folded z, I05, I95: the column sets of the scratch chain
+
+struct RankBuffers {
+    uint64_t *key_a = nullptr, *key_b = nullptr, *picked = nullptr;
+    uint32_t* counts = nullptr;
+    unsigned long long* nan = nullptr;
+    double *centre = nullptr, *out_z = nullptr;
+    int64_t* out_rank2 = nullptr;
+    ~RankBuffers()
+    {
+        (void)hipFree(key_a); (void)hipFree(key_b); (void)hipFree(picked); (void)hipFree(counts); (void)hipFree(nan); (void)hipFree(centre);
+        (void)hipFree(out_z); (void)hipFree(out_rank2);
+    }
+};
+
+struct RankSource {
+    const void* src;
+    bool is_float;
+    int64_t ld;
+    int32_t ndim, col0;
+};
+
+std::vector<RankSource> rank_sources(const ChainView& v, bool with_logp)
+{
+    std::vector<RankSource> s;
+    s.push_back({v.chain, v.is_float, v.ld, (int32_t)v.ndim, 0});
+    if (with_logp) s.push_back({v.logp, false, 1, 1, (int32_t)v.ndim});
+    return s;
+}
+
+int64_t tiles_of(int64_t S) { return (S + kRankTileKeys - 1) / kRankTileKeys; }
+
+// the sizes one call may have, from the shape alone
+kmc_status rank_limits(const ConvShape& sh, int64_t ncols)
+{
+    const int64_t S = sh.m * sh.h;
+    if (S >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "2^31 pooled draws or more per column (" + std::to_string(S) + ")");
+    if (ncols > 65535) return fail(KMC_ERR_UNSUPPORTED, "more than 65535 columns");
+    return KMC_OK;
+}
+
+// The work space: two key buffers (16 B), the digit counts, and 8 B per transformed column (or 16 B for rank2 and z), per pooled draw.
+kmc_status rank_room(const ConvShape& sh, int64_t ncols, int transformed, bool outputs)
+{
+    const int64_t S = sh.m * sh.h;
+    const double keys = 16.0 * (double)ncols * (double)S, counts = 4.0 * kRankBins * (double)tiles_of(S) * (double)ncols;
+    const double scratch = 8.0 * (double)transformed * (double)ncols * (double)sh.n * (double)sh.nw, outs = outputs ? 16.0 * (double)ncols * (double)S : 0.0;
+    const double need = keys + counts + scratch + outs + 64.0 * 1048576.0;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (need > (double)free_b)
+        return fail(KMC_ERR_UNSUPPORTED, "ranking " + std::to_string(ncols) + " columns of " + std::to_string(S) + " pooled draws needs " +
+                                             std::to_string((int64_t)(need / 1048576.0)) + " MiB of device memory (keys " + std::to_string((int64_t)(keys / 1048576.0)) +
+                                             " MiB, transformed columns " + std::to_string((int64_t)((scratch + outs) / 1048576.0)) + " MiB), " +
+                                             std::to_string(free_b >> 20) + " MiB are free; ranking in column groups is not built");
+    return KMC_OK;
+}
+
+kmc_status rank_alloc(RankBuffers& rb, int64_t ncols, int64_t S, bool outputs)
+{
+    const size_t kb = (size_t)ncols * (size_t)S * sizeof(uint64_t);
+    HIP_TRY(hipMalloc((void**)&rb.key_a, kb));
+    HIP_TRY(hipMalloc((void**)&rb.key_b, kb));
+    HIP_TRY(hipMalloc((void**)&rb.counts, (size_t)ncols * (size_t)tiles_of(S) * kRankBins * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&rb.nan, (size_t)ncols * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc((void**)&rb.picked, (size_t)ncols * kRankPicks * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc((void**)&rb.centre, (size_t)ncols * 3 * sizeof(double)));
+    if (outputs) {
+        HIP_TRY(hipMalloc((void**)&rb.out_rank2, kb));
+        HIP_TRY(hipMalloc((void**)&rb.out_z, kb));
+    }
+    return KMC_OK;
+}
+
+// keys of the (folded) selection into key_a; nan[c]: the NaNs among them
+kmc_status gather(RankBuffers& rb, const ConvBuffers& b, const ChainView& v, const ConvShape& sh, bool with_logp, bool folded, hipStream_t st,
+                  std::vector<int64_t>* nan)
+{
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0), S = sh.m * sh.h;
+    HIP_TRY(hipMemsetAsync(rb.nan, 0, (size_t)ncols * sizeof(unsigned long long), st));
+    for (const RankSource& src : rank_sources(v, with_logp)) {
+        GatherArgs a{};
+        a.src = src.src; a.rank = b.rank; a.centre = folded ? rb.centre : nullptr; a.keys = rb.key_a; a.nan_count = rb.nan;
+        a.first = sh.first; a.half_off = sh.half_off; a.h = sh.h; a.nl = v.nl; a.ld = src.ld; a.np = v.nl * src.ld; a.nw = sh.nw; a.S = S;
+        a.ntile_p = (a.np + kRankGatherTile - 1) / kRankGatherTile;
+        a.ntile_i = (sh.h + kRankGatherTile - 1) / kRankGatherTile;
+        a.ndim = src.ndim; a.is_float = src.is_float ? 1 : 0; a.col0 = src.col0;
+        const int64_t grid = a.ntile_p * a.ntile_i * sh.nhalf;
+        if (grid >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one ranking call");
+        hipLaunchKernelGGL(rank_gather, dim3((unsigned)grid), dim3(kRankThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<unsigned long long> n((size_t)ncols);
+    HIP_TRY(copy_sync(n.data(), rb.nan, n.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    nan->assign(n.begin(), n.end());
+    return KMC_OK;
+}
+
+// key_a sorted, every column on its own: 8 passes between key_a and key_b, an even number, so the result is in key_a again
+kmc_status sort_columns(RankBuffers& rb, int64_t ncols, int64_t S, hipStream_t st)
+{
+    SortArgs a{};
+    a.S = S; a.ntiles = tiles_of(S); a.counts = rb.counts;
+    uint64_t *in = rb.key_a, *out = rb.key_b;
+    for (int pass = 0; pass < kRankPasses; ++pass) {
+        a.in = in; a.out = out; a.shift = pass * kRankDigitBits;
+        const dim3 grid((unsigned)a.ntiles, (unsigned)ncols);
+        hipLaunchKernelGGL(rank_sort_hist, grid, dim3(kRankThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rank_sort_scan, dim3((unsigned)ncols), dim3(kRankThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rank_sort_scatter, grid, dim3(kRankThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        std::swap(in, out);
+    }
+    return KMC_OK;
+}
+
+double unkey(uint64_t key)
+{
+    const uint64_t bits = rank_bits_of_key(key);
+    double x;
+    std::memcpy(&x, &bits, sizeof x);
+    return x;
+}
+
+// The quantiles 0.5, 0.05, 0.95 of the sorted columns in key_a by the rule of the order statistics (kmc.quantile_ranks with N = S):
+// h = q (S - 1), lo = floor(h), hi = min(lo + 1, S - 1), frac = h - lo, x_lo + frac (x_hi - x_lo), and x_lo itself where frac == 0.
+// centre[3][ncols] on the host and in rb.centre; NaN for a column that holds one.
+kmc_status quantiles(RankBuffers& rb, int64_t ncols, int64_t S, const std::vector<int64_t>& nan, hipStream_t st, std::vector<double>* centre)
+{
+    static const double q[3] = {0.5, 0.05, 0.95};
+    PickArgs a{};
+    a.sorted = rb.key_a; a.out = rb.picked; a.S = S; a.ncols = ncols;
+    double frac[3];
+    for (int k = 0; k < 3; ++k) {
+        const double hq = q[k] * (double)(S - 1), lo = std::floor(hq);
+        a.at[2 * k] = (int64_t)lo;
+        a.at[2 * k + 1] = std::min<int64_t>((int64_t)lo + 1, S - 1);
+        frac[k] = hq - lo;
+    }
+    hipLaunchKernelGGL(rank_pick, dim3((unsigned)((ncols * kRankPicks + kRankThreads - 1) / kRankThreads)), dim3(kRankThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint64_t> got((size_t)ncols * kRankPicks);
+    HIP_TRY(copy_sync(got.data(), rb.picked, got.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    centre->assign((size_t)(3 * ncols), std::numeric_limits<double>::quiet_NaN());
+    for (int64_t c = 0; c < ncols; ++c) {
+        if (nan[(size_t)c]) continue;
+        for (int k = 0; k < 3; ++k) {
+            const double x_lo = unkey(got[(size_t)(c * kRankPicks + 2 * k)]), x_hi = unkey(got[(size_t)(c * kRankPicks + 2 * k + 1)]);
+            (*centre)[(size_t)(k * ncols + c)] = frac[k] == 0.0 ? x_lo : x_lo + frac[k] * (x_hi - x_lo);
+        }
+    }
+    HIP_TRY(copy_sync(rb.centre, centre->data(), centre->size() * sizeof(double), hipMemcpyHostToDevice, st));
+    return KMC_OK;
+}
+
+kmc_status score(RankBuffers& rb, const ConvBuffers& b, const ChainView& v, const ConvShape& sh, bool with_logp, bool folded, bool indicators,
+                 double* scratch, int64_t scratch_cols, hipStream_t st)
+{
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
+    for (const RankSource& src : rank_sources(v, with_logp)) {
+        ScoreArgs a{};
+        a.src = src.src; a.rank = b.rank; a.sorted = rb.key_a; a.centre = rb.centre; a.scratch = scratch; a.out_rank2 = rb.out_rank2; a.out_z = rb.out_z;
+        a.first = sh.first; a.half_off = sh.half_off; a.h = sh.h; a.nl = v.nl; a.ld = src.ld; a.np = v.nl * src.ld; a.nw = sh.nw; a.S = sh.m * sh.h;
+        a.lds_cols = scratch_cols; a.nelem = (int64_t)sh.nhalf * sh.h * a.np;
+        a.ndim = src.ndim; a.is_float = src.is_float ? 1 : 0; a.col0 = src.col0; a.ncols = (int32_t)ncols; a.folded = folded ? 1 : 0;
+        a.indicators = indicators ? 1 : 0; a.zcol0 = folded ? (int32_t)ncols : 0;
+        const int64_t grid = (a.nelem + kRankThreads - 1) / kRankThreads;
+        if (grid >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one ranking call");
+        hipLaunchKernelGGL(rank_score, dim3((unsigned)grid), dim3(kRankThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return KMC_OK;
+}
+
+// ---- the device stage alone: rank2 and z of the (folded) columns ----
+kmc_status rank_scores_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, bool folded,
+                              int64_t* rank2, double* z, double* centre_out, int64_t* nan_count)
+{
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0), S = sh.m * sh.h;
+    KMC_TRY(rank_room(sh, ncols, 0, true));
+    ScopedStream ss;
+    HIP_TRY(ss.create());
+    KMC_TRY(upload_rank(b, mask_host, v.nl, ss.st));
+    RankBuffers rb;
+    KMC_TRY(rank_alloc(rb, ncols, S, true));
+    std::vector<int64_t> nan;
+    std::vector<double> centre;
+    KMC_TRY(gather(rb, b, v, sh, with_logp, false, ss.st, &nan));
+    KMC_TRY(sort_columns(rb, ncols, S, ss.st));
+    if (folded) {
+        KMC_TRY(quantiles(rb, ncols, S, nan, ss.st, &centre));
+        KMC_TRY(gather(rb, b, v, sh, with_logp, true, ss.st, &nan));
+        KMC_TRY(sort_columns(rb, ncols, S, ss.st));
+        if (centre_out) std::copy(centre.begin(), centre.begin() + ncols, centre_out);
+    }
+    KMC_TRY(score(rb, b, v, sh, with_logp, folded, false, nullptr, 0, ss.st));
+    const size_t bytes = (size_t)ncols * (size_t)S * 8;
+    if (rank2) HIP_TRY(copy_sync(rank2, rb.out_rank2, bytes, hipMemcpyDeviceToHost, ss.st));
+    if (z) HIP_TRY(copy_sync(z, rb.out_z, bytes, hipMemcpyDeviceToHost, ss.st));
+    HIP_TRY(hipStreamSynchronize(ss.st));
+    for (int64_t c = 0; c < ncols; ++c) {                     // a column that holds a NaN has no ranks
+        if (nan_count) nan_count[c] = nan[(size_t)c];
+        if (!nan[(size_t)c]) continue;
+        if (rank2) std::fill(rank2 + c * S, rank2 + (c + 1) * S, (int64_t)0);
+        if (z) std::fill(z + c * S, z + (c + 1) * S, std::numeric_limits<double>::quiet_NaN());
+    }
+    return KMC_OK;
+}
+
+// ---- the whole thing ----
+struct RankOut {
+    double *rhat, *rhat_bulk, *rhat_folded, *ess_bulk, *ess_tail, *ess_q05, *ess_q95, *median, *q05, *q95;
+    int64_t* T;                        // [4][ncols]
+    int32_t* flags;
+    bool complete() const { return rhat && rhat_bulk && rhat_folded && ess_bulk && ess_tail && ess_q05 && ess_q95 && median && q05 && q95 && T && flags; }
+};
+
+kmc_status rank_convergence_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, int64_t max_lag,
+                                   const RankOut& o, int64_t* info)
+{
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0), S = sh.m * sh.h, tcols = kTransforms * ncols;
+    const double nan_v = std::numeric_limits<double>::quiet_NaN();
+    KMC_TRY(rank_room(sh, ncols, kTransforms, false));
+    std::vector<int64_t> nan_bulk, nan_fold;
+    std::vector<double> centre;
+    ConvBuffers sb;                                           // owns the scratch chain (as its uploaded chain) and the work space of the statistics
+    {
+        ScopedStream ss;
+        HIP_TRY(ss.create());
+        KMC_TRY(upload_rank(b, mask_host, v.nl, ss.st));
+        RankBuffers rb;
+        KMC_TRY(rank_alloc(rb, ncols, S, false));
+        const size_t srow = (size_t)sh.nw * (size_t)tcols;
+        HIP_TRY(hipMalloc((void**)&sb.chain, (size_t)sh.n * srow * sizeof(double)));
+        if (sh.nhalf == 2 && sh.n != 2 * sh.h)               // the middle sample of an odd n belongs to no chain: a row of zeros nobody reads
+            HIP_TRY(hipMemsetAsync(sb.chain + (size_t)sh.h * srow, 0, srow * sizeof(double), ss.st));
+        KMC_TRY(gather(rb, b, v, sh, with_logp, false, ss.st, &nan_bulk));
+        KMC_TRY(sort_columns(rb, ncols, S, ss.st));
+        KMC_TRY(quantiles(rb, ncols, S, nan_bulk, ss.st, &centre));
+        KMC_TRY(score(rb, b, v, sh, with_logp, false, true, sb.chain, tcols, ss.st));
+        KMC_TRY(gather(rb, b, v, sh, with_logp, true, ss.st, &nan_fold));
+        KMC_TRY(sort_columns(rb, ncols, S, ss.st));
+        KMC_TRY(score(rb, b, v, sh, with_logp, true, false, sb.chain, tcols, ss.st));
+        HIP_TRY(hipStreamSynchronize(ss.st));
+    }                                                         // (the keys are freed before the statistics take their work space)
+    ChainView sv;
+    sv.chain = sb.chain; sv.is_float = false; sv.ld = tcols; sv.ndim = tcols; sv.logp = nullptr; sv.nsamples = sh.n; sv.nl = sh.nw;
+    ConvShape ssh = sh;
+    ssh.first = 0;
+    std::vector<double> mean((size_t)tcols), W((size_t)tcols), B((size_t)tcols), vp((size_t)tcols), rhat((size_t)tcols), ess((size_t)tcols), mcse((size_t)tcols);
+    std::vector<int64_t> T((size_t)tcols);
+    std::vector<int32_t> flags((size_t)tcols);
+    const StatsOut so{mean.data(), W.data(), B.data(), vp.data(), rhat.data(), ess.data(), mcse.data(), T.data(), flags.data()};
+    int64_t cinfo[4] = {0, 0, 0, 0};
+    KMC_TRY(convergence_device(sb, sv, ssh, nullptr, false, max_lag, so, cinfo));
+    for (int64_t c = 0; c < ncols; ++c) {
+        const size_t bk = (size_t)c, fd = (size_t)(ncols + c), i5 = (size_t)(2 * ncols + c), i95 = (size_t)(3 * ncols + c);
+        int32_t f = flags[bk] | flags[fd] | flags[i5] | flags[i95];
+        for (int t = 0; t < kTransforms; ++t) o.T[t * ncols + c] = T[(size_t)(t * ncols + c)];
+        o.rhat_bulk[c] = rhat[bk]; o.rhat_folded[c] = rhat[fd];
+        o.ess_bulk[c] = ess[bk]; o.ess_q05[c] = ess[i5]; o.ess_q95[c] = ess[i95];
+        o.median[c] = centre[(size_t)c]; o.q05[c] = centre[(size_t)(ncols + c)]; o.q95[c] = centre[(size_t)(2 * ncols + c)];
+        if (nan_bulk[(size_t)c]) {                            // a NaN among the draws: no ranks, nothing to report
+            o.rhat_bulk[c] = o.rhat_folded[c] = o.ess_bulk[c] = o.ess_q05[c] = o.ess_q95[c] = nan_v;
+            for (int t = 0; t < kTransforms; ++t) o.T[t * ncols + c] = 0;
+            f = KMC_CONV_HAS_NAN;
+        } else if (nan_fold[(size_t)c]) {                     // inf - inf in the fold: a NaN of the folded column only
+            o.rhat_folded[c] = nan_v;
+            o.T[ncols + c] = 0;
+            f = flags[bk] | flags[i5] | flags[i95] | KMC_CONV_HAS_NAN;
+        }
+        const double rb_ = o.rhat_bulk[c], rf = o.rhat_folded[c], e5 = o.ess_q05[c], e95 = o.ess_q95[c];
+        o.rhat[c] = (rb_ != rb_ || rf != rf) ? nan_v : std::max(rb_, rf);
+        o.ess_tail[c] = (e5 != e5 || e95 != e95) ? nan_v : std::min(e5, e95);
+        o.flags[c] = f;
+    }
+    if (info) {
+        info[0] = cinfo[0];
+        info[1] = 2 * (int64_t)kRankPasses * 24 * ncols * S;                                          // two sorts: a pass reads the keys twice and writes them once
+        info[2] = cinfo[2]; info[3] = cinfo[3];
+    }
+    return KMC_OK;
+}
+
+}  // namespace
+
+// The shape of the sort; for tests and benchmarks.  Touches no device.
+KMC_EXPORT kmc_status kmc_rank_plan(int32_t* tile_keys, int32_t* digit_bits, int32_t* passes, int32_t* lds_bytes)
+{
+    if (tile_keys) *tile_keys = kRankTileKeys;
+    if (digit_bits) *digit_bits = kRankDigitBits;
+    if (passes) *passes = kRankPasses;
+    if (lds_bytes) *lds_bytes = kRankLdsBytes;
+    return KMC_OK;
+}
+
+// The host form of the score.  Touches no device.
+KMC_EXPORT kmc_status kmc_rank_normal_scores(const int64_t* rank2, int64_t n, int64_t S, double* z)
+{
+    if (n < 0 || (n > 0 && (!rank2 || !z))) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (S < 1 || S >= ((int64_t)1 << 52)) return fail(KMC_ERR_BAD_ARG, "need 1 <= S < 2^52");
+    for (int64_t i = 0; i < n; ++i)
+        if (rank2[i] < 2 || rank2[i] > 2 * S) return fail(KMC_ERR_BAD_ARG, "rank2 must lie in [2, 2 S] (element " + std::to_string(i) + ")");
+    for (int64_t i = 0; i < n; ++i) z[i] = rank_score_of(rank2[i], S);
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_rank_scores(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
+                                              int32_t folded, int64_t* rank2, double* z, double* centre, int64_t* nan_count, int64_t* m_out,
+                                              int64_t* h_out)
+{
+    ChainView v;
+    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_rank_scores", &v));
+    ConvShape sh;
+    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(rank_limits(sh, v.ndim + (with_logp ? 1 : 0)));
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    return rank_scores_device(b, v, sh, walker_mask, with_logp != 0, folded != 0, rank2, z, centre, nan_count);
+}
+
+KMC_EXPORT kmc_status kmc_chain_rank_scores(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
+                                            int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t folded, int device,
+                                            int64_t* rank2, double* z, double* centre, int64_t* nan_count, int64_t* m_out, int64_t* h_out)
+{
+    ConvShape sh;
+    KMC_TRY(host_shape(chain_host, nsamples, nwalkers, ndim, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(rank_limits(sh, ndim + (logp_host ? 1 : 0)));
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    ChainView v;
+    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
+    return rank_scores_device(b, v, sh, walker_mask, logp_host != nullptr, folded != 0, rank2, z, centre, nan_count);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_rank_convergence(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
+                                                   int64_t max_lag, double* rhat, double* rhat_bulk, double* rhat_folded, double* ess_bulk,
+                                                   double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
+                                                   int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info)
+{
+    ChainView v;
+    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_rank_convergence", &v));
+    ConvShape sh;
+    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(resolve_max_lag(sh, &max_lag));
+    KMC_TRY(rank_limits(sh, v.ndim + (with_logp ? 1 : 0)));
+    const RankOut o{rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95, T, flags};
+    if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    return rank_convergence_device(b, v, sh, walker_mask, with_logp != 0, max_lag, o, info);
+}
+
+KMC_EXPORT kmc_status kmc_chain_rank_convergence(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
+                                                 int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag, int device,
+                                                 double* rhat, double* rhat_bulk, double* rhat_folded, double* ess_bulk, double* ess_tail,
+                                                 double* ess_q05, double* ess_q95, double* median, double* q05, double* q95, int64_t* T,
+                                                 int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info)
+{
+    ConvShape sh;
+    KMC_TRY(host_shape(chain_host, nsamples, nwalkers, ndim, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(resolve_max_lag(sh, &max_lag));
+    KMC_TRY(rank_limits(sh, ndim + (logp_host ? 1 : 0)));
+    const RankOut o{rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95, T, flags};
+    if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    ChainView v;
+    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
+    return rank_convergence_device(b, v, sh, walker_mask, logp_host != nullptr, max_lag, o, info);
+}

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -688,15 +688,16 @@ function corner(thetas; bins=32, range=nothing, dims=nothing, first_sample=0, wa
 end
 
 """
-    convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+    convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0, rank=false)
 
 Split-R-hat, effective sample size and Monte-Carlo standard error per dimension of `thetas[walker][sample]` as `emcee` /
 `metropolis_chains` return it (and of `logdensities`, as a last column, when given), computed on the GPU (`kmc_chain_convergence`; the
 definitions are in include/kissmcmc_hip.h: BDA3, Gelman et al. 2014, pp. 284-287).  Every selected walker is a chain, cut into halves
 with `split`.  Returns a named tuple `(mean, std, rhat, ess, mcse, lag, truncated, m, h)`.  The walkers of ONE emcee ensemble are not
 independent, so R-hat over them is optimistic (src/analysis.jl:69-71): pass the concatenated walkers of separate runs, or Metropolis chains.
+`rank=true` adds `rhat_rank`, `ess_bulk` and `ess_tail` of `rank_convergence`.
 """
-function convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+function convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0, rank=false)
     chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
     mask = _summary_mask(walkers, nw)
     ncols = nd + (logp === nothing ? 0 : 1)
@@ -712,7 +713,64 @@ function convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothi
                max_lag === nothing ? 0 : (max_lag == 0 ? -1 : max_lag), Cint(device),
                mean, W, B, var_plus, rhat, ess, mcse, T, flags, m, h, C_NULL)
     st == 0 || error("kmc_chain_convergence failed ($st): $(last_error())")
-    return (mean=mean, std=sqrt.(var_plus), rhat=rhat, ess=ess, mcse=mcse, lag=T, truncated=(flags .& Int32(2)) .!= 0, m=m[], h=h[])
+    out = (mean=mean, std=sqrt.(var_plus), rhat=rhat, ess=ess, mcse=mcse, lag=T, truncated=(flags .& Int32(2)) .!= 0, m=m[], h=h[])
+    rank || return out
+    r = rank_convergence(thetas; logdensities=logdensities, first_sample=first_sample, walkers=walkers, split=split, max_lag=max_lag, device=device)
+    return merge(out, (rhat_rank=r.rhat, ess_bulk=r.ess_bulk, ess_tail=r.ess_tail))
+end
+
+"""
+    rank_convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+
+Rank-normalised R-hat with bulk and tail effective sample sizes (Vehtari et al. 2021), ranked on the GPU (`kmc_chain_rank_convergence`; the
+definitions are in include/kissmcmc_hip.h).  Returns a named tuple `(rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95,
+median, q05, q95, lag, truncated, has_nan, m, h)`; `lag` is `[column, transform]` for the bulk scores, the folded scores, `I05` and `I95`.
+"""
+function rank_convergence(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    ncols = nd + (logp === nothing ? 0 : 1)
+    cols = [Vector{Float64}(undef, ncols) for _ in 1:10]
+    T = Matrix{Int64}(undef, ncols, 4); flags = Vector{Int32}(undef, ncols)
+    m = Ref{Int64}(0); h = Ref{Int64}(0)
+    st = ccall((:kmc_chain_rank_convergence, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int32, Int64, Cint,
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Int32(split ? 1 : 0),
+               max_lag === nothing ? 0 : (max_lag == 0 ? -1 : max_lag), Cint(device),
+               cols[1], cols[2], cols[3], cols[4], cols[5], cols[6], cols[7], cols[8], cols[9], cols[10], T, flags, m, h, C_NULL)
+    st == 0 || error("kmc_chain_rank_convergence failed ($st): $(last_error())")
+    return (rhat=cols[1], rhat_bulk=cols[2], rhat_folded=cols[3], ess_bulk=cols[4], ess_tail=cols[5], ess_q05=cols[6], ess_q95=cols[7],
+            median=cols[8], q05=cols[9], q95=cols[10], lag=T, truncated=(flags .& Int32(2)) .!= 0, has_nan=(flags .& Int32(4)) .!= 0,
+            m=m[], h=h[])
+end
+
+"""
+    rank_scores(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, folded=false, device=0)
+
+The exact ranks of the pooled draws and their normal scores, ranked on the GPU (`kmc_chain_rank_scores`): a named tuple `(rank2, z, centre,
+nan_count, S, m, h)` with `rank2[sample, chain, column] = #{y < x} + #{y <= x} + 1` (twice the average 1-based rank) and `z` its normal score;
+with `folded` the draws are folded about their column's median (`centre`) first.
+"""
+function rank_scores(thetas; logdensities=nothing, first_sample=0, walkers=nothing, split=true, folded=false, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    ncols = nd + (logp === nothing ? 0 : 1)
+    nsel = mask === nothing ? nw : count(!iszero, mask)
+    n = max(ns - first_sample, 0)
+    hh = split ? n ÷ 2 : n
+    mm = (split ? 2 : 1) * nsel
+    rank2 = zeros(Int64, hh, mm, ncols); z = fill(NaN, hh, mm, ncols)
+    centre = fill(NaN, ncols); nan_count = zeros(Int64, ncols)
+    m = Ref{Int64}(0); h = Ref{Int64}(0)
+    st = ccall((:kmc_chain_rank_scores, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int32, Int32, Cint,
+                Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Int32(split ? 1 : 0),
+               Int32(folded ? 1 : 0), Cint(device), rank2, z, centre, nan_count, m, h)
+    st == 0 || error("kmc_chain_rank_scores failed ($st): $(last_error())")
+    return (rank2=rank2, z=z, centre=folded ? centre : nothing, nan_count=nan_count, S=m[] * h[], m=m[], h=h[])
 end
 
 # make_theta0s (src/samplers.jl:311-349) and squash_walkers (src/samplers.jl:372-428): KissMCMC's own, imported above.

@@ -546,19 +546,36 @@ class Sampler:
         from .chain_convergence import sampler_lag_sums
         return sampler_lag_sums(self, lag0, nlags, first_sample, walkers, split, logp, moments)
 
-    def convergence(self, first_sample: int = 0, walkers=None, split: bool = True, logp: bool = False, max_lag=None):
+    def convergence(self, first_sample: int = 0, walkers=None, split: bool = True, logp: bool = False, max_lag=None, rank: bool = False):
         """Split-R-hat, effective sample size and Monte-Carlo standard error per dimension of the stored chain (with ``logp=True``
         also of the stored log-densities, as the last column), read on the device where it lies (``kmc_sampler_convergence``): a dict
         of columns ``mean, std, rhat, ess, mcse, lag, truncated`` and ``m``, ``h``.  Every walker is a chain (cut in two with
         ``split``); the walkers of one ensemble are not independent, so ``rhat`` over them is optimistic -- see
-        :func:`kissmcmc_jl_amd.convergence` and :func:`kissmcmc_jl_amd.evaluate_convergence`."""
-        from .chain_convergence import columns, sampler_convergence_raw
-        return columns(sampler_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
+        :func:`kissmcmc_jl_amd.convergence` and :func:`kissmcmc_jl_amd.evaluate_convergence`.  ``rank=True`` adds the columns
+        ``rhat_rank, ess_bulk, ess_tail`` of :meth:`rank_convergence`."""
+        from .chain_convergence import add_rank_columns, columns, sampler_convergence_raw
+        cols = columns(sampler_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
+        return add_rank_columns(cols, self.rank_convergence(first_sample, walkers, split, logp, max_lag)) if rank else cols
 
-    def summary(self, theta_true=None, names=None, eff_samples=None, convergence: bool = False):
+    def rank_scores(self, first_sample: int = 0, walkers=None, split: bool = True, folded: bool = False, logp: bool = False):
+        """The exact ranks of the pooled draws of the stored chain and their normal scores, ranked on the device
+        (``kmc_sampler_rank_scores``): a dict ``rank2[ncols, m, h], z[ncols, m, h], centre, nan_count, S, m, h``; see
+        :func:`kissmcmc_jl_amd.rank_scores`."""
+        from .chain_convergence import sampler_rank_scores
+        return sampler_rank_scores(self, first_sample, walkers, split, folded, logp)
+
+    def rank_convergence(self, first_sample: int = 0, walkers=None, split: bool = True, logp: bool = False, max_lag=None):
+        """Rank-normalised R-hat with bulk and tail effective sample sizes of the stored chain (``kmc_sampler_rank_convergence``): a
+        dict of columns ``rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95``, ``lag[4, ncols]``,
+        ``truncated``, ``has_nan`` and ``m``, ``h``; see :func:`kissmcmc_jl_amd.rank_convergence`."""
+        from .chain_convergence import rank_columns, sampler_rank_convergence_raw
+        return rank_columns(sampler_rank_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
+
+    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
         from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain;
-        ``convergence=True`` adds the columns ``rhat, ess, mcse`` of :meth:`convergence`."""
+        ``convergence=True`` adds the columns ``rhat, ess, mcse`` of :meth:`convergence`, ``convergence="rank"`` also
+        ``rhat_rank, ess_bulk, ess_tail``."""
         from .summary import _SamplerProvider, quantiles_from, summary_columns
         p = _SamplerProvider(self)
         median = quantiles_from(p, [0.5])[0]
@@ -571,7 +588,8 @@ class Sampler:
             flat = self.chain(logp=False)[0].reshape(-1, self.ndim)
             mean = flat.mean(axis=0)
             std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(self.ndim, np.nan)
-        return summary_columns(names, median, mean, std, mode, theta_true, eff_samples, self.convergence() if convergence else None)
+        conv = self.convergence(rank=convergence == "rank") if convergence else None
+        return summary_columns(names, median, mean, std, mode, theta_true, eff_samples, conv)
 
     def device_ptr(self, which: int) -> int:
         return int(self._L.kmc_sampler_device_ptr(self._h, int(which)) or 0)

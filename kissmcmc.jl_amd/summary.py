@@ -337,7 +337,7 @@ def credible_levels(hist2d, levels=(0.393, 0.865)):
 def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_samples=None, convergence=None):
     """The table of ``summarize_run`` (reference ``src/analysis.jl:14-38``) as a dict of columns, in the reference's order:
     ``var, [err,] median, mean, mode, std[, eff_samples]``; then ``rhat, ess, mcse`` when ``convergence`` (the dict of
-    :func:`kissmcmc_jl_amd.convergence`) is given."""
+    :func:`kissmcmc_jl_amd.convergence`) is given, and ``rhat_rank, ess_bulk, ess_tail`` when it holds them (``rank=True``)."""
     median, mean, std = (np.asarray(a, dtype=np.float64) for a in (median, mean, std))
     nt = median.size
     names = [str(i + 1) for i in range(nt)] if names is None else [str(v) for v in names]          # :9 names=["$i" for i=1:nt]
@@ -356,13 +356,14 @@ def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_sa
     if eff_samples is not None:
         cols["eff_samples"] = np.asarray(eff_samples)                                              # :26, :37
     if convergence is not None:
-        for k in ("rhat", "ess", "mcse"):
-            cols[k] = np.asarray(convergence[k], dtype=np.float64)[:nt]
+        for k in ("rhat", "ess", "mcse", "rhat_rank", "ess_bulk", "ess_tail"):
+            if k in convergence:
+                cols[k] = np.asarray(convergence[k], dtype=np.float64)[:nt]
     return cols
 
 
 def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_samples=None, provider=None, device: int = 0,
-                  convergence: bool = False):
+                  convergence=False):
     """Summary statistics of a run, reference ``src/analysis.jl:9-42`` (commented out there; followed as written): a dict of columns
     ``var`` (the names, ``"1" .. "ndim"`` by default), ``err = |theta_true - median|`` (only with ``theta_true``), ``median``,
     ``mean``, ``mode``, ``std`` (Julia's: n - 1 in the denominator) and ``eff_samples`` (only when given, passed through).
@@ -373,7 +374,8 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     the source of order statistics and arg-max (tests).
 
     ``convergence=True`` adds the columns ``rhat``, ``ess`` and ``mcse`` of :func:`kissmcmc_jl_amd.convergence` (split chains, every
-    walker a chain; computed on the device)."""
+    walker a chain; computed on the device); ``convergence="rank"`` also ``rhat_rank``, ``ess_bulk`` and ``ess_tail`` of
+    :func:`kissmcmc_jl_amd.rank_convergence`."""
     th = np.asarray(thetas, dtype=np.float64)
     if th.ndim == 2:
         th = th[:, :, None]
@@ -388,5 +390,5 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     conv = None
     if convergence:
         from .chain_convergence import convergence as _convergence
-        conv = _convergence(th, device=device)
+        conv = _convergence(th, device=device, rank=convergence == "rank")
     return summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv)
