@@ -22,7 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .summary import _HostProvider, _p, walker_mask
+from .summary import _HostProvider, _SamplerProvider, _p
 
 COLUMNS = ("mean", "std", "rhat", "ess", "mcse", "lag", "truncated", "m", "h")
 
@@ -60,10 +60,6 @@ def _max_lag_arg(max_lag):
     return 0 if max_lag is None else (int(max_lag) if int(max_lag) != 0 else -1)
 
 
-def _count(mask, nwalkers):
-    return nwalkers if mask is None else int(np.count_nonzero(mask))
-
-
 def _lag_buffers(ncols, nw, nlags, split, moments):
     m = max(1, (2 if split else 1) * nw)
     cm = np.empty((ncols, m)) if moments else None
@@ -71,18 +67,19 @@ def _lag_buffers(ncols, nw, nlags, split, moments):
     return cm, cv, np.empty((ncols, max(0, int(nlags))))
 
 
-def _lag_result(cm, cv, lag, m, h, lag0):
+def lag_sums_from(p, lag0=1, nlags=0, split=True, logp=False, moments=True):
+    """:func:`lag_sums` from a provider (``summary._SamplerProvider``, ``summary._HostProvider``): ``kmc_sampler_lag_sums`` /
+    ``kmc_chain_lag_sums``."""
+    cm, cv, lag = _lag_buffers(p.ndim + (1 if logp else 0), p.nselected, nlags, split, moments)
+    m, h = C.c_int64(), C.c_int64()
+    p.call("lag_sums", [int(bool(split)), int(lag0), int(nlags)], [_p(cm, C.c_double), _p(cv, C.c_double), _p(lag, C.c_double), C.byref(m), C.byref(h)],
+           logp, logp_at=1)
     return {"chain_mean": cm, "chain_var": cv, "lagsum": lag, "lag0": int(lag0), "m": m.value, "h": h.value}
 
 
 def sampler_lag_sums(s, lag0=1, nlags=0, first_sample=0, walkers=None, split=True, logp=False, moments=True):
     """The device stage on the chain a :class:`Sampler` holds (``kmc_sampler_lag_sums``); see :func:`lag_sums`."""
-    mask = walker_mask(walkers, s.nlocal)
-    cm, cv, lag = _lag_buffers(s.ndim + (1 if logp else 0), _count(mask, s.nlocal), nlags, split, moments)
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(s._L.kmc_sampler_lag_sums(s._h, int(first_sample), _p(mask, C.c_uint8), int(bool(split)), int(bool(logp)), int(lag0), int(nlags),
-                                         _p(cm, C.c_double), _p(cv, C.c_double), _p(lag, C.c_double), C.byref(m), C.byref(h)))
-    return _lag_result(cm, cv, lag, m, h, lag0)
+    return lag_sums_from(_SamplerProvider(s, first_sample, walkers), lag0, nlags, split, logp, moments)
 
 
 def lag_sums(thetas, logdensities=None, lag0=1, nlags=0, first_sample=0, walkers=None, split=True, moments=True, device=0):
@@ -91,12 +88,15 @@ def lag_sums(thetas, logdensities=None, lag0=1, nlags=0, first_sample=0, walkers
     ``i >= t`` of ``(x[i, j] - x[i - t, j])**2``, and ``m``, ``h``.  Chain ``j = half * nw + k`` for the k-th selected walker.  Each
     number is the sum of its terms in an order the library chooses: equal bits from equal calls, no float atomics."""
     p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
-    cm, cv, lag = _lag_buffers(p.ndim + (0 if p.logp is None else 1), _count(p.mask, p.nwalkers), nlags, split, moments)
+    return lag_sums_from(p, lag0, nlags, split, p.logp is not None, moments)
+
+
+def _raw(p, name, out, args, split, logp, max_lag):
+    """One of the two whole-diagnostic calls: ``split``, ``with_logp`` / ``device`` by the route, ``max_lag``, the outputs, ``m``, ``h``, ``info``."""
     m, h = C.c_int64(), C.c_int64()
-    _lib.check(_lib.lib().kmc_chain_lag_sums(_p(p.chain, C.c_double), _p(p.logp, C.c_double), p.nsamples, p.nwalkers, p.ndim, p.first,
-                                             _p(p.mask, C.c_uint8), int(bool(split)), int(lag0), int(nlags), p.device, _p(cm, C.c_double),
-                                             _p(cv, C.c_double), _p(lag, C.c_double), C.byref(m), C.byref(h)))
-    return _lag_result(cm, cv, lag, m, h, lag0)
+    p.call(name, [int(bool(split)), _max_lag_arg(max_lag)], args + [C.byref(m), C.byref(h), _p(out["info"], C.c_int64)], logp, logp_at=1)
+    out["m"], out["h"] = m.value, h.value
+    return out
 
 
 def _full_buffers(ncols):
@@ -108,28 +108,21 @@ def _full_buffers(ncols):
     return out, args
 
 
+def convergence_raw_from(p, split=True, logp=False, max_lag=None):
+    """Everything ``kmc_sampler_convergence`` / ``kmc_chain_convergence`` returns: the arrays of :func:`convergence_stats` plus ``m``, ``h``
+    and ``info`` (lags computed, blocks of 32 lags run, bytes of the chain loaded by the lag kernel and by the moment kernels)."""
+    return _raw(p, "convergence", *_full_buffers(p.ndim + (1 if logp else 0)), split, logp, max_lag)
+
+
 def sampler_convergence_raw(s, first_sample=0, walkers=None, split=True, logp=False, max_lag=None):
-    """Everything ``kmc_sampler_convergence`` returns: the arrays of :func:`convergence_stats` plus ``m``, ``h`` and ``info`` (lags
-    computed, blocks of 32 lags run, bytes of the chain loaded by the lag kernel and by the moment kernels)."""
-    mask = walker_mask(walkers, s.nlocal)
-    out, args = _full_buffers(s.ndim + (1 if logp else 0))
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(s._L.kmc_sampler_convergence(s._h, int(first_sample), _p(mask, C.c_uint8), int(bool(split)), int(bool(logp)), _max_lag_arg(max_lag), *args,
-                                            C.byref(m), C.byref(h), _p(out["info"], C.c_int64)))
-    out["m"], out["h"] = m.value, h.value
-    return out
+    """:func:`convergence_raw_from` on the chain a :class:`Sampler` holds."""
+    return convergence_raw_from(_SamplerProvider(s, first_sample, walkers), split, logp, max_lag)
 
 
 def chain_convergence_raw(thetas, logdensities=None, first_sample=0, walkers=None, split=True, max_lag=None, device=0):
-    """The same for a chain in host memory (``kmc_chain_convergence``)."""
+    """The same for a chain in host memory."""
     p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
-    out, args = _full_buffers(p.ndim + (0 if p.logp is None else 1))
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(_lib.lib().kmc_chain_convergence(_p(p.chain, C.c_double), _p(p.logp, C.c_double), p.nsamples, p.nwalkers, p.ndim, p.first,
-                                                _p(p.mask, C.c_uint8), int(bool(split)), _max_lag_arg(max_lag), p.device, *args, C.byref(m), C.byref(h),
-                                                _p(out["info"], C.c_int64)))
-    out["m"], out["h"] = m.value, h.value
-    return out
+    return convergence_raw_from(p, split, p.logp is not None, max_lag)
 
 
 RANK_COLUMNS = ("rhat", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_q05", "ess_q95", "median", "q05", "q95")
@@ -159,19 +152,18 @@ def _score_buffers(ncols, nw, n, split, folded):
             np.zeros(ncols, dtype=np.int64))
 
 
-def _score_result(rank2, z, centre, nan_count, m, h):
+def rank_scores_from(p, split=True, folded=False, logp=False):
+    """:func:`rank_scores` from a provider: ``kmc_sampler_rank_scores`` / ``kmc_chain_rank_scores``."""
+    rank2, z, centre, nan_count = _score_buffers(p.ndim + (1 if logp else 0), p.nselected, p.nsamples - p.first, split, folded)
+    m, h = C.c_int64(), C.c_int64()
+    p.call("rank_scores", [int(bool(split)), int(bool(folded))],
+           [_p(rank2, C.c_int64), _p(z, C.c_double), _p(centre, C.c_double), _p(nan_count, C.c_int64), C.byref(m), C.byref(h)], logp, logp_at=1)
     return {"rank2": rank2, "z": z, "centre": centre, "nan_count": nan_count, "S": m.value * h.value, "m": m.value, "h": h.value}
 
 
 def sampler_rank_scores(s, first_sample=0, walkers=None, split=True, folded=False, logp=False):
     """:func:`rank_scores` on the chain a :class:`Sampler` holds (``kmc_sampler_rank_scores``)."""
-    mask = walker_mask(walkers, s.nlocal)
-    rank2, z, centre, nan_count = _score_buffers(s.ndim + (1 if logp else 0), _count(mask, s.nlocal), s.samples_done - int(first_sample), split, folded)
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(s._L.kmc_sampler_rank_scores(s._h, int(first_sample), _p(mask, C.c_uint8), int(bool(split)), int(bool(logp)), int(bool(folded)),
-                                            _p(rank2, C.c_int64), _p(z, C.c_double), _p(centre, C.c_double), _p(nan_count, C.c_int64),
-                                            C.byref(m), C.byref(h)))
-    return _score_result(rank2, z, centre, nan_count, m, h)
+    return rank_scores_from(_SamplerProvider(s, first_sample, walkers), split, folded, logp)
 
 
 def rank_scores(thetas, logdensities=None, first_sample: int = 0, walkers=None, split: bool = True, folded: bool = False, device: int = 0):
@@ -182,12 +174,7 @@ def rank_scores(thetas, logdensities=None, first_sample: int = 0, walkers=None, 
     else None), ``nan_count[ncols]``, ``S``, ``m``, ``h``.  Order is by value (``-0.0`` ties with ``+0.0``, infinities are ordinary
     values); a column that holds a NaN gets ``rank2 = 0`` and ``z = NaN``.  Chains as in :func:`convergence`."""
     p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
-    rank2, z, centre, nan_count = _score_buffers(p.ndim + (0 if p.logp is None else 1), _count(p.mask, p.nwalkers), p.nsamples - p.first, split, folded)
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(_lib.lib().kmc_chain_rank_scores(_p(p.chain, C.c_double), _p(p.logp, C.c_double), p.nsamples, p.nwalkers, p.ndim, p.first,
-                                                _p(p.mask, C.c_uint8), int(bool(split)), int(bool(folded)), p.device, _p(rank2, C.c_int64),
-                                                _p(z, C.c_double), _p(centre, C.c_double), _p(nan_count, C.c_int64), C.byref(m), C.byref(h)))
-    return _score_result(rank2, z, centre, nan_count, m, h)
+    return rank_scores_from(p, split, folded, p.logp is not None)
 
 
 def _rank_buffers(ncols):
@@ -198,28 +185,22 @@ def _rank_buffers(ncols):
     return out, [_p(out[k], C.c_double) for k in RANK_COLUMNS] + [_p(out["T"], C.c_int64), _p(out["flags"], C.c_int32)]
 
 
+def rank_convergence_raw_from(p, split=True, logp=False, max_lag=None):
+    """Everything ``kmc_sampler_rank_convergence`` / ``kmc_chain_rank_convergence`` returns: the columns of :data:`RANK_COLUMNS`,
+    ``T[4, ncols]``, ``flags``, ``m``, ``h`` and ``info`` (lags computed, bytes the two sorts moved, bytes the lag kernel and the moment
+    kernels loaded)."""
+    return _raw(p, "rank_convergence", *_rank_buffers(p.ndim + (1 if logp else 0)), split, logp, max_lag)
+
+
 def sampler_rank_convergence_raw(s, first_sample=0, walkers=None, split=True, logp=False, max_lag=None):
-    """Everything ``kmc_sampler_rank_convergence`` returns: the columns of :data:`RANK_COLUMNS`, ``T[4, ncols]``, ``flags``, ``m``,
-    ``h`` and ``info`` (lags computed, bytes the two sorts moved, bytes the lag kernel and the moment kernels loaded)."""
-    mask = walker_mask(walkers, s.nlocal)
-    out, args = _rank_buffers(s.ndim + (1 if logp else 0))
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(s._L.kmc_sampler_rank_convergence(s._h, int(first_sample), _p(mask, C.c_uint8), int(bool(split)), int(bool(logp)), _max_lag_arg(max_lag),
-                                                 *args, C.byref(m), C.byref(h), _p(out["info"], C.c_int64)))
-    out["m"], out["h"] = m.value, h.value
-    return out
+    """:func:`rank_convergence_raw_from` on the chain a :class:`Sampler` holds."""
+    return rank_convergence_raw_from(_SamplerProvider(s, first_sample, walkers), split, logp, max_lag)
 
 
 def chain_rank_convergence_raw(thetas, logdensities=None, first_sample=0, walkers=None, split=True, max_lag=None, device=0):
-    """The same for a chain in host memory (``kmc_chain_rank_convergence``)."""
+    """The same for a chain in host memory."""
     p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
-    out, args = _rank_buffers(p.ndim + (0 if p.logp is None else 1))
-    m, h = C.c_int64(), C.c_int64()
-    _lib.check(_lib.lib().kmc_chain_rank_convergence(_p(p.chain, C.c_double), _p(p.logp, C.c_double), p.nsamples, p.nwalkers, p.ndim, p.first,
-                                                     _p(p.mask, C.c_uint8), int(bool(split)), _max_lag_arg(max_lag), p.device, *args, C.byref(m),
-                                                     C.byref(h), _p(out["info"], C.c_int64)))
-    out["m"], out["h"] = m.value, h.value
-    return out
+    return rank_convergence_raw_from(p, split, p.logp is not None, max_lag)
 
 
 def rank_columns(raw):

@@ -1,5 +1,5 @@
-// kmc_chain_view.hpp -- what the calls that read a stored chain where it lies share on the host side (kmc_summary.hip: order statistics and
-// arg-max; kmc_hist.hip: histograms): the view of a chain on the device, the selection (first_sample, walker mask) and the two ways to
+// kmc_chain_view.hpp -- what the calls that read a stored chain where it lies share on the host side (kmc_summary.hip, kmc_hist.hip,
+// kmc_convergence.hip, kmc_rank.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
 // such a view -- the chain a sampler holds, or a dense host chain uploaded for the call.  Internal.
 #pragma once
 #include "kmc_host.hpp"
@@ -48,51 +48,73 @@ inline kmc_status upload_mask(ChainUpload& b, const uint8_t* mask_host, int64_t 
     return KMC_OK;
 }
 
-// the checks the sampler calls share; `host_call` names the call for a chain in host memory in the messages
-inline kmc_status sampler_view(kmc_sampler* s, bool need_logp, const char* host_call, ChainView* v)
-{
-    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
-    if (!s->d_chain) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_CHAIN");
-    if (need_logp && !s->d_chain_logp) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_LOGP");
-    if (s->stream_chain) return fail(KMC_ERR_UNSUPPORTED, std::string("KMC_STREAM_CHAIN: the chain is on the host; use ") + host_call + " on it");
-    if (s->cfg.shard_count > 1 || s->p2p)
-        return fail(KMC_ERR_UNSUPPORTED, std::string("sharded sampler: a shard holds only its own walkers and a select across GPUs is not built; gather the chain and use ") + host_call);
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    v->chain = s->d_chain; v->is_float = s->f32; v->ld = s->ld; v->ndim = s->cfg.ndim;
-    v->logp = s->d_chain_logp; v->nsamples = samples_done(s); v->nl = s->nlocal;
-    return KMC_OK;
-}
+// Where a read-out takes its chain from: the chain a sampler holds, or a dense host chain uploaded for the call.
+// Two steps, so that every read-out, by either route, goes describe -> its own argument checks on the sizes -> sizes out (m, h, n) ->
+// open -> device work: a host chain is refused from its sizes before the device is touched.
+struct ChainSource {
+    kmc_sampler* s = nullptr;
+    const char* host_call = nullptr;                             // the call for a chain in host memory, for the sampler route's messages
+    const double *chain_host = nullptr, *logp_host = nullptr;    // [nsamples][nwalkers][ndim], [nsamples][nwalkers] or nullptr
+    int64_t nsamples = 0, nwalkers = 0, ndim = 0;
+    int device = 0;
+    bool host = false, with_logp = false;                        // with_logp: the log-densities are one more column (host: when they are given)
 
-// kmc_chain_*: a dense host chain on the device (its checks first: nothing is read before they pass)
-inline kmc_status host_view(ChainUpload& b, const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim, int device, ChainView* v)
-{
-    if (!chain_host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (nsamples <= 0 || nwalkers <= 0 || ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples, nwalkers, ndim > 0");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(KMC_ERR_NO_DEVICE, "no HIP device visible");
+    ChainSource(kmc_sampler* s_, bool with_logp_, const char* host_call_) : s(s_), host_call(host_call_), with_logp(with_logp_) {}
+    ChainSource(const double* chain, const double* logp, int64_t nsamples_, int64_t nwalkers_, int64_t ndim_, int device_)
+        : chain_host(chain), logp_host(logp), nsamples(nsamples_), nwalkers(nwalkers_), ndim(ndim_), device(device_), host(true), with_logp(logp != nullptr) {}
+
+    // the sizes of the view.  Host chain: from the arguments alone, no HIP call.  Sampler: its checks, its device made current and its
+    // stream drained; the view is complete.
+    kmc_status describe(ChainView* v) const
+    {
+        if (host) {
+            if (!chain_host) return fail(KMC_ERR_BAD_ARG, "null argument");
+            if (nsamples <= 0 || nwalkers <= 0 || ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples, nwalkers, ndim > 0");
+            v->is_float = false; v->ld = ndim; v->ndim = ndim; v->nsamples = nsamples; v->nl = nwalkers;
+            return KMC_OK;
+        }
+        if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+        if (!s->d_chain) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_CHAIN");
+        if (with_logp && !s->d_chain_logp) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_STORE_LOGP");
+        if (s->stream_chain) return fail(KMC_ERR_UNSUPPORTED, std::string("KMC_STREAM_CHAIN: the chain is on the host; use ") + host_call + " on it");
+        if (s->cfg.shard_count > 1 || s->p2p)
+            return fail(KMC_ERR_UNSUPPORTED, std::string("sharded sampler: a shard holds only its own walkers and a select across GPUs is not built; gather the chain and use ") + host_call);
+        HIP_TRY(hipSetDevice(s->cfg.device));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        v->chain = s->d_chain; v->is_float = s->f32; v->ld = s->ld; v->ndim = s->cfg.ndim;
+        v->logp = s->d_chain_logp; v->nsamples = samples_done(s); v->nl = s->nlocal;
+        return KMC_OK;
     }
-    if (device < 0 || device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(device));
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const double need = (double)nsamples * (double)nwalkers * ((double)ndim + 1.0) * 8.0 + 64.0 * 1048576.0;
-    if (need > (double)free_b)
-        return fail(KMC_ERR_UNSUPPORTED, "the chain (" + std::to_string((int64_t)(need / 1048576.0)) + " MiB with its work space) does not fit the device (" +
-                                             std::to_string(free_b >> 20) + " MiB free); streaming a host chain through the device is not built");
-    const size_t rows = (size_t)nsamples * (size_t)nwalkers;
-    ScopedStream up;
-    HIP_TRY(up.create());
-    HIP_TRY(hipMalloc((void**)&b.chain, rows * (size_t)ndim * sizeof(double)));
-    HIP_TRY(copy_sync(b.chain, chain_host, rows * (size_t)ndim * sizeof(double), hipMemcpyHostToDevice, up.st));
-    if (logp_host) {
-        HIP_TRY(hipMalloc((void**)&b.logp, rows * sizeof(double)));
-        HIP_TRY(copy_sync(b.logp, logp_host, rows * sizeof(double), hipMemcpyHostToDevice, up.st));
+
+    // the pointers of the view.  Host chain: the device, the room and the upload, owned by `b`.  Sampler: nothing left to do.
+    kmc_status open(ChainUpload& b, ChainView* v) const
+    {
+        if (!host) return KMC_OK;
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+            (void)hipGetLastError();
+            return fail(KMC_ERR_NO_DEVICE, "no HIP device visible");
+        }
+        if (device < 0 || device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
+        HIP_TRY(hipSetDevice(device));
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const double need = (double)nsamples * (double)nwalkers * ((double)ndim + 1.0) * 8.0 + 64.0 * 1048576.0;
+        if (need > (double)free_b)
+            return fail(KMC_ERR_UNSUPPORTED, "the chain (" + std::to_string((int64_t)(need / 1048576.0)) + " MiB with its work space) does not fit the device (" +
+                                                 std::to_string(free_b >> 20) + " MiB free); streaming a host chain through the device is not built");
+        const size_t rows = (size_t)nsamples * (size_t)nwalkers;
+        ScopedStream up;
+        HIP_TRY(up.create());
+        HIP_TRY(hipMalloc((void**)&b.chain, rows * (size_t)ndim * sizeof(double)));
+        HIP_TRY(copy_sync(b.chain, chain_host, rows * (size_t)ndim * sizeof(double), hipMemcpyHostToDevice, up.st));
+        if (logp_host) {
+            HIP_TRY(hipMalloc((void**)&b.logp, rows * sizeof(double)));
+            HIP_TRY(copy_sync(b.logp, logp_host, rows * sizeof(double), hipMemcpyHostToDevice, up.st));
+        }
+        v->chain = b.chain; v->logp = b.logp;
+        return KMC_OK;
     }
-    v->chain = b.chain; v->is_float = false; v->ld = ndim; v->ndim = ndim; v->logp = b.logp; v->nsamples = nsamples; v->nl = nwalkers;
-    return KMC_OK;
-}
+};
 
 }  // namespace kmc_chain_view

@@ -53,22 +53,6 @@ kmc_status resolve_max_lag(const ConvShape& sh, int64_t* max_lag)
     return KMC_OK;
 }
 
-// one source of columns: the chain, or the log-densities as a chain of ld = ndim = 1
-struct ConvSource {
-    const void* src;
-    bool is_float;
-    int64_t ld;
-    int32_t ndim, col0;
-};
-
-std::vector<ConvSource> sources(const ChainView& v, bool with_logp)
-{
-    std::vector<ConvSource> s;
-    s.push_back({v.chain, v.is_float, v.ld, (int32_t)v.ndim, 0});
-    if (with_logp) s.push_back({v.logp, false, 1, 1, (int32_t)v.ndim});
-    return s;
-}
-
 kmc_status upload_rank(ConvBuffers& b, const uint8_t* mask_host, int64_t nl, hipStream_t st)
 {
     std::vector<int32_t> rank((size_t)nl);
@@ -284,34 +268,6 @@ kmc_status convergence_device(ConvBuffers& b, const ChainView& v, const ConvShap
     return KMC_OK;
 }
 
-kmc_status lag_sums_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, int64_t lag0, int64_t nlags,
-                           double* chain_mean, double* chain_var, double* lagsum)
-{
-    ScopedStream ss;
-    HIP_TRY(ss.create());
-    KMC_TRY(upload_rank(b, mask_host, v.nl, ss.st));
-    if (chain_mean) KMC_TRY(moments_device(b, v, sh, with_logp, ss.st, chain_mean, chain_var));
-    return lags_device(b, v, sh, with_logp, lag0, nlags, ss.st, lagsum, nlags, 0, nullptr);
-}
-
-kmc_status lag_sums_args(int64_t nlags, const double* chain_mean, const double* chain_var, const double* lagsum)
-{
-    if ((chain_mean == nullptr) != (chain_var == nullptr)) return fail(KMC_ERR_BAD_ARG, "chain_mean and chain_var go together: both or neither");
-    if (nlags > 0 && !lagsum) return fail(KMC_ERR_BAD_ARG, "null lagsum with nlags > 0");
-    return KMC_OK;
-}
-
-// the shape of a host chain, for the checks that come before the device is touched
-kmc_status host_shape(const double* chain_host, int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
-                      bool split, ConvShape* sh)
-{
-    if (!chain_host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (nsamples <= 0 || nwalkers <= 0 || ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples, nwalkers, ndim > 0");
-    ChainView shape;
-    shape.nsamples = nsamples; shape.nl = nwalkers; shape.ndim = ndim;
-    return conv_shape(shape, first_sample, walker_mask, split, sh);
-}
-
 }  // namespace kmc_conv_host
 
 using namespace kmc_conv_host;
@@ -326,53 +282,69 @@ KMC_EXPORT kmc_status kmc_convergence_stats(int64_t m, int64_t h, int64_t ncols,
     return KMC_OK;
 }
 
-KMC_EXPORT kmc_status kmc_sampler_lag_sums(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
-                                           int64_t lag0, int64_t nlags, double* chain_mean, double* chain_var, double* lagsum, int64_t* m_out,
-                                           int64_t* h_out)
+namespace {
+
+kmc_status lag_sums(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t lag0, int64_t nlags,
+                    double* chain_mean, double* chain_var, double* lagsum, int64_t* m_out, int64_t* h_out)
 {
     ChainView v;
-    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_lag_sums", &v));
-    KMC_TRY(lag_sums_args(nlags, chain_mean, chain_var, lagsum));
+    KMC_TRY(src.describe(&v));
+    if ((chain_mean == nullptr) != (chain_var == nullptr)) return fail(KMC_ERR_BAD_ARG, "chain_mean and chain_var go together: both or neither");
+    if (nlags > 0 && !lagsum) return fail(KMC_ERR_BAD_ARG, "null lagsum with nlags > 0");
     ConvShape sh;
     KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
     KMC_TRY(check_lags(sh, lag0, nlags));
     if (m_out) *m_out = sh.m;
     if (h_out) *h_out = sh.h;
     ConvBuffers b;
-    return lag_sums_device(b, v, sh, walker_mask, with_logp != 0, lag0, nlags, chain_mean, chain_var, lagsum);
+    KMC_TRY(src.open(b, &v));
+    ScopedStream ss;
+    HIP_TRY(ss.create());
+    KMC_TRY(upload_rank(b, walker_mask, v.nl, ss.st));
+    if (chain_mean) KMC_TRY(moments_device(b, v, sh, src.with_logp, ss.st, chain_mean, chain_var));
+    return lags_device(b, v, sh, src.with_logp, lag0, nlags, ss.st, lagsum, nlags, 0, nullptr);
+}
+
+kmc_status convergence(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag, const StatsOut& o,
+                       int64_t* m_out, int64_t* h_out, int64_t* info)
+{
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    ConvShape sh;
+    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(resolve_max_lag(sh, &max_lag));
+    if (!o.mean || !o.W || !o.B || !o.var_plus || !o.rhat || !o.ess || !o.mcse || !o.T || !o.flags) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    KMC_TRY(src.open(b, &v));
+    return convergence_device(b, v, sh, walker_mask, src.with_logp, max_lag, o, info);
+}
+
+}  // namespace
+
+KMC_EXPORT kmc_status kmc_sampler_lag_sums(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
+                                           int64_t lag0, int64_t nlags, double* chain_mean, double* chain_var, double* lagsum, int64_t* m_out,
+                                           int64_t* h_out)
+{
+    return lag_sums(ChainSource(s, with_logp != 0, "kmc_chain_lag_sums"), first_sample, walker_mask, split, lag0, nlags, chain_mean, chain_var,
+                    lagsum, m_out, h_out);
 }
 
 KMC_EXPORT kmc_status kmc_chain_lag_sums(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
                                          int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t lag0, int64_t nlags, int device,
                                          double* chain_mean, double* chain_var, double* lagsum, int64_t* m_out, int64_t* h_out)
 {
-    ConvShape sh;
-    KMC_TRY(host_shape(chain_host, nsamples, nwalkers, ndim, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(lag_sums_args(nlags, chain_mean, chain_var, lagsum));
-    KMC_TRY(check_lags(sh, lag0, nlags));
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
-    return lag_sums_device(b, v, sh, walker_mask, logp_host != nullptr, lag0, nlags, chain_mean, chain_var, lagsum);
+    return lag_sums(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, split, lag0, nlags, chain_mean,
+                    chain_var, lagsum, m_out, h_out);
 }
 
 KMC_EXPORT kmc_status kmc_sampler_convergence(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
                                               int64_t max_lag, double* mean, double* W, double* B, double* var_plus, double* rhat, double* ess,
                                               double* mcse, int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info)
 {
-    ChainView v;
-    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_convergence", &v));
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(resolve_max_lag(sh, &max_lag));
-    const StatsOut o{mean, W, B, var_plus, rhat, ess, mcse, T, flags};
-    if (!mean || !W || !B || !var_plus || !rhat || !ess || !mcse || !T || !flags) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    return convergence_device(b, v, sh, walker_mask, with_logp != 0, max_lag, o, info);
+    return convergence(ChainSource(s, with_logp != 0, "kmc_chain_convergence"), first_sample, walker_mask, split, max_lag,
+                       {mean, W, B, var_plus, rhat, ess, mcse, T, flags}, m_out, h_out, info);
 }
 
 KMC_EXPORT kmc_status kmc_chain_convergence(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
@@ -380,17 +352,8 @@ KMC_EXPORT kmc_status kmc_chain_convergence(const double* chain_host, const doub
                                             double* mean, double* W, double* B, double* var_plus, double* rhat, double* ess, double* mcse,
                                             int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info)
 {
-    ConvShape sh;
-    KMC_TRY(host_shape(chain_host, nsamples, nwalkers, ndim, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(resolve_max_lag(sh, &max_lag));
-    const StatsOut o{mean, W, B, var_plus, rhat, ess, mcse, T, flags};
-    if (!mean || !W || !B || !var_plus || !rhat || !ess || !mcse || !T || !flags) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
-    return convergence_device(b, v, sh, walker_mask, logp_host != nullptr, max_lag, o, info);
+    return convergence(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, split, max_lag,
+                       {mean, W, B, var_plus, rhat, ess, mcse, T, flags}, m_out, h_out, info);
 }
 
 // The tile shape of the lag kernel; for tests and benchmarks.  Touches no device.

@@ -3,6 +3,7 @@
 // lag sums, the whole thing on a view.  Internal.
 #pragma once
 #include <cstdint>
+#include <vector>
 
 #include "kmc_chain_view.hpp"
 
@@ -34,6 +35,22 @@ struct ConvBuffers : ChainUpload {
     }
 };
 
+// one source of columns: the chain, or the log-densities as a chain of ld = ndim = 1
+struct ConvSource {
+    const void* src;
+    bool is_float;
+    int64_t ld;
+    int32_t ndim, col0;
+};
+
+inline std::vector<ConvSource> sources(const ChainView& v, bool with_logp)
+{
+    std::vector<ConvSource> s;
+    s.push_back({v.chain, v.is_float, v.ld, (int32_t)v.ndim, 0});
+    if (with_logp) s.push_back({v.logp, false, 1, 1, (int32_t)v.ndim});
+    return s;
+}
+
 // Per column, every sum sequential in index order; no device.
 struct StatsOut {
     double *mean, *W, *B, *var_plus, *rhat, *ess, *mcse;
@@ -44,9 +61,6 @@ struct StatsOut {
 kmc_status conv_shape(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, bool split, ConvShape* sh);
 kmc_status resolve_max_lag(const ConvShape& sh, int64_t* max_lag);
 kmc_status upload_rank(ConvBuffers& b, const uint8_t* mask_host, int64_t nl, hipStream_t st);
-// the shape of a host chain, for the checks that come before the device is touched
-kmc_status host_shape(const double* chain_host, int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
-                      bool split, ConvShape* sh);
 // the whole thing on a view: chain moments once, then lag blocks until every column's rule has fired or max_lag is reached
 kmc_status convergence_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, int64_t max_lag,
                               const StatsOut& o, int64_t* info);

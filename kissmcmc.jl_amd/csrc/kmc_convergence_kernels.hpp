@@ -15,7 +15,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "kmc_chain_kernels.hpp"
+
 namespace kmc_conv {
+
+using namespace kmc_chain;
 
 constexpr int kConvThreads = 256;
 constexpr int kConvLanes = 64;                              // positions p of one tile: one wave's width
@@ -29,22 +33,6 @@ constexpr int kConvLdsBytes = kConvWindowRows * kConvLanes * (int)sizeof(double)
 static_assert(kConvLdsBytes <= 64 * 1024, "the window must fit the default dynamic LDS limit");
 static_assert(kConvLagBlock * kConvLanes <= kConvWindowRows * kConvLanes, "the reduction reuses the window");
 static_assert(kConvTileSamples % kConvLagsPerLane == 0, "a tile is walked in steps of the lags per lane");
-
-__device__ inline double conv_load(const void* src, int is_float, int64_t at)
-{
-    return is_float ? (double)reinterpret_cast<const float*>(src)[at] : reinterpret_cast<const double*>(src)[at];     // exact
-}
-
-// what the lane at position p reads: nothing (false) for a walker outside the selection, a padding column or a position past the row
-__device__ inline bool conv_lane(const int32_t* rank, int64_t p, int64_t np, int64_t ld, int32_t ndim, int64_t* walker, int32_t* col)
-{
-    if (p >= np) return false;
-    const int64_t w = p / ld;
-    const int32_t c = (int32_t)(p - w * ld);
-    *walker = w;
-    *col = c;
-    return c < ndim && rank[w] >= 0;
-}
 
 // ---- chain moments ----
 // pass 0: sum of x; pass 1: sum of (x - mean)^2 with the mean pass 0 left in mean_p.  Workgroup (blockIdx.x, blockIdx.y = hf * nchunk + ck)
@@ -69,18 +57,18 @@ __global__ __launch_bounds__(kConvThreads) void conv_moment_partials(MomentArgs 
     int32_t c = 0;
     if (p >= a.np) return;
     double s = 0.0;
-    if (conv_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c)) {
+    if (chain_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c)) {
         const int64_t i0 = (int64_t)ck * a.clen, i1 = i0 + a.clen < a.h ? i0 + a.clen : a.h;
         const int64_t row = a.nl * a.ld;
         int64_t at = (a.first + (int64_t)hf * a.half_off + i0) * row + p;
         if (a.pass == 0) {
 #pragma unroll 4
-            for (int64_t i = i0; i < i1; ++i, at += row) s += conv_load(a.src, a.is_float, at);
+            for (int64_t i = i0; i < i1; ++i, at += row) s += chain_load(a.src, a.is_float, at);
         } else {
             const double mu = a.mean_p[(int64_t)hf * a.np + p];
 #pragma unroll 4
             for (int64_t i = i0; i < i1; ++i, at += row) {
-                const double d = conv_load(a.src, a.is_float, at) - mu;
+                const double d = chain_load(a.src, a.is_float, at) - mu;
                 s += d * d;
             }
         }
@@ -94,7 +82,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_moment_fold(MomentArgs a)
     const int hf = (int)blockIdx.y;
     int64_t w = 0;
     int32_t c = 0;
-    if (!conv_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c)) return;
+    if (!chain_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c)) return;
     double s = 0.0;
     for (int ck = 0; ck < a.nchunk; ++ck) s += a.part[((int64_t)hf * a.nchunk + ck) * a.np + p];
     const double v = a.pass == 0 ? s / (double)a.h : s / (double)(a.h - 1);
@@ -178,14 +166,14 @@ __global__ __launch_bounds__(kConvThreads) void conv_lag_partials(LagArgs a)
         const int64_t p = q * kConvLanes + lane;
         int64_t w = 0;
         int32_t c = 0;
-        const bool lane_ok = conv_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c);
+        const bool lane_ok = chain_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c);
         for (int64_t ti = ti0; ti < ti1; ++ti) {
             const int64_t i0 = ti * kConvTileSamples;
 #pragma unroll 4
             for (int s = wave; s < nrows; s += kConvWaves) {
                 const int64_t li = s < kConvPartnerRows ? i0 - span + s : i0 + (s - cur_base);
                 double x = 0.0;
-                if (lane_ok && li >= 0 && li < a.h) x = conv_load(a.src, a.is_float, (base + li) * row + p);
+                if (lane_ok && li >= 0 && li < a.h) x = chain_load(a.src, a.is_float, (base + li) * row + p);
                 conv_lds[s * kConvLanes + lane] = x;
             }
             __syncthreads();

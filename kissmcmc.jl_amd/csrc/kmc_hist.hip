@@ -108,9 +108,19 @@ int64_t workgroups(int64_t nsteps)
     return nwg < 1 ? 1 : nwg;
 }
 
-kmc_status histograms_device(HistBuffers& b, const ChainView& v, int64_t first_sample, const uint8_t* mask_host, const std::vector<int32_t>& sel,
-                             const double* edges, int32_t nbins, bool with_logp, int64_t* counts1, int64_t* outside, int64_t* counts2)
+kmc_status histograms(const ChainSource& src, int64_t first_sample, const uint8_t* mask_host, const int32_t* dims, int32_t ndims, const double* edges,
+                      int32_t nbins, int64_t* counts1, int64_t* outside, int64_t* counts2, int64_t* n_out)
 {
+    const bool with_logp = src.with_logp;                             // the log-densities are the last column of the 1-D output
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    std::vector<int32_t> sel;
+    KMC_TRY(check_request(v.ndim, dims, ndims, edges, nbins, with_logp, counts2 != nullptr, counts1, outside, &sel));
+    int64_t N = 0;
+    KMC_TRY(selection_size(v, first_sample, mask_host, &N));
+    if (n_out) *n_out = N;
+    HistBuffers b;
+    KMC_TRY(src.open(b, &v));
     const int64_t nsel = (int64_t)sel.size(), ncols = nsel + (with_logp ? 1 : 0), nrows = (v.nsamples - first_sample) * v.nl;
     const int ne = nbins + 1, nc = nbins + 3;
     ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
@@ -193,35 +203,16 @@ KMC_EXPORT kmc_status kmc_sampler_histograms(kmc_sampler* s, int64_t first_sampl
                                              const double* edges, int32_t nbins, int32_t with_logp, int64_t* counts1, int64_t* outside,
                                              int64_t* counts2, int64_t* n_out)
 {
-    ChainView v;
-    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_histograms", &v));
-    std::vector<int32_t> sel;
-    KMC_TRY(check_request(v.ndim, dims, ndims, edges, nbins, with_logp != 0, counts2 != nullptr, counts1, outside, &sel));
-    int64_t N = 0;
-    KMC_TRY(selection_size(v, first_sample, walker_mask, &N));
-    if (n_out) *n_out = N;
-    HistBuffers b;
-    return histograms_device(b, v, first_sample, walker_mask, sel, edges, nbins, with_logp != 0, counts1, outside, counts2);
+    return histograms(ChainSource(s, with_logp != 0, "kmc_chain_histograms"), first_sample, walker_mask, dims, ndims, edges, nbins, counts1,
+                      outside, counts2, n_out);
 }
 
 KMC_EXPORT kmc_status kmc_chain_histograms(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
                                            int64_t first_sample, const uint8_t* walker_mask, const int32_t* dims, int32_t ndims, const double* edges,
                                            int32_t nbins, int device, int64_t* counts1, int64_t* outside, int64_t* counts2, int64_t* n_out)
 {
-    if (!chain_host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (nsamples <= 0 || nwalkers <= 0 || ndim <= 0) return fail(KMC_ERR_BAD_ARG, "need nsamples, nwalkers, ndim > 0");
-    const bool with_logp = logp_host != nullptr;                      // the log-densities, when given, are the last column of the 1-D output
-    std::vector<int32_t> sel;
-    KMC_TRY(check_request(ndim, dims, ndims, edges, nbins, with_logp, counts2 != nullptr, counts1, outside, &sel));
-    ChainView shape;                                                  // the selection is checked from the sizes, before the device is touched
-    shape.nsamples = nsamples; shape.nl = nwalkers; shape.ndim = ndim;
-    int64_t N = 0;
-    KMC_TRY(selection_size(shape, first_sample, walker_mask, &N));
-    if (n_out) *n_out = N;
-    HistBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
-    return histograms_device(b, v, first_sample, walker_mask, sel, edges, nbins, with_logp, counts1, outside, counts2);
+    return histograms(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, dims, ndims, edges, nbins,
+                      counts1, outside, counts2, n_out);
 }
 
 // How the pairs of `ndims` selected dimensions with `nbins` bins are cut into groups (hist2d reads the selection once per group), and the

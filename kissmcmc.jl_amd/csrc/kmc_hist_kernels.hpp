@@ -10,7 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "kmc_chain_kernels.hpp"
+
 namespace kmc_hist {
+
+using namespace kmc_chain;
 
 // What one workgroup may ask of LDS: the default dynamic limit of a kernel, which needs no function attribute and leaves room for two
 // workgroups per compute unit.  Edges, counters and hist2d's tile of bin indices all come out of it.
@@ -172,9 +176,7 @@ __global__ __launch_bounds__(kHistThreads) void hist2d(Hist2Args a)
             }
             int bin = -1;
             if (ok) {
-                const int64_t at = (a.row0 + row) * a.ld + col;
-                const double v = a.is_float ? (double)reinterpret_cast<const float*>(a.chain)[at] : reinterpret_cast<const double*>(a.chain)[at];
-                bin = hist_bin(my_e, B, v);
+                bin = hist_bin(my_e, B, chain_load(a.chain, a.is_float, (a.row0 + row) * a.ld + col));
             }
             tile[(r << a.sel_shift) + j] = bin >= 0 ? (uint8_t)bin : kHistOut;
         }

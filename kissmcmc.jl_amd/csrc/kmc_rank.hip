@@ -35,21 +35,6 @@ struct RankBuffers {
     }
 };
 
-struct RankSource {
-    const void* src;
-    bool is_float;
-    int64_t ld;
-    int32_t ndim, col0;
-};
-
-std::vector<RankSource> rank_sources(const ChainView& v, bool with_logp)
-{
-    std::vector<RankSource> s;
-    s.push_back({v.chain, v.is_float, v.ld, (int32_t)v.ndim, 0});
-    if (with_logp) s.push_back({v.logp, false, 1, 1, (int32_t)v.ndim});
-    return s;
-}
-
 int64_t tiles_of(int64_t S) { return (S + kRankTileKeys - 1) / kRankTileKeys; }
 
 // the sizes one call may have, from the shape alone
@@ -100,7 +85,7 @@ kmc_status gather(RankBuffers& rb, const ConvBuffers& b, const ChainView& v, con
 {
     const int64_t ncols = v.ndim + (with_logp ? 1 : 0), S = sh.m * sh.h;
     HIP_TRY(hipMemsetAsync(rb.nan, 0, (size_t)ncols * sizeof(unsigned long long), st));
-    for (const RankSource& src : rank_sources(v, with_logp)) {
+    for (const ConvSource& src : sources(v, with_logp)) {
         GatherArgs a{};
         a.src = src.src; a.rank = b.rank; a.centre = folded ? rb.centre : nullptr; a.keys = rb.key_a; a.nan_count = rb.nan;
         a.first = sh.first; a.half_off = sh.half_off; a.h = sh.h; a.nl = v.nl; a.ld = src.ld; a.np = v.nl * src.ld; a.nw = sh.nw; a.S = S;
@@ -140,7 +125,7 @@ kmc_status sort_columns(RankBuffers& rb, int64_t ncols, int64_t S, hipStream_t s
 
 double unkey(uint64_t key)
 {
-    const uint64_t bits = rank_bits_of_key(key);
+    const uint64_t bits = chain_unkey(key);
     double x;
     std::memcpy(&x, &bits, sizeof x);
     return x;
@@ -181,7 +166,7 @@ kmc_status score(RankBuffers& rb, const ConvBuffers& b, const ChainView& v, cons
                  double* scratch, int64_t scratch_cols, hipStream_t st)
 {
     const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
-    for (const RankSource& src : rank_sources(v, with_logp)) {
+    for (const ConvSource& src : sources(v, with_logp)) {
         ScoreArgs a{};
         a.src = src.src; a.rank = b.rank; a.sorted = rb.key_a; a.centre = rb.centre; a.scratch = scratch; a.out_rank2 = rb.out_rank2; a.out_z = rb.out_z;
         a.first = sh.first; a.half_off = sh.half_off; a.h = sh.h; a.nl = v.nl; a.ld = src.ld; a.np = v.nl * src.ld; a.nw = sh.nw; a.S = sh.m * sh.h;
@@ -306,6 +291,38 @@ kmc_status rank_convergence_device(ConvBuffers& b, const ChainView& v, const Con
     return KMC_OK;
 }
 
+kmc_status rank_scores(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t folded, int64_t* rank2, double* z,
+                       double* centre, int64_t* nan_count, int64_t* m_out, int64_t* h_out)
+{
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    ConvShape sh;
+    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(rank_limits(sh, v.ndim + (src.with_logp ? 1 : 0)));
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    KMC_TRY(src.open(b, &v));
+    return rank_scores_device(b, v, sh, walker_mask, src.with_logp, folded != 0, rank2, z, centre, nan_count);
+}
+
+kmc_status rank_convergence(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag, const RankOut& o,
+                            int64_t* m_out, int64_t* h_out, int64_t* info)
+{
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    ConvShape sh;
+    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
+    KMC_TRY(resolve_max_lag(sh, &max_lag));
+    KMC_TRY(rank_limits(sh, v.ndim + (src.with_logp ? 1 : 0)));
+    if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (m_out) *m_out = sh.m;
+    if (h_out) *h_out = sh.h;
+    ConvBuffers b;
+    KMC_TRY(src.open(b, &v));
+    return rank_convergence_device(b, v, sh, walker_mask, src.with_logp, max_lag, o, info);
+}
+
 }  // namespace
 
 // The shape of the sort; for tests and benchmarks.  Touches no device.
@@ -333,30 +350,16 @@ KMC_EXPORT kmc_status kmc_sampler_rank_scores(kmc_sampler* s, int64_t first_samp
                                               int32_t folded, int64_t* rank2, double* z, double* centre, int64_t* nan_count, int64_t* m_out,
                                               int64_t* h_out)
 {
-    ChainView v;
-    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_rank_scores", &v));
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(rank_limits(sh, v.ndim + (with_logp ? 1 : 0)));
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    return rank_scores_device(b, v, sh, walker_mask, with_logp != 0, folded != 0, rank2, z, centre, nan_count);
+    return rank_scores(ChainSource(s, with_logp != 0, "kmc_chain_rank_scores"), first_sample, walker_mask, split, folded, rank2, z, centre,
+                       nan_count, m_out, h_out);
 }
 
 KMC_EXPORT kmc_status kmc_chain_rank_scores(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
                                             int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t folded, int device,
                                             int64_t* rank2, double* z, double* centre, int64_t* nan_count, int64_t* m_out, int64_t* h_out)
 {
-    ConvShape sh;
-    KMC_TRY(host_shape(chain_host, nsamples, nwalkers, ndim, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(rank_limits(sh, ndim + (logp_host ? 1 : 0)));
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
-    return rank_scores_device(b, v, sh, walker_mask, logp_host != nullptr, folded != 0, rank2, z, centre, nan_count);
+    return rank_scores(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, split, folded, rank2, z,
+                       centre, nan_count, m_out, h_out);
 }
 
 KMC_EXPORT kmc_status kmc_sampler_rank_convergence(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
@@ -364,18 +367,8 @@ KMC_EXPORT kmc_status kmc_sampler_rank_convergence(kmc_sampler* s, int64_t first
                                                    double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
                                                    int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info)
 {
-    ChainView v;
-    KMC_TRY(sampler_view(s, with_logp != 0, "kmc_chain_rank_convergence", &v));
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(resolve_max_lag(sh, &max_lag));
-    KMC_TRY(rank_limits(sh, v.ndim + (with_logp ? 1 : 0)));
-    const RankOut o{rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95, T, flags};
-    if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    return rank_convergence_device(b, v, sh, walker_mask, with_logp != 0, max_lag, o, info);
+    return rank_convergence(ChainSource(s, with_logp != 0, "kmc_chain_rank_convergence"), first_sample, walker_mask, split, max_lag,
+                            {rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95, T, flags}, m_out, h_out, info);
 }
 
 KMC_EXPORT kmc_status kmc_chain_rank_convergence(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
@@ -384,16 +377,6 @@ KMC_EXPORT kmc_status kmc_chain_rank_convergence(const double* chain_host, const
                                                  double* ess_q05, double* ess_q95, double* median, double* q05, double* q95, int64_t* T,
                                                  int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info)
 {
-    ConvShape sh;
-    KMC_TRY(host_shape(chain_host, nsamples, nwalkers, ndim, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(resolve_max_lag(sh, &max_lag));
-    KMC_TRY(rank_limits(sh, ndim + (logp_host ? 1 : 0)));
-    const RankOut o{rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95, T, flags};
-    if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
-    return rank_convergence_device(b, v, sh, walker_mask, logp_host != nullptr, max_lag, o, info);
+    return rank_convergence(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, split, max_lag,
+                            {rhat, rhat_bulk, rhat_folded, ess_bulk, ess_tail, ess_q05, ess_q95, median, q05, q95, T, flags}, m_out, h_out, info);
 }

@@ -22,7 +22,11 @@
 #include <cmath>
 #include <cstdint>
 
+#include "kmc_chain_kernels.hpp"
+
 namespace kmc_rank {
+
+using namespace kmc_chain;
 
 constexpr int kRankThreads = 256;
 constexpr int kRankLanes = 64;
@@ -87,16 +91,13 @@ __host__ __device__ inline double rank_score_of(int64_t rank2, int64_t S)
 // (-0.0 + 0.0 = +0.0, so that the two zeros share a key)
 __device__ inline double rank_value(const void* src, int is_float, int64_t at, const double* centre, int32_t col)
 {
-    double x = is_float ? (double)reinterpret_cast<const float*>(src)[at] : reinterpret_cast<const double*>(src)[at];
+    double x = chain_load(src, is_float, at);
     if (centre) x = fabs(x - centre[col]);
     return x + 0.0;
 }
 
-// the key of the order statistics (kmc_summary_kernels.hpp: select_key): all bits flipped when the sign bit is set, else the sign bit
-// flipped, so that keys compare as unsigned integers in value order
-__host__ __device__ inline uint64_t rank_key_of_bits(uint64_t bits) { return (bits >> 63) ? ~bits : (bits ^ 0x8000000000000000ull); }
-__host__ __device__ inline uint64_t rank_bits_of_key(uint64_t key) { return (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key; }
-__device__ inline uint64_t rank_key(double v) { return rank_key_of_bits((uint64_t)__double_as_longlong(v)); }
+// the key of the order statistics: keys compare as unsigned integers in value order
+__device__ inline uint64_t rank_key(double v) { return chain_key((uint64_t)__double_as_longlong(v)); }
 
 // ---- gather ----
 // Workgroup b of a 1-D grid: position tile b % ntile_p (64 positions p = walker * ld + column of a row), sample tile b / ntile_p of the
@@ -121,13 +122,9 @@ __global__ __launch_bounds__(kRankThreads) void rank_gather(GatherArgs a)
     const int64_t row = a.nl * a.ld, base = a.first + hf * a.half_off;
     {
         const int64_t p = p0 + lane;
-        bool ok = p < a.np;
+        int64_t w = 0;
         int32_t c = 0;
-        if (ok) {
-            const int64_t w = p / a.ld;
-            c = (int32_t)(p - w * a.ld);
-            ok = c < a.ndim && a.rank[w] >= 0;
-        }
+        const bool ok = chain_lane(a.rank, p, a.np, a.ld, a.ndim, &w, &c);
         unsigned long long nans = 0;
         for (int s = wave; s < kRankGatherTile; s += kRankWaves) {
             const int64_t i = i0 + s;
@@ -146,11 +143,11 @@ __global__ __launch_bounds__(kRankThreads) void rank_gather(GatherArgs a)
     for (int pp = wave; pp < kRankGatherTile; pp += kRankWaves) {
         const int64_t p = p0 + pp;
         if (p >= a.np) break;
-        const int64_t w = p / a.ld;
-        const int32_t c = (int32_t)(p - w * a.ld);
-        if (c >= a.ndim) continue;
+        int64_t w = 0;
+        int32_t c = 0;
+        if (!chain_lane_in_row(a.rank, p, a.ld, a.ndim, &w, &c) || i >= a.h) continue;
         const int32_t k = a.rank[w];
-        if (k < 0 || i >= a.h) continue;
+        __builtin_assume(k >= 0);                  // (chain_lane_in_row has seen it; told so, the compiler widens k without a sign extension)
         a.keys[(int64_t)(a.col0 + c) * a.S + (hf * a.nw + k) * a.h + i] = t[lane][pp];
     }
 }
@@ -329,11 +326,10 @@ __global__ __launch_bounds__(kRankThreads) void rank_score(ScoreArgs a)
     if (e >= a.nelem) return;
     const int64_t r = e / a.np, p = e - r * a.np;
     const int64_t hf = r / a.h, i = r - hf * a.h;
-    const int64_t w = p / a.ld;
-    const int32_t cs = (int32_t)(p - w * a.ld);
-    if (cs >= a.ndim) return;
+    int64_t w = 0;
+    int32_t cs = 0;
+    if (!chain_lane_in_row(a.rank, p, a.ld, a.ndim, &w, &cs)) return;
     const int32_t k = a.rank[w];
-    if (k < 0) return;
     const int32_t c = a.col0 + cs;
     const double x = rank_value(a.src, a.is_float, (a.first + hf * a.half_off + i) * (a.nl * a.ld) + p, nullptr, 0);
     const double v = a.folded ? fabs(x - a.centre[c]) + 0.0 : x;

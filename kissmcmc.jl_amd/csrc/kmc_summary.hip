@@ -33,9 +33,11 @@ struct SummaryBuffers : ChainUpload {                 // (kmc_chain_view.hpp: th
     }
 };
 
-kmc_status order_stats_device(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, const int64_t* ranks, int32_t nranks,
-                              double* theta_out, double* logp_out, int64_t* n_out)
+kmc_status order_stats(const ChainSource& src, int64_t first_sample, const uint8_t* mask_host, const int64_t* ranks, int32_t nranks,
+                       double* theta_out, double* logp_out, int64_t* n_out)
 {
+    ChainView v;
+    KMC_TRY(src.describe(&v));
     if (!ranks || !theta_out) return fail(KMC_ERR_BAD_ARG, "null argument");
     if (nranks < 1 || nranks > kMaxRanks) return fail(KMC_ERR_BAD_ARG, "between 1 and 16 ranks per call");
     int64_t N = 0;
@@ -59,10 +61,11 @@ kmc_status order_stats_device(const ChainView& v, int64_t first_sample, const ui
     if (nwg < 1) nwg = 1;
     if (ngroups * nwg >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one select");
 
+    SummaryBuffers b;
+    KMC_TRY(src.open(b, &v));
     ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
     HIP_TRY(ss.create());
     const hipStream_t st = ss.st;
-    SummaryBuffers b;
     KMC_TRY(upload_mask(b, mask_host, v.nl, st));
     const size_t hist_bytes = (size_t)nslots * kSelectBins * sizeof(unsigned long long);
     HIP_TRY(hipMalloc((void**)&b.hist, hist_bytes));
@@ -98,18 +101,21 @@ kmc_status order_stats_device(const ChainView& v, int64_t first_sample, const ui
     return KMC_OK;
 }
 
-kmc_status argmax_device(const ChainView& v, int64_t first_sample, const uint8_t* mask_host, int64_t* sample, int64_t* walker, double* theta, double* logp)
+kmc_status argmax(const ChainSource& src, int64_t first_sample, const uint8_t* mask_host, int64_t* sample, int64_t* walker, double* theta, double* logp)
 {
+    ChainView v;
+    KMC_TRY(src.describe(&v));
     if (!sample || !walker || !theta || !logp) return fail(KMC_ERR_BAD_ARG, "null argument");
     int64_t N = 0;
     KMC_TRY(selection_size(v, first_sample, mask_host, &N));
     const int64_t nrows = (v.nsamples - first_sample) * v.nl;
     int64_t np = (nrows + 2047) / 2048;
     if (np > 1024) np = 1024;
+    SummaryBuffers b;
+    KMC_TRY(src.open(b, &v));
     ScopedStream ss;
     HIP_TRY(ss.create());
     const hipStream_t st = ss.st;
-    SummaryBuffers b;
     KMC_TRY(upload_mask(b, mask_host, v.nl, st));
     HIP_TRY(hipMalloc((void**)&b.pv, (size_t)np * sizeof(double)));
     HIP_TRY(hipMalloc((void**)&b.pi, (size_t)np * sizeof(int64_t)));
@@ -135,17 +141,14 @@ kmc_status argmax_device(const ChainView& v, int64_t first_sample, const uint8_t
 KMC_EXPORT kmc_status kmc_sampler_order_stats(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, const int64_t* ranks, int32_t nranks,
                                               double* theta_out, double* logp_out, int64_t* n_out)
 {
-    ChainView v;
-    KMC_TRY(sampler_view(s, logp_out != nullptr, "kmc_chain_order_stats", &v));
-    return order_stats_device(v, first_sample, walker_mask, ranks, nranks, theta_out, logp_out, n_out);
+    return order_stats(ChainSource(s, logp_out != nullptr, "kmc_chain_order_stats"), first_sample, walker_mask, ranks, nranks, theta_out,
+                       logp_out, n_out);
 }
 
 KMC_EXPORT kmc_status kmc_sampler_chain_argmax(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t* sample, int64_t* walker,
                                                double* theta, double* logp)
 {
-    ChainView v;
-    KMC_TRY(sampler_view(s, true, "kmc_chain_argmax", &v));
-    return argmax_device(v, first_sample, walker_mask, sample, walker, theta, logp);
+    return argmax(ChainSource(s, true, "kmc_chain_argmax"), first_sample, walker_mask, sample, walker, theta, logp);
 }
 
 KMC_EXPORT kmc_status kmc_chain_order_stats(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
@@ -153,10 +156,8 @@ KMC_EXPORT kmc_status kmc_chain_order_stats(const double* chain_host, const doub
                                             double* theta_out, double* logp_out, int64_t* n_out)
 {
     if (logp_out && !logp_host) return fail(KMC_ERR_BAD_ARG, "logp_out without logp_host");
-    SummaryBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_out ? logp_host : nullptr, nsamples, nwalkers, ndim, device, &v));
-    return order_stats_device(v, first_sample, walker_mask, ranks, nranks, theta_out, logp_out, n_out);
+    return order_stats(ChainSource(chain_host, logp_out ? logp_host : nullptr, nsamples, nwalkers, ndim, device), first_sample, walker_mask,
+                       ranks, nranks, theta_out, logp_out, n_out);               // (the log-densities are uploaded only when asked for)
 }
 
 KMC_EXPORT kmc_status kmc_chain_argmax(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
@@ -164,8 +165,5 @@ KMC_EXPORT kmc_status kmc_chain_argmax(const double* chain_host, const double* l
                                        double* logp)
 {
     if (!logp_host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    SummaryBuffers b;
-    ChainView v;
-    KMC_TRY(host_view(b, chain_host, logp_host, nsamples, nwalkers, ndim, device, &v));
-    return argmax_device(v, first_sample, walker_mask, sample, walker, theta, logp);
+    return argmax(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, sample, walker, theta, logp);
 }

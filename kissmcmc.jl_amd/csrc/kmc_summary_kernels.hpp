@@ -1,8 +1,7 @@
 // kmc_summary_kernels.hpp -- device kernels of the posterior summaries (kmc_summary.hip): order statistics of a stored chain by
 // most-significant-digit radix select, and the arg-max of the stored log-densities.  Internal.
 //
-// A double maps to a 64-bit key whose unsigned order is the value order (select_key): all bits flipped when the sign bit is set, else
-// the sign bit flipped;  -inf < ... < -0.0 < +0.0 < ... < +inf, NaNs by bit pattern beyond the infinities of their sign.  The select
+// A double maps to a 64-bit key whose unsigned order is the value order (kmc_chain_kernels.hpp: chain_key).  The select
 // walks the key from its top byte down, kSelectPasses passes of kSelectBits bits.  Every (column, rank) pair is a SLOT with a prefix
 // (the digits found so far) and a residual rank; a pass counts, per slot, the next digit of the elements whose higher digits equal the
 // slot's prefix (select_hist), and one small workgroup per slot then finds the digit at which the cumulative count crosses the residual
@@ -12,7 +11,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "kmc_chain_kernels.hpp"
+
 namespace kmc_summary {
+
+using namespace kmc_chain;
 
 constexpr int kSelectBits = 8;                          // digit width: 256 bins, 1 KiB of 32-bit LDS counters per slot
 constexpr int kSelectBins = 1 << kSelectBits;
@@ -20,9 +23,6 @@ constexpr int kSelectPasses = 64 / kSelectBits;
 constexpr int kSelectSlots = 64;                        // slots of one workgroup: 64 KiB of LDS at most
 constexpr int kSelectUnroll = 8;                        // loads a thread has in flight
 constexpr int kMaxRanks = 16;
-
-__host__ __device__ inline uint64_t select_key(uint64_t bits) { return (bits >> 63) ? ~bits : (bits ^ 0x8000000000000000ull); }
-__host__ __device__ inline uint64_t select_unkey(uint64_t key) { return (key >> 63) ? (key ^ 0x8000000000000000ull) : ~key; }
 
 // The columns of the chain are cut into groups of 1 << cg_shift (a power of two, so that a group's piece of every row starts on a
 // 64-byte boundary when it is 8 doubles or more); the log-densities are one more group of one column, number ndim.  Workgroup
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256) void select_hist(SelectArgs a)
                 else if (a.is_float) v = (double)reinterpret_cast<const float*>(a.chain)[r * a.ld + c0 + c];   // exact
                 else v = reinterpret_cast<const double*>(a.chain)[r * a.ld + c0 + c];
             }
-            key[u] = select_key((uint64_t)__double_as_longlong(v));
+            key[u] = chain_key((uint64_t)__double_as_longlong(v));
         }
 #pragma unroll
         for (int u = 0; u < kSelectUnroll; ++u) {
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(kSelectBins) void select_scan(const unsigned long l
         const uint64_t p = prefix[slot] | ((uint64_t)t << (64 - kSelectBits * (pass + 1)));
         prefix[slot] = p;
         krem[slot] = (int64_t)(k - excl);
-        if (pass == kSelectPasses - 1) out[slot] = __longlong_as_double((long long)select_unkey(p));
+        if (pass == kSelectPasses - 1) out[slot] = __longlong_as_double((long long)chain_unkey(p));
     }
 }
 

@@ -81,47 +81,63 @@ def _hist_buffers(dims, edges, logp, pairs):
     return dims, edges, np.zeros((ncols, B), dtype=np.int64), np.zeros((ncols, 3), dtype=np.int64), c2
 
 
-class _SamplerProvider:
-    """Order statistics and arg-max of the chain a :class:`Sampler` holds on the device."""
+class _Provider:
+    """The read-outs of a stored chain, written once for the two routes to it.  A route gives ``ndim``, ``nwalkers``, ``nsamples`` (stored)
+    and ``call(name, ins, outs, logp, logp_at)``: ``kmc_sampler_<name>`` or ``kmc_chain_<name>`` with the route's leading arguments,
+    the call's own inputs ``ins`` and outputs ``outs``; ``logp``: the log-densities take part."""
 
-    def __init__(self, sampler, first_sample=0, walkers=None):
-        self.s, self.first = sampler, int(first_sample)
-        self.ndim = sampler.ndim
-        self.mask = walker_mask(walkers, sampler.nlocal)
-        nw = sampler.nlocal if self.mask is None else int(np.count_nonzero(self.mask))
-        self.n = max(0, sampler.samples_done - self.first) * nw
+    def _select(self, first_sample, walkers):
+        self.first = int(first_sample)
+        self.mask = walker_mask(walkers, self.nwalkers)
+        self.nselected = self.nwalkers if self.mask is None else int(np.count_nonzero(self.mask))
+        self.n = max(0, self.nsamples - self.first) * self.nselected
+
+    def require_logp(self, logp):
+        pass
 
     def order_stats(self, ranks, logp=False):
         ranks = np.ascontiguousarray(ranks, dtype=np.int64)
         th = np.empty((ranks.size, self.ndim))
         lp = np.empty(ranks.size) if logp else None
         n = C.c_int64()
-        _lib.check(self.s._L.kmc_sampler_order_stats(self.s._h, self.first, _p(self.mask, C.c_uint8), _p(ranks, C.c_int64), ranks.size,
-                                                     _p(th, C.c_double), _p(lp, C.c_double), C.byref(n)))
+        self.call("order_stats", [_p(ranks, C.c_int64), ranks.size], [_p(th, C.c_double), _p(lp, C.c_double), C.byref(n)], logp)
         self.n = n.value
         return th, lp
 
     def argmax(self):
         th = np.empty(self.ndim)
         lp, k, w = C.c_double(), C.c_int64(), C.c_int64()
-        _lib.check(self.s._L.kmc_sampler_chain_argmax(self.s._h, self.first, _p(self.mask, C.c_uint8), C.byref(k), C.byref(w),
-                                                      _p(th, C.c_double), C.byref(lp)))
+        self.call("argmax", [], [C.byref(k), C.byref(w), _p(th, C.c_double), C.byref(lp)], True)
         return th, lp.value, k.value, w.value
 
     def histograms(self, dims, edges, logp=False, pairs=False):
         """``(counts1[ncols, B], outside[ncols, 3], counts2[npairs, B, B] | None)`` for the chain columns ``dims`` (and the
         log-densities as the last column with ``logp``) and ``edges[ncols, B + 1]``."""
+        self.require_logp(logp)
         dims, edges, c1, out, c2 = _hist_buffers(dims, edges, logp, pairs)
         n = C.c_int64()
-        _lib.check(self.s._L.kmc_sampler_histograms(self.s._h, self.first, _p(self.mask, C.c_uint8), _p(dims, C.c_int32), dims.size,
-                                                    _p(edges, C.c_double), edges.shape[1] - 1, int(bool(logp)), _p(c1, C.c_int64),
-                                                    _p(out, C.c_int64), _p(c2, C.c_int64), C.byref(n)))
+        self.call("histograms", [_p(dims, C.c_int32), dims.size, _p(edges, C.c_double), edges.shape[1] - 1],
+                  [_p(c1, C.c_int64), _p(out, C.c_int64), _p(c2, C.c_int64), C.byref(n)], logp, logp_at=4)
         self.n = n.value
         return c1, out, c2
 
 
-class _HostProvider:
-    """The same on a chain in host memory (``kmc_chain_order_stats`` / ``kmc_chain_argmax`` upload it)."""
+class _SamplerProvider(_Provider):
+    """The chain a :class:`Sampler` holds on the device (``kmc_sampler_*``)."""
+
+    def __init__(self, sampler, first_sample=0, walkers=None):
+        self.s, self.ndim, self.nwalkers, self.nsamples = sampler, sampler.ndim, sampler.nlocal, sampler.samples_done
+        self._select(first_sample, walkers)
+
+    def call(self, name, ins, outs, logp=False, logp_at=None):
+        """Leading arguments: the handle, ``first``, the mask; ``with_logp`` goes in front of ``ins[logp_at]`` where the call has it."""
+        ins = list(ins) if logp_at is None else list(ins[:logp_at]) + [int(bool(logp))] + list(ins[logp_at:])
+        fn = getattr(self.s._L, "kmc_sampler_" + ("chain_argmax" if name == "argmax" else name))
+        _lib.check(fn(self.s._h, self.first, _p(self.mask, C.c_uint8), *ins, *outs))
+
+
+class _HostProvider(_Provider):
+    """A chain in host memory, uploaded for the call (``kmc_chain_*``)."""
 
     def __init__(self, thetas, logdensities=None, first_sample=0, walkers=None, device=0):
         th = np.asarray(thetas, dtype=np.float64)
@@ -137,45 +153,19 @@ class _HostProvider:
             if lp.shape != (self.nwalkers, self.nsamples):
                 raise ValueError("logdensities must be [walker][sample], like thetas")
             self.logp = np.ascontiguousarray(lp.T)
-        self.first, self.device = int(first_sample), int(device)
-        self.mask = walker_mask(walkers, self.nwalkers)
-        nw = self.nwalkers if self.mask is None else int(np.count_nonzero(self.mask))
-        self.n = max(0, self.nsamples - self.first) * nw
+        self.device = int(device)
+        self._select(first_sample, walkers)
 
-    def order_stats(self, ranks, logp=False):
+    def require_logp(self, logp):
         if logp and self.logp is None:
             raise ValueError("no logdensities were given")
-        ranks = np.ascontiguousarray(ranks, dtype=np.int64)
-        th = np.empty((ranks.size, self.ndim))
-        lp = np.empty(ranks.size) if logp else None
-        n = C.c_int64()
-        _lib.check(_lib.lib().kmc_chain_order_stats(_p(self.chain, C.c_double), _p(self.logp, C.c_double), self.nsamples, self.nwalkers, self.ndim,
-                                                    self.first, _p(self.mask, C.c_uint8), _p(ranks, C.c_int64), ranks.size, self.device,
-                                                    _p(th, C.c_double), _p(lp, C.c_double), C.byref(n)))
-        self.n = n.value
-        return th, lp
 
-    def argmax(self):
-        if self.logp is None:
-            raise ValueError("no logdensities were given")
-        th = np.empty(self.ndim)
-        lp, k, w = C.c_double(), C.c_int64(), C.c_int64()
-        _lib.check(_lib.lib().kmc_chain_argmax(_p(self.chain, C.c_double), _p(self.logp, C.c_double), self.nsamples, self.nwalkers, self.ndim,
-                                               self.first, _p(self.mask, C.c_uint8), self.device, C.byref(k), C.byref(w), _p(th, C.c_double),
-                                               C.byref(lp)))
-        return th, lp.value, k.value, w.value
-
-    def histograms(self, dims, edges, logp=False, pairs=False):
-        if logp and self.logp is None:
-            raise ValueError("no logdensities were given")
-        dims, edges, c1, out, c2 = _hist_buffers(dims, edges, logp, pairs)
-        n = C.c_int64()
-        _lib.check(_lib.lib().kmc_chain_histograms(_p(self.chain, C.c_double), _p(self.logp if logp else None, C.c_double), self.nsamples,
-                                                   self.nwalkers, self.ndim, self.first, _p(self.mask, C.c_uint8), _p(dims, C.c_int32), dims.size,
-                                                   _p(edges, C.c_double), edges.shape[1] - 1, self.device, _p(c1, C.c_int64), _p(out, C.c_int64),
-                                                   _p(c2, C.c_int64), C.byref(n)))
-        self.n = n.value
-        return c1, out, c2
+    def call(self, name, ins, outs, logp=False, logp_at=None):
+        """Leading arguments: chain, log-densities (when they take part), sizes, ``first``, the mask; ``device`` follows ``ins``."""
+        self.require_logp(logp)
+        fn = getattr(_lib.lib(), "kmc_chain_" + name)
+        _lib.check(fn(_p(self.chain, C.c_double), _p(self.logp if logp else None, C.c_double), self.nsamples, self.nwalkers, self.ndim, self.first,
+                      _p(self.mask, C.c_uint8), *ins, self.device, *outs))
 
 
 def quantiles_from(provider, q, logp=False):

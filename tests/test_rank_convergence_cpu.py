@@ -124,3 +124,45 @@ def test_host_chain_refusals_come_before_the_device(kmc):
     assert L.kmc_chain_rank_scores(None, None, 16, 2, 2, 0, None, 1, 0, 0, None, None, None, None, None, None) == _lib.ERR_BAD_ARG
     assert L.kmc_sampler_rank_scores(None, 0, None, 1, 0, 0, None, None, None, None, None, None) == _lib.ERR_BAD_ARG
     assert L.kmc_sampler_rank_convergence(None, 0, None, 1, 0, 0, *([None] * 12), None, None, None) == _lib.ERR_BAD_ARG
+
+
+def test_every_host_chain_call_refuses_from_its_sizes_before_the_device(kmc):
+    """All seven kmc_chain_* read-outs go describe -> arguments -> sizes out -> open -> device work, so a fault in
+    the chain, the selection or the call's own arguments is ERR_BAD_ARG on a machine with no device, never ERR_NO_DEVICE."""
+    from kissmcmc_jl_amd import _lib
+    L = _lib.lib()
+    dp, ip, bp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    NS, NW, ND = 16, 4, 2
+    chain, logp = np.zeros(NS * NW * ND), np.zeros(NS * NW)
+    d, i8 = np.zeros(4096), np.zeros(4096, dtype=np.int64)                     # room for every output of every call
+    i4, ranks = np.zeros(64, dtype=np.int32), np.zeros(17, dtype=np.int64)
+    edges = np.tile(np.linspace(-1.0, 1.0, 9), ND + 1)
+    D, I, I4 = d.ctypes.data_as(dp), i8.ctypes.data_as(ip), i4.ctypes.data_as(i32p)
+
+    def source(c):                                                              # the arguments every call leads with
+        mask = None if c["mask"] is None else c["mask"].ctypes.data_as(bp)
+        return (None if c["chain"] is None else c["chain"].ctypes.data_as(dp), None if c["logp"] is None else c["logp"].ctypes.data_as(dp),
+                c["nsamples"], NW, ND, c["first"], mask)
+
+    def order_stats(c):
+        return L.kmc_chain_order_stats(*source(c), c["ranks"].ctypes.data_as(ip), c["nranks"], 0, D, c["logp_out"], I)
+
+    calls = {
+        "order_stats": order_stats,
+        "argmax": lambda c: L.kmc_chain_argmax(*source(c), 0, I, I, D, D),
+        "histograms": lambda c: L.kmc_chain_histograms(*source(c), None, 0, edges.ctypes.data_as(dp), 8, 0, I, I, I, I),
+        "lag_sums": lambda c: L.kmc_chain_lag_sums(*source(c), 1, 1, 5, 0, D, D, D, I, I),
+        "convergence": lambda c: L.kmc_chain_convergence(*source(c), 1, 0, 0, *([D] * 7), I, I4, I, I, I),
+        "rank_scores": lambda c: L.kmc_chain_rank_scores(*source(c), 1, 1, 0, I, D, D, I, I, I),
+        "rank_convergence": lambda c: L.kmc_chain_rank_convergence(*source(c), 1, 0, 0, *([D] * 10), I, I4, I, I, I),
+    }
+    good = dict(chain=chain, logp=logp, nsamples=NS, first=0, mask=None, ranks=ranks, nranks=1, logp_out=None)
+    faults = {"null chain": dict(chain=None), "nsamples = 0": dict(nsamples=0), "an all-zero walker mask": dict(mask=np.zeros(NW, dtype=np.uint8)),
+              "first_sample > nsamples": dict(first=NS + 1)}
+    own = {"order_stats": {"a rank equal to N": dict(ranks=np.full(1, NS * NW, dtype=np.int64)), "17 ranks": dict(nranks=17),
+                           "logp_out without logp_host": dict(logp=None, logp_out=D)},
+           "argmax": {"null logp_host": dict(logp=None)}}
+    for name, call in calls.items():
+        assert call(good) in (_lib.OK, _lib.ERR_NO_DEVICE), name                  # the table's own call is sound: it gets as far as the device
+        for what, change in {**faults, **own.get(name, {})}.items():
+            assert call({**good, **change}) == _lib.ERR_BAD_ARG, (name, what)
