@@ -887,6 +887,53 @@ kmc_status  kmc_chain_rank_convergence(const double* chain_host, const double* l
                                        double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
                                        int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
 
+/* ---- the posterior covariance and correlation matrix of a stored chain, summed on the device ----
+ * What a corner plot only shows: the covariance of every pair of columns over the selection -- the Gaussian approximation of the
+ * posterior, the shape a proposal, a re-parametrisation or a new starting ball is built from.
+ *
+ * Selection and columns are those of kmc_sampler_lag_sums without the split: the rows are the pairs (stored sample >= first_sample,
+ * walker in the mask), n of them; the columns are the ndim coordinates and, when asked (needs KMC_STORE_LOGP), the log-densities as the
+ * last: C = ncols.  With x[r][c] column c of row r:
+ *   mean[c]   = (sum_r x[r][c]) / n
+ *   cov[a][b] = (sum_r (x[r][a] - mean[a]) (x[r][b] - mean[b])) / (n - 1)      two passes: centred on the device's own mean
+ *   corr[a][b] = cov[a][b] / (sqrt(cov[a][a]) * sqrt(cov[b][b]))                in exactly that operation order; the diagonal is 1.0
+ *                                                                               exactly where the variance is finite and positive
+ * cov is computed for a <= b and mirrored: cov[a][b] and cov[b][a] have the same bits.  A chain of floats (KMC_F32) is widened to double
+ * exactly, element by element, and everything after that is double.  NaN and +-inf in a selected row propagate, by the IEEE rules, into
+ * the entries of the columns they are in and into no others; a constant column has variance 0 and NaN correlations, and no error.  A
+ * row that is not selected -- before first_sample, or of a walker outside the mask -- contributes nothing: its elements are replaced by a
+ * select, never multiplied by zero, so a NaN there does no harm.
+ *
+ * The device stage.  Two passes over the chain where it lies, each writing per-wave partial sums that a second
+ * kernel adds in a fixed order; no floating-point atomics.  The cross products are a SYRK on the double-precision matrix instruction
+ * (v_mfma_f64_16x16x4_f64): columns in tiles of 16, 4 rows an instruction, operands loaded straight from the chain's
+ * [sample][walker][ld] storage.  Up to 32 columns the chain is read once for the products; wider matrices read, per strip of up to
+ * strip_tiles tile pairs, the columns of that strip's tiles.  Which wave takes which rows and the order of the fold follow from the
+ * selection's shape (samples kept, walkers, mask) and C alone -- not from ld, float or double storage, the route or the device -- so two
+ * identical calls return the same bits, and kmc_sampler_covariance equals kmc_chain_covariance on the downloaded chain bit for bit.
+ * Each number is the sum of its terms, formed in double as written above, in an order the library and the instruction choose.
+ *
+ * mean [C], cov [C][C]; *n_out (may be NULL) gets n; info (may be NULL) gets 4 numbers for benchmarks: the rows walked (selected or
+ * not), the partial sums per entry the fold added, the strips, and the bytes of the chain the kernels loaded, counted from the shapes.
+ * KMC_ERR_UNSUPPORTED, naming the limit, for C > 1024; KMC_ERR_BAD_ARG for n < 2 or a null output; the other refusals are those of
+ * kmc_sampler_lag_sums (no KMC_STORE_CHAIN, with_logp without KMC_STORE_LOGP, a streamed chain, a sharded or P2P sampler, an empty
+ * selection, a host chain that does not fit), all before the device is touched. */
+kmc_status  kmc_sampler_covariance(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */,
+                                   int32_t with_logp, double* mean, double* cov, int64_t* n_out, int64_t* info);
+/* The same on a chain in host memory, uploaded to `device` first.  The log-densities are the last column exactly when logp_host is
+ * not NULL. */
+kmc_status  kmc_chain_covariance(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                                 int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                                 int device, double* mean, double* cov, int64_t* n_out, int64_t* info);
+/* The cut of the product kernel for ncols columns: columns of a tile (16), tile pairs a wave keeps accumulators for (strip_tiles: one A
+ * tile against up to that many B tiles), the strips -- 1 up to 32 columns (two tiles, three pairs, one read), else the sum over the A
+ * tiles ta of ceil((ntiles - ta) / strip_tiles) -- and the rows of one block of a wave (the rows are dealt to the waves in blocks of
+ * that many).  Needs no device; pointers may be NULL.  KMC_ERR_BAD_ARG for ncols < 1, KMC_ERR_UNSUPPORTED for ncols > 1024. */
+kmc_status  kmc_cov_plan(int64_t ncols, int32_t* tile_cols, int32_t* strip_tiles, int32_t* nstrips, int32_t* rows_per_wave_block);
+/* The host stage; needs no device.  cov [ncols][ncols] -> corr [ncols][ncols] and sd [ncols] (may be NULL) = sqrt(cov[a][a]), in the
+ * operation order above, so that a restatement in another language gives the same bits.  corr must not overlap cov. */
+kmc_status  kmc_cov_correlation(int64_t ncols, const double* cov, double* corr, double* sd);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

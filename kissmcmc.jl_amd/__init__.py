@@ -14,6 +14,7 @@ from .densities import (CDensity, DataDensity, DeviceLogPdf, Exponential, ExprDe
                         Rosenbrock)
 from .chain_convergence import convergence, convergence_stats, error_of_estimated_mean, evaluate_convergence, lag_sums, samples_vs_tau
 from .chain_convergence import normal_scores, rank_convergence, rank_plan, rank_scores
+from .chain_covariance import correlation, cov_plan, covariance
 from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
@@ -28,6 +29,7 @@ __all__ = [
     "quantiles", "quantile_ranks", "map_sample", "summarize_run", "histogram", "corner", "hist_mode", "credible_levels",
     "convergence", "convergence_stats", "lag_sums", "evaluate_convergence", "error_of_estimated_mean", "samples_vs_tau",
     "rank_convergence", "rank_scores", "rank_plan", "normal_scores",
+    "covariance", "correlation", "cov_plan",
 ]
 
 

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -744,6 +744,31 @@ function rank_convergence(thetas; logdensities=nothing, first_sample=0, walkers=
     return (rhat=cols[1], rhat_bulk=cols[2], rhat_folded=cols[3], ess_bulk=cols[4], ess_tail=cols[5], ess_q05=cols[6], ess_q95=cols[7],
             median=cols[8], q05=cols[9], q95=cols[10], lag=T, truncated=(flags .& Int32(2)) .!= 0, has_nan=(flags .& Int32(4)) .!= 0,
             m=m[], h=h[])
+end
+
+"""
+    covariance(thetas; logdensities=nothing, first_sample=0, walkers=nothing, device=0)
+
+The covariance matrix of the posterior sample `thetas[walker][sample]` as `emcee` / `metropolis_chains` return it (and of `logdensities`,
+as a last column, when given), summed on the GPU (`kmc_chain_covariance`; the definitions are in include/kissmcmc_hip.h), and the
+correlation matrix taken from it on the host (`kmc_cov_correlation`).  Returns a named tuple `(mean, cov, corr, std, n)`; `cov` has
+n - 1 in the denominator and is symmetric bit for bit.
+"""
+function covariance(thetas; logdensities=nothing, first_sample=0, walkers=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    ncols = nd + (logp === nothing ? 0 : 1)
+    mean = Vector{Float64}(undef, ncols); sd = similar(mean)
+    cov = Matrix{Float64}(undef, ncols, ncols); corr = similar(cov)      # symmetric: row- and column-major agree
+    n = Ref{Int64}(0)
+    st = ccall((:kmc_chain_covariance, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Cint(device),
+               mean, cov, n, C_NULL)
+    st == 0 || error("kmc_chain_covariance failed ($st): $(last_error())")
+    st = ccall((:kmc_cov_correlation, LIB), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ncols, cov, corr, sd)
+    st == 0 || error("kmc_cov_correlation failed ($st): $(last_error())")
+    return (mean=mean, cov=cov, corr=corr, std=sd, n=n[])
 end
 
 """

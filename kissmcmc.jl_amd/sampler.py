@@ -571,11 +571,18 @@ class Sampler:
         from .chain_convergence import rank_columns, sampler_rank_convergence_raw
         return rank_columns(sampler_rank_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
 
-    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False):
+    def covariance(self, first_sample: int = 0, walkers=None, logp: bool = False):
+        """The covariance matrix of the stored chain (with ``logp=True`` the stored log-densities are the last column), summed on the
+        device where it lies (``kmc_sampler_covariance``): a dict ``mean[C], cov[C, C], corr[C, C], std[C], n``; see
+        :func:`kissmcmc_jl_amd.covariance`."""
+        from .chain_covariance import sampler_covariance
+        return sampler_covariance(self, first_sample, walkers, logp)
+
+    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False, covariance=False):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
         from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain;
         ``convergence=True`` adds the columns ``rhat, ess, mcse`` of :meth:`convergence`, ``convergence="rank"`` also
-        ``rhat_rank, ess_bulk, ess_tail``."""
+        ``rhat_rank, ess_bulk, ess_tail``; ``covariance=True`` adds the matrices ``cov`` and ``corr`` of :meth:`covariance`."""
         from .summary import _SamplerProvider, quantiles_from, summary_columns
         p = _SamplerProvider(self)
         median = quantiles_from(p, [0.5])[0]
@@ -589,7 +596,11 @@ class Sampler:
             mean = flat.mean(axis=0)
             std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(self.ndim, np.nan)
         conv = self.convergence(rank=convergence == "rank") if convergence else None
-        return summary_columns(names, median, mean, std, mode, theta_true, eff_samples, conv)
+        cols = summary_columns(names, median, mean, std, mode, theta_true, eff_samples, conv)
+        if covariance:
+            c = self.covariance()
+            cols.update(cov=c["cov"], corr=c["corr"])
+        return cols
 
     def device_ptr(self, which: int) -> int:
         return int(self._L.kmc_sampler_device_ptr(self._h, int(which)) or 0)

@@ -353,7 +353,7 @@ def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_sa
 
 
 def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_samples=None, provider=None, device: int = 0,
-                  convergence=False):
+                  convergence=False, covariance=False):
     """Summary statistics of a run, reference ``src/analysis.jl:9-42`` (commented out there; followed as written): a dict of columns
     ``var`` (the names, ``"1" .. "ndim"`` by default), ``err = |theta_true - median|`` (only with ``theta_true``), ``median``,
     ``mean``, ``mode``, ``std`` (Julia's: n - 1 in the denominator) and ``eff_samples`` (only when given, passed through).
@@ -365,7 +365,8 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
 
     ``convergence=True`` adds the columns ``rhat``, ``ess`` and ``mcse`` of :func:`kissmcmc_jl_amd.convergence` (split chains, every
     walker a chain; computed on the device); ``convergence="rank"`` also ``rhat_rank``, ``ess_bulk`` and ``ess_tail`` of
-    :func:`kissmcmc_jl_amd.rank_convergence`."""
+    :func:`kissmcmc_jl_amd.rank_convergence`.  ``covariance=True`` adds the matrices ``cov`` and ``corr`` of
+    :func:`kissmcmc_jl_amd.covariance` (of the dimensions; summed on the device)."""
     th = np.asarray(thetas, dtype=np.float64)
     if th.ndim == 2:
         th = th[:, :, None]
@@ -381,4 +382,9 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     if convergence:
         from .chain_convergence import convergence as _convergence
         conv = _convergence(th, device=device, rank=convergence == "rank")
-    return summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv)
+    cols = summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv)
+    if covariance:
+        from .chain_covariance import covariance as _covariance
+        c = _covariance(th, device=device)
+        cols.update(cov=c["cov"], corr=c["corr"])
+    return cols
