@@ -259,7 +259,7 @@ KMC_EXPORT kmc_status kmc_debug_accept_terms(uint64_t seed, uint64_t step, uint6
     DrawConsts dc{};
     dc.seed_lo = (uint32_t)seed; dc.seed_hi = (uint32_t)(seed >> 32);
     dc.nhalf = (uint32_t)nhalf;
-    dc.c0 = std::sqrt(1.0 / a_scale);                                  // as make_args (src/samplers.jl:227, hoisted)
+    dc.c0 = std::sqrt(1.0 / a_scale);                                  // as draw_consts (src/samplers.jl:227, hoisted)
     dc.c1 = std::sqrt(a_scale) - std::sqrt(1.0 / a_scale);
     dc.nm1 = (double)(ndim - 1);
     const int64_t piece = (int64_t)1 << 22;                             // 4 Mi draws per launch: 112 MiB of device scratch

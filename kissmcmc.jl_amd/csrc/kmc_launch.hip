@@ -1,11 +1,10 @@
 // kmc_launch.hip -- the `_emcee` generation loop (reference src/samplers.jl:232-293) as a stream of kernel launches: two dependent
 // half-step launches per generation (the kernel boundary is the join of src/samplers.jl:273) -- or, for small states, one launch per
 // generation (kmc_generation.hpp) --, replayed from a hipGraph in chunks of kGraphChunk generations -- table-driven, or with per-replay
-// parameter updates -- or issued eagerly; the calibration that picks between them and the process-wide budget of the updated-graph mode.
+// parameter updates (kmc_updated.hip) -- or issued eagerly, and the calibration that picks between them; the routes that are no such stream
+// (resident, islands, data density, host density).
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 
@@ -49,6 +48,30 @@ FlushFn flush_lookup(int L, int K, int iter, bool f32)
     return nullptr;
 }
 
+// what the draws of every kernel take from the configuration (nhalf = nwalkers / 2; island mode overrides it)
+DrawConsts draw_consts(const kmc_sampler* s)
+{
+    DrawConsts dc{};
+    dc.seed_lo = (uint32_t)s->cfg.seed;
+    dc.seed_hi = (uint32_t)(s->cfg.seed >> 32);
+    dc.nhalf = (uint32_t)s->h;
+    dc.c0 = std::sqrt(1.0 / s->cfg.a_scale);                            // src/samplers.jl:227
+    dc.c1 = std::sqrt(s->cfg.a_scale) - std::sqrt(1.0 / s->cfg.a_scale);
+    dc.nm1 = (double)(s->cfg.ndim - 1);
+    if (s->cfg.move == KMC_MOVE_DE) {                                     // the DE kernels read gamma0 and sigma here (kmc_device.hpp: de_gamma)
+        dc.c0 = de_gamma0_of(s->cfg);
+        dc.c1 = s->cfg.de_sigma;
+        dc.nm1 = 0.0;
+    } else if (s->cfg.move == KMC_MOVE_SNOOKER) {                         // gamma; nm1 stays ndim - 1 (the Hastings factor)
+        dc.c0 = snooker_gamma_of(s->cfg.snooker_gamma);
+        dc.c1 = 0.0;
+    } else if (s->cfg.move == KMC_MOVE_MIX) {                             // the member's c0, c1 come from the table (kmc_kernels.hpp: mix_pick)
+        dc.c0 = 0.0;
+        dc.c1 = 0.0;
+    }
+    return dc;
+}
+
 // graph_mode: the generation is (device counter) + gen_offset, looked up in the device schedule
 // table; otherwise gen_offset is the absolute generation and its schedule travels in the args.
 HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t gen_offset)
@@ -74,24 +97,8 @@ HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t 
     a.half = half;
     a.ndim = (int32_t)s->cfg.ndim;
     a.ld = (int32_t)s->ld;
-    a.dc.seed_lo = (uint32_t)s->cfg.seed;
-    a.dc.seed_hi = (uint32_t)(s->cfg.seed >> 32);
-    a.dc.nhalf = (uint32_t)s->h;
-    a.dc.c0 = std::sqrt(1.0 / s->cfg.a_scale);                            // src/samplers.jl:227
-    a.dc.c1 = std::sqrt(s->cfg.a_scale) - std::sqrt(1.0 / s->cfg.a_scale);
-    a.dc.nm1 = (double)(s->cfg.ndim - 1);
-    if (s->cfg.move == KMC_MOVE_DE) {                                     // the DE kernels read gamma0 and sigma here (kmc_device.hpp: de_gamma)
-        a.dc.c0 = de_gamma0_of(s->cfg);
-        a.dc.c1 = s->cfg.de_sigma;
-        a.dc.nm1 = 0.0;
-    } else if (s->cfg.move == KMC_MOVE_SNOOKER) {                         // gamma; nm1 stays ndim - 1 (the Hastings factor)
-        a.dc.c0 = snooker_gamma_of(s->cfg.snooker_gamma);
-        a.dc.c1 = 0.0;
-    } else if (s->cfg.move == KMC_MOVE_MIX) {                             // the member's c0, c1 come from the table (kmc_kernels.hpp: mix_pick)
-        a.dc.c0 = 0.0;
-        a.dc.c1 = 0.0;
-        a.peer_pos[0] = reinterpret_cast<double*>(s->d_mix);
-    }
+    a.dc = draw_consts(s);
+    if (s->cfg.move == KMC_MOVE_MIX) a.peer_pos[0] = reinterpret_cast<double*>(s->d_mix);      // the members' table
     if (s->temper) a.peer_pos[1] = s->d_betas;                            // the tempered kernels read beta_t there (one GPU: no peers)
     if (s->temper_like) {                                                 // likelihood tempering: the walkers' S and priors, the proposals' priors behind their S
         a.peer_pos[2] = s->d_like;
@@ -148,10 +155,9 @@ hipError_t launch_half_kernel(const kmc_sampler* s, const HalfStepArgs& a);
 // Parallel tempering: the node behind a generation's second half-step -- the stored state's log-densities into logp_sum, then the swap
 // sweep (kmc_kernels.hpp: temper_sweep).  Which generations store or sweep changes from one to the next, so the kernel reads that from
 // its schedule entry like the half-step kernels do: inside a graph it is a node of every generation and leaves at once when there is
-// nothing to do; launched eagerly it is launched only where it has work.
-hipError_t launch_temper_sweep(const kmc_sampler* s, const HalfStepArgs& a, bool* launched)
+// nothing to do; launched eagerly it is launched only where it has work, and counted there (a replayed chunk counts its sweep nodes itself).
+hipError_t launch_temper_sweep(kmc_sampler* s, const HalfStepArgs& a)
 {
-    *launched = false;
     if (a.sched_index < 0) {
         const bool stored = (a.sched_inline.flags & kSample) != 0;
         const bool sweep = s->cfg.swap_every > 0 && (a.sched_inline.gen + 1) % s->cfg.swap_every == 0;
@@ -191,19 +197,16 @@ hipError_t launch_temper_sweep(const kmc_sampler* s, const HalfStepArgs& a, bool
     }
     else if (s->temper_like) hipLaunchKernelGGL(temper_sweep_like, grid, dim3(256), 0, s->stream, TemperSweepLikeArgs{t, s->d_like, s->d_prior, s->d_like_sum});
     else hipLaunchKernelGGL(temper_sweep, grid, dim3(256), 0, s->stream, t);
-    *launched = true;
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess && a.sched_index < 0) s->launches += 1;
+    return e;
 }
 
 kmc_status launch_half(kmc_sampler* s, int half, bool graph_mode, int64_t gen_offset)
 {
     const HalfStepArgs a = make_args(s, half, graph_mode, gen_offset);
     HIP_TRY(launch_half_kernel(s, a));
-    if (s->temper && half == 1) {
-        bool swept = false;
-        HIP_TRY(launch_temper_sweep(s, a, &swept));
-        if (swept && !graph_mode) s->launches += 1;           // (the callers count the two half-steps; a replayed chunk counts its sweep nodes itself)
-    }
+    if (s->temper && half == 1) HIP_TRY(launch_temper_sweep(s, a));      // (the callers count the two half-steps)
     if (s->p2p && s->cfg.shard_count > 1) {
         // the kernel boundary puts this half-step's rows in memory; then publish the progress
         SignalArgs sg{};
@@ -232,8 +235,7 @@ hipError_t launch_half_kernel(const kmc_sampler* s, const HalfStepArgs& a)
     if (s->user) {
         const HalfStepLaunch la{f, a};
         if (s->uk.staged) return launch_module(s->uk.staged, (unsigned)s->grid, (unsigned)s->tpb, s->stream, la, (unsigned)staged_lds_bytes((int)s->cfg.ndim));
-        if (s->temper) return launch_module_y(s->plan.vec ? s->uk.vec : s->uk.generic, (unsigned)s->grid, (unsigned)s->ntemps, (unsigned)s->tpb, s->stream, la, s->plan.vec ? s->vec_lds : 0u);
-        return launch_module(s->plan.vec ? s->uk.vec : s->uk.generic, (unsigned)s->grid, (unsigned)s->tpb, s->stream, la, s->plan.vec ? s->vec_lds : 0u);
+        return launch_module_y(s->plan.vec ? s->uk.vec : s->uk.generic, (unsigned)s->grid, (unsigned)s->ntemps, (unsigned)s->tpb, s->stream, la, s->plan.vec ? s->vec_lds : 0u);      // (ntemps: 1 without a ladder)
     }
     if (debug_opt("menu-via-module")) {
         // experiment: the compiled-in kernel launched the way runtime-compiled ones are (hipFunction_t + argument buffer) -- is it the
@@ -293,7 +295,7 @@ GenerationArgs make_generation_args(const kmc_sampler* s, int from, bool graph_m
     a.naccept = s->d_naccept;
     a.sched = graph_mode ? s->d_sched + gen_offset : nullptr;
     a.sched_inline = make_sched(gen_offset, s->cfg.nburnin, s->cfg.nthin, s->nsamples, s->ring_slots);
-    a.dc = make_args(s, 0, false, 0).dc;
+    a.dc = draw_consts(s);
     a.dp = s->dp;
     a.h = (uint32_t)s->h;
     const int64_t per_wg = s->fused_L > 0 ? s->fused_tpb / s->fused_L : s->fused_tpb;       // walkers per workgroup
@@ -344,17 +346,6 @@ hipError_t generation_settle(kmc_sampler* s)
 // at creation): for a caller that steps by halves (kmc_sampler_half_step) or attaches an RCCL communicator (an all-gather follows every
 // half-step).  The moments credited so far -- every walker's current value included, up to now -- are read out once and carried on the host
 // (added at every later read-out); the walkers' current values stand for the samples from here on (klast = samples taken).
-void drop_updated_graph(kmc_sampler* s)
-{
-    for (int i = 0; i < kUExec; ++i) {
-        if (s->uexec[i]) { (void)hipGraphExecDestroy(s->uexec[i]); s->uexec[i] = nullptr; }
-        if (s->udone[i]) { (void)hipEventDestroy(s->udone[i]); s->udone[i] = nullptr; }      // (ensure_updated_graph creates them anew)
-        s->uinflight[i] = false;
-    }
-    s->unext = 0;
-    if (s->ugraph) { (void)hipGraphDestroy(s->ugraph); s->ugraph = nullptr; }
-}
-
 kmc_status unfuse(kmc_sampler* s)
 {
     if (!s->fused) return KMC_OK;
@@ -423,184 +414,6 @@ kmc_status ensure_graph(kmc_sampler* s)
     return KMC_OK;
 }
 
-// ---- updated graph --------------------------------------------------------------------------------------
-struct KernelParamPack {      // storage the kernelParams pointers of one node refer to
-    HalfStepFront f;
-    HalfStepArgs a;
-    void* ptrs[11];
-    void bind()
-    {
-        ptrs[0] = &f.pos; ptrs[1] = &f.sched; ptrs[2] = &f.ring_now; ptrs[3] = &f.logp; ptrs[4] = &f.gw0; ptrs[5] = &f.nact_half;
-        ptrs[6] = &f.seed_lo; ptrs[7] = &f.seed_hi; ptrs[8] = &f.nhalf; ptrs[9] = &f.step; ptrs[10] = &a;
-    }
-};
-
-struct GenerationParamPack {  // the same for a generation kernel's node (one launch per generation)
-    GenerationFront f;
-    GenerationArgs a;
-    void* ptrs[11];
-    void bind()
-    {
-        ptrs[0] = &f.sched; ptrs[1] = &f.pin; ptrs[2] = &f.lin; ptrs[3] = &f.pout; ptrs[4] = &f.seed_lo; ptrs[5] = &f.seed_hi;
-        ptrs[6] = &f.h; ptrs[7] = &f.nb; ptrs[8] = &f.ld; ptrs[9] = &f.gen; ptrs[10] = &a;
-    }
-};
-
-hipKernelNodeParams generation_node_params(const kmc_sampler* s, GenerationParamPack* pk)
-{
-    hipKernelNodeParams np{};
-    np.func = s->user ? reinterpret_cast<void*>(s->uk.generation) : reinterpret_cast<void*>(s->generation_kernel);
-    np.gridDim = dim3(2u * pk->a.nb);
-    np.blockDim = dim3((unsigned)s->fused_tpb);
-    np.sharedMemBytes = 0u;
-    np.kernelParams = pk->ptrs;
-    np.extra = nullptr;
-    return np;
-}
-
-hipKernelNodeParams node_params(const kmc_sampler* s, KernelParamPack* pk)
-{
-    hipKernelNodeParams np{};
-    // (a runtime-compiled density's lane-striped kernel is a module function: the runtime accepts its hipFunction_t as the node's
-    //  function -- ensure_updated_graph tries it once and the sampler stays with the table graph if it does not)
-    np.func = s->user ? reinterpret_cast<void*>(s->uk.vec) : reinterpret_cast<void*>(s->plan.fn);
-    np.gridDim = dim3((unsigned)s->grid);
-    np.blockDim = dim3((unsigned)s->tpb);
-    np.sharedMemBytes = s->user ? s->vec_lds : 0u;
-    np.kernelParams = pk->ptrs;
-    np.extra = nullptr;
-    return np;
-}
-
-bool updated_graph_possible(const kmc_sampler* s)
-{
-    if (s->p2p || s->host_eval || s->islands || s->resident || s->comm || s->updated_refused) return false;
-    if (s->temper) return false;            // (a tempered sampler replays the table graph: the sweep node's work changes per generation -- DESIGN.md 4d)
-    if (s->fused) return s->user ? s->uk.generation != nullptr : s->generation_kernel != nullptr;      // (one node per generation: the generation among the preloaded parameters)
-    return s->user ? (s->plan.vec && s->uk.vec != nullptr) : s->plan.fn != nullptr;
-}
-
-kmc_status ensure_updated_graph(kmc_sampler* s)
-{
-    if (s->uexec[0]) return KMC_OK;
-    HIP_TRY(hipGraphCreate(&s->ugraph, 0));
-    s->unodes.assign((size_t)((s->fused ? 1 : 2) * s->uchunk), nullptr);
-    hipGraphNode_t prev = nullptr;
-    if (s->fused) {
-        // one node per generation, reading copy g & 1 of the state and writing the other (uchunk is even: a replay ends in the copy it started from)
-        GenerationParamPack gp;
-        gp.bind();
-        for (int64_t g = 0; g < s->uchunk; ++g) {
-            gp.a = make_generation_args(s, (int)(g & 1), false, g);
-            gp.f = generation_front_of(gp.a, s->fused_tpb);
-            const hipKernelNodeParams np = generation_node_params(s, &gp);
-            hipGraphNode_t node = nullptr;
-            HIP_TRY(hipGraphAddKernelNode(&node, s->ugraph, prev ? &prev : nullptr, prev ? 1 : 0, &np));
-            s->unodes[(size_t)g] = node;
-            prev = node;
-        }
-    }
-    KernelParamPack pk;
-    pk.bind();
-    for (int64_t g = 0; g < s->uchunk && !s->fused; ++g)
-        for (int half = 0; half < 2; ++half) {
-            pk.a = make_args(s, half, false, g);
-            pk.f = front_of(pk.a, s->ragged_vec());
-            const hipKernelNodeParams np = node_params(s, &pk);
-            hipGraphNode_t node = nullptr;
-            HIP_TRY(hipGraphAddKernelNode(&node, s->ugraph, prev ? &prev : nullptr, prev ? 1 : 0, &np));
-            s->unodes[(size_t)(2 * g + half)] = node;
-            prev = node;
-        }
-    for (int i = 0; i < kUExec; ++i) {
-        HIP_TRY(hipGraphInstantiate(&s->uexec[i], s->ugraph, nullptr, nullptr, 0));
-        HIP_TRY(hipEventCreateWithFlags(&s->udone[i], hipEventDisableTiming));
-    }
-    return KMC_OK;
-}
-
-// hipGraphExecKernelNodeSetParams keeps host memory inside the runtime, per call and for good (kmc_sampler_run: launch modes): ~80 bytes in the HIP 7.0 runtime (the one
-// PyTorch's wheel bundles and a Python process therefore runs on), ~1.4 bytes in 7.2 (/opt/rocm of this image; scripts/probes/updated_graph_rss.py, profiles/r05_updated_graph_rss.txt).
-// A process-wide budget of such calls -- 64 MiB worth by default, priced by the runtime this process actually loaded.
-double update_bytes_each()
-{
-    static const double b = [] {
-        int v = 0;
-        return (hipRuntimeGetVersion(&v) == hipSuccess && v >= 70200000) ? 2.0 : 80.0;
-    }();
-    return b;
-}
-std::atomic<int64_t> g_update_calls{0};
-std::atomic<int64_t>& update_budget()
-{
-    static std::atomic<int64_t> budget{[] {
-        double mb = 64.0;
-        std::string v;
-        if (debug_opt("updated-budget-mb", &v) && !v.empty()) mb = std::atof(v.c_str());
-        return (int64_t)(mb * 1048576.0 / update_bytes_each());
-    }()};
-    return budget;
-}
-// room for `need` more parameter updates (a replay of this sampler: 2 * uchunk)?  A replay that would overshoot the budget is not started.
-bool update_budget_left(int64_t need) { return g_update_calls.load(std::memory_order_relaxed) + need <= update_budget().load(std::memory_order_relaxed); }
-
-void note_budget_spent(kmc_sampler* s)
-{
-    s->budget_fallback = true;
-    static std::atomic<bool> said{false};
-    if (!said.exchange(true))
-        std::fprintf(stderr, "[kissmcmc_hip] the updated-graph launch mode has used up this process's budget (%lld parameter updates, "
-                             "kmc_set_updated_budget_mb / KMC_DEBUG=updated-budget-mb=n; this HIP runtime keeps ~%.0f B per update): samplers now "
-                             "choose between the table graph and eager launches (up to ~9 %% slower per half-step; results are identical)\n",
-                     (long long)g_update_calls.load(std::memory_order_relaxed), update_bytes_each());
-}
-
-// one replay of s->uchunk generations starting at s->generation.  *launched tells a failure BEFORE the replay was
-// enqueued (nothing ran: the caller may issue these generations another way) from one after it (they are running).
-kmc_status launch_updated_graph(kmc_sampler* s, bool* launched)
-{
-    *launched = false;
-    KMC_TRY(ensure_updated_graph(s));
-    g_update_calls.fetch_add((s->fused ? 1 : 2) * s->uchunk, std::memory_order_relaxed);
-    const int i = s->unext;
-    const auto t_wait0 = std::chrono::steady_clock::now();
-    if (s->uinflight[i]) { HIP_TRY(hipEventSynchronize(s->udone[i])); s->uinflight[i] = false; }
-    const auto t_upd0 = std::chrono::steady_clock::now();
-    if (s->fused) {
-        GenerationParamPack gp;
-        gp.bind();
-        for (int64_t g = 0; g < s->uchunk; ++g) {
-            gp.a = make_generation_args(s, (int)(g & 1), false, s->generation + g);
-            gp.f = generation_front_of(gp.a, s->fused_tpb);
-            const hipKernelNodeParams np = generation_node_params(s, &gp);
-            HIP_TRY(hipGraphExecKernelNodeSetParams(s->uexec[i], s->unodes[(size_t)g], &np));
-        }
-    }
-    KernelParamPack pk;
-    pk.bind();
-    for (int64_t g = 0; g < s->uchunk && !s->fused; ++g)
-        for (int half = 0; half < 2; ++half) {
-            pk.a = make_args(s, half, false, s->generation + g);
-            pk.f = front_of(pk.a, s->ragged_vec());
-            const hipKernelNodeParams np = node_params(s, &pk);
-            HIP_TRY(hipGraphExecKernelNodeSetParams(s->uexec[i], s->unodes[(size_t)(2 * g + half)], &np));
-        }
-    const auto t_upd1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipGraphLaunch(s->uexec[i], s->stream));
-    const auto t_launch1 = std::chrono::steady_clock::now();
-    // where the feeding thread's time goes (kmc_sampler_describe with KMC_DEBUG=feed-stats): waiting for a free executable = the GPU is
-    // the bottleneck; updating + launching = the host's own cost per replay, which must stay below the replay's GPU time
-    s->feed_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t_upd0 - t_wait0).count();
-    s->feed_update_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t_upd1 - t_upd0).count();
-    s->feed_launch_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(t_launch1 - t_upd1).count();
-    s->feed_replays += 1;
-    *launched = true;
-    HIP_TRY(hipEventRecord(s->udone[i], s->stream));
-    s->uinflight[i] = true;
-    s->unext = (i + 1) % kUExec;
-    return KMC_OK;
-}
-
 // Streaming moments of the multi-launch kernels are sojourn-weighted (a walker's value is credited when it is replaced):
 // credit every walker's CURRENT value with the samples it has stood for so far (enqueued on the sampler's stream; after
 // it every klast equals the number of samples taken).  Before a read-out, and before walkers change slots (deal).
@@ -629,7 +442,362 @@ kmc_status flush_moments_now(kmc_sampler* s)
     return KMC_OK;
 }
 
+// ---- kmc_sampler_run, route by route: each enqueues `ngen` generations from s->generation on -----------------------------
+
+// what the resident and the island kernels share: n generations from s->generation on (permA, permC and an island's nhalf: the caller's)
+IslandArgs island_args(const kmc_sampler* s, int64_t n)
+{
+    IslandArgs ia{};
+    ia.pos = s->d_pos; ia.logp = s->d_logp; ia.naccept = s->d_naccept;
+    ia.nwalkers = s->cfg.nwalkers;
+    ia.gen0 = s->generation; ia.ngen = (int32_t)n;
+    ia.ndim = (int32_t)s->cfg.ndim; ia.ld = (int32_t)s->ld;
+    ia.nburnin = s->cfg.nburnin; ia.nthin = s->cfg.nthin; ia.nsamples = s->nsamples;
+    ia.dc = draw_consts(s);              // nhalf = nwalkers / 2, as in the multi-launch kernels
+    ia.dp = s->dp;
+    ia.msum = s->d_isum; ia.msumsq = s->d_isumsq;
+    return ia;
+}
+
+// the whole ensemble lives in one workgroup's LDS; a launch carries up to 1024 generations, whose draws a wide kernel
+// computes first (draw_table_fill, kmc_islands.hpp)
+kmc_status run_resident(kmc_sampler* s, int64_t ngen)
+{
+    while (ngen > 0) {
+        int64_t n = std::min<int64_t>(ngen, kDrawTableGens);
+        if (s->stream_chain) n = std::min<int64_t>(n, std::max<int64_t>(1, (s->ring_blk - 1) * s->cfg.nthin));   // a launch fills less than a block of the ring
+        KMC_TRY(chain_before(s, s->generation + n));
+        ResidentArgs ra{};
+        ra.is = island_args(s, n);
+        ra.is.permA = 1; ra.is.permC = 0;
+        ra.S = (int32_t)s->cfg.nwalkers;
+        ra.chain = s->d_chain; ra.chain_logp = s->d_chain_logp;
+        ra.blob = s->d_blob; ra.chain_blob = s->d_chain_blob;
+        ra.ring_slots = s->stream_chain ? s->ring_slots : 0;
+        {                                    // (d_draws: allocated with every resident sampler)
+            DrawTableArgs ta{};
+            const int64_t npad = (n + kDrawBatch - 1) / kDrawBatch * kDrawBatch;      // whole batches (<= kDrawTableGens, a multiple)
+            ta.dc = ra.is.dc; ta.gen0 = s->generation; ta.ngen = (int32_t)npad; ta.S = ra.S; ta.out = s->d_draws;
+            hipLaunchKernelGGL(draw_table_fill, dim3((unsigned)((npad * ra.S + 255) / 256)), dim3(256), 0, s->stream, ta);
+            HIP_TRY(hipGetLastError());
+            ra.draws = s->d_draws;
+            s->launches += 1;
+        }
+        if (s->user) {
+            HIP_TRY(launch_module(s->uk.resident, 1u, (unsigned)s->resident_tpb, s->stream, ra, (unsigned)s->island_lds));
+        } else {
+            hipLaunchKernelGGL(s->resident_kernel, dim3(1), dim3((unsigned)s->resident_tpb), s->island_lds, s->stream, ra);
+            HIP_TRY(hipGetLastError());
+        }
+        s->generation += n;
+        s->launches += 1;
+        ngen -= n;
+        KMC_TRY(chain_after(s));
+    }
+    return KMC_OK;
+}
+
+// one launch per epoch (or per piece of one, when a run stops inside an epoch)
+kmc_status run_islands(kmc_sampler* s, int64_t ngen)
+{
+    while (ngen > 0) {
+        const int64_t epoch = s->generation / s->island_gens;
+        const int64_t upto = (epoch + 1) * s->island_gens;
+        const int64_t n = std::min<int64_t>(ngen, upto - s->generation);
+        IslandArgs ia = island_args(s, n);
+        island_perm(s->cfg.seed, epoch, s->cfg.nwalkers, &ia.permA, &ia.permC);
+        ia.dc.nhalf = (uint32_t)(s->island_size / 2);
+        if (s->user) {
+            HIP_TRY(launch_module(s->uk.island, (unsigned)s->nislands, (unsigned)s->island_size, s->stream, ia, (unsigned)s->island_lds));
+        } else {
+            hipLaunchKernelGGL(s->island_kernel, dim3((unsigned)s->nislands), dim3((unsigned)s->island_size), s->island_lds, s->stream, ia);
+            HIP_TRY(hipGetLastError());
+        }
+        s->generation += n;
+        s->launches += 1;
+        ngen -= n;
+    }
+    return KMC_OK;
+}
+
+kmc_status run_data(kmc_sampler* s, int64_t ngen)
+{
+    // per half-step: PROPOSE (the host route's first pass) -> partial sums -> fold -> ACCEPT, all on the sampler's stream.  A likelihood-tempered
+    // ladder does the same four launches for every rung at once (the rung as the grid's second dimension in PROPOSE and ACCEPT, ntemps h proposals
+    // in one pass of the data kernels -- S does not depend on beta), then the sweep where it has work
+    const int64_t nprop = (int64_t)s->ntemps * s->h;
+    for (; ngen > 0; --ngen) {
+        KMC_TRY(chain_before(s, s->generation + 1));
+        for (int half = 0; half < 2; ++half) {
+            HalfStepArgs a = make_args(s, half, false, s->generation);
+            a.prop_out = s->d_prop;
+            a.prop_ld = (int32_t)s->ld;
+            HIP_TRY(launch_half_kernel(s, a));
+            HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_half, s->d_prop, nprop, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_p1, s->stream, s->temper_like));
+            a.prop_out = nullptr;
+            a.p1_in = s->d_p1;
+            HIP_TRY(launch_half_kernel(s, a));
+            s->launches += 4;
+            if (s->temper && half == 1) HIP_TRY(launch_temper_sweep(s, a));
+        }
+        s->generation += 1;
+        KMC_TRY(chain_after(s));
+    }
+    return KMC_OK;
+}
+
+kmc_status run_host(kmc_sampler* s, int64_t ngen)
+{
+    // per half-step: PROPOSE on the device -> proposals to the host -> callback -> log-pdfs back
+    // -> ACCEPT on the device (which recomputes the same proposals from the same draws)
+    const size_t hh = (size_t)s->h, nd = (size_t)s->cfg.ndim, ld = (size_t)s->ld;
+    // Large batches travel in pieces, each behind its own event: the callback works on piece c while piece c + 1 is still
+    // on the link (the D2H of the proposals is the larger half of a half-step's time once the closure is cheap).  Not when
+    // accept outcomes go back to the host as well: that caller keeps per-batch state (blobs) between the two callbacks.
+    int npiece = (!s->cfg.host_accepted && hh >= 8192) ? 4 : 1;
+    { const long v = debug_opt_long("host-pieces", 0); if (v >= 1 && v <= kHostPieces && !s->cfg.host_accepted) npiece = (int)v; }
+    for (int i = 0; i < npiece && npiece > 1; ++i)
+        if (!s->host_ev[i]) HIP_TRY(hipEventCreateWithFlags(&s->host_ev[i], hipEventDisableTiming));
+    // Small batches (the reference's own sizes) skip the copies: the propose kernel writes the dense proposal rows straight into
+    // the page-locked host array over the link and the accept kernel reads the log-pdfs straight from theirs -- a half-step is
+    // then two launches, one synchronisation and the callback (100 walkers: 32 -> ~15 us with a Python callable).
+    // KMC_DEBUG=host-zerocopy=0|1 forces it off / on.
+    bool zero_copy = npiece == 1 && s->h_prop_dev != nullptr && hh * nd * sizeof(double) <= ((size_t)256 << 10);
+    { std::string e; if (debug_opt("host-zerocopy", &e)) zero_copy = e == "1" && npiece == 1 && s->h_prop_dev != nullptr; }
+    for (; ngen > 0; --ngen) {
+        KMC_TRY(chain_before(s, s->generation + 1));
+        for (int half = 0; half < 2; ++half) {
+            HalfStepArgs a = make_args(s, half, false, s->generation);
+            a.prop_out = zero_copy ? s->h_prop_dev : s->d_prop;
+            a.prop_ld = zero_copy ? (int32_t)nd : (int32_t)ld;
+            HIP_TRY(launch_half_kernel(s, a));
+            bool cb_failed = false;
+            if (npiece == 1) {                     // (zero_copy: one piece, already there)
+                if (!zero_copy) HIP_TRY(hipMemcpy2DAsync(s->h_prop, nd * sizeof(double), s->d_prop, ld * sizeof(double), nd * sizeof(double), hh,
+                                                         hipMemcpyDeviceToHost, s->stream));
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                cb_failed = s->cfg.host_logpdf(s->h_prop, (int64_t)hh, (int64_t)nd, s->h_p1, s->cfg.host_user) != 0;   // :257
+            } else {
+                auto r0 = [&](int c) { return hh * (size_t)c / (size_t)npiece; };
+                for (int c = 0; c < npiece; ++c) {
+                    HIP_TRY(hipMemcpy2DAsync(s->h_prop + r0(c) * nd, nd * sizeof(double), s->d_prop + r0(c) * ld, ld * sizeof(double), nd * sizeof(double),
+                                             r0(c + 1) - r0(c), hipMemcpyDeviceToHost, s->stream));
+                    HIP_TRY(hipEventRecord(s->host_ev[c], s->stream));
+                }
+                for (int c = 0; c < npiece; ++c) {
+                    HIP_TRY(hipEventSynchronize(s->host_ev[c]));
+                    if (!cb_failed)
+                        cb_failed = s->cfg.host_logpdf(s->h_prop + r0(c) * nd, (int64_t)(r0(c + 1) - r0(c)), (int64_t)nd, s->h_p1 + r0(c), s->cfg.host_user) != 0;   // :257
+                }
+            }
+            if (cb_failed) {
+                s->positions_set = false;
+                return fail(KMC_ERR_BAD_ARG, "the host log-pdf callback failed in generation " + std::to_string(s->generation));
+            }
+            if (!zero_copy) HIP_TRY(hipMemcpyAsync(s->d_p1, s->h_p1, hh * sizeof(double), hipMemcpyHostToDevice, s->stream));
+            a.prop_out = nullptr;
+            a.p1_in = zero_copy ? s->h_p1_dev : s->d_p1;
+            a.acc_out = s->d_acc;
+            HIP_TRY(launch_half_kernel(s, a));
+            s->launches += 2;
+            if (s->cfg.host_accepted) {
+                HIP_TRY(hipMemcpyAsync(s->h_acc, s->d_acc, hh, hipMemcpyDeviceToHost, s->stream));
+                HIP_TRY(hipStreamSynchronize(s->stream));
+                const int32_t stored = (a.sched_inline.flags & kSample) != 0 ? 1 : 0;
+                if (s->cfg.host_accepted(s->h_acc, (int64_t)hh, (int64_t)half * (int64_t)hh, s->generation, stored, s->cfg.host_user) != 0) {
+                    s->positions_set = false;
+                    return fail(KMC_ERR_BAD_ARG, "the host accept callback failed in generation " + std::to_string(s->generation));
+                }
+            }
+        }
+        s->generation += 1;
+        KMC_TRY(chain_after(s));
+    }
+    return KMC_OK;
+}
+
+// ---- the multi-launch route: `*left` generations are still owed; every piece below takes what it enqueues off it ---------
+kmc_status eager_generations(kmc_sampler* s, int64_t n, int64_t* left)
+{
+    for (; n > 0; --n, --*left) {
+        KMC_TRY(chain_before(s, s->generation + 1));
+        if (s->fused) {
+            HIP_TRY(launch_generation(s, s->fused_cur, false, s->generation));
+            s->fused_cur ^= 1;
+        } else {
+            for (int half = 0; half < 2; ++half) KMC_TRY(launch_half(s, half, false, s->generation));
+        }
+        s->generation += 1;
+        s->launches += launches_per_generation(s);
+        if (!s->fused && ++s->gens_since_sweep >= kSweepEvery) HIP_TRY(launch_sweep(s));
+        KMC_TRY(chain_after(s));
+    }
+    return KMC_OK;
+}
+
+kmc_status graph_chunk(kmc_sampler* s, int64_t* left)
+{
+    if (s->fused) HIP_TRY(generation_settle(s));                    // (a chunk of generation kernels starts in copy 0 and ends there)
+    KMC_TRY(ensure_graph(s));
+    if (!s->graph_exec) return eager_generations(s, kGraphChunk, left);      // (RCCL all-gather that cannot be captured)
+    KMC_TRY(sync_device_counter(s));
+    KMC_TRY(chain_before(s, s->generation + kGraphChunk));
+    HIP_TRY(hipGraphLaunch(s->graph_exec, s->stream));
+    if (!s->fused) HIP_TRY(launch_sweep(s));
+    s->generation += kGraphChunk;
+    s->dev_gen += kGraphChunk;
+    s->launches += (launches_per_generation(s) + (s->temper ? 1 : 0)) * kGraphChunk;          // (a tempered chunk: the sweep node of every generation)
+    *left -= kGraphChunk;
+    return chain_after(s);
+}
+
+kmc_status updated_chunk(kmc_sampler* s, int64_t* left)
+{
+    if (s->fused) HIP_TRY(generation_settle(s));
+    KMC_TRY(chain_before(s, s->generation + s->uchunk));
+    bool launched = false;
+    if (launch_updated_graph(s, &launched) != KMC_OK) {
+        // this sampler uses the table graph from here on (run_launches goes on with graph_chunk while a whole chunk is
+        // left, eagerly after that: exactly the generations asked for).  Failed before the replay was enqueued: nothing
+        // ran, nothing to account.  Failed after it (the event of this executable): the replay is running -- account
+        // it; without its event the executable is not reused, which leaving this mode guarantees.
+        s->launch_mode = 1;
+        if (debug_opt("feed-stats")) std::fprintf(stderr, "[kissmcmc_hip] the updated-graph replay failed (%s): table graph from here on\n", kmc_last_error());
+        if (!launched) return KMC_OK;
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (!s->fused) HIP_TRY(launch_sweep(s));
+    s->generation += s->uchunk;
+    s->launches += launches_per_generation(s) * s->uchunk;
+    *left -= s->uchunk;
+    return chain_after(s);
+}
+
+// generations measured in each mode, and the shortest run that measures: warm-up pieces + both measurements + a chunk to spare (896)
+inline int64_t calib_gens(const kmc_sampler* s) { return std::max<int64_t>(4 * kGraphChunk, 2 * s->uchunk); }
+inline int64_t calib_min(const kmc_sampler* s) { return kGraphChunk + 2 * std::max<int64_t>(kGraphChunk, s->uchunk) + 2 * calib_gens(s) + kGraphChunk; }
+
+// the table graph against the updated graph (or eager launches): calib_gens generations each, between HIP events
+kmc_status calibrate(kmc_sampler* s, bool with_updated, int64_t* left)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventCreate(&e2));
+    const int64_t gens = calib_gens(s);
+    kmc_status st = graph_chunk(s, left);                                    // warm: instantiation, code objects
+    if (st == KMC_OK) st = with_updated ? updated_chunk(s, left) : eager_generations(s, kGraphChunk, left);
+    if (st == KMC_OK) st = with_updated ? updated_chunk(s, left) : eager_generations(s, kGraphChunk, left);
+    if (st == KMC_OK && hipEventRecord(e0, s->stream) != hipSuccess) st = KMC_ERR_HIP;
+    for (int64_t r = 0; r < gens / kGraphChunk && st == KMC_OK; ++r) st = graph_chunk(s, left);
+    if (st == KMC_OK && hipEventRecord(e1, s->stream) != hipSuccess) st = KMC_ERR_HIP;
+    if (with_updated) { for (int64_t r = 0; r < gens / s->uchunk && st == KMC_OK && s->launch_mode == 0; ++r) st = updated_chunk(s, left); }
+    else if (st == KMC_OK) st = eager_generations(s, gens, left);
+    if (st == KMC_OK && hipEventRecord(e2, s->stream) != hipSuccess) st = KMC_ERR_HIP;
+    float tg = 0.f, tu = 0.f;
+    if (st == KMC_OK && (hipEventSynchronize(e2) != hipSuccess || hipEventElapsedTime(&tg, e0, e1) != hipSuccess ||
+                         hipEventElapsedTime(&tu, e1, e2) != hipSuccess)) st = KMC_ERR_HIP;
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
+    if (st != KMC_OK) return st == KMC_ERR_HIP ? fail(st, "launch-mode calibration failed") : st;
+    if (s->launch_mode == 0) {
+        s->launch_mode = tu < 0.98f * tg ? (with_updated ? 3 : 2) : 1;        // the alternative must win clearly
+        s->calib_graph_ms = tg * (float)kGraphChunk / (float)gens; s->calib_eager_ms = tu * (float)kGraphChunk / (float)gens;
+    }
+    return KMC_OK;
+}
+
+// KMC_LAUNCH, read at every kmc_sampler_run (the tests set it between calls)
+enum class LaunchEnv { none, graph, eager, updated, updated_budget };
+LaunchEnv launch_env()
+{
+    static const char* const names[] = {"graph", "eager", "updated", "updated,budget"};        // (in the enum's order; anything else: none)
+    const char* const e = std::getenv("KMC_LAUNCH");
+    for (int i = 0; e && i < 4; ++i)
+        if (std::strcmp(e, names[i]) == 0) return (LaunchEnv)(i + 1);
+    return LaunchEnv::none;
+}
+
+// How to issue the launches?  Same kernels, same results, three ways:
+//   1 table graph   -- hipGraph replay; the kernels read their generation from a device table (one scalar round
+//                      trip in front of Philox: C2 4.32 us per half-step); the host is free after ~16 ms per 10^4
+//                      generations;
+//   2 eager         -- the step travels among the preloaded kernel parameters, Philox starts at wave entry (C2 4.03 us)
+//                      -- as long as the host launches as fast as the GPU drains, which it does not reliably (three
+//                      bench runs: 8.7, 6.5, 8.6 x 10^9 walker-steps/s; C3 3.7-4.8 us against 3.25);
+//   3 updated graph -- the eager form of the kernels inside a graph whose node parameters are rewritten before
+//                      every replay (C2 4.00 us, C3 3.25 us; steady).  But hipGraphExecKernelNodeSetParams keeps host
+//                      memory per call inside the runtime -- ~80 bytes in HIP 7.0 (1.6 MB per 10^4 generations, not returned
+//                      when the executables are destroyed), ~1.4 in 7.2: update_bytes_each, kmc_updated.hip -- so the process has a BUDGET
+//                      of such calls (kmc_set_updated_budget_mb): beyond it samplers choose
+//                      between 1 and 2.
+// A long run (>= 896 generations) measures 1 against 3 (or 2) once -- 256 generations each, HIP events: a starved GPU shows as idle time
+// between the events -- and keeps the faster; KMC_LAUNCH=graph|eager|updated decides without measuring.
+// This sampler's launch mode, where a graph is in use and nothing is decided yet (the measurement runs its generations off `*left`).
+kmc_status decide_launch_mode(kmc_sampler* s, LaunchEnv env, bool use_graph, int64_t* left)
+{
+    // The measurement and the updated graph's set-up (six executables of 128 or 256 nodes) cost about a millisecond once: worth it for a job planned long
+    // (kmc_config::ngenerations) or a sampler that has come this far anyway, not for a one-shot run of a few thousand generations (4 096 x 4, one run of 1 024
+    // generations: 4.3 ms with the measurement, 3.4 ms from the table graph alone; break-even ~2 000 generations at C2, ~10 000 for a short-row ensemble)
+    constexpr int64_t kWorthMeasuring = 4096;
+    const bool long_job = s->cfg.ngenerations >= kWorthMeasuring || s->generation + *left >= kWorthMeasuring;
+    const bool updated_asked = env == LaunchEnv::updated || env == LaunchEnv::updated_budget;
+    if (use_graph && s->launch_mode == 0 && s->user && updated_graph_possible(s) && !s->uexec[0] && (updated_asked || (long_job && *left >= calib_min(s)))) {
+        // module functions as graph kernel nodes: build the graph now; a runtime that refuses leaves this sampler with the table graph
+        if (ensure_updated_graph(s) != KMC_OK) {
+            (void)hipGetLastError();
+            drop_updated_graph(s);
+            s->updated_refused = true;
+        }
+    }
+    if (s->temper && updated_asked) s->temper_updated_fallback = true;    // (said by kmc_sampler_describe: the run below replays the table graph)
+    if (!use_graph || s->launch_mode != 0) return KMC_OK;
+    if (env == LaunchEnv::graph) s->launch_mode = 1;
+    else if (env == LaunchEnv::eager) s->launch_mode = 2;
+    else if (env == LaunchEnv::updated && updated_graph_possible(s)) { s->launch_mode = 3; s->updated_forced = true; }
+    else if (env == LaunchEnv::updated_budget && updated_graph_possible(s) && update_budget_left(s)) s->launch_mode = 3;   // (as if measured: the budget applies)
+    else if (!updated_graph_possible(s)) s->launch_mode = 1;
+    else if (*left >= calib_min(s) && long_job) {
+        const bool room = update_budget_left(s);      // (the measurement itself may overshoot by its six replays; the run after it may not)
+        if (!room) note_budget_spent(s);
+        KMC_TRY(calibrate(s, room, left));
+    }
+    return KMC_OK;
+}
+
+kmc_status run_launches(kmc_sampler* s, int64_t ngen)
+{
+    if (s->fused && s->fused_L > 0 && ngen > 0 && !(s->pos2_current && s->own_pos && !s->pos_exposed)) {
+        // One launch per generation reads one copy of the state and writes the other.  The lane-striped form writes a row to the output copy only when that
+        // copy does not hold it already: the copies are made equal whenever somebody may have changed d_pos / d_logp since the last run (set_positions,
+        // set_state, the initial ball: they write the first pair only; a caller-owned buffer -- kmc_sampler_bind_positions -- may change at any time: every
+        // run); between runs the kernels keep them consistent.  (Launch modes: below, with the two-launch kernels' -- whole chunks start in copy 0.)
+        HIP_TRY(generation_settle(s));         // (a run that failed after an odd number of generations left the newest state in copy 1: bring it home before copy 0 overwrites it)
+        HIP_TRY(hipMemcpyAsync(s->d_pos2, s->d_pos, (size_t)s->nrows * (size_t)s->ld * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_logp2, s->d_logp, (size_t)s->nrows * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        s->pos2_current = true;
+    }
+    int64_t left = ngen;
+    bool use_graph = !(s->cfg.flags & KMC_NO_GRAPH);
+    if (s->comm && !s->comm_graph_ok) use_graph = false;    // (decided at the first capture, kmc_sampler_rccl_capture)
+    KMC_TRY(decide_launch_mode(s, launch_env(), use_graph, &left));
+    while (use_graph && s->launch_mode == 3 && left >= s->uchunk) {
+        if (!s->updated_forced && !update_budget_left(s)) {             // the process has used up its leak budget: decide again, between 1 and 2
+            note_budget_spent(s);
+            s->launch_mode = 0;
+            if (left >= calib_min(s)) KMC_TRY(calibrate(s, false, &left));
+            break;
+        }
+        KMC_TRY(updated_chunk(s, &left));
+    }
+    if (s->launch_mode == 2) use_graph = false;
+    while (use_graph && left >= kGraphChunk) KMC_TRY(graph_chunk(s, &left));
+    KMC_TRY(eager_generations(s, left, &left));
+    if (s->fused) HIP_TRY(generation_settle(s));                        // the state back in d_pos / d_logp (after an odd number of generations)
+    return KMC_OK;
+}
+
 }  // namespace kmc_host
+
 KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
 {
     if (!s || ngen < 0) return fail(KMC_ERR_BAD_ARG, "bad argument");
@@ -643,335 +811,9 @@ KMC_EXPORT kmc_status kmc_sampler_run(kmc_sampler* s, int64_t ngen)
         return fail(KMC_ERR_BAD_ARG, "KMC_STREAM_CHAIN: call kmc_sampler_set_chain_host before kmc_sampler_run");
     HIP_TRY(hipSetDevice(s->cfg.device));
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    if (s->resident) {
-        // the whole ensemble lives in one workgroup's LDS; a launch carries up to 1024 generations, whose draws a wide kernel
-        // computes first (draw_table_fill, kmc_islands.hpp)
-        while (ngen > 0) {
-            int64_t n = std::min<int64_t>(ngen, kDrawTableGens);
-            if (s->stream_chain) n = std::min<int64_t>(n, std::max<int64_t>(1, (s->ring_blk - 1) * s->cfg.nthin));   // a launch fills less than a block of the ring
-            KMC_TRY(chain_before(s, s->generation + n));
-            ResidentArgs ra{};
-            IslandArgs& ia = ra.is;
-            ia.pos = s->d_pos; ia.logp = s->d_logp; ia.naccept = s->d_naccept;
-            ia.nwalkers = s->cfg.nwalkers; ia.permA = 1; ia.permC = 0;
-            ia.gen0 = s->generation; ia.ngen = (int32_t)n;
-            ia.ndim = (int32_t)s->cfg.ndim; ia.ld = (int32_t)s->ld;
-            ia.nburnin = s->cfg.nburnin; ia.nthin = s->cfg.nthin; ia.nsamples = s->nsamples;
-            const HalfStepArgs ha = make_args(s, 0, false, s->generation);
-            ia.dc = ha.dc;                       // nhalf = nwalkers / 2, as in the multi-launch kernels
-            ia.dp = s->dp;
-            ia.msum = s->d_isum; ia.msumsq = s->d_isumsq;
-            ra.S = (int32_t)s->cfg.nwalkers;
-            ra.chain = s->d_chain; ra.chain_logp = s->d_chain_logp;
-            ra.blob = s->d_blob; ra.chain_blob = s->d_chain_blob;
-            ra.ring_slots = s->stream_chain ? s->ring_slots : 0;
-            {                                    // (d_draws: allocated with every resident sampler)
-                DrawTableArgs ta{};
-                const int64_t npad = (n + kDrawBatch - 1) / kDrawBatch * kDrawBatch;      // whole batches (<= kDrawTableGens, a multiple)
-                ta.dc = ia.dc; ta.gen0 = s->generation; ta.ngen = (int32_t)npad; ta.S = ra.S; ta.out = s->d_draws;
-                hipLaunchKernelGGL(draw_table_fill, dim3((unsigned)((npad * ra.S + 255) / 256)), dim3(256), 0, s->stream, ta);
-                HIP_TRY(hipGetLastError());
-                ra.draws = s->d_draws;
-                s->launches += 1;
-            }
-            if (s->user) {
-                HIP_TRY(launch_module(s->uk.resident, 1u, (unsigned)s->resident_tpb, s->stream, ra, (unsigned)s->island_lds));
-            } else {
-                hipLaunchKernelGGL(s->resident_kernel, dim3(1), dim3((unsigned)s->resident_tpb), s->island_lds, s->stream, ra);
-                HIP_TRY(hipGetLastError());
-            }
-            s->generation += n;
-            s->launches += 1;
-            ngen -= n;
-            KMC_TRY(chain_after(s));
-        }
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
-        s->have_run_events = true;
-        return KMC_OK;
-    }
-    if (s->fused && s->fused_L > 0 && ngen > 0 && !(s->pos2_current && s->own_pos && !s->pos_exposed)) {
-        // One launch per generation reads one copy of the state and writes the other.  The lane-striped form writes a row to the output copy only when that
-        // copy does not hold it already: the copies are made equal whenever somebody may have changed d_pos / d_logp since the last run (set_positions,
-        // set_state, the initial ball: they write the first pair only; a caller-owned buffer -- kmc_sampler_bind_positions -- may change at any time: every
-        // run); between runs the kernels keep them consistent.  (Launch modes: below, with the two-launch kernels' -- whole chunks start in copy 0.)
-        HIP_TRY(generation_settle(s));         // (a run that failed after an odd number of generations left the newest state in copy 1: bring it home before copy 0 overwrites it)
-        HIP_TRY(hipMemcpyAsync(s->d_pos2, s->d_pos, (size_t)s->nrows * (size_t)s->ld * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(s->d_logp2, s->d_logp, (size_t)s->nrows * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        s->pos2_current = true;
-    }
-    if (s->islands) {
-        // one launch per epoch (or per piece of one, when a run stops inside an epoch)
-        while (ngen > 0) {
-            const int64_t epoch = s->generation / s->island_gens;
-            const int64_t upto = (epoch + 1) * s->island_gens;
-            const int64_t n = std::min<int64_t>(ngen, upto - s->generation);
-            IslandArgs ia{};
-            ia.pos = s->d_pos; ia.logp = s->d_logp; ia.naccept = s->d_naccept;
-            ia.nwalkers = s->cfg.nwalkers;
-            island_perm(s->cfg.seed, epoch, s->cfg.nwalkers, &ia.permA, &ia.permC);
-            ia.gen0 = s->generation; ia.ngen = (int32_t)n;
-            ia.ndim = (int32_t)s->cfg.ndim; ia.ld = (int32_t)s->ld;
-            ia.nburnin = s->cfg.nburnin; ia.nthin = s->cfg.nthin; ia.nsamples = s->nsamples;
-            const HalfStepArgs ha = make_args(s, 0, false, s->generation);
-            ia.dc = ha.dc;
-            ia.dc.nhalf = (uint32_t)(s->island_size / 2);
-            ia.dp = s->dp;
-            ia.msum = s->d_isum; ia.msumsq = s->d_isumsq;
-            if (s->user) {
-                HIP_TRY(launch_module(s->uk.island, (unsigned)s->nislands, (unsigned)s->island_size, s->stream, ia, (unsigned)s->island_lds));
-            } else {
-                hipLaunchKernelGGL(s->island_kernel, dim3((unsigned)s->nislands), dim3((unsigned)s->island_size), s->island_lds, s->stream, ia);
-                HIP_TRY(hipGetLastError());
-            }
-            s->generation += n;
-            s->launches += 1;
-            ngen -= n;
-        }
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
-        s->have_run_events = true;
-        return KMC_OK;
-    }
-    if (s->data_eval) {
-        // per half-step: PROPOSE (the host route's first pass) -> partial sums -> fold -> ACCEPT, all on the sampler's stream.  A likelihood-tempered
-        // ladder does the same four launches for every rung at once (the rung as the grid's second dimension in PROPOSE and ACCEPT, ntemps h proposals
-        // in one pass of the data kernels -- S does not depend on beta), then the sweep where it has work
-        const int64_t nprop = (int64_t)s->ntemps * s->h;
-        for (; ngen > 0; --ngen) {
-            KMC_TRY(chain_before(s, s->generation + 1));
-            for (int half = 0; half < 2; ++half) {
-                HalfStepArgs a = make_args(s, half, false, s->generation);
-                a.prop_out = s->d_prop;
-                a.prop_ld = (int32_t)s->ld;
-                HIP_TRY(launch_half_kernel(s, a));
-                HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_half, s->d_prop, nprop, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_p1, s->stream, s->temper_like));
-                a.prop_out = nullptr;
-                a.p1_in = s->d_p1;
-                HIP_TRY(launch_half_kernel(s, a));
-                s->launches += 4;
-                if (s->temper && half == 1) {
-                    bool swept = false;
-                    HIP_TRY(launch_temper_sweep(s, a, &swept));
-                    if (swept) s->launches += 1;
-                }
-            }
-            s->generation += 1;
-            KMC_TRY(chain_after(s));
-        }
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
-        s->have_run_events = true;
-        return KMC_OK;
-    }
-    if (s->host_eval) {
-        // per half-step: PROPOSE on the device -> proposals to the host -> callback -> log-pdfs back
-        // -> ACCEPT on the device (which recomputes the same proposals from the same draws)
-        const size_t hh = (size_t)s->h, nd = (size_t)s->cfg.ndim, ld = (size_t)s->ld;
-        // Large batches travel in pieces, each behind its own event: the callback works on piece c while piece c + 1 is still
-        // on the link (the D2H of the proposals is the larger half of a half-step's time once the closure is cheap).  Not when
-        // accept outcomes go back to the host as well: that caller keeps per-batch state (blobs) between the two callbacks.
-        int npiece = (!s->cfg.host_accepted && hh >= 8192) ? 4 : 1;
-        { const long v = debug_opt_long("host-pieces", 0); if (v >= 1 && v <= kHostPieces && !s->cfg.host_accepted) npiece = (int)v; }
-        for (int i = 0; i < npiece && npiece > 1; ++i)
-            if (!s->host_ev[i]) HIP_TRY(hipEventCreateWithFlags(&s->host_ev[i], hipEventDisableTiming));
-        // Small batches (the reference's own sizes) skip the copies: the propose kernel writes the dense proposal rows straight into
-        // the page-locked host array over the link and the accept kernel reads the log-pdfs straight from theirs -- a half-step is
-        // then two launches, one synchronisation and the callback (100 walkers: 32 -> ~15 us with a Python callable).
-        // KMC_DEBUG=host-zerocopy=0|1 forces it off / on.
-        bool zero_copy = npiece == 1 && s->h_prop_dev != nullptr && hh * nd * sizeof(double) <= ((size_t)256 << 10);
-        { std::string e; if (debug_opt("host-zerocopy", &e)) zero_copy = e == "1" && npiece == 1 && s->h_prop_dev != nullptr; }
-        for (; ngen > 0; --ngen) {
-            KMC_TRY(chain_before(s, s->generation + 1));
-            for (int half = 0; half < 2; ++half) {
-                HalfStepArgs a = make_args(s, half, false, s->generation);
-                a.prop_out = zero_copy ? s->h_prop_dev : s->d_prop;
-                a.prop_ld = zero_copy ? (int32_t)nd : (int32_t)ld;
-                HIP_TRY(launch_half_kernel(s, a));
-                bool cb_failed = false;
-                if (zero_copy) {
-                    HIP_TRY(hipStreamSynchronize(s->stream));
-                    cb_failed = s->cfg.host_logpdf(s->h_prop, (int64_t)hh, (int64_t)nd, s->h_p1, s->cfg.host_user) != 0;   // :257
-                } else if (npiece == 1) {
-                    HIP_TRY(hipMemcpy2DAsync(s->h_prop, nd * sizeof(double), s->d_prop, ld * sizeof(double), nd * sizeof(double), hh,
-                                             hipMemcpyDeviceToHost, s->stream));
-                    HIP_TRY(hipStreamSynchronize(s->stream));
-                    cb_failed = s->cfg.host_logpdf(s->h_prop, (int64_t)hh, (int64_t)nd, s->h_p1, s->cfg.host_user) != 0;   // :257
-                } else {
-                    auto r0 = [&](int c) { return hh * (size_t)c / (size_t)npiece; };
-                    for (int c = 0; c < npiece; ++c) {
-                        HIP_TRY(hipMemcpy2DAsync(s->h_prop + r0(c) * nd, nd * sizeof(double), s->d_prop + r0(c) * ld, ld * sizeof(double), nd * sizeof(double),
-                                                 r0(c + 1) - r0(c), hipMemcpyDeviceToHost, s->stream));
-                        HIP_TRY(hipEventRecord(s->host_ev[c], s->stream));
-                    }
-                    for (int c = 0; c < npiece; ++c) {
-                        HIP_TRY(hipEventSynchronize(s->host_ev[c]));
-                        if (!cb_failed)
-                            cb_failed = s->cfg.host_logpdf(s->h_prop + r0(c) * nd, (int64_t)(r0(c + 1) - r0(c)), (int64_t)nd, s->h_p1 + r0(c), s->cfg.host_user) != 0;   // :257
-                    }
-                }
-                if (cb_failed) {
-                    s->positions_set = false;
-                    return fail(KMC_ERR_BAD_ARG, "the host log-pdf callback failed in generation " + std::to_string(s->generation));
-                }
-                if (!zero_copy) HIP_TRY(hipMemcpyAsync(s->d_p1, s->h_p1, hh * sizeof(double), hipMemcpyHostToDevice, s->stream));
-                a.prop_out = nullptr;
-                a.p1_in = zero_copy ? s->h_p1_dev : s->d_p1;
-                a.acc_out = s->d_acc;
-                HIP_TRY(launch_half_kernel(s, a));
-                s->launches += 2;
-                if (s->cfg.host_accepted) {
-                    HIP_TRY(hipMemcpyAsync(s->h_acc, s->d_acc, hh, hipMemcpyDeviceToHost, s->stream));
-                    HIP_TRY(hipStreamSynchronize(s->stream));
-                    const int32_t stored = (a.sched_inline.flags & kSample) != 0 ? 1 : 0;
-                    if (s->cfg.host_accepted(s->h_acc, (int64_t)hh, (int64_t)half * (int64_t)hh, s->generation, stored, s->cfg.host_user) != 0) {
-                        s->positions_set = false;
-                        return fail(KMC_ERR_BAD_ARG, "the host accept callback failed in generation " + std::to_string(s->generation));
-                    }
-                }
-            }
-            s->generation += 1;
-            KMC_TRY(chain_after(s));
-        }
-        HIP_TRY(hipEventRecord(s->ev1, s->stream));
-        s->have_run_events = true;
-        return KMC_OK;
-    }
-    const int64_t lpg = s->fused ? 1 : 2;                    // launches per generation
-    auto eager_generations = [&](int64_t n) -> kmc_status {
-        for (; n > 0; --n, --ngen) {
-            KMC_TRY(chain_before(s, s->generation + 1));
-            if (s->fused) {
-                HIP_TRY(launch_generation(s, s->fused_cur, false, s->generation));
-                s->fused_cur ^= 1;
-            } else {
-                for (int half = 0; half < 2; ++half) KMC_TRY(launch_half(s, half, false, s->generation));
-            }
-            s->generation += 1;
-            s->launches += lpg;
-            if (!s->fused && ++s->gens_since_sweep >= kSweepEvery) HIP_TRY(launch_sweep(s));
-            KMC_TRY(chain_after(s));
-        }
-        return KMC_OK;
-    };
-    auto graph_chunk = [&]() -> kmc_status {
-        if (s->fused) HIP_TRY(generation_settle(s));                    // (a chunk of generation kernels starts in copy 0 and ends there)
-        KMC_TRY(ensure_graph(s));
-        if (!s->graph_exec) return eager_generations(kGraphChunk);      // (RCCL all-gather that cannot be captured)
-        KMC_TRY(sync_device_counter(s));
-        KMC_TRY(chain_before(s, s->generation + kGraphChunk));
-        HIP_TRY(hipGraphLaunch(s->graph_exec, s->stream));
-        if (!s->fused) HIP_TRY(launch_sweep(s));
-        s->generation += kGraphChunk;
-        s->dev_gen += kGraphChunk;
-        s->launches += (lpg + (s->temper ? 1 : 0)) * kGraphChunk;          // (a tempered chunk: the sweep node of every generation)
-        ngen -= kGraphChunk;
-        return chain_after(s);
-    };
-    auto updated_chunk = [&]() -> kmc_status {
-        if (s->fused) HIP_TRY(generation_settle(s));
-        KMC_TRY(chain_before(s, s->generation + s->uchunk));
-        bool launched = false;
-        if (launch_updated_graph(s, &launched) != KMC_OK) {
-            // this sampler uses the table graph from here on (the loops below go on with graph_chunk while a whole chunk is
-            // left, eagerly after that: exactly the generations asked for).  Failed before the replay was enqueued: nothing
-            // ran, nothing to account.  Failed after it (the event of this executable): the replay is running -- account
-            // it; without its event the executable is not reused, which leaving this mode guarantees.
-            s->launch_mode = 1;
-            if (debug_opt("feed-stats")) std::fprintf(stderr, "[kissmcmc_hip] the updated-graph replay failed (%s): table graph from here on\n", kmc_last_error());
-            if (!launched) return KMC_OK;
-            HIP_TRY(hipStreamSynchronize(s->stream));
-        }
-        if (!s->fused) HIP_TRY(launch_sweep(s));
-        s->generation += s->uchunk;
-        s->launches += lpg * s->uchunk;
-        ngen -= s->uchunk;
-        return chain_after(s);
-    };
-    // How to issue the launches?  Same kernels, same results, three ways:
-    //   1 table graph   -- hipGraph replay; the kernels read their generation from a device table (one scalar round
-    //                      trip in front of Philox: C2 4.32 us per half-step); the host is free after ~16 ms per 10^4
-    //                      generations;
-    //   2 eager         -- the step travels among the preloaded kernel parameters, Philox starts at wave entry (C2 4.03 us)
-    //                      -- as long as the host launches as fast as the GPU drains, which it does not reliably (three
-    //                      bench runs: 8.7, 6.5, 8.6 x 10^9 walker-steps/s; C3 3.7-4.8 us against 3.25);
-    //   3 updated graph -- the eager form of the kernels inside a graph whose node parameters are rewritten before
-    //                      every replay (C2 4.00 us, C3 3.25 us; steady).  But hipGraphExecKernelNodeSetParams keeps host
-    //                      memory per call inside the runtime -- ~80 bytes in HIP 7.0 (1.6 MB per 10^4 generations, not returned
-    //                      when the executables are destroyed), ~1.4 in 7.2: update_bytes_each above -- so the process has a BUDGET
-    //                      of such calls (kmc_set_updated_budget_mb): beyond it samplers choose
-    //                      between 1 and 2.
-    // A long run (>= 896 generations) measures 1 against 3 (or 2) once -- 256 generations each, HIP events: a starved GPU shows as idle time
-    // between the events -- and keeps the faster; KMC_LAUNCH=graph|eager|updated decides without measuring.
-    bool use_graph = !(s->cfg.flags & KMC_NO_GRAPH);
-    if (s->comm && !s->comm_graph_ok) use_graph = false;    // (decided at the first capture, kmc_sampler_rccl_capture)
-    const int64_t calib_gens = std::max<int64_t>(4 * kGraphChunk, 2 * s->uchunk);                               // generations measured in each mode
-    const int64_t calib_min = kGraphChunk + 2 * std::max<int64_t>(kGraphChunk, s->uchunk) + 2 * calib_gens + kGraphChunk;    // warm-up pieces + both measurements + a chunk to spare (896)
-    auto calibrate = [&](bool with_updated) -> kmc_status {
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventCreate(&e2));
-        const int64_t gens = calib_gens;
-        kmc_status st = graph_chunk();                                    // warm: instantiation, code objects
-        if (st == KMC_OK) st = with_updated ? updated_chunk() : eager_generations(kGraphChunk);
-        if (st == KMC_OK) st = with_updated ? updated_chunk() : eager_generations(kGraphChunk);
-        if (st == KMC_OK && hipEventRecord(e0, s->stream) != hipSuccess) st = KMC_ERR_HIP;
-        for (int64_t r = 0; r < gens / kGraphChunk && st == KMC_OK; ++r) st = graph_chunk();
-        if (st == KMC_OK && hipEventRecord(e1, s->stream) != hipSuccess) st = KMC_ERR_HIP;
-        if (with_updated) { for (int64_t r = 0; r < gens / s->uchunk && st == KMC_OK && s->launch_mode == 0; ++r) st = updated_chunk(); }
-        else if (st == KMC_OK) st = eager_generations(gens);
-        if (st == KMC_OK && hipEventRecord(e2, s->stream) != hipSuccess) st = KMC_ERR_HIP;
-        float tg = 0.f, tu = 0.f;
-        if (st == KMC_OK && (hipEventSynchronize(e2) != hipSuccess || hipEventElapsedTime(&tg, e0, e1) != hipSuccess ||
-                             hipEventElapsedTime(&tu, e1, e2) != hipSuccess)) st = KMC_ERR_HIP;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
-        if (st != KMC_OK) return st == KMC_ERR_HIP ? fail(st, "launch-mode calibration failed") : st;
-        if (s->launch_mode == 0) {
-            s->launch_mode = tu < 0.98f * tg ? (with_updated ? 3 : 2) : 1;        // the alternative must win clearly
-            s->calib_graph_ms = tg * (float)kGraphChunk / (float)gens; s->calib_eager_ms = tu * (float)kGraphChunk / (float)gens;
-        }
-        return KMC_OK;
-    };
-    // The measurement and the updated graph's set-up (six executables of 128 or 256 nodes) cost about a millisecond once: worth it for a job planned long
-    // (kmc_config::ngenerations) or a sampler that has come this far anyway, not for a one-shot run of a few thousand generations (4 096 x 4, one run of 1 024
-    // generations: 4.3 ms with the measurement, 3.4 ms from the table graph alone; break-even ~2 000 generations at C2, ~10 000 for a short-row ensemble)
-    constexpr int64_t kWorthMeasuring = 4096;
-    const bool long_job = s->cfg.ngenerations >= kWorthMeasuring || s->generation + ngen >= kWorthMeasuring;
-    const char* const launch_env = std::getenv("KMC_LAUNCH");
-    const bool updated_asked = launch_env && (std::strcmp(launch_env, "updated") == 0 || std::strcmp(launch_env, "updated,budget") == 0);
-    if (use_graph && s->launch_mode == 0 && s->user && updated_graph_possible(s) && !s->uexec[0] && (updated_asked || (long_job && ngen >= calib_min))) {
-        // module functions as graph kernel nodes: build the graph now; a runtime that refuses leaves this sampler with the table graph
-        if (ensure_updated_graph(s) != KMC_OK) {
-            (void)hipGetLastError();
-            drop_updated_graph(s);
-            s->updated_refused = true;
-        }
-    }
-    if (s->temper && updated_asked) s->temper_updated_fallback = true;    // (said by kmc_sampler_describe: the run below replays the table graph)
-    if (use_graph && s->launch_mode == 0) {
-        const char* env = std::getenv("KMC_LAUNCH");
-        if (env && std::strcmp(env, "graph") == 0) s->launch_mode = 1;
-        else if (env && std::strcmp(env, "eager") == 0) s->launch_mode = 2;
-        else if (env && std::strcmp(env, "updated") == 0 && updated_graph_possible(s)) { s->launch_mode = 3; s->updated_forced = true; }
-        else if (env && std::strcmp(env, "updated,budget") == 0 && updated_graph_possible(s) && update_budget_left(lpg * s->uchunk)) s->launch_mode = 3;   // (as if measured: the budget applies)
-        else if (!updated_graph_possible(s)) s->launch_mode = 1;
-        else if (ngen >= calib_min && long_job) {
-            const bool left = update_budget_left(lpg * s->uchunk);      // (the measurement itself may overshoot by its six replays; the run after it may not)
-            if (!left) note_budget_spent(s);
-            KMC_TRY(calibrate(left));
-        }
-    }
-    while (use_graph && s->launch_mode == 3 && ngen >= s->uchunk) {
-        if (!s->updated_forced && !update_budget_left(lpg * s->uchunk)) {             // the process has used up its leak budget: decide again, between 1 and 2
-            note_budget_spent(s);
-            s->launch_mode = 0;
-            if (ngen >= calib_min) KMC_TRY(calibrate(false));
-            break;
-        }
-        KMC_TRY(updated_chunk());
-    }
-    if (s->launch_mode == 2) use_graph = false;
-    while (use_graph && ngen >= kGraphChunk) KMC_TRY(graph_chunk());
-    KMC_TRY(eager_generations(ngen));
-    if (s->fused) HIP_TRY(generation_settle(s));                        // the state back in d_pos / d_logp (after an odd number of generations)
+    const kmc_status st = s->resident ? run_resident(s, ngen) : s->islands ? run_islands(s, ngen) : s->data_eval ? run_data(s, ngen) :
+                          s->host_eval ? run_host(s, ngen) : run_launches(s, ngen);
+    KMC_TRY(st);
     HIP_TRY(hipEventRecord(s->ev1, s->stream));
     s->have_run_events = true;
     return KMC_OK;
@@ -1033,15 +875,3 @@ KMC_EXPORT int kmc_sampler_launch_mode(const kmc_sampler* s, int* budget_fallbac
     if ((s->cfg.flags & KMC_NO_GRAPH) || (s->comm && !s->comm_graph_ok)) return KMC_LAUNCH_EAGER;
     return s->launch_mode;
 }
-
-KMC_EXPORT void kmc_updated_budget(int64_t* calls_used, int64_t* calls_budget)
-{
-    if (calls_used) *calls_used = g_update_calls.load(std::memory_order_relaxed);
-    if (calls_budget) *calls_budget = update_budget().load(std::memory_order_relaxed);
-}
-
-KMC_EXPORT void kmc_set_updated_budget_mb(double mb)
-{
-    update_budget().store(mb <= 0.0 ? 0 : (int64_t)(mb * 1048576.0 / update_bytes_each()), std::memory_order_relaxed);
-}
-

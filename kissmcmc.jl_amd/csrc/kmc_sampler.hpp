@@ -1,5 +1,5 @@
 // kmc_sampler.hpp -- what the sampler's translation units share (kmc_sampler.hip: lifecycle; kmc_launch.hip: the generation
-// loop; kmc_state.hip: state in and out; kmc_copy.hip: copies and the chain ring; kmc_rtc.hip: runtime-compiled densities;
+// loop; kmc_updated.hip: its updated-graph launch mode; kmc_state.hip: state in and out; kmc_copy.hip: copies and the chain ring; kmc_rtc.hip: runtime-compiled densities;
 // kmc_p2p.hip: multi-GPU wiring; kmc_diag.hip: diagnostics): the handle behind kmc_sampler* and the internal entry points
 // that cross those files.  Internal.
 #pragma once
@@ -235,6 +235,9 @@ inline int64_t samples_done(const kmc_sampler* s)
     return k < s->nsamples ? k : s->nsamples;
 }
 
+// launches (graph nodes) per generation of the multi-launch kernels: the two half-steps, or one generation kernel
+inline int64_t launches_per_generation(const kmc_sampler* s) { return s->fused ? 1 : 2; }
+
 // kmc_plan.hip
 Plan make_plan(const kmc_config& c, int64_t n_active);
 bool resident_lane_wanted(int64_t ndim);
@@ -246,6 +249,20 @@ void deal_perm(uint64_t seed, int64_t epoch, int32_t rank, int64_t S, int64_t* A
 // kmc_launch.hip
 kmc_status ensure_graph(kmc_sampler* s);                 // capture + instantiate the table-graph chunk (no-op when it exists)
 kmc_status flush_moments_now(kmc_sampler* s);            // credit every walker's current value with the samples it stood for
+kmc_status unfuse(kmc_sampler* s);                       // back to the two-launch kernels, in place
+kmc::DrawConsts draw_consts(const kmc_sampler* s);       // the draws' constants: the same in every kernel's arguments
+kmc::HalfStepArgs make_args(const kmc_sampler* s, int half, bool graph_mode, int64_t gen_offset);
+kmc::HalfStepFront front_of(const kmc::HalfStepArgs& a, bool ragged_vec);
+kmc::GenerationArgs make_generation_args(const kmc_sampler* s, int from, bool graph_mode, int64_t gen_offset);
+kmc::GenerationFront generation_front_of(const kmc::GenerationArgs& a, int tpb);
+
+// kmc_updated.hip
+bool updated_graph_possible(const kmc_sampler* s);
+kmc_status ensure_updated_graph(kmc_sampler* s);         // the template graph and its executables (no-op when they exist)
+kmc_status launch_updated_graph(kmc_sampler* s, bool* launched);   // one replay of s->uchunk generations from s->generation on
+void drop_updated_graph(kmc_sampler* s);                 // the executables, their events and the template graph
+bool update_budget_left(const kmc_sampler* s);           // the process-wide budget of parameter updates has room for one more replay
+void note_budget_spent(kmc_sampler* s);
 
 // kmc_copy.hip
 hipError_t upload_rows(const kmc_sampler* s, double* dst_dev, const double* src_host, size_t rows);
@@ -259,8 +276,6 @@ void chain_unregister(kmc_sampler* s);
 kmc_status load_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged, UserKernels* uk,
                      int resident_K = 0, bool resident_ragged = false, int island_S = 0, bool f32 = false, int64_t ndim = 0, bool p2p = false,
                      int generation_nd = 0, int move = 0);
-void drop_updated_graph(kmc_sampler* s);                               // the updated-graph mode's executables, events and template graph (kmc_launch.hip)
-kmc_status unfuse(kmc_sampler* s);                                     // back to the two-launch kernels, in place (kmc_launch.hip)
 void set_offline_compiler_hint(bool wanted);                          // runtime-compiled kernels of this thread: hipcc as a child process instead of hiprtc (kmc_rtc.hip)
 bool body_vec_possible(const kmc_user_density* ud, int64_t ndim);     // a function body inside the vector kernels, evaluated per walker (kmc_rtc.hip)
 

@@ -51,7 +51,7 @@ def run(kmc, pdf, th, G, nburn=0, nthin=1, seed=11, **kw):
         ch, cl = s.chain()
         m = s.moments()
         return dict(pos=s.positions(), logp=s.logp(), nacc=s.naccept(), chain=ch, chain_logp=cl, sum=m[0], sumsq=m[1], n=m[2], desc=desc,
-                    mode=s.launch_mode())
+                    mode=s.launch_mode(), launches=s.launch_count)
 
 
 def assert_same(got, want, moments=True):
@@ -80,6 +80,7 @@ def test_regression_is_bit_identical_to_the_host_route(kmc, nw, nd, ndata):
     got, want = run(kmc, dd, th, G, 5, 2), run(kmc, host, th, G, 5, 2)
     assert "data density" in got["desc"]
     assert got["mode"] == want["mode"]            # reported as the host route is
+    assert got["launches"] == 8 * G               # per half-step: PROPOSE, partial sums, fold, ACCEPT
     assert_same(got, want)
     assert got["nacc"].sum() > 0
     # the stateless evaluation (make_theta0s' pdf(theta)) is the same value as the sampler's

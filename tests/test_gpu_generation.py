@@ -135,8 +135,10 @@ def test_stepping_by_halves_takes_the_two_launch_kernels_in_place(kmc, oracle):
             s.set_positions(th)
             s.run(41)
             for _ in range(9):
-                s.half_step(0)
-                s.half_step(1)
+                for half in (0, 1):
+                    before = s.launch_count
+                    s.half_step(half)
+                    assert s.launch_count == before + 1
             assert "one launch per generation" not in s.describe()
             s.run(G - 50)
             s.sync()

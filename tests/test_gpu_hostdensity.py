@@ -18,6 +18,7 @@ def _run(kmc, pdf, th, G, nburn, nthin, seed):
         s.run(G // 2)
         s.run(G - G // 2)
         s.sync()
+        assert s.launch_count == 4 * G          # PROPOSE and ACCEPT per half-step
         ch, cl = s.chain()
         m = s.moments()
         return dict(pos=s.positions(), logp=s.logp(), nacc=s.naccept(), chain=ch, chain_logp=cl, sum=m[0], sumsq=m[1],

@@ -19,6 +19,11 @@ def _run(kmc, pdf, th, G, nburn, nthin, seed, k):
                     ms=s.last_run_ms(), launches=s.launch_count)
 
 
+def _epochs_touched(g, n, k):
+    """launches of a run(n) from generation g: one per epoch of k generations that [g, g + n) touches"""
+    return (g + n - 1) // k - g // k + 1 if n > 0 else 0
+
+
 CASES = [
     ("gauss", 512, 32, 70, 20, 1, 16),
     ("gauss", 1024, 32, 45, 10, 2, 7),       # epochs that do not divide the run
@@ -54,6 +59,7 @@ def test_island_mode_matches_island_oracle(kmc, oracle, name, nw, nd, G, nburn, 
     cfg = oracle.make_config(did, params, nw, nd, G, nburn, nthin, 2.0, 31, nthreads=4)
     ref = oracle.emcee_islands(cfg, 256, k, th)
     assert ref["status"] == 0
+    assert got["launches"] == _epochs_touched(0, G, k)
     np.testing.assert_array_equal(got["nacc"], ref["naccept"])
     np.testing.assert_array_equal(got["pos"], ref["final_pos"])
     assert np.all(np.abs(got["logp"] - ref["final_logp"]) <= 1e-12 * np.maximum(1.0, np.abs(ref["final_logp"])))
@@ -67,8 +73,12 @@ def test_island_mode_pieces_equal_one_run(kmc):
     a = _run(kmc, kmc.GaussianIso(), th, 64, 16, 1, 5, 16)
     with kmc.Sampler(kmc.GaussianIso(), 1024, 32, 64, 16, 1, 2.0, 5, moments=True, island_gens=16) as s:
         s.set_positions(th)
+        g = want = 0
         for n in (5, 11, 1, 30, 17):
             s.run(n)
+            want += _epochs_touched(g, n, 16)
+            g += n
+            assert s.launch_count == want                 # (a run that stops inside an epoch launches the rest of it at the next call)
         s.sync()
         np.testing.assert_array_equal(s.positions(), a["pos"])
         np.testing.assert_array_equal(s.naccept(), a["nacc"])

@@ -291,6 +291,8 @@ def test_launch_modes_are_the_same_sampler(kmc, oracle, mode, monkeypatch):
         chain, clogp = s.chain()
         msum, msq, n = s.moments()
         how = s.describe()
+        launches, (launch_mode, _) = s.launch_count, s.launch_mode()
+        code = {name: k for k, name in s.LAUNCH_MODES.items()}          # KMC_LAUNCH_* of include/kissmcmc_hip.h, as the package names them
     ref = oracle.emcee(oracle.make_config(oracle.GAUSSIAN_ISO, [0.0, 1.0], nw, nd, G, nburn, nthin, 2.0, seed, nthreads=8), th)
     np.testing.assert_array_equal(nacc, ref["naccept"])
     np.testing.assert_array_equal(pos, ref["final_pos"])
@@ -298,6 +300,10 @@ def test_launch_modes_are_the_same_sampler(kmc, oracle, mode, monkeypatch):
     assert n == ref["nmoment"]
     np.testing.assert_allclose(msum, ref["sum"], rtol=1e-11, atol=1e-9)
     np.testing.assert_allclose(msq, ref["sumsq"], rtol=1e-11, atol=1e-9)
+    assert launches == 2 * G                           # two half-steps per generation, however they are issued (replayed, updated, eager, measured)
+    decided = {"graph": [code["table graph"]], "eager": [code["eager"]], "updated": [code["updated graph"]],
+               None: [code["table graph"], code["eager"], code["updated graph"]]}[mode]
+    assert launch_mode in decided, (launch_mode, how)
     if mode == "updated":
         assert "parameter updates" in how
     if mode is None:
@@ -345,6 +351,7 @@ def test_updated_graph_budget_fallbacks_are_the_same_sampler(kmc, oracle, when, 
             how = s.describe()
             mode, fell_back = s.launch_mode()
             assert s.generation == G
+            assert s.launch_count == 2 * G             # (the replays before the budget ran out, the measurement after it, the table graph, the eager tail)
     finally:
         L.kmc_set_updated_budget_mb(budget.value * each / 1048576.0 + 1e-9)
     assert fell_back and mode in (0, 1, 2), (mode, fell_back, how)

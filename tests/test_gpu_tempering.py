@@ -40,7 +40,7 @@ def run(kmc, pdf, th, betas, G, nburn=0, nthin=1, seed=11, move=None, swap_every
         ch, cl = s.chain()
         return dict(pos=s.rung_positions(), logp=s.rung_logp(), nacc=s.rung_naccept(), nswap=s.nswap().astype(np.int64), chain=ch,
                     chain_logp=cl, logp_sum=s.rung_logp_sum(), pos0=s.positions(), logp0=s.logp(), nacc0=s.naccept(), desc=s.describe(),
-                    rates=s.swap_rates(), attempts=s.swap_attempts())
+                    rates=s.swap_rates(), attempts=s.swap_attempts(), launches=s.launch_count)
 
 
 def assert_matches(got, want):
@@ -195,10 +195,20 @@ def c2ish():
 @pytest.mark.parametrize("mv", ["stretch", "de", "mix"])
 def test_launch_paths_agree(kmc, monkeypatch, c2ish, mv):
     res = {}
+    G, nburn, nthin, swap_every = 150, 10, 3, 3
     for mode in ("graph", "eager", "updated"):
         monkeypatch.setenv("KMC_LAUNCH", mode)
-        res[mode] = run(kmc, kmc.GaussianIso(), c2ish[:2048], LADDERS[5], 150, nburn=10, nthin=3, seed=3, move=moves(kmc, mv)[0], swap_every=3, pieces=1)
+        res[mode] = run(kmc, kmc.GaussianIso(), c2ish[:2048], LADDERS[5], G, nburn=nburn, nthin=nthin, seed=3, move=moves(kmc, mv)[0], swap_every=swap_every, pieces=1)
     monkeypatch.delenv("KMC_LAUNCH")
+    # launches: a replayed chunk of 64 generations has the sweep node in every generation (3 per generation); a generation launched eagerly has its two
+    # half-steps and the sweep only where it has work -- a sample to store (the schedule's rule) or an exchange
+    nsamples = (G - nburn) // nthin
+    stores = lambda g: g + 1 - nburn > 0 and (g + 1 - nburn) % nthin == 0 and (g + 1 - nburn) // nthin - 1 < nsamples
+    eagerly = lambda g0: sum(2 + (stores(g) or (g + 1) % swap_every == 0) for g in range(g0, G))
+    replayed = G // 64 * 64
+    assert res["eager"]["launches"] == eagerly(0)
+    assert res["graph"]["launches"] == 3 * replayed + eagerly(replayed)
+    assert res["updated"]["launches"] == res["graph"]["launches"]          # (a ladder falls back to the table graph)
     assert "half_step_temper_vec" in res["graph"]["desc"]
     assert_identical(res["graph"], res["eager"])
     assert_identical(res["graph"], res["updated"])

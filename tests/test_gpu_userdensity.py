@@ -398,7 +398,7 @@ def test_body_density_with_blobs_runs_resident(kmc):
         s.set_positions(th)
         s.run(1000)
         s.sync()
-        assert "resident mode" in s.describe() and s.launch_count <= 2        # (the draw table's kernel + the resident one)
+        assert "resident mode" in s.describe() and s.launch_count == 2 * -(-1000 // 1024)        # (the draw table's kernel + the resident one, per 1024 generations of the run)
         chain, clogp = s.chain()
         blobs = s.blobs(by_walker=False)
         cur, pos, lp = s.current_blobs(), s.positions(), s.logp()
