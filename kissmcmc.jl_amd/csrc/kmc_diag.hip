@@ -75,17 +75,18 @@ void kmc_host::reinstall_abort_backtrace()
 namespace kmc_host {
 void check_guards(kmc_sampler* s)
 {
-    std::vector<unsigned char> h(kGuardBytes);
-    for (const auto& g : s->guards) {
-        if (copy_sync(h.data(), g.first, kGuardBytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) { (void)hipGetLastError(); continue; }
+    std::vector<unsigned char> h;
+    for (const DevAlloc& a : s->allocs) {
+        if (!a.guarded) continue;
+        h.resize(kGuardBytes);
+        if (copy_sync(h.data(), static_cast<const char*>(a.p) + a.bytes, kGuardBytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) { (void)hipGetLastError(); continue; }
         for (size_t i = 0; i < kGuardBytes; ++i)
             if (h[i] != 0xA5) {
-                std::fprintf(stderr, "[kissmcmc_hip] KMC_DEBUG=poison: byte %zu behind a device allocation of %zu bytes was overwritten (%s)\n", i, g.second,
+                std::fprintf(stderr, "[kissmcmc_hip] KMC_DEBUG=poison: byte %zu behind a device allocation of %zu bytes was overwritten (%s)\n", i, a.bytes,
                              s->plan.vec ? "vec kernels" : "generic / staged kernels");
                 std::abort();
             }
     }
-    s->guards.clear();
 }
 // ---- the allocation cache (kmc_host.hpp) ----------------------------------------------------------------------------
 namespace {

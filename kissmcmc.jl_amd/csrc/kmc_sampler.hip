@@ -1,6 +1,8 @@
 // kmc_sampler.hip -- the sampler's lifecycle behind the C ABI (include/kissmcmc_hip.h): validation of a configuration
 // (the reference's asserts, src/samplers.jl:200-205), creation / destruction of the device state of the `emcee` front-end
 // (src/samplers.jl:188-216), and the description of how a sampler executes.  Kernel tables and the launch plan per ndim are kmc_plan.hip.
+// kmc_sampler_create runs named steps: init_shape; the route (setup_islands, setup_user_density / setup_menu_resident, setup_generation,
+// setup_launch_geometry); the device state (alloc_*).  Every execution route of the library is decided there and nowhere else.
 // The generation loop (src/samplers.jl:232-293) is kmc_launch.hip; state in and out is kmc_state.hip; copies and the chain
 // ring are kmc_copy.hip; runtime-compiled densities kmc_rtc.hip; multi-GPU wiring kmc_p2p.hip; diagnostics kmc_diag.hip.
 #include <algorithm>
@@ -45,6 +47,25 @@ KMC_EXPORT const char* kmc_status_string(kmc_status st)
     }
     return "unknown status";
 }
+
+namespace {
+// dynamic LDS a workgroup of the resident and island kernels may ask for (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
+constexpr size_t kResidentLdsMax = 156 * 1024;
+
+// The own-stream moves and the tempered ladder run the two-launch kernels on one GPU with double rows: what a configuration has that
+// they cannot take (nullptr: nothing), in the words of their refusals.  P: the shard count.
+const char* not_on_one_gpu_with_double_rows(const kmc_config* c, int P)
+{
+    if (c->flags & KMC_ISLANDS) return "KMC_ISLANDS";
+    if (c->flags & KMC_P2P) return "KMC_P2P";
+    if (P > 1) return "shard_count > 1";
+    if (c->deal_count > 0) return "dealt sub-ensembles (deal_count > 0)";
+    if (c->dtype == KMC_F32) return "KMC_F32";
+    if (c->flags & KMC_STORE_BLOBS) return "KMC_STORE_BLOBS";
+    if (c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) return "a density with blobs";
+    return nullptr;
+}
+}  // namespace
 
 // src/samplers.jl:200-205
 KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
@@ -100,7 +121,7 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
         if ((S != 64 && S != 128 && S != 256) || c->nwalkers % S != 0 || c->ndim > 32 || c->ndim + 2 > S || P != 1 ||
             (c->flags & (KMC_P2P | KMC_STORE_CHAIN | KMC_STORE_LOGP)) || c->island_gens < 0)
             return fail(KMC_ERR_UNSUPPORTED, "KMC_ISLANDS needs island_size in {64,128,256} >= ndim+2 dividing nwalkers, ndim <= 32, one shard and no chain storage");
-        if (c->density == KMC_USER_DENSITY && (size_t)S * (size_t)(2 * c->ndim + 9) * sizeof(double) > 156 * 1024)
+        if (c->density == KMC_USER_DENSITY && (size_t)S * (size_t)(2 * c->ndim + 9) * sizeof(double) > kResidentLdsMax)
             return fail(KMC_ERR_UNSUPPORTED, "KMC_ISLANDS with a user density: island_size * (2 ndim + 9) * 8 must stay below 156 KiB");
     }
     if (c->flags & KMC_STREAM_CHAIN) {
@@ -139,11 +160,7 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
             for (int i = 0; i < c->mix_count; ++i) sum += c->mix_weight[i];
             if (!std::isfinite(sum)) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: the weights' sum must be finite");
         }
-        const char* what = (c->flags & KMC_ISLANDS) ? "KMC_ISLANDS" : (c->flags & KMC_P2P) ? "KMC_P2P" : P > 1 ? "shard_count > 1"
-                         : c->deal_count > 0 ? "dealt sub-ensembles (deal_count > 0)" : c->dtype == KMC_F32 ? "KMC_F32"
-                         : (c->flags & KMC_STORE_BLOBS) ? "KMC_STORE_BLOBS" : nullptr;
-        if (!what && c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) what = "a density with blobs";
-        if (what) return fail(KMC_ERR_UNSUPPORTED, name + ": two launches per generation on one GPU with double rows -- not with " + what);
+        if (const char* what = not_on_one_gpu_with_double_rows(c, P)) return fail(KMC_ERR_UNSUPPORTED, name + ": two launches per generation on one GPU with double rows -- not with " + what);
     }
     {
         const int nb = c->density == KMC_USER_DENSITY && c->user_density ? static_cast<const kmc_user_density*>(c->user_density)->nblob : 0;
@@ -173,10 +190,7 @@ KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
             return fail(KMC_ERR_UNSUPPORTED, "parallel tempering: KMC_TEMPER_LIKELIHOOD needs KMC_DATA_DENSITY (prior + beta * S): nothing says where another density's prior ends");
         const char* what = c->density == KMC_HOST_DENSITY ? "KMC_HOST_DENSITY"
                          : (c->density == KMC_DATA_DENSITY && !like) ? "KMC_DATA_DENSITY in the default temper_mode (temper_mode = KMC_TEMPER_LIKELIHOOD, temper=\"likelihood\", tempers its likelihood)"
-                         : (c->flags & KMC_ISLANDS) ? "KMC_ISLANDS" : (c->flags & KMC_P2P) ? "KMC_P2P" : P > 1 ? "shard_count > 1"
-                         : c->deal_count > 0 ? "dealt sub-ensembles (deal_count > 0)" : c->dtype == KMC_F32 ? "KMC_F32"
-                         : (c->flags & KMC_STORE_BLOBS) ? "KMC_STORE_BLOBS" : nullptr;
-        if (!what && c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) what = "a density with blobs";
+                         : not_on_one_gpu_with_double_rows(c, P);
         if (what) return fail(KMC_ERR_UNSUPPORTED, std::string("parallel tempering (ntemps >= 2): a ladder of ensembles on one GPU with double rows and a device density -- not with ") + what);
     }
     if (c->adapt != 0) {
@@ -219,21 +233,30 @@ KMC_EXPORT double kmc_cdf_g_inv(double u, double a)   // src/samplers.jl:227
 // allocator happened to return.
 // ... and is followed by a 4 KiB guard of 0xA5 that kmc_sampler_destroy checks: a kernel that writes past the end of one of
 // its buffers aborts the process there, with the size of the allocation (the tests then fail loudly).
+// Every buffer handed out is recorded in kmc_sampler::allocs: kmc_sampler_destroy frees that list, so a new buffer needs no line there.
 template <class T>
 hipError_t dev_alloc(kmc_sampler* s, T** p, size_t bytes)
 {
     static const bool poison = debug_opt("poison");
-    if (!poison || bytes == 0) {
-        // (IPC-exported buffers stay plain allocations: a peer maps them by their base address)
-        const hipError_t e0 = (s->cfg.flags & KMC_P2P) ? hipMalloc(reinterpret_cast<void**>(p), bytes) : cache_alloc(reinterpret_cast<void**>(p), bytes);
-        return e0;
+    const bool guarded = poison && bytes != 0;
+    // (IPC-exported buffers stay plain allocations: a peer maps them by their base address)
+    hipError_t e = guarded                       ? hipMalloc(reinterpret_cast<void**>(p), bytes + kGuardBytes)
+                   : (s->cfg.flags & KMC_P2P)    ? hipMalloc(reinterpret_cast<void**>(p), bytes)
+                                                 : cache_alloc(reinterpret_cast<void**>(p), bytes);
+    if (e != hipSuccess || !*p) return e;
+    s->allocs.push_back({*p, bytes, guarded});
+    if (guarded) {
+        e = hipMemsetAsync(*p, 0xFF, bytes, s->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(reinterpret_cast<char*>(*p) + bytes, 0xA5, kGuardBytes, s->stream);
     }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), bytes + kGuardBytes);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(*p, 0xFF, bytes, s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(reinterpret_cast<char*>(*p) + bytes, 0xA5, kGuardBytes, s->stream);
-    s->guards.emplace_back(reinterpret_cast<char*>(*p) + bytes, bytes);
     return e;
+}
+// a buffer of the sampler's goes on its own (kmc_sampler_bind_positions): out of the record, back to the allocator
+static void dev_free(kmc_sampler* s, void* p)
+{
+    auto it = std::find_if(s->allocs.begin(), s->allocs.end(), [p](const DevAlloc& a) { return a.p == p; });
+    if (it != s->allocs.end()) s->allocs.erase(it);
+    cache_free(p);
 }
 
 namespace {
@@ -380,6 +403,552 @@ int generation_wanted(const kmc_sampler* s)
 }
 }  // namespace
 
+// ---- kmc_sampler_create: the steps, in the order they run ----------------------------------------------------------------------------
+namespace {
+// (a step that fails just returns: the sampler under construction is held by this and goes through kmc_sampler_destroy)
+struct SamplerDeleter { void operator()(kmc_sampler* s) const { kmc_sampler_destroy(s); } };
+
+// the copied configuration and what follows from it alone: ladder, shard and half sizes, row stride, sample count, parameter digest, plan
+kmc_status init_shape(kmc_sampler* s, const kmc_config& cfg)
+{
+    s->cfg = cfg;
+    s->user_seed = cfg.seed;
+    s->temper = tempered(cfg);
+    s->ntemps = s->temper ? cfg.ntemps : 1;
+    if (s->temper) s->betas.assign(cfg.betas, cfg.betas + cfg.ntemps);          // (the caller's array is copied here)
+    s->cfg.betas = s->temper ? s->betas.data() : nullptr;
+    s->temper_like = s->temper && cfg.temper_mode == KMC_TEMPER_LIKELIHOOD;
+    s->adapt = s->temper && cfg.adapt != 0;
+    if (s->adapt && s->cfg.adapt_until == 0) s->cfg.adapt_until = cfg.nburnin;
+    for (int j = 1; s->temper && j + 1 < s->ntemps; ++j)                          // (state from here on: never derived from the betas again)
+        s->S0.push_back(std::log(1.0 / s->betas[(size_t)j] - 1.0 / s->betas[(size_t)j - 1]));
+    if (cfg.deal_count > 0) s->cfg.seed = deal_seed(cfg.seed, cfg.deal_rank);    // this sub-ensemble's Philox key
+    if (s->cfg.shard_count <= 0) s->cfg.shard_count = 1;
+    s->h = cfg.nwalkers / 2;
+    s->h_loc = s->h / s->cfg.shard_count;
+    s->active_begin = s->h_loc * s->cfg.shard_rank;
+    s->nlocal = 2 * s->h_loc;
+    s->nsamples = cfg.ngenerations > cfg.nburnin ? (cfg.ngenerations - cfg.nburnin) / cfg.nthin : 0;   // :234
+    s->ld = cfg.ndim + (cfg.ndim & 1);      // whole two-element chunks: 16-byte aligned double rows, 8-byte aligned float rows
+    s->f32 = cfg.dtype == KMC_F32;
+    s->p2p = (cfg.flags & KMC_P2P) != 0;
+    s->nrows = s->p2p ? s->nlocal : cfg.nwalkers;
+    KMC_TRY(digest_params(cfg, &s->dp));
+    s->plan = make_plan(s->cfg, s->h_loc);
+    return KMC_OK;
+}
+
+// ---- resident mode: the whole ensemble in one workgroup's LDS.  One decision for the menu and the runtime-compiled densities ----
+// 16-byte chunks each of a walker's two lanes holds in the pair kernels (resident and island): the smallest power of two K with 2 K >= ld / 2
+int row_chunks_K(int64_t ld)
+{
+    int K = 1;
+    while (2 * K < ld / 2) K *= 2;
+    return K;
+}
+// LDS of n walkers, a pair of lanes per walker: two lanes x 2 (K + 1) doubles of row, and the log-pdf
+size_t pair_lds_bytes(int64_t n, int K) { return ((size_t)n * (size_t)(4 * (K + 1)) + (size_t)n) * sizeof(double); }
+// ... one or two walkers per thread: rows of nd | 1 doubles, and the log-pdf
+size_t lane_lds_bytes(int64_t n, int64_t nd) { return ((size_t)n * (size_t)((nd | 1) + 1)) * sizeof(double); }
+
+struct ResidentChoice {
+    enum Kind { None, Pair, Lane, Lane2 };   // not resident; a pair of lanes per walker; one walker per thread; two walkers per thread
+    Kind kind = None;
+    int K = 0;             // row_chunks_K(ld), whatever the kind: the moment sums are sized by it
+    int tpb = 256;         // threads of the one workgroup
+    size_t lds = 0;        // bytes its rows take (the callers round up: the moment reduction reuses the buffer)
+};
+// what differs between the callers
+struct ResidentFacts {
+    bool body;             // a function body: one walker per thread at any row length (kmc_islands.hpp: resident_lane_body), its registers hold the proposal
+    bool blobs;
+    bool f32;              // float rows: the one-walker-per-thread kernels only -- their LDS rows are double either way
+    bool has_pair;         // the density has a pair kernel for these rows
+    int64_t pair_max;      // ... for ensembles up to this size
+};
+
+// whatever the density: what keeps an ensemble out of resident mode
+bool resident_possible(const kmc_config& c)
+{
+    return c.ndim <= 32 && c.shard_count == 1 && !(c.flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && !two_launch_only(c) && !debug_opt("no-resident");
+}
+
+ResidentChoice choose_resident(const kmc_config& c, int64_t ld, const ResidentFacts& f)
+{
+    ResidentChoice r;
+    const int64_t n = c.nwalkers;
+    if (n > 1024) {                  // 1026 .. 2048 walkers: two walkers per thread (kmc_islands.hpp: resident_lane2_body; short double rows, no blobs), as LDS allows
+        if (n > 2048 || f.f32 || c.ndim > 8 || f.blobs || !resident_lane_wanted(c.ndim)) return r;
+        r.kind = ResidentChoice::Lane2;
+        r.tpb = (int)((n / 2 + 63) / 64 * 64);
+        r.lds = lane_lds_bytes(n, lane_nd(c.ndim));
+    } else if (f.body || resident_lane_wanted(c.ndim)) {      // short rows: one walker per thread (measured faster up to ndim 8)
+        r.kind = ResidentChoice::Lane;
+        r.tpb = (int)((n + 63) / 64 * 64);
+        r.lds = lane_lds_bytes(n, lane_nd(c.ndim));
+    } else if (f.has_pair && n <= f.pair_max) {
+        r.kind = ResidentChoice::Pair;
+        r.tpb = n <= 256 ? 256 : (n <= 512 ? 512 : 1024);
+        r.lds = pair_lds_bytes(n, row_chunks_K(ld));
+    }
+    if (r.lds > kResidentLdsMax) return ResidentChoice{};
+    if (r.kind != ResidentChoice::None) r.K = row_chunks_K(ld);
+    return r;
+}
+
+void set_resident(kmc_sampler* s, const ResidentChoice& r, size_t lds)
+{
+    s->resident = true;
+    s->island_K = r.K;
+    s->nislands = 1;
+    s->island_lds = lds;
+    s->resident_lane = r.kind != ResidentChoice::Pair;
+    s->resident_lane2 = r.kind == ResidentChoice::Lane2;
+    s->resident_tpb = r.tpb;
+}
+
+// a menu density: the kernel comes from the tables; one that is missing, or that the runtime will not give the LDS, leaves the
+// ensemble to the launches per generation
+void setup_menu_resident(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    if (!resident_possible(c)) return;
+    const ResidentChoice r = choose_resident(c, s->ld, ResidentFacts{false, false, s->f32, !s->f32, 1024});
+    if (r.kind == ResidentChoice::None) return;
+    const ResidentFn rf = with_density(c.density, ResidentFn(nullptr), [&](auto d) {
+        using D = decltype(d);
+        return r.kind == ResidentChoice::Lane2 ? resident_lane2_lookup<D>((int)c.ndim)
+               : r.kind == ResidentChoice::Lane ? resident_lane_lookup<D>((int)c.ndim, s->f32)
+                                                : resident_lookup<D>(r.tpb, r.K, 4 * r.K != c.ndim);
+    });
+    if (!rf) return;
+    const size_t lds = std::max<size_t>(r.lds, 8192);           // the moment reduction reuses the buffer
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    set_resident(s, r, lds);
+    s->resident_kernel = rf;
+}
+
+// ---- island mode (KMC_ISLANDS): every island field; a menu density's kernel (a runtime-compiled one's comes with its module) ----
+kmc_status setup_islands(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    s->islands = true;
+    s->island_gens = c.island_gens > 0 ? c.island_gens : 32;
+    s->island_size = c.island_size > 0 ? c.island_size : kIslandSizeDefault;
+    s->nislands = c.nwalkers / s->island_size;
+    s->island_K = row_chunks_K(s->ld);                   // 16-byte chunks per row, 2 lanes per walker
+    s->island_ragged = 4 * s->island_K != c.ndim;
+    s->island_lds = std::max<size_t>(pair_lds_bytes(s->island_size, s->island_K), 4096);          // the moment reduction reuses the buffer
+    if (c.density == KMC_USER_DENSITY) return KMC_OK;
+    s->island_kernel = with_density(c.density, IslandFn(nullptr),
+                                    [&](auto d) { return island_lookup<decltype(d)>((int)s->island_size, s->island_K, s->island_ragged); });
+    if (!s->island_kernel) return fail(KMC_ERR_UNSUPPORTED, "no island kernel for this density / ndim");
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(s->island_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->island_lds);
+    if (ea != hipSuccess) { (void)hipGetLastError(); return fail(KMC_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
+    return KMC_OK;
+}
+
+// ---- a runtime-compiled density: what load_user (kmc_rtc.hip) is asked to compile ----
+// `resident_K`, what the resident kernel is compiled as: a term / pair density on short rows -> -ndim = one walker per thread, with two
+// walkers per thread -(100 + ndim); a body density -> the workgroup size bound, 256, 512 or 1024 (a body of 32 dimensions needs its
+// registers), with two walkers per thread 2048; else the two-lane kernel's K.  0: no resident kernel.
+int resident_code(const ResidentChoice& r, bool body, const kmc_config& c)
+{
+    switch (r.kind) {
+    case ResidentChoice::Lane2: return body ? 2048 : -(100 + (int)c.ndim);
+    case ResidentChoice::Lane: return body ? (c.nwalkers <= 256 ? 256 : c.nwalkers <= 512 ? 512 : 1024) : -lane_nd(c.ndim);
+    case ResidentChoice::Pair: return r.K;
+    default: return 0;
+    }
+}
+// `generation_nd`, the kernel of one launch per generation by generation_wanted's kind: ndim -> one walker per lane; -(100 L + K) -> rows
+// lane-striped in the plan's geometry; -401 -> the row over a quad.  0: none.
+int generation_code(int kind, const Plan& p, const kmc_config& c)
+{
+    return kind == 1 ? (int)c.ndim : kind == 2 ? -(100 * p.L + p.K) : kind == 3 ? -401 : 0;
+}
+
+// the kernels of the sampler's plan as it stands (again after a re-plan); `r`: the resident choice, none in island mode
+kmc_status load_user_kernels(kmc_sampler* s, const ResidentChoice& r)
+{
+    const kmc_config& c = s->cfg;
+    const int iS = s->islands ? (int)s->island_size : 0;
+    const int rK = s->islands ? s->island_K : r.K;                     // the pair kernels' chunks (0: neither mode)
+    const int rcode = s->islands ? rK : resident_code(r, s->user->is_body, c);
+    const bool lds_mode = rK != 0 || iS != 0;
+    // a big ensemble's kernels are worth the better compiler (hipcc as a child process: ~1.2 s once per density and geometry, then
+    // cached on disk): inside a PyTorch process hiprtc means the older comgr the wheel bundles (kmc_rtc.hip: offline_compiler_wanted)
+    set_offline_compiler_hint(s->h_loc >= 8192 && !lds_mode);
+    const kmc_status st = load_user(s->user, s->plan.vec, s->plan.L, s->plan.K, s->plan.ITER, s->plan.ragged, &s->uk, rcode, 4 * rK != c.ndim, iS, s->f32, c.ndim,
+                                    (c.flags & KMC_P2P) != 0, lds_mode ? 0 : generation_code(generation_wanted(s), s->plan, c),
+                                    (int)c.move + (s->temper ? kTemperMoveBase : 0));
+    set_offline_compiler_hint(false);
+    return st;
+}
+
+kmc_status setup_user_density(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    kmc_user_density* ud = s->user = static_cast<kmc_user_density*>(c.user_density);
+    s->nblob = ud->nblob;
+    if (ud->is_body && s->islands) return fail(KMC_ERR_UNSUPPORTED, "KMC_ISLANDS needs a menu or term / pair density (a body density runs one walker per lane)");
+    if (ud->is_body && c.ndim > 1024) return fail(KMC_ERR_UNSUPPORTED, "a body density holds the proposal per lane: ndim <= 1024");
+    // small ensembles: resident mode too.  A term / pair density's pair kernel takes 256 walkers
+    ResidentChoice r;
+    if (resident_possible(c) && !(ud->is_body && c.deal_count > 0))
+        r = choose_resident(c, s->ld, ResidentFacts{ud->is_body, ud->nblob > 0, s->f32, !s->f32 && !ud->is_body, 256});
+    // the first sampler over a body taken for a sum over elements finds out whether it is one (check_sum_form); samplers created
+    // meanwhile on other threads wait for the answer instead of planning on a guess
+    std::unique_lock<std::mutex> first_use;
+    if (ud->is_body && ud->sep && sum_form_case(s) == 0) {
+        first_use = std::unique_lock<std::mutex>(ud->check_mu);
+        s->plan = make_plan(s->cfg, s->h_loc);
+    }
+    if (ud->is_body && ud->sep && sum_form_case(s) == 3) {       // (an earlier sampler of this very case found nothing to check the form against)
+        s->sep_off = true;
+        s->sep_off_note = "no test row had a finite log-density at this ndim with these parameters: its per-element form could not be checked";
+    }
+    SepOff sep_off_scope(s->sep_off);        // (for make_plan / compile_user / load_user below, which see the density, not the sampler; the rest of the set-up reads s->sep_off)
+    if (s->sep_off) s->plan = make_plan(s->cfg, s->h_loc);
+    KMC_TRY(load_user_kernels(s, r));
+    // a body taken for a sum over elements: its generated form against the body itself, once, before anything runs it
+    if (s->uk.logpdf_sep && sum_form_case(s) != 1) {
+        KMC_TRY(check_sum_form(s));
+        if (!ud->sep || s->sep_off) {                                 // not shown equal: plan and kernels for the body as written
+            g_sep_off = g_sep_off || s->sep_off;                      // (restored by sep_off_scope at the end of this function)
+            s->uk = UserKernels{};
+            s->plan = make_plan(s->cfg, s->h_loc);
+            KMC_TRY(load_user_kernels(s, r));
+        }
+    }
+    if (r.kind != ResidentChoice::None) set_resident(s, r, std::max<size_t>(r.lds, 4096));
+    return KMC_OK;
+}
+
+// ---- one launch per generation (see generation_wanted), for what is neither resident nor in islands ----
+void setup_generation(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    const int kind = (!s->islands && !s->resident) ? generation_wanted(s) : 0;
+    if (kind == 0) return;
+    if (s->user) s->fused = s->uk.generation != nullptr;
+    else {
+        s->generation_kernel = with_density(c.density, GenerationFn(nullptr), [&](auto d) {
+            using D = decltype(d);
+            return kind == 1 ? generation_lane_lookup<D>((int)c.ndim) : kind == 3 ? generation_group_lookup<D>(4, 1)
+                                                                     : generation_group_lookup<D>(s->plan.L, s->plan.K);
+        });
+        s->fused = s->generation_kernel != nullptr;
+    }
+    if (!s->fused) return;
+    s->fused_L = kind == 1 ? 0 : kind == 3 ? 4 : s->plan.L;
+    // one wave per workgroup (measured best at every size for one walker per lane, `profiles/r04_generation_variants_ab.txt`); lane-striped:
+    // two once the half's waves exceed the chip's SIMDs about once
+    s->fused_tpb = (kind == 2 && s->h * s->plan.L > 64 * 512) ? 128 : 64;
+    s->nislands = c.nwalkers;                     // per-walker moment sums [nwalkers][ld], within [nislands][4 island_K] (kmc_sampler_get_moments)
+    s->island_K = (int)((s->ld + 3) / 4);
+    s->fused_fold = s->fused_L > 0 && s->plan.K == 2 && (s->fused_L == 8 || s->fused_L == 16 || s->fused_L == 32) && kind == 2;
+    if (s->fused_fold) {                          // ... or per-wave accumulators [waves][NVL][64] (generation_group, FoldT): the same sizing fields
+        const int64_t per_wg = s->fused_tpb / s->fused_L;
+        s->nislands = 2 * ((s->h + per_wg - 1) / per_wg) * (s->fused_tpb / 64);      // waves of a launch
+        s->island_K = (8 * s->fused_L / 64) * 16;                                     // 4 island_K = NVL * 64 doubles per wave
+    }
+}
+
+// ---- grid and accumulator layout of the two-launch kernels ----
+void setup_launch_geometry(kmc_sampler* s)
+{
+    // vec: a wave owns W = (64/L)*ITER walkers; generic: one walker per lane
+    const int64_t per_wave = s->plan.vec ? (int64_t)(64 / s->plan.L) * s->plan.ITER : 64;
+    const int64_t waves = (s->h_loc + per_wave - 1) / per_wave;
+    // vec kernels: vec_tpb(L) threads per workgroup; the generic kernel keeps 256
+    const bool staged = s->user && s->uk.staged != nullptr;         // a body density's staged kernel: two waves per workgroup
+    s->vec_lds = (s->user && s->user->is_body && !(s->user->sep && !s->sep_off) && s->plan.vec) ? (unsigned)body_vec_lds_bytes(s->plan.L, s->plan.K, s->plan.ITER) : 0u;
+    s->tpb = s->plan.vec ? vec_tpb(s->plan.L) : (staged ? kStagedTPB : 256);
+    s->grid = (int)((waves * 64 + s->tpb - 1) / s->tpb);
+    s->macc_stride = (int64_t)s->grid * s->tpb;
+    s->macc_elems = s->plan.vec ? s->macc_stride * 2 * s->plan.K : s->macc_stride * s->cfg.ndim;
+}
+
+// ---- device state.  Every fill below is asynchronous on the sampler's stream: kmc_sampler_create waits for all of them once ----
+kmc_status create_stream(kmc_sampler* s)
+{
+    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    s->own_stream = true;
+    HIP_TRY(hipEventCreate(&s->ev0));
+    HIP_TRY(hipEventCreate(&s->ev1));
+    return KMC_OK;
+}
+
+// the mixture's table and the P2P flags
+kmc_status alloc_exchange(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    if (c.move == KMC_MOVE_MIX) {
+        const MixTable mt = mix_table_of(c);
+        HIP_TRY(dev_alloc(s, (void**)&s->d_mix, sizeof(MixTable)));
+        HIP_TRY(copy_sync(s->d_mix, &mt, sizeof(MixTable), hipMemcpyHostToDevice, s->stream));
+    }
+    if (s->p2p) {
+        HIP_TRY(hipExtMallocWithFlags((void**)&s->d_flags, 4096, hipDeviceMallocFinegrained));
+        HIP_TRY(hipMemsetAsync(s->d_flags, 0, 4096, s->stream));
+        HIP_TRY(dev_alloc(s, (void**)&s->d_err, 64));
+        HIP_TRY(hipMemsetAsync(s->d_err, 0, 64, s->stream));
+        // KMC_P2P_PUSH: local copies of the other shards, which their owners write; the menu densities' vector kernels carry it (anything
+        // else keeps the pull -- kmc_sampler_describe says which runs)
+        s->push = (c.flags & KMC_P2P_PUSH) != 0 && s->plan.vec && s->user == nullptr && !(c.flags & KMC_P2P_FINEGRAINED) && c.shard_count > 1;
+    }
+    return KMC_OK;
+}
+
+// the ladder's block: betas, logp_sum, the moments credited at exchanges, the adaptive ladder's state (kmc_sampler.hpp), and the swap counters
+kmc_status alloc_tempering(kmc_sampler* s)
+{
+    if (!s->temper) return KMC_OK;
+    const size_t nt = (size_t)s->ntemps;
+    const size_t nb = (2 * nt + 2 * (size_t)s->ld + 2 * nt + 2 + 2 * nt) * sizeof(double);
+    HIP_TRY(dev_alloc(s, &s->d_betas, nb));
+    HIP_TRY(hipMemsetAsync(s->d_betas, 0, nb, s->stream));
+    HIP_TRY(copy_sync(s->d_betas, s->betas.data(), nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    s->d_rung_sum = s->d_betas + nt;
+    s->d_tsum = s->d_rung_sum + nt;
+    s->d_S = s->d_tsum + 2 * (size_t)s->ld;
+    s->d_round_acc = reinterpret_cast<unsigned long long*>(s->d_S + nt);
+    s->d_ticket = reinterpret_cast<unsigned int*>(s->d_round_acc + nt);
+    s->d_skipped = s->d_round_acc + nt + 1;
+    s->d_stage = reinterpret_cast<double*>(s->d_skipped + 1);
+    if (!s->S0.empty()) HIP_TRY(copy_sync(s->d_S, s->S0.data(), s->S0.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(dev_alloc(s, (void**)&s->d_nswap, nt * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(s->d_nswap, 0, nt * sizeof(unsigned long long), s->stream));
+    return KMC_OK;
+}
+
+// rows, the per-walker block, the generation counter, the schedule, a dealt sub-ensemble's ids; every per-walker array holds ntemps ensembles
+kmc_status alloc_state(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    const size_t nw = (size_t)s->nrows, nt = (size_t)s->ntemps, ldz = (size_t)s->ld;
+    const size_t esz = s->f32 ? sizeof(float) : sizeof(double);      // element size of rows and chain
+    const size_t pos_bytes = (s->push ? 1 + (size_t)c.shard_count : nt) * nw * ldz * esz;
+    if (s->p2p && (c.flags & KMC_P2P_FINEGRAINED))   // peers map the rows uncached: nothing of them can go stale in a reader's L2
+        HIP_TRY(hipExtMallocWithFlags((void**)&s->d_pos, nw * ldz * sizeof(double), hipDeviceMallocFinegrained));
+    else
+        HIP_TRY(dev_alloc(s, &s->d_pos, pos_bytes));
+    HIP_TRY(hipMemsetAsync(s->d_pos, 0, pos_bytes, s->stream));   // the pad column of odd ndim stays 0
+    // per-walker block {logp[nrows], naccept[nrows], klast[nrows]}: one allocation, so the half-step kernels reach all
+    // three from one preloaded pointer (HalfStepFront::logp)
+    const size_t block_bytes = nt * nw * (sizeof(double) + 2 * sizeof(uint32_t));
+    HIP_TRY(dev_alloc(s, &s->d_logp, block_bytes));
+    if (s->temper) HIP_TRY(hipMemsetAsync(s->d_logp, 0, block_bytes, s->stream));   // (every rung's counters)
+    s->d_naccept = reinterpret_cast<uint32_t*>(s->d_logp + nw);
+    s->d_klast = s->d_naccept + nw;
+    if (s->ragged_vec() && (reinterpret_cast<uint64_t>(s->d_logp) >> 48) != 0)   // (kmc_launch.hip: front_of -- ndim rides in the 16 bits above this address)
+        return fail(KMC_ERR_UNSUPPORTED, "device addresses beyond 2^48: the ragged vector kernels carry ndim in the upper 16 bits of a pointer");
+    HIP_TRY(hipMemsetAsync(s->d_klast, 0, nw * sizeof(uint32_t), s->stream));
+    static_assert(kGraphChunk <= 64, "advance_schedule runs one 64-thread block");
+    HIP_TRY(dev_alloc(s, &s->d_gen, 64));
+    HIP_TRY(hipMemsetAsync(s->d_gen, 0, 64, s->stream));
+    HIP_TRY(dev_alloc(s, &s->d_sched, (size_t)kGraphChunk * sizeof(SchedEntry)));
+    HIP_TRY(hipMemsetAsync(s->d_naccept, 0, nw * sizeof(uint32_t), s->stream));
+    if (c.deal_count > 0) HIP_TRY(dev_alloc(s, (void**)&s->d_ids, nw * sizeof(uint32_t)));
+    return KMC_OK;
+}
+
+// the vector kernels' draw ring and resident mode's draw table
+kmc_status alloc_draws(kmc_sampler* s)
+{
+    // Draw ring (kmc_kernels.hpp: kRing; possible for L = 16 / 32 with L / ITER >= 2): a wave computes its walkers' next steps' draws with its idle lanes and parks
+    // them, 4 slots x rows x 32 B; tags start at 0xffffffff (no step carries it), so nothing is "parked" yet.  Where it pays was re-measured in round 5
+    // (scripts/probes/ring_ab.py, profiles/r05_ring_ab.txt) -- since the launches carry their step among the preloaded parameters Philox starts at wave entry and the
+    // ring's entry is one more dependent load in front of the partner row: rows LOSE 2-7 % with it at ITER = 2 and at L = 32, exact-size and ragged alike (the ragged
+    // kernels gained 6-10 % from it only while their loads sat behind exec-mask regions and scalar waits; without those they behave like the exact-size ones), and
+    // 6-14 % in the large-ensemble geometries (ITER >= 4: bandwidth-bound, the ring is bytes); L = 16, ITER = 1 (C3's geometry) is +-1 % exact-size, -1..2 % ragged, and keeps it.
+    // KMC_DEBUG=ring=0|1 forces it off / on wherever the kernel has one.
+    const Plan& p = s->plan;
+    bool want_ring = p.vec && !two_launch_only(s->cfg) && !s->islands && !s->resident && p.L >= 16 && p.L <= 32 && p.L / p.ITER >= 2;
+    std::string forced;
+    if (want_ring && debug_opt("ring", &forced)) want_ring = forced != "0";
+    else if (want_ring) want_ring = p.L == 16 && p.ITER == 1;
+    if (want_ring) {
+        const size_t nb = 4 * (size_t)s->nrows * 2 * sizeof(double2);
+        HIP_TRY(dev_alloc(s, (void**)&s->d_ring, nb));
+        HIP_TRY(hipMemsetAsync(s->d_ring, 0xff, nb, s->stream));
+    }
+    if (s->resident)                                 // the launch's draws come from a wide kernel (draw_table_fill, kmc_islands.hpp)
+        HIP_TRY(dev_alloc(s, (void**)&s->d_draws, (size_t)kDrawTableGens * (size_t)s->nrows * 2 * sizeof(double2)));
+    return KMC_OK;
+}
+
+// KMC_MOMENTS: the two-launch kernels' accumulators, long rows' moment ring, and the per-island / per-walker / per-wave sums of the other routes
+kmc_status alloc_moments(kmc_sampler* s)
+{
+    if (!(s->cfg.flags & KMC_MOMENTS)) return KMC_OK;
+    const size_t macc_bytes = (size_t)s->macc_elems * sizeof(double);
+    HIP_TRY(dev_alloc(s, &s->d_msum, macc_bytes));
+    HIP_TRY(dev_alloc(s, &s->d_msumsq, macc_bytes));
+    HIP_TRY(hipMemsetAsync(s->d_msum, 0, macc_bytes, s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_msumsq, 0, macc_bytes, s->stream));
+    if (s->plan.vec && s->plan.L == 64 && !s->islands && !s->resident && !debug_opt("no-moment-ring")) {
+        // moment ring for long rows (kmc_kernels.hpp, HalfStepArgs::mring): up to 128 posted rows per wave,
+        // within 512 MiB in all; swept every kSweepEvery generations
+        const int64_t nwaves = s->macc_stride / 64;
+        const size_t slot = (size_t)s->plan.K * 64 * sizeof(double2);       // one row
+        int64_t depth = (int64_t)(((size_t)1 << 29) / ((size_t)nwaves * slot));
+        if (depth > 128) depth = 128;
+        const long forced_depth = debug_opt_long("moment-ring-depth", 0);                         // tests: force overflows
+        if (forced_depth >= 1 && forced_depth < depth) depth = forced_depth;
+        if (depth >= 4 || (depth >= 2 && forced_depth > 0)) {
+            HIP_TRY(dev_alloc(s, (void**)&s->d_mring, (size_t)nwaves * (size_t)depth * slot));
+            HIP_TRY(dev_alloc(s, (void**)&s->d_mring_w, (size_t)nwaves * (size_t)depth * sizeof(double)));
+            HIP_TRY(dev_alloc(s, (void**)&s->d_mcnt, 2 * (size_t)nwaves * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(s->d_mcnt, 0, 2 * (size_t)nwaves * sizeof(uint32_t), s->stream));
+            s->mring_depth = (int)depth;
+            s->mring_waves = nwaves;
+        }
+    }
+    if (s->islands || s->resident || s->fused) {
+        const size_t ne = (size_t)s->nislands * 4 * (size_t)s->island_K;
+        HIP_TRY(dev_alloc(s, &s->d_isum, ne * sizeof(double)));
+        HIP_TRY(dev_alloc(s, &s->d_isumsq, ne * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(s->d_isum, 0, ne * sizeof(double), s->stream));
+        HIP_TRY(hipMemsetAsync(s->d_isumsq, 0, ne * sizeof(double), s->stream));
+    }
+    return KMC_OK;
+}
+
+// one launch per generation: the second copy of the state (pad column of an odd ndim: 0 in both)
+kmc_status alloc_second_state(kmc_sampler* s)
+{
+    if (!s->fused) return KMC_OK;
+    const size_t nw = (size_t)s->nrows;
+    HIP_TRY(dev_alloc(s, &s->d_pos2, nw * (size_t)s->ld * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(s->d_pos2, 0, nw * (size_t)s->ld * sizeof(double), s->stream));
+    HIP_TRY(dev_alloc(s, &s->d_logp2, nw * sizeof(double)));
+    if (s->fused_L > 0) {
+        HIP_TRY(dev_alloc(s, (void**)&s->d_glast, nw * sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(s->d_glast, 0, nw * sizeof(uint32_t), s->stream));
+    }
+    return KMC_OK;
+}
+
+// KMC_DATA_DENSITY: proposals, their sums and the tree's scratch
+kmc_status alloc_data_route(kmc_sampler* s)
+{
+    // (a likelihood-tempered ladder: every rung's proposals in one pass -- nt h rows, S and the prior apart -- and every rung's rows at set_positions)
+    const size_t nt = (size_t)s->ntemps, np_half = nt * (size_t)s->h, np_all = nt * (size_t)s->nrows;
+    HIP_TRY(dev_alloc(s, &s->d_prop, np_half * (size_t)s->ld * sizeof(double)));
+    HIP_TRY(dev_alloc(s, &s->d_p1, (s->temper_like ? 2 : 1) * np_half * sizeof(double)));
+    // the plans are decided here, once (KMC_DEBUG=data-map may change later in the process: the kernels keep the geometry d_part was sized for)
+    s->plan_half = data_plan(s->data_ud, (int64_t)np_half);
+    s->plan_all = data_plan(s->data_ud, (int64_t)np_all);
+    s->part_doubles = std::max((size_t)s->plan_half.nblocks * np_half, (size_t)s->plan_all.nblocks * np_all);
+    HIP_TRY(dev_alloc(s, &s->d_part, s->part_doubles * sizeof(double)));
+    if (s->temper_like) {
+        const size_t nb = (2 * np_all + nt) * sizeof(double);
+        HIP_TRY(dev_alloc(s, &s->d_like, nb));
+        HIP_TRY(hipMemsetAsync(s->d_like, 0, nb, s->stream));
+        s->d_prior = s->d_like + np_all;
+        s->d_like_sum = s->d_prior + np_all;
+    }
+    return KMC_OK;
+}
+
+// KMC_HOST_DENSITY: proposals and log-pdfs on the device and page-locked on the host, accept outcomes for host_accepted
+kmc_status alloc_host_route(kmc_sampler* s)
+{
+    const size_t h = (size_t)s->h;
+    HIP_TRY(dev_alloc(s, &s->d_prop, h * (size_t)s->ld * sizeof(double)));
+    HIP_TRY(dev_alloc(s, &s->d_p1, h * sizeof(double)));
+    HIP_TRY(hipHostMalloc((void**)&s->h_prop, h * (size_t)s->cfg.ndim * sizeof(double), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&s->h_p1, h * sizeof(double), hipHostMallocDefault));
+    if (hipHostGetDevicePointer((void**)&s->h_prop_dev, s->h_prop, 0) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&s->h_p1_dev, s->h_p1, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        s->h_prop_dev = s->h_p1_dev = nullptr;          // (then every batch goes through the copies)
+    }
+    if (s->cfg.host_accepted) {
+        HIP_TRY(dev_alloc(s, &s->d_acc, h));
+        HIP_TRY(hipHostMalloc((void**)&s->h_acc, h, hipHostMallocDefault));
+    }
+    return KMC_OK;
+}
+
+// KMC_STREAM_CHAIN: the ring's block size, the transposed / compacted block, the copy stream and its events.  Returns through
+// s->ring_slots how many sample slots the chain on the device then has.
+kmc_status setup_stream_ring(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    // a ring of three blocks; a block holds at least the samples of one launch unit (a graph replay), so a unit never
+    // touches more than two blocks, and about 512 MiB otherwise (measured at C2: 128 MiB blocks stream 22-26 GB/s at nthin = 10, 512 MiB blocks 43-45 GB/s of the
+    // 56 GB/s this link copies alone; many small blocks cost more at the block boundaries than their earlier start
+    // returns -- nthin = 100: +19 % on the loop with 64 MiB blocks, +6 % with 512 MiB; KMC_DEBUG=chain-block=n: samples per block, for tests)
+    const int64_t unit = s->resident ? 1 : std::max<int64_t>(kGraphChunk, s->uchunk);     // (a resident launch is cut to the block: kmc_sampler_run)
+    const int64_t per_unit = (unit + c.nthin - 1) / c.nthin + 1;
+    const size_t sample_bytes = (size_t)s->nlocal * (size_t)s->ld * sizeof(double);
+    int64_t blk = (int64_t)(((size_t)512 << 20) / sample_bytes);
+    if (blk < 1) blk = 1;
+    if (blk > 4096) blk = 4096;
+    { const long v = debug_opt_long("chain-block", 0); if (v >= 1) blk = v; }
+    if (blk < per_unit) blk = per_unit;
+    s->stream_chain = true;
+    s->stream_by_walker = (c.flags & KMC_CHAIN_BY_WALKER) != 0;
+    const size_t block_doubles = (size_t)blk * (size_t)s->nlocal;
+    if (s->stream_by_walker) {
+        if (c.flags & KMC_STORE_CHAIN) HIP_TRY(dev_alloc(s, &s->bw_scratch, block_doubles * (size_t)c.ndim * sizeof(double)));
+        if (c.flags & KMC_STORE_LOGP) HIP_TRY(dev_alloc(s, &s->bw_scratch_logp, block_doubles * sizeof(double)));
+    } else if ((c.flags & KMC_STORE_CHAIN) && s->ld != c.ndim) {
+        HIP_TRY(dev_alloc(s, &s->bw_scratch, block_doubles * (size_t)c.ndim * sizeof(double)));   // (rows_compact)
+    }
+    s->ring_blk = blk;
+    s->ring_slots = 3 * blk;
+    HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 3; ++i) {
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_filled[i], hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&s->ev_copied[i], hipEventDisableTiming));
+    }
+    return KMC_OK;
+}
+
+// the stored chain, its log-pdfs and blobs -- whole, or as the stream ring
+kmc_status alloc_chain(kmc_sampler* s)
+{
+    const kmc_config& c = s->cfg;
+    const size_t ldz = (size_t)s->ld, esz = s->f32 ? sizeof(float) : sizeof(double);
+    const bool stored = s->nsamples > 0;
+    if ((c.flags & KMC_STREAM_CHAIN) && stored) KMC_TRY(setup_stream_ring(s));
+    const size_t slot_rows = (size_t)(s->stream_chain ? s->ring_slots : s->nsamples) * (size_t)s->nlocal;
+    if ((c.flags & (KMC_STORE_CHAIN | KMC_STORE_LOGP)) && stored) {
+        // A chain that cannot fit is refused HERE, not by a failing hipMalloc: after a failed allocation of hundreds of GB the
+        // runtime aborted the process a few calls later (observed: 4 of 5 runs, in the first HIP call of the next sampler).
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        const size_t need = slot_rows * (((c.flags & KMC_STORE_CHAIN) ? ldz * esz : 0) + ((c.flags & KMC_STORE_LOGP) ? sizeof(double) : 0));
+        if (need > free_b)
+            return fail(KMC_ERR_OOM, "the chain needs " + std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) +
+                                     (s->nblob > 0 ? " MiB are free: thin it (nthin)" : " MiB are free: thin it (nthin), or stream it to host memory (KMC_STREAM_CHAIN)"));
+    }
+    if ((c.flags & KMC_STORE_CHAIN) && stored) HIP_TRY(dev_alloc(s, &s->d_chain, slot_rows * ldz * esz));
+    if ((c.flags & KMC_STORE_LOGP) && stored) HIP_TRY(dev_alloc(s, &s->d_chain_logp, slot_rows * sizeof(double)));
+    if (s->nblob > 0) {
+        const size_t blob_bytes = (size_t)s->nrows * (size_t)s->nblob * sizeof(double);
+        HIP_TRY(dev_alloc(s, &s->d_blob, blob_bytes));
+        HIP_TRY(hipMemsetAsync(s->d_blob, 0, blob_bytes, s->stream));
+        if ((c.flags & KMC_STORE_BLOBS) && stored) {
+            const size_t need_b = (size_t)s->nsamples * (size_t)s->nlocal * (size_t)s->nblob * sizeof(double);
+            size_t free_b = 0, total_b = 0;
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            if (need_b > free_b)
+                return fail(KMC_ERR_OOM, "the stored blobs need " + std::to_string(need_b >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB are free: thin the chain (nthin)");
+            HIP_TRY(dev_alloc(s, &s->d_chain_blob, need_b));
+        }
+    }
+    return KMC_OK;
+}
+}  // namespace
+
 KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** out)
 {
     if (!out) return fail(KMC_ERR_BAD_ARG, "null out");
@@ -393,107 +962,13 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
     if (cfg->device < 0 || cfg->device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
     HIP_TRY(hipSetDevice(cfg->device));
 
-    kmc_sampler* s = new kmc_sampler();
-    s->cfg = *cfg;
-    s->user_seed = cfg->seed;
-    s->temper = tempered(*cfg);
-    s->ntemps = s->temper ? cfg->ntemps : 1;
-    if (s->temper) s->betas.assign(cfg->betas, cfg->betas + cfg->ntemps);          // (the caller's array is copied here)
-    s->cfg.betas = s->temper ? s->betas.data() : nullptr;
-    s->temper_like = s->temper && cfg->temper_mode == KMC_TEMPER_LIKELIHOOD;
-    s->adapt = s->temper && cfg->adapt != 0;
-    if (s->adapt && s->cfg.adapt_until == 0) s->cfg.adapt_until = cfg->nburnin;
-    for (int j = 1; s->temper && j + 1 < s->ntemps; ++j)                             // (state from here on: never derived from the betas again)
-        s->S0.push_back(std::log(1.0 / s->betas[(size_t)j] - 1.0 / s->betas[(size_t)j - 1]));
-    if (cfg->deal_count > 0) s->cfg.seed = deal_seed(cfg->seed, cfg->deal_rank);    // this sub-ensemble's Philox key
-    if (s->cfg.shard_count <= 0) s->cfg.shard_count = 1;
-    s->h = cfg->nwalkers / 2;
-    s->h_loc = s->h / s->cfg.shard_count;
-    s->active_begin = s->h_loc * s->cfg.shard_rank;
-    s->nlocal = 2 * s->h_loc;
-    s->nsamples = cfg->ngenerations > cfg->nburnin ? (cfg->ngenerations - cfg->nburnin) / cfg->nthin : 0;   // :234
-    s->ld = cfg->ndim + (cfg->ndim & 1);      // whole two-element chunks: 16-byte aligned double rows, 8-byte aligned float rows
-    s->f32 = cfg->dtype == KMC_F32;
-    kmc_status st = digest_params(*cfg, &s->dp);
-    if (st != KMC_OK) { delete s; return st; }
-    s->plan = make_plan(s->cfg, s->h_loc);
+    std::unique_ptr<kmc_sampler, SamplerDeleter> owner(new kmc_sampler());
+    kmc_sampler* s = owner.get();
+    // which route: islands, resident, one launch per generation, or the two launches of the plan
+    KMC_TRY(init_shape(s, *cfg));
+    if (cfg->flags & KMC_ISLANDS) KMC_TRY(setup_islands(s));
     if (cfg->density == KMC_USER_DENSITY) {
-        s->user = static_cast<kmc_user_density*>(cfg->user_density);
-        s->nblob = s->user->nblob;
-        // small ensembles: resident mode too (one workgroup, LDS within the default 64 KiB limit)
-        int rK = 0, rK0 = 1;
-        while (2 * rK0 < s->ld / 2) rK0 *= 2;
-        size_t rlds = ((size_t)cfg->nwalkers * (size_t)(4 * (rK0 + 1)) + (size_t)cfg->nwalkers) * sizeof(double);
-        // a body density: one walker per thread (kmc_islands.hpp: resident_lane_body), rows of ndim | 1 doubles, up to 1024 walkers
-        if (s->user->is_body) rlds = ((size_t)cfg->nwalkers * (size_t)((cfg->ndim | 1) + 1)) * sizeof(double);
-        const bool expr_lane = !s->user->is_body && resident_lane_wanted(cfg->ndim);     // term / pair density, short rows: the lane kernel too
-        if (expr_lane) rlds = ((size_t)cfg->nwalkers * (size_t)((lane_nd(cfg->ndim) | 1) + 1)) * sizeof(double);
-        // (float rows: the one-walker-per-thread kernels only -- their LDS rows are double either way)
-        // 1026 .. 2048 walkers: two walkers per thread (kmc_islands.hpp: resident_lane2_body; double rows, ndim <= 8, no blobs)
-        const bool lane2 = cfg->nwalkers > 1024 && cfg->nwalkers <= 2048 && !s->f32 && cfg->ndim <= 8 && s->user->nblob == 0 && resident_lane_wanted(cfg->ndim);
-        if (lane2) rlds = ((size_t)cfg->nwalkers * (size_t)((cfg->ndim | 1) + 1)) * sizeof(double);
-        if ((!s->f32 || s->user->is_body || expr_lane) && (cfg->nwalkers <= ((s->user->is_body || expr_lane) ? 1024 : 256) || lane2) && cfg->ndim <= 32 && s->cfg.shard_count == 1 && !(s->user->is_body && cfg->deal_count > 0) &&
-            !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH | KMC_ISLANDS)) && !two_launch_only(*cfg) &&
-            rlds <= 156 * 1024 && !debug_opt("no-resident"))    // (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
-            rK = rK0;
-        int iS = 0;
-        if (cfg->flags & KMC_ISLANDS) {
-            iS = cfg->island_size > 0 ? cfg->island_size : kIslandSizeDefault;
-            rK = 1;
-            while (2 * rK < s->ld / 2) rK *= 2;
-        }
-        if (s->user->is_body && iS > 0) { kmc_sampler_destroy(s); return fail(KMC_ERR_UNSUPPORTED, "KMC_ISLANDS needs a menu or term / pair density (a body density runs one walker per lane)"); }
-        if (s->user->is_body && cfg->ndim > 1024) { kmc_sampler_destroy(s); return fail(KMC_ERR_UNSUPPORTED, "a body density holds the proposal per lane: ndim <= 1024"); }
-        // (what the resident kernel is compiled as: term / pair density on short rows -> -ndim = one walker per thread; body density ->
-        //  the workgroup size bound, 256 or 1024: a body of 32 dimensions needs its registers; else the two-lane kernel's K)
-        //  two walkers per thread: 2048 for a body, -(100 + ndim) for a term / pair density)
-        const int rcode = (rK > 0 && iS == 0) ? (lane2 ? (s->user->is_body ? 2048 : -(100 + (int)cfg->ndim))
-                                                       : s->user->is_body ? (cfg->nwalkers <= 256 ? 256 : cfg->nwalkers <= 512 ? 512 : 1024) : (expr_lane ? -lane_nd(cfg->ndim) : rK)) : rK;
-        // a big ensemble's kernels are worth the better compiler (hipcc as a child process: ~1.2 s once per density and geometry, then
-        // cached on disk): inside a PyTorch process hiprtc means the older comgr the wheel bundles (kmc_rtc.hip: offline_compiler_wanted)
-        // the first sampler over a body taken for a sum over elements finds out whether it is one (check_sum_form); samplers created
-        // meanwhile on other threads wait for the answer instead of planning on a guess
-        std::unique_lock<std::mutex> first_use;
-        if (s->user->is_body && s->user->sep && sum_form_case(s) == 0) {
-            first_use = std::unique_lock<std::mutex>(s->user->check_mu);
-            s->plan = make_plan(s->cfg, s->h_loc);
-        }
-        if (s->user->is_body && s->user->sep && sum_form_case(s) == 3) {       // (an earlier sampler of this very case found nothing to check the form against)
-            s->sep_off = true;
-            s->sep_off_note = "no test row had a finite log-density at this ndim with these parameters: its per-element form could not be checked";
-        }
-        SepOff sep_off_scope(s->sep_off);        // (for make_plan / compile_user / load_user below, which see the density, not the sampler; the rest of the set-up reads s->sep_off)
-        if (s->sep_off) s->plan = make_plan(s->cfg, s->h_loc);
-        auto load = [&]() {
-            set_offline_compiler_hint(s->h_loc >= 8192 && rK == 0 && iS == 0);
-            const kmc_status lst = load_user(s->user, s->plan.vec, s->plan.L, s->plan.K, s->plan.ITER, s->plan.ragged, &s->uk, rcode, 4 * rK != cfg->ndim, iS, s->f32,
-                                             cfg->ndim, (cfg->flags & KMC_P2P) != 0, (rK != 0 || iS != 0) ? 0 : generation_wanted(s) == 1 ? (int)cfg->ndim : generation_wanted(s) == 2 ? -(100 * s->plan.L + s->plan.K) : generation_wanted(s) == 3 ? -401 : 0,
-                                             (int)cfg->move + (s->temper ? kTemperMoveBase : 0));
-            set_offline_compiler_hint(false);
-            return lst;
-        };
-        st = load();
-        // a body taken for a sum over elements: its generated form against the body itself, once, before anything runs it
-        if (st == KMC_OK && s->uk.logpdf_sep && sum_form_case(s) != 1) {
-            st = check_sum_form(s);
-            if (st == KMC_OK && (!s->user->sep || s->sep_off)) {          // not shown equal: plan and kernels for the body as written
-                g_sep_off = g_sep_off || s->sep_off;                      // (restored by sep_off_scope at the end of this block)
-                s->uk = UserKernels{};
-                s->plan = make_plan(s->cfg, s->h_loc);
-                st = load();
-            }
-        }
-        if (st != KMC_OK) { kmc_sampler_destroy(s); return st; }
-        if (iS > 0) rK = 0;     // island mode is set up below, not resident mode
-        if (rK > 0) {
-            s->resident = true;
-            s->island_K = rK;
-            s->nislands = 1;
-            s->island_lds = rlds < 4096 ? 4096 : rlds;
-            s->resident_lane = s->user->is_body || expr_lane || lane2;
-            s->resident_lane2 = lane2;
-            s->resident_tpb = lane2 ? (int)((cfg->nwalkers / 2 + 63) / 64 * 64) : s->resident_lane ? (int)((cfg->nwalkers + 63) / 64 * 64) : 256;
-        }
+        KMC_TRY(setup_user_density(s));
     } else if (cfg->density == KMC_HOST_DENSITY) {
         s->host_eval = true;
     } else if (cfg->density == KMC_DATA_DENSITY) {
@@ -501,355 +976,31 @@ KMC_EXPORT kmc_status kmc_sampler_create(const kmc_config* cfg, kmc_sampler** ou
         s->host_eval = true;
         s->data_eval = true;
         s->data_ud = static_cast<kmc_user_density*>(cfg->user_density);
-        st = load_data(s->data_ud, cfg->ndim, &s->dk);
-        if (st != KMC_OK) { kmc_sampler_destroy(s); return st; }
+        KMC_TRY(load_data(s->data_ud, cfg->ndim, &s->dk));
     } else {
         s->logpdf_fn = logpdf_fn(cfg->density);
+        setup_menu_resident(s);
     }
-    // vec: a wave owns W = (64/L)*ITER walkers; generic: one walker per lane
-    const int64_t per_wave = s->plan.vec ? (int64_t)(64 / s->plan.L) * s->plan.ITER : 64;
-    const int64_t waves = (s->h_loc + per_wave - 1) / per_wave;
-    if (cfg->flags & KMC_ISLANDS) {
-        s->islands = true;
-        s->island_gens = cfg->island_gens > 0 ? cfg->island_gens : 32;
-        s->island_size = cfg->island_size > 0 ? cfg->island_size : kIslandSizeDefault;
-        s->nislands = cfg->nwalkers / s->island_size;
-        const int64_t chunks = s->ld / 2;                   // 16-byte chunks per row, 2 lanes per walker
-        int K = 1;
-        while (2 * K < chunks) K *= 2;
-        s->island_K = K;
-        s->island_ragged = 4 * K != cfg->ndim;
-        s->island_lds = ((size_t)s->island_size * (size_t)(4 * (K + 1)) + (size_t)s->island_size) * sizeof(double);
-        if (s->island_lds < 4096) s->island_lds = 4096;          // the moment reduction reuses the buffer
-        hipError_t ea = hipSuccess;
-        if (!s->user) {
-            s->island_kernel = with_density(cfg->density, IslandFn(nullptr),
-                                            [&](auto d) { return island_lookup<decltype(d)>((int)s->island_size, K, s->island_ragged); });
-            if (!s->island_kernel) { kmc_sampler_destroy(s); return fail(KMC_ERR_UNSUPPORTED, "no island kernel for this density / ndim"); }
-            ea = hipFuncSetAttribute(reinterpret_cast<const void*>(s->island_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->island_lds);
-        }
-        if (ea != hipSuccess) { (void)hipGetLastError(); kmc_sampler_destroy(s); return fail(KMC_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(ea)); }
-    }
-    if (!s->islands && cfg->density != KMC_USER_DENSITY && !s->host_eval && cfg->nwalkers <= 2048 && cfg->ndim <= 32 &&
-        s->cfg.shard_count == 1 && !(cfg->flags & (KMC_P2P | KMC_NO_GRAPH)) && !two_launch_only(*cfg) && !debug_opt("no-resident")) {
-        const int64_t chunks = s->ld / 2;
-        int K = 1;
-        while (2 * K < chunks) K *= 2;
-        int rtpb = cfg->nwalkers <= 256 ? 256 : (cfg->nwalkers <= 512 ? 512 : 1024);
-        size_t need = ((size_t)cfg->nwalkers * (size_t)(4 * (K + 1)) + (size_t)cfg->nwalkers) * sizeof(double);
-        ResidentFn rf = (!s->f32 && need <= 156 * 1024 && cfg->nwalkers <= 1024)         // (float rows: the lane kernels only)
-                         ? with_density(cfg->density, ResidentFn(nullptr), [&](auto d) { return resident_lookup<decltype(d)>(rtpb, K, 4 * K != cfg->ndim); })
-                         : nullptr;
-        if (cfg->nwalkers > 1024) {                       // 1026 .. 2048 walkers: two walkers per thread, short double rows, as LDS allows
-            const size_t need2 = ((size_t)cfg->nwalkers * (size_t)((lane_nd(cfg->ndim) | 1) + 1)) * sizeof(double);
-            ResidentFn l2 = (!s->f32 && resident_lane_wanted(cfg->ndim) && need2 <= 156 * 1024) ? with_density(cfg->density, ResidentFn(nullptr), [&](auto d) { return resident_lane2_lookup<decltype(d)>((int)cfg->ndim); })
-                                                                                                      : nullptr;
-            if (l2) {
-                rf = l2;
-                rtpb = (int)((cfg->nwalkers / 2 + 63) / 64 * 64);
-                need = need2;
-                s->resident_lane = true;
-                s->resident_lane2 = true;
-            }
-        } else
-        if (resident_lane_wanted(cfg->ndim)) {            // short rows: one walker per thread (measured faster up to ndim 8)
-            ResidentFn lf = with_density(cfg->density, ResidentFn(nullptr), [&](auto d) { return resident_lane_lookup<decltype(d)>((int)cfg->ndim, s->f32); });
-            if (lf) {
-                rf = lf;
-                rtpb = (int)((cfg->nwalkers + 63) / 64 * 64);
-                need = ((size_t)cfg->nwalkers * (size_t)((lane_nd(cfg->ndim) | 1) + 1)) * sizeof(double);
-                s->resident_lane = true;
-            }
-        }
-        if (rf) {
-            s->resident_tpb = rtpb;
-            s->island_lds = need;
-            if (s->island_lds < 8192) s->island_lds = 8192;     // the moment reduction reuses the buffer
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(rf), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)s->island_lds) == hipSuccess) {
-                s->resident = true;
-                s->resident_kernel = rf;
-                s->island_K = K;
-                s->nislands = 1;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-    }
-    if (const int kind = (!s->islands && !s->resident) ? generation_wanted(s) : 0) {          // one launch per generation (see generation_wanted)
-        if (s->user) s->fused = s->uk.generation != nullptr;
-        else {
-            s->generation_kernel = with_density(cfg->density, GenerationFn(nullptr), [&](auto d) {
-                using D = decltype(d);
-                return kind == 1 ? generation_lane_lookup<D>((int)cfg->ndim) : kind == 3 ? generation_group_lookup<D>(4, 1)
-                                                                             : generation_group_lookup<D>(s->plan.L, s->plan.K);
-            });
-            s->fused = s->generation_kernel != nullptr;
-        }
-        if (s->fused) {
-            s->fused_L = kind == 1 ? 0 : kind == 3 ? 4 : s->plan.L;
-            // one wave per workgroup (measured best at every size for one walker per lane, `profiles/r04_generation_variants_ab.txt`); lane-striped:
-            // two once the half's waves exceed the chip's SIMDs about once
-            s->fused_tpb = (kind == 2 && s->h * s->plan.L > 64 * 512) ? 128 : 64;
-            s->nislands = cfg->nwalkers;                  // per-walker moment sums [nwalkers][ld], within [nislands][4 island_K] (kmc_sampler_get_moments)
-            s->island_K = (int)((s->ld + 3) / 4);
-            s->fused_fold = s->fused_L > 0 && s->plan.K == 2 && (s->fused_L == 8 || s->fused_L == 16 || s->fused_L == 32) && kind == 2;
-            if (s->fused_fold) {                          // ... or per-wave accumulators [waves][NVL][64] (generation_group, FoldT): the same sizing fields
-                const int64_t per_wg = s->fused_tpb / s->fused_L;
-                s->nislands = 2 * ((s->h + per_wg - 1) / per_wg) * (s->fused_tpb / 64);      // waves of a launch
-                s->island_K = (8 * s->fused_L / 64) * 16;                                     // 4 island_K = NVL * 64 doubles per wave
-            }
-        }
-    }
-    // vec kernels: vec_tpb(L) threads per workgroup; the generic kernel keeps 256
-    const bool staged = s->user && s->uk.staged != nullptr;         // a body density's staged kernel: two waves per workgroup
-    s->vec_lds = (s->user && s->user->is_body && !(s->user->sep && !s->sep_off) && s->plan.vec) ? (unsigned)body_vec_lds_bytes(s->plan.L, s->plan.K, s->plan.ITER) : 0u;
-    const int tpb = s->plan.vec ? vec_tpb(s->plan.L) : (staged ? kStagedTPB : 256);
-    s->tpb = tpb;
-    s->grid = (int)((waves * 64 + tpb - 1) / tpb);
-    s->macc_stride = (int64_t)s->grid * tpb;
-    s->macc_elems = s->plan.vec ? s->macc_stride * 2 * s->plan.K : s->macc_stride * cfg->ndim;
-
-#define CREATE_TRY(expr)                                                                       \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (void)hipGetLastError();                                                           \
-            kmc_status r_ = fail(e_ == hipErrorOutOfMemory ? KMC_ERR_OOM : KMC_ERR_HIP,        \
-                                 std::string(#expr) + ": " + hipGetErrorString(e_));           \
-            kmc_sampler_destroy(s);                                                            \
-            return r_;                                                                         \
-        }                                                                                      \
-    } while (0)
-
-    CREATE_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    s->own_stream = true;
-    CREATE_TRY(hipEventCreate(&s->ev0));
-    CREATE_TRY(hipEventCreate(&s->ev1));
-    s->p2p = (cfg->flags & KMC_P2P) != 0;
-    s->nrows = s->p2p ? s->nlocal : cfg->nwalkers;
-    const size_t nw = (size_t)s->nrows;
-    if (cfg->move == KMC_MOVE_MIX) {
-        const MixTable mt = mix_table_of(*cfg);
-        CREATE_TRY(dev_alloc(s, (void**)&s->d_mix, sizeof(MixTable)));
-        CREATE_TRY(copy_sync(s->d_mix, &mt, sizeof(MixTable), hipMemcpyHostToDevice, s->stream));
-    }
-    if (s->p2p) {
-        CREATE_TRY(hipExtMallocWithFlags((void**)&s->d_flags, 4096, hipDeviceMallocFinegrained));
-        CREATE_TRY(hipMemsetAsync(s->d_flags, 0, 4096, s->stream));
-        CREATE_TRY(dev_alloc(s, (void**)&s->d_err, 64));
-        CREATE_TRY(hipMemsetAsync(s->d_err, 0, 64, s->stream));
-        // KMC_P2P_PUSH: local copies of the other shards, which their owners write; the menu densities' vector kernels carry it (anything
-        // else keeps the pull -- kmc_sampler_describe says which runs)
-        s->push = (cfg->flags & KMC_P2P_PUSH) != 0 && s->plan.vec && s->user == nullptr && !(cfg->flags & KMC_P2P_FINEGRAINED) &&
-                  s->cfg.shard_count > 1;
-    }
-    const size_t nt = (size_t)s->ntemps;                              // rungs: every per-walker array below holds nt ensembles
-    if (s->temper) {
-        const size_t nb = (2 * nt + 2 * (size_t)s->ld + 2 * nt + 2 + 2 * nt) * sizeof(double);
-        CREATE_TRY(dev_alloc(s, &s->d_betas, nb));
-        CREATE_TRY(hipMemsetAsync(s->d_betas, 0, nb, s->stream));
-        CREATE_TRY(copy_sync(s->d_betas, s->betas.data(), nt * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        s->d_rung_sum = s->d_betas + nt;
-        s->d_tsum = s->d_rung_sum + nt;
-        s->d_S = s->d_tsum + 2 * (size_t)s->ld;
-        s->d_round_acc = reinterpret_cast<unsigned long long*>(s->d_S + nt);
-        s->d_ticket = reinterpret_cast<unsigned int*>(s->d_round_acc + nt);
-        s->d_skipped = s->d_round_acc + nt + 1;
-        s->d_stage = reinterpret_cast<double*>(s->d_skipped + 1);
-        if (!s->S0.empty()) CREATE_TRY(copy_sync(s->d_S, s->S0.data(), s->S0.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        CREATE_TRY(dev_alloc(s, (void**)&s->d_nswap, nt * sizeof(unsigned long long)));
-        CREATE_TRY(hipMemsetAsync(s->d_nswap, 0, nt * sizeof(unsigned long long), s->stream));
-    }
-    const size_t ldz = (size_t)s->ld;
-    const size_t esz = s->f32 ? sizeof(float) : sizeof(double);      // element size of rows and chain
-    if (s->p2p && (cfg->flags & KMC_P2P_FINEGRAINED))   // peers map the rows uncached: nothing of them can go stale in a reader's L2
-        CREATE_TRY(hipExtMallocWithFlags((void**)&s->d_pos, nw * ldz * sizeof(double), hipDeviceMallocFinegrained));
-    else
-        CREATE_TRY(dev_alloc(s, &s->d_pos, (s->push ? 1 + (size_t)s->cfg.shard_count : nt) * nw * ldz * esz ));
-    CREATE_TRY(hipMemsetAsync(s->d_pos, 0, (s->push ? 1 + (size_t)s->cfg.shard_count : nt) * nw * ldz * esz, s->stream));   // the pad column of odd ndim stays 0
-    // per-walker block {logp[nrows], naccept[nrows], klast[nrows]}: one allocation, so the half-step kernels reach all
-    // three from one preloaded pointer (HalfStepFront::logp)
-    CREATE_TRY(dev_alloc(s, &s->d_logp, nt * nw * (sizeof(double) + 2 * sizeof(uint32_t))));
-    if (s->temper) CREATE_TRY(hipMemsetAsync(s->d_logp, 0, nt * nw * (sizeof(double) + 2 * sizeof(uint32_t)), s->stream));   // (every rung's counters)
-    s->d_naccept = reinterpret_cast<uint32_t*>(s->d_logp + nw);
-    s->d_klast = s->d_naccept + nw;
-    if (s->ragged_vec() && (reinterpret_cast<uint64_t>(s->d_logp) >> 48) != 0) {   // (kmc_launch.hip: front_of -- ndim rides in the 16 bits above this address)
-        kmc_sampler_destroy(s);
-        return fail(KMC_ERR_UNSUPPORTED, "device addresses beyond 2^48: the ragged vector kernels carry ndim in the upper 16 bits of a pointer");
-    }
-    CREATE_TRY(hipMemsetAsync(s->d_klast, 0, nw * sizeof(uint32_t), s->stream));
-    static_assert(kGraphChunk <= 64, "advance_schedule runs one 64-thread block");
-    CREATE_TRY(dev_alloc(s, &s->d_gen, 64));
-    CREATE_TRY(hipMemsetAsync(s->d_gen, 0, 64, s->stream));
-    CREATE_TRY(dev_alloc(s, &s->d_sched, (size_t)kGraphChunk * sizeof(SchedEntry)));
-    CREATE_TRY(hipMemsetAsync(s->d_naccept, 0, nw * sizeof(uint32_t), s->stream));
-    if (cfg->deal_count > 0) CREATE_TRY(dev_alloc(s, (void**)&s->d_ids, nw * sizeof(uint32_t)));
-    // Draw ring (kmc_kernels.hpp: kRing; possible for L = 16 / 32 with L / ITER >= 2): a wave computes its walkers' next steps' draws with its idle lanes and parks
-    // them, 4 slots x rows x 32 B; tags start at 0xffffffff (no step carries it), so nothing is "parked" yet.  Where it pays was re-measured in round 5
-    // (scripts/probes/ring_ab.py, profiles/r05_ring_ab.txt) -- since the launches carry their step among the preloaded parameters Philox starts at wave entry and the
-    // ring's entry is one more dependent load in front of the partner row: rows LOSE 2-7 % with it at ITER = 2 and at L = 32, exact-size and ragged alike (the ragged
-    // kernels gained 6-10 % from it only while their loads sat behind exec-mask regions and scalar waits; without those they behave like the exact-size ones), and
-    // 6-14 % in the large-ensemble geometries (ITER >= 4: bandwidth-bound, the ring is bytes); L = 16, ITER = 1 (C3's geometry) is +-1 % exact-size, -1..2 % ragged, and keeps it.
-    // KMC_DEBUG=ring=0|1 forces it off / on wherever the kernel has one.
-    bool want_ring = s->plan.vec && !two_launch_only(*cfg) && !s->islands && !s->resident && s->plan.L >= 16 && s->plan.L <= 32 && s->plan.L / s->plan.ITER >= 2;
-    {
-        std::string forced;
-        if (want_ring && debug_opt("ring", &forced)) want_ring = forced != "0";
-        else if (want_ring) want_ring = s->plan.L == 16 && s->plan.ITER == 1;
-    }
-    if (want_ring) {
-        const size_t nb = 4 * (size_t)s->nrows * 2 * sizeof(double2);
-        CREATE_TRY(dev_alloc(s, (void**)&s->d_ring, nb));
-        CREATE_TRY(hipMemsetAsync(s->d_ring, 0xff, nb, s->stream));
-    }
-    if (s->resident)                                 // the launch's draws come from a wide kernel (draw_table_fill, kmc_islands.hpp)
-        CREATE_TRY(dev_alloc(s, (void**)&s->d_draws, (size_t)kDrawTableGens * nw * 2 * sizeof(double2)));
-    if (cfg->flags & KMC_MOMENTS) {
-        CREATE_TRY(dev_alloc(s, &s->d_msum, (size_t)s->macc_elems * sizeof(double)));
-        CREATE_TRY(dev_alloc(s, &s->d_msumsq, (size_t)s->macc_elems * sizeof(double)));
-        CREATE_TRY(hipMemsetAsync(s->d_msum, 0, (size_t)s->macc_elems * sizeof(double), s->stream));
-        CREATE_TRY(hipMemsetAsync(s->d_msumsq, 0, (size_t)s->macc_elems * sizeof(double), s->stream));
-        if (s->plan.vec && s->plan.L == 64 && !s->islands && !s->resident && !debug_opt("no-moment-ring")) {
-            // moment ring for long rows (kmc_kernels.hpp, HalfStepArgs::mring): up to 128 posted rows per wave,
-            // within 512 MiB in all; swept every kSweepEvery generations
-            const int64_t nwaves = s->macc_stride / 64;
-            const size_t slot = (size_t)s->plan.K * 64 * sizeof(double2);       // one row
-            int64_t depth = (int64_t)(((size_t)1 << 29) / ((size_t)nwaves * slot));
-            if (depth > 128) depth = 128;
-            const long forced_depth = debug_opt_long("moment-ring-depth", 0);                         // tests: force overflows
-            if (forced_depth >= 1 && forced_depth < depth) depth = forced_depth;
-            if (depth >= 4 || (depth >= 2 && forced_depth > 0)) {
-                CREATE_TRY(dev_alloc(s, (void**)&s->d_mring, (size_t)nwaves * (size_t)depth * slot));
-                CREATE_TRY(dev_alloc(s, (void**)&s->d_mring_w, (size_t)nwaves * (size_t)depth * sizeof(double)));
-                CREATE_TRY(dev_alloc(s, (void**)&s->d_mcnt, 2 * (size_t)nwaves * sizeof(uint32_t)));
-                CREATE_TRY(hipMemsetAsync(s->d_mcnt, 0, 2 * (size_t)nwaves * sizeof(uint32_t), s->stream));
-                s->mring_depth = (int)depth;
-                s->mring_waves = nwaves;
-            }
-        }
-        if (s->islands || s->resident || s->fused) {
-            const size_t ne = (size_t)s->nislands * 4 * (size_t)s->island_K;
-            CREATE_TRY(dev_alloc(s, &s->d_isum, ne * sizeof(double)));
-            CREATE_TRY(dev_alloc(s, &s->d_isumsq, ne * sizeof(double)));
-            CREATE_TRY(hipMemsetAsync(s->d_isum, 0, ne * sizeof(double), s->stream));
-            CREATE_TRY(hipMemsetAsync(s->d_isumsq, 0, ne * sizeof(double), s->stream));
-        }
-    }
-    if (s->fused) {                                  // the second copy of the state (pad column of an odd ndim: 0 in both)
-        CREATE_TRY(dev_alloc(s, &s->d_pos2, nw * ldz * sizeof(double)));
-        CREATE_TRY(hipMemsetAsync(s->d_pos2, 0, nw * ldz * sizeof(double), s->stream));
-        CREATE_TRY(dev_alloc(s, &s->d_logp2, nw * sizeof(double)));
-        if (s->fused_L > 0) {
-            CREATE_TRY(dev_alloc(s, (void**)&s->d_glast, nw * sizeof(uint32_t)));
-            CREATE_TRY(hipMemsetAsync(s->d_glast, 0, nw * sizeof(uint32_t), s->stream));
-        }
-    }
-    if (s->data_eval) {
-        // (a likelihood-tempered ladder: every rung's proposals in one pass -- nt h rows, S and the prior apart -- and every rung's rows at set_positions)
-        const size_t np_half = nt * (size_t)s->h, np_all = nt * nw;
-        CREATE_TRY(dev_alloc(s, &s->d_prop, np_half * ldz * sizeof(double)));
-        CREATE_TRY(dev_alloc(s, &s->d_p1, (s->temper_like ? 2 : 1) * np_half * sizeof(double)));
-        // the plans are decided here, once (KMC_DEBUG=data-map may change later in the process: the kernels keep the geometry d_part was sized for)
-        s->plan_half = data_plan(s->data_ud, (int64_t)np_half);
-        s->plan_all = data_plan(s->data_ud, (int64_t)np_all);
-        s->part_doubles = std::max((size_t)s->plan_half.nblocks * np_half, (size_t)s->plan_all.nblocks * np_all);
-        CREATE_TRY(dev_alloc(s, &s->d_part, s->part_doubles * sizeof(double)));
-        if (s->temper_like) {
-            const size_t nb = (2 * np_all + nt) * sizeof(double);
-            CREATE_TRY(dev_alloc(s, &s->d_like, nb));
-            CREATE_TRY(hipMemsetAsync(s->d_like, 0, nb, s->stream));
-            s->d_prior = s->d_like + np_all;
-            s->d_like_sum = s->d_prior + np_all;
-        }
-    } else if (s->host_eval) {
-        CREATE_TRY(dev_alloc(s, &s->d_prop, (size_t)s->h * ldz * sizeof(double)));
-        CREATE_TRY(dev_alloc(s, &s->d_p1, (size_t)s->h * sizeof(double)));
-        CREATE_TRY(hipHostMalloc((void**)&s->h_prop, (size_t)s->h * (size_t)cfg->ndim * sizeof(double), hipHostMallocDefault));
-        CREATE_TRY(hipHostMalloc((void**)&s->h_p1, (size_t)s->h * sizeof(double), hipHostMallocDefault));
-        if (hipHostGetDevicePointer((void**)&s->h_prop_dev, s->h_prop, 0) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&s->h_p1_dev, s->h_p1, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            s->h_prop_dev = s->h_p1_dev = nullptr;          // (then every batch goes through the copies)
-        }
-        if (cfg->host_accepted) {
-            CREATE_TRY(dev_alloc(s, &s->d_acc, (size_t)s->h));
-            CREATE_TRY(hipHostMalloc((void**)&s->h_acc, (size_t)s->h, hipHostMallocDefault));
-        }
-    }
-    int64_t chain_slots = s->nsamples;
-    if ((cfg->flags & KMC_STREAM_CHAIN) && s->nsamples > 0) {
-        // a ring of three blocks; a block holds at least the samples of one launch unit (a graph replay), so a unit never
-        // touches more than two blocks, and about 512 MiB otherwise (measured at C2: 128 MiB blocks stream 22-26 GB/s at nthin = 10, 512 MiB blocks 43-45 GB/s of the
-        // 56 GB/s this link copies alone; many small blocks cost more at the block boundaries than their earlier start
-        // returns -- nthin = 100: +19 % on the loop with 64 MiB blocks, +6 % with 512 MiB; KMC_DEBUG=chain-block=n: samples per block, for tests)
-        const int64_t unit = s->resident ? 1 : std::max<int64_t>(kGraphChunk, s->uchunk);     // (a resident launch is cut to the block: kmc_sampler_run)
-        const int64_t per_unit = (unit + cfg->nthin - 1) / cfg->nthin + 1;
-        const size_t sample_bytes = (size_t)s->nlocal * ldz * sizeof(double);
-        int64_t blk = (int64_t)(((size_t)512 << 20) / sample_bytes);
-        if (blk < 1) blk = 1;
-        if (blk > 4096) blk = 4096;
-        { const long v = debug_opt_long("chain-block", 0); if (v >= 1) blk = v; }
-        if (blk < per_unit) blk = per_unit;
-        s->stream_chain = true;
-        s->stream_by_walker = (cfg->flags & KMC_CHAIN_BY_WALKER) != 0;
-        if (s->stream_by_walker) {
-            if (cfg->flags & KMC_STORE_CHAIN) CREATE_TRY(dev_alloc(s, &s->bw_scratch, (size_t)blk * (size_t)s->nlocal * (size_t)cfg->ndim * sizeof(double)));
-            if (cfg->flags & KMC_STORE_LOGP) CREATE_TRY(dev_alloc(s, &s->bw_scratch_logp, (size_t)blk * (size_t)s->nlocal * sizeof(double)));
-        } else if (!s->stream_by_walker && (cfg->flags & KMC_STORE_CHAIN) && s->ld != cfg->ndim) {
-            CREATE_TRY(dev_alloc(s, &s->bw_scratch, (size_t)blk * (size_t)s->nlocal * (size_t)cfg->ndim * sizeof(double)));   // (rows_compact)
-        }
-        s->ring_blk = blk;
-        s->ring_slots = 3 * blk;
-        chain_slots = s->ring_slots;
-        CREATE_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 3; ++i) {
-            CREATE_TRY(hipEventCreateWithFlags(&s->ev_filled[i], hipEventDisableTiming));
-            CREATE_TRY(hipEventCreateWithFlags(&s->ev_copied[i], hipEventDisableTiming));
-        }
-    }
-    if ((cfg->flags & (KMC_STORE_CHAIN | KMC_STORE_LOGP)) && s->nsamples > 0) {
-        // A chain that cannot fit is refused HERE, not by a failing hipMalloc: after a failed allocation of hundreds of GB the
-        // runtime aborted the process a few calls later (observed: 4 of 5 runs, in the first HIP call of the next sampler).
-        size_t free_b = 0, total_b = 0;
-        CREATE_TRY(hipMemGetInfo(&free_b, &total_b));
-        const size_t need = (size_t)chain_slots * (size_t)s->nlocal *
-                            (((cfg->flags & KMC_STORE_CHAIN) ? ldz * esz : 0) + ((cfg->flags & KMC_STORE_LOGP) ? sizeof(double) : 0));
-        if (need > free_b) {
-            kmc_status r_ = fail(KMC_ERR_OOM, "the chain needs " + std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) +
-                                              (s->nblob > 0 ? " MiB are free: thin it (nthin)" : " MiB are free: thin it (nthin), or stream it to host memory (KMC_STREAM_CHAIN)"));
-            kmc_sampler_destroy(s);
-            return r_;
-        }
-    }
-    if ((cfg->flags & KMC_STORE_CHAIN) && s->nsamples > 0)
-        CREATE_TRY(dev_alloc(s, &s->d_chain, (size_t)chain_slots * (size_t)s->nlocal * ldz * esz));
-    if ((cfg->flags & KMC_STORE_LOGP) && s->nsamples > 0)
-        CREATE_TRY(dev_alloc(s, &s->d_chain_logp, (size_t)chain_slots * (size_t)s->nlocal * sizeof(double)));
-    if (s->nblob > 0) {
-        CREATE_TRY(dev_alloc(s, &s->d_blob, nw * (size_t)s->nblob * sizeof(double)));
-        CREATE_TRY(hipMemsetAsync(s->d_blob, 0, nw * (size_t)s->nblob * sizeof(double), s->stream));
-        if ((cfg->flags & KMC_STORE_BLOBS) && s->nsamples > 0) {
-            const size_t need_b = (size_t)s->nsamples * (size_t)s->nlocal * (size_t)s->nblob * sizeof(double);
-            size_t free_b = 0, total_b = 0;
-            CREATE_TRY(hipMemGetInfo(&free_b, &total_b));
-            if (need_b > free_b) {
-                kmc_status r_ = fail(KMC_ERR_OOM, "the stored blobs need " + std::to_string(need_b >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB are free: thin the chain (nthin)");
-                kmc_sampler_destroy(s);
-                return r_;
-            }
-            CREATE_TRY(dev_alloc(s, &s->d_chain_blob, need_b));
-        }
-    }
-    CREATE_TRY(hipStreamSynchronize(s->stream));         // the fills above (asynchronous, one wait for all of them)
-#undef CREATE_TRY
+    setup_generation(s);
+    setup_launch_geometry(s);
+    // its device state
+    KMC_TRY(create_stream(s));
+    KMC_TRY(alloc_exchange(s));
+    KMC_TRY(alloc_tempering(s));
+    KMC_TRY(alloc_state(s));
+    KMC_TRY(alloc_draws(s));
+    KMC_TRY(alloc_moments(s));
+    KMC_TRY(alloc_second_state(s));
+    if (s->data_eval) KMC_TRY(alloc_data_route(s));
+    else if (s->host_eval) KMC_TRY(alloc_host_route(s));
+    KMC_TRY(alloc_chain(s));
+    HIP_TRY(hipStreamSynchronize(s->stream));         // the fills above (asynchronous, one wait for all of them)
     if (s->p2p) {
         s->peer_pos[s->cfg.shard_rank] = s->d_pos;
         s->peer_flags[s->cfg.shard_rank] = s->d_flags;
         s->connected = s->cfg.shard_count == 1;
     }
-    *out = s;
+    *out = owner.release();
     return KMC_OK;
 }
 
@@ -863,7 +1014,7 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
     // streams may still have in flight on them -- a caller's stream bound earlier (kmc_sampler_set_stream), a framework's
     // collectives on a replica shard's rows -- is waited for here; a plain single-GPU sampler (its own stream only) pays nothing.
     if (s->foreign_stream_seen || s->cfg.shard_count > 1 || s->comm) (void)hipDeviceSynchronize();
-    if (!s->guards.empty() && s->stream) check_guards(s);
+    if (s->stream) check_guards(s);
     drop_updated_graph(s);
     if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
     s->uk.keep.reset();                 // (the module goes when its last holder does: the density's cache, other samplers)
@@ -876,12 +1027,7 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
             if (s->peer_pos[r]) (void)hipIpcCloseMemHandle(s->peer_pos[r]);
             if (s->peer_flags[r]) (void)hipIpcCloseMemHandle(s->peer_flags[r]);
         }
-        cache_free(s->d_flags);
-        cache_free(s->d_err);
     }
-    cache_free(s->d_mix);
-    cache_free(s->d_betas);
-    cache_free(s->d_nswap);
     if (s->comm) { rccl_comm_destroy(s->comm); s->comm = nullptr; }
     if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
     for (int i = 0; i < 3; ++i) {
@@ -889,36 +1035,14 @@ KMC_EXPORT void kmc_sampler_destroy(kmc_sampler* s)
         if (s->ev_copied[i]) (void)hipEventDestroy(s->ev_copied[i]);
     }
     chain_unregister(s);
-    if (s->own_pos) cache_free(s->d_pos);
-    cache_free(s->d_logp);          // the {logp, naccept, klast} block
-    cache_free(s->d_mring);
-    cache_free(s->d_ids);
-    cache_free(s->d_mring_w);
-    cache_free(s->d_mcnt);
-    cache_free(s->d_gen);
-    cache_free(s->d_sched);
-    cache_free(s->d_chain);
-    cache_free(s->bw_scratch);
-    cache_free(s->bw_scratch_logp);
-    cache_free(s->d_chain_logp);
-    cache_free(s->d_blob);
-    cache_free(s->d_chain_blob);
-    cache_free(s->d_msum);
-    cache_free(s->d_msumsq);
-    cache_free(s->d_ring);
-    cache_free(s->d_draws);
-    cache_free(s->d_isum);
-    cache_free(s->d_isumsq);
-    cache_free(s->d_pos2);
-    cache_free(s->d_logp2);
-    cache_free(s->d_glast);
-    cache_free(s->d_prop);
-    cache_free(s->d_p1);
-    cache_free(s->d_part);
-    cache_free(s->d_like);
+    for (const DevAlloc& a : s->allocs) cache_free(a.p);              // everything dev_alloc handed out (a bound d_pos is not the sampler's: not in the list)
+    // ... and what did not come from it: the fine-grained P2P buffers and the page-locked host arrays
+    if (s->p2p) {
+        cache_free(s->d_flags);
+        if ((s->cfg.flags & KMC_P2P_FINEGRAINED) && s->own_pos) cache_free(s->d_pos);
+    }
     if (s->h_prop) (void)hipHostFree(s->h_prop);
     if (s->h_p1) (void)hipHostFree(s->h_p1);
-    cache_free(s->d_acc);
     if (s->h_acc) (void)hipHostFree(s->h_acc);
     for (int i = 0; i < kHostPieces; ++i) if (s->host_ev[i]) (void)hipEventDestroy(s->host_ev[i]);
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -950,11 +1074,7 @@ KMC_EXPORT kmc_status kmc_sampler_bind_positions(kmc_sampler* s, void* pos_dev)
     if (s->graph_exec) { (void)hipGraphExecDestroy(s->graph_exec); s->graph_exec = nullptr; }
     if (s->graph) { (void)hipGraphDestroy(s->graph); s->graph = nullptr; }
     drop_updated_graph(s);                                              // (ensure_updated_graph builds it anew)
-    if (s->own_pos) {
-        for (size_t i = 0; i < s->guards.size(); ++i)                   // (KMC_DEBUG=poison: this allocation's guard goes with it)
-            if (s->guards[i].first - s->guards[i].second == reinterpret_cast<char*>(s->d_pos)) { s->guards.erase(s->guards.begin() + (long)i); break; }
-        cache_free(s->d_pos);
-    }
+    if (s->own_pos) dev_free(s, s->d_pos);                              // (out of the allocation record: its guard, under KMC_DEBUG=poison, goes with it)
     s->d_pos = static_cast<double*>(pos_dev);
     s->own_pos = false;
     s->pos2_current = false;
@@ -1087,6 +1207,26 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
         o << "; replica shard " << s->cfg.shard_rank << "/" << s->cfg.shard_count
           << (s->comm ? ((s->comm_graph_ok && !(s->cfg.flags & KMC_NO_GRAPH) && s->launch_mode != 2) ? ", RCCL all-gather of the updated half after every half-step (captured in the graph)"
                                                                                                          : ", RCCL all-gather of the updated half after every half-step (enqueued launch by launch)") : "");
+    if (debug_opt("geometry")) {
+        // what creation derived from the configuration and the text above does not show (tests/test_gpu_create_routes.py pins it); nothing
+        // that depends on the machine: no addresses, no word on whether pinned host memory got a device alias
+        const Plan& p = s->plan;
+        auto data_plan_text = [](const DataPlan& d) { return std::to_string((int)d.obs) + "/" + std::to_string(d.rounds) + "/" + std::to_string(d.nblocks); };
+        o << "; geometry: plan=" << (p.vec ? "vec" : "generic") << "/" << p.L << "/" << p.K << "/" << p.ITER << "/" << (p.ragged ? "ragged" : "exact")
+          << " tpb=" << s->tpb << " grid=" << s->grid << " macc_stride=" << s->macc_stride << " macc_elems=" << s->macc_elems << " vec_lds=" << s->vec_lds
+          << " nrows=" << s->nrows << " resident=" << s->resident << " resident_tpb=" << s->resident_tpb << " resident_lane=" << s->resident_lane
+          << " resident_lane2=" << s->resident_lane2 << " islands=" << s->islands << " island_K=" << s->island_K << " island_ragged=" << s->island_ragged
+          << " nislands=" << s->nislands << " island_lds=" << s->island_lds << " fused=" << s->fused << " fused_L=" << s->fused_L
+          << " fused_tpb=" << s->fused_tpb << " fused_fold=" << s->fused_fold << " mring_depth=" << s->mring_depth << " mring_waves=" << s->mring_waves
+          << " ring_blk=" << s->ring_blk << " ring_slots=" << s->ring_slots << " stream_by_walker=" << s->stream_by_walker << " push=" << s->push
+          << " part_doubles=" << s->part_doubles << " plan_half=" << data_plan_text(s->plan_half) << " plan_all=" << data_plan_text(s->plan_all);
+        const std::pair<const char*, const void*> bufs[] = {
+            {"d_ring", s->d_ring}, {"d_draws", s->d_draws}, {"d_pos2", s->d_pos2}, {"d_glast", s->d_glast}, {"d_isum", s->d_isum}, {"d_msum", s->d_msum},
+            {"d_mring", s->d_mring}, {"bw_scratch", s->bw_scratch}, {"bw_scratch_logp", s->bw_scratch_logp}, {"d_ids", s->d_ids}, {"d_mix", s->d_mix},
+            {"d_like", s->d_like}, {"d_acc", s->d_acc}, {"d_prop", s->d_prop}, {"d_part", s->d_part}, {"d_betas", s->d_betas}, {"d_chain", s->d_chain},
+            {"d_chain_logp", s->d_chain_logp}, {"d_blob", s->d_blob}, {"d_chain_blob", s->d_chain_blob}, {"d_err", s->d_err}};
+        for (const auto& b : bufs) o << " " << b.first << "=" << (b.second != nullptr);
+    }
     const std::string t = o.str();
     std::snprintf(buf, (size_t)buflen, "%s", t.c_str());
     return KMC_OK;

@@ -51,6 +51,13 @@ struct DataPlan {
 };
 constexpr int64_t kDataMaxDim = 32, kDataMaxCols = 16, kDataMaxRows = (int64_t)1 << 30;
 
+// one device buffer of a sampler; guarded (KMC_DEBUG=poison): kGuardBytes of 0xA5 follow its `bytes`
+struct DevAlloc {
+    void* p = nullptr;
+    size_t bytes = 0;
+    bool guarded = false;
+};
+
 }  // namespace kmc_host
 
 struct kmc_sampler {
@@ -132,7 +139,7 @@ struct kmc_sampler {
     unsigned vec_lds = 0;          // dynamic LDS of the vector kernel (a function body evaluated per walker: one tile of proposals per wave)
     bool updated_refused = false;  // a runtime-compiled kernel the runtime would not take as a graph kernel node: table graph / eager only
     bool budget_fallback = false;  // this sampler left (or never entered) the updated-graph mode because the process budget was spent
-    std::vector<std::pair<char*, size_t>> guards;      // KMC_DEBUG=poison: (guard address, size of the allocation in front of it)
+    std::vector<kmc_host::DevAlloc> allocs;            // every device buffer dev_alloc handed out (kmc_sampler.hip): what kmc_sampler_destroy frees and check_guards reads
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_run_events = false;
     bool positions_set = false;
