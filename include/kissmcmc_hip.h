@@ -934,6 +934,74 @@ kmc_status  kmc_cov_plan(int64_t ncols, int32_t* tile_cols, int32_t* strip_tiles
  * operation order above, so that a restatement in another language gives the same bits.  corr must not overlap cov. */
 kmc_status  kmc_cov_correlation(int64_t ncols, const double* cov, double* corr, double* sd);
 
+/* ---- pointwise log-likelihoods of a data density over a stored chain; WAIC ----
+ * What a model comparison needs from a fit with KMC_DATA_DENSITY, computed where the chain, the observations and the compiled term are.
+ *
+ * Rows: the stored samples first_sample, first_sample + thin, ... (thin >= 1) of the walkers in the mask, sample by sample, walkers
+ * ascending: n rows, n >= 2.  Observations: the density's own J = ndata rows d_j, or, when `data` is not NULL, a held-out array
+ * [ndata2][ncols2] uploaded for the call (ncols2 must be the density's ncols; J = ndata2).
+ * Terms: l[r][j] = term(x_r, ndim, d_j, p), the user's term body as the sampler's kernels compile it (same source, -ffp-contract=off,
+ * -O3): for a body of + - * only it equals a host evaluation bit for bit.  The prior takes no part.
+ *
+ * Per observation, two passes over the rows, the second centred on what the first found:
+ *   pass 1:  M_j  = max_r l[r][j]   (exact; NaN when a term is NaN),     S1_j = sum_r l[r][j]
+ *   pass 2:  E_j  = sum_r exp(l[r][j] - M_j)   (every row contributes 0.0 when M_j == -inf),
+ *            V_j  = sum_r (l[r][j] - S1_j / n)^2
+ * stats is [4][J]: M, S1, E, V.  The host stage (kmc_waic_stats; no device, every operation in this order, log and sqrt the C
+ * library's, so that a restatement in another language gives the same bits):
+ *   lppd_j   = M_j + (log(E_j) - log(n))
+ *   p_waic_j = V_j / (n - 1)                  the sample variance: n - 1 as in BDA3 and the R package loo (ArviZ divides by n)
+ *   elpd_j   = lppd_j - p_waic_j
+ *   lppd, p_waic, elpd_waic: the sums over j by the data-density contract's pairwise tree in observation order
+ *   se       = sqrt(J * tree_j((elpd_j - elpd_waic / J)^2) / (J - 1))          (NaN for J = 1)
+ *   waic     = -2 * elpd_waic
+ *   n_high   = #{j : p_waic_j > 0.4}  (loo's warning count);   n_nan = #{j : S1_j is NaN}
+ * IEEE rules, no special case beyond the one of E_j: a NaN, or a +inf next to a -inf, among the terms of an observation makes S1_j
+ * NaN, then every output of that observation is NaN and it counts in n_nan; a -inf among finite terms leaves lppd_j finite and makes
+ * p_waic_j NaN; an observation whose terms are all -inf has lppd_j = -inf.  A row outside the selection is never visited.
+ *
+ * The device stage.  One observation per lane, its d_j in registers; the rows are cut into nruns runs of
+ * run_len consecutive rows, from n and J alone (kmc_pointwise_plan).  A run is added up in row order from 0.0, the runs' partial
+ * results in run order from 0.0, by a second kernel: no floating-point atomics.  So two identical calls return the same bits, the
+ * selection (first_sample, thin, mask) gives the bits of the same call on the rows copied out, and kmc_sampler_pointwise_stats equals
+ * kmc_chain_pointwise_stats on the downloaded chain bit for bit.  Each sum is within (n + 4) 2^-53 sum |term| of the exact sum of its
+ * terms as computed.
+ *
+ * n_out (may be NULL) gets n; info (may be NULL) gets 6 numbers: the rows n, the runs, the terms evaluated (both passes), run_len, and
+ * the nanoseconds of pass 1 and of pass 2 on the device (events around each pass's partial kernel and fold; for benchmarks).
+ * KMC_ERR_BAD_ARG, naming the value: a sampler or density that is not a data density; ndim > 32; thin < 1; n < 2; first_sample
+ * outside [0, samples stored]; held-out data with ncols2 != ncols or ndata2 outside 1 .. 2^30; a null output.  KMC_ERR_UNSUPPORTED:
+ * n >= 2^40, and what the other chain read-outs refuse (no stored chain: KMC_ERR_BAD_ARG; a streamed chain; a sharded or P2P sampler;
+ * a host chain that does not fit the device).  For a host chain all of these are decided before the device is touched.  A
+ * likelihood-tempered sampler is fine: its chain is rung 0's, beta = 1. */
+kmc_status  kmc_sampler_pointwise_stats(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */,
+                                        int64_t thin, const double* data /* [ndata2][ncols2] or NULL */, int64_t ndata2, int32_t ncols2,
+                                        double* stats, int64_t* n_out, int64_t* info);
+/* The same on a chain in host memory, uploaded to `device` first, for the data density `density` with its parameters params[6]. */
+kmc_status  kmc_chain_pointwise_stats(kmc_user_density* density, const double* params, const double* chain_host /* [nsamples][nwalkers][ndim] */,
+                                      int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                                      int64_t thin, const double* data, int64_t ndata2, int32_t ncols2, int device, double* stats,
+                                      int64_t* n_out, int64_t* info);
+/* The matrix itself for the observations [obs_first, obs_first + obs_count): out [n][obs_count], dense (the way to PSIS-LOO outside the
+ * library).  Besides the refusals above, KMC_ERR_BAD_ARG for obs_count < 1 or a range outside [0, J), and KMC_ERR_UNSUPPORTED, naming
+ * the size, for a matrix that does not fit the device's free memory. */
+kmc_status  kmc_sampler_pointwise_loglike(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* data,
+                                          int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, double* out, int64_t* n_out);
+kmc_status  kmc_chain_pointwise_loglike(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                        int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                        const double* data, int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, int device,
+                                        double* out, int64_t* n_out);
+/* The cut of the two passes for n rows and ndata observations: run r covers the rows [r run_len, min(n, (r + 1) run_len)), and there
+ * are nruns of them; a wave carries `slots` runs side by side, each over lanes_per_run observations (64 and 1 from 64 observations up;
+ * below, the next power of two >= ndata and 64 over it), so nwaves = ceil(nruns / slots) waves walk the rows, wave w with the runs
+ * w slots .. w slots + slots - 1.  Needs no device; pointers may be NULL.  KMC_ERR_BAD_ARG for n < 2 or ndata outside 1 .. 2^30,
+ * KMC_ERR_UNSUPPORTED for n >= 2^40. */
+kmc_status  kmc_pointwise_plan(int64_t n, int64_t ndata, int64_t* run_len, int64_t* nruns, int32_t* lanes_per_run, int32_t* slots,
+                               int64_t* nwaves);
+/* The host stage; needs no device.  stats [4][J] -> lppd_j, p_waic_j, elpd_j [J] (each may be NULL) and totals [7]: lppd, p_waic,
+ * elpd_waic, se, waic, n_high, n_nan.  KMC_ERR_BAD_ARG for J < 1, n < 2 or a null stats / totals. */
+kmc_status  kmc_waic_stats(int64_t J, int64_t n, const double* stats, double* lppd_j, double* p_waic_j, double* elpd_j, double* totals);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

@@ -15,6 +15,7 @@ from .densities import (CDensity, DataDensity, DeviceLogPdf, Exponential, ExprDe
 from .chain_convergence import convergence, convergence_stats, error_of_estimated_mean, evaluate_convergence, lag_sums, samples_vs_tau
 from .chain_convergence import normal_scores, rank_convergence, rank_plan, rank_scores
 from .chain_covariance import correlation, cov_plan, covariance
+from .chain_predictive import compare_waic, pointwise_loglike, pointwise_plan, pointwise_stats, waic, waic_stats
 from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
@@ -30,6 +31,7 @@ __all__ = [
     "convergence", "convergence_stats", "lag_sums", "evaluate_convergence", "error_of_estimated_mean", "samples_vs_tau",
     "rank_convergence", "rank_scores", "rank_plan", "normal_scores",
     "covariance", "correlation", "cov_plan",
+    "waic", "pointwise_loglike", "pointwise_stats", "compare_waic", "waic_stats", "pointwise_plan",
 ]
 
 

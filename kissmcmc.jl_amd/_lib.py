@@ -65,6 +65,8 @@ SYMBOLS = [
     "kmc_rank_plan", "kmc_rank_normal_scores", "kmc_sampler_rank_scores", "kmc_chain_rank_scores", "kmc_sampler_rank_convergence",
     "kmc_chain_rank_convergence",
     "kmc_sampler_covariance", "kmc_chain_covariance", "kmc_cov_plan", "kmc_cov_correlation",
+    "kmc_sampler_pointwise_stats", "kmc_chain_pointwise_stats", "kmc_sampler_pointwise_loglike", "kmc_chain_pointwise_loglike",
+    "kmc_pointwise_plan", "kmc_waic_stats",
 ]
 
 
@@ -298,6 +300,14 @@ def lib() -> C.CDLL:
     L.kmc_chain_covariance.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int, dp, dp, ip, ip]
     L.kmc_cov_plan.argtypes = [C.c_int64, i32p, i32p, i32p, i32p]
     L.kmc_cov_correlation.argtypes = [C.c_int64, dp, dp, dp]
+    held_out = [dp, C.c_int64, C.c_int32]
+    host_chain = [vp, dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int64]
+    L.kmc_sampler_pointwise_stats.argtypes = [vp, C.c_int64, bp, C.c_int64] + held_out + [dp, ip, ip]
+    L.kmc_chain_pointwise_stats.argtypes = host_chain + held_out + [C.c_int, dp, ip, ip]
+    L.kmc_sampler_pointwise_loglike.argtypes = [vp, C.c_int64, bp, C.c_int64] + held_out + [C.c_int64, C.c_int64, dp, ip]
+    L.kmc_chain_pointwise_loglike.argtypes = host_chain + held_out + [C.c_int64, C.c_int64, C.c_int, dp, ip]
+    L.kmc_pointwise_plan.argtypes = [C.c_int64, C.c_int64, ip, ip, i32p, i32p, ip]
+    L.kmc_waic_stats.argtypes = [C.c_int64, C.c_int64, dp, dp, dp, dp, dp]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

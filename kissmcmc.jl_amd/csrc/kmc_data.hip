@@ -10,11 +10,7 @@
 using namespace kmc;
 using namespace kmc_host;
 
-namespace {
-constexpr int kDataTPB = kmc_data::kWaves * 64;
-// A cap on the partial kernel's grid: above it, more rounds per wave.  Not the residency: a 4-wave workgroup of ~86 VGPRs fits 5 per CU (5 waves
-// per SIMD), 1 280 at once on 256 CUs, so a grid near the cap runs one full round and a partial tail round (S2: 1 568 = 1 280 + 288).
-constexpr int64_t kTargetGroups = 2048;
+namespace kmc_host {
 
 std::string data_functor_source(const kmc_user_density* ud)
 {
@@ -26,6 +22,14 @@ std::string data_functor_source(const kmc_user_density* ud)
         << (ud->data_prior.empty() ? std::string("return 0.0;") : ud->data_prior) << "\n  }\n};\n}\n";
     return src.str();
 }
+
+}  // namespace kmc_host
+
+namespace {
+constexpr int kDataTPB = kmc_data::kWaves * 64;
+// A cap on the partial kernel's grid: above it, more rounds per wave.  Not the residency: a 4-wave workgroup of ~86 VGPRs fits 5 per CU (5 waves
+// per SIMD), 1 280 at once on 256 CUs, so a grid near the cap runs one full round and a partial tail round (S2: 1 568 = 1 280 + 288).
+constexpr int64_t kTargetGroups = 2048;
 
 kmc_status compile_data(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
 {
@@ -59,6 +63,26 @@ kmc_status compile_data(kmc_user_density* ud, int64_t ndim, const std::vector<ch
 
 namespace kmc_host {
 
+// the observations on device `dev` (the current one): uploaded on first use, shared by everything over this density
+kmc_status data_on_device(kmc_user_density* ud, int dev, std::shared_ptr<void>* keep)
+{
+    std::lock_guard<std::mutex> lock(ud->mu);
+    auto& dslot = ud->data_dev[dev];
+    if (!dslot) {
+        const size_t bytes = ud->data.size() * sizeof(double);
+        void* p = nullptr;
+        KMC_TRY(check_device_room(bytes, "the data of a data density"));
+        HIP_TRY(hipMalloc(&p, bytes));
+        ScopedStream ss;
+        hipError_t e = ss.create();
+        if (e == hipSuccess) e = copy_sync(p, ud->data.data(), bytes, hipMemcpyHostToDevice, ss.st);
+        if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
+        dslot = std::shared_ptr<void>(p, [dev](void* q) { int cur = 0; (void)hipGetDevice(&cur); (void)hipSetDevice(dev); (void)hipFree(q); (void)hipSetDevice(cur); });
+    }
+    *keep = dslot;
+    return KMC_OK;
+}
+
 kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk)
 {
     const std::vector<char>* code = nullptr;
@@ -74,21 +98,9 @@ kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk)
             slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
         }
         dk->keep = slot;
-        auto& dslot = ud->data_dev[dev];
-        if (!dslot) {
-            const size_t bytes = ud->data.size() * sizeof(double);
-            void* p = nullptr;
-            KMC_TRY(check_device_room(bytes, "the data of a data density"));
-            HIP_TRY(hipMalloc(&p, bytes));
-            ScopedStream ss;
-            hipError_t e = ss.create();
-            if (e == hipSuccess) e = copy_sync(p, ud->data.data(), bytes, hipMemcpyHostToDevice, ss.st);
-            if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
-            dslot = std::shared_ptr<void>(p, [dev](void* q) { int cur = 0; (void)hipGetDevice(&cur); (void)hipSetDevice(dev); (void)hipFree(q); (void)hipSetDevice(cur); });
-        }
-        dk->keep_data = dslot;
-        dk->data = static_cast<const double*>(dslot.get());
     }
+    KMC_TRY(data_on_device(ud, dev, &dk->keep_data));
+    dk->data = static_cast<const double*>(dk->keep_data.get());
     hipModule_t mod = static_cast<hipModule_t>(dk->keep.get());
     HIP_TRY(hipModuleGetFunction(&dk->lane, mod, "kmc_data_lane"));
     HIP_TRY(hipModuleGetFunction(&dk->obs, mod, "kmc_data_obs"));

@@ -160,8 +160,14 @@ inline kmc_status check_device_room(size_t need, const char* what)
 // a private non-blocking stream for the duration of one call
 struct ScopedStream {
     hipStream_t st = nullptr;
+    hipStream_t borrowed = nullptr;      // ... or a stream the caller owns and has drained: synchronised at the end, not destroyed
     hipError_t create() { return hipStreamCreateWithFlags(&st, hipStreamNonBlocking); }
-    ~ScopedStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+    hipStream_t get() const { return st ? st : borrowed; }
+    ~ScopedStream()
+    {
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+        else if (borrowed) (void)hipStreamSynchronize(borrowed);
+    }
 };
 
 // hiprtc compilation of `text` (+ named headers) for gfx950, with a DISK CACHE of the code objects: a script that defines its

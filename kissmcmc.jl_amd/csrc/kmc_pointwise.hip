@@ -1,0 +1,368 @@
+// kmc_pointwise.hip -- the pointwise log-likelihood of a data density over a stored chain, on the device where the chain, the data and
+// the compiled term are: the per-observation statistics behind WAIC (kmc_sampler_pointwise_stats, kmc_chain_pointwise_stats), the
+// matrix itself for a range of observations (kmc_sampler_pointwise_loglike, kmc_chain_pointwise_loglike), the plan (kmc_pointwise_plan)
+// and the pure host stage (kmc_waic_stats).  include/kissmcmc_hip.h has the definitions, DESIGN.md section 4k the plan.  Kernels:
+// kmc_pointwise.hpp, compiled at run time with the density's term as the module "pointwise:<ndim>".
+#include <algorithm>
+#include <cmath>
+#include <sstream>
+#include <vector>
+
+#include "kmc_chain_view.hpp"
+#include "kmc_pointwise.hpp"
+
+using namespace kmc_host;
+using namespace kmc_chain_view;
+using namespace kmc_pw;
+
+namespace {
+
+constexpr int64_t kPwTargetWaves = 4096;          // of one pass: 4 per SIMD of 256 compute units
+constexpr int64_t kPwMinRun = 16;                 // rows of a run at least: a run loads d_j once and writes two partials
+constexpr int64_t kPwMatrixWaves = 65536;         // pw_matrix: waves along the rows at most
+
+// the cut of n rows and J observations: from n and J alone
+struct PwPlan {
+    int64_t run_len = 0, nruns = 0, nwaves = 0;   // nwaves: along the rows, each over ceil(J / 64) groups of observations
+    int32_t lanes = 64, slots = 1, jp_log2 = 6;   // packed (J < 64): lanes = Jp observations per run slot, slots = 64 / Jp
+    bool packed = false;
+};
+
+PwPlan pw_plan(int64_t n, int64_t J)
+{
+    PwPlan p;
+    p.packed = J < 64;
+    if (p.packed) {
+        p.jp_log2 = 0;
+        while (((int64_t)1 << p.jp_log2) < J) ++p.jp_log2;
+        p.lanes = 1 << p.jp_log2;
+        p.slots = 64 / p.lanes;
+    }
+    const int64_t groups = (J + 63) / 64;
+    const int64_t max_runs = std::max<int64_t>(1, kPwTargetWaves / groups);
+    p.run_len = std::max(kPwMinRun, (n + max_runs - 1) / max_runs);
+    p.nruns = (n + p.run_len - 1) / p.run_len;
+    p.nwaves = (p.nruns + p.slots - 1) / p.slots;
+    return p;
+}
+
+struct PwKernels {
+    std::shared_ptr<void> keep, keep_data;
+    hipFunction_t pass[2][2] = {};                // [pass - 1][packed]
+    hipFunction_t matrix = nullptr;
+};
+
+kmc_status compile_pointwise(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
+{
+    const std::string key = "pointwise:" + std::to_string(ndim);
+    std::lock_guard<std::mutex> lock(ud->mu);
+    auto it = ud->code.find(key);
+    if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
+    const std::string dir = user_header_dir();
+    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_pw = read_file(dir + "/kmc_pointwise.hpp");
+    if (h_dev.empty() || h_pw.empty()) return fail(KMC_ERR_BAD_ARG, "data density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
+    const std::string t = "<UserData, " + std::to_string(ndim) + ", " + std::to_string(ud->ncols);
+    const std::string head = "extern \"C\" __global__ __launch_bounds__(" + std::to_string(kPwThreads) + ") void ";
+    std::ostringstream src;
+    src << "#include \"kmc_pointwise.hpp\"\n" << data_functor_source(ud)
+        << head << "kmc_pw_pass1(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, false>(a); }\n"
+        << head << "kmc_pw_pass2(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, false>(a); }\n"
+        << head << "kmc_pw_pass1_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, true>(a); }\n"
+        << head << "kmc_pw_pass2_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, true>(a); }\n"
+        << head << "kmc_pw_matrix(const kmc_pw::PwArgs a) { kmc_pw::pw_matrix" << t << ">(a); }\n";
+    const char* headers[2] = {h_dev.c_str(), h_pw.c_str()};
+    const char* names[2] = {"kmc_device.hpp", "kmc_pointwise.hpp"};
+    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
+    std::vector<char> code;
+    std::string log;
+    const kmc_status cst = rtc_compile_cached(src.str(), "kmc_pointwise.hip", 2, headers, names, 4, opts, &code, &log);
+    if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "data density does not compile:\n" + log);
+    if (cst != KMC_OK) return cst;
+    auto ins = ud->code.emplace(key, std::move(code));
+    *out = &ins.first->second;
+    return KMC_OK;
+}
+
+// compile (cached) + module on the current device + the device copy of the density's own observations
+kmc_status load_pointwise(kmc_user_density* ud, int64_t ndim, bool own_data, PwKernels* pk)
+{
+    const std::vector<char>* code = nullptr;
+    KMC_TRY(compile_pointwise(ud, ndim, &code));
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    {
+        std::lock_guard<std::mutex> lock(ud->mu);
+        auto& slot = ud->modules[{static_cast<const void*>(code), dev}];
+        if (!slot) {
+            hipModule_t m = nullptr;
+            HIP_TRY(hipModuleLoadData(&m, code->data()));
+            slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
+        }
+        pk->keep = slot;
+    }
+    if (own_data) KMC_TRY(data_on_device(ud, dev, &pk->keep_data));
+    hipModule_t mod = static_cast<hipModule_t>(pk->keep.get());
+    HIP_TRY(hipModuleGetFunction(&pk->pass[0][0], mod, "kmc_pw_pass1"));
+    HIP_TRY(hipModuleGetFunction(&pk->pass[1][0], mod, "kmc_pw_pass2"));
+    HIP_TRY(hipModuleGetFunction(&pk->pass[0][1], mod, "kmc_pw_pass1_packed"));
+    HIP_TRY(hipModuleGetFunction(&pk->pass[1][1], mod, "kmc_pw_pass2_packed"));
+    HIP_TRY(hipModuleGetFunction(&pk->matrix, mod, "kmc_pw_matrix"));
+    return KMC_OK;
+}
+
+__global__ __launch_bounds__(256) void pw_fold(const PwArgs a, int pass) { pw_fold_body(a, pass); }
+
+// the device copies one call owns, beyond the chain's: the list of selected walkers, held-out observations, the work space
+struct PwBuffers : ChainUpload {
+    int32_t* sel = nullptr;
+    double *data = nullptr, *work = nullptr;
+    ~PwBuffers() { (void)hipFree(sel); (void)hipFree(data); (void)hipFree(work); }
+};
+
+// the events around the two passes, for info: each pass is its partial kernel and its fold
+struct PassEvents {
+    hipEvent_t e[3] = {};
+    hipError_t create()
+    {
+        for (auto& x : e) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
+        return hipSuccess;
+    }
+    ~PassEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// what the two calls ask for beyond the chain
+struct PwRequest {
+    kmc_user_density* ud = nullptr;
+    const double* params = nullptr;               // 6
+    int64_t first_sample = 0, thin = 1;
+    const uint8_t* walker_mask = nullptr;
+    const double* data = nullptr;                 // held-out observations [ndata2][ncols2] or nullptr
+    int64_t ndata2 = 0;
+    int32_t ncols2 = 0;
+    bool matrix = false;
+    int64_t obs_first = 0, obs_count = 0;
+};
+
+// stats [4][J] (statistics), or out [n][obs_count] (matrix)
+kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result, int64_t* n_out, int64_t* info)
+{
+    if (!q.ud || !q.ud->is_data) return fail(KMC_ERR_BAD_ARG, "the pointwise log-likelihood needs a data density (kmc_data_density_create): other densities have no per-observation term");
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    if (v.ndim > kDataMaxDim) return fail(KMC_ERR_BAD_ARG, "a data density takes at most " + std::to_string(kDataMaxDim) + " dimensions (ndim = " + std::to_string(v.ndim) + ")");
+    if (q.thin < 1) return fail(KMC_ERR_BAD_ARG, "thin must be >= 1 (thin = " + std::to_string(q.thin) + ")");
+    int64_t n_all = 0;
+    KMC_TRY(selection_size(v, q.first_sample, q.walker_mask, &n_all));
+    const int64_t kept = (v.nsamples - q.first_sample + q.thin - 1) / q.thin;
+    const int64_t nsel = n_all / (v.nsamples - q.first_sample);
+    const int64_t n = kept * nsel;
+    if (n < 2) return fail(KMC_ERR_BAD_ARG, "the pointwise statistics need at least 2 selected rows (n = " + std::to_string(n) + ")");
+    if (n >= ((int64_t)1 << 40)) return fail(KMC_ERR_UNSUPPORTED, "too many rows for one pointwise call: n = " + std::to_string(n) + ", the limit is 2^40");
+    int64_t J = q.ud->ndata;
+    if (q.data) {
+        if (q.ncols2 != q.ud->ncols)
+            return fail(KMC_ERR_BAD_ARG, "held-out data of " + std::to_string(q.ncols2) + " columns: the density's observations have " + std::to_string(q.ud->ncols));
+        if (q.ndata2 < 1 || q.ndata2 > kDataMaxRows) return fail(KMC_ERR_BAD_ARG, "held-out data: ndata must be in 1 .. 2^30 (ndata = " + std::to_string(q.ndata2) + ")");
+        J = q.ndata2;
+    }
+    if (q.matrix) {
+        if (q.obs_count < 1) return fail(KMC_ERR_BAD_ARG, "the matrix needs obs_count >= 1 (obs_count = " + std::to_string(q.obs_count) + ")");
+        if (q.obs_first < 0 || q.obs_first > J - q.obs_count)
+            return fail(KMC_ERR_BAD_ARG, "observations [" + std::to_string(q.obs_first) + ", " + std::to_string(q.obs_first) + " + " + std::to_string(q.obs_count) +
+                                             ") lie outside [0, " + std::to_string(J) + ")");
+    }
+    if (v.is_float) return fail(KMC_ERR_UNSUPPORTED, "a chain of floats: data densities sample in double");
+    if (!result || !q.params) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (n_out) *n_out = n;
+    const PwPlan pl = pw_plan(n, J);
+
+    PwBuffers b;
+    KMC_TRY(src.open(b, &v));
+    // Never the legacy stream (kmc_host.hpp: copy_sync).  A sampler's own stream, which describe() has drained, serves: creating and
+    // destroying a stream for the call costs 3.4 to 4.4 ms, several times the two passes at the README's small shape.
+    ScopedStream ss;
+    if (src.host || !src.s->stream) HIP_TRY(ss.create());
+    else ss.borrowed = src.s->stream;
+    PwKernels pk;
+    KMC_TRY(load_pointwise(q.ud, v.ndim, !q.data, &pk));
+
+    PwArgs a{};
+    a.chain = static_cast<const double*>(v.chain);
+    a.n = n; a.J = J; a.nl = v.nl; a.ld = v.ld; a.nsel = nsel; a.first = q.first_sample; a.thin = q.thin;
+    a.nd = (double)n; a.jp_log2 = pl.jp_log2;
+    for (int i = 0; i < 6; ++i) a.p[i] = q.params[i];
+    if (q.walker_mask) {
+        std::vector<int32_t> sel;
+        for (int64_t w = 0; w < v.nl; ++w) if (q.walker_mask[w]) sel.push_back((int32_t)w);
+        HIP_TRY(hipMalloc((void**)&b.sel, sel.size() * sizeof(int32_t)));
+        HIP_TRY(copy_sync(b.sel, sel.data(), sel.size() * sizeof(int32_t), hipMemcpyHostToDevice, ss.get()));
+        a.sel = b.sel;
+    }
+    if (q.data) {
+        const size_t bytes = (size_t)J * (size_t)q.ncols2 * sizeof(double);
+        KMC_TRY(check_device_room(bytes, "the held-out observations"));
+        HIP_TRY(hipMalloc((void**)&b.data, bytes));
+        HIP_TRY(copy_sync(b.data, q.data, bytes, hipMemcpyHostToDevice, ss.get()));
+        a.data = b.data;
+    } else {
+        a.data = static_cast<const double*>(pk.keep_data.get());
+    }
+
+    if (q.matrix) {
+        const double need = (double)n * (double)q.obs_count * 8.0;
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        if (need > (double)free_b)
+            return fail(KMC_ERR_UNSUPPORTED, "a matrix of " + std::to_string(n) + " x " + std::to_string(q.obs_count) + " log-likelihoods (" +
+                                                 std::to_string((int64_t)(need / 1048576.0)) + " MiB) does not fit the device (" + std::to_string(free_b >> 20) +
+                                                 " MiB free): ask for fewer observations at a time, or thin");
+        const size_t bytes = (size_t)n * (size_t)q.obs_count * sizeof(double);
+        HIP_TRY(hipMalloc((void**)&b.work, bytes));
+        a.out = b.work; a.obs_first = q.obs_first; a.obs_count = q.obs_count;
+        a.run_len = std::max(kPwMinRun, (n + kPwMatrixWaves - 1) / kPwMatrixWaves);
+        const int64_t waves = (n + a.run_len - 1) / a.run_len;
+        HIP_TRY(launch_module_y(pk.matrix, (unsigned)((q.obs_count + 63) / 64), (unsigned)((waves + kPwWaves - 1) / kPwWaves), kPwThreads, ss.get(), a));
+        HIP_TRY(copy_sync(result, b.work, bytes, hipMemcpyDeviceToHost, ss.get()));
+        if (info) { info[0] = n; info[1] = waves; info[2] = n * q.obs_count; info[3] = a.run_len; }
+        return KMC_OK;
+    }
+
+    const size_t part = 2 * (size_t)pl.nruns * (size_t)J, doubles = part + 5 * (size_t)J;
+    KMC_TRY(check_device_room(doubles * sizeof(double), "the pointwise work space"));
+    HIP_TRY(hipMalloc((void**)&b.work, doubles * sizeof(double)));
+    a.part = b.work; a.stats = b.work + part; a.centre = a.stats + 4 * (size_t)J;
+    a.run_len = pl.run_len; a.nruns = pl.nruns;
+    const unsigned gx = (unsigned)((J + 63) / 64), gy = (unsigned)((pl.nwaves + kPwWaves - 1) / kPwWaves), gf = (unsigned)((J + 255) / 256);
+    PassEvents ev;
+    if (info) HIP_TRY(ev.create());
+    for (int pass = 1; pass <= 2; ++pass) {
+        if (info) HIP_TRY(hipEventRecord(ev.e[pass - 1], ss.get()));
+        HIP_TRY(launch_module_y(pk.pass[pass - 1][pl.packed ? 1 : 0], gx, gy, kPwThreads, ss.get(), a));
+        hipLaunchKernelGGL(pw_fold, dim3(gf), dim3(256), 0, ss.get(), a, pass);
+        HIP_TRY(hipGetLastError());
+    }
+    if (info) HIP_TRY(hipEventRecord(ev.e[2], ss.get()));
+    HIP_TRY(copy_sync(result, a.stats, 4 * (size_t)J * sizeof(double), hipMemcpyDeviceToHost, ss.get()));
+    if (info) {
+        float ms1 = 0.f, ms2 = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms1, ev.e[0], ev.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms2, ev.e[1], ev.e[2]));
+        info[0] = n; info[1] = pl.nruns; info[2] = 2 * n * J; info[3] = pl.run_len;
+        info[4] = (int64_t)((double)ms1 * 1e6); info[5] = (int64_t)((double)ms2 * 1e6);
+    }
+    return KMC_OK;
+}
+
+kmc_status sampler_density(kmc_sampler* s, PwRequest* q)
+{
+    if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
+    q->ud = s->data_ud;
+    q->params = s->dp.p;
+    return KMC_OK;
+}
+
+// the data-density contract's pairwise tree over v[0 .. m), in index order: each level adds neighbours, an odd last element passes up
+double pairwise_tree(std::vector<double>& v)
+{
+    size_t m = v.size();
+    while (m > 1) {
+        const size_t half = m / 2;
+        for (size_t i = 0; i < half; ++i) v[i] = v[2 * i] + v[2 * i + 1];
+        if (m & 1) v[half] = v[m - 1];
+        m = half + (m & 1);
+    }
+    return v[0];
+}
+
+}  // namespace
+
+KMC_EXPORT kmc_status kmc_sampler_pointwise_stats(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* data,
+                                                  int64_t ndata2, int32_t ncols2, double* stats, int64_t* n_out, int64_t* info)
+{
+    PwRequest q;
+    KMC_TRY(sampler_density(s, &q));
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask; q.data = data; q.ndata2 = ndata2; q.ncols2 = ncols2;
+    return pointwise(ChainSource(s, false, "kmc_chain_pointwise_stats"), q, stats, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_chain_pointwise_stats(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                                int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                                const double* data, int64_t ndata2, int32_t ncols2, int device, double* stats, int64_t* n_out,
+                                                int64_t* info)
+{
+    PwRequest q;
+    q.ud = density; q.params = params;
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask; q.data = data; q.ndata2 = ndata2; q.ncols2 = ncols2;
+    return pointwise(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, stats, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_pointwise_loglike(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* data,
+                                                    int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, double* out, int64_t* n_out)
+{
+    PwRequest q;
+    KMC_TRY(sampler_density(s, &q));
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask; q.data = data; q.ndata2 = ndata2; q.ncols2 = ncols2;
+    q.matrix = true; q.obs_first = obs_first; q.obs_count = obs_count;
+    return pointwise(ChainSource(s, false, "kmc_chain_pointwise_loglike"), q, out, n_out, nullptr);
+}
+
+KMC_EXPORT kmc_status kmc_chain_pointwise_loglike(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                                  int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                                  const double* data, int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count,
+                                                  int device, double* out, int64_t* n_out)
+{
+    PwRequest q;
+    q.ud = density; q.params = params;
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask; q.data = data; q.ndata2 = ndata2; q.ncols2 = ncols2;
+    q.matrix = true; q.obs_first = obs_first; q.obs_count = obs_count;
+    return pointwise(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, out, n_out, nullptr);
+}
+
+// The cut of the two passes; for tests and benchmarks.  Touches no device.
+KMC_EXPORT kmc_status kmc_pointwise_plan(int64_t n, int64_t ndata, int64_t* run_len, int64_t* nruns, int32_t* lanes_per_run, int32_t* slots,
+                                         int64_t* nwaves)
+{
+    if (n < 2) return fail(KMC_ERR_BAD_ARG, "need n >= 2 (n = " + std::to_string(n) + ")");
+    if (n >= ((int64_t)1 << 40)) return fail(KMC_ERR_UNSUPPORTED, "too many rows for one pointwise call: n = " + std::to_string(n) + ", the limit is 2^40");
+    if (ndata < 1 || ndata > kDataMaxRows) return fail(KMC_ERR_BAD_ARG, "ndata must be in 1 .. 2^30 (ndata = " + std::to_string(ndata) + ")");
+    const PwPlan p = pw_plan(n, ndata);
+    if (run_len) *run_len = p.run_len;
+    if (nruns) *nruns = p.nruns;
+    if (lanes_per_run) *lanes_per_run = p.lanes;
+    if (slots) *slots = p.slots;
+    if (nwaves) *nwaves = p.nwaves;
+    return KMC_OK;
+}
+
+// The host stage, in the operation order of include/kissmcmc_hip.h.  No device; no fused multiply-add (the library is built with
+// -ffp-contract=off).  totals: lppd, p_waic, elpd_waic, se, waic, n_high, n_nan.
+KMC_EXPORT kmc_status kmc_waic_stats(int64_t J, int64_t n, const double* stats, double* lppd_j, double* p_waic_j, double* elpd_j, double* totals)
+{
+    if (J < 1) return fail(KMC_ERR_BAD_ARG, "need J >= 1 (J = " + std::to_string(J) + ")");
+    if (n < 2) return fail(KMC_ERR_BAD_ARG, "need n >= 2 (n = " + std::to_string(n) + ")");
+    if (!stats || !totals) return fail(KMC_ERR_BAD_ARG, "null argument");
+    const double *M = stats, *S1 = stats + J, *E = stats + 2 * J, *V = stats + 3 * J;
+    const double logn = std::log((double)n), nm1 = (double)(n - 1), dJ = (double)J;
+    std::vector<double> lp((size_t)J), pw((size_t)J), el((size_t)J), t((size_t)J);
+    int64_t n_high = 0, n_nan = 0;
+    for (int64_t j = 0; j < J; ++j) {
+        lp[(size_t)j] = M[j] + (std::log(E[j]) - logn);
+        pw[(size_t)j] = V[j] / nm1;
+        el[(size_t)j] = lp[(size_t)j] - pw[(size_t)j];
+        n_high += pw[(size_t)j] > 0.4;
+        n_nan += std::isnan(S1[j]);
+    }
+    if (lppd_j) std::copy(lp.begin(), lp.end(), lppd_j);
+    if (p_waic_j) std::copy(pw.begin(), pw.end(), p_waic_j);
+    if (elpd_j) std::copy(el.begin(), el.end(), elpd_j);
+    t = lp; totals[0] = pairwise_tree(t);
+    t = pw; totals[1] = pairwise_tree(t);
+    t = el; totals[2] = pairwise_tree(t);
+    const double centre = totals[2] / dJ;
+    for (int64_t j = 0; j < J; ++j) { const double dv = el[(size_t)j] - centre; t[(size_t)j] = dv * dv; }
+    totals[3] = std::sqrt(dJ * pairwise_tree(t) / (double)(J - 1));
+    totals[4] = -2.0 * totals[2];
+    totals[5] = (double)n_high;
+    totals[6] = (double)n_nan;
+    return KMC_OK;
+}

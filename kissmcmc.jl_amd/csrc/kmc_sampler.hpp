@@ -288,7 +288,9 @@ bool body_vec_possible(const kmc_user_density* ud, int64_t ndim);     // a funct
 
 // kmc_data.hip
 kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk);       // compile (cached) + module + device copy of the data
-DataPlan data_plan(const kmc_user_density* ud, int64_t nprop);                   // reads KMC_DEBUG=data-map: call it once per evaluation size, keep the result
+std::string data_functor_source(const kmc_user_density* ud);                      // "struct UserData { term, prior };" from the two bodies
+kmc_status data_on_device(kmc_user_density* ud, int dev, std::shared_ptr<void>* keep);   // the observations on the current device `dev`, uploaded once
+DataPlan data_plan(const kmc_user_density* ud, int64_t nprop);                  // reads KMC_DEBUG=data-map: call it once per evaluation size, keep the result
 // one evaluation of nprop rows cut as `p` says; `part` holds part_doubles doubles (p.nblocks * nprop are written: refused beyond that).
 // split: `out` takes the tree sums S [nprop] and then the priors [nprop] instead of the log-pdfs (data_fold_split)
 hipError_t launch_data_eval(const DataKernels& dk, const kmc_user_density* ud, const DataPlan& p, const double* prop, int64_t nprop, int32_t ld,

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, waic, pointwise_loglike, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -181,7 +181,7 @@ end
 # `double prior(const double* x, int n, const double* p)` (nothing: 0).  `data` is ndata x ncols (a vector: one column), copied at
 # creation; lp = -Inf where the prior is -Inf, else prior + the pairwise sum of the terms in observation order.
 mutable struct DataDensity <: DeviceLogPdf
-    handle::Ptr{Cvoid}; p::Vector{Float64}
+    handle::Ptr{Cvoid}; p::Vector{Float64}; ndata::Int
     function DataDensity(term::String, data::AbstractVecOrMat; prior::Union{String,Nothing}=nothing, params=Float64[])
         D = data isa AbstractVector ? reshape(collect(Float64, data), :, 1) : collect(Float64, data)
         rows = permutedims(D)                          # row-major [ndata][ncols] for the C ABI
@@ -189,7 +189,7 @@ mutable struct DataDensity <: DeviceLogPdf
         st = ccall((:kmc_data_density_create, LIB), Cint, (Cstring, Cstring, Ptr{Float64}, Int64, Int32, Ref{Ptr{Cvoid}}),
                    term, prior === nothing ? "" : prior, rows, size(D, 1), Int32(size(D, 2)), h)
         st == 0 || error("kmc_data_density_create failed: $(last_error())")
-        d = new(h[], collect(Float64, params))
+        d = new(h[], collect(Float64, params), size(D, 1))
         finalizer(x -> ccall((:kmc_user_density_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.handle), d)
         return d
     end
@@ -769,6 +769,71 @@ function covariance(thetas; logdensities=nothing, first_sample=0, walkers=nothin
     st = ccall((:kmc_cov_correlation, LIB), Cint, (Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), ncols, cov, corr, sd)
     st == 0 || error("kmc_cov_correlation failed ($st): $(last_error())")
     return (mean=mean, cov=cov, corr=corr, std=sd, n=n[])
+end
+
+# the six parameters and the held-out observations (row-major [ndata][ncols] for the C ABI) of a pointwise call
+_pointwise_params(pdf::DataDensity) = Float64[i <= length(pdf.p) ? pdf.p[i] : 0.0 for i in 1:6]
+function _pointwise_data(data)
+    data === nothing && return nothing, 0, 0
+    D = data isa AbstractVector ? reshape(collect(Float64, data), :, 1) : collect(Float64, data)
+    return permutedims(D), size(D, 1), size(D, 2)
+end
+
+"""
+    waic(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, data=nothing, device=0)
+
+WAIC of the data density `pdf` over the posterior sample `thetas[walker][sample]` as `emcee` returns it: the rows are the samples
+`first_sample, first_sample + thin, ...` of the walkers `walkers`.  The term of every row and observation is evaluated on the GPU and
+reduced per observation (`kmc_chain_pointwise_stats`), the host stage is `kmc_waic_stats`; the definitions are in
+include/kissmcmc_hip.h.  Returns a named tuple `(elpd_waic, se, p_waic, lppd, waic, n_high, n_nan, n, lppd_j, p_waic_j, elpd_j)`;
+`p_waic_j` has n - 1 in the denominator (BDA3, loo; ArviZ divides by n).  With `data` the observations are that held-out array
+`[ndata, ncols]` instead of the density's own.
+"""
+function waic(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, data=nothing, device=0)
+    chain, _, ns, nw, nd = _summary_chain(thetas, nothing)
+    mask = _summary_mask(walkers, nw)
+    D, nd2, nc2 = _pointwise_data(data)
+    J = D === nothing ? pdf.ndata : nd2
+    stats = Matrix{Float64}(undef, J, 4)                  # column-major [J, 4] is the C ABI's [4][J]
+    n = Ref{Int64}(0)
+    st = ccall((:kmc_chain_pointwise_stats, LIB), Cint,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Ptr{Float64}, Int64, Int32, Cint,
+                Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+               pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin,
+               D === nothing ? C_NULL : D, nd2, Int32(nc2), Cint(device), stats, n, C_NULL)
+    st == 0 || error("kmc_chain_pointwise_stats failed ($st): $(last_error())")
+    lppd_j = Vector{Float64}(undef, J); p_waic_j = similar(lppd_j); elpd_j = similar(lppd_j); tot = Vector{Float64}(undef, 7)
+    st = ccall((:kmc_waic_stats, LIB), Cint, (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               J, n[], stats, lppd_j, p_waic_j, elpd_j, tot)
+    st == 0 || error("kmc_waic_stats failed ($st): $(last_error())")
+    return (elpd_waic=tot[3], se=tot[4], p_waic=tot[2], lppd=tot[1], waic=tot[5], n_high=Int(tot[6]), n_nan=Int(tot[7]), n=n[],
+            lppd_j=lppd_j, p_waic_j=p_waic_j, elpd_j=elpd_j)
+end
+
+"""
+    pointwise_loglike(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, obs=nothing, data=nothing, device=0)
+
+The matrix `l[j, r] = term(x_r, d_j)` of the selected rows `r` (as for `waic`) and the observations `obs = (first, stop)`, 0-based and
+half-open (all by default), evaluated on the GPU (`kmc_chain_pointwise_loglike`): an `(stop - first) x n` matrix, one column per row of
+the chain -- what PSIS-LOO outside this package starts from.
+"""
+function pointwise_loglike(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, obs=nothing, data=nothing, device=0)
+    chain, _, ns, nw, nd = _summary_chain(thetas, nothing)
+    mask = _summary_mask(walkers, nw)
+    D, nd2, nc2 = _pointwise_data(data)
+    J = D === nothing ? pdf.ndata : nd2
+    first, stop = obs === nothing ? (0, J) : obs
+    nsel = mask === nothing ? nw : count(!iszero, mask)
+    rows = cld(max(ns - first_sample, 0), max(thin, 1)) * nsel
+    out = Matrix{Float64}(undef, max(stop - first, 1), max(rows, 1))     # column-major [count, n] is the C ABI's [n][count]
+    n = Ref{Int64}(0)
+    st = ccall((:kmc_chain_pointwise_loglike, LIB), Cint,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Ptr{Float64}, Int64, Int32, Int64, Int64,
+                Cint, Ptr{Float64}, Ptr{Int64}),
+               pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin,
+               D === nothing ? C_NULL : D, nd2, Int32(nc2), first, stop - first, Cint(device), out, n)
+    st == 0 || error("kmc_chain_pointwise_loglike failed ($st): $(last_error())")
+    return out
 end
 
 """

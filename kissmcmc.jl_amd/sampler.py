@@ -578,6 +578,20 @@ class Sampler:
         from .chain_covariance import sampler_covariance
         return sampler_covariance(self, first_sample, walkers, logp)
 
+    def waic(self, first_sample: int = 0, thin: int = 1, walkers=None, data=None):
+        """WAIC of the sampler's :class:`DataDensity` over the stored chain -- the samples ``first_sample, first_sample + thin, ...`` of
+        the walkers ``walkers`` -- evaluated on the device where chain and observations lie (``kmc_sampler_pointwise_stats``): a dict
+        ``elpd_waic, se, p_waic, lppd, waic, n_high, n_nan, n`` and the arrays ``lppd_j, p_waic_j, elpd_j``; with ``data=`` over held-out
+        observations instead of the density's own.  See :func:`kissmcmc_jl_amd.waic`."""
+        from .chain_predictive import sampler_waic
+        return sampler_waic(self, first_sample, thin, walkers, data)
+
+    def pointwise_loglike(self, first_sample: int = 0, thin: int = 1, walkers=None, obs=None, data=None):
+        """The matrix ``l[r, j] = term(x_r, d_j)`` of the selected rows of the stored chain and the observations ``obs = (first, stop)``
+        (default: all), ``[n, stop - first]`` (``kmc_sampler_pointwise_loglike``); see :func:`kissmcmc_jl_amd.pointwise_loglike`."""
+        from .chain_predictive import sampler_pointwise_loglike
+        return sampler_pointwise_loglike(self, first_sample, thin, walkers, obs, data)
+
     def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False, covariance=False):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
         from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain;
