@@ -169,6 +169,16 @@ struct ScopedStream {
         else if (borrowed) (void)hipStreamSynchronize(borrowed);
     }
 };
+// a hipMalloc block for the duration of one call: freed with the scope, so the stream that uses it is synchronised before the scope ends
+struct ScopedDeviceBlock {
+    void* p = nullptr;
+    ScopedDeviceBlock() = default;
+    ScopedDeviceBlock(const ScopedDeviceBlock&) = delete;
+    ScopedDeviceBlock& operator=(const ScopedDeviceBlock&) = delete;
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    ~ScopedDeviceBlock() { if (p) (void)hipFree(p); }
+};
 
 // hiprtc compilation of `text` (+ named headers) for gfx950, with a DISK CACHE of the code objects: a script that defines its
 // density in source pays the compiler (0.2-0.5 s per density and kernel geometry) once, not in every process.  Key: two

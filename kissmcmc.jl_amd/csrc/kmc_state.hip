@@ -1,6 +1,11 @@
 // kmc_state.hip -- a sampler's state in and out: the initial ensemble and its log-pdfs (reference src/samplers.jl:198,
 // :209-210), the device-side initial ball (:311-349), checkpoint / resume, the read-outs (positions, log-pdfs, accept
 // statistics :291, streaming moments), the deal of dealt sub-ensembles, and the one-shot `emcee` call (:188-293).
+// Every way in ends in reset_run_state (accumulators, run fields, the finiteness scan); the two that start a run from nothing go
+// through start_at_generation_0 first.  kmc_sampler_get_moments dispatches to one function per accumulator layout.  The getters
+// and setters that only need the stream drained begin with settle() after their argument checks (kmc_sampler_get_moments flushes
+// first and keeps its own preamble; the deal kernels and get_accept_ratio drain nothing themselves); temporaries on the device are
+// ScopedDeviceBlock (kmc_host.hpp).
 #include <signal.h>
 
 #include <cmath>
@@ -31,36 +36,77 @@ static double* rung_logp(const kmc_sampler* s, int t) { return s->d_logp + 2 * (
 static uint32_t* rung_naccept(const kmc_sampler* s, int t) { return reinterpret_cast<uint32_t*>(rung_logp(s, t) + s->nrows); }
 static double* rung_pos(const kmc_sampler* s, int t) { return s->d_pos + (size_t)t * (size_t)s->nrows * (size_t)s->ld; }
 
+// What every getter and setter starts with, after its argument checks: the sampler's device current and its stream drained;
+// p2p_err: and no peer wait timed out (a read-out of a sharded run).
+static kmc_status settle(kmc_sampler* s, bool p2p_err = false)
+{
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return p2p_err ? check_p2p_err(s) : KMC_OK;
+}
+
+// int64 host arrays over uint32 device arrays (accept counters, walker ids); src_host null: zeros
+static hipError_t upload_u32(const kmc_sampler* s, uint32_t* dst_dev, const int64_t* src_host, size_t n)
+{
+    std::vector<uint32_t> tmp(n, 0u);
+    if (src_host) for (size_t i = 0; i < n; ++i) tmp[i] = (uint32_t)src_host[i];
+    return copy_sync(dst_dev, tmp.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream);
+}
+static hipError_t download_u32(const kmc_sampler* s, int64_t* dst_host, const uint32_t* src_dev, size_t n)
+{
+    std::vector<uint32_t> tmp(n);
+    const hipError_t e = copy_sync(tmp.data(), src_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream);
+    for (size_t i = 0; e == hipSuccess && i < n; ++i) dst_host[i] = (int64_t)tmp[i];
+    return e;
+}
+
 kmc_status eval_initial_logp(kmc_sampler* s, double* logp_out = nullptr, int rung = 0)      // (logp_out: somewhere else than d_logp -- a caller that only wants the blobs)
 {
     const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
     double* rows = rung_pos(s, rung);
     if (rung > 0 && !logp_out) logp_out = rung_logp(s, rung);
-    double* scratch = nullptr;
+    ScopedDeviceBlock scratch;
     if (s->f32) {
         const int64_t n = (int64_t)(nw * (size_t)s->ld);
-        HIP_TRY(hipMalloc((void**)&scratch, (size_t)n * sizeof(double)));
-        hipLaunchKernelGGL(widen_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, reinterpret_cast<const float*>(s->d_pos), scratch, n);
-        rows = scratch;
+        HIP_TRY(scratch.alloc((size_t)n * sizeof(double)));
+        hipLaunchKernelGGL(widen_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, reinterpret_cast<const float*>(s->d_pos), scratch.as<double>(), n);
+        rows = scratch.as<double>();
     }
     const LogpdfArgs la{rows, logp_out ? logp_out : s->d_logp, (int64_t)nw, (int32_t)nd, (int32_t)s->ld, s->dp, s->d_blob};   // (blobs of the initial evaluations, :209-210)
-    hipError_t e = hipSuccess;
     if (s->user) {
-        e = launch_module(s->uk.logpdf, (unsigned)((nw + 255) / 256), 256u, s->stream, la);
+        HIP_TRY(launch_module(s->uk.logpdf, (unsigned)((nw + 255) / 256), 256u, s->stream, la));
     } else {
         hipLaunchKernelGGL(s->logpdf_fn, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s->stream, la);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    if (scratch) {
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        (void)hipFree(scratch);
-    }
-    HIP_TRY(e);
+    if (scratch.p) HIP_TRY(hipStreamSynchronize(s->stream));    // (the kernel reads the scratch until then)
     return KMC_OK;
 }
 
-// Everything set_positions does after the rows are in place: initial log-pdfs (src/samplers.jl:209-210)
-// unless they are supplied, counters, accumulators, finiteness check.
+// What "start at generation 0" means (kmc_sampler_set_positions, kmc_sampler_init_ball): accept counters, the device's generation
+// counter, the P2P progress flags and error word, the moments' base, a dealt sub-ensemble's walker ids.  A field added to a sampler
+// that a new start must clear goes here; one that a restored state must clear too goes into reset_run_state.
+kmc_status start_at_generation_0(kmc_sampler* s)
+{
+    HIP_TRY(hipMemsetAsync(s->d_naccept, 0, (size_t)s->nrows * sizeof(uint32_t), s->stream));
+    HIP_TRY(hipMemsetAsync(s->d_gen, 0, 64, s->stream));
+    if (s->p2p) {                                                // (callers barrier across ranks before running)
+        HIP_TRY(fill_sync(s->d_flags, 0, 4096, s->stream));
+        HIP_TRY(fill_sync(s->d_err, 0, 64, s->stream));
+    }
+    s->dev_gen = 0;
+    s->moment_base = 0;
+    if (s->d_ids) {                                              // dealt sub-ensembles: slot i holds global walker r S + i
+        hipLaunchKernelGGL(deal_init_ids, dim3((unsigned)((s->nrows + 255) / 256)), dim3(256), 0, s->stream, s->d_ids, s->nrows,
+                           (uint32_t)((uint64_t)s->cfg.deal_rank * (uint64_t)s->nrows));
+        HIP_TRY(hipGetLastError());
+    }
+    return KMC_OK;
+}
+
+// Everything an entry point does after the rows are in place -- the only place that zeroes the accumulators, clears the host-side
+// run fields and scans for a non-finite log-pdf: initial log-pdfs (src/samplers.jl:209-210) unless they are supplied, accumulators
+// (klast: the samples taken so far), the run fields, finiteness check.
 kmc_status reset_run_state(kmc_sampler* s, bool eval_logp, int64_t generation, uint32_t klast_value)
 {
     const size_t nw = (size_t)s->nrows;
@@ -147,33 +193,24 @@ kmc_status replicate_rung0(kmc_sampler* s)
     return reset_temper_counters(s, nullptr, nullptr);
 }
 
-}  // namespace kmc_host
-// Device-side make_theta0s: src/samplers.jl:311-349 (see init_ball in kmc_kernels.hpp).
-KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0, const double* ball_radius,
-                                            uint64_t seed, int halving_steps, int ntries)
+// The ball of kmc_sampler_init_ball into d_pos / d_logp, on the sampler's stream; *nfail: walkers that found no point with pdf > 0.
+// (Its temporaries go with this scope, after the stream has drained.)
+kmc_status draw_ball(kmc_sampler* s, const double* theta0, const double* ball_radius, uint64_t seed, int halving_steps, int ntries, unsigned long long* nfail)
 {
-    if (!s || !theta0 || !ball_radius || halving_steps < 1 || ntries < 1) return fail(KMC_ERR_BAD_ARG, "bad argument");
-    if (s->data_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with KMC_DATA_DENSITY (build the initial ensemble on the host, e.g. make_theta0s)");
-    if (s->host_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball evaluates the density on the device; with KMC_HOST_DENSITY build the ball on the host");
-    if (s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with parallel tempering (build the initial ensemble on the host, e.g. make_theta0s; kmc_sampler_set_positions copies it to every rung)");
-    if (s->push) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball fills this rank's rows only; with KMC_P2P_PUSH use kmc_sampler_set_positions (the peers' copies must be filled too)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    const size_t nd = (size_t)s->cfg.ndim;
-    double* d_par = nullptr;
-    unsigned long long* d_fail = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_par, 2 * nd * sizeof(double)));
-    hipError_t e = hipMalloc((void**)&d_fail, sizeof(unsigned long long));
-    if (e == hipSuccess) e = copy_sync(d_par, theta0, nd * sizeof(double), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = copy_sync(d_par + nd, ball_radius, nd * sizeof(double), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = fill_sync(d_fail, 0, sizeof(unsigned long long), s->stream);
-    const size_t nelem = (size_t)s->nrows * (size_t)s->ld;
+    const size_t nd = (size_t)s->cfg.ndim, nelem = (size_t)s->nrows * (size_t)s->ld;
+    ScopedDeviceBlock par, fails, ball;
+    HIP_TRY(par.alloc(2 * nd * sizeof(double)));
+    HIP_TRY(fails.alloc(sizeof(unsigned long long)));
+    double* d_par = par.as<double>();
+    HIP_TRY(copy_sync(d_par, theta0, nd * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(copy_sync(d_par + nd, ball_radius, nd * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(fill_sync(fails.p, 0, sizeof(unsigned long long), s->stream));
     double* d_ball = s->d_pos;                  // KMC_F32: the ball is drawn in double, then rounded into the float rows
-    if (s->f32 && e == hipSuccess) e = hipMalloc((void**)&d_ball, nelem * sizeof(double));
-    if (e == hipSuccess) e = fill_sync(d_ball, 0, nelem * sizeof(double), s->stream);
+    if (s->f32) { HIP_TRY(ball.alloc(nelem * sizeof(double))); d_ball = ball.as<double>(); }
+    HIP_TRY(fill_sync(d_ball, 0, nelem * sizeof(double), s->stream));
     InitBallFn fn = s->user ? nullptr : with_density(s->cfg.density, InitBallFn(nullptr), [](auto d) { return init_ball_lookup<decltype(d)>(); });
     const int pieces = s->p2p ? 2 : 1;
-    for (int piece = 0; piece < pieces && e == hipSuccess; ++piece) {
+    for (int piece = 0; piece < pieces; ++piece) {
         InitBallArgs a{};
         const int64_t rows = s->p2p ? s->h_loc : s->nrows;
         a.pos = d_ball + (size_t)piece * (size_t)s->h_loc * (size_t)s->ld;
@@ -186,54 +223,46 @@ KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0
         a.halving_steps = halving_steps; a.ntries = ntries;
         a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
         a.dp = s->dp;
-        a.fail = d_fail;
+        a.fail = fails.as<unsigned long long>();
         a.blob = s->d_blob;
         const unsigned grid = (unsigned)((rows + 255) / 256);
-        if (s->user) e = launch_module(s->uk.init_ball, grid, 256u, s->stream, a);
-        else { hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, s->stream, a); e = hipGetLastError(); }
+        if (s->user) HIP_TRY(launch_module(s->uk.init_ball, grid, 256u, s->stream, a));
+        else { hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, s->stream, a); HIP_TRY(hipGetLastError()); }
     }
-    unsigned long long nfail = 0;
-    if (s->f32 && e == hipSuccess) {
+    if (s->f32) {
         hipLaunchKernelGGL(narrow_rows, dim3((unsigned)((nelem + 255) / 256)), dim3(256), 0, s->stream, d_ball, reinterpret_cast<float*>(s->d_pos), (int64_t)nelem);
-        e = hipGetLastError();
+        HIP_TRY(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    if (e == hipSuccess) e = copy_sync(&nfail, d_fail, sizeof(nfail), hipMemcpyDeviceToHost, s->stream);
-    (void)hipFree(d_par);
-    (void)hipFree(d_fail);
-    if (s->f32) (void)hipFree(d_ball);
-    HIP_TRY(e);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(copy_sync(nfail, fails.p, sizeof(*nfail), hipMemcpyDeviceToHost, s->stream));
+    return KMC_OK;
+}
+
+}  // namespace kmc_host
+// Device-side make_theta0s: src/samplers.jl:311-349 (see init_ball in kmc_kernels.hpp).
+KMC_EXPORT kmc_status kmc_sampler_init_ball(kmc_sampler* s, const double* theta0, const double* ball_radius,
+                                            uint64_t seed, int halving_steps, int ntries)
+{
+    if (!s || !theta0 || !ball_radius || halving_steps < 1 || ntries < 1) return fail(KMC_ERR_BAD_ARG, "bad argument");
+    if (s->data_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with KMC_DATA_DENSITY (build the initial ensemble on the host, e.g. make_theta0s)");
+    if (s->host_eval) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball evaluates the density on the device; with KMC_HOST_DENSITY build the ball on the host");
+    if (s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball: not with parallel tempering (build the initial ensemble on the host, e.g. make_theta0s; kmc_sampler_set_positions copies it to every rung)");
+    if (s->push) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_init_ball fills this rank's rows only; with KMC_P2P_PUSH use kmc_sampler_set_positions (the peers' copies must be filled too)");
+    KMC_TRY(settle(s));
+    unsigned long long nfail = 0;
+    KMC_TRY(draw_ball(s, theta0, ball_radius, seed, halving_steps, ntries, &nfail));
     if (nfail != 0) {
         s->positions_set = false;
         return fail(KMC_ERR_NONFINITE_LOGP, "Could not find suitable initial theta.  PDF is zero in too many places inside ball. (" +
                                             std::to_string(nfail) + " walkers)");
     }
-    HIP_TRY(hipMemsetAsync(s->d_naccept, 0, (size_t)s->nrows * sizeof(uint32_t), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_gen, 0, 64, s->stream));
-    if (s->p2p) {
-        HIP_TRY(fill_sync(s->d_flags, 0, 4096, s->stream));
-        HIP_TRY(fill_sync(s->d_err, 0, 64, s->stream));
-    }
-    s->dev_gen = 0;
-    s->moment_base = 0;
-    if (s->d_ids) {
-        hipLaunchKernelGGL(deal_init_ids, dim3((unsigned)((s->nrows + 255) / 256)), dim3(256), 0, s->stream, s->d_ids, s->nrows,
-                           (uint32_t)((uint64_t)s->cfg.deal_rank * (uint64_t)s->nrows));
-        HIP_TRY(hipGetLastError());
-    }
+    KMC_TRY(start_at_generation_0(s));
     return reset_run_state(s, /*eval_logp=*/s->f32, 0, 0u);      // KMC_F32: the log-pdfs of the rows as rounded
 }
 
 // Checkpoint / resume: restore (positions, log-pdfs, acceptance counters, generation).  The random
 // stream is a pure function of (seed, generation, walker), so the continued run is bit-identical to an
 // uninterrupted one.  Moments and the chain restart at the restored generation.
-static kmc_status set_state_rung0(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host, int64_t generation);
-KMC_EXPORT kmc_status kmc_sampler_set_state(kmc_sampler* s, const double* pos_host, const double* logp_host,
-                                            const int64_t* naccept_host, int64_t generation)
-{
-    if (s && s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_set_state restores one ensemble: a sampler with parallel tempering takes every rung through kmc_sampler_set_rung_state");
-    return set_state_rung0(s, pos_host, logp_host, naccept_host, generation);
-}
 static kmc_status set_state_rung0(kmc_sampler* s, const double* pos_host, const double* logp_host, const int64_t* naccept_host, int64_t generation)
 {
     if (!s || !pos_host || !logp_host || generation < 0) return fail(KMC_ERR_BAD_ARG, "bad argument");
@@ -242,14 +271,11 @@ static kmc_status set_state_rung0(kmc_sampler* s, const double* pos_host, const 
         return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_set_state: not with chain / blob storage (download the chain before checkpointing)");
     if (s->p2p && s->cfg.shard_count > 1)
         return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_set_state: P2P progress flags restart at 0; restore is single-GPU for now");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     const size_t nw = (size_t)s->nrows;
     HIP_TRY(upload_rows(s, s->d_pos, pos_host, nw));
     HIP_TRY(copy_sync(s->d_logp, logp_host, nw * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    std::vector<uint32_t> na(nw, 0u);
-    if (naccept_host) for (size_t i = 0; i < nw; ++i) na[i] = (uint32_t)naccept_host[i];
-    HIP_TRY(copy_sync(s->d_naccept, na.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(upload_u32(s, s->d_naccept, naccept_host, nw));
     if (s->p2p) {
         HIP_TRY(fill_sync(s->d_flags, 0, 4096, s->stream));
         HIP_TRY(fill_sync(s->d_err, 0, 64, s->stream));
@@ -257,53 +283,56 @@ static kmc_status set_state_rung0(kmc_sampler* s, const double* pos_host, const 
     if (s->d_blob) {
         // the blobs of the restored positions: evaluated again (same kernel and order as the initial evaluation: same bits);
         // the restored log-pdfs stay as given
-        double* scratch = nullptr;
-        HIP_TRY(hipMalloc((void**)&scratch, nw * sizeof(double)));
-        const kmc_status bst = eval_initial_logp(s, scratch);
-        const hipError_t be = hipStreamSynchronize(s->stream);
-        (void)hipFree(scratch);
-        KMC_TRY(bst);
-        HIP_TRY(be);
+        ScopedDeviceBlock scratch;
+        HIP_TRY(scratch.alloc(nw * sizeof(double)));
+        KMC_TRY(eval_initial_logp(s, scratch.as<double>()));
+        HIP_TRY(hipStreamSynchronize(s->stream));
     }
     s->generation = generation;            // the device counter follows at the next graph replay
     const int64_t done = samples_done(s);
     s->moment_base = done;
     return reset_run_state(s, /*eval_logp=*/false, generation, (uint32_t)done);
 }
+KMC_EXPORT kmc_status kmc_sampler_set_state(kmc_sampler* s, const double* pos_host, const double* logp_host,
+                                            const int64_t* naccept_host, int64_t generation)
+{
+    if (s && s->temper) return fail(KMC_ERR_UNSUPPORTED, "kmc_sampler_set_state restores one ensemble: a sampler with parallel tempering takes every rung through kmc_sampler_set_rung_state");
+    return set_state_rung0(s, pos_host, logp_host, naccept_host, generation);
+}
+
+// theta_host is the GLOBAL ensemble: the whole of it, or (P2P) this shard's slice of each half -- local rows
+// [0,h_loc) = global [begin, begin+h_loc), local [h_loc,2h_loc) = global [h+begin, ...) -- and, with KMC_P2P_PUSH, the local copies of the other shards' rows
+static kmc_status upload_ensemble(kmc_sampler* s, const double* theta_host)
+{
+    const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
+    if (!s->p2p) {
+        HIP_TRY(upload_rows(s, s->d_pos, theta_host, nw));       // :198 (caller's array untouched)
+        return KMC_OK;
+    }
+    const size_t hl = (size_t)s->h_loc;
+    HIP_TRY(upload_rows(s, s->d_pos, theta_host + (size_t)s->active_begin * nd, hl));
+    HIP_TRY(upload_rows(s, s->d_pos + hl * (size_t)s->ld, theta_host + ((size_t)s->h + (size_t)s->active_begin) * nd, hl));
+    for (int q = 0; s->push && q < s->cfg.shard_count; ++q) {      // (block 1 + q = rank q's rows)
+        if (q == s->cfg.shard_rank) continue;
+        double* blk = s->d_pos + (size_t)(1 + q) * nw * (size_t)s->ld;
+        HIP_TRY(upload_rows(s, blk, theta_host + (size_t)q * hl * nd, hl));
+        HIP_TRY(upload_rows(s, blk + hl * (size_t)s->ld, theta_host + ((size_t)s->h + (size_t)q * hl) * nd, hl));
+    }
+    return KMC_OK;
+}
 
 // replicate: a tempered sampler copies the ensemble to every rung (kmc_sampler_set_positions); kmc_sampler_set_rung_state fills the
 // other rungs itself
-static kmc_status set_positions_rung0(kmc_sampler* s, const double* theta_host, bool replicate);
-KMC_EXPORT kmc_status kmc_sampler_set_positions(kmc_sampler* s, const double* theta_host)
-{
-    return set_positions_rung0(s, theta_host, true);
-}
 static kmc_status set_positions_rung0(kmc_sampler* s, const double* theta_host, bool replicate)
 {
     if (!s || !theta_host) return fail(KMC_ERR_BAD_ARG, "null argument");
     reinstall_abort_backtrace();                                 // (diagnostics: somebody may have replaced the handler)
-    HIP_TRY(hipSetDevice(s->cfg.device));
+    KMC_TRY(settle(s));
     const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (!s->p2p) {
-        HIP_TRY(upload_rows(s, s->d_pos, theta_host, nw));   // :198 (caller's array untouched)
-    } else {
-        // theta_host is the GLOBAL ensemble; keep this shard's slice of each half: local rows
-        // [0,h_loc) = global [begin, begin+h_loc), local [h_loc,2h_loc) = global [h+begin, ...)
-        const size_t hl = (size_t)s->h_loc;
-        HIP_TRY(upload_rows(s, s->d_pos, theta_host + (size_t)s->active_begin * nd, hl));
-        HIP_TRY(upload_rows(s, s->d_pos + hl * (size_t)s->ld, theta_host + ((size_t)s->h + (size_t)s->active_begin) * nd, hl));
-        if (s->push) {      // the local copies of the other shards (block 1 + q = rank q's rows)
-            for (int q = 0; q < s->cfg.shard_count; ++q) {
-                if (q == s->cfg.shard_rank) continue;
-                double* blk = s->d_pos + (size_t)(1 + q) * nw * (size_t)s->ld;
-                HIP_TRY(upload_rows(s, blk, theta_host + (size_t)q * hl * nd, hl));
-                HIP_TRY(upload_rows(s, blk + hl * (size_t)s->ld, theta_host + ((size_t)s->h + (size_t)q * hl) * nd, hl));
-            }
-        }
-        HIP_TRY(fill_sync(s->d_flags, 0, 4096, s->stream));     // callers barrier across ranks before running
-        HIP_TRY(fill_sync(s->d_err, 0, 64, s->stream));
-    }
+    KMC_TRY(upload_ensemble(s, theta_host));
+    // (ahead of the evaluation: if that fails, the counters are already zero and the ids dealt -- the sampler has no positions then, and
+    //  every entry point that gives it some starts or restores them again)
+    KMC_TRY(start_at_generation_0(s));
     if (s->data_eval) {                                          // :209-210, the same kernels as every half-step's proposals
         HIP_TRY(launch_data_eval(s->dk, s->data_ud, s->plan_all, s->d_pos, (int64_t)nw, (int32_t)s->ld, s->dp.p, s->d_part, s->part_doubles, s->d_logp, s->stream));
     } else if (s->host_eval) {                                   // :209-210, on the caller's thread
@@ -316,45 +345,13 @@ static kmc_status set_positions_rung0(kmc_sampler* s, const double* theta_host, 
     } else {
         KMC_TRY(eval_initial_logp(s));                           // :209-210
     }
-    std::vector<double> lp(nw);
-    HIP_TRY(copy_sync(lp.data(), s->d_logp, nw * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_naccept, 0, nw * sizeof(uint32_t), s->stream));
-    HIP_TRY(hipMemsetAsync(s->d_gen, 0, 64, s->stream));
-    if (s->d_msum) {
-        HIP_TRY(hipMemsetAsync(s->d_msum, 0, (size_t)s->macc_elems * sizeof(double), s->stream));
-        HIP_TRY(hipMemsetAsync(s->d_msumsq, 0, (size_t)s->macc_elems * sizeof(double), s->stream));
-        if (s->d_klast) HIP_TRY(hipMemsetAsync(s->d_klast, 0, nw * sizeof(uint32_t), s->stream));
-        if (s->d_mcnt) HIP_TRY(hipMemsetAsync(s->d_mcnt, 0, 2 * (size_t)s->mring_waves * sizeof(uint32_t), s->stream));
-        if (s->d_isum) {
-            const size_t ne = (size_t)s->nislands * 4 * (size_t)s->island_K;
-            HIP_TRY(hipMemsetAsync(s->d_isum, 0, ne * sizeof(double), s->stream));
-            HIP_TRY(hipMemsetAsync(s->d_isumsq, 0, ne * sizeof(double), s->stream));
-        }
-        s->carry_sum.clear(); s->carry_sumsq.clear();
-    }
-    if (s->d_ids) {                                              // dealt sub-ensembles: slot i holds global walker r S + i
-        hipLaunchKernelGGL(deal_init_ids, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s->stream, s->d_ids, (int64_t)nw,
-                           (uint32_t)((uint64_t)s->cfg.deal_rank * (uint64_t)nw));
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    s->pos2_current = false;
-    s->fused_cur = 0;                  // (the caller's state is in d_pos / d_logp: whatever a failed run left in copy 1 is void)
-    s->generation = 0;
-    s->dev_gen = 0;
-    s->moment_base = 0;
-    s->launches = 0;
-    s->have_run_events = false;
-    if (s->stream_chain) { HIP_TRY(hipStreamSynchronize(s->copy_stream)); s->blocks_copied = 0; s->blocks_waited = 0; s->flushed_done = -1; }
-    for (size_t w = 0; w < nw; ++w)
-        if (!std::isfinite(lp[w])) {
-            s->positions_set = false;
-            return fail(KMC_ERR_NONFINITE_LOGP,
-                        "walker " + std::to_string(w) + " has a non-finite initial log-pdf");
-        }
-    s->positions_set = true;
+    KMC_TRY(reset_run_state(s, /*eval_logp=*/false, 0, 0u));
     if (s->temper && replicate) KMC_TRY(replicate_rung0(s));     // the same ensemble on every rung
     return KMC_OK;
+}
+KMC_EXPORT kmc_status kmc_sampler_set_positions(kmc_sampler* s, const double* theta_host)
+{
+    return set_positions_rung0(s, theta_host, true);
 }
 
 // ---- parallel tempering: every rung in and out (include/kissmcmc_hip.h) ---------------------------------------------------
@@ -368,27 +365,20 @@ KMC_EXPORT kmc_status kmc_sampler_set_rung_state(kmc_sampler* s, const double* p
     // rung 0 through the untempered entry points (initial log-pdfs, counters, moments, the finiteness check) ...
     if (generation == 0 && !logp_host) {
         KMC_TRY(set_positions_rung0(s, pos_host, false));
-        if (naccept_host) {
-            std::vector<uint32_t> na(nw);
-            for (size_t i = 0; i < nw; ++i) na[i] = (uint32_t)naccept_host[i];
-            HIP_TRY(copy_sync(s->d_naccept, na.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-        }
+        if (naccept_host) HIP_TRY(upload_u32(s, s->d_naccept, naccept_host, nw));
     } else {
         KMC_TRY(set_state_rung0(s, pos_host, logp_host, naccept_host, generation));
     }
     // ... then the others the same way: rows, log-pdfs (given or evaluated), counters; klast as rung 0's (unused: moments are rung 0's)
+    // (every rung's rows go up before any rung's log-pdfs are looked at: a non-finite one is reported with all rows in place, positions_set false)
+    for (int t = 1; t < s->ntemps; ++t) HIP_TRY(upload_rows(s, rung_pos(s, t), pos_host + (size_t)t * nw * nd, nw));
+    // likelihood tempering: every rung's S and prior again from the rows (and the log-pdfs, unless given): the same bits
+    if (s->temper_like) KMC_TRY(eval_like_all(s, logp_host == nullptr));
     std::vector<double> lp(nw);
-    std::vector<uint32_t> na(nw);
-    if (s->temper_like) {                  // every rung's S and prior again from the rows (and the log-pdfs, unless given): the same bits
-        for (int t = 1; t < s->ntemps; ++t) HIP_TRY(upload_rows(s, rung_pos(s, t), pos_host + (size_t)t * nw * nd, nw));
-        KMC_TRY(eval_like_all(s, logp_host == nullptr));
-    }
     for (int t = 1; t < s->ntemps; ++t) {
-        HIP_TRY(upload_rows(s, rung_pos(s, t), pos_host + (size_t)t * nw * nd, nw));
         if (logp_host) HIP_TRY(copy_sync(rung_logp(s, t), logp_host + (size_t)t * nw, nw * sizeof(double), hipMemcpyHostToDevice, s->stream));
         else if (!s->temper_like) KMC_TRY(eval_initial_logp(s, nullptr, t));
-        for (size_t i = 0; i < nw; ++i) na[i] = naccept_host ? (uint32_t)naccept_host[(size_t)t * nw + i] : 0u;
-        HIP_TRY(copy_sync(rung_naccept(s, t), na.data(), nw * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(upload_u32(s, rung_naccept(s, t), naccept_host ? naccept_host + (size_t)t * nw : nullptr, nw));
         HIP_TRY(hipMemsetAsync(rung_naccept(s, t) + nw, 0, nw * sizeof(uint32_t), s->stream));
         HIP_TRY(copy_sync(lp.data(), rung_logp(s, t), nw * sizeof(double), hipMemcpyDeviceToHost, s->stream));
         for (size_t w = 0; w < nw; ++w)
@@ -404,17 +394,12 @@ KMC_EXPORT kmc_status kmc_sampler_get_rung_state(kmc_sampler* s, double* pos_hos
 {
     if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
     if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_rung_state: the sampler was created without parallel tempering (ntemps < 2)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     const size_t nw = (size_t)s->nrows, nd = (size_t)s->cfg.ndim;
-    std::vector<uint32_t> na(nw);
     for (int t = 0; t < s->ntemps; ++t) {
         if (pos_host) HIP_TRY(download_rows(s, pos_host + (size_t)t * nw * nd, rung_pos(s, t), nw));
         if (logp_host) HIP_TRY(copy_sync(logp_host + (size_t)t * nw, rung_logp(s, t), nw * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        if (naccept_host) {
-            HIP_TRY(copy_sync(na.data(), rung_naccept(s, t), nw * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-            for (size_t i = 0; i < nw; ++i) naccept_host[(size_t)t * nw + i] = (int64_t)na[i];
-        }
+        if (naccept_host) HIP_TRY(download_u32(s, naccept_host + (size_t)t * nw, rung_naccept(s, t), nw));
     }
     if (logp_sum_host) HIP_TRY(copy_sync(logp_sum_host, s->d_rung_sum, (size_t)s->ntemps * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     return KMC_OK;
@@ -424,8 +409,7 @@ KMC_EXPORT kmc_status kmc_sampler_get_rung_loglike(kmc_sampler* s, double* logli
 {
     if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
     if (!s->temper_like) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_rung_loglike: the sampler was created without likelihood tempering (temper_mode = KMC_TEMPER_LIKELIHOOD)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     const size_t n = (size_t)s->ntemps * (size_t)s->nrows;
     if (loglike_host) HIP_TRY(copy_sync(loglike_host, s->d_like, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (logprior_host) HIP_TRY(copy_sync(logprior_host, s->d_prior, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -437,8 +421,7 @@ KMC_EXPORT kmc_status kmc_sampler_set_rung_loglike_sum(kmc_sampler* s, const dou
 {
     if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
     if (!s->temper_like) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_set_rung_loglike_sum: the sampler was created without likelihood tempering (temper_mode = KMC_TEMPER_LIKELIHOOD)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     if (loglike_sum_host) HIP_TRY(copy_sync(s->d_like_sum, loglike_sum_host, (size_t)s->ntemps * sizeof(double), hipMemcpyHostToDevice, s->stream));
     else HIP_TRY(fill_sync(s->d_like_sum, 0, (size_t)s->ntemps * sizeof(double), s->stream));
     return KMC_OK;
@@ -448,8 +431,7 @@ KMC_EXPORT kmc_status kmc_sampler_get_swaps(kmc_sampler* s, uint64_t* nswap_host
 {
     if (!s || !nswap_host) return fail(KMC_ERR_BAD_ARG, "null argument");
     if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_swaps: the sampler was created without parallel tempering (ntemps < 2)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     std::vector<unsigned long long> ns((size_t)s->ntemps);
     HIP_TRY(copy_sync(ns.data(), s->d_nswap, ns.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s->stream));
     for (int t = 0; t + 1 < s->ntemps; ++t) nswap_host[t] = (uint64_t)ns[(size_t)t];
@@ -460,8 +442,7 @@ KMC_EXPORT kmc_status kmc_sampler_get_ladder(kmc_sampler* s, double* betas_host,
 {
     if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
     if (!s->temper) return fail(KMC_ERR_BAD_ARG, "kmc_sampler_get_ladder: the sampler was created without parallel tempering (ntemps < 2)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     const size_t nt = (size_t)s->ntemps;
     if (betas_host) HIP_TRY(copy_sync(betas_host, s->d_betas, nt * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (S_host && nt > 2) HIP_TRY(copy_sync(S_host, s->d_S, (nt - 2) * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -492,8 +473,7 @@ KMC_EXPORT kmc_status kmc_sampler_set_ladder(kmc_sampler* s, const double* betas
         if (std::isnan(S_host[j])) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: kmc_sampler_set_ladder: S must not be NaN");
     for (size_t t = 0; t + 1 < nt; ++t)
         if (round_acc_host[t] > (uint64_t)s->nrows) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: kmc_sampler_set_ladder: round_acc counts at most nwalkers exchanges per pair");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     std::vector<unsigned long long> tail(nt + 2, 0ull);                    // round_acc, then the ticket (0: between sweeps) and the rounds skipped
     for (size_t t = 0; t + 1 < nt; ++t) tail[t] = (unsigned long long)round_acc_host[t];
     tail[nt + 1] = (unsigned long long)*skipped_host;
@@ -506,9 +486,7 @@ KMC_EXPORT kmc_status kmc_sampler_set_ladder(kmc_sampler* s, const double* betas
 KMC_EXPORT kmc_status kmc_sampler_get_positions(kmc_sampler* s, double* host)
 {
     if (!s || !host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    KMC_TRY(check_p2p_err(s));
+    KMC_TRY(settle(s, /*p2p_err=*/true));
     HIP_TRY(download_rows(s, host, s->d_pos, (size_t)s->nrows));
     return KMC_OK;
 }
@@ -516,9 +494,7 @@ KMC_EXPORT kmc_status kmc_sampler_get_positions(kmc_sampler* s, double* host)
 KMC_EXPORT kmc_status kmc_sampler_get_logp(kmc_sampler* s, double* host)
 {
     if (!s || !host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    KMC_TRY(check_p2p_err(s));
+    KMC_TRY(settle(s, /*p2p_err=*/true));
     HIP_TRY(copy_sync(host, s->d_logp, (size_t)s->nrows * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     return KMC_OK;
 }
@@ -526,12 +502,8 @@ KMC_EXPORT kmc_status kmc_sampler_get_logp(kmc_sampler* s, double* host)
 KMC_EXPORT kmc_status kmc_sampler_get_naccept(kmc_sampler* s, int64_t* host)
 {
     if (!s || !host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    KMC_TRY(check_p2p_err(s));
-    std::vector<uint32_t> tmp((size_t)s->nrows);
-    HIP_TRY(copy_sync(tmp.data(), s->d_naccept, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    for (size_t i = 0; i < tmp.size(); ++i) host[i] = (int64_t)tmp[i];
+    KMC_TRY(settle(s, /*p2p_err=*/true));
+    HIP_TRY(download_u32(s, host, s->d_naccept, (size_t)s->nrows));
     return KMC_OK;
 }
 
@@ -545,135 +517,147 @@ KMC_EXPORT kmc_status kmc_sampler_get_accept_ratio(kmc_sampler* s, double* host)
     return KMC_OK;
 }
 
+// ---- streaming moments (KMC_MOMENTS): one function per accumulator layout adds what the device holds into S / Q [ndim]; every one keeps
+// its summation order (the sums are compared bit for bit: tests/test_gpu_state_routes.py) --------------------------------------------------
+namespace {
+hipError_t fetch(const kmc_sampler* s, const double* dev, size_t n, std::vector<double>* h)
+{
+    h->resize(n);
+    return copy_sync(h->data(), dev, n * sizeof(double), hipMemcpyDeviceToHost, s->stream);
+}
+
+// rows [count][ld] of per-dimension sums, added up in row order: per walker (one launch per generation: laid out like the rows), per island
+// (island and resident mode), per wave (half_step_staged with staged_tile_moments)
+void add_rows(const double* hs, const double* hq, int64_t count, int64_t ld, int64_t nd, double* S, double* Q)
+{
+    for (int64_t r = 0; r < count; ++r)
+        for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += hs[(size_t)(r * ld + d)]; Q[(size_t)d] += hq[(size_t)(r * ld + d)]; }
+}
+
+// transposed fold (kmc_kernels.hpp, FoldT; K == 2, L = 8 / 16 / 32): every lane of a wave owns NVL of the wave's 8 L / 64 * 64 sums -- sums and
+// sums of squares in ONE array [nwaves][NVL][64], added up wave, then register, then lane
+void add_transposed(const double* h, int L, int64_t nwaves, int64_t nd, double* S, double* Q)
+{
+    const int NVL = 8 * L / 64;
+    for (int64_t w = 0; w < nwaves; ++w)
+        for (int r = 0; r < NVL; ++r)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int b3 = (lane >> 3) & 1, b4 = (lane >> 4) & 1, b5 = (lane >> 5) & 1;
+                const int v = L == 8 ? 4 * b3 + 2 * b4 + b5 : L == 16 ? 4 * b4 + 2 * b5 + r : 4 * b5 + r;
+                const int64_t d = 2 * ((int64_t)((v >> 1) & 1) * L + (lane & (L - 1))) + (v & 1);
+                if (d >= nd) continue;
+                const double x = h[(size_t)((w * NVL + r) * 64 + lane)];
+                if (v >> 2) Q[(size_t)d] += x; else S[(size_t)d] += x;
+            }
+}
+bool transposed(int L, int K) { return K == 2 && (L == 8 || L == 16 || L == 32); }
+
+// the vector kernel's plain layout: per chunk k and thread t a pair of dimensions, [K][stride][2]
+void add_striped(const double* hs, const double* hq, int L, int K, int64_t stride, int64_t nd, double* S, double* Q)
+{
+    for (int k = 0; k < K; ++k)
+        for (int64_t t = 0; t < stride; ++t) {
+            const int64_t d0 = 2 * ((int64_t)k * L + (t % L));
+            const int64_t idx = 2 * ((int64_t)k * stride + t);
+            if (d0 < nd) { S[(size_t)d0] += hs[(size_t)idx]; Q[(size_t)d0] += hq[(size_t)idx]; }
+            if (d0 + 1 < nd) { S[(size_t)d0 + 1] += hs[(size_t)idx + 1]; Q[(size_t)d0 + 1] += hq[(size_t)idx + 1]; }
+        }
+}
+
+// one walker per lane (half_step_generic; half_step_staged otherwise): columns [ndim][stride]
+void add_columns(const double* hs, const double* hq, int64_t stride, int64_t nd, double* S, double* Q)
+{
+    for (int64_t d = 0; d < nd; ++d)
+        for (int64_t t = 0; t < stride; ++t) { S[(size_t)d] += hs[(size_t)(d * stride + t)]; Q[(size_t)d] += hq[(size_t)(d * stride + t)]; }
+}
+
+// One launch per generation.  The lane-striped form credits a value when it is replaced (sojourn weights, like the two-launch kernels): every walker's
+// CURRENT value still stands for the samples taken since its last move -- credited here, on the host, leaving the device state as it is.
+kmc_status add_generation_sums(kmc_sampler* s, double* S, double* Q)
+{
+    const int64_t nd = s->cfg.ndim, nw = s->cfg.nwalkers, ld = s->ld;
+    if (s->fused_fold) {
+        const int64_t nwaves = s->nislands;
+        std::vector<double> hs;
+        HIP_TRY(fetch(s, s->d_isum, (size_t)(nwaves * (8 * s->fused_L / 64) * 64), &hs));
+        add_transposed(hs.data(), s->fused_L, nwaves, nd, S, Q);
+    } else {
+        std::vector<double> hs, hq;                   // (freed before the rows below are fetched, as they always were: 2 x 2 MiB at 16 384 x 16)
+        HIP_TRY(fetch(s, s->d_isum, (size_t)(ld * nw), &hs));
+        HIP_TRY(fetch(s, s->d_isumsq, (size_t)(ld * nw), &hq));
+        add_rows(hs.data(), hq.data(), nw, ld, nd, S, Q);
+    }
+    if (s->fused_L == 0) return KMC_OK;
+    std::vector<double> hp;
+    std::vector<uint32_t> kl((size_t)nw);
+    HIP_TRY(fetch(s, s->d_pos, (size_t)(ld * nw), &hp));
+    HIP_TRY(copy_sync(kl.data(), s->d_klast, kl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    const uint32_t done = (uint32_t)samples_done(s);
+    for (int64_t w = 0; w < nw; ++w) {
+        const double wgt = (double)(done - kl[(size_t)w]);
+        if (wgt == 0.0) continue;
+        for (int64_t d = 0; d < nd; ++d) {
+            const double x = hp[(size_t)(w * ld + d)];
+            S[(size_t)d] += x * wgt;
+            Q[(size_t)d] += (x * x) * wgt;
+        }
+    }
+    return KMC_OK;
+}
+
+kmc_status add_island_sums(kmc_sampler* s, double* S, double* Q)
+{
+    const int64_t per = 4 * (int64_t)s->island_K, nd = s->cfg.ndim;
+    std::vector<double> hs, hq;
+    HIP_TRY(fetch(s, s->d_isum, (size_t)(s->nislands * per), &hs));
+    HIP_TRY(fetch(s, s->d_isumsq, (size_t)(s->nislands * per), &hq));
+    add_rows(hs.data(), hq.data(), s->nislands, per, nd < per ? nd : per, S, Q);
+    return KMC_OK;
+}
+
+// two launches per generation, after flush_moments_now
+kmc_status add_two_launch_sums(kmc_sampler* s, double* S, double* Q)
+{
+    const int64_t nd = s->cfg.ndim;
+    std::vector<double> hs, hq;
+    HIP_TRY(fetch(s, s->d_msum, (size_t)s->macc_elems, &hs));
+    HIP_TRY(fetch(s, s->d_msumsq, (size_t)s->macc_elems, &hq));
+    if (s->plan.vec && transposed(s->plan.L, s->plan.K)) add_transposed(hs.data(), s->plan.L, s->macc_stride / 64, nd, S, Q);
+    else if (s->plan.vec) add_striped(hs.data(), hq.data(), s->plan.L, s->plan.K, s->macc_stride, nd, S, Q);
+    else if (s->user && s->uk.staged != nullptr && staged_tile_moments((int)nd)) add_rows(hs.data(), hq.data(), s->macc_stride / 64, s->ld, nd, S, Q);
+    else add_columns(hs.data(), hq.data(), s->macc_stride, nd, S, Q);
+    return KMC_OK;
+}
+
+// The tail of every read-out, what was credited elsewhere: by temper_sweep when walkers left rung 0 ([2][ld] behind logp_sum; a ladder runs two
+// launches per generation), and by a sampler until it stopped running one launch per generation (unfuse: carried on the host)
+kmc_status add_credits_from_elsewhere(kmc_sampler* s, double* S, double* Q)
+{
+    const int64_t nd = s->cfg.ndim;
+    if (s->temper && s->plan.vec) {
+        std::vector<double> ts;
+        HIP_TRY(fetch(s, s->d_tsum, 2 * (size_t)s->ld, &ts));
+        for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += ts[(size_t)d]; Q[(size_t)d] += ts[(size_t)(s->ld + d)]; }
+    }
+    for (int64_t d = 0; !s->carry_sum.empty() && d < nd; ++d) { S[(size_t)d] += s->carry_sum[(size_t)d]; Q[(size_t)d] += s->carry_sumsq[(size_t)d]; }
+    return KMC_OK;
+}
+}  // namespace
+
 KMC_EXPORT kmc_status kmc_sampler_get_moments(kmc_sampler* s, double* sum, double* sumsq, int64_t* n)
 {
     if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
     if (!s->d_msum) return fail(KMC_ERR_BAD_ARG, "sampler was created without KMC_MOMENTS");
     HIP_TRY(hipSetDevice(s->cfg.device));
-    if (s->fused) {
-        // one launch per generation: per-walker sums [nwalkers][ld] (laid out like the rows), added up in walker order -- or, lane-striped rows with
-        // K == 2 and L = 8 / 16 / 32, per-wave accumulators in the vector kernels' transposed layout (kmc_kernels.hpp: FoldT), added up in wave order
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        const int64_t nd = s->cfg.ndim, nw = s->cfg.nwalkers, ld = s->ld;
-        std::vector<double> S((size_t)nd, 0.0), Q((size_t)nd, 0.0);
-        if (s->fused_fold) {
-            const int L = s->fused_L, NVL = 8 * L / 64;
-            const int64_t nwaves = s->nislands;
-            std::vector<double> hs((size_t)(nwaves * NVL * 64));
-            HIP_TRY(copy_sync(hs.data(), s->d_isum, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-            for (int64_t w = 0; w < nwaves; ++w)
-                for (int r = 0; r < NVL; ++r)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int b3 = (lane >> 3) & 1, b4 = (lane >> 4) & 1, b5 = (lane >> 5) & 1;
-                        const int v = L == 8 ? 4 * b3 + 2 * b4 + b5 : L == 16 ? 4 * b4 + 2 * b5 + r : 4 * b5 + r;
-                        const int64_t d = 2 * ((int64_t)((v >> 1) & 1) * L + (lane & (L - 1))) + (v & 1);
-                        if (d >= nd) continue;
-                        const double x = hs[(size_t)((w * NVL + r) * 64 + lane)];
-                        if (v >> 2) Q[(size_t)d] += x; else S[(size_t)d] += x;
-                    }
-        } else {
-            std::vector<double> hs((size_t)(ld * nw)), hq((size_t)(ld * nw));
-            HIP_TRY(copy_sync(hs.data(), s->d_isum, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(copy_sync(hq.data(), s->d_isumsq, hq.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-            for (int64_t w = 0; w < nw; ++w)
-                for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += hs[(size_t)(w * ld + d)]; Q[(size_t)d] += hq[(size_t)(w * ld + d)]; }
-        }
-        if (s->fused_L > 0) {
-            // the lane-striped form credits a value when it is replaced (sojourn weights, like the two-launch kernels): every walker's CURRENT value
-            // still stands for the samples taken since its last move -- credited here, on the host, leaving the device state as it is
-            std::vector<double> hp((size_t)(ld * nw));
-            std::vector<uint32_t> kl((size_t)nw);
-            HIP_TRY(copy_sync(hp.data(), s->d_pos, hp.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-            HIP_TRY(copy_sync(kl.data(), s->d_klast, kl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-            const uint32_t done = (uint32_t)samples_done(s);
-            for (int64_t w = 0; w < nw; ++w) {
-                const double wgt = (double)(done - kl[(size_t)w]);
-                if (wgt == 0.0) continue;
-                for (int64_t d = 0; d < nd; ++d) {
-                    const double x = hp[(size_t)(w * ld + d)];
-                    S[(size_t)d] += x * wgt;
-                    Q[(size_t)d] += (x * x) * wgt;
-                }
-            }
-        }
-        for (int64_t d = 0; d < nd; ++d) {
-            if (sum) sum[d] = S[(size_t)d];
-            if (sumsq) sumsq[d] = Q[(size_t)d];
-        }
-        if (n) *n = (samples_done(s) - s->moment_base) * s->nlocal;
-        return KMC_OK;
-    }
-    if (s->islands || s->resident) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        const int64_t nd = s->cfg.ndim;
-        const size_t per = 4 * (size_t)s->island_K, ne = (size_t)s->nislands * per;
-        std::vector<double> hs(ne), hq(ne);
-        HIP_TRY(copy_sync(hs.data(), s->d_isum, ne * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(copy_sync(hq.data(), s->d_isumsq, ne * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        std::vector<double> S((size_t)nd, 0.0), Q((size_t)nd, 0.0);
-        for (int64_t b = 0; b < s->nislands; ++b)
-            for (size_t e = 0; e < per; ++e)
-                if ((int64_t)e < nd) { S[e] += hs[(size_t)b * per + e]; Q[e] += hq[(size_t)b * per + e]; }
-        for (int64_t d = 0; d < nd; ++d) {
-            if (sum) sum[d] = S[d];
-            if (sumsq) sumsq[d] = Q[d];
-        }
-        if (n) *n = (samples_done(s) - s->moment_base) * s->nlocal;
-        return KMC_OK;
-    }
-    KMC_TRY(flush_moments_now(s));
+    const bool two_launch = !s->fused && !s->islands && !s->resident;
+    if (two_launch) KMC_TRY(flush_moments_now(s));              // (launches on the stream: ahead of the drain)
     HIP_TRY(hipStreamSynchronize(s->stream));
-    KMC_TRY(check_p2p_err(s));
-    const int64_t nd = s->cfg.ndim;
-    std::vector<double> hs((size_t)s->macc_elems), hq((size_t)s->macc_elems);
-    HIP_TRY(copy_sync(hs.data(), s->d_msum, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(copy_sync(hq.data(), s->d_msumsq, hq.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    std::vector<double> S((size_t)nd, 0.0), Q((size_t)nd, 0.0);
-    if (s->plan.vec && s->plan.K == 2 && (s->plan.L == 8 || s->plan.L == 16 || s->plan.L == 32)) {
-        // transposed fold (kmc_kernels.hpp, FoldT): every lane of a wave owns NVL of the wave's 8 L / 64 * 64 sums
-        const int L = s->plan.L, NVL = 8 * L / 64;
-        const int64_t nwaves = s->macc_stride / 64;
-        for (int64_t w = 0; w < nwaves; ++w)
-            for (int r = 0; r < NVL; ++r)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int b3 = (lane >> 3) & 1, b4 = (lane >> 4) & 1, b5 = (lane >> 5) & 1;
-                    const int v = L == 8 ? 4 * b3 + 2 * b4 + b5 : L == 16 ? 4 * b4 + 2 * b5 + r : 4 * b5 + r;
-                    const int64_t d = 2 * ((int64_t)((v >> 1) & 1) * L + (lane & (L - 1))) + (v & 1);
-                    if (d >= nd) continue;
-                    const double x = hs[(size_t)((w * NVL + r) * 64 + lane)];
-                    if (v >> 2) Q[(size_t)d] += x; else S[(size_t)d] += x;
-                }
-    } else if (s->plan.vec) {
-        const int L = s->plan.L, K = s->plan.K;
-        for (int k = 0; k < K; ++k)
-            for (int64_t t = 0; t < s->macc_stride; ++t) {
-                const int64_t d0 = 2 * ((int64_t)k * L + (t % L));
-                const int64_t idx = 2 * ((int64_t)k * s->macc_stride + t);
-                if (d0 < nd) { S[d0] += hs[idx]; Q[d0] += hq[idx]; }
-                if (d0 + 1 < nd) { S[d0 + 1] += hs[idx + 1]; Q[d0 + 1] += hq[idx + 1]; }
-            }
-    } else if (s->user && s->uk.staged != nullptr && staged_tile_moments((int)nd)) {
-        // half_step_staged: one accumulator row [ld] per wave
-        for (int64_t w = 0; w < s->macc_stride / 64; ++w)
-            for (int64_t d = 0; d < nd; ++d) {
-                S[d] += hs[w * s->ld + d];
-                Q[d] += hq[w * s->ld + d];
-            }
-    } else {
-        for (int64_t d = 0; d < nd; ++d)
-            for (int64_t t = 0; t < s->macc_stride; ++t) {
-                S[d] += hs[d * s->macc_stride + t];
-                Q[d] += hq[d * s->macc_stride + t];
-            }
-    }
-    if (s->temper && s->plan.vec) {               // what temper_sweep credited when walkers left rung 0 ([2][ld] behind logp_sum)
-        std::vector<double> ts(2 * (size_t)s->ld);
-        HIP_TRY(copy_sync(ts.data(), s->d_tsum, ts.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += ts[(size_t)d]; Q[(size_t)d] += ts[(size_t)(s->ld + d)]; }
-    }
-    if (!s->carry_sum.empty())                    // what the sampler credited while it ran one launch per generation (unfuse)
-        for (int64_t d = 0; d < nd; ++d) { S[(size_t)d] += s->carry_sum[(size_t)d]; Q[(size_t)d] += s->carry_sumsq[(size_t)d]; }
-    for (int64_t d = 0; d < nd; ++d) {
+    if (two_launch) KMC_TRY(check_p2p_err(s));
+    const size_t nd = (size_t)s->cfg.ndim;
+    std::vector<double> S(nd, 0.0), Q(nd, 0.0);
+    KMC_TRY(s->fused ? add_generation_sums(s, S.data(), Q.data()) : two_launch ? add_two_launch_sums(s, S.data(), Q.data()) : add_island_sums(s, S.data(), Q.data()));
+    KMC_TRY(add_credits_from_elsewhere(s, S.data(), Q.data()));
+    for (size_t d = 0; d < nd; ++d) {
         if (sum) sum[d] = S[d];
         if (sumsq) sumsq[d] = Q[d];
     }
@@ -686,8 +670,7 @@ KMC_EXPORT kmc_status kmc_sampler_get_blobs(kmc_sampler* s, double* current, dou
 {
     if (!s) return fail(KMC_ERR_BAD_ARG, "null sampler");
     if (s->nblob == 0) return fail(KMC_ERR_BAD_ARG, "this sampler's density returns no blobs (kmc_user_density_create_body_blob)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     const size_t nb = (size_t)s->nblob;
     if (current) HIP_TRY(copy_sync(current, s->d_blob, (size_t)s->nrows * nb * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     if (stored) {
@@ -750,12 +733,9 @@ KMC_EXPORT kmc_status kmc_sampler_deal_unpack(kmc_sampler* s, const void* recv_d
 KMC_EXPORT kmc_status kmc_sampler_get_walker_ids(kmc_sampler* s, int64_t* host)
 {
     if (!s || !host) return fail(KMC_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     if (!s->d_ids) { for (int64_t i = 0; i < s->nrows; ++i) host[i] = i; return KMC_OK; }
-    std::vector<uint32_t> tmp((size_t)s->nrows);
-    HIP_TRY(copy_sync(tmp.data(), s->d_ids, tmp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    for (size_t i = 0; i < tmp.size(); ++i) host[i] = (int64_t)tmp[i];
+    HIP_TRY(download_u32(s, host, s->d_ids, (size_t)s->nrows));
     return KMC_OK;
 }
 
@@ -765,14 +745,10 @@ KMC_EXPORT kmc_status kmc_sampler_set_walker_ids(kmc_sampler* s, const int64_t* 
 {
     if (!s || !host) return fail(KMC_ERR_BAD_ARG, "null argument");
     if (!s->d_ids) return fail(KMC_ERR_BAD_ARG, "sampler was created without kmc_config.deal_count");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    std::vector<uint32_t> tmp((size_t)s->nrows);
-    for (size_t i = 0; i < tmp.size(); ++i) {
+    KMC_TRY(settle(s));
+    for (int64_t i = 0; i < s->nrows; ++i)
         if (host[i] < 0 || host[i] >= (int64_t)1 << 32) return fail(KMC_ERR_BAD_ARG, "walker index out of range");
-        tmp[i] = (uint32_t)host[i];
-    }
-    HIP_TRY(copy_sync(s->d_ids, tmp.data(), tmp.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(upload_u32(s, s->d_ids, host, (size_t)s->nrows));
     return KMC_OK;
 }
 
@@ -844,14 +820,12 @@ KMC_EXPORT kmc_status kmc_logpdf_eval(const kmc_config* cfg, const double* pos_d
         if (cfg->ndim < 1 || cfg->ndim > kDataMaxDim) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: ndim must be in 1 .. " + std::to_string(kDataMaxDim));
         DataKernels dk;
         KMC_TRY(load_data(ud, cfg->ndim, &dk));
-        double* part = nullptr;
+        ScopedDeviceBlock part;
         const DataPlan plan = data_plan(ud, nrows);                  // (one plan for the allocation and the launch)
         const size_t part_doubles = (size_t)plan.nblocks * (size_t)nrows;
-        HIP_TRY(hipMalloc((void**)&part, part_doubles * sizeof(double)));
-        hipError_t e = launch_data_eval(dk, ud, plan, pos_dev, nrows, (int32_t)cfg->ndim, dp.p, part, part_doubles, logp_dev, (hipStream_t)hip_stream);
-        if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)hip_stream);     // (the scratch and dk's hold on the module end with this scope)
-        (void)hipFree(part);
-        HIP_TRY(e);
+        HIP_TRY(part.alloc(part_doubles * sizeof(double)));
+        HIP_TRY(launch_data_eval(dk, ud, plan, pos_dev, nrows, (int32_t)cfg->ndim, dp.p, part.as<double>(), part_doubles, logp_dev, (hipStream_t)hip_stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));      // (the scratch and dk's hold on the module end with this scope)
         return KMC_OK;
     }
     const LogpdfFn lp = logpdf_fn(cfg->density);
@@ -875,19 +849,14 @@ KMC_EXPORT kmc_status kmc_logpdf_eval_host(const kmc_config* cfg, const double* 
     HIP_TRY(hipSetDevice(cfg->device));
     ScopedStream ss;
     HIP_TRY(ss.create());
-    double *dpos = nullptr, *dlp = nullptr;
+    ScopedDeviceBlock dlp, dpos;                                     // (freed before the stream goes: dpos, then dlp)
     const size_t nb = (size_t)nrows * (size_t)cfg->ndim * sizeof(double);
-    HIP_TRY(hipMalloc(&dpos, nb));
-    hipError_t e = hipMalloc(&dlp, (size_t)nrows * sizeof(double));
-    kmc_status st = KMC_OK;
-    if (e == hipSuccess) e = copy_sync(dpos, pos_host, nb, hipMemcpyHostToDevice, ss.st);
-    if (e == hipSuccess) st = kmc_logpdf_eval(cfg, dpos, dlp, nrows, ss.st);
-    if (e == hipSuccess && st == KMC_OK) e = hipStreamSynchronize(ss.st);
-    if (e == hipSuccess && st == KMC_OK) e = copy_sync(logp_host, dlp, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ss.st);
-    (void)hipFree(dpos);
-    (void)hipFree(dlp);
-    if (st != KMC_OK) return st;
-    HIP_TRY(e);
+    HIP_TRY(dpos.alloc(nb));
+    HIP_TRY(dlp.alloc((size_t)nrows * sizeof(double)));
+    HIP_TRY(copy_sync(dpos.p, pos_host, nb, hipMemcpyHostToDevice, ss.st));
+    KMC_TRY(kmc_logpdf_eval(cfg, dpos.as<double>(), dlp.as<double>(), nrows, ss.st));
+    HIP_TRY(hipStreamSynchronize(ss.st));
+    HIP_TRY(copy_sync(logp_host, dlp.p, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ss.st));
     return KMC_OK;
 }
 
@@ -907,25 +876,19 @@ KMC_EXPORT kmc_status kmc_logpdf_blob_eval_host(const kmc_config* cfg, const dou
     ScopedStream ss;
     HIP_TRY(ss.create());
     const size_t nb = (size_t)nrows * (size_t)cfg->ndim * sizeof(double), bb = (size_t)nrows * (size_t)ud->nblob * sizeof(double);
-    char* buf = nullptr;
-    HIP_TRY(hipMalloc((void**)&buf, nb + (size_t)nrows * sizeof(double) + bb));
-    double* dpos = reinterpret_cast<double*>(buf);
+    UserKernels uk;                                                  // (its hold on the module ends after the block is freed)
+    ScopedDeviceBlock buf;
+    HIP_TRY(buf.alloc(nb + (size_t)nrows * sizeof(double) + bb));
+    double* dpos = buf.as<double>();
     double* dlp = dpos + (size_t)nrows * (size_t)cfg->ndim;
     double* dbl = dlp + nrows;
-    UserKernels uk;
-    kmc_status st = load_user(const_cast<kmc_user_density*>(ud), false, 0, 0, 0, false, &uk, 0, false, 0, false, cfg->ndim);
-    hipError_t e = hipSuccess;
-    if (st == KMC_OK) {
-        e = copy_sync(dpos, pos_host, nb, hipMemcpyHostToDevice, ss.st);
-        const LogpdfArgs la{dpos, dlp, nrows, (int32_t)cfg->ndim, (int32_t)cfg->ndim, dp, dbl};
-        if (e == hipSuccess) e = launch_module(uk.logpdf, (unsigned)((nrows + 255) / 256), 256u, ss.st, la);
-        if (e == hipSuccess) e = hipStreamSynchronize(ss.st);
-        if (e == hipSuccess) e = copy_sync(logp_host, dlp, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ss.st);
-        if (e == hipSuccess) e = copy_sync(blob_host, dbl, bb, hipMemcpyDeviceToHost, ss.st);
-    }
-    (void)hipFree(buf);
-    if (st != KMC_OK) return st;
-    HIP_TRY(e);
+    KMC_TRY(load_user(const_cast<kmc_user_density*>(ud), false, 0, 0, 0, false, &uk, 0, false, 0, false, cfg->ndim));
+    HIP_TRY(copy_sync(dpos, pos_host, nb, hipMemcpyHostToDevice, ss.st));
+    const LogpdfArgs la{dpos, dlp, nrows, (int32_t)cfg->ndim, (int32_t)cfg->ndim, dp, dbl};
+    HIP_TRY(launch_module(uk.logpdf, (unsigned)((nrows + 255) / 256), 256u, ss.st, la));
+    HIP_TRY(hipStreamSynchronize(ss.st));
+    HIP_TRY(copy_sync(logp_host, dlp, (size_t)nrows * sizeof(double), hipMemcpyDeviceToHost, ss.st));
+    HIP_TRY(copy_sync(blob_host, dbl, bb, hipMemcpyDeviceToHost, ss.st));
     return KMC_OK;
 }
 
@@ -937,8 +900,7 @@ KMC_EXPORT kmc_status kmc_sampler_int_acorr(kmc_sampler* s, double c, double* ta
     if (s->stream_chain) return fail(KMC_ERR_UNSUPPORTED, "KMC_STREAM_CHAIN: the chain is on the host; use kmc_int_acorr on it");
     if (s->ld != s->cfg.ndim) return fail(KMC_ERR_UNSUPPORTED, "odd ndim: rows are padded on the device; use kmc_int_acorr on the downloaded chain");
     if (s->f32) return fail(KMC_ERR_UNSUPPORTED, "KMC_F32: the device chain is float; use kmc_int_acorr on the downloaded chain");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    KMC_TRY(settle(s));
     const int64_t ns = samples_done(s);
     KMC_TRY(int_acorr_check(ns, s->nlocal, s->cfg.ndim, c, tau, converged));
     return int_acorr_device(s->d_chain, ns, s->nlocal, s->cfg.ndim, c, tau, converged);
