@@ -1002,6 +1002,87 @@ kmc_status  kmc_pointwise_plan(int64_t n, int64_t ndata, int64_t* run_len, int64
  * elpd_waic, se, waic, n_high, n_nan.  KMC_ERR_BAD_ARG for J < 1, n < 2 or a null stats / totals. */
 kmc_status  kmc_waic_stats(int64_t J, int64_t n, const double* stats, double* lppd_j, double* p_waic_j, double* elpd_j, double* totals);
 
+/* ---- PSIS-LOO: Pareto-smoothed importance-sampling leave-one-out cross-validation of a data density ----
+ * (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024.)  Rows, observations and terms l[r][j] are those of the
+ * block above; the observations are always the density's own (a held-out observation has no leave-one-out), restricted to
+ * [obs_first, obs_first + obs_count).  n >= 5.  The [n][J] matrix never exists: every pass recomputes the terms.
+ *
+ * Per observation j, over the n rows, with l_r = l[r][j]:
+ *  1. Shift.  m_j = min_r l_r and x_r = m_j - l_r (<= 0, in double: the shifted log importance ratio).  When a term is NaN or m_j is
+ *     not finite, every output of the observation is NaN (n_tail_j: -1) and it counts in n_nan.  l_r = +inf is an ordinary value
+ *     (x_r = -inf, weight 0).
+ *  2. Tail.  M = ceil(min(0.2 n, 3 sqrt(n / r_eff))), the products and the root in double as written (ArviZ's rule; kmc_psis_plan
+ *     returns it).  Cut-off xc_j = max(log(DBL_MIN), x_[n-M-1]) with x_[i] the ascending order statistics, i.e. the (M+1)-th largest,
+ *     found exactly.  The tail is {r : x_r > xc_j} (ArviZ's strict rule, not loo's positional one): ties with the cut-off stay out,
+ *     n_tail_j <= M.
+ *  3. Fit.  nt = n_tail_j.  nt <= 4: k = +inf, the tail keeps its raw weights.  Otherwise, with the tail ascending x_(1..nt) and
+ *     e_i = exp(x_(i)) - exp(xc_j), Zhang & Stephens' estimator as ArviZ's _gpdfit writes it:  m_est = 30 + floor(sqrt(nt));
+ *     b_i = (1 - sqrt(m_est / (i - 0.5))) / (3 e_[floor(nt/4 + 0.5) - 1]) + 1 / e_[nt-1], i = 1..m_est (0-based indices into e);
+ *     kappa_i = mean_t log1p(-b_i e_t);  L_i = nt (log(-b_i / kappa_i) - kappa_i - 1);  w_i = 1 / sum_q exp(L_q - L_i); entries with
+ *     w_i < 10 DBL_EPSILON are dropped and the rest divided by their sum;  b = sum w_i b_i;  kappa = mean_t log1p(-b e_t);
+ *     sigma = -kappa / b;  k = (nt kappa + 5) / (nt + 10).
+ *  4. Smoothing.  k finite: s_i = min(0, log(sigma expm1(-k log1p(-p_i)) / k + exp(xc_j))), p_i = (i - 0.5) / nt, given to the tail in
+ *     sorted order; NaN where sigma is not finite and positive, which makes the observation NaN.  k not finite: s_i = x_(i).
+ *  5. Result.  W_j = sum_{r outside the tail} exp(x_r) + sum_i exp(s_i),  N_j = (n - nt) + sum_i exp(s_i - x_(i)),
+ *     elpd_loo_j = m_j + log(N_j / W_j):  ArviZ's logsumexp(log weights + l), with the raw product w_r p_r = exp(m_j) of a row outside
+ *     the tail taken exactly instead of through two roundings.  p_loo_j = lppd_j - elpd_loo_j, lppd_j from the two passes of the block
+ *     above over the same rows, run inside the same call.
+ *  6. Host stage (kmc_loo_stats; no device, fixed order):  elpd_loo, p_loo, lppd: the data-density contract's pairwise tree over the
+ *     observations in order;  se = sqrt(J tree_j((elpd_loo_j - elpd_loo / J)^2) / (J - 1));  looic = -2 elpd_loo;  n_nan = #{j :
+ *     elpd_loo_j is NaN};  k_counts = #{k <= 0.5}, #{0.5 < k <= 0.7}, #{0.7 < k <= 1}, #{k > 1} (+inf in the last, NaN in none).
+ *
+ * Order of summation.  The sum outside the tail runs over the runs of kmc_pointwise_plan(n, J), J the density's own count whatever
+ * the range: a run in row order from 0.0, the runs' partials in run order from 0.0.  The sums of steps 3 to 5 over a tail run in an
+ * order that depends on its length alone: lane l of 256 adds the entries l, l + 256, ... from 0.0, and the 256 partials are folded by
+ * halving (p[l] += p[l + h], h = 128 .. 1); b and the sum of the kept w_i are added in index order.  kmc_psis_smooth_host is the same
+ * code compiled for the host (csrc/kmc_psis_fit.hpp), so it differs from the device in exp / log / log1p / expm1 alone.  No
+ * floating-point atomics; the tail is collected through an integer cursor per observation and then sorted, the select counts in
+ * integers.  So two identical calls return the same bits, a selection gives the bits of the same call on the rows copied out,
+ * kmc_sampler_psis_loo equals kmc_chain_psis_loo on the downloaded chain, and the outputs of an observation depend neither on the
+ * range asked for nor on workspace_bytes.
+ *
+ * The device stage.  Observations are worked in blocks whose tail buffer and counters fit workspace_bytes
+ * (0: 1 GiB; at least 64 observations).  Per block 2 + 16 passes recompute the terms: the minimum, 16 digits of 4 bits of a radix
+ * select on the bits of l - m_j, and the gather; then one workgroup per observation sorts the tail and fits.
+ *
+ * stats [4][obs_count]: elpd_loo_j, pareto_k, n_tail_j (as double; NaN where the observation is NaN), sigma_j.  lppd_j [obs_count].
+ * info (may be NULL) gets 12 numbers: n, M, the blocks, the observations of a block, the nanoseconds of the minimum pass, of the 16
+ * select passes, of the gather and of the fit (events; summed over the blocks), the terms of one recompute pass (n obs_count), the
+ * log1p evaluations of the fit, the nanoseconds of the two statistics passes, and the runs.
+ * Refusals: those of kmc_sampler_pointwise_stats, and KMC_ERR_BAD_ARG, naming the value, for r_eff not finite or <= 0, n < 5, obs_count
+ * < 1 or a range outside [0, J); KMC_ERR_UNSUPPORTED for n >= 2^31 and for M > 4096, naming n / r_eff (the tail of one observation is
+ * sorted in one workgroup's LDS): never a partial answer.  Not built: a per-observation r_eff, r_eff from the chain, moment matching. */
+kmc_status  kmc_sampler_psis_loo(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int64_t thin,
+                                 double r_eff, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes, double* stats, double* lppd_j,
+                                 int64_t* n_out, int64_t* info);
+kmc_status  kmc_chain_psis_loo(kmc_user_density* density, const double* params, const double* chain_host /* [nsamples][nwalkers][ndim] */,
+                               int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                               double r_eff, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes, int device, double* stats,
+                               double* lppd_j, int64_t* n_out, int64_t* info);
+/* Steps 1 and 2 alone, read out: tail [obs_count][tail_len], each row the tail's x ascending, padded with NaN; m_j, xc_j [obs_count];
+ * n_tail_j [obs_count] (-1 where the observation is NaN, and then its row, m_j and xc_j are NaN).  Outputs other than tail may be
+ * NULL.  tail_len holds the columns of `tail` on entry (size it by kmc_psis_plan; KMC_ERR_BAD_ARG when it is less than M) and M on
+ * return. */
+kmc_status  kmc_sampler_psis_tail(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first,
+                                  int64_t obs_count, int64_t workspace_bytes, double* tail, double* m_j, double* xc_j, int32_t* n_tail_j,
+                                  int64_t* tail_len, int64_t* n_out);
+kmc_status  kmc_chain_psis_tail(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples, int64_t nwalkers,
+                                int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first,
+                                int64_t obs_count, int64_t workspace_bytes, int device, double* tail, double* m_j, double* xc_j,
+                                int32_t* n_tail_j, int64_t* tail_len, int64_t* n_out);
+/* The cut of a call; needs no device; pointers may be NULL.  tail_len = M, m_est = 30 + floor(sqrt(M)) (the largest grid of a fit),
+ * obs_per_block (a multiple of 64: workspace_bytes over the bytes of one observation, 8 M + 72 nruns + 72), passes = 18 recompute
+ * passes per block.  Refuses what the calls refuse from n and r_eff, ndata outside 1 .. 2^30 and workspace_bytes < 0. */
+kmc_status  kmc_psis_plan(int64_t n, int64_t ndata, double r_eff, int64_t workspace_bytes, int64_t* tail_len, int64_t* m_est,
+                          int64_t* obs_per_block, int64_t* passes);
+/* Step 6; needs no device.  stats [4][J] and lppd_j [J] -> p_loo_j [J] (may be NULL) and totals [10]: elpd_loo, se, p_loo, looic,
+ * lppd, n_nan, k_counts[4].  KMC_ERR_BAD_ARG for J < 1, n < 5 or a null argument. */
+kmc_status  kmc_loo_stats(int64_t J, int64_t n, const double* stats, const double* lppd_j, double* p_loo_j, double* totals);
+/* Steps 3 and 4 for one observation on the host: x [nt] the tail ascending, every x_i in (xc, 0]; k_hat, sigma, s [nt] and sums [2] =
+ * sum_i exp(s_i), sum_i exp(s_i - x_(i)) (k_hat, sigma, sums may be NULL).  KMC_ERR_BAD_ARG, naming the value, for nt outside
+ * 0 .. 4096 or a tail that is not ascending within (xc, 0]. */
+kmc_status  kmc_psis_smooth_host(int64_t nt, const double* x, double xc, double* k_hat, double* sigma, double* s, double* sums);
+
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as
  * the half-step kernels compute it, for walkers walker0 .. walker0 + n - 1 of one step (= 2 * generation + half): the partner

@@ -67,6 +67,8 @@ SYMBOLS = [
     "kmc_sampler_covariance", "kmc_chain_covariance", "kmc_cov_plan", "kmc_cov_correlation",
     "kmc_sampler_pointwise_stats", "kmc_chain_pointwise_stats", "kmc_sampler_pointwise_loglike", "kmc_chain_pointwise_loglike",
     "kmc_pointwise_plan", "kmc_waic_stats",
+    "kmc_sampler_psis_loo", "kmc_chain_psis_loo", "kmc_sampler_psis_tail", "kmc_chain_psis_tail", "kmc_psis_plan", "kmc_loo_stats",
+    "kmc_psis_smooth_host",
 ]
 
 
@@ -308,6 +310,14 @@ def lib() -> C.CDLL:
     L.kmc_chain_pointwise_loglike.argtypes = host_chain + held_out + [C.c_int64, C.c_int64, C.c_int, dp, ip]
     L.kmc_pointwise_plan.argtypes = [C.c_int64, C.c_int64, ip, ip, i32p, i32p, ip]
     L.kmc_waic_stats.argtypes = [C.c_int64, C.c_int64, dp, dp, dp, dp, dp]
+    psis_sel = [C.c_double, C.c_int64, C.c_int64, C.c_int64]         # r_eff, obs_first, obs_count, workspace_bytes
+    L.kmc_sampler_psis_loo.argtypes = [vp, C.c_int64, bp, C.c_int64] + psis_sel + [dp, dp, ip, ip]
+    L.kmc_chain_psis_loo.argtypes = host_chain + psis_sel + [C.c_int, dp, dp, ip, ip]
+    L.kmc_sampler_psis_tail.argtypes = [vp, C.c_int64, bp, C.c_int64] + psis_sel + [dp, dp, dp, i32p, ip, ip]
+    L.kmc_chain_psis_tail.argtypes = host_chain + psis_sel + [C.c_int, dp, dp, dp, i32p, ip, ip]
+    L.kmc_psis_plan.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_int64, ip, ip, ip, ip]
+    L.kmc_loo_stats.argtypes = [C.c_int64, C.c_int64, dp, dp, dp, dp]
+    L.kmc_psis_smooth_host.argtypes = [C.c_int64, dp, C.c_double, dp, dp, dp, dp]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

@@ -53,7 +53,12 @@ def compare_waic(w_a, w_b):
     """The difference of two models' ``elpd_waic`` over the same observations, from the pointwise arrays of two :func:`waic` results
     (needs no device): dict ``elpd_diff = sum_j (elpd_a_j - elpd_b_j)`` (positive: ``a`` predicts better), ``se =
     sqrt(J var(elpd_a_j - elpd_b_j))`` with the sample variance (``J - 1``), and ``J``."""
-    a, b = np.asarray(w_a["elpd_j"], dtype=np.float64), np.asarray(w_b["elpd_j"], dtype=np.float64)
+    return _elpd_difference(w_a["elpd_j"], w_b["elpd_j"])
+
+
+def _elpd_difference(elpd_a_j, elpd_b_j):
+    """``elpd_diff``, ``se`` and ``J`` of two models' pointwise elpd (:func:`compare_waic`, ``compare_loo``)."""
+    a, b = np.asarray(elpd_a_j, dtype=np.float64), np.asarray(elpd_b_j, dtype=np.float64)
     if a.shape != b.shape or a.ndim != 1:
         raise ValueError("the two results are not over the same observations")
     d = a - b

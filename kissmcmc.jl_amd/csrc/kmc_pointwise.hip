@@ -1,8 +1,10 @@
 // kmc_pointwise.hip -- the pointwise log-likelihood of a data density over a stored chain, on the device where the chain, the data and
 // the compiled term are: the per-observation statistics behind WAIC (kmc_sampler_pointwise_stats, kmc_chain_pointwise_stats), the
 // matrix itself for a range of observations (kmc_sampler_pointwise_loglike, kmc_chain_pointwise_loglike), the plan (kmc_pointwise_plan)
-// and the pure host stage (kmc_waic_stats).  include/kissmcmc_hip.h has the definitions, DESIGN.md section 4k the plan.  Kernels:
-// kmc_pointwise.hpp, compiled at run time with the density's term as the module "pointwise:<ndim>".
+// and the pure host stage (kmc_waic_stats); and PSIS-LOO over the same rows (kmc_sampler_psis_loo, kmc_chain_psis_loo, the read-out of its
+// tails kmc_*_psis_tail, kmc_psis_plan, kmc_loo_stats, kmc_psis_smooth_host).  include/kissmcmc_hip.h has the definitions, DESIGN.md
+// sections 4k and 4l the plans.  Kernels: kmc_pointwise.hpp, compiled at run time with the density's term as the module "pointwise:<ndim>";
+// the folds and the PSIS fit, which do not touch the term, are compiled here.
 #include <algorithm>
 #include <cmath>
 #include <sstream>
@@ -50,6 +52,7 @@ struct PwKernels {
     std::shared_ptr<void> keep, keep_data;
     hipFunction_t pass[2][2] = {};                // [pass - 1][packed]
     hipFunction_t matrix = nullptr;
+    hipFunction_t psis[3][2] = {};                // [mode][packed]
 };
 
 kmc_status compile_pointwise(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
@@ -59,8 +62,9 @@ kmc_status compile_pointwise(kmc_user_density* ud, int64_t ndim, const std::vect
     auto it = ud->code.find(key);
     if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
     const std::string dir = user_header_dir();
-    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_pw = read_file(dir + "/kmc_pointwise.hpp");
-    if (h_dev.empty() || h_pw.empty()) return fail(KMC_ERR_BAD_ARG, "data density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
+    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_pw = read_file(dir + "/kmc_pointwise.hpp"),
+                      h_fit = read_file(dir + "/kmc_psis_fit.hpp");
+    if (h_dev.empty() || h_pw.empty() || h_fit.empty()) return fail(KMC_ERR_BAD_ARG, "data density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
     const std::string t = "<UserData, " + std::to_string(ndim) + ", " + std::to_string(ud->ncols);
     const std::string head = "extern \"C\" __global__ __launch_bounds__(" + std::to_string(kPwThreads) + ") void ";
     std::ostringstream src;
@@ -70,12 +74,16 @@ kmc_status compile_pointwise(kmc_user_density* ud, int64_t ndim, const std::vect
         << head << "kmc_pw_pass1_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, true>(a); }\n"
         << head << "kmc_pw_pass2_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, true>(a); }\n"
         << head << "kmc_pw_matrix(const kmc_pw::PwArgs a) { kmc_pw::pw_matrix" << t << ">(a); }\n";
-    const char* headers[2] = {h_dev.c_str(), h_pw.c_str()};
-    const char* names[2] = {"kmc_device.hpp", "kmc_pointwise.hpp"};
+    for (int mode = 0; mode < 3; ++mode)
+        for (int packed = 0; packed < 2; ++packed)
+            src << head << "kmc_psis_walk" << mode << (packed ? "_packed" : "") << "(const kmc_pw::PsisArgs q) { kmc_pw::psis_walk" << t << ", " << mode << ", "
+                << (packed ? "true" : "false") << ">(q); }\n";
+    const char* headers[3] = {h_dev.c_str(), h_pw.c_str(), h_fit.c_str()};
+    const char* names[3] = {"kmc_device.hpp", "kmc_pointwise.hpp", "kmc_psis_fit.hpp"};
     const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
     std::vector<char> code;
     std::string log;
-    const kmc_status cst = rtc_compile_cached(src.str(), "kmc_pointwise.hip", 2, headers, names, 4, opts, &code, &log);
+    const kmc_status cst = rtc_compile_cached(src.str(), "kmc_pointwise.hip", 3, headers, names, 4, opts, &code, &log);
     if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "data density does not compile:\n" + log);
     if (cst != KMC_OK) return cst;
     auto ins = ud->code.emplace(key, std::move(code));
@@ -107,16 +115,22 @@ kmc_status load_pointwise(kmc_user_density* ud, int64_t ndim, bool own_data, PwK
     HIP_TRY(hipModuleGetFunction(&pk->pass[0][1], mod, "kmc_pw_pass1_packed"));
     HIP_TRY(hipModuleGetFunction(&pk->pass[1][1], mod, "kmc_pw_pass2_packed"));
     HIP_TRY(hipModuleGetFunction(&pk->matrix, mod, "kmc_pw_matrix"));
+    for (int mode = 0; mode < 3; ++mode)
+        for (int packed = 0; packed < 2; ++packed)
+            HIP_TRY(hipModuleGetFunction(&pk->psis[mode][packed], mod, ("kmc_psis_walk" + std::to_string(mode) + (packed ? "_packed" : "")).c_str()));
     return KMC_OK;
 }
 
 __global__ __launch_bounds__(256) void pw_fold(const PwArgs a, int pass) { pw_fold_body(a, pass); }
+__global__ __launch_bounds__(256) void psis_fold(const PsisArgs q, int stage) { psis_fold_body(q, stage); }
+__global__ __launch_bounds__(kmc_psis::kFitLanes) void psis_fit_kernel(const PsisArgs q, int sort_len) { psis_fit_body(q, sort_len); }
 
 // the device copies one call owns, beyond the chain's: the list of selected walkers, held-out observations, the work space
 struct PwBuffers : ChainUpload {
     int32_t* sel = nullptr;
     double *data = nullptr, *work = nullptr;
-    ~PwBuffers() { (void)hipFree(sel); (void)hipFree(data); (void)hipFree(work); }
+    void* work2 = nullptr;
+    ~PwBuffers() { (void)hipFree(sel); (void)hipFree(data); (void)hipFree(work); (void)hipFree(work2); }
 };
 
 // the events around the two passes, for info: each pass is its partial kernel and its fold
@@ -141,13 +155,67 @@ struct PwRequest {
     int32_t ncols2 = 0;
     bool matrix = false;
     int64_t obs_first = 0, obs_count = 0;
+    bool psis = false;                            // PSIS-LOO: over the observations [obs_first, obs_first + obs_count)
+    double r_eff = 1.0;
+    int64_t workspace = 0;                        // bytes of work space a block of observations may take; 0: kPsisWorkspace
 };
 
-// stats [4][J] (statistics), or out [n][obs_count] (matrix)
-kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result, int64_t* n_out, int64_t* info)
+constexpr int64_t kPsisWorkspace = (int64_t)1 << 30;
+
+// the refusals PSIS-LOO adds, from the sizes alone; M: the tail length
+kmc_status psis_check(int64_t n, double r_eff, int64_t* M)
 {
-    if (!q.ud || !q.ud->is_data) return fail(KMC_ERR_BAD_ARG, "the pointwise log-likelihood needs a data density (kmc_data_density_create): other densities have no per-observation term");
+    if (!(r_eff > 0.0) || !std::isfinite(r_eff)) return fail(KMC_ERR_BAD_ARG, "r_eff must be finite and > 0 (r_eff = " + std::to_string(r_eff) + ")");
+    if (n < kmc_psis::kMinFit) return fail(KMC_ERR_BAD_ARG, "PSIS-LOO needs at least 5 selected rows (n = " + std::to_string(n) + ")");
+    if (n >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "too many rows for one PSIS-LOO call: n = " + std::to_string(n) + ", the limit is 2^31");
+    const int64_t m = kmc_psis::tail_length(n, r_eff);
+    if (m > kmc_psis::kMaxTail)
+        return fail(KMC_ERR_UNSUPPORTED, "a tail of M = " + std::to_string(m) + " draws (n / r_eff = " + std::to_string((double)n / r_eff) + ") is longer than " +
+                                             std::to_string(kmc_psis::kMaxTail) + ", what one workgroup sorts: thin the chain");
+    if (M) *M = m;
+    return KMC_OK;
+}
+
+// how PSIS-LOO cuts J' observations of n rows into blocks: from n, the density's J, r_eff and the work-space budget alone
+struct PsisPlan {
+    int64_t M = 0, m_est = 0, block = 0, passes = 2 + kmc_psis::kSelectPasses;
+    size_t per_obs = 0;                           // bytes of work space of one observation
+    int sort_len = 1;
+};
+
+PsisPlan psis_plan(int64_t M, const PwPlan& pl, int64_t workspace)
+{
+    PsisPlan p;
+    p.M = M;
+    p.m_est = 30 + (int64_t)std::floor(std::sqrt((double)M));
+    while (p.sort_len < M) p.sort_len <<= 1;
+    p.per_obs = (size_t)M * 8 + (size_t)pl.nruns * (8 + 4 * kmc_psis::kSelectBins) + 8 * 8 + 8;
+    const int64_t budget = workspace > 0 ? workspace : kPsisWorkspace;
+    p.block = std::max<int64_t>(64, budget / (int64_t)p.per_obs / 64 * 64);
+    return p;
+}
+
+// one call's view of the chain, its stream, kernels and arguments.  (Members die in reverse order: the stream is drained before the
+// buffers go.)
+struct PwSession {
     ChainView v;
+    PwBuffers b;
+    ScopedStream ss;
+    PwKernels pk;
+    PwArgs a{};
+    PwPlan pl;
+    int64_t n = 0, J = 0;
+};
+
+// the refusals, then the chain, the stream, the module and the arguments every kernel shares
+kmc_status pw_open(const ChainSource& src, const PwRequest& q, const void* result, PwSession* S)
+{
+    ChainView& v = S->v;
+    PwBuffers& b = S->b;
+    ScopedStream& ss = S->ss;
+    PwKernels& pk = S->pk;
+    PwArgs& a = S->a;
+    if (!q.ud || !q.ud->is_data) return fail(KMC_ERR_BAD_ARG, "the pointwise log-likelihood needs a data density (kmc_data_density_create): other densities have no per-observation term");
     KMC_TRY(src.describe(&v));
     if (v.ndim > kDataMaxDim) return fail(KMC_ERR_BAD_ARG, "a data density takes at most " + std::to_string(kDataMaxDim) + " dimensions (ndim = " + std::to_string(v.ndim) + ")");
     if (q.thin < 1) return fail(KMC_ERR_BAD_ARG, "thin must be >= 1 (thin = " + std::to_string(q.thin) + ")");
@@ -158,6 +226,7 @@ kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result,
     const int64_t n = kept * nsel;
     if (n < 2) return fail(KMC_ERR_BAD_ARG, "the pointwise statistics need at least 2 selected rows (n = " + std::to_string(n) + ")");
     if (n >= ((int64_t)1 << 40)) return fail(KMC_ERR_UNSUPPORTED, "too many rows for one pointwise call: n = " + std::to_string(n) + ", the limit is 2^40");
+    if (q.psis) KMC_TRY(psis_check(n, q.r_eff, nullptr));
     int64_t J = q.ud->ndata;
     if (q.data) {
         if (q.ncols2 != q.ud->ncols)
@@ -165,7 +234,7 @@ kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result,
         if (q.ndata2 < 1 || q.ndata2 > kDataMaxRows) return fail(KMC_ERR_BAD_ARG, "held-out data: ndata must be in 1 .. 2^30 (ndata = " + std::to_string(q.ndata2) + ")");
         J = q.ndata2;
     }
-    if (q.matrix) {
+    if (q.matrix || q.psis) {
         if (q.obs_count < 1) return fail(KMC_ERR_BAD_ARG, "the matrix needs obs_count >= 1 (obs_count = " + std::to_string(q.obs_count) + ")");
         if (q.obs_first < 0 || q.obs_first > J - q.obs_count)
             return fail(KMC_ERR_BAD_ARG, "observations [" + std::to_string(q.obs_first) + ", " + std::to_string(q.obs_first) + " + " + std::to_string(q.obs_count) +
@@ -173,20 +242,17 @@ kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result,
     }
     if (v.is_float) return fail(KMC_ERR_UNSUPPORTED, "a chain of floats: data densities sample in double");
     if (!result || !q.params) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (n_out) *n_out = n;
-    const PwPlan pl = pw_plan(n, J);
+    S->n = n; S->J = J;
+    S->pl = pw_plan(n, J);
+    const PwPlan& pl = S->pl;
 
-    PwBuffers b;
     KMC_TRY(src.open(b, &v));
     // Never the legacy stream (kmc_host.hpp: copy_sync).  A sampler's own stream, which describe() has drained, serves: creating and
     // destroying a stream for the call costs 3.4 to 4.4 ms, several times the two passes at the README's small shape.
-    ScopedStream ss;
     if (src.host || !src.s->stream) HIP_TRY(ss.create());
     else ss.borrowed = src.s->stream;
-    PwKernels pk;
     KMC_TRY(load_pointwise(q.ud, v.ndim, !q.data, &pk));
 
-    PwArgs a{};
     a.chain = static_cast<const double*>(v.chain);
     a.n = n; a.J = J; a.nl = v.nl; a.ld = v.ld; a.nsel = nsel; a.first = q.first_sample; a.thin = q.thin;
     a.nd = (double)n; a.jp_log2 = pl.jp_log2;
@@ -207,6 +273,53 @@ kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result,
     } else {
         a.data = static_cast<const double*>(pk.keep_data.get());
     }
+    a.run_len = pl.run_len; a.nruns = pl.nruns;
+    return KMC_OK;
+}
+
+// the two passes of the statistics, left on the device: work gets the work space, a.stats [4][J]
+kmc_status pw_stats(PwSession& S, double** work, int64_t* info)
+{
+    PwArgs& a = S.a;
+    const PwPlan& pl = S.pl;
+    const int64_t n = S.n, J = S.J;
+    const size_t part = 2 * (size_t)pl.nruns * (size_t)J, doubles = part + 5 * (size_t)J;
+    KMC_TRY(check_device_room(doubles * sizeof(double), "the pointwise work space"));
+    HIP_TRY(hipMalloc((void**)work, doubles * sizeof(double)));
+    a.part = *work; a.stats = *work + part; a.centre = a.stats + 4 * (size_t)J;
+    a.run_len = pl.run_len; a.nruns = pl.nruns;
+    const unsigned gx = (unsigned)((J + 63) / 64), gy = (unsigned)((pl.nwaves + kPwWaves - 1) / kPwWaves), gf = (unsigned)((J + 255) / 256);
+    PassEvents ev;
+    if (info) HIP_TRY(ev.create());
+    for (int pass = 1; pass <= 2; ++pass) {
+        if (info) HIP_TRY(hipEventRecord(ev.e[pass - 1], S.ss.get()));
+        HIP_TRY(launch_module_y(S.pk.pass[pass - 1][pl.packed ? 1 : 0], gx, gy, kPwThreads, S.ss.get(), a));
+        hipLaunchKernelGGL(pw_fold, dim3(gf), dim3(256), 0, S.ss.get(), a, pass);
+        HIP_TRY(hipGetLastError());
+    }
+    if (info) {
+        HIP_TRY(hipEventRecord(ev.e[2], S.ss.get()));
+        HIP_TRY(hipStreamSynchronize(S.ss.get()));
+        float ms1 = 0.f, ms2 = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms1, ev.e[0], ev.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms2, ev.e[1], ev.e[2]));
+        info[0] = n; info[1] = pl.nruns; info[2] = 2 * n * J; info[3] = pl.run_len;
+        info[4] = (int64_t)((double)ms1 * 1e6); info[5] = (int64_t)((double)ms2 * 1e6);
+    }
+    return KMC_OK;
+}
+
+// stats [4][J] (statistics), or out [n][obs_count] (matrix)
+kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result, int64_t* n_out, int64_t* info)
+{
+    PwSession S;
+    KMC_TRY(pw_open(src, q, result, &S));
+    PwBuffers& b = S.b;
+    ScopedStream& ss = S.ss;
+    PwKernels& pk = S.pk;
+    PwArgs& a = S.a;
+    const int64_t n = S.n, J = S.J;
+    if (n_out) *n_out = n;
 
     if (q.matrix) {
         const double need = (double)n * (double)q.obs_count * 8.0;
@@ -227,29 +340,8 @@ kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result,
         return KMC_OK;
     }
 
-    const size_t part = 2 * (size_t)pl.nruns * (size_t)J, doubles = part + 5 * (size_t)J;
-    KMC_TRY(check_device_room(doubles * sizeof(double), "the pointwise work space"));
-    HIP_TRY(hipMalloc((void**)&b.work, doubles * sizeof(double)));
-    a.part = b.work; a.stats = b.work + part; a.centre = a.stats + 4 * (size_t)J;
-    a.run_len = pl.run_len; a.nruns = pl.nruns;
-    const unsigned gx = (unsigned)((J + 63) / 64), gy = (unsigned)((pl.nwaves + kPwWaves - 1) / kPwWaves), gf = (unsigned)((J + 255) / 256);
-    PassEvents ev;
-    if (info) HIP_TRY(ev.create());
-    for (int pass = 1; pass <= 2; ++pass) {
-        if (info) HIP_TRY(hipEventRecord(ev.e[pass - 1], ss.get()));
-        HIP_TRY(launch_module_y(pk.pass[pass - 1][pl.packed ? 1 : 0], gx, gy, kPwThreads, ss.get(), a));
-        hipLaunchKernelGGL(pw_fold, dim3(gf), dim3(256), 0, ss.get(), a, pass);
-        HIP_TRY(hipGetLastError());
-    }
-    if (info) HIP_TRY(hipEventRecord(ev.e[2], ss.get()));
+    KMC_TRY(pw_stats(S, &b.work, info));
     HIP_TRY(copy_sync(result, a.stats, 4 * (size_t)J * sizeof(double), hipMemcpyDeviceToHost, ss.get()));
-    if (info) {
-        float ms1 = 0.f, ms2 = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms1, ev.e[0], ev.e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms2, ev.e[1], ev.e[2]));
-        info[0] = n; info[1] = pl.nruns; info[2] = 2 * n * J; info[3] = pl.run_len;
-        info[4] = (int64_t)((double)ms1 * 1e6); info[5] = (int64_t)((double)ms2 * 1e6);
-    }
     return KMC_OK;
 }
 
@@ -364,5 +456,257 @@ KMC_EXPORT kmc_status kmc_waic_stats(int64_t J, int64_t n, const double* stats, 
     totals[4] = -2.0 * totals[2];
     totals[5] = (double)n_high;
     totals[6] = (double)n_nan;
+    return KMC_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// PSIS-LOO (include/kissmcmc_hip.h)
+// ---------------------------------------------------------------------------------------------------------------------------------
+namespace {
+
+struct PsisEvents {
+    hipEvent_t e[5] = {};
+    hipError_t create()
+    {
+        for (auto& x : e) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
+        return hipSuccess;
+    }
+    ~PsisEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// what one call hands back, each [obs_count] or nullptr
+struct PsisOut {
+    double* res = nullptr;        // [4][obs_count]: elpd_loo_j, pareto_k, n_tail_j, sigma_j
+    double* lppd_j = nullptr;     // the statistics' passes run only when this is asked for
+    double* tail = nullptr;       // [obs_count][M]
+    double *m = nullptr, *xc = nullptr;
+    int32_t* n_tail = nullptr;
+    int64_t* tail_len = nullptr;
+};
+
+kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, int64_t* n_out, int64_t* info)
+{
+    PwSession S;
+    KMC_TRY(pw_open(src, q, out.res ? (const void*)out.res : (const void*)out.tail, &S));
+    const int64_t n = S.n, J = S.J, count = q.obs_count;
+    if (n_out) *n_out = n;
+    int64_t M = 0;
+    KMC_TRY(psis_check(n, q.r_eff, &M));
+    if (out.tail) {
+        if (!out.tail_len) return fail(KMC_ERR_BAD_ARG, "null argument");
+        if (*out.tail_len < M)
+            return fail(KMC_ERR_BAD_ARG, "the tail array has " + std::to_string(*out.tail_len) + " columns, the tail length is " + std::to_string(M));
+        *out.tail_len = M;
+    }
+    const PwPlan& pl = S.pl;
+    const PsisPlan pp = psis_plan(M, pl, q.workspace);
+    const int64_t block = std::min(pp.block, pl.packed ? (int64_t)64 : count);
+    hipStream_t st = S.ss.get();
+    int64_t ns_stats = 0;
+
+    if (out.lppd_j) {
+        int64_t sinfo[6] = {};
+        KMC_TRY(pw_stats(S, &S.b.work, info ? sinfo : nullptr));
+        std::vector<double> stats(4 * (size_t)J), lp((size_t)J), totals(7);
+        HIP_TRY(copy_sync(stats.data(), S.a.stats, stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        KMC_TRY(kmc_waic_stats(J, n, stats.data(), lp.data(), nullptr, nullptr, totals.data()));
+        std::copy(lp.begin() + q.obs_first, lp.begin() + q.obs_first + count, out.lppd_j);
+        ns_stats = sinfo[4] + sinfo[5];
+    }
+
+    // the work space of one block, carved in order of alignment
+    const size_t B = (size_t)block, R = (size_t)pl.nruns;
+    const size_t bytes = B * (size_t)M * 8 + R * B * 8 + B * 8 * 4 + B * 32 + R * B * kmc_psis::kSelectBins * 4 + B * 4;
+    KMC_TRY(check_device_room(bytes, "the PSIS-LOO work space"));
+    HIP_TRY(hipMalloc(&S.b.work2, bytes));
+    PsisArgs qa{};
+    qa.a = S.a;
+    qa.M = (int32_t)M;
+    {
+        char* p = static_cast<char*>(S.b.work2);
+        qa.tail = reinterpret_cast<double*>(p); p += B * (size_t)M * 8;
+        qa.runval = reinterpret_cast<double*>(p); p += R * B * 8;
+        qa.m = reinterpret_cast<double*>(p); p += B * 8;
+        qa.xc = reinterpret_cast<double*>(p); p += B * 8;
+        qa.prefix = reinterpret_cast<uint64_t*>(p); p += B * 8;
+        qa.rank = reinterpret_cast<int64_t*>(p); p += B * 8;
+        qa.res = reinterpret_cast<double*>(p); p += B * 32;
+        qa.counts = reinterpret_cast<uint32_t*>(p); p += R * B * kmc_psis::kSelectBins * 4;
+        qa.cursor = reinterpret_cast<int32_t*>(p);
+    }
+    PsisEvents ev;
+    if (info) HIP_TRY(ev.create());
+    double ms[4] = {};
+    std::vector<double> res_host(4 * B);
+    const unsigned gy = (unsigned)((pl.nwaves + kPwWaves - 1) / kPwWaves);
+    const int pk = pl.packed ? 1 : 0;
+    int64_t nblocks = 0, log1ps = 0;
+    for (int64_t b0 = 0; b0 < count; b0 += block, ++nblocks) {
+        const int64_t bc = std::min(block, count - b0);
+        qa.a.obs_first = q.obs_first + b0;
+        qa.a.obs_count = bc;
+        const unsigned gx = pl.packed ? 1u : (unsigned)((bc + 63) / 64), gf = (unsigned)((bc + 255) / 256);
+        if (info) HIP_TRY(hipEventRecord(ev.e[0], st));
+        HIP_TRY(launch_module_y(S.pk.psis[0][pk], gx, gy, kPwThreads, st, qa));
+        hipLaunchKernelGGL(psis_fold, dim3(gf), dim3(256), 0, st, qa, 0);
+        HIP_TRY(hipGetLastError());
+        if (info) HIP_TRY(hipEventRecord(ev.e[1], st));
+        for (int pass = 0; pass < kmc_psis::kSelectPasses; ++pass) {
+            qa.shift = 64 - kmc_psis::kSelectBits * (pass + 1);
+            HIP_TRY(launch_module_y(S.pk.psis[1][pk], gx, gy, kPwThreads, st, qa));
+            hipLaunchKernelGGL(psis_fold, dim3(gf), dim3(256), 0, st, qa, 1);
+            HIP_TRY(hipGetLastError());
+        }
+        if (info) HIP_TRY(hipEventRecord(ev.e[2], st));
+        HIP_TRY(launch_module_y(S.pk.psis[2][pk], gx, gy, kPwThreads, st, qa));
+        if (info) HIP_TRY(hipEventRecord(ev.e[3], st));
+        hipLaunchKernelGGL(psis_fit_kernel, dim3((unsigned)bc), dim3(kmc_psis::kFitLanes), 0, st, qa, pp.sort_len);
+        HIP_TRY(hipGetLastError());
+        if (info) HIP_TRY(hipEventRecord(ev.e[4], st));
+        HIP_TRY(copy_sync(res_host.data(), qa.res, 4 * (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, st));
+        for (int64_t c = 0; c < bc; ++c) {
+            const double nt = res_host[2 * (size_t)bc + (size_t)c];
+            if (out.res) for (int k = 0; k < 4; ++k) out.res[k * count + b0 + c] = res_host[(size_t)k * (size_t)bc + (size_t)c];
+            if (out.n_tail) out.n_tail[b0 + c] = nt == nt ? (int32_t)nt : -1;
+            if (nt >= kmc_psis::kMinFit) log1ps += (int64_t)nt * (31 + (int64_t)std::floor(std::sqrt(nt)));
+        }
+        if (out.tail) HIP_TRY(copy_sync(out.tail + b0 * M, qa.tail, (size_t)bc * (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (out.m) HIP_TRY(copy_sync(out.m + b0, qa.m, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (out.xc) HIP_TRY(copy_sync(out.xc + b0, qa.xc, (size_t)bc * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (info)
+            for (int k = 0; k < 4; ++k) {
+                float t = 0.f;
+                HIP_TRY(hipEventElapsedTime(&t, ev.e[k], ev.e[k + 1]));
+                ms[k] += (double)t;
+            }
+    }
+    if (info) {
+        info[0] = n; info[1] = M; info[2] = nblocks; info[3] = block;
+        for (int k = 0; k < 4; ++k) info[4 + k] = (int64_t)(ms[k] * 1e6);
+        info[8] = n * count; info[9] = log1ps; info[10] = ns_stats; info[11] = pl.nruns;
+    }
+    return KMC_OK;
+}
+
+PwRequest psis_request(int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first, int64_t obs_count, int64_t workspace)
+{
+    PwRequest q;
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask;
+    q.psis = true; q.r_eff = r_eff; q.obs_first = obs_first; q.obs_count = obs_count; q.workspace = workspace;
+    return q;
+}
+
+}  // namespace
+
+KMC_EXPORT kmc_status kmc_sampler_psis_loo(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first,
+                                           int64_t obs_count, int64_t workspace_bytes, double* stats, double* lppd_j, int64_t* n_out, int64_t* info)
+{
+    PwRequest q = psis_request(first_sample, walker_mask, thin, r_eff, obs_first, obs_count, workspace_bytes);
+    KMC_TRY(sampler_density(s, &q));
+    if (!lppd_j) return fail(KMC_ERR_BAD_ARG, "null argument");
+    PsisOut out;
+    out.res = stats; out.lppd_j = lppd_j;
+    return psis(ChainSource(s, false, "kmc_chain_psis_loo"), q, out, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_chain_psis_loo(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples, int64_t nwalkers,
+                                         int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first,
+                                         int64_t obs_count, int64_t workspace_bytes, int device, double* stats, double* lppd_j, int64_t* n_out, int64_t* info)
+{
+    PwRequest q = psis_request(first_sample, walker_mask, thin, r_eff, obs_first, obs_count, workspace_bytes);
+    q.ud = density; q.params = params;
+    if (!lppd_j) return fail(KMC_ERR_BAD_ARG, "null argument");
+    PsisOut out;
+    out.res = stats; out.lppd_j = lppd_j;
+    return psis(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, out, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_psis_tail(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first,
+                                            int64_t obs_count, int64_t workspace_bytes, double* tail, double* m_j, double* xc_j, int32_t* n_tail_j,
+                                            int64_t* tail_len, int64_t* n_out)
+{
+    PwRequest q = psis_request(first_sample, walker_mask, thin, r_eff, obs_first, obs_count, workspace_bytes);
+    KMC_TRY(sampler_density(s, &q));
+    PsisOut out;
+    out.tail = tail; out.m = m_j; out.xc = xc_j; out.n_tail = n_tail_j; out.tail_len = tail_len;
+    return psis(ChainSource(s, false, "kmc_chain_psis_tail"), q, out, n_out, nullptr);
+}
+
+KMC_EXPORT kmc_status kmc_chain_psis_tail(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples, int64_t nwalkers,
+                                          int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, double r_eff, int64_t obs_first,
+                                          int64_t obs_count, int64_t workspace_bytes, int device, double* tail, double* m_j, double* xc_j,
+                                          int32_t* n_tail_j, int64_t* tail_len, int64_t* n_out)
+{
+    PwRequest q = psis_request(first_sample, walker_mask, thin, r_eff, obs_first, obs_count, workspace_bytes);
+    q.ud = density; q.params = params;
+    PsisOut out;
+    out.tail = tail; out.m = m_j; out.xc = xc_j; out.n_tail = n_tail_j; out.tail_len = tail_len;
+    return psis(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, out, n_out, nullptr);
+}
+
+// The cut of a PSIS-LOO call; touches no device.
+KMC_EXPORT kmc_status kmc_psis_plan(int64_t n, int64_t ndata, double r_eff, int64_t workspace_bytes, int64_t* tail_len, int64_t* m_est,
+                                    int64_t* obs_per_block, int64_t* passes)
+{
+    if (ndata < 1 || ndata > kDataMaxRows) return fail(KMC_ERR_BAD_ARG, "ndata must be in 1 .. 2^30 (ndata = " + std::to_string(ndata) + ")");
+    if (workspace_bytes < 0) return fail(KMC_ERR_BAD_ARG, "workspace_bytes must be >= 0 (workspace_bytes = " + std::to_string(workspace_bytes) + ")");
+    int64_t M = 0;
+    KMC_TRY(psis_check(n, r_eff, &M));
+    const PsisPlan p = psis_plan(M, pw_plan(n, ndata), workspace_bytes);
+    if (tail_len) *tail_len = p.M;
+    if (m_est) *m_est = p.m_est;
+    if (obs_per_block) *obs_per_block = p.block;
+    if (passes) *passes = p.passes;
+    return KMC_OK;
+}
+
+// The host stage, in the operation order of include/kissmcmc_hip.h.  stats [4][J]: elpd_loo_j, pareto_k, n_tail_j, sigma_j.
+// totals: elpd_loo, se, p_loo, looic, lppd, n_nan, k_counts[4].
+KMC_EXPORT kmc_status kmc_loo_stats(int64_t J, int64_t n, const double* stats, const double* lppd_j, double* p_loo_j, double* totals)
+{
+    if (J < 1) return fail(KMC_ERR_BAD_ARG, "need J >= 1 (J = " + std::to_string(J) + ")");
+    if (n < kmc_psis::kMinFit) return fail(KMC_ERR_BAD_ARG, "need n >= 5 (n = " + std::to_string(n) + ")");
+    if (!stats || !lppd_j || !totals) return fail(KMC_ERR_BAD_ARG, "null argument");
+    const double *el = stats, *kh = stats + J;
+    const double dJ = (double)J;
+    std::vector<double> pl((size_t)J), t((size_t)J);
+    int64_t n_nan = 0, kc[4] = {};
+    for (int64_t j = 0; j < J; ++j) {
+        pl[(size_t)j] = lppd_j[j] - el[j];
+        n_nan += std::isnan(el[j]);
+        if (kh[j] <= 0.5) ++kc[0];
+        else if (kh[j] <= 0.7) ++kc[1];
+        else if (kh[j] <= 1.0) ++kc[2];
+        else if (kh[j] > 1.0) ++kc[3];
+    }
+    if (p_loo_j) std::copy(pl.begin(), pl.end(), p_loo_j);
+    t.assign(el, el + J); totals[0] = pairwise_tree(t);
+    const double centre = totals[0] / dJ;
+    for (int64_t j = 0; j < J; ++j) { const double dv = el[j] - centre; t[(size_t)j] = dv * dv; }
+    totals[1] = std::sqrt(dJ * pairwise_tree(t) / (double)(J - 1));
+    t = pl; totals[2] = pairwise_tree(t);
+    totals[3] = -2.0 * totals[0];
+    t.assign(lppd_j, lppd_j + J); totals[4] = pairwise_tree(t);
+    totals[5] = (double)n_nan;
+    for (int k = 0; k < 4; ++k) totals[6 + k] = (double)kc[k];
+    return KMC_OK;
+}
+
+// Steps 3 and 4 for one observation on the host, with the arithmetic and the summation order of the device's fit kernel
+// (kmc_psis_fit.hpp).  x: the tail ascending, [nt]; s: [nt] out.  sums: sum exp(s_i), sum exp(s_i - x_(i)).
+KMC_EXPORT kmc_status kmc_psis_smooth_host(int64_t nt, const double* x, double xc, double* k_hat, double* sigma, double* s, double* sums)
+{
+    if (nt < 0 || nt > kmc_psis::kMaxTail) return fail(KMC_ERR_BAD_ARG, "the tail must hold 0 .. 4096 draws (nt = " + std::to_string(nt) + ")");
+    if (nt > 0 && (!x || !s)) return fail(KMC_ERR_BAD_ARG, "null argument");
+    for (int64_t i = 0; i < nt; ++i)
+        if (!(x[i] > xc) || x[i] > 0.0 || (i > 0 && x[i] < x[i - 1]))
+            return fail(KMC_ERR_BAD_ARG, "the tail must be ascending, above the cut-off and <= 0 (x[" + std::to_string(i) + "] = " + std::to_string(x[i]) + ")");
+    double grid[3][kmc_psis::kMaxGrid];
+    kmc_psis::HostCtx ctx;
+    const kmc_psis::FitScratch sc{grid[0], grid[1], grid[2]};
+    const kmc_psis::FitResult r = kmc_psis::psis_fit(ctx, x, s, (int)nt, xc, sc);
+    if (k_hat) *k_hat = r.k;
+    if (sigma) *sigma = r.sigma;
+    if (sums) { sums[0] = r.w_tail; sums[1] = r.n_tail; }
     return KMC_OK;
 }

@@ -16,8 +16,10 @@
 //                        observation l % Jp of the run slot l / Jp, and loads its rows itself.  Grid (1, ceil(nruns / (slots kPwWaves))).
 //   pw_fold_body      -- one observation per thread: the runs' partials in run order; pass 1 also writes S1 / n for pass 2.
 //   pw_matrix         -- l[r][j] for the selected rows and the observations [obs_first, obs_first + obs_count): [n][obs_count], dense.
+//   psis_walk, psis_fold_body, psis_fit_body -- PSIS-LOO over the same walk: below, with their own contract.
 #pragma once
 #include "kmc_device.hpp"
+#include "kmc_psis_fit.hpp"
 
 namespace kmc_pw {
 
@@ -154,6 +156,224 @@ __device__ __forceinline__ void pw_matrix(const PwArgs& a)
         const double t = F::term(x, ND, d, a.p);
         if (live) a.out[k * a.obs_count + col] = t;
         cur.next(a);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// PSIS-LOO (include/kissmcmc_hip.h).  The terms are recomputed in every pass, by the walk of pw_partials over
+// the runs of the same plan; a block of observations [obs_first, obs_first + obs_count) is in work at a time, and every buffer below
+// is indexed by the column col = j - obs_first.  With y = l - m_j >= 0 (the negated shifted log ratio x = m_j - l) the bits of y order
+// as unsigned integers, so the cut-off -- the (M + 1)-th largest x -- is the y of ascending rank M, found digit by digit.
+//   psis_walk<MODE = 0>  the run's minimum of l (a NaN stays)
+//   psis_walk<MODE = 1>  the run's count of each value of the current digit among the keys that agree with the digits found so far;
+//                        a lane counts its own observation in its own column of LDS
+//   psis_walk<MODE = 2>  x > xc_j goes to the tail through the observation's integer cursor; the others' exp(x) are summed in row order
+//   psis_fold_body       one column per thread: the runs' minima / counts in run order; the last digit also gives xc_j
+//   psis_fit_kernel      one workgroup per column: bitonic sort of the tail in LDS, then kmc_psis_fit.hpp
+struct PsisArgs {
+    PwArgs    a;            // obs_first / obs_count: the block in work
+    double*   runval;       // [nruns][obs_count]: the runs' minima (MODE 0), then their sums outside the tail (MODE 2)
+    uint32_t* counts;       // [nruns][obs_count][kSelectBins]
+    double*   m;            // [obs_count]: the shift; NaN for an observation whose outputs are NaN
+    uint64_t* prefix;       // [obs_count]: the digits of the cut-off's key found so far
+    int64_t*  rank;         // [obs_count]: the rank still looked for among the keys that agree with prefix
+    double*   xc;           // [obs_count]
+    int32_t*  cursor;       // [obs_count]: entries x > xc_j met so far
+    double*   tail;         // [obs_count][M]: unordered after MODE 2, ascending and padded with NaN after the fit
+    double*   res;          // [4][obs_count]: elpd_loo_j, pareto_k, n_tail_j, sigma
+    int32_t   M;
+    int32_t   shift;        // of the current digit
+};
+
+// the lane's observation, run and column
+template <bool PACKED>
+struct PsisLane {
+    int64_t j, run, col;
+    bool live;
+    __device__ __forceinline__ PsisLane(const PwArgs& a)
+    {
+        const int lane = (int)(threadIdx.x & 63);
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const int64_t wid = (int64_t)blockIdx.y * kPwWaves + wave;
+        if constexpr (PACKED) {
+            j = lane & ((1 << a.jp_log2) - 1);
+            run = (wid << (6 - a.jp_log2)) + (lane >> a.jp_log2);
+        } else {
+            j = a.obs_first + (int64_t)blockIdx.x * 64 + lane;
+            run = wid;
+        }
+        col = j - a.obs_first;
+        live = col >= 0 && col < a.obs_count && run < a.nruns;
+        if (!live) { j = a.obs_first; col = 0; }                                       // (idle lanes hold a real observation, write nothing)
+    }
+};
+
+template <class F, int ND, int NCOLS, int MODE, bool PACKED>
+__device__ __forceinline__ void psis_walk(const PsisArgs& q)
+{
+    const PwArgs& a = q.a;
+    const PsisLane<PACKED> ln(a);
+    const int64_t j = ln.j, run = ln.run, col = ln.col;
+    double d[NCOLS];
+#pragma unroll
+    for (int c = 0; c < NCOLS; ++c) d[c] = a.data[j * NCOLS + c];
+    int64_t k0 = run * a.run_len, k1 = k0 + a.run_len < a.n ? k0 + a.run_len : a.n;
+    if (run >= a.nruns) k0 = k1 = 0;
+    __shared__ uint32_t cnt[MODE == 1 ? kmc_psis::kSelectBins : 1][kPwThreads];
+    double m = 0.0, xc = 0.0, acc = MODE == 0 ? INFINITY : 0.0;
+    uint64_t hi = 0;
+    const int shift = q.shift;
+    if constexpr (MODE >= 1) m = q.m[col];
+    if constexpr (MODE == 1) {
+        hi = shift + kmc_psis::kSelectBits < 64 ? q.prefix[col] >> (shift + kmc_psis::kSelectBits) : 0;
+#pragma unroll
+        for (int b = 0; b < kmc_psis::kSelectBins; ++b) cnt[b][threadIdx.x] = 0;
+    }
+    if constexpr (MODE == 2) xc = q.xc[col];
+    RowCursor cur(a, k0);
+    for (int64_t k = k0; k < k1; ++k) {
+        const double* __restrict__ row = cur.row(a);
+        double x[ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) x[i] = row[i];
+        const double t = F::term(x, ND, d, a.p);
+        if constexpr (MODE == 0) {
+            acc = (t < acc || t != t) ? t : acc;
+        } else if constexpr (MODE == 1) {
+            const uint64_t key = (uint64_t)__double_as_longlong(t - m);
+            const uint64_t top = shift + kmc_psis::kSelectBits < 64 ? key >> (shift + kmc_psis::kSelectBits) : 0;
+            if (top == hi) cnt[(key >> shift) & (kmc_psis::kSelectBins - 1)][threadIdx.x] += 1;
+        } else {
+            const double xr = m - t;
+            if (xr > xc) {
+                if (ln.live) {
+                    const int32_t at = atomicAdd(&q.cursor[col], 1);
+                    if (at < q.M) q.tail[col * q.M + at] = xr;
+                }
+            } else {
+                acc += exp(xr);
+            }
+        }
+        cur.next(a);
+    }
+    if (!ln.live) return;
+    if constexpr (MODE == 1) {
+#pragma unroll
+        for (int b = 0; b < kmc_psis::kSelectBins; ++b) q.counts[(run * a.obs_count + col) * kmc_psis::kSelectBins + b] = cnt[b][threadIdx.x];
+    } else {
+        q.runval[run * a.obs_count + col] = acc;
+    }
+}
+
+// one column per thread; grid ceil(obs_count / 256).  stage 0: after MODE 0; stage 1: after a MODE 1 pass
+__device__ __forceinline__ void psis_fold_body(const PsisArgs& q, int stage)
+{
+    const PwArgs& a = q.a;
+    const int64_t col = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= a.obs_count) return;
+    if (stage == 0) {
+        double acc = INFINITY;
+        for (int64_t r = 0; r < a.nruns; ++r) {
+            const double p = q.runval[r * a.obs_count + col];
+            acc = (p < acc || p != p) ? p : acc;
+        }
+        q.m[col] = acc - acc == 0.0 ? acc : __builtin_nan("");                     // (NaN among the terms, or no finite minimum)
+        q.prefix[col] = 0;
+        q.rank[col] = q.M;
+        q.cursor[col] = 0;
+        return;
+    }
+    int64_t left = q.rank[col], below = 0;
+    int digit = kmc_psis::kSelectBins - 1;
+    bool found = false;
+    for (int b = 0; b < kmc_psis::kSelectBins; ++b) {
+        int64_t c = 0;
+        for (int64_t r = 0; r < a.nruns; ++r) c += q.counts[(r * a.obs_count + col) * kmc_psis::kSelectBins + b];
+        if (!found && left < below + c) { digit = b; found = true; left -= below; }
+        if (!found) below += c;
+    }
+    const uint64_t prefix = q.prefix[col] | ((uint64_t)digit << q.shift);
+    q.prefix[col] = prefix;
+    q.rank[col] = found ? left : 0;
+    if (q.shift == 0) {
+        const double y = __longlong_as_double((long long)prefix);
+        const double xr = y == 0.0 ? 0.0 : -y;
+        const double m = q.m[col];
+        q.xc[col] = m != m ? m : (xr > kmc_psis::kLogDblMin ? xr : kmc_psis::kLogDblMin);
+    }
+}
+
+// the device's context of kmc_psis_fit.hpp
+struct PsisDeviceCtx {
+    double* red;            // [kFitLanes] in LDS
+    template <class Fn> __device__ __forceinline__ void par(int count, Fn f)
+    {
+        for (int t = (int)threadIdx.x; t < count; t += kmc_psis::kFitLanes) f(t);
+        __syncthreads();
+    }
+    template <class Fn> __device__ __forceinline__ double sum(int count, Fn f)
+    {
+        double acc = 0.0;
+        for (int t = (int)threadIdx.x; t < count; t += kmc_psis::kFitLanes) acc += f(t);
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        for (int h = kmc_psis::kFitLanes / 2; h > 0; h >>= 1) {
+            if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+            __syncthreads();
+        }
+        const double r = red[0];
+        __syncthreads();
+        return r;
+    }
+    __device__ __forceinline__ void set(double* arr, int i, double v) { if (threadIdx.x == 0) arr[i] = v; }
+    __device__ __forceinline__ void sync() { __syncthreads(); }
+};
+
+// one workgroup of kFitLanes threads per column; grid obs_count.  sort_len: the power of two >= M (at most kMaxTail)
+__device__ __forceinline__ void psis_fit_body(const PsisArgs& q, int sort_len)
+{
+    using namespace kmc_psis;
+    const PwArgs& a = q.a;
+    const int64_t col = blockIdx.x;
+    const int tid = (int)threadIdx.x;
+    __shared__ double xs[kMaxTail];
+    __shared__ double red[kFitLanes];
+    __shared__ double grid[3][kMaxGrid];
+    double* tail = q.tail + col * q.M;
+    const double m = q.m[col];
+    if (m != m) {
+        for (int t = tid; t < q.M; t += kFitLanes) tail[t] = m;
+        if (tid < 4) q.res[tid * a.obs_count + col] = m;
+        return;
+    }
+    int nt = q.cursor[col];
+    nt = nt < q.M ? nt : q.M;
+    for (int t = tid; t < sort_len; t += kFitLanes) xs[t] = t < nt ? tail[t] : INFINITY;
+    __syncthreads();
+    for (int size = 2; size <= sort_len; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < sort_len; t += kFitLanes) {
+                const int u = t ^ stride;
+                if (u > t) {
+                    const double p = xs[t], r = xs[u];
+                    const bool up = (t & size) == 0;
+                    if ((p > r) == up) { xs[t] = r; xs[u] = p; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int t = tid; t < q.M; t += kFitLanes) tail[t] = t < nt ? xs[t] : __builtin_nan("");   // (thread t % kFitLanes reads tail[t] back below)
+    __syncthreads();
+    double nontail = 0.0;
+    for (int64_t r = 0; r < a.nruns; ++r) nontail += q.runval[r * a.obs_count + col];
+    PsisDeviceCtx ctx{red};
+    const FitScratch sc{grid[0], grid[1], grid[2]};
+    const FitResult fr = psis_fit(ctx, tail, xs, nt, q.xc[col], sc);
+    if (tid == 0) {
+        q.res[col] = psis_elpd(m, nontail, a.n, nt, fr);
+        q.res[a.obs_count + col] = fr.k;
+        q.res[2 * a.obs_count + col] = (double)nt;
+        q.res[3 * a.obs_count + col] = fr.sigma;
     }
 }
 

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, waic, pointwise_loglike, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, waic, pointwise_loglike, loo, compare_loo, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -834,6 +834,50 @@ function pointwise_loglike(pdf::DataDensity, thetas; first_sample=0, thin=1, wal
                D === nothing ? C_NULL : D, nd2, Int32(nc2), first, stop - first, Cint(device), out, n)
     st == 0 || error("kmc_chain_pointwise_loglike failed ($st): $(last_error())")
     return out
+end
+
+"""
+    loo(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, r_eff=1.0, obs=nothing, workspace=0, device=0)
+
+PSIS-LOO of the data density `pdf` over the posterior sample `thetas[walker][sample]`: the rows are those of `waic` (at least 5), the
+observations `obs = (first, count)`, 0-based (all by default).  Selected, fitted and smoothed on the GPU (`kmc_chain_psis_loo`), the host
+stage is `kmc_loo_stats`; the definition is in include/kissmcmc_hip.h.  Returns a named tuple `(elpd_loo, se, p_loo, looic, lppd, n_nan,
+k_counts, n, elpd_loo_j, p_loo_j, pareto_k, n_tail_j, lppd_j)`; `k_counts` counts `pareto_k <= 0.5`, `(0.5, 0.7]`, `(0.7, 1]` and `> 1`;
+`n_tail_j` is -1 for an observation whose outputs are NaN.  `r_eff` is one number.
+"""
+function loo(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, r_eff=1.0, obs=nothing, workspace=0, device=0)
+    chain, _, ns, nw, nd = _summary_chain(thetas, nothing)
+    mask = _summary_mask(walkers, nw)
+    first, count = obs === nothing ? (0, pdf.ndata) : obs
+    stats = Matrix{Float64}(undef, max(count, 1), 4)      # column-major [count, 4] is the C ABI's [4][count]
+    lppd_j = Vector{Float64}(undef, max(count, 1))
+    n = Ref{Int64}(0)
+    st = ccall((:kmc_chain_psis_loo, LIB), Cint,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Float64, Int64, Int64, Int64, Cint,
+                Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+               pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin, Float64(r_eff),
+               first, count, workspace, Cint(device), stats, lppd_j, n, C_NULL)
+    st == 0 || error("kmc_chain_psis_loo failed ($st): $(last_error())")
+    p_loo_j = similar(lppd_j); tot = Vector{Float64}(undef, 10)
+    st = ccall((:kmc_loo_stats, LIB), Cint, (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+               count, n[], stats, lppd_j, p_loo_j, tot)
+    st == 0 || error("kmc_loo_stats failed ($st): $(last_error())")
+    return (elpd_loo=tot[1], se=tot[2], p_loo=tot[3], looic=tot[4], lppd=tot[5], n_nan=Int(tot[6]), k_counts=Tuple(Int.(tot[7:10])), n=n[],
+            elpd_loo_j=stats[:, 1], p_loo_j=p_loo_j, pareto_k=stats[:, 2], n_tail_j=[isnan(v) ? -1 : Int(v) for v in stats[:, 3]], lppd_j=lppd_j)
+end
+
+"""
+    compare_loo(a, b)
+
+The difference of two models' `elpd_loo` over the same observations, from two `loo` results: `(elpd_diff, se, J)` with
+`se = sqrt(J var(elpd_loo_j(a) - elpd_loo_j(b)))` (sample variance); positive `elpd_diff`: `a` predicts better.  No device.
+"""
+function compare_loo(a, b)
+    length(a.elpd_loo_j) == length(b.elpd_loo_j) || error("the two results are not over the same observations")
+    d = a.elpd_loo_j .- b.elpd_loo_j
+    J = length(d)
+    m = sum(d) / J
+    return (elpd_diff=sum(d), se=J > 1 ? sqrt(J * sum((d .- m) .^ 2) / (J - 1)) : NaN, J=J)
 end
 
 """

@@ -83,3 +83,22 @@ end
     b = emcee(GaussianIso(-5.0, 3.0), theta0s; niter=10^4, use_progress_meter=false, seed=UInt64(7))
     @test a[1] == b[1] && a[2] == b[2]
 end
+
+@testset "PSIS-LOO of a data density" begin
+    # 200 observations y ~ N(mu, 1/4), flat prior: elpd_loo is closed form, and WAIC agrees with it within the standard error
+    # (a fixed, roughly bell-shaped sample; p[1] = 0.5 log(4 / (2 pi)))
+    y = [0.5 + 0.5 * ((j % 7) / 7 + (j % 13) / 13 + (j % 17) / 17 + (j % 23) / 23 - 2.0) for j in 1:200]
+    pdf = DataDensity("double r = d[0] - x[0]; return -0.5 * p[0] * r * r + p[1];", y; params=[4.0, -0.2257913526447274])
+    thetas, _, _ = emcee(pdf, make_theta0s(mean(y), 0.05, pdf, 64); niter=64 * 1200, nburnin=64 * 200, use_progress_meter=false)
+    w = loo(pdf, thetas)
+    others = (200 * mean(y) .- y) ./ 199
+    v = 0.25 * 200 / 199                                     # 0.5 log(2 pi v) = 0.22829762355649952
+    exact = 200 * mean(@. -0.5 * (y - others)^2 / v - 0.22829762355649952)
+    @test w.n_nan == 0 && length(w.pareto_k) == 200 && all(w.pareto_k .< 0.5) && w.k_counts == (200, 0, 0, 0)
+    @test abs(w.elpd_loo - exact) < 0.2 && w.looic == -2 * w.elpd_loo
+    @test abs(w.elpd_loo - waic(pdf, thetas).elpd_waic) < w.se
+    part = loo(pdf, thetas; obs=(17, 40))
+    @test part.elpd_loo_j == w.elpd_loo_j[18:57]
+    d = compare_loo(w, w)
+    @test d.elpd_diff == 0.0 && d.J == 200
+end

@@ -586,6 +586,20 @@ class Sampler:
         from .chain_predictive import sampler_waic
         return sampler_waic(self, first_sample, thin, walkers, data)
 
+    def loo(self, first_sample: int = 0, thin: int = 1, walkers=None, r_eff: float = 1.0, obs=None, workspace=None, with_info: bool = False):
+        """PSIS-LOO of the sampler's :class:`DataDensity` over the stored chain -- the samples ``first_sample, first_sample + thin, ...`` of
+        the walkers ``walkers`` -- smoothed on the device (``kmc_sampler_psis_loo``): a dict ``elpd_loo, se, p_loo, looic, lppd, n, tail_len,
+        n_nan, k_counts`` and the arrays ``elpd_loo_j, p_loo_j, pareto_k, n_tail_j, lppd_j``; ``obs = (first, count)`` restricts the
+        observations.  See :func:`kissmcmc_jl_amd.loo`."""
+        from .chain_loo import sampler_loo
+        return sampler_loo(self, first_sample, thin, walkers, r_eff, obs, workspace, with_info)
+
+    def psis_tail(self, first_sample: int = 0, thin: int = 1, walkers=None, r_eff: float = 1.0, obs=None, workspace=None):
+        """The shift, the cut-off and the sorted tail of every observation, as :meth:`loo` selects them (``kmc_sampler_psis_tail``); see
+        :func:`kissmcmc_jl_amd.psis_tail`."""
+        from .chain_loo import sampler_psis_tail
+        return sampler_psis_tail(self, first_sample, thin, walkers, r_eff, obs, workspace)
+
     def pointwise_loglike(self, first_sample: int = 0, thin: int = 1, walkers=None, obs=None, data=None):
         """The matrix ``l[r, j] = term(x_r, d_j)`` of the selected rows of the stored chain and the observations ``obs = (first, stop)``
         (default: all), ``[n, stop - first]`` (``kmc_sampler_pointwise_loglike``); see :func:`kissmcmc_jl_amd.pointwise_loglike`."""
