@@ -33,31 +33,18 @@ constexpr int64_t kTargetGroups = 2048;
 
 kmc_status compile_data(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
 {
-    const std::string key = "data:" + std::to_string(ndim);
-    std::lock_guard<std::mutex> lock(ud->mu);
-    auto it = ud->code.find(key);
-    if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
-    const std::string dir = user_header_dir();
-    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_data = read_file(dir + "/kmc_data.hpp");
-    if (h_dev.empty() || h_data.empty()) return fail(KMC_ERR_BAD_ARG, "data density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
-    const std::string nd = std::to_string(ndim), nc = std::to_string(ud->ncols);
-    std::ostringstream src;
-    src << "#include \"kmc_data.hpp\"\n" << data_functor_source(ud)
-        << "extern \"C\" __global__ __launch_bounds__(" << kDataTPB << ") void kmc_data_lane(const kmc_data::DataArgs a) { kmc_data::data_partial_lane_body<UserData, " << nd << ", " << nc << ">(a); }\n"
-        << "extern \"C\" __global__ __launch_bounds__(" << kDataTPB << ") void kmc_data_obs(const kmc_data::DataArgs a) { kmc_data::data_partial_obs_body<UserData, " << nd << ", " << nc << ">(a); }\n"
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold(const kmc_data::DataArgs a) { kmc_data::data_fold_body<UserData, " << nd << ">(a); }\n"
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold_split(const kmc_data::DataArgs a) { kmc_data::data_fold_split_body<UserData, " << nd << ">(a); }\n";
-    const char* headers[2] = {h_dev.c_str(), h_data.c_str()};
-    const char* names[2] = {"kmc_device.hpp", "kmc_data.hpp"};
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
-    std::vector<char> code;
-    std::string log;
-    const kmc_status cst = rtc_compile_cached(src.str(), "kmc_data_density.hip", 2, headers, names, 4, opts, &code, &log);
-    if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "data density does not compile:\n" + log);
-    if (cst != KMC_OK) return cst;
-    auto ins = ud->code.emplace(key, std::move(code));
-    *out = &ins.first->second;
-    return KMC_OK;
+    static const RtcModule m{"data density", "kmc_data_density.hip", {"kmc_device.hpp", "kmc_data.hpp"}, rtc_options()};
+    return compile_keyed(ud, "data:" + std::to_string(ndim), m, [&](std::string* text) {
+        const std::string nd = std::to_string(ndim), nc = std::to_string(ud->ncols);
+        std::ostringstream src;
+        src << "#include \"kmc_data.hpp\"\n" << data_functor_source(ud)
+            << "extern \"C\" __global__ __launch_bounds__(" << kDataTPB << ") void kmc_data_lane(const kmc_data::DataArgs a) { kmc_data::data_partial_lane_body<UserData, " << nd << ", " << nc << ">(a); }\n"
+            << "extern \"C\" __global__ __launch_bounds__(" << kDataTPB << ") void kmc_data_obs(const kmc_data::DataArgs a) { kmc_data::data_partial_obs_body<UserData, " << nd << ", " << nc << ">(a); }\n"
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold(const kmc_data::DataArgs a) { kmc_data::data_fold_body<UserData, " << nd << ">(a); }\n"
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_data_fold_split(const kmc_data::DataArgs a) { kmc_data::data_fold_split_body<UserData, " << nd << ">(a); }\n";
+        *text = src.str();
+        return KMC_OK;
+    }, out);
 }
 }  // namespace
 
@@ -87,18 +74,9 @@ kmc_status load_data(kmc_user_density* ud, int64_t ndim, DataKernels* dk)
 {
     const std::vector<char>* code = nullptr;
     KMC_TRY(compile_data(ud, ndim, &code));
+    KMC_TRY(shared_module(ud, code, &dk->keep));
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lock(ud->mu);
-        auto& slot = ud->modules[{static_cast<const void*>(code), dev}];
-        if (!slot) {
-            hipModule_t m = nullptr;
-            HIP_TRY(hipModuleLoadData(&m, code->data()));
-            slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
-        }
-        dk->keep = slot;
-    }
     KMC_TRY(data_on_device(ud, dev, &dk->keep_data));
     dk->data = static_cast<const double*>(dk->keep_data.get());
     hipModule_t mod = static_cast<hipModule_t>(dk->keep.get());

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -187,6 +188,28 @@ struct ScopedDeviceBlock {
 // read or written is simply not used.  On a compile error *log holds the compiler's messages.
 kmc_status rtc_compile_cached(const std::string& text, const char* program_name, int nheaders, const char* const* header_text,
                               const char* const* header_names, int nopts, const char* const* opts, std::vector<char>* code, std::string* log);
+
+// One runtime-compiled module of a density: what rtc_compile_cached hashes into the cache file's name besides the text -- the program
+// name, the headers in this order, the options in this order -- so none of it changes without recompiling everyone's cache.
+struct RtcModule {
+    const char* what;                        // "user density" / "data density", for the messages
+    const char* program_name;
+    std::vector<const char*> headers;        // file names in the header directory (user_header_dir)
+    std::vector<const char*> options;
+};
+inline std::vector<const char*> rtc_options(bool kernarg_preload = false)     // (the preload: the sampler modules' half-step kernels only, kmc_kernels.hpp)
+{
+    std::vector<const char*> o = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
+    if (kernarg_preload) o.insert(o.end(), {"-mllvm", "-amdgpu-kernarg-preload-count=14"});
+    return o;
+}
+// The code object under `key` in ud->code; on a miss: the headers read, `text` asked for the program (a failure of its own is passed on),
+// rtc_compile_cached, the compiler's messages worded for `m.what`.  The one compile path of every runtime-compiled module (kmc_rtc.hip).
+kmc_status compile_keyed(kmc_user_density* ud, const std::string& key, const RtcModule& m, const std::function<kmc_status(std::string*)>& text,
+                         const std::vector<char>** out);
+// ... and the one load path: the module of a code object on the current device, shared per (density, code object, device) by everything
+// that runs it; unloaded when the last holder -- the density or one of those -- lets go of `keep`
+kmc_status shared_module(kmc_user_density* ud, const std::vector<char>* code, std::shared_ptr<void>* keep);
 
 kmc_status download_by_walker(const void* src_dev, bool is_float, int64_t nl, int64_t ld, int64_t width, int64_t K, double* dst_host, hipStream_t st);
 std::string user_functor_source(const kmc_user_density* ud);      // the functor(s) ...

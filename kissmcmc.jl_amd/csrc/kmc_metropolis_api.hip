@@ -27,56 +27,24 @@ kmc_status compile_user_metropolis(kmc_user_density* ud, int ND, const std::vect
     if (ud->is_body) ND = 0;                     // a body density: the chain-in-memory kernel (the proposal is collected per lane)
     char key[64];
     std::snprintf(key, sizeof(key), "M:%d:%lld:%d", ND, ud->is_body ? (long long)ndim : 0ll, TND);
-    std::lock_guard<std::mutex> lock(ud->mu);
-    auto it = ud->code.find(key);
-    if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
-    const std::string dir = user_header_dir();
-    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_ker = read_file(dir + "/kmc_kernels.hpp"),
-                      h_met = read_file(dir + "/kmc_metropolis.hpp");
-    if (h_dev.empty() || h_ker.empty() || h_met.empty())
-        return fail(KMC_ERR_BAD_ARG, "user density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
-    std::ostringstream src;
-    src << "#include \"kmc_kernels.hpp\"\n#include \"kmc_metropolis.hpp\"\n" << user_functor_source(ud) << user_density_alias(ud, ndim)
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_metropolis(const kmc::MetropolisArgs a) { ";
-    if (ND > 0) src << "kmc::metropolis_chains_body<UD, " << ND << ">(a); }\n";
-    else src << "kmc::metropolis_chains_any_body<UD>(a); }\n";
-    if (TND > 0)
-        src << "extern \"C\" __global__ __launch_bounds__(128) void kmc_user_metropolis_tabled(const kmc::MetropolisTabledArgs t) { "
-            << "kmc::metropolis_chains_tabled_body<UD, " << TND << ">(t.a, t.draws, t.nsteps); }\n";
-    const std::string text = src.str();
-    const char* headers[3] = {h_ker.c_str(), h_dev.c_str(), h_met.c_str()};
-    const char* names[3] = {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_metropolis.hpp"};
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
-    std::vector<char> code;
-    std::string log;
-    const kmc_status cst = rtc_compile_cached(text, "kmc_user_metropolis.hip", 3, headers, names, 4, opts, &code, &log);
-    if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "user density does not compile:\n" + log);
-    if (cst != KMC_OK) return cst;
-    auto ins = ud->code.emplace(key, std::move(code));
-    *out = &ins.first->second;
-    return KMC_OK;
+    static const RtcModule m{"user density", "kmc_user_metropolis.hip", {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_metropolis.hpp"}, rtc_options()};
+    return compile_keyed(ud, key, m, [&](std::string* text) {
+        std::ostringstream src;
+        src << "#include \"kmc_kernels.hpp\"\n#include \"kmc_metropolis.hpp\"\n" << user_functor_source(ud) << user_density_alias(ud, ndim)
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_metropolis(const kmc::MetropolisArgs a) { ";
+        if (ND > 0) src << "kmc::metropolis_chains_body<UD, " << ND << ">(a); }\n";
+        else src << "kmc::metropolis_chains_any_body<UD>(a); }\n";
+        if (TND > 0)
+            src << "extern \"C\" __global__ __launch_bounds__(128) void kmc_user_metropolis_tabled(const kmc::MetropolisTabledArgs t) { "
+                << "kmc::metropolis_chains_tabled_body<UD, " << TND << ">(t.a, t.draws, t.nsteps); }\n";
+        *text = src.str();
+        return KMC_OK;
+    }, out);
 }
 
 template <class T>
 hipError_t metro_alloc(T** p, size_t bytes) { return cache_alloc(reinterpret_cast<void**>(p), bytes); }
-
-// the loaded module of a code object, shared per (density, code object, device) like the samplers' (kmc_rtc.hip: load_user)
-kmc_status shared_module(kmc_user_density* ud, const std::vector<char>* code, std::shared_ptr<void>* keep, hipModule_t* mod)
-{
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(ud->mu);
-    auto& slot = ud->modules[{static_cast<const void*>(code), dev}];
-    if (!slot) {
-        hipModule_t m = nullptr;
-        HIP_TRY(hipModuleLoadData(&m, code->data()));
-        slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
-    }
-    *keep = slot;
-    *mod = static_cast<hipModule_t>(slot.get());
-    return KMC_OK;
-}
 
 // device buffers of one kmc_metropolis_run call
 struct MetroBuffers {
@@ -174,7 +142,8 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
         if (c->density == KMC_USER_DENSITY) {
             const std::vector<char>* code = nullptr;
             KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), metropolis_nd(nd), &code, nd));
-            KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep, &b.mod));
+            KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep));
+            b.mod = static_cast<hipModule_t>(b.keep.get());
             HIP_TRY(hipModuleGetFunction(&ulp, b.mod, "kmc_user_logpdf"));
         } else {
             lp = logpdf_fn(c->density);
@@ -399,7 +368,8 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     if (c->density == KMC_USER_DENSITY) {
         const std::vector<char>* code = nullptr;
         KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), ND, &code, nd, tabled ? metropolis_nd(nd) : 0));
-        KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep, &b.mod));
+        KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep));
+        b.mod = static_cast<hipModule_t>(b.keep.get());
         HIP_TRY(hipModuleGetFunction(&ufn, b.mod, "kmc_user_metropolis"));
         HIP_TRY(hipModuleGetFunction(&ulp, b.mod, "kmc_user_logpdf"));
         if (tabled) HIP_TRY(hipModuleGetFunction(&utfn, b.mod, "kmc_user_metropolis_tabled"));

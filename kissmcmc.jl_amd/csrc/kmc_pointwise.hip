@@ -57,38 +57,24 @@ struct PwKernels {
 
 kmc_status compile_pointwise(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
 {
-    const std::string key = "pointwise:" + std::to_string(ndim);
-    std::lock_guard<std::mutex> lock(ud->mu);
-    auto it = ud->code.find(key);
-    if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
-    const std::string dir = user_header_dir();
-    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_pw = read_file(dir + "/kmc_pointwise.hpp"),
-                      h_fit = read_file(dir + "/kmc_psis_fit.hpp");
-    if (h_dev.empty() || h_pw.empty() || h_fit.empty()) return fail(KMC_ERR_BAD_ARG, "data density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
-    const std::string t = "<UserData, " + std::to_string(ndim) + ", " + std::to_string(ud->ncols);
-    const std::string head = "extern \"C\" __global__ __launch_bounds__(" + std::to_string(kPwThreads) + ") void ";
-    std::ostringstream src;
-    src << "#include \"kmc_pointwise.hpp\"\n" << data_functor_source(ud)
-        << head << "kmc_pw_pass1(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, false>(a); }\n"
-        << head << "kmc_pw_pass2(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, false>(a); }\n"
-        << head << "kmc_pw_pass1_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, true>(a); }\n"
-        << head << "kmc_pw_pass2_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, true>(a); }\n"
-        << head << "kmc_pw_matrix(const kmc_pw::PwArgs a) { kmc_pw::pw_matrix" << t << ">(a); }\n";
-    for (int mode = 0; mode < 3; ++mode)
-        for (int packed = 0; packed < 2; ++packed)
-            src << head << "kmc_psis_walk" << mode << (packed ? "_packed" : "") << "(const kmc_pw::PsisArgs q) { kmc_pw::psis_walk" << t << ", " << mode << ", "
-                << (packed ? "true" : "false") << ">(q); }\n";
-    const char* headers[3] = {h_dev.c_str(), h_pw.c_str(), h_fit.c_str()};
-    const char* names[3] = {"kmc_device.hpp", "kmc_pointwise.hpp", "kmc_psis_fit.hpp"};
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
-    std::vector<char> code;
-    std::string log;
-    const kmc_status cst = rtc_compile_cached(src.str(), "kmc_pointwise.hip", 3, headers, names, 4, opts, &code, &log);
-    if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "data density does not compile:\n" + log);
-    if (cst != KMC_OK) return cst;
-    auto ins = ud->code.emplace(key, std::move(code));
-    *out = &ins.first->second;
-    return KMC_OK;
+    static const RtcModule m{"data density", "kmc_pointwise.hip", {"kmc_device.hpp", "kmc_pointwise.hpp", "kmc_psis_fit.hpp"}, rtc_options()};
+    return compile_keyed(ud, "pointwise:" + std::to_string(ndim), m, [&](std::string* text) {
+        const std::string t = "<UserData, " + std::to_string(ndim) + ", " + std::to_string(ud->ncols);
+        const std::string head = "extern \"C\" __global__ __launch_bounds__(" + std::to_string(kPwThreads) + ") void ";
+        std::ostringstream src;
+        src << "#include \"kmc_pointwise.hpp\"\n" << data_functor_source(ud)
+            << head << "kmc_pw_pass1(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, false>(a); }\n"
+            << head << "kmc_pw_pass2(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, false>(a); }\n"
+            << head << "kmc_pw_pass1_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 1, true>(a); }\n"
+            << head << "kmc_pw_pass2_packed(const kmc_pw::PwArgs a) { kmc_pw::pw_partials" << t << ", 2, true>(a); }\n"
+            << head << "kmc_pw_matrix(const kmc_pw::PwArgs a) { kmc_pw::pw_matrix" << t << ">(a); }\n";
+        for (int mode = 0; mode < 3; ++mode)
+            for (int packed = 0; packed < 2; ++packed)
+                src << head << "kmc_psis_walk" << mode << (packed ? "_packed" : "") << "(const kmc_pw::PsisArgs q) { kmc_pw::psis_walk" << t << ", " << mode << ", "
+                    << (packed ? "true" : "false") << ">(q); }\n";
+        *text = src.str();
+        return KMC_OK;
+    }, out);
 }
 
 // compile (cached) + module on the current device + the device copy of the density's own observations
@@ -96,18 +82,9 @@ kmc_status load_pointwise(kmc_user_density* ud, int64_t ndim, bool own_data, PwK
 {
     const std::vector<char>* code = nullptr;
     KMC_TRY(compile_pointwise(ud, ndim, &code));
+    KMC_TRY(shared_module(ud, code, &pk->keep));
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    {
-        std::lock_guard<std::mutex> lock(ud->mu);
-        auto& slot = ud->modules[{static_cast<const void*>(code), dev}];
-        if (!slot) {
-            hipModule_t m = nullptr;
-            HIP_TRY(hipModuleLoadData(&m, code->data()));
-            slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
-        }
-        pk->keep = slot;
-    }
     if (own_data) KMC_TRY(data_on_device(ud, dev, &pk->keep_data));
     hipModule_t mod = static_cast<hipModule_t>(pk->keep.get());
     HIP_TRY(hipModuleGetFunction(&pk->pass[0][0], mod, "kmc_pw_pass1"));

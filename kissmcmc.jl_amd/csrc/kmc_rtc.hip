@@ -187,6 +187,12 @@ std::string rtc_cache_dir()
 kmc_status kmc_host::rtc_compile_cached(const std::string& text, const char* program_name, int nheaders, const char* const* header_text,
                                         const char* const* header_names, int nopts, const char* const* opts, std::vector<char>* code, std::string* log)
 {
+    // KMC_DEBUG=rtc-text=<dir>: every program text that asks for a compile, cached or not, as <dir>/<sequence>_<program_name> (best effort)
+    std::string dump_dir;
+    if (debug_opt("rtc-text", &dump_dir) && !dump_dir.empty()) {
+        static std::atomic<unsigned> sequence{0};
+        std::ofstream(dump_dir + "/" + std::to_string(1000000u + sequence++).substr(1) + "_" + program_name, std::ios::binary) << text;
+    }
     // key
     uint64_t h1 = 0xcbf29ce484222325ull, h2 = 0x84222325cbf29ce4ull;
     auto mix = [&](const void* p, size_t n) { h1 = fnv1a(h1, p, n); h2 = fnv1a(h2 ^ (uint64_t)n, p, n); h2 = (h2 << 7) | (h2 >> 57); };
@@ -343,133 +349,204 @@ std::string kmc_host::user_header_dir()
     return envdir ? std::string(envdir) : library_dir() + "/csrc";
 }
 
-namespace kmc_host {
-kmc_status compile_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged,
-                        int resident_K, bool resident_ragged, int island_S, bool f32, const std::vector<char>** out, int64_t ndim = 0,
-                        bool p2p = false, int generation_nd = 0, int move_id = 0)
+// ---- the one compile path and the one load path of every runtime-compiled module ----
+kmc_status kmc_host::compile_keyed(kmc_user_density* ud, const std::string& key, const RtcModule& m, const std::function<kmc_status(std::string*)>& text,
+                                   const std::vector<char>** out)
 {
-    // resident_K also sizes the island kernel (same row striping: 2 lanes per walker, K chunks)
-    // a body in the vector kernels: lane-striped when it is a recognised sum over elements (sep), else rows lane-striped and the body
-    // evaluated per walker on the whole proposal (kmc_kernels.hpp, RowEvalTrait; no blobs, ndim <= kBodyVecMaxDim)
-    if (ud->is_body && ((with_vec && !sep_routed(ud) && !body_vec_possible(ud, ndim)) || island_S > 0))
-        return fail(KMC_ERR_UNSUPPORTED, "this body density runs in the one-walker-per-lane kernels only");
-    // KMC_MOVE_DE / _SNOOKER: the two half-step bodies with that move; KMC_MOVE_MIX: the bodies that pick the member (no staged kernel; one GPU, double rows: kmc_validate)
-    // move_id >= kTemperMoveBase: the tempered form of that move's bodies (the rung as blockIdx.y; in the key, and in the program text the disk cache hashes)
-    const bool temper = move_id >= kTemperMoveBase;
-    const int move_key = move_id;
-    if (temper) move_id -= kTemperMoveBase;
-    const bool de = move_id != KMC_MOVE_STRETCH || temper, mix = move_id == KMC_MOVE_MIX;
-    const bool staged = !de && !with_vec && staged_possible(ud, f32, ndim, p2p);
-    char key[128];
-    std::snprintf(key, sizeof(key), "%d:%d,%d,%d,%d|%d,%d|%d|%d|%lld|%d|%d|%d|%d|%d|%d", (int)with_vec, L, K, iter, (int)ragged, resident_K,
-                  (int)resident_ragged, island_S, (int)f32, ud->is_body ? (long long)ndim : 0ll, (int)staged, (int)p2p, ud->nblob, (int)sep_routed(ud) + 2 * (int)offline_compiler_wanted(),
-                  generation_nd, move_key);
-    const char* peer = p2p ? "true" : "false";         // KMC_P2P: partner rows read from their owners (pull)
-    const char* rowt = f32 ? "float" : "double";       // storage type of the walker rows (KMC_F32 / KMC_F64)
-    const char* move = move_id == KMC_MOVE_SNOOKER ? ", kmc::Move::Snooker" : move_id == KMC_MOVE_DE ? ", kmc::Move::DE" : temper ? ", kmc::Move::Stretch" : "";    // the half-step bodies' move (the stretch move by default)
     std::lock_guard<std::mutex> lock(ud->mu);
     auto it = ud->code.find(key);
     if (it != ud->code.end()) { *out = &it->second; return KMC_OK; }
-
-    const char* envdir = std::getenv("KMC_CSRC_DIR");
-    const std::string dir = envdir ? std::string(envdir) : library_dir() + "/csrc";
-    const std::string h_dev = read_file(dir + "/kmc_device.hpp"), h_ker = read_file(dir + "/kmc_kernels.hpp"),
-                      h_isl = read_file(dir + "/kmc_islands.hpp"), h_gen = read_file(dir + "/kmc_generation.hpp");
-    if (h_dev.empty() || h_ker.empty() || h_isl.empty() || h_gen.empty())
-        return fail(KMC_ERR_BAD_ARG, "user density: kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
-
-    std::ostringstream src;
-    src << "#include \"kmc_islands.hpp\"\n#include \"kmc_generation.hpp\"\n" << user_functor_source(ud) << user_density_alias(ud, ndim)
-        << (ud->is_body && with_vec && sep_routed(ud) ? ud->sep_functor + (ud->sep_nacc > 1 ? "using UDV = kmc::SepDensityN<UserS>;\n" : "using UDV = kmc::SepDensity<UserS>;\n")
-                                                : std::string("using UDV = UD;\n"))
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_generic(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { "
-        << (temper ? "const kmc::HalfStepArgs b = kmc::temper_args(a); " : "")
-        << (mix ? std::string("kmc::half_step_mix_generic_body<UD") + (temper ? ", true" : "") : std::string("kmc::half_step_generic_body<UD, ") + peer + ", " + rowt + move + (temper ? ", true" : ""))
-        << (temper ? ">(KMC_FRONT_PACK, b); }\n" : ">(KMC_FRONT_PACK, a); }\n")
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
-        << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_init_ball(const kmc::InitBallArgs a) { kmc::init_ball_body<UD>(a); }\n";
-    if (ud->is_body && with_vec && sep_routed(ud))
-        src << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf_sep(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UDV>(a); }\n";
-    if (staged)
-        src << "extern \"C\" __global__ __launch_bounds__(" << kStagedTPB << ") void kmc_user_staged(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_staged_body<UD, "
-            << ndim << ">(KMC_FRONT_PACK, a); }\n";
-    if (with_vec && temper)
-        src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { const kmc::HalfStepFront f = kmc::temper_front<"
-            << L << ", " << K << ", " << (ragged ? "true" : "false") << ">(KMC_FRONT_PACK); "
-            << (mix ? std::string("kmc::half_step_mix_vec_body<UDV, ") + std::to_string(L) + ", " + std::to_string(K) + ", " + std::to_string(iter) + ", " + (ragged ? "true" : "false") + ", true"
-                    : std::string("kmc::half_step_vec_body<UDV, ") + std::to_string(L) + ", " + std::to_string(K) + ", " + std::to_string(iter) + ", false, " + (ragged ? "true" : "false") + ", double" + move + ", true")
-            << ">(f, a); }\n";
-    else if (with_vec && mix)
-        src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_mix_vec_body<UDV, "
-            << L << ", " << K << ", " << iter << ", " << (ragged ? "true" : "false") << ">(KMC_FRONT_PACK, a); }\n";
-    else if (with_vec)
-        src << "extern \"C\" __global__ __launch_bounds__(" << vec_tpb(L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_vec_body<UDV, "
-            << L << ", " << K << ", " << iter << ", " << peer << ", " << (ragged ? "true" : "false") << ", " << rowt << move << ">(KMC_FRONT_PACK, a); }\n";
-    if (resident_K == 2048 && island_S == 0 && ud->is_body)   // two walkers per thread (1026 .. 2048 walkers)
-        src << "extern \"C\" __global__ __launch_bounds__(1024) void kmc_user_resident(const kmc::ResidentArgs a) { kmc::resident_lane2_body<UD, " << ndim << ">(a); }\n";
-    else if (resident_K <= -100 && island_S == 0 && !ud->is_body)
-        src << "extern \"C\" __global__ __launch_bounds__(1024) void kmc_user_resident(const kmc::ResidentArgs a) { kmc::resident_lane2_body<UD, " << -resident_K - 100 << ">(a); }\n";
-    else if (resident_K > 0 && island_S == 0 && ud->is_body)       // one walker per thread; resident_K = the workgroup size it is launched with at most
-        src << "extern \"C\" __global__ __launch_bounds__(" << resident_K << ") void kmc_user_resident(const kmc::ResidentArgs a) { kmc::resident_lane_body<UD, " << ndim << ", true, " << rowt << ">(a); }\n";
-    if (resident_K > 0 && island_S == 0 && !ud->is_body)
-        src << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_resident(const kmc::ResidentArgs a) { kmc::resident_body<UD, "
-            << resident_K << ", " << (resident_ragged ? "true" : "false") << ">(a); }\n";
-    if (resident_K < 0 && resident_K > -100 && island_S == 0 && !ud->is_body)      // short rows: one walker per thread, ndim <= ND = -resident_K
-        src << "extern \"C\" __global__ __launch_bounds__(1024) void kmc_user_resident(const kmc::ResidentArgs a) { kmc::resident_lane_body<UD, " << -resident_K << ", true, " << rowt << ">(a); }\n";
-    if (resident_K > 0 && island_S > 0)
-        src << "extern \"C\" __global__ __launch_bounds__(" << island_S << ") void kmc_user_island(const kmc::IslandArgs a) { kmc::island_epoch_body<UD, "
-            << island_S << ", " << resident_K << ", " << (resident_ragged ? "true" : "false") << ">(a); }\n";
-    if (generation_nd > 0)          // one launch per generation, one walker per lane (kmc_generation.hpp): the density element by element / the body as written
-        src << "extern \"C\" __global__ __launch_bounds__(" << kGenerationTPB << ") void kmc_user_generation(KMC_GEN_FRONT_PARAMS, const kmc::GenerationArgs a) { kmc::generation_lane_body<UD, "
-            << generation_nd << ">(KMC_GEN_FRONT_PACK, a); }\n";
-    if (generation_nd < 0)          // ... rows lane-striped (L = -generation_nd / 100, K = -generation_nd % 100): term / pair densities, bodies recognised as sums
-        src << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_generation(KMC_GEN_FRONT_PARAMS, const kmc::GenerationArgs a) { kmc::generation_group_body<UDV, "
-            << (-generation_nd) / 100 << ", " << (-generation_nd) % 100 << ">(KMC_GEN_FRONT_PACK, a); }\n";
-    const std::string text = src.str();
-
-    const char* headers[4] = {h_ker.c_str(), h_dev.c_str(), h_isl.c_str(), h_gen.c_str()};
-    const char* names[4] = {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_islands.hpp", "kmc_generation.hpp"};
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-kernarg-preload-count=14"};
+    const std::string dir = user_header_dir();
+    std::vector<std::string> bodies(m.headers.size());
+    std::vector<const char*> header_text;
+    for (size_t i = 0; i < bodies.size(); ++i) {
+        bodies[i] = read_file(dir + "/" + m.headers[i]);
+        if (bodies[i].empty()) return fail(KMC_ERR_BAD_ARG, std::string(m.what) + ": kernel headers not found in " + dir + " (set KMC_CSRC_DIR)");
+        header_text.push_back(bodies[i].c_str());
+    }
+    std::string program;
+    KMC_TRY(text(&program));
     std::vector<char> code;
     std::string log;
-    const kmc_status cst = rtc_compile_cached(text, "kmc_user_density.hip", 4, headers, names, 6, opts, &code, &log);
-    if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, "user density does not compile:\n" + log);
+    const kmc_status cst = rtc_compile_cached(program, m.program_name, (int)m.headers.size(), header_text.data(), m.headers.data(),
+                                              (int)m.options.size(), m.options.data(), &code, &log);
+    if (cst == KMC_ERR_BAD_ARG) return fail(KMC_ERR_BAD_ARG, std::string(m.what) + " does not compile:\n" + log);
     if (cst != KMC_OK) return cst;
-    auto ins = ud->code.emplace(key, std::move(code));
-    *out = &ins.first->second;
+    *out = &ud->code.emplace(key, std::move(code)).first->second;
     return KMC_OK;
 }
 
-kmc_status load_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged, UserKernels* uk,
-                     int resident_K, bool resident_ragged, int island_S, bool f32, int64_t ndim, bool p2p, int generation_nd, int move)
+kmc_status kmc_host::shared_module(kmc_user_density* ud, const std::vector<char>* code, std::shared_ptr<void>* keep)
 {
-    const bool de = move != KMC_MOVE_STRETCH;         // (a tempered sampler too: move >= kTemperMoveBase)
-    const std::vector<char>* code = nullptr;
-    KMC_TRY(compile_user(ud, with_vec, L, K, iter, ragged, resident_K, resident_ragged, island_S, f32, &code, ndim, p2p, generation_nd, move));
-    {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(ud->mu);
-        auto& slot = ud->modules[{static_cast<const void*>(code), dev}];
-        if (!slot) {
-            hipModule_t m = nullptr;
-            HIP_TRY(hipModuleLoadData(&m, code->data()));
-            slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
-        }
-        uk->keep = slot;
-        uk->mod = static_cast<hipModule_t>(slot.get());
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(ud->mu);
+    auto& slot = ud->modules[{static_cast<const void*>(code), dev}];
+    if (!slot) {
+        hipModule_t m = nullptr;
+        HIP_TRY(hipModuleLoadData(&m, code->data()));
+        slot = std::shared_ptr<void>(static_cast<void*>(m), [](void* p) { if (p) (void)hipModuleUnload(static_cast<hipModule_t>(p)); });
     }
+    *keep = slot;
+    return KMC_OK;
+}
+
+// ---- a sampler's module: the program text as a function of the density and the spec, one emitter per kernel ----
+namespace {
+using Resident = UserModuleSpec::Resident;
+using Generation = UserModuleSpec::Generation;
+const char* tf(bool b) { return b ? "true" : "false"; }
+const char* row_type(const UserModuleSpec& s) { return s.f32 ? "float" : "double"; }      // storage type of the walker rows (KMC_F32 / KMC_F64)
+bool mix_move(const UserModuleSpec& s) { return s.move == KMC_MOVE_MIX; }                  // the bodies that pick the member (no staged kernel; one GPU, double rows: kmc_validate)
+// the half-step bodies' move argument (the stretch move by default; a tempered body names it)
+const char* move_arg(const UserModuleSpec& s)
+{
+    return s.move == KMC_MOVE_SNOOKER ? ", kmc::Move::Snooker" : s.move == KMC_MOVE_DE ? ", kmc::Move::DE" : s.temper ? ", kmc::Move::Stretch" : "";
+}
+// a body recognised as a sum over elements runs the vector kernels in its generated per-element form (UDV)
+bool sum_form(const kmc_user_density* ud, const UserModuleSpec& s) { return ud->is_body && s.vec && sep_routed(ud); }
+// a body density's staged kernel: the stretch move, untempered, when the plan has no vector kernel
+bool staged_kernel(const kmc_user_density* ud, const UserModuleSpec& s)
+{
+    return s.move == KMC_MOVE_STRETCH && !s.temper && !s.vec && staged_possible(ud, s.f32, s.ndim, s.p2p);
+}
+const char kGlobal[] = "extern \"C\" __global__ __launch_bounds__(";
+
+void emit_density(std::ostream& o, const kmc_user_density* ud, const UserModuleSpec& s)
+{
+    o << "#include \"kmc_islands.hpp\"\n#include \"kmc_generation.hpp\"\n" << user_functor_source(ud) << user_density_alias(ud, s.ndim);
+    if (sum_form(ud, s)) o << ud->sep_functor << (ud->sep_nacc > 1 ? "using UDV = kmc::SepDensityN<UserS>;\n" : "using UDV = kmc::SepDensity<UserS>;\n");
+    else o << "using UDV = UD;\n";
+}
+void emit_generic(std::ostream& o, const UserModuleSpec& s)
+{
+    o << kGlobal << "256) void kmc_user_generic(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { " << (s.temper ? "const kmc::HalfStepArgs b = kmc::temper_args(a); " : "");
+    if (mix_move(s)) o << "kmc::half_step_mix_generic_body<UD" << (s.temper ? ", true" : "");
+    else o << "kmc::half_step_generic_body<UD, " << tf(s.p2p) << ", " << row_type(s) << move_arg(s) << (s.temper ? ", true" : "");
+    o << (s.temper ? ">(KMC_FRONT_PACK, b); }\n" : ">(KMC_FRONT_PACK, a); }\n");
+}
+void emit_logpdf(std::ostream& o) { o << kGlobal << "256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"; }
+void emit_init_ball(std::ostream& o) { o << kGlobal << "256) void kmc_user_init_ball(const kmc::InitBallArgs a) { kmc::init_ball_body<UD>(a); }\n"; }
+void emit_logpdf_sep(std::ostream& o) { o << kGlobal << "256) void kmc_user_logpdf_sep(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UDV>(a); }\n"; }
+void emit_staged(std::ostream& o, const UserModuleSpec& s)
+{
+    o << kGlobal << kStagedTPB << ") void kmc_user_staged(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { kmc::half_step_staged_body<UD, " << s.ndim << ">(KMC_FRONT_PACK, a); }\n";
+}
+void emit_vec(std::ostream& o, const UserModuleSpec& s)
+{
+    o << kGlobal << vec_tpb(s.L) << ") void kmc_user_vec(KMC_FRONT_PARAMS, const kmc::HalfStepArgs a) { ";
+    if (s.temper) {              // (a tempered ladder: one GPU, double rows)
+        o << "const kmc::HalfStepFront f = kmc::temper_front<" << s.L << ", " << s.K << ", " << tf(s.ragged) << ">(KMC_FRONT_PACK); ";
+        if (mix_move(s)) o << "kmc::half_step_mix_vec_body<UDV, " << s.L << ", " << s.K << ", " << s.iter << ", " << tf(s.ragged) << ", true";
+        else o << "kmc::half_step_vec_body<UDV, " << s.L << ", " << s.K << ", " << s.iter << ", false, " << tf(s.ragged) << ", double" << move_arg(s) << ", true";
+        o << ">(f, a); }\n";
+    } else if (mix_move(s))
+        o << "kmc::half_step_mix_vec_body<UDV, " << s.L << ", " << s.K << ", " << s.iter << ", " << tf(s.ragged) << ">(KMC_FRONT_PACK, a); }\n";
+    else
+        o << "kmc::half_step_vec_body<UDV, " << s.L << ", " << s.K << ", " << s.iter << ", " << tf(s.p2p) << ", " << tf(s.ragged) << ", " << row_type(s) << move_arg(s)
+          << ">(KMC_FRONT_PACK, a); }\n";
+}
+kmc_status emit_resident(std::ostream& o, const kmc_user_density* ud, const UserModuleSpec& s)
+{
+    const char* args = ") void kmc_user_resident(const kmc::ResidentArgs a) { ";
+    switch (s.resident) {
+    case Resident::None: break;
+    case Resident::Lane2:        // two walkers per thread (1026 .. 2048 walkers)
+        o << kGlobal << 1024 << args << "kmc::resident_lane2_body<UD, " << s.ndim << ">(a); }\n";
+        break;
+    case Resident::Lane:         // one walker per thread: a body at its own ndim under its workgroup bound, a term / pair density on short rows of up to lane_nd
+        if (ud->is_body) o << kGlobal << s.lane_bound << args << "kmc::resident_lane_body<UD, " << s.ndim << ", true, " << row_type(s) << ">(a); }\n";
+        else o << kGlobal << 1024 << args << "kmc::resident_lane_body<UD, " << s.lane_nd << ", true, " << row_type(s) << ">(a); }\n";
+        break;
+    case Resident::Pair:
+        if (ud->is_body) return fail(KMC_ERR_UNSUPPORTED, "a body density has no resident kernel with a pair of lanes per walker");
+        o << kGlobal << 256 << args << "kmc::resident_body<UD, " << s.pair_K << ", " << tf(s.pair_ragged) << ">(a); }\n";
+        break;
+    }
+    return KMC_OK;
+}
+void emit_island(std::ostream& o, const UserModuleSpec& s)       // (the pair kernels' row striping: 2 lanes per walker, pair_K chunks)
+{
+    o << kGlobal << s.island_S << ") void kmc_user_island(const kmc::IslandArgs a) { kmc::island_epoch_body<UD, " << s.island_S << ", " << s.pair_K << ", " << tf(s.pair_ragged) << ">(a); }\n";
+}
+void emit_generation(std::ostream& o, const UserModuleSpec& s)   // one launch per generation (kmc_generation.hpp)
+{
+    const char* args = ") void kmc_user_generation(KMC_GEN_FRONT_PARAMS, const kmc::GenerationArgs a) { ";
+    switch (s.generation) {
+    case Generation::None: break;
+    case Generation::Lane:       // one walker per lane: the density element by element / the body as written
+        o << kGlobal << kGenerationTPB << args << "kmc::generation_lane_body<UD, " << s.ndim << ">(KMC_GEN_FRONT_PACK, a); }\n";
+        break;
+    case Generation::Striped:    // rows lane-striped (term / pair densities, bodies recognised as sums): in the vector geometry, or the row over a quad
+    case Generation::Quad:
+        o << kGlobal << 256 << args << "kmc::generation_group_body<UDV, " << (s.generation == Generation::Quad ? 4 : s.L) << ", " << (s.generation == Generation::Quad ? 1 : s.K)
+          << ">(KMC_GEN_FRONT_PACK, a); }\n";
+        break;
+    }
+}
+
+// The program of a sampler's module: a pure function of the density and the spec (no lock, no file, no compiler).  The disk cache hashes
+// this text, so the same text is the same code object; tests/test_gpu_user_modules.py pins it for every spec a caller produces.
+kmc_status user_program_text(const kmc_user_density* ud, const UserModuleSpec& s, std::string* text)
+{
+    // a body in the vector kernels: lane-striped when it is a recognised sum over elements, else rows lane-striped and the body
+    // evaluated per walker on the whole proposal (kmc_kernels.hpp, RowEvalTrait; ndim <= kBodyVecMaxDim); never in the pair kernels' striping
+    if (ud->is_body && ((s.vec && !sep_routed(ud) && !body_vec_possible(ud, s.ndim)) || s.island_S > 0))
+        return fail(KMC_ERR_UNSUPPORTED, "this body density runs in the one-walker-per-lane kernels only");
+    std::ostringstream o;
+    emit_density(o, ud, s);
+    emit_generic(o, s);
+    emit_logpdf(o);
+    emit_init_ball(o);
+    if (sum_form(ud, s)) emit_logpdf_sep(o);
+    if (staged_kernel(ud, s)) emit_staged(o, s);
+    if (s.vec) emit_vec(o, s);
+    if (s.island_S > 0) emit_island(o, s);
+    else KMC_TRY(emit_resident(o, ud, s));
+    emit_generation(o, s);
+    *text = o.str();
+    return KMC_OK;
+}
+
+// The key of a sampler's code object within its density: every field of the spec, the density facts the text reads beyond the functor
+// itself (is_body and nblob choose the alias, the sum-form routing the UDV, `staged` the staged kernel) and which compiler builds it.
+// ndim counts where the text reads it: always for a body density (alias, staged, Lane), for a term / pair density in resident Lane2 and in
+// generation Lane (both built for the exact row length); its other modules are shared across row lengths.
+std::string user_module_key(const kmc_user_density* ud, const UserModuleSpec& s)
+{
+    const bool reads_ndim = ud->is_body || s.resident == Resident::Lane2 || s.generation == Generation::Lane;
+    char key[192];
+    std::snprintf(key, sizeof(key), "%d:%d,%d,%d,%d|%d:%d,%d,%d,%d|%d|%d|%lld|%d|%d|%d,%d|%d,%d,%d,%d,%d", (int)s.vec, s.L, s.K, s.iter, (int)s.ragged,
+                  (int)s.resident, s.pair_K, (int)s.pair_ragged, s.lane_nd, s.lane_bound, s.island_S, (int)s.f32, reads_ndim ? (long long)s.ndim : 0ll, (int)s.p2p,
+                  (int)s.generation, s.move, (int)s.temper, (int)ud->is_body, ud->nblob, (int)sep_routed(ud), (int)staged_kernel(ud, s), (int)offline_compiler_wanted());
+    return key;
+}
+}  // namespace
+
+namespace kmc_host {
+kmc_status compile_user(kmc_user_density* ud, const UserModuleSpec& spec, const std::vector<char>** out)
+{
+    static const RtcModule m{"user density", "kmc_user_density.hip", {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_islands.hpp", "kmc_generation.hpp"}, rtc_options(true)};
+    return compile_keyed(ud, user_module_key(ud, spec), m, [&](std::string* text) { return user_program_text(ud, spec, text); }, out);
+}
+
+kmc_status load_user(kmc_user_density* ud, const UserModuleSpec& spec, UserKernels* uk)
+{
+    const std::vector<char>* code = nullptr;
+    KMC_TRY(compile_user(ud, spec, &code));
+    KMC_TRY(shared_module(ud, code, &uk->keep));
+    uk->mod = static_cast<hipModule_t>(uk->keep.get());
     HIP_TRY(hipModuleGetFunction(&uk->generic, uk->mod, "kmc_user_generic"));
     HIP_TRY(hipModuleGetFunction(&uk->logpdf, uk->mod, "kmc_user_logpdf"));
     HIP_TRY(hipModuleGetFunction(&uk->init_ball, uk->mod, "kmc_user_init_ball"));
-    if (with_vec) HIP_TRY(hipModuleGetFunction(&uk->vec, uk->mod, "kmc_user_vec"));
+    if (spec.vec) HIP_TRY(hipModuleGetFunction(&uk->vec, uk->mod, "kmc_user_vec"));
     uk->logpdf_sep = nullptr;
-    if (with_vec && ud->is_body && sep_routed(ud)) HIP_TRY(hipModuleGetFunction(&uk->logpdf_sep, uk->mod, "kmc_user_logpdf_sep"));
-    if (!de && !with_vec && staged_possible(ud, f32, ndim, p2p)) HIP_TRY(hipModuleGetFunction(&uk->staged, uk->mod, "kmc_user_staged"));
-    if (resident_K != 0 && island_S == 0) HIP_TRY(hipModuleGetFunction(&uk->resident, uk->mod, "kmc_user_resident"));
-    if (resident_K > 0 && island_S > 0) HIP_TRY(hipModuleGetFunction(&uk->island, uk->mod, "kmc_user_island"));
+    if (sum_form(ud, spec)) HIP_TRY(hipModuleGetFunction(&uk->logpdf_sep, uk->mod, "kmc_user_logpdf_sep"));
+    if (staged_kernel(ud, spec)) HIP_TRY(hipModuleGetFunction(&uk->staged, uk->mod, "kmc_user_staged"));
+    if (spec.island_S > 0) HIP_TRY(hipModuleGetFunction(&uk->island, uk->mod, "kmc_user_island"));
+    else if (spec.resident != Resident::None) HIP_TRY(hipModuleGetFunction(&uk->resident, uk->mod, "kmc_user_resident"));
     uk->generation = nullptr;
-    if (generation_nd != 0) HIP_TRY(hipModuleGetFunction(&uk->generation, uk->mod, "kmc_user_generation"));
+    if (spec.generation != Generation::None) HIP_TRY(hipModuleGetFunction(&uk->generation, uk->mod, "kmc_user_generation"));
     return KMC_OK;
 }
 
@@ -483,7 +560,7 @@ KMC_EXPORT kmc_status kmc_user_density_create(const char* term_expr, const char*
     ud->has_pair = pair_expr != nullptr && pair_expr[0] != '\0';
     if (ud->has_pair) ud->pair = pair_expr;
     const std::vector<char>* code = nullptr;
-    const kmc_status st = compile_user(ud, false, 0, 0, 0, false, 0, false, 0, false, &code);   // syntax check now, not at first use
+    const kmc_status st = compile_user(ud, UserModuleSpec::syntax_check(false), &code);   // syntax check now, not at first use
     if (st != KMC_OK) { delete ud; return st; }
     *out = ud;
     return KMC_OK;
@@ -497,12 +574,12 @@ KMC_EXPORT kmc_status kmc_user_density_create_body(const char* body, kmc_user_de
     ud->body = body;
     ud->is_body = true;
     const std::vector<char>* code = nullptr;
-    const kmc_status st = compile_user(ud, false, 0, 0, 0, false, 0, false, 0, false, &code, 4);   // syntax check now (any ndim)
+    const kmc_status st = compile_user(ud, UserModuleSpec::syntax_check(true), &code);   // syntax check now (any ndim)
     if (st != KMC_OK) { delete ud; return st; }
     if (recognise_separable(ud)) {
         // the generated functor must compile too (a body the recogniser misread: then it is simply not routed)
         const std::vector<char>* vcode = nullptr;
-        if (compile_user(ud, true, 4, 1, 1, false, 0, false, 0, false, &vcode, 8) != KMC_OK) { ud->sep = false; ud->sep_functor.clear(); }
+        if (compile_user(ud, UserModuleSpec::sum_form_check(), &vcode) != KMC_OK) { ud->sep = false; ud->sep_functor.clear(); }
     }
     *out = ud;
     return KMC_OK;
@@ -522,7 +599,7 @@ KMC_EXPORT kmc_status kmc_user_density_create_body_blob(const char* body, int nb
     ud->is_body = true;
     ud->nblob = nblob;
     const std::vector<char>* code = nullptr;
-    const kmc_status st = compile_user(ud, false, 0, 0, 0, false, 0, false, 0, false, &code, 4);   // syntax check now (any ndim)
+    const kmc_status st = compile_user(ud, UserModuleSpec::syntax_check(true), &code);   // syntax check now (any ndim)
     if (st != KMC_OK) { delete ud; return st; }
     *out = ud;
     return KMC_OK;

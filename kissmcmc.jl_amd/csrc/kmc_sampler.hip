@@ -551,40 +551,35 @@ kmc_status setup_islands(kmc_sampler* s)
     return KMC_OK;
 }
 
-// ---- a runtime-compiled density: what load_user (kmc_rtc.hip) is asked to compile ----
-// `resident_K`, what the resident kernel is compiled as: a term / pair density on short rows -> -ndim = one walker per thread, with two
-// walkers per thread -(100 + ndim); a body density -> the workgroup size bound, 256, 512 or 1024 (a body of 32 dimensions needs its
-// registers), with two walkers per thread 2048; else the two-lane kernel's K.  0: no resident kernel.
-int resident_code(const ResidentChoice& r, bool body, const kmc_config& c)
-{
-    switch (r.kind) {
-    case ResidentChoice::Lane2: return body ? 2048 : -(100 + (int)c.ndim);
-    case ResidentChoice::Lane: return body ? (c.nwalkers <= 256 ? 256 : c.nwalkers <= 512 ? 512 : 1024) : -lane_nd(c.ndim);
-    case ResidentChoice::Pair: return r.K;
-    default: return 0;
-    }
-}
-// `generation_nd`, the kernel of one launch per generation by generation_wanted's kind: ndim -> one walker per lane; -(100 L + K) -> rows
-// lane-striped in the plan's geometry; -401 -> the row over a quad.  0: none.
-int generation_code(int kind, const Plan& p, const kmc_config& c)
-{
-    return kind == 1 ? (int)c.ndim : kind == 2 ? -(100 * p.L + p.K) : kind == 3 ? -401 : 0;
-}
-
+// ---- a runtime-compiled density: what load_user (kmc_rtc.hip) is asked to compile, as a UserModuleSpec ----
+// The vector geometry is the plan's; the resident kernel is the ResidentChoice's kind with what that kind is built from -- Pair: the
+// row chunks K and whether 4 K != ndim; Lane: a term / pair density's short-row length lane_nd(ndim), a body density's workgroup size
+// bound (a body of 32 dimensions needs its registers); Lane2: ndim alone --; in island mode the island size and the same row chunks
+// instead; the kernel of one launch per generation by generation_wanted's kind, for what is neither resident nor in islands.
 // the kernels of the sampler's plan as it stands (again after a re-plan); `r`: the resident choice, none in island mode
 kmc_status load_user_kernels(kmc_sampler* s, const ResidentChoice& r)
 {
+    using Spec = UserModuleSpec;
     const kmc_config& c = s->cfg;
-    const int iS = s->islands ? (int)s->island_size : 0;
-    const int rK = s->islands ? s->island_K : r.K;                     // the pair kernels' chunks (0: neither mode)
-    const int rcode = s->islands ? rK : resident_code(r, s->user->is_body, c);
-    const bool lds_mode = rK != 0 || iS != 0;
+    Spec m;
+    m.vec = s->plan.vec; m.L = s->plan.L; m.K = s->plan.K; m.iter = s->plan.ITER; m.ragged = s->plan.ragged;
+    m.f32 = s->f32; m.ndim = c.ndim; m.p2p = (c.flags & KMC_P2P) != 0; m.move = c.move; m.temper = s->temper;
+    if (s->islands) m.island_S = (int)s->island_size;
+    else m.resident = r.kind == ResidentChoice::Pair ? Spec::Resident::Pair : r.kind == ResidentChoice::Lane ? Spec::Resident::Lane
+                      : r.kind == ResidentChoice::Lane2 ? Spec::Resident::Lane2 : Spec::Resident::None;
+    if (s->islands || m.resident == Spec::Resident::Pair) {
+        m.pair_K = s->islands ? s->island_K : r.K;
+        m.pair_ragged = 4 * m.pair_K != c.ndim;
+    }
+    if (m.resident == Spec::Resident::Lane && s->user->is_body) m.lane_bound = c.nwalkers <= 256 ? 256 : c.nwalkers <= 512 ? 512 : 1024;
+    else if (m.resident == Spec::Resident::Lane) m.lane_nd = lane_nd(c.ndim);
+    const bool lds_mode = s->islands || m.resident != Spec::Resident::None;
+    const int gen = lds_mode ? 0 : generation_wanted(s);
+    m.generation = gen == 1 ? Spec::Generation::Lane : gen == 2 ? Spec::Generation::Striped : gen == 3 ? Spec::Generation::Quad : Spec::Generation::None;
     // a big ensemble's kernels are worth the better compiler (hipcc as a child process: ~1.2 s once per density and geometry, then
     // cached on disk): inside a PyTorch process hiprtc means the older comgr the wheel bundles (kmc_rtc.hip: offline_compiler_wanted)
     set_offline_compiler_hint(s->h_loc >= 8192 && !lds_mode);
-    const kmc_status st = load_user(s->user, s->plan.vec, s->plan.L, s->plan.K, s->plan.ITER, s->plan.ragged, &s->uk, rcode, 4 * rK != c.ndim, iS, s->f32, c.ndim,
-                                    (c.flags & KMC_P2P) != 0, lds_mode ? 0 : generation_code(generation_wanted(s), s->plan, c),
-                                    (int)c.move + (s->temper ? kTemperMoveBase : 0));
+    const kmc_status st = load_user(s->user, m, &s->uk);
     set_offline_compiler_hint(false);
     return st;
 }

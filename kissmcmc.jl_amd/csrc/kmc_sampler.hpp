@@ -18,7 +18,6 @@ constexpr int64_t kDrawTableGens = 1024;   // resident mode with a draw table: g
 constexpr int64_t kGraphChunk = 64;   // generations per hipGraph replay (128 kernel nodes + 1)
 constexpr int kUExec = 6;             // executables of the "updated graph" launch mode (kmc_sampler::uexec)
 constexpr size_t kGuardBytes = 4096;  // KMC_DEBUG=poison: guard band behind every device allocation of a sampler
-constexpr int kTemperMoveBase = 100;  // load_user's `move` of a tempered sampler: this + kmc_config.move (kmc_rtc.hip)
 constexpr int kHostPieces = 8;        // KMC_HOST_DENSITY: most pieces a half-step's proposals travel to the host in
 
 struct Plan {
@@ -36,6 +35,35 @@ struct UserKernels {
     hipFunction_t generation = nullptr; // one launch per generation (kmc_generation.hpp), when the sampler asked for it
     hipFunction_t staged = nullptr;     // body densities, double rows, ndim <= kStagedMaxDim: half_step_staged_body
     hipFunction_t logpdf_sep = nullptr; // a body recognised as a sum over elements: the generated form, row by row (check_sum_form)
+};
+
+// What a sampler wants a runtime-compiled density built as, in the caller's terms: kmc_rtc.hip turns it into the program text
+// (user_program_text) and, with the density's own facts, into the key of the density's code objects (user_module_key).
+struct UserModuleSpec {
+    enum class Resident { None, Pair, Lane, Lane2 };          // ResidentChoice's kinds (kmc_sampler.hip: choose_resident)
+    enum class Generation { None, Lane, Striped, Quad };      // generation_wanted's kinds: one walker per lane (ND = ndim); rows striped in the vector geometry's L, K; the row over a quad
+    bool vec = false;                       // the vector kernel: rows striped over L lanes x K chunks, `iter` walkers per group
+    int L = 0, K = 0, iter = 0;
+    bool ragged = false;
+    Resident resident = Resident::None;
+    int pair_K = 0;                         // Pair, and the island kernel: 16-byte chunks per lane, two lanes per walker
+    bool pair_ragged = false;               //   ... 4 pair_K != ndim
+    int lane_nd = 0;                        // Lane, a term / pair density: the row length the kernel is built for (lane_nd(ndim))
+    int lane_bound = 0;                     // Lane, a body density: the workgroup size bound, 256, 512 or 1024 (a body of 32 dimensions needs its registers)
+    int island_S = 0;                       // walkers per island (KMC_ISLANDS; no resident kernel then), 0: no island kernel
+    bool f32 = false;                       // rows kept in float
+    int64_t ndim = 0;                       // read by a body density's kernels, by Lane2 and by Generation::Lane
+    bool p2p = false;                       // partner rows read from their owners
+    Generation generation = Generation::None;
+    int move = KMC_MOVE_STRETCH;            // kmc_config.move
+    bool temper = false;                    // the tempered form of that move's bodies (the rung as blockIdx.y)
+
+    // no sampler kernel beyond the generic one: what kmc_logpdf_eval and its kin load at their rows' ndim
+    static UserModuleSpec logpdf_only(int64_t ndim) { UserModuleSpec s; s.ndim = ndim; return s; }
+    // ... and what a density is compiled as when it is created, to report a syntax error then (a term / pair density's text reads no ndim)
+    static UserModuleSpec syntax_check(bool body) { return logpdf_only(body ? 4 : 0); }
+    // the generated per-element form of a body recognised as a sum: it must compile too, in some vector geometry
+    static UserModuleSpec sum_form_check() { UserModuleSpec s; s.vec = true; s.L = 4; s.K = 1; s.iter = 1; s.ndim = 8; return s; }
 };
 
 // kernels and device data of a data density (kmc_data.hip), and how one evaluation over `nprop` rows is cut
@@ -280,9 +308,7 @@ kmc_status chain_flush(kmc_sampler* s);                  //   at a synchronisati
 void chain_unregister(kmc_sampler* s);
 
 // kmc_rtc.hip
-kmc_status load_user(kmc_user_density* ud, bool with_vec, int L, int K, int iter, bool ragged, UserKernels* uk,
-                     int resident_K = 0, bool resident_ragged = false, int island_S = 0, bool f32 = false, int64_t ndim = 0, bool p2p = false,
-                     int generation_nd = 0, int move = 0);
+kmc_status load_user(kmc_user_density* ud, const UserModuleSpec& spec, UserKernels* uk);       // compile (cached) + module on the current device + its kernels
 void set_offline_compiler_hint(bool wanted);                          // runtime-compiled kernels of this thread: hipcc as a child process instead of hiprtc (kmc_rtc.hip)
 bool body_vec_possible(const kmc_user_density* ud, int64_t ndim);     // a function body inside the vector kernels, evaluated per walker (kmc_rtc.hip)
 

@@ -807,7 +807,7 @@ KMC_EXPORT kmc_status kmc_logpdf_eval(const kmc_config* cfg, const double* pos_d
     const unsigned grid = (unsigned)((nrows + 255) / 256);
     if (cfg->density == KMC_USER_DENSITY) {
         UserKernels uk;
-        KMC_TRY(load_user(static_cast<kmc_user_density*>(cfg->user_density), false, 0, 0, 0, false, &uk, 0, false, 0, false, cfg->ndim));
+        KMC_TRY(load_user(static_cast<kmc_user_density*>(cfg->user_density), UserModuleSpec::logpdf_only(cfg->ndim), &uk));
         const hipError_t e = launch_module(uk.logpdf, grid, 256u, (hipStream_t)hip_stream, la);
         if (e == hipSuccess) (void)hipStreamSynchronize((hipStream_t)hip_stream);   // (uk's hold on the module ends with this scope)
         HIP_TRY(e);
@@ -882,7 +882,7 @@ KMC_EXPORT kmc_status kmc_logpdf_blob_eval_host(const kmc_config* cfg, const dou
     double* dpos = buf.as<double>();
     double* dlp = dpos + (size_t)nrows * (size_t)cfg->ndim;
     double* dbl = dlp + nrows;
-    KMC_TRY(load_user(const_cast<kmc_user_density*>(ud), false, 0, 0, 0, false, &uk, 0, false, 0, false, cfg->ndim));
+    KMC_TRY(load_user(const_cast<kmc_user_density*>(ud), UserModuleSpec::logpdf_only(cfg->ndim), &uk));
     HIP_TRY(copy_sync(dpos, pos_host, nb, hipMemcpyHostToDevice, ss.st));
     const LogpdfArgs la{dpos, dlp, nrows, (int32_t)cfg->ndim, (int32_t)cfg->ndim, dp, dbl};
     HIP_TRY(launch_module(uk.logpdf, (unsigned)((nrows + 255) / 256), 256u, ss.st, la));

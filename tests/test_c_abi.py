@@ -205,6 +205,33 @@ def test_runtime_compiled_densities_through_the_offline_compiler(kmc, kmc_debug,
     assert len(list(tmp_path.glob("*.co"))) > n_before
 
 
+# what a density sends to the compiler when it is created (no device needed): id -> (constructor, arguments, keywords, sha256 over the
+# program texts sorted by content, how many texts).  Recorded like the digests of tests/test_gpu_user_modules.py, whose rows continue these.
+CREATE_TIME_TEXTS = {
+    "expr": ("ExprDensity", ("d < n-1 ? -((p[0]-x)*(p[0]-x))/p[2] : 0.0", "-(p[1]*((y-x*x)*(y-x*x)))/p[2]"), dict(params=[1.0, 100.0, 20.0]),
+             "f5ce4e12b15db6d987cca889ed7bc82428acb1420de41efe5c2d72902302dd8c", 1),
+    "body": ("CDensity", ("double m = 0.0; for (int i = 0; i < n; ++i) m += x[i]; m = m / n; double s = 0.0; for (int i = 0; i < n; ++i) { double t = x[i] - m; s += t * t; } "
+                          "return -0.5 * s - 0.5 * p[0] * m * m;",), dict(params=[4.0]), "1139d70373f2896b0e09d1e8e78cc50556d5522cdbbc9e786232c9e9bea9460e", 1),
+    "sum_body": ("CDensity", ("double s = 0.0; for (int i = 0; i < n; ++i) { double t = (x[i] - p[0]) * p[1]; s += t * t; } return -0.5 * s;",),
+                 dict(params=[0.0, 1.0]), "99c947f9f8387d6ffa2eb2f7a9fc70455bf7c05c2f5d7a6647b7a20d67dc3e5d", 2),          # the syntax check, then the generated per-element form (`vec, 4, 1, 1` at ndim 8)
+    "blob_body": ("CDensity", ("double s = 0.0; for (int i = 0; i < n; ++i) s += x[i] * x[i]; blob[0] = x[0]; blob[1] = s; return -0.5 * s;",), dict(nblob=2),
+                  "f074c764f9fd18c54937c81a5737e2945ddddcbf3559a213abf3f5ff777196ae", 1),
+}
+
+
+@pytest.mark.parametrize("case", sorted(CREATE_TIME_TEXTS))
+def test_create_time_program_texts_are_the_recorded_ones(kmc, kmc_debug, tmp_path, case):
+    import hashlib
+    ctor, args, kw, want, count = CREATE_TIME_TEXTS[case]
+    kmc_debug.set("rtc-text", str(tmp_path))
+    d = getattr(kmc, ctor)(*args, **kw)
+    assert case != "sum_body" or d.separable
+    texts = sorted(p.read_bytes() for p in tmp_path.iterdir())
+    assert len(texts) == count and all(p.name.endswith("_kmc_user_density.hip") for p in tmp_path.iterdir())
+    got = hashlib.sha256(b"\0".join(texts)).hexdigest()
+    assert got == want, f"{case}: '{got}'"
+
+
 def test_product_never_touches_the_oracle():
     """The product package must not import, link or execute anything under oracle/."""
     pkg = os.path.join(ROOT, "kissmcmc.jl_amd")
