@@ -1104,6 +1104,9 @@ kmc_status  kmc_debug_chain_by_walker(const void* src_host, int is_float, int64_
  * c < nd; needs dst_len >= rows * nd. */
 kmc_status  kmc_debug_rows_compact(const double* src_host, int64_t rows, int64_t ld, int64_t nd, double* dst_host, int64_t dst_len,
                                    int device);
+/* 1 when the library holds the phase-specialised (credit) instance of the lane-striped stretch kernel (double rows of exact size, one GPU)
+ * for a menu density in the geometry L lanes x K chunks, iter walkers per group; else 0.  Needs no GPU. */
+int         kmc_debug_phase_spec(int density, int L, int K, int iter);
 
 #ifdef __cplusplus
 }

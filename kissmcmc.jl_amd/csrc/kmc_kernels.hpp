@@ -52,6 +52,8 @@ struct SchedEntry {
 };
 static_assert(sizeof(SchedEntry) == 32, "schedule_of loads an entry as eight dwords");
 enum : uint32_t { kCount = 1u, kSample = 2u };
+// the phase-specialised instance of the lane-striped half-step kernel (half_step_vec_body)
+enum class Spec { Generic, Credit };
 
 // ring_slots > 0 (KMC_STREAM_CHAIN): the device keeps only a ring of that many sample slots; sample k goes to slot k % ring_slots.
 __host__ __device__ inline SchedEntry make_sched(int64_t gen, int64_t nburnin, int64_t nthin, int64_t nsamples, int64_t ring_slots = 0)
@@ -439,9 +441,18 @@ static __device__ unsigned long long g_probe[2][8192][8];
 // TEMPER (parallel tempering): the rung is blockIdx.y.  The caller has moved f.pos and f.logp to the rung's rows and
 // per-walker block (temper_front); here the draws take the walker word t nwalkers + w, the accept test takes beta_t (one scalar load from
 // the table behind HalfStepArgs::peer_pos[1]) and only rung 0 stores samples and credits moments.
-template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double, Move M = Move::Stretch, bool TEMPER = false>
+// SP (phase-specialised instance): what the host knows about a whole launch, fixed at compile time.  Spec::Credit is the
+// eager form (the step among the preloaded parameters, the schedule entry in the argument struct) on a grid that is exactly full (every walker
+// index of every wave lies inside the launch), for a counted generation of a sampler with moments (a.msum != nullptr) and without chain, chain
+// log-pdf or blobs.  The arithmetic, its order and every store are Spec::Generic's; only the decisions are gone.  The host picks the kernel per
+// replay (kmc_updated.hip: spec_of_chunk).  (A burn-in instance -- nothing counted, sampled or credited -- was built and measured as well: 290
+// static instructions fewer and not a nanosecond faster, so burn-in replays keep the generic kernel; profiles/NOTES.md.)
+template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = double, Move M = Move::Stretch, bool TEMPER = false, Spec SP = Spec::Generic>
 __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const HalfStepArgs& a, const DrawConsts* over = nullptr)
 {
+    constexpr bool kSpec = SP != Spec::Generic;
+    static_assert(!kSpec || (M == Move::Stretch && !P2P && !RAGGED && !TEMPER && sizeof(T) == 8 && ITER <= 2 && BlobTrait<Dens>::n == 0 && RowEvalTrait<Dens>::n == 0),
+                  "phase-specialised instances: the stretch move, one GPU, double rows of exact size, menu densities with a fragment form");
     static_assert(!TEMPER || (!P2P && sizeof(T) == 8 && BlobTrait<Dens>::n == 0), "tempering: one GPU, double rows, no blobs (kmc_validate)");
     const uint32_t rung = TEMPER ? (uint32_t)blockIdx.y : 0u;
     const uint32_t rung_w0 = TEMPER ? rung * (2u * f.nhalf) : 0u;       // added to the walker word of every draw
@@ -505,8 +516,8 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     const int  jq     = j / ITER, js = j - jq * ITER;
     const bool useA   = jq == 0;
     const int  iA     = w0 + (kOwn || jq < Q ? js : 0) * G + g;
-    const bool validA = useA && (iA < nact);
-    const int      iAc = iA < nact ? iA : nact - 1;
+    const bool validA = useA && (kSpec || iA < nact);
+    const int      iAc = kSpec || iA < nact ? iA : nact - 1;
     const int64_t  rowA = own_row0 + iAc;                                // row in pos / index in logp, naccept
     const bool ring_on = kRing && f.ring_now != nullptr;
     double2 e0 = zero2, e1 = zero2;                                     // this launch's parked draws, if any
@@ -522,7 +533,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         const int i = w0 + it * G + g;
-        validB[it] = i < nact;
+        validB[it] = kSpec || i < nact;
         const V2* own = reinterpret_cast<const V2*>(posT + row_off(own_row0 + (validB[it] ? i : nact - 1)));
 #pragma unroll
         for (int k = 0; k < K; ++k) xc[it][k] = load_row(&own[ck[k]]);
@@ -539,7 +550,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     // ---- the step, then Philox: nothing here touches the argument struct.  Eager launch: the step is a preloaded
     //      parameter, so the partner index is known without any memory access; graph replay: one scalar round trip
     //      for the schedule entry (the struct's fields ride the same round trip, see below) -----------------------
-    const bool eager = f.sched == nullptr;
+    const bool eager = kSpec || f.sched == nullptr;
     SchedEntry sch_t{0, 0, 0u, 0u, {0u, 0u}};
     if (!eager) sch_t = schedule_entry(f);
     const uint64_t step = eager ? (uint64_t)f.step : 2ull * (uint64_t)sch_t.gen + (uint64_t)half;
@@ -640,18 +651,24 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
 
     // ---- from here on the argument struct: one scalar round trip for all of it (have every field the kernel
     //      uses later requested by now, otherwise the compiler fetches some lazily: a round trip each) ----------
+    if constexpr (SP == Spec::Generic)
     asm volatile("" :: "s"(a.chain), "s"(a.chain_logp), "s"(a.chain_rows), "s"(a.chain_row0),
                  "s"(a.msum), "s"(a.msumsq), "s"(a.macc_stride), "s"(a.sched_inline.gen), "s"(a.sched_inline.slot),
                  "s"(a.sched_inline.flags), "s"(a.sched_inline.nbefore));
+    else asm volatile("" :: "s"(a.msum), "s"(a.msumsq), "s"(a.macc_stride), "s"(a.sched_inline.nbefore));
     // (the launch kind again, opaque to the optimiser: merged with the branch above it would pull the struct's first
     //  use -- and the wait for it -- in front of Philox)
-    int eager_late = eager ? 1 : 0;
-    asm volatile("" : "+v"(eager_late));
-    eager_late = __builtin_amdgcn_readfirstlane(eager_late);
     SchedEntry sch = sch_t;
-    if (eager_late != 0) sch = a.sched_inline;
-    const bool count  = (sch.flags & kCount) != 0;
-    const bool sample = (sch.flags & kSample) != 0 && (!TEMPER || rung == 0u);      // (the chain is rung 0's)
+    if constexpr (kSpec) {
+        sch.nbefore = a.sched_inline.nbefore;                           // (all a specialised instance reads of the entry)
+    } else {
+        int eager_late = eager ? 1 : 0;
+        asm volatile("" : "+v"(eager_late));
+        eager_late = __builtin_amdgcn_readfirstlane(eager_late);
+        if (eager_late != 0) sch = a.sched_inline;
+    }
+    const bool count  = kSpec || (sch.flags & kCount) != 0;
+    const bool sample = !kSpec && (sch.flags & kSample) != 0 && (!TEMPER || rung == 0u);      // (the chain is rung 0's)
     double beta = 1.0;
     if constexpr (TEMPER) beta = reinterpret_cast<const double*>(a.peer_pos[1])[rung];
     DrawConsts dc = a.dc;                                               // seed and nhalf from the front parameters (DE: gamma0 in c0, sigma in c1)
@@ -660,7 +677,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     // Streaming moments are sojourn-weighted: a walker's value is credited, times the number of
     // samples it stood for, when it is replaced (and by flush_moments_vec at read-out).  Only waves
     // with an accepted move touch their accumulators -- at low acceptance (large ndim) almost none.
-    const bool do_mom = count && a.msum != nullptr && (!TEMPER || rung == 0u);
+    const bool do_mom = kSpec || (count && a.msum != nullptr && (!TEMPER || rung == 0u));
     // small rows: nearly every wave has an accepted move, so fetch its accumulator slots now and
     // keep that latency off the kernel's tail; large rows: fetch only when needed
     constexpr bool kPrefetchAcc = K <= 2 && L != 64;                   // L == 64: the moment ring instead (below)
@@ -725,7 +742,7 @@ __device__ __forceinline__ void half_step_vec_body(const HalfStepFront& f, const
     } else if (!fresh) {
         dr.lu = log_pos_normal(ua);                                     // :260
         if constexpr (kRing) {
-            if (ring_on && jq >= 1 && jq < Q && iA < nact) {            // park the walkers' next steps
+            if (ring_on && jq >= 1 && jq < Q && (kSpec || iA < nact)) { // park the walkers' next steps
                 double2* slot = a.ring + ((int64_t)((a.ring_slot + jq) & 3) * a.ring_rows + rowA) * 2;
                 store_wt(&slot[0], make_double2(dr.t1, dr.lu));
                 store_wt(&slot[1], make_double2(dr.z, __hiloint2double((int)(uint32_t)(step + 2ull * (uint64_t)jq), (int)dr.partner)));
@@ -957,6 +974,12 @@ template <class Dens, int L, int K, int ITER, bool P2P, bool RAGGED, class T = d
 __global__ __launch_bounds__(vec_tpb(L)) void half_step_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)
 {
     half_step_vec_body<Dens, L, K, ITER, P2P, RAGGED, T>(KMC_FRONT_PACK, a);
+}
+// the phase-specialised instance of half_step_vec<Dens, L, K, ITER, false, false, double> (a kernel of its own: the generic kernels keep their names)
+template <class Dens, int L, int K, int ITER, Spec SP>
+__global__ __launch_bounds__(vec_tpb(L)) void half_step_vec_spec(KMC_FRONT_PARAMS, const HalfStepArgs a)
+{
+    half_step_vec_body<Dens, L, K, ITER, false, false, double, Move::Stretch, false, SP>(KMC_FRONT_PACK, a);
 }
 template <class Dens, int L, int K, int ITER, bool RAGGED>
 __global__ __launch_bounds__(vec_tpb(L)) void half_step_de_vec(KMC_FRONT_PARAMS, const HalfStepArgs a)

@@ -741,7 +741,7 @@ kmc_status decide_launch_mode(kmc_sampler* s, LaunchEnv env, bool use_graph, int
     constexpr int64_t kWorthMeasuring = 4096;
     const bool long_job = s->cfg.ngenerations >= kWorthMeasuring || s->generation + *left >= kWorthMeasuring;
     const bool updated_asked = env == LaunchEnv::updated || env == LaunchEnv::updated_budget;
-    if (use_graph && s->launch_mode == 0 && s->user && updated_graph_possible(s) && !s->uexec[0] && (updated_asked || (long_job && *left >= calib_min(s)))) {
+    if (use_graph && s->launch_mode == 0 && s->user && updated_graph_possible(s) && !s->uexec[0][0] && (updated_asked || (long_job && *left >= calib_min(s)))) {
         // module functions as graph kernel nodes: build the graph now; a runtime that refuses leaves this sampler with the table graph
         if (ensure_updated_graph(s) != KMC_OK) {
             (void)hipGetLastError();

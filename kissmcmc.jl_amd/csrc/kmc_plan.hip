@@ -49,6 +49,12 @@ bool lookup_temper(int move, int density, int L, int K, int iter, bool ragged, H
     });
 }
 
+// the phase-specialised instance of PART 0's vector kernel for this geometry (kmc_tables.hpp: spec_part)
+HalfStepFn lookup_spec(int density, int L, int K, int iter)
+{
+    return with_density(density, HalfStepFn(nullptr), [&](auto d) { return spec_part<decltype(d)>(L, K, iter); });
+}
+
 LogpdfFn logpdf_fn(int density)
 {
     return with_density(density, LogpdfFn(nullptr), [](auto d) { return logpdf_lookup<decltype(d)>(); });
@@ -193,6 +199,8 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     else lookup(c.density, L, K, iter, (c.flags & KMC_P2P) != 0, ragged, f32, &vec, &gen);
     if (!force_generic && L > 0 && 2 * L * K >= c.ndim && vec != nullptr) {
         p.fn = vec; p.vec = true; p.L = L; p.K = K; p.ITER = iter;
+        // the stretch move on one GPU, double rows of exact size, one or two walkers per group: PART 0's kernel has a phase-specialised instance
+        if (!tempered(c) && !de && !(c.flags & KMC_P2P) && !ragged && !f32 && iter <= 2) p.fn_credit = lookup_spec(c.density, L, K, iter);
     } else {
         p.fn = gen; p.vec = false; p.L = 1; p.K = 1; p.ITER = 1;
     }
@@ -247,4 +255,9 @@ kmc_status kmc_host::digest_params(const kmc_config& c, DensityParams* dp)
     default:
         return fail(KMC_ERR_BAD_ARG, "unknown density id");
     }
+}
+
+KMC_EXPORT int kmc_debug_phase_spec(int density, int L, int K, int iter)
+{
+    return kmc_host::lookup_spec(density, L, K, iter) != nullptr ? 1 : 0;
 }

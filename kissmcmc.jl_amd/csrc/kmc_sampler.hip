@@ -1133,6 +1133,11 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
         o << "multi-launch (exact): half_step_vec L=" << s->plan.L << " K=" << s->plan.K << " ITER=" << s->plan.ITER
           << (s->plan.ragged ? " ragged" : " exact-size") << ", grid " << s->grid << " x " << s->tpb
           << launch_mode_text(s, "step");
+        if (s->launch_mode == 3 && !(s->cfg.flags & KMC_NO_GRAPH)) {      // which kernel variant a replay's nodes run (kmc_updated.hip: spec_of_chunk)
+            const char* why = nullptr;
+            if (spec_variant_possible(s, kVarCredit, &why)) o << "; phase-specialised kernel instance in counted replays";
+            else o << "; generic kernel in every phase (" << why << ")";
+        }
     } else
         o << "multi-launch (exact): " << (s->user && s->uk.staged ? "half_step_staged (one walker per lane, rows staged through LDS)" : "half_step_generic (one walker per lane)")
           << ", grid " << s->grid << " x " << s->tpb;

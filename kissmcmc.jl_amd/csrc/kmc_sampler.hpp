@@ -16,12 +16,14 @@ namespace kmc_host {
 static_assert(1024 % kmc::kDrawBatch == 0, "the draw table holds whole batches");
 constexpr int64_t kDrawTableGens = 1024;   // resident mode with a draw table: generations per launch (table = 32 B x nwalkers x this)
 constexpr int64_t kGraphChunk = 64;   // generations per hipGraph replay (128 kernel nodes + 1)
-constexpr int kUExec = 6;             // executables of the "updated graph" launch mode (kmc_sampler::uexec)
+constexpr int kUExec = 6;             // executables of the "updated graph" launch mode (kmc_sampler::uexec), per kernel variant
+enum : int { kVarGeneric = 0, kVarCredit = 1, kUVariants = 2 };     // the kernel behind an updated graph's nodes (kmc_kernels.hpp: Spec)
 constexpr size_t kGuardBytes = 4096;  // KMC_DEBUG=poison: guard band behind every device allocation of a sampler
 constexpr int kHostPieces = 8;        // KMC_HOST_DENSITY: most pieces a half-step's proposals travel to the host in
 
 struct Plan {
     kmc::HalfStepFn fn = nullptr;
+    kmc::HalfStepFn fn_credit = nullptr;      // the phase-specialised instance of fn (kmc_kernels.hpp: Spec::Credit), nullptr where there is none
     bool vec = false;
     bool ragged = false;
     int L = 1, K = 1, ITER = 1;
@@ -155,12 +157,14 @@ struct kmc_sampler {
     // take turns, so the host updates up to kUExec - 1 replays ahead of the one that is running (two were enough for
     // a quiet host -- the update of 128 nodes takes about as long as their replay -- but left a single replay of
     // slack: one scheduling hiccup of the host process starved the GPU, 4.27 instead of 3.8 us per launch in one run)
-    hipGraph_t ugraph = nullptr;
-    hipGraphExec_t uexec[kmc_host::kUExec] = {};
+    // One graph and its executables per kernel variant (generic; the credit instance where the sampler can use it: spec_variant_possible):
+    // a replay takes the variant all of its generations qualify for (spec_of_chunk), in the one ring of kUExec turns.
+    hipGraph_t ugraph[kmc_host::kUVariants] = {};
+    hipGraphExec_t uexec[kmc_host::kUVariants][kmc_host::kUExec] = {};
     hipEvent_t udone[kmc_host::kUExec] = {};
     bool uinflight[kmc_host::kUExec] = {};
     int unext = 0;
-    std::vector<hipGraphNode_t> unodes;
+    std::vector<hipGraphNode_t> unodes[kmc_host::kUVariants];
     int64_t uchunk = 128;     // generations per replay of the updated graph (consecutive replays are ~10 us apart on the GPU: 64 -> 128 is 1-3 % of a launch-bound period; profiles/NOTES.md round 5)
     bool updated_forced = false;   // KMC_LAUNCH=updated: no budget
     int64_t feed_wait_ns = 0, feed_update_ns = 0, feed_launch_ns = 0, feed_replays = 0;   // updated-graph mode: the feeding thread's time per phase
@@ -293,6 +297,8 @@ kmc::GenerationFront generation_front_of(const kmc::GenerationArgs& a, int tpb);
 
 // kmc_updated.hip
 bool updated_graph_possible(const kmc_sampler* s);
+bool spec_variant_possible(const kmc_sampler* s, int variant, const char** why_not = nullptr);   // may a replay of this sampler ever run that kernel variant?
+int spec_of_chunk(const kmc_sampler* s, int64_t g0, int64_t n);                                  // the variant for generations [g0, g0 + n)
 kmc_status ensure_updated_graph(kmc_sampler* s);         // the template graph and its executables (no-op when they exist)
 kmc_status launch_updated_graph(kmc_sampler* s, bool* launched);   // one replay of s->uchunk generations from s->generation on
 void drop_updated_graph(kmc_sampler* s);                 // the executables, their events and the template graph

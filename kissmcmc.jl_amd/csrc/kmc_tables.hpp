@@ -11,6 +11,7 @@
 //   kmc_inst_<density>_temper.hip          temper_part: the tempered kernels (parallel tempering, the rung as blockIdx.y) of the stretch and DE moves
 //   kmc_inst_<density>_temper_snooker.hip  temper_part of the snooker move and the mixtures (exact and ragged double rows, one GPU, like PART 3 .. 5)
 //   kmc_inst_host_temper*.hip    temper_part of the host-evaluated density: likelihood tempering of a data density (generic kernels only)
+//   kmc_inst_<density>_spec.hip  spec_part: the phase-specialised instance (Spec::Credit) of PART 0's vector kernels, planner geometries with ITER <= 2
 //   kmc_inst_<density>_lds.hip   the LDS-resident (islands, resident mode), one-launch-per-generation and many-chain Metropolis kernels
 // Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_move).
 #pragma once
@@ -34,6 +35,8 @@ using MetropolisTabledFn = void (*)(const MetropolisArgs, const double*, int);
 // (the part's vector kernel for this geometry or nullptr, its generic kernel)
 template <class D, int PART> void density_part(int L, int K, int iter, bool ragged, bool f32, HalfStepFn* vec, HalfStepFn* gen);
 template <class D, Move M> void temper_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen);
+// (the credit instance of half_step_vec<D, L, K, iter, false, false, double>, nullptr where there is none)
+template <class D> HalfStepFn spec_part(int L, int K, int iter);
 template <class D> LogpdfFn logpdf_lookup();
 template <class D> InitBallFn init_ball_lookup();
 template <class D> IslandFn island_lookup(int S, int K, bool ragged);
@@ -153,6 +156,25 @@ void temper_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepF
         KMC_LK(64, 4) KMC_LK(64, 8)
 #undef KMC_LK
     }
+}
+
+// the phase-specialised instance: the geometries make_plan picks by itself, one or two walkers per group
+template <class D, int L, int K, int ITER>
+HalfStepFn spec_one()
+{
+    if constexpr (ITER <= L && ITER * K <= 16) return half_step_vec_spec<D, L, K, ITER, Spec::Credit>;
+    else return nullptr;
+}
+template <class D>
+HalfStepFn spec_part(int L, int K, int iter)
+{
+    if constexpr (D::kHasFrag && BlobTrait<D>::n == 0 && RowEvalTrait<D>::n == 0) {
+#define KMC_LK(l, k) if (L == l && K == k) return iter == 1 ? spec_one<D, l, k, 1>() : iter == 2 ? spec_one<D, l, k, 2>() : nullptr;
+        KMC_LK(1, 1) KMC_LK(2, 1) KMC_LK(4, 1) KMC_LK(4, 2) KMC_LK(8, 2) KMC_LK(16, 2) KMC_LK(32, 2) KMC_LK(64, 2)
+        KMC_LK(64, 4) KMC_LK(64, 8)
+#undef KMC_LK
+    }
+    return nullptr;
 }
 
 template <class D>
@@ -306,6 +328,7 @@ MetropolisTabledFn metropolis_tabled_lookup(int ndim)
 // the explicit instantiations of one translation unit of density D (see the top of this file)
 #define KMC_INSTANTIATE_PART(D, PART) template void density_part<D, PART>(int, int, int, bool, bool, HalfStepFn*, HalfStepFn*)
 #define KMC_INSTANTIATE_TEMPER(D, M) template void temper_part<D, M>(int, int, int, bool, HalfStepFn*, HalfStepFn*)
+#define KMC_INSTANTIATE_SPEC(D) template HalfStepFn spec_part<D>(int, int, int)
 #define KMC_INSTANTIATE_ROWS(D) \
     template LogpdfFn logpdf_lookup<D>(); \
     template InitBallFn init_ball_lookup<D>()

@@ -33,7 +33,13 @@ struct ParamPack {
     }
 };
 
-hipKernelNodeParams node_params(const kmc_sampler* s, ParamPack* pk)
+// the kernel behind the nodes of a variant's graph (half-step kernels of a menu density; everything else has the generic variant only)
+HalfStepFn variant_fn(const kmc_sampler* s, int variant)
+{
+    return variant == kVarCredit ? s->plan.fn_credit : s->plan.fn;
+}
+
+hipKernelNodeParams node_params(const kmc_sampler* s, int variant, ParamPack* pk)
 {
     hipKernelNodeParams np{};
     if (s->fused) {
@@ -44,7 +50,7 @@ hipKernelNodeParams node_params(const kmc_sampler* s, ParamPack* pk)
     } else {
         // (a runtime-compiled density's lane-striped kernel is a module function: the runtime accepts its hipFunction_t as the node's
         //  function -- ensure_updated_graph tries it once and the sampler stays with the table graph if it does not)
-        np.func = s->user ? reinterpret_cast<void*>(s->uk.vec) : reinterpret_cast<void*>(s->plan.fn);
+        np.func = s->user ? reinterpret_cast<void*>(s->uk.vec) : reinterpret_cast<void*>(variant_fn(s, variant));
         np.gridDim = dim3((unsigned)s->grid);
         np.blockDim = dim3((unsigned)s->tpb);
         np.sharedMemBytes = s->user ? s->vec_lds : 0u;
@@ -58,7 +64,7 @@ hipKernelNodeParams node_params(const kmc_sampler* s, ParamPack* pk)
 // runs one launch per generation has one node per generation, reading copy g & 1 of the state and writing the other (uchunk is even: a replay
 // ends in the copy it started from); otherwise a generation is its two half-steps.
 template <class Visit>
-kmc_status for_each_node(const kmc_sampler* s, int64_t g0, Visit&& visit)
+kmc_status for_each_node(const kmc_sampler* s, int variant, int64_t g0, Visit&& visit)
 {
     ParamPack pk(s->fused);
     const int64_t per_gen = launches_per_generation(s);
@@ -71,7 +77,7 @@ kmc_status for_each_node(const kmc_sampler* s, int64_t g0, Visit&& visit)
             pk.ha = make_args(s, (int)(k & 1), false, g0 + g);
             pk.hf = front_of(pk.ha, s->ragged_vec());
         }
-        KMC_TRY(visit(k, node_params(s, &pk)));
+        KMC_TRY(visit(k, node_params(s, variant, &pk)));
     }
     return KMC_OK;
 }
@@ -80,12 +86,41 @@ kmc_status for_each_node(const kmc_sampler* s, int64_t g0, Visit&& visit)
 void drop_updated_graph(kmc_sampler* s)
 {
     for (int i = 0; i < kUExec; ++i) {
-        if (s->uexec[i]) { (void)hipGraphExecDestroy(s->uexec[i]); s->uexec[i] = nullptr; }
+        for (int v = 0; v < kUVariants; ++v)
+            if (s->uexec[v][i]) { (void)hipGraphExecDestroy(s->uexec[v][i]); s->uexec[v][i] = nullptr; }
         if (s->udone[i]) { (void)hipEventDestroy(s->udone[i]); s->udone[i] = nullptr; }      // (ensure_updated_graph creates them anew)
         s->uinflight[i] = false;
     }
     s->unext = 0;
-    if (s->ugraph) { (void)hipGraphDestroy(s->ugraph); s->ugraph = nullptr; }
+    for (int v = 0; v < kUVariants; ++v)
+        if (s->ugraph[v]) { (void)hipGraphDestroy(s->ugraph[v]); s->ugraph[v] = nullptr; }
+}
+
+// The phase-specialised instance (kmc_kernels.hpp: Spec::Credit) serves the two-launch vector route of a menu density whose grid is exactly full, with
+// streaming moments and nothing stored per sample.  KMC_DEBUG=spec=0: the generic kernel everywhere (A/B runs, tests).
+bool spec_variant_possible(const kmc_sampler* s, int variant, const char** why_not)
+{
+    const char* why = nullptr;
+    std::string v;
+    const int64_t per_wg = (int64_t)(s->tpb / 64) * (64 / s->plan.L) * s->plan.ITER;
+    if (variant == kVarGeneric) return true;
+    if (debug_opt("spec", &v) && v == "0") why = "KMC_DEBUG=spec=0";
+    else if (s->user || s->fused || s->host_eval || !s->plan.vec) why = "not the two-launch vector route of a menu density";
+    else if (variant_fn(s, variant) == nullptr) why = "no instance for this move, row type or geometry";
+    else if (s->h_loc != (int64_t)s->grid * per_wg) why = "grid not full";
+    else if (variant == kVarCredit && !s->d_msum) why = "moments off";
+    else if (variant == kVarCredit && (s->d_chain || s->d_chain_logp || s->d_chain_blob)) why = "chain on";
+    if (why_not) *why_not = why;
+    return why == nullptr;
+}
+
+// A replay runs the specialised variant only when every generation of it qualifies: all of them counted.  (Burn-in replays and the one that
+// straddles nburnin run the generic kernel.)
+int spec_of_chunk(const kmc_sampler* s, int64_t g0, int64_t n)
+{
+    (void)n;
+    if (g0 >= s->cfg.nburnin) return spec_variant_possible(s, kVarCredit) ? kVarCredit : kVarGeneric;
+    return kVarGeneric;
 }
 
 bool updated_graph_possible(const kmc_sampler* s)
@@ -98,21 +133,23 @@ bool updated_graph_possible(const kmc_sampler* s)
 
 kmc_status ensure_updated_graph(kmc_sampler* s)
 {
-    if (s->uexec[0]) return KMC_OK;
-    HIP_TRY(hipGraphCreate(&s->ugraph, 0));
-    s->unodes.assign((size_t)(launches_per_generation(s) * s->uchunk), nullptr);
-    hipGraphNode_t prev = nullptr;
-    KMC_TRY(for_each_node(s, 0, [&](int64_t k, const hipKernelNodeParams& np) -> kmc_status {
-        hipGraphNode_t node = nullptr;
-        HIP_TRY(hipGraphAddKernelNode(&node, s->ugraph, prev ? &prev : nullptr, prev ? 1 : 0, &np));
-        s->unodes[(size_t)k] = node;
-        prev = node;
-        return KMC_OK;
-    }));
-    for (int i = 0; i < kUExec; ++i) {
-        HIP_TRY(hipGraphInstantiate(&s->uexec[i], s->ugraph, nullptr, nullptr, 0));
-        HIP_TRY(hipEventCreateWithFlags(&s->udone[i], hipEventDisableTiming));
+    if (s->uexec[kVarGeneric][0]) return KMC_OK;
+    // every variant this sampler can need, now: instantiating one at its first use would fall into a run's steady state
+    for (int v = 0; v < kUVariants; ++v) {
+        if (!spec_variant_possible(s, v)) continue;
+        HIP_TRY(hipGraphCreate(&s->ugraph[v], 0));
+        s->unodes[v].assign((size_t)(launches_per_generation(s) * s->uchunk), nullptr);
+        hipGraphNode_t prev = nullptr;
+        KMC_TRY(for_each_node(s, v, 0, [&](int64_t k, const hipKernelNodeParams& np) -> kmc_status {
+            hipGraphNode_t node = nullptr;
+            HIP_TRY(hipGraphAddKernelNode(&node, s->ugraph[v], prev ? &prev : nullptr, prev ? 1 : 0, &np));
+            s->unodes[v][(size_t)k] = node;
+            prev = node;
+            return KMC_OK;
+        }));
+        for (int i = 0; i < kUExec; ++i) HIP_TRY(hipGraphInstantiate(&s->uexec[v][i], s->ugraph[v], nullptr, nullptr, 0));
     }
+    for (int i = 0; i < kUExec; ++i) HIP_TRY(hipEventCreateWithFlags(&s->udone[i], hipEventDisableTiming));
     return KMC_OK;
 }
 
@@ -166,15 +203,18 @@ kmc_status launch_updated_graph(kmc_sampler* s, bool* launched)
     KMC_TRY(ensure_updated_graph(s));
     g_update_calls.fetch_add(launches_per_generation(s) * s->uchunk, std::memory_order_relaxed);
     const int i = s->unext;
+    // (slot i's event covers whichever variant took that turn; a variant's executable i last ran in an earlier turn of slot i: done as well)
+    int v = spec_of_chunk(s, s->generation, s->uchunk);
+    if (!s->uexec[v][i]) v = kVarGeneric;                   // (KMC_DEBUG=spec changed after the graphs were built)
     const auto t_wait0 = std::chrono::steady_clock::now();
     if (s->uinflight[i]) { HIP_TRY(hipEventSynchronize(s->udone[i])); s->uinflight[i] = false; }
     const auto t_upd0 = std::chrono::steady_clock::now();
-    KMC_TRY(for_each_node(s, s->generation, [&](int64_t k, const hipKernelNodeParams& np) -> kmc_status {
-        HIP_TRY(hipGraphExecKernelNodeSetParams(s->uexec[i], s->unodes[(size_t)k], &np));
+    KMC_TRY(for_each_node(s, v, s->generation, [&](int64_t k, const hipKernelNodeParams& np) -> kmc_status {
+        HIP_TRY(hipGraphExecKernelNodeSetParams(s->uexec[v][i], s->unodes[v][(size_t)k], &np));
         return KMC_OK;
     }));
     const auto t_upd1 = std::chrono::steady_clock::now();
-    HIP_TRY(hipGraphLaunch(s->uexec[i], s->stream));
+    HIP_TRY(hipGraphLaunch(s->uexec[v][i], s->stream));
     const auto t_launch1 = std::chrono::steady_clock::now();
     // where the feeding thread's time goes (kmc_sampler_describe with KMC_DEBUG=feed-stats): waiting for a free executable = the GPU is
     // the bottleneck; updating + launching = the host's own cost per replay, which must stay below the replay's GPU time

@@ -74,7 +74,8 @@ def main():
                                               "period_us_hip_events_probe_build": ms / 1024 * 1e3, "wave_duration_median_us": float(np.median(t[0, :, 7] - t[0, :, 0]))}))
             s.close()
             continue
-        rc = (L.kmc_probe_read_rosenbrock if name == 'C3' else L.kmc_probe_read_var if name[0] == 'R' else L.kmc_probe_read)(buf.ctypes.data_as(ctypes.c_void_p))
+        spec = name == 'C2' and "phase-specialised kernel instance in counted replays" in how      # (counted replays ran the credit instance: its stamps are its own unit's)
+        rc = (L.kmc_probe_read_spec if spec else L.kmc_probe_read_rosenbrock if name == 'C3' else L.kmc_probe_read_var if name[0] == 'R' else L.kmc_probe_read)(buf.ctypes.data_as(ctypes.c_void_p))
         assert rc == 0
         print(f"== {name} moments={int(mom)} KMC_LAUNCH={os.environ.get('KMC_LAUNCH', 'auto')}: {how}  {ms / 2048 * 1e3:.2f} us per half-step launch")
         nwave = int((buf[0, :, 0] != 0).sum())
