@@ -1051,7 +1051,8 @@ kmc_status  kmc_waic_stats(int64_t J, int64_t n, const double* stats, double* lp
  * log1p evaluations of the fit, the nanoseconds of the two statistics passes, and the runs.
  * Refusals: those of kmc_sampler_pointwise_stats, and KMC_ERR_BAD_ARG, naming the value, for r_eff not finite or <= 0, n < 5, obs_count
  * < 1 or a range outside [0, J); KMC_ERR_UNSUPPORTED for n >= 2^31 and for M > 4096, naming n / r_eff (the tail of one observation is
- * sorted in one workgroup's LDS): never a partial answer.  Not built: a per-observation r_eff, r_eff from the chain, moment matching. */
+ * sorted in one workgroup's LDS): never a partial answer.  A per-observation r_eff, supplied or computed from the chain: the *_reff forms below.  Not built: ArviZ's
+ * one r_eff from the parameters' ESS, mcse_elpd_loo, moment matching. */
 kmc_status  kmc_sampler_psis_loo(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int64_t thin,
                                  double r_eff, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes, double* stats, double* lppd_j,
                                  int64_t* n_out, int64_t* info);
@@ -1082,6 +1083,81 @@ kmc_status  kmc_loo_stats(int64_t J, int64_t n, const double* stats, const doubl
  * sum_i exp(s_i), sum_i exp(s_i - x_(i)) (k_hat, sigma, sums may be NULL).  KMC_ERR_BAD_ARG, naming the value, for nt outside
  * 0 .. 4096 or a tail that is not ascending within (xc, 0]. */
 kmc_status  kmc_psis_smooth_host(int64_t nt, const double* x, double xc, double* k_hat, double* sigma, double* s, double* sums);
+
+/* ---- PSIS-LOO's relative efficiency, per observation, from the chain ----
+ * The tail length of step 2 wants r_eff = ESS / n of the importance weights.  For observation j that series is the likelihood
+ * exp(l[r][j]) over the selected rows; the library takes
+ *     v[k][j] = exp(l[k][j] - M_j),   M_j = max_r l[r][j] exactly (pass 1 of the block above),
+ * in the library's row order (sample by sample, selected walkers ascending), and defines
+ *     r_eff_j = ess_j / (m h)
+ * with ess, m and h exactly those of the convergence contract (kmc_sampler_convergence) on the series v[.][.][j] read as `nsel` chains
+ * of n / nsel samples: split (default on) halves each chain (an odd count leaves the middle sample out), max_lag 0 means
+ * min(h - 1, 1024).  The effective sample size is invariant under a scale, so this is loo's relative_eff(exp(log_lik)) under the
+ * library's BDA3 estimator; the shift by M_j only keeps exp in range.  r_eff_j is NaN where ess is NaN (a constant column, or a NaN
+ * in the column) and may exceed 1.  For ensemble chains it is usually well below 1.
+ *
+ * IEEE rules of v: a column whose M_j is NaN or -inf is all NaN; l = -inf under a finite M_j gives 0.0; the arg-max rows give exactly
+ * 1.0.  Elsewhere v is the device's exp of the rounded difference.
+ *
+ * The device stage.  v is written in groups of 64 observations aligned to the absolute index (group g: observations [64 g, 64 g + 64),
+ * laid out [n][64]), as many groups at a time as workspace_bytes holds (0: 1 GiB; at least one), and each group goes through the
+ * convergence kernels as a chain of ld = 64 where it lies.  With ld = 64 every lane of the lag kernel owns one column, and the grid
+ * depends on the shape of the selection alone: the bits of an observation's outputs depend neither on the range asked for, nor on
+ * the other observations, nor on workspace_bytes, and equal kmc_chain_convergence on the group's v padded to 64 columns.
+ *
+ * r_eff_j, ess_j, T_j (the lag the rule stopped at), flags_j (KMC_CONV_TRUNCATED): each [obs_count] or NULL, but r_eff_j.  info (may
+ * be NULL) gets 6 numbers: n, the groups, the nanoseconds of pass 1, of the weight passes and of the ESS stage (chain moments, lag
+ * blocks and their copies, per group), and h.  Refusals: those of kmc_sampler_pointwise_loglike and of kmc_sampler_convergence (h < 4,
+ * m < 2, max_lag outside [3, h - 1]) in their words, from the sizes, before the device is touched where the sizes suffice; and
+ * KMC_ERR_UNSUPPORTED, with the byte count, when one group of 64 n doubles does not fit the device's free memory. */
+kmc_status  kmc_sampler_relative_eff(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int64_t thin,
+                                     int64_t obs_first, int64_t obs_count, int32_t split, int64_t max_lag, int64_t workspace_bytes,
+                                     double* r_eff_j, double* ess_j, int64_t* T_j, int32_t* flags_j, int64_t* m_out, int64_t* h_out, int64_t* n_out,
+                                     int64_t* info);
+kmc_status  kmc_chain_relative_eff(kmc_user_density* density, const double* params, const double* chain_host /* [nsamples][nwalkers][ndim] */,
+                                   int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                   int64_t obs_first, int64_t obs_count, int32_t split, int64_t max_lag, int64_t workspace_bytes, int device,
+                                   double* r_eff_j, double* ess_j, int64_t* T_j, int32_t* flags_j, int64_t* m_out, int64_t* h_out, int64_t* n_out,
+                                   int64_t* info);
+/* The series itself, read out: v [n][obs_count] dense and M_j [obs_count] (may be NULL), for the observations (the density's own, or
+ * the held-out `data`) [obs_first, obs_first + obs_count).  The refusals of kmc_sampler_pointwise_loglike. */
+kmc_status  kmc_sampler_pointwise_weights(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* data,
+                                          int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, double* v, double* M_j,
+                                          int64_t* n_out);
+kmc_status  kmc_chain_pointwise_weights(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                        int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                        const double* data, int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, int device,
+                                        double* v, double* M_j, int64_t* n_out);
+/* PSIS-LOO with a tail length per observation: kmc_*_psis_loo and kmc_*_psis_tail with r_eff_j [obs_count] in place of the one r_eff,
+ * or NULL to compute it from the chain as above with `split` and `max_lag`.  M_j = ceil(min(0.2 n, 3 sqrt(n / r))) with r = r_eff_j
+ * where that is finite and > 0 and 1.0 elsewhere (a computed NaN; counted in n_reff_nan).  Step 2 uses M_j for observation j; nothing
+ * else changes, so r_eff_j all equal to r returns the bits of the scalar call with r, and NULL returns the bits of the call with the
+ * computed r_eff_j (NaN replaced by 1) supplied.  r_eff_used [obs_count]: as computed (NaN kept) or as supplied; tail_len_j
+ * [obs_count]: M_j; n_reff_nan; each may be NULL.  info as kmc_sampler_psis_loo with info[1] = max_j M_j and four more numbers, 16 in
+ * all: the nanoseconds of the weight passes and of the ESS stage, the groups, n_reff_nan.  For the tails, tail_len holds the columns of
+ * `tail` on entry and max_j M_j on return, the length of its rows then (KMC_ERR_BAD_ARG when it is less; min(4096, ceil(0.2 n))
+ * always suffices).
+ * Refusals besides those of the scalar calls and of kmc_sampler_relative_eff: KMC_ERR_BAD_ARG, naming the index, for a supplied entry
+ * that is not finite and > 0, before the device is touched; KMC_ERR_UNSUPPORTED for max_j M_j > 4096, naming the observation and its
+ * r_eff_j (thin the chain): with r_eff = 0.1, n = 200 000 already asks for 4 243. */
+kmc_status  kmc_sampler_psis_loo_reff(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                      const double* r_eff_j /* [obs_count] or NULL */, int32_t split, int64_t max_lag, int64_t obs_first,
+                                      int64_t obs_count, int64_t workspace_bytes, double* stats, double* lppd_j, double* r_eff_used,
+                                      int64_t* tail_len_j, int64_t* n_reff_nan, int64_t* n_out, int64_t* info);
+kmc_status  kmc_chain_psis_loo_reff(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples, int64_t nwalkers,
+                                    int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* r_eff_j,
+                                    int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes, int device,
+                                    double* stats, double* lppd_j, double* r_eff_used, int64_t* tail_len_j, int64_t* n_reff_nan, int64_t* n_out,
+                                    int64_t* info);
+kmc_status  kmc_sampler_psis_tail_reff(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* r_eff_j,
+                                       int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes, double* tail,
+                                       double* m_j, double* xc_j, int32_t* n_tail_j, int64_t* tail_len, double* r_eff_used, int64_t* tail_len_j,
+                                       int64_t* n_reff_nan, int64_t* n_out);
+kmc_status  kmc_chain_psis_tail_reff(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples, int64_t nwalkers,
+                                     int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* r_eff_j,
+                                     int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes, int device,
+                                     double* tail, double* m_j, double* xc_j, int32_t* n_tail_j, int64_t* tail_len, double* r_eff_used,
+                                     int64_t* tail_len_j, int64_t* n_reff_nan, int64_t* n_out);
 
 /* ---- diagnostics ----
  * The random side of the accept test of reference src/samplers.jl:260, "(N-1)*log(z) + p1 - p0 >= log(rand())", exactly as

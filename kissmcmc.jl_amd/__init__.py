@@ -16,7 +16,7 @@ from .chain_convergence import convergence, convergence_stats, error_of_estimate
 from .chain_convergence import normal_scores, rank_convergence, rank_plan, rank_scores
 from .chain_covariance import correlation, cov_plan, covariance
 from .chain_predictive import compare_waic, pointwise_loglike, pointwise_plan, pointwise_stats, waic, waic_stats
-from .chain_loo import compare_loo, loo, loo_stats, psis_plan, psis_smooth, psis_tail
+from .chain_loo import compare_loo, loo, loo_stats, pointwise_weights, psis_plan, psis_smooth, psis_tail, relative_eff
 from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
@@ -33,7 +33,7 @@ __all__ = [
     "rank_convergence", "rank_scores", "rank_plan", "normal_scores",
     "covariance", "correlation", "cov_plan",
     "waic", "pointwise_loglike", "pointwise_stats", "compare_waic", "waic_stats", "pointwise_plan",
-    "loo", "compare_loo", "psis_plan", "loo_stats", "psis_smooth", "psis_tail",
+    "loo", "compare_loo", "psis_plan", "loo_stats", "psis_smooth", "psis_tail", "relative_eff", "pointwise_weights",
 ]
 
 

@@ -69,6 +69,8 @@ SYMBOLS = [
     "kmc_pointwise_plan", "kmc_waic_stats",
     "kmc_sampler_psis_loo", "kmc_chain_psis_loo", "kmc_sampler_psis_tail", "kmc_chain_psis_tail", "kmc_psis_plan", "kmc_loo_stats",
     "kmc_psis_smooth_host",
+    "kmc_sampler_relative_eff", "kmc_chain_relative_eff", "kmc_sampler_pointwise_weights", "kmc_chain_pointwise_weights",
+    "kmc_sampler_psis_loo_reff", "kmc_chain_psis_loo_reff", "kmc_sampler_psis_tail_reff", "kmc_chain_psis_tail_reff",
 ]
 
 
@@ -318,6 +320,16 @@ def lib() -> C.CDLL:
     L.kmc_psis_plan.argtypes = [C.c_int64, C.c_int64, C.c_double, C.c_int64, ip, ip, ip, ip]
     L.kmc_loo_stats.argtypes = [C.c_int64, C.c_int64, dp, dp, dp, dp]
     L.kmc_psis_smooth_host.argtypes = [C.c_int64, dp, C.c_double, dp, dp, dp, dp]
+    reff_sel = [C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int64]   # obs_first, obs_count, split, max_lag, workspace_bytes
+    L.kmc_sampler_relative_eff.argtypes = [vp, C.c_int64, bp, C.c_int64] + reff_sel + [dp, dp, ip, i32p, ip, ip, ip, ip]
+    L.kmc_chain_relative_eff.argtypes = host_chain + reff_sel + [C.c_int, dp, dp, ip, i32p, ip, ip, ip, ip]
+    L.kmc_sampler_pointwise_weights.argtypes = [vp, C.c_int64, bp, C.c_int64] + held_out + [C.c_int64, C.c_int64, dp, dp, ip]
+    L.kmc_chain_pointwise_weights.argtypes = host_chain + held_out + [C.c_int64, C.c_int64, C.c_int, dp, dp, ip]
+    psis_reff = [dp, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64]   # r_eff_j, split, max_lag, obs_first, obs_count, workspace_bytes
+    L.kmc_sampler_psis_loo_reff.argtypes = [vp, C.c_int64, bp, C.c_int64] + psis_reff + [dp, dp, dp, ip, ip, ip, ip]
+    L.kmc_chain_psis_loo_reff.argtypes = host_chain + psis_reff + [C.c_int, dp, dp, dp, ip, ip, ip, ip]
+    L.kmc_sampler_psis_tail_reff.argtypes = [vp, C.c_int64, bp, C.c_int64] + psis_reff + [dp, dp, dp, i32p, ip, dp, ip, ip, ip]
+    L.kmc_chain_psis_tail_reff.argtypes = host_chain + psis_reff + [C.c_int, dp, dp, dp, i32p, ip, dp, ip, ip, ip]
     L.kmc_deal_seed.restype = C.c_uint64
     L.kmc_deal_seed.argtypes = [C.c_uint64, C.c_int32]
     L.kmc_deal_perm.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_int64, ip, ip]

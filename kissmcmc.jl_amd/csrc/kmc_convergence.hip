@@ -79,9 +79,7 @@ kmc_status moments_device(ConvBuffers& b, const ChainView& v, const ConvShape& s
         const int64_t clen = (sh.h + nchunk - 1) / nchunk;
         nchunk = (sh.h + clen - 1) / clen;
         if (gx >= ((int64_t)1 << 23) || nchunk * sh.nhalf > 65535) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one convergence call");
-        HIP_TRY(hipFree(b.mean_p));
-        b.mean_p = nullptr;
-        HIP_TRY(hipMalloc((void**)&b.mean_p, (size_t)sh.nhalf * (size_t)np * sizeof(double)));
+        KMC_TRY(b.room(&b.mean_p, &b.mean_bytes, (size_t)sh.nhalf * (size_t)np * sizeof(double)));   // (kept from call to call: a view per group of observations)
         KMC_TRY(b.room(&b.part, &b.part_bytes, (size_t)(sh.nhalf * nchunk) * (size_t)np * sizeof(double)));
         MomentArgs a{};
         a.src = src.src; a.rank = b.rank; a.mean_p = b.mean_p; a.part = b.part;
@@ -240,19 +238,26 @@ void stats_host(int64_t m, int64_t h, int64_t ncols, const double* chain_mean, c
 kmc_status convergence_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, int64_t max_lag,
                               const StatsOut& o, int64_t* info)
 {
-    const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
     ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
     HIP_TRY(ss.create());
     KMC_TRY(upload_rank(b, mask_host, v.nl, ss.st));
+    return convergence_on_stream(b, v, sh, with_logp, max_lag, o, info, ss.st);
+}
+
+// ... on the caller's stream, with b.rank in place: a caller that runs many views of one shape keeps its stream and its buffers
+kmc_status convergence_on_stream(ConvBuffers& b, const ChainView& v, const ConvShape& sh, bool with_logp, int64_t max_lag, const StatsOut& o,
+                                 int64_t* info, hipStream_t st)
+{
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
     std::vector<double> cm((size_t)(ncols * sh.m)), cv((size_t)(ncols * sh.m)), lag, next;
-    KMC_TRY(moments_device(b, v, sh, with_logp, ss.st, cm.data(), cv.data()));
+    KMC_TRY(moments_device(b, v, sh, with_logp, st, cm.data(), cv.data()));
     LagWork work;
     int64_t have = 0;
     for (;;) {
         const int64_t want = std::min(max_lag, have == 0 ? (int64_t)kConvLagBlock : 2 * have);        // 32, 64, 128, ... lags in all
         next.assign((size_t)(ncols * want), 0.0);
         for (int64_t c = 0; c < ncols; ++c) std::copy(lag.begin() + c * have, lag.begin() + (c + 1) * have, next.begin() + c * want);
-        KMC_TRY(lags_device(b, v, sh, with_logp, have + 1, want - have, ss.st, next.data(), want, have, &work));
+        KMC_TRY(lags_device(b, v, sh, with_logp, have + 1, want - have, st, next.data(), want, have, &work));
         lag.swap(next);
         have = want;
         stats_host(sh.m, sh.h, ncols, cm.data(), cv.data(), lag.data(), have, max_lag, o);

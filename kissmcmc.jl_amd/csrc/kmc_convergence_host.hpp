@@ -21,7 +21,7 @@ struct ConvShape {
 struct ConvBuffers : ChainUpload {
     int32_t* rank = nullptr;
     double *mean_p = nullptr, *part = nullptr, *out = nullptr;
-    size_t part_bytes = 0, out_bytes = 0;
+    size_t mean_bytes = 0, part_bytes = 0, out_bytes = 0;
     ~ConvBuffers() { (void)hipFree(rank); (void)hipFree(mean_p); (void)hipFree(part); (void)hipFree(out); }
     kmc_status room(double** p, size_t* have, size_t need)
     {
@@ -64,5 +64,8 @@ kmc_status upload_rank(ConvBuffers& b, const uint8_t* mask_host, int64_t nl, hip
 // the whole thing on a view: chain moments once, then lag blocks until every column's rule has fired or max_lag is reached
 kmc_status convergence_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, int64_t max_lag,
                               const StatsOut& o, int64_t* info);
+// the same on the caller's stream, with b.rank uploaded (upload_rank): for a caller that runs many views of one shape
+kmc_status convergence_on_stream(ConvBuffers& b, const ChainView& v, const ConvShape& sh, bool with_logp, int64_t max_lag, const StatsOut& o,
+                                 int64_t* info, hipStream_t st);
 
 }  // namespace kmc_conv_host

@@ -2,7 +2,9 @@
 // the compiled term are: the per-observation statistics behind WAIC (kmc_sampler_pointwise_stats, kmc_chain_pointwise_stats), the
 // matrix itself for a range of observations (kmc_sampler_pointwise_loglike, kmc_chain_pointwise_loglike), the plan (kmc_pointwise_plan)
 // and the pure host stage (kmc_waic_stats); and PSIS-LOO over the same rows (kmc_sampler_psis_loo, kmc_chain_psis_loo, the read-out of its
-// tails kmc_*_psis_tail, kmc_psis_plan, kmc_loo_stats, kmc_psis_smooth_host).  include/kissmcmc_hip.h has the definitions, DESIGN.md
+// tails kmc_*_psis_tail, kmc_psis_plan, kmc_loo_stats, kmc_psis_smooth_host; with a relative efficiency per observation, supplied or
+// computed from the chain: kmc_*_relative_eff, kmc_*_pointwise_weights, kmc_*_psis_loo_reff, kmc_*_psis_tail_reff, whose ESS stage is
+// kmc_convergence.hip's on groups of 64 observations).  include/kissmcmc_hip.h has the definitions, DESIGN.md
 // sections 4k and 4l the plans.  Kernels: kmc_pointwise.hpp, compiled at run time with the density's term as the module "pointwise:<ndim>";
 // the folds and the PSIS fit, which do not touch the term, are compiled here.
 #include <algorithm>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "kmc_chain_view.hpp"
+#include "kmc_convergence_host.hpp"
 #include "kmc_pointwise.hpp"
 
 using namespace kmc_host;
@@ -49,9 +52,9 @@ PwPlan pw_plan(int64_t n, int64_t J)
 }
 
 struct PwKernels {
-    std::shared_ptr<void> keep, keep_data;
+    std::shared_ptr<void> keep, keep_data, keep_weights;
     hipFunction_t pass[2][2] = {};                // [pass - 1][packed]
-    hipFunction_t matrix = nullptr;
+    hipFunction_t matrix = nullptr, weights = nullptr;
     hipFunction_t psis[3][2] = {};                // [mode][packed]
 };
 
@@ -75,6 +78,29 @@ kmc_status compile_pointwise(kmc_user_density* ud, int64_t ndim, const std::vect
         *text = src.str();
         return KMC_OK;
     }, out);
+}
+
+// The weight series' kernel (pw_weights) is a module of its own, "pointwise_weights:<ndim>", compiled when a relative efficiency or the
+// series is first asked for: the module above keeps the text it has for WAIC and for PSIS-LOO with one r_eff.
+kmc_status compile_weights(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
+{
+    static const RtcModule m{"data density", "kmc_pointwise_weights.hip", {"kmc_device.hpp", "kmc_pointwise.hpp", "kmc_psis_fit.hpp"}, rtc_options()};
+    return compile_keyed(ud, "pointwise_weights:" + std::to_string(ndim), m, [&](std::string* text) {
+        std::ostringstream src;
+        src << "#include \"kmc_pointwise.hpp\"\n" << data_functor_source(ud) << "extern \"C\" __global__ __launch_bounds__(" << kPwThreads
+            << ") void kmc_pw_weights(const kmc_pw::WeightArgs q) { kmc_pw::pw_weights<UserData, " << ndim << ", " << ud->ncols << ">(q); }\n";
+        *text = src.str();
+        return KMC_OK;
+    }, out);
+}
+
+kmc_status load_weights(kmc_user_density* ud, int64_t ndim, PwKernels* pk)
+{
+    const std::vector<char>* code = nullptr;
+    KMC_TRY(compile_weights(ud, ndim, &code));
+    KMC_TRY(shared_module(ud, code, &pk->keep_weights));
+    HIP_TRY(hipModuleGetFunction(&pk->weights, static_cast<hipModule_t>(pk->keep_weights.get()), "kmc_pw_weights"));
+    return KMC_OK;
 }
 
 // compile (cached) + module on the current device + the device copy of the density's own observations
@@ -104,10 +130,10 @@ __global__ __launch_bounds__(kmc_psis::kFitLanes) void psis_fit_kernel(const Psi
 
 // the device copies one call owns, beyond the chain's: the list of selected walkers, held-out observations, the work space
 struct PwBuffers : ChainUpload {
-    int32_t* sel = nullptr;
+    int32_t *sel = nullptr, *Mj = nullptr;
     double *data = nullptr, *work = nullptr;
     void* work2 = nullptr;
-    ~PwBuffers() { (void)hipFree(sel); (void)hipFree(data); (void)hipFree(work); (void)hipFree(work2); }
+    ~PwBuffers() { (void)hipFree(sel); (void)hipFree(Mj); (void)hipFree(data); (void)hipFree(work); (void)hipFree(work2); }
 };
 
 // the events around the two passes, for info: each pass is its partial kernel and its fold
@@ -135,18 +161,24 @@ struct PwRequest {
     bool psis = false;                            // PSIS-LOO: over the observations [obs_first, obs_first + obs_count)
     double r_eff = 1.0;
     int64_t workspace = 0;                        // bytes of work space a block of observations may take; 0: kPsisWorkspace
+    // the relative efficiency per observation: supplied [obs_count], or -- reff_chain -- computed from the chain (reff_stage)
+    const double* r_eff_j = nullptr;
+    bool reff_chain = false, split = true, weights = false;      // weights: the series itself is asked for (no PSIS, no ESS)
+    int64_t max_lag = 0;
+    double* weights_M = nullptr;                  // weights: M_j [obs_count] out
 };
 
 constexpr int64_t kPsisWorkspace = (int64_t)1 << 30;
 
 // the refusals PSIS-LOO adds, from the sizes alone; M: the tail length
-kmc_status psis_check(int64_t n, double r_eff, int64_t* M)
+kmc_status psis_check(int64_t n, double r_eff, int64_t* M, bool sizes_only = false)
 {
+    if (sizes_only) r_eff = 1.0;
     if (!(r_eff > 0.0) || !std::isfinite(r_eff)) return fail(KMC_ERR_BAD_ARG, "r_eff must be finite and > 0 (r_eff = " + std::to_string(r_eff) + ")");
     if (n < kmc_psis::kMinFit) return fail(KMC_ERR_BAD_ARG, "PSIS-LOO needs at least 5 selected rows (n = " + std::to_string(n) + ")");
     if (n >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "too many rows for one PSIS-LOO call: n = " + std::to_string(n) + ", the limit is 2^31");
     const int64_t m = kmc_psis::tail_length(n, r_eff);
-    if (m > kmc_psis::kMaxTail)
+    if (m > kmc_psis::kMaxTail && !sizes_only)                                         // (a per-observation r_eff: tail_lengths decides)
         return fail(KMC_ERR_UNSUPPORTED, "a tail of M = " + std::to_string(m) + " draws (n / r_eff = " + std::to_string((double)n / r_eff) + ") is longer than " +
                                              std::to_string(kmc_psis::kMaxTail) + ", what one workgroup sorts: thin the chain");
     if (M) *M = m;
@@ -182,7 +214,31 @@ struct PwSession {
     PwArgs a{};
     PwPlan pl;
     int64_t n = 0, J = 0;
+    kmc_conv_host::ConvShape sh;                  // reff_chain: the chains of the weight series
+    int64_t max_lag = 0;
+    std::vector<double> r_used;                   // a per-observation r_eff: as used (1.0 where it is not finite and > 0) ...
+    std::vector<int32_t> Mj;                      // ... and the tail lengths
+    int64_t n_reff_nan = 0;
 };
+
+// the tail lengths of a per-observation r_eff, and the refusal of one longer than a workgroup sorts
+kmc_status tail_lengths(int64_t n, int64_t obs_first, const double* r, int64_t count, PwSession* S)
+{
+    S->r_used.assign(r, r + count);
+    S->Mj.assign((size_t)count, 0);
+    S->n_reff_nan = 0;
+    for (int64_t c = 0; c < count; ++c) {
+        double& rc = S->r_used[(size_t)c];
+        if (!(rc > 0.0) || !std::isfinite(rc)) { rc = 1.0; ++S->n_reff_nan; }
+        const int64_t m = kmc_psis::tail_length(n, rc);
+        if (m > kmc_psis::kMaxTail)
+            return fail(KMC_ERR_UNSUPPORTED, "observation " + std::to_string(obs_first + c) + ": a tail of M = " + std::to_string(m) + " draws (n = " + std::to_string(n) +
+                                                 ", r_eff_j = " + std::to_string(rc) + ") is longer than " + std::to_string(kmc_psis::kMaxTail) +
+                                                 ", what one workgroup sorts: thin the chain");
+        S->Mj[(size_t)c] = (int32_t)m;
+    }
+    return KMC_OK;
+}
 
 // the refusals, then the chain, the stream, the module and the arguments every kernel shares
 kmc_status pw_open(const ChainSource& src, const PwRequest& q, const void* result, PwSession* S)
@@ -203,7 +259,14 @@ kmc_status pw_open(const ChainSource& src, const PwRequest& q, const void* resul
     const int64_t n = kept * nsel;
     if (n < 2) return fail(KMC_ERR_BAD_ARG, "the pointwise statistics need at least 2 selected rows (n = " + std::to_string(n) + ")");
     if (n >= ((int64_t)1 << 40)) return fail(KMC_ERR_UNSUPPORTED, "too many rows for one pointwise call: n = " + std::to_string(n) + ", the limit is 2^40");
-    if (q.psis) KMC_TRY(psis_check(n, q.r_eff, nullptr));
+    if (q.psis) KMC_TRY(psis_check(n, q.r_eff, nullptr, q.r_eff_j || q.reff_chain));
+    if (q.reff_chain) {                           // the chains of the weight series: nsel of `kept` samples each
+        ChainView gv;
+        gv.ld = 64; gv.ndim = 1; gv.nsamples = kept; gv.nl = nsel;
+        KMC_TRY(kmc_conv_host::conv_shape(gv, 0, nullptr, q.split, &S->sh));
+        S->max_lag = q.max_lag;
+        KMC_TRY(kmc_conv_host::resolve_max_lag(S->sh, &S->max_lag));
+    }
     int64_t J = q.ud->ndata;
     if (q.data) {
         if (q.ncols2 != q.ud->ncols)
@@ -211,11 +274,17 @@ kmc_status pw_open(const ChainSource& src, const PwRequest& q, const void* resul
         if (q.ndata2 < 1 || q.ndata2 > kDataMaxRows) return fail(KMC_ERR_BAD_ARG, "held-out data: ndata must be in 1 .. 2^30 (ndata = " + std::to_string(q.ndata2) + ")");
         J = q.ndata2;
     }
-    if (q.matrix || q.psis) {
+    if (q.matrix || q.psis || q.reff_chain || q.weights) {
         if (q.obs_count < 1) return fail(KMC_ERR_BAD_ARG, "the matrix needs obs_count >= 1 (obs_count = " + std::to_string(q.obs_count) + ")");
         if (q.obs_first < 0 || q.obs_first > J - q.obs_count)
             return fail(KMC_ERR_BAD_ARG, "observations [" + std::to_string(q.obs_first) + ", " + std::to_string(q.obs_first) + " + " + std::to_string(q.obs_count) +
                                              ") lie outside [0, " + std::to_string(J) + ")");
+    }
+    if (q.r_eff_j) {
+        for (int64_t c = 0; c < q.obs_count; ++c)
+            if (!(q.r_eff_j[c] > 0.0) || !std::isfinite(q.r_eff_j[c]))
+                return fail(KMC_ERR_BAD_ARG, "r_eff_j must be finite and > 0 (r_eff_j[" + std::to_string(c) + "] = " + std::to_string(q.r_eff_j[c]) + ")");
+        KMC_TRY(tail_lengths(n, q.obs_first, q.r_eff_j, q.obs_count, S));
     }
     if (v.is_float) return fail(KMC_ERR_UNSUPPORTED, "a chain of floats: data densities sample in double");
     if (!result || !q.params) return fail(KMC_ERR_BAD_ARG, "null argument");
@@ -255,7 +324,7 @@ kmc_status pw_open(const ChainSource& src, const PwRequest& q, const void* resul
 }
 
 // the two passes of the statistics, left on the device: work gets the work space, a.stats [4][J]
-kmc_status pw_stats(PwSession& S, double** work, int64_t* info)
+kmc_status pw_stats(PwSession& S, double** work, int64_t* info, int npass = 2)
 {
     PwArgs& a = S.a;
     const PwPlan& pl = S.pl;
@@ -268,7 +337,7 @@ kmc_status pw_stats(PwSession& S, double** work, int64_t* info)
     const unsigned gx = (unsigned)((J + 63) / 64), gy = (unsigned)((pl.nwaves + kPwWaves - 1) / kPwWaves), gf = (unsigned)((J + 255) / 256);
     PassEvents ev;
     if (info) HIP_TRY(ev.create());
-    for (int pass = 1; pass <= 2; ++pass) {
+    for (int pass = 1; pass <= npass; ++pass) {                                        // (npass = 1: M and S1 alone; info needs both)
         if (info) HIP_TRY(hipEventRecord(ev.e[pass - 1], S.ss.get()));
         HIP_TRY(launch_module_y(S.pk.pass[pass - 1][pl.packed ? 1 : 0], gx, gy, kPwThreads, S.ss.get(), a));
         hipLaunchKernelGGL(pw_fold, dim3(gf), dim3(256), 0, S.ss.get(), a, pass);
@@ -283,6 +352,99 @@ kmc_status pw_stats(PwSession& S, double** work, int64_t* info)
         info[0] = n; info[1] = pl.nruns; info[2] = 2 * n * J; info[3] = pl.run_len;
         info[4] = (int64_t)((double)ms1 * 1e6); info[5] = (int64_t)((double)ms2 * 1e6);
     }
+    return KMC_OK;
+}
+
+// what the relative-efficiency stage hands back, each [obs_count] or nullptr
+struct ReffOut {
+    double *r_eff = nullptr, *ess = nullptr;
+    int64_t* T = nullptr;
+    int32_t* flags = nullptr;
+    double* v = nullptr;                          // the series itself, dense [n][obs_count]; with it the ESS is not taken
+};
+
+// The weight series v = exp(l - M_j) of the observations [obs_first, obs_first + obs_count), in groups of 64 observations aligned to
+// the absolute index, and the effective sample size of every column by the convergence diagnostics' own stages (kmc_convergence.hip)
+// on each group as a chain [kept][nsel][64].  ld = 64 whatever the group holds: lags_device then has period = 1 and a lane owns one
+// column, so the grid and the order of a column's additions follow from the selection's shape alone -- not from the group, the other
+// columns, the range or the work space.  Needs a.stats of pass 1.  info3: nanoseconds of the weight passes, of the ESS stage, groups.
+kmc_status reff_stage(PwSession& S, const PwRequest& q, const ReffOut& o, int64_t* info3)
+{
+    const int64_t n = S.n, count = q.obs_count;
+    hipStream_t st = S.ss.get();
+    KMC_TRY(load_weights(q.ud, S.v.ndim, &S.pk));
+    const int64_t g_first = q.obs_first / 64, g_last = (q.obs_first + count - 1) / 64, ngroups = g_last - g_first + 1;
+    const double group_bytes = (double)n * 64.0 * 8.0;
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    if (group_bytes > (double)free_b)
+        return fail(KMC_ERR_UNSUPPORTED, "the weight series of one group of 64 observations (" + std::to_string((int64_t)group_bytes) + " bytes, n = " +
+                                             std::to_string(n) + ") does not fit the device (" + std::to_string(free_b) + " bytes free): thin the chain");
+    const int64_t budget = std::min<int64_t>(q.workspace > 0 ? q.workspace : kPsisWorkspace, (int64_t)(free_b / 2));
+    const int64_t per_batch = std::max<int64_t>(1, std::min<int64_t>(ngroups, budget / (int64_t)group_bytes));
+    double* buf = nullptr;
+    HIP_TRY(hipMalloc((void**)&buf, (size_t)per_batch * (size_t)n * 64 * sizeof(double)));
+    std::shared_ptr<void> keep(buf, [](void* p) { (void)hipFree(p); });
+
+    WeightArgs wa{};
+    wa.a = S.a;
+    wa.a.out = buf; wa.a.obs_first = q.obs_first; wa.a.obs_count = count;
+    wa.a.run_len = std::max(kPwMinRun, (n + kPwMatrixWaves - 1) / kPwMatrixWaves);
+    const int64_t waves = (n + wa.a.run_len - 1) / wa.a.run_len;
+
+    kmc_conv_host::ConvBuffers cb;
+    if (!o.v) KMC_TRY(kmc_conv_host::upload_rank(cb, nullptr, S.a.nsel, st));
+    ChainView gv;
+    gv.ld = 64; gv.nsamples = n / S.a.nsel; gv.nl = S.a.nsel;
+    double mean[64], W[64], B[64], vp[64], rhat[64], ess[64], mcse[64];
+    int64_t T[64];
+    int32_t flags[64];
+    const kmc_conv_host::StatsOut so{mean, W, B, vp, rhat, ess, mcse, T, flags};
+    const double mh = (double)S.sh.m * (double)S.sh.h;
+    std::vector<double> host_group;
+    if (o.v) host_group.resize((size_t)n * 64);
+
+    PassEvents ev;
+    if (info3) HIP_TRY(ev.create());
+    double ms_w = 0.0, ms_e = 0.0;
+    for (int64_t g0 = g_first; g0 <= g_last; g0 += per_batch) {
+        const int64_t ng = std::min(per_batch, g_last - g0 + 1);
+        wa.group0 = g0;
+        if (info3) HIP_TRY(hipEventRecord(ev.e[0], st));
+        HIP_TRY(launch_module_y(S.pk.weights, (unsigned)ng, (unsigned)((waves + kPwWaves - 1) / kPwWaves), kPwThreads, st, wa));
+        if (info3) HIP_TRY(hipEventRecord(ev.e[1], st));
+        for (int64_t i = 0; i < ng; ++i) {
+            const int64_t j0 = (g0 + i) * 64;
+            const int64_t lo = std::max<int64_t>(0, q.obs_first - j0), hi = std::min<int64_t>(63, q.obs_first + count - 1 - j0);    // the live lanes
+            const double* group = buf + (size_t)i * (size_t)n * 64;
+            if (o.v) {
+                HIP_TRY(copy_sync(host_group.data(), group, host_group.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+                for (int64_t k = 0; k < n; ++k)
+                    for (int64_t l = lo; l <= hi; ++l) o.v[k * count + (j0 + l - q.obs_first)] = host_group[(size_t)(k * 64 + l)];
+                continue;
+            }
+            gv.chain = group;
+            gv.ndim = hi + 1;                                                          // (the lanes below lo are constant 0.0: no ESS, no lags)
+            KMC_TRY(kmc_conv_host::convergence_on_stream(cb, gv, S.sh, false, S.max_lag, so, nullptr, st));
+            for (int64_t l = lo; l <= hi; ++l) {
+                const int64_t c = j0 + l - q.obs_first;
+                if (o.r_eff) o.r_eff[c] = ess[l] / mh;
+                if (o.ess) o.ess[c] = ess[l];
+                if (o.T) o.T[c] = T[l];
+                if (o.flags) o.flags[c] = flags[l];
+            }
+        }
+        if (info3) {
+            HIP_TRY(hipEventRecord(ev.e[2], st));
+            HIP_TRY(hipStreamSynchronize(st));
+            float t0 = 0.f, t1 = 0.f;
+            HIP_TRY(hipEventElapsedTime(&t0, ev.e[0], ev.e[1]));
+            HIP_TRY(hipEventElapsedTime(&t1, ev.e[1], ev.e[2]));
+            ms_w += (double)t0; ms_e += (double)t1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));                                                 // (buf goes with this scope)
+    if (info3) { info3[0] = (int64_t)(ms_w * 1e6); info3[1] = (int64_t)(ms_e * 1e6); info3[2] = ngroups; }
     return KMC_OK;
 }
 
@@ -317,8 +479,40 @@ kmc_status pointwise(const ChainSource& src, const PwRequest& q, double* result,
         return KMC_OK;
     }
 
+    if (q.weights) {
+        KMC_TRY(pw_stats(S, &b.work, nullptr, 1));
+        ReffOut o;
+        o.v = result;
+        KMC_TRY(reff_stage(S, q, o, nullptr));
+        if (q.weights_M) HIP_TRY(copy_sync(q.weights_M, a.stats + q.obs_first, (size_t)q.obs_count * sizeof(double), hipMemcpyDeviceToHost, ss.get()));
+        return KMC_OK;
+    }
+
     KMC_TRY(pw_stats(S, &b.work, info));
     HIP_TRY(copy_sync(result, a.stats, 4 * (size_t)J * sizeof(double), hipMemcpyDeviceToHost, ss.get()));
+    return KMC_OK;
+}
+
+// r_eff_j = ess_j / (m h) of the weight series, alone.  info [6]: n, groups, nanoseconds of pass 1, of the weight passes, of the ESS
+// stage (moments, lags and their copies per group), h.
+kmc_status relative_eff(const ChainSource& src, const PwRequest& q, const ReffOut& o, int64_t* m_out, int64_t* h_out, int64_t* n_out, int64_t* info)
+{
+    PwSession S;
+    KMC_TRY(pw_open(src, q, o.r_eff, &S));
+    if (m_out) *m_out = S.sh.m;
+    if (h_out) *h_out = S.sh.h;
+    if (n_out) *n_out = S.n;
+    PassEvents ev;
+    if (info) { HIP_TRY(ev.create()); HIP_TRY(hipEventRecord(ev.e[0], S.ss.get())); }
+    KMC_TRY(pw_stats(S, &S.b.work, nullptr, 1));
+    if (info) HIP_TRY(hipEventRecord(ev.e[1], S.ss.get()));
+    int64_t i3[3] = {};
+    KMC_TRY(reff_stage(S, q, o, info ? i3 : nullptr));
+    if (info) {
+        float t = 0.f;
+        HIP_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
+        info[0] = S.n; info[1] = i3[2]; info[2] = (int64_t)((double)t * 1e6); info[3] = i3[0]; info[4] = i3[1]; info[5] = S.sh.h;
+    }
     return KMC_OK;
 }
 
@@ -459,6 +653,8 @@ struct PsisOut {
     double *m = nullptr, *xc = nullptr;
     int32_t* n_tail = nullptr;
     int64_t* tail_len = nullptr;
+    double* r_eff = nullptr;      // a per-observation r_eff: as computed (NaN where it has none) or as supplied
+    int64_t *tail_len_j = nullptr, *n_reff_nan = nullptr;
 };
 
 kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, int64_t* n_out, int64_t* info)
@@ -467,8 +663,28 @@ kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, 
     KMC_TRY(pw_open(src, q, out.res ? (const void*)out.res : (const void*)out.tail, &S));
     const int64_t n = S.n, J = S.J, count = q.obs_count;
     if (n_out) *n_out = n;
+    hipStream_t st = S.ss.get();
+    int64_t ns_stats = 0, reff_info[3] = {};
+    if (out.lppd_j || q.reff_chain) {
+        int64_t sinfo[6] = {};
+        KMC_TRY(pw_stats(S, &S.b.work, info && out.lppd_j ? sinfo : nullptr, out.lppd_j ? 2 : 1));
+        ns_stats = sinfo[4] + sinfo[5];
+    }
+    if (q.reff_chain) {
+        std::vector<double> r((size_t)count);
+        ReffOut ro;
+        ro.r_eff = r.data();
+        KMC_TRY(reff_stage(S, q, ro, info ? reff_info : nullptr));
+        if (out.r_eff) std::copy(r.begin(), r.end(), out.r_eff);
+        KMC_TRY(tail_lengths(n, q.obs_first, r.data(), count, &S));
+    } else if (q.r_eff_j && out.r_eff) {
+        std::copy(S.r_used.begin(), S.r_used.end(), out.r_eff);
+    }
     int64_t M = 0;
-    KMC_TRY(psis_check(n, q.r_eff, &M));
+    if (S.Mj.empty()) KMC_TRY(psis_check(n, q.r_eff, &M));
+    else M = *std::max_element(S.Mj.begin(), S.Mj.end());
+    if (out.tail_len_j) for (int64_t c = 0; c < count; ++c) out.tail_len_j[c] = S.Mj.empty() ? M : S.Mj[(size_t)c];
+    if (out.n_reff_nan) *out.n_reff_nan = S.n_reff_nan;
     if (out.tail) {
         if (!out.tail_len) return fail(KMC_ERR_BAD_ARG, "null argument");
         if (*out.tail_len < M)
@@ -478,17 +694,12 @@ kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, 
     const PwPlan& pl = S.pl;
     const PsisPlan pp = psis_plan(M, pl, q.workspace);
     const int64_t block = std::min(pp.block, pl.packed ? (int64_t)64 : count);
-    hipStream_t st = S.ss.get();
-    int64_t ns_stats = 0;
 
     if (out.lppd_j) {
-        int64_t sinfo[6] = {};
-        KMC_TRY(pw_stats(S, &S.b.work, info ? sinfo : nullptr));
         std::vector<double> stats(4 * (size_t)J), lp((size_t)J), totals(7);
         HIP_TRY(copy_sync(stats.data(), S.a.stats, stats.size() * sizeof(double), hipMemcpyDeviceToHost, st));
         KMC_TRY(kmc_waic_stats(J, n, stats.data(), lp.data(), nullptr, nullptr, totals.data()));
         std::copy(lp.begin() + q.obs_first, lp.begin() + q.obs_first + count, out.lppd_j);
-        ns_stats = sinfo[4] + sinfo[5];
     }
 
     // the work space of one block, carved in order of alignment
@@ -496,6 +707,10 @@ kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, 
     const size_t bytes = B * (size_t)M * 8 + R * B * 8 + B * 8 * 4 + B * 32 + R * B * kmc_psis::kSelectBins * 4 + B * 4;
     KMC_TRY(check_device_room(bytes, "the PSIS-LOO work space"));
     HIP_TRY(hipMalloc(&S.b.work2, bytes));
+    if (!S.Mj.empty()) {
+        HIP_TRY(hipMalloc((void**)&S.b.Mj, (size_t)count * sizeof(int32_t)));
+        HIP_TRY(copy_sync(S.b.Mj, S.Mj.data(), (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
     PsisArgs qa{};
     qa.a = S.a;
     qa.M = (int32_t)M;
@@ -522,6 +737,7 @@ kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, 
         const int64_t bc = std::min(block, count - b0);
         qa.a.obs_first = q.obs_first + b0;
         qa.a.obs_count = bc;
+        qa.Mj = S.b.Mj ? S.b.Mj + b0 : nullptr;
         const unsigned gx = pl.packed ? 1u : (unsigned)((bc + 63) / 64), gf = (unsigned)((bc + 255) / 256);
         if (info) HIP_TRY(hipEventRecord(ev.e[0], st));
         HIP_TRY(launch_module_y(S.pk.psis[0][pk], gx, gy, kPwThreads, st, qa));
@@ -561,6 +777,7 @@ kmc_status psis(const ChainSource& src, const PwRequest& q, const PsisOut& out, 
         info[0] = n; info[1] = M; info[2] = nblocks; info[3] = block;
         for (int k = 0; k < 4; ++k) info[4 + k] = (int64_t)(ms[k] * 1e6);
         info[8] = n * count; info[9] = log1ps; info[10] = ns_stats; info[11] = pl.nruns;
+        if (q.reff_chain || q.r_eff_j) { info[12] = reff_info[0]; info[13] = reff_info[1]; info[14] = reff_info[2]; info[15] = S.n_reff_nan; }
     }
     return KMC_OK;
 }
@@ -618,6 +835,131 @@ KMC_EXPORT kmc_status kmc_chain_psis_tail(kmc_user_density* density, const doubl
     q.ud = density; q.params = params;
     PsisOut out;
     out.tail = tail; out.m = m_j; out.xc = xc_j; out.n_tail = n_tail_j; out.tail_len = tail_len;
+    return psis(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, out, n_out, nullptr);
+}
+
+// ---- a per-observation relative efficiency (include/kissmcmc_hip.h) ----
+namespace {
+
+PwRequest reff_request(int64_t first_sample, const uint8_t* walker_mask, int64_t thin, int64_t obs_first, int64_t obs_count, int32_t split, int64_t max_lag,
+                       int64_t workspace)
+{
+    PwRequest q;
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask;
+    q.obs_first = obs_first; q.obs_count = obs_count; q.workspace = workspace;
+    q.reff_chain = true; q.split = split != 0; q.max_lag = max_lag;
+    return q;
+}
+
+// the request of the *_reff forms of PSIS-LOO: r_eff_j supplied, or computed from the chain
+PwRequest psis_reff_request(int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* r_eff_j, int32_t split, int64_t max_lag,
+                            int64_t obs_first, int64_t obs_count, int64_t workspace)
+{
+    PwRequest q = psis_request(first_sample, walker_mask, thin, 1.0, obs_first, obs_count, workspace);
+    q.r_eff_j = r_eff_j;
+    q.reff_chain = r_eff_j == nullptr; q.split = split != 0; q.max_lag = max_lag;
+    return q;
+}
+
+}  // namespace
+
+KMC_EXPORT kmc_status kmc_sampler_relative_eff(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, int64_t obs_first,
+                                               int64_t obs_count, int32_t split, int64_t max_lag, int64_t workspace_bytes, double* r_eff_j, double* ess_j,
+                                               int64_t* T_j, int32_t* flags_j, int64_t* m_out, int64_t* h_out, int64_t* n_out, int64_t* info)
+{
+    PwRequest q = reff_request(first_sample, walker_mask, thin, obs_first, obs_count, split, max_lag, workspace_bytes);
+    KMC_TRY(sampler_density(s, &q));
+    ReffOut o;
+    o.r_eff = r_eff_j; o.ess = ess_j; o.T = T_j; o.flags = flags_j;
+    return relative_eff(ChainSource(s, false, "kmc_chain_relative_eff"), q, o, m_out, h_out, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_chain_relative_eff(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples, int64_t nwalkers,
+                                             int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, int64_t obs_first,
+                                             int64_t obs_count, int32_t split, int64_t max_lag, int64_t workspace_bytes, int device, double* r_eff_j,
+                                             double* ess_j, int64_t* T_j, int32_t* flags_j, int64_t* m_out, int64_t* h_out, int64_t* n_out, int64_t* info)
+{
+    PwRequest q = reff_request(first_sample, walker_mask, thin, obs_first, obs_count, split, max_lag, workspace_bytes);
+    q.ud = density; q.params = params;
+    ReffOut o;
+    o.r_eff = r_eff_j; o.ess = ess_j; o.T = T_j; o.flags = flags_j;
+    return relative_eff(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, o, m_out, h_out, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_pointwise_weights(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* data,
+                                                    int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, double* v, double* M_j,
+                                                    int64_t* n_out)
+{
+    PwRequest q;
+    KMC_TRY(sampler_density(s, &q));
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask; q.data = data; q.ndata2 = ndata2; q.ncols2 = ncols2;
+    q.weights = true; q.obs_first = obs_first; q.obs_count = obs_count; q.weights_M = M_j;
+    return pointwise(ChainSource(s, false, "kmc_chain_pointwise_weights"), q, v, n_out, nullptr);
+}
+
+KMC_EXPORT kmc_status kmc_chain_pointwise_weights(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                                  int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                                  const double* data, int64_t ndata2, int32_t ncols2, int64_t obs_first, int64_t obs_count, int device,
+                                                  double* v, double* M_j, int64_t* n_out)
+{
+    PwRequest q;
+    q.ud = density; q.params = params;
+    q.first_sample = first_sample; q.thin = thin; q.walker_mask = walker_mask; q.data = data; q.ndata2 = ndata2; q.ncols2 = ncols2;
+    q.weights = true; q.obs_first = obs_first; q.obs_count = obs_count; q.weights_M = M_j;
+    return pointwise(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, v, n_out, nullptr);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_psis_loo_reff(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* r_eff_j,
+                                                int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes,
+                                                double* stats, double* lppd_j, double* r_eff_used, int64_t* tail_len_j, int64_t* n_reff_nan,
+                                                int64_t* n_out, int64_t* info)
+{
+    PwRequest q = psis_reff_request(first_sample, walker_mask, thin, r_eff_j, split, max_lag, obs_first, obs_count, workspace_bytes);
+    KMC_TRY(sampler_density(s, &q));
+    if (!lppd_j) return fail(KMC_ERR_BAD_ARG, "null argument");
+    PsisOut out;
+    out.res = stats; out.lppd_j = lppd_j; out.r_eff = r_eff_used; out.tail_len_j = tail_len_j; out.n_reff_nan = n_reff_nan;
+    return psis(ChainSource(s, false, "kmc_chain_psis_loo_reff"), q, out, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_chain_psis_loo_reff(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                              int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                              const double* r_eff_j, int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count,
+                                              int64_t workspace_bytes, int device, double* stats, double* lppd_j, double* r_eff_used,
+                                              int64_t* tail_len_j, int64_t* n_reff_nan, int64_t* n_out, int64_t* info)
+{
+    PwRequest q = psis_reff_request(first_sample, walker_mask, thin, r_eff_j, split, max_lag, obs_first, obs_count, workspace_bytes);
+    q.ud = density; q.params = params;
+    if (!lppd_j) return fail(KMC_ERR_BAD_ARG, "null argument");
+    PsisOut out;
+    out.res = stats; out.lppd_j = lppd_j; out.r_eff = r_eff_used; out.tail_len_j = tail_len_j; out.n_reff_nan = n_reff_nan;
+    return psis(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, out, n_out, info);
+}
+
+KMC_EXPORT kmc_status kmc_sampler_psis_tail_reff(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int64_t thin, const double* r_eff_j,
+                                                 int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count, int64_t workspace_bytes,
+                                                 double* tail, double* m_j, double* xc_j, int32_t* n_tail_j, int64_t* tail_len, double* r_eff_used,
+                                                 int64_t* tail_len_j, int64_t* n_reff_nan, int64_t* n_out)
+{
+    PwRequest q = psis_reff_request(first_sample, walker_mask, thin, r_eff_j, split, max_lag, obs_first, obs_count, workspace_bytes);
+    KMC_TRY(sampler_density(s, &q));
+    PsisOut out;
+    out.tail = tail; out.m = m_j; out.xc = xc_j; out.n_tail = n_tail_j; out.tail_len = tail_len;
+    out.r_eff = r_eff_used; out.tail_len_j = tail_len_j; out.n_reff_nan = n_reff_nan;
+    return psis(ChainSource(s, false, "kmc_chain_psis_tail_reff"), q, out, n_out, nullptr);
+}
+
+KMC_EXPORT kmc_status kmc_chain_psis_tail_reff(kmc_user_density* density, const double* params, const double* chain_host, int64_t nsamples,
+                                               int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int64_t thin,
+                                               const double* r_eff_j, int32_t split, int64_t max_lag, int64_t obs_first, int64_t obs_count,
+                                               int64_t workspace_bytes, int device, double* tail, double* m_j, double* xc_j, int32_t* n_tail_j,
+                                               int64_t* tail_len, double* r_eff_used, int64_t* tail_len_j, int64_t* n_reff_nan, int64_t* n_out)
+{
+    PwRequest q = psis_reff_request(first_sample, walker_mask, thin, r_eff_j, split, max_lag, obs_first, obs_count, workspace_bytes);
+    q.ud = density; q.params = params;
+    PsisOut out;
+    out.tail = tail; out.m = m_j; out.xc = xc_j; out.n_tail = n_tail_j; out.tail_len = tail_len;
+    out.r_eff = r_eff_used; out.tail_len_j = tail_len_j; out.n_reff_nan = n_reff_nan;
     return psis(ChainSource(chain_host, nullptr, nsamples, nwalkers, ndim, device), q, out, n_out, nullptr);
 }
 

@@ -16,6 +16,8 @@
 //                        observation l % Jp of the run slot l / Jp, and loads its rows itself.  Grid (1, ceil(nruns / (slots kPwWaves))).
 //   pw_fold_body      -- one observation per thread: the runs' partials in run order; pass 1 also writes S1 / n for pass 2.
 //   pw_matrix         -- l[r][j] for the selected rows and the observations [obs_first, obs_first + obs_count): [n][obs_count], dense.
+//   pw_weights        -- v[r][j] = exp(l[r][j] - M_j) in groups of 64 observations, [n][64] each: the series whose effective sample
+//                        size is PSIS-LOO's relative efficiency.  A module of its own, "pointwise_weights:<ndim>".
 //   psis_walk, psis_fold_body, psis_fit_body -- PSIS-LOO over the same walk: below, with their own contract.
 #pragma once
 #include "kmc_device.hpp"
@@ -159,6 +161,46 @@ __device__ __forceinline__ void pw_matrix(const PwArgs& a)
     }
 }
 
+// The weight series behind PSIS-LOO's relative efficiency: v[k][j] = exp(l[k][j] - M_j) for the selected rows k in row order, with M_j
+// the exact maximum pass 1 left in a.stats.  IEEE rules: a column whose M_j is NaN or -inf is all NaN, l = -inf under a finite M_j gives
+// 0.0, the arg-max rows exactly 1.0.  Output in groups of 64 observations aligned to the absolute index: group g holds the observations
+// [64 g, 64 g + 64) as [n][64], a chain of ld = 64 the convergence kernels read where it lies; the lanes outside
+// [obs_first, obs_first + obs_count) are written as 0.0.  a.out: [gridDim.x][n][64], the groups group0 .. group0 + gridDim.x - 1.
+// pw_matrix's walk: one observation per lane, run_len rows per wave; grid (groups, ceil(ceil(n / run_len) / kPwWaves)).
+struct WeightArgs {
+    PwArgs  a;
+    int64_t group0;
+};
+
+template <class F, int ND, int NCOLS>
+__device__ __forceinline__ void pw_weights(const WeightArgs& q)
+{
+    const PwArgs& a = q.a;
+    const int lane = (int)(threadIdx.x & 63);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t wid = (int64_t)blockIdx.y * kPwWaves + wave;
+    const int64_t jg = (q.group0 + (int64_t)blockIdx.x) * 64 + lane;
+    const bool live = jg >= a.obs_first && jg < a.obs_first + a.obs_count;
+    const int64_t j = live ? jg : a.obs_first;                                         // (idle lanes hold a real observation, write 0.0)
+    const int64_t k0 = wid * a.run_len, k1 = k0 + a.run_len < a.n ? k0 + a.run_len : a.n;
+    if (k0 >= a.n) return;
+    double d[NCOLS];
+#pragma unroll
+    for (int c = 0; c < NCOLS; ++c) d[c] = a.data[j * NCOLS + c];
+    const double m = a.stats[j];
+    double* __restrict__ out = a.out + (int64_t)blockIdx.x * a.n * 64 + lane;
+    RowCursor cur(a, k0);
+    for (int64_t k = k0; k < k1; ++k) {
+        const double* row = cur.row(a);
+        double x[ND];
+#pragma unroll
+        for (int i = 0; i < ND; ++i) x[i] = row[i];
+        const double t = F::term(x, ND, d, a.p);
+        out[k * 64] = live ? exp(t - m) : 0.0;
+        cur.next(a);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------
 // PSIS-LOO (include/kissmcmc_hip.h).  The terms are recomputed in every pass, by the walk of pw_partials over
 // the runs of the same plan; a block of observations [obs_first, obs_first + obs_count) is in work at a time, and every buffer below
@@ -170,6 +212,8 @@ __device__ __forceinline__ void pw_matrix(const PwArgs& a)
 //   psis_walk<MODE = 2>  x > xc_j goes to the tail through the observation's integer cursor; the others' exp(x) are summed in row order
 //   psis_fold_body       one column per thread: the runs' minima / counts in run order; the last digit also gives xc_j
 //   psis_fit_kernel      one workgroup per column: bitonic sort of the tail in LDS, then kmc_psis_fit.hpp
+// With Mj the rank looked for is the column's own M_j; the strict tail rule keeps n_tail_j <= M_j <= M, so the stride of the tail, the
+// gather's bound and the sort's length stay those of M = max_j M_j.
 struct PsisArgs {
     PwArgs    a;            // obs_first / obs_count: the block in work
     double*   runval;       // [nruns][obs_count]: the runs' minima (MODE 0), then their sums outside the tail (MODE 2)
@@ -181,8 +225,9 @@ struct PsisArgs {
     int32_t*  cursor;       // [obs_count]: entries x > xc_j met so far
     double*   tail;         // [obs_count][M]: unordered after MODE 2, ascending and padded with NaN after the fit
     double*   res;          // [4][obs_count]: elpd_loo_j, pareto_k, n_tail_j, sigma
-    int32_t   M;
+    int32_t   M;            // the tail length; with Mj the largest of them: the stride of tail, what the fit kernel sorts
     int32_t   shift;        // of the current digit
+    const int32_t* Mj;      // [obs_count]: the tail length of each observation (a per-observation r_eff); nullptr: M for all
 };
 
 // the lane's observation, run and column
@@ -279,7 +324,7 @@ __device__ __forceinline__ void psis_fold_body(const PsisArgs& q, int stage)
         }
         q.m[col] = acc - acc == 0.0 ? acc : __builtin_nan("");                     // (NaN among the terms, or no finite minimum)
         q.prefix[col] = 0;
-        q.rank[col] = q.M;
+        q.rank[col] = q.Mj ? q.Mj[col] : q.M;
         q.cursor[col] = 0;
         return;
     }
@@ -347,7 +392,8 @@ __device__ __forceinline__ void psis_fit_body(const PsisArgs& q, int sort_len)
         return;
     }
     int nt = q.cursor[col];
-    nt = nt < q.M ? nt : q.M;
+    const int cap = q.Mj ? q.Mj[col] : q.M;
+    nt = nt < cap ? nt : cap;
     for (int t = tid; t < sort_len; t += kFitLanes) xs[t] = t < nt ? tail[t] : INFINITY;
     __syncthreads();
     for (int size = 2; size <= sort_len; size <<= 1)

@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, waic, pointwise_loglike, loo, compare_loo, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, waic, pointwise_loglike, loo, compare_loo, relative_eff, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -837,33 +837,71 @@ function pointwise_loglike(pdf::DataDensity, thetas; first_sample=0, thin=1, wal
 end
 
 """
-    loo(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, r_eff=1.0, obs=nothing, workspace=0, device=0)
+    loo(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, r_eff=1.0, obs=nothing, workspace=0, device=0, split=true, max_lag=0)
 
 PSIS-LOO of the data density `pdf` over the posterior sample `thetas[walker][sample]`: the rows are those of `waic` (at least 5), the
 observations `obs = (first, count)`, 0-based (all by default).  Selected, fitted and smoothed on the GPU (`kmc_chain_psis_loo`), the host
 stage is `kmc_loo_stats`; the definition is in include/kissmcmc_hip.h.  Returns a named tuple `(elpd_loo, se, p_loo, looic, lppd, n_nan,
 k_counts, n, elpd_loo_j, p_loo_j, pareto_k, n_tail_j, lppd_j)`; `k_counts` counts `pareto_k <= 0.5`, `(0.5, 0.7]`, `(0.7, 1]` and `> 1`;
-`n_tail_j` is -1 for an observation whose outputs are NaN.  `r_eff` is one number.
+`n_tail_j` is -1 for an observation whose outputs are NaN.  `r_eff` is one number, a vector with one entry per observation asked for, or
+`:chain` to compute it per observation from the chain (`kmc_chain_psis_loo_reff`; `split`, `max_lag` as `relative_eff`); the tuple then
+also holds `r_eff_j`, `tail_len_j` and `n_reff_nan`.
 """
-function loo(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, r_eff=1.0, obs=nothing, workspace=0, device=0)
+function loo(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, r_eff=1.0, obs=nothing, workspace=0, device=0, split=true, max_lag=0)
     chain, _, ns, nw, nd = _summary_chain(thetas, nothing)
     mask = _summary_mask(walkers, nw)
     first, count = obs === nothing ? (0, pdf.ndata) : obs
     stats = Matrix{Float64}(undef, max(count, 1), 4)      # column-major [count, 4] is the C ABI's [4][count]
     lppd_j = Vector{Float64}(undef, max(count, 1))
     n = Ref{Int64}(0)
-    st = ccall((:kmc_chain_psis_loo, LIB), Cint,
-               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Float64, Int64, Int64, Int64, Cint,
-                Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
-               pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin, Float64(r_eff),
-               first, count, workspace, Cint(device), stats, lppd_j, n, C_NULL)
-    st == 0 || error("kmc_chain_psis_loo failed ($st): $(last_error())")
+    r_eff_j = fill(NaN, max(count, 1)); tail_len_j = zeros(Int64, max(count, 1)); n_reff_nan = Ref{Int64}(0)
+    if r_eff isa Real
+        st = ccall((:kmc_chain_psis_loo, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Float64, Int64, Int64, Int64, Cint,
+                    Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+                   pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin, Float64(r_eff),
+                   first, count, workspace, Cint(device), stats, lppd_j, n, C_NULL)
+        st == 0 || error("kmc_chain_psis_loo failed ($st): $(last_error())")
+    else
+        r_eff === :chain || length(r_eff) == count || error("r_eff must have one entry per observation asked for ($count)")
+        given = r_eff === :chain ? C_NULL : Vector{Float64}(r_eff)
+        st = ccall((:kmc_chain_psis_loo_reff, LIB), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Ptr{Float64}, Int32, Int64, Int64, Int64,
+                    Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                   pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin, given,
+                   Int32(split), max_lag, first, count, workspace, Cint(device), stats, lppd_j, r_eff_j, tail_len_j, n_reff_nan, n, C_NULL)
+        st == 0 || error("kmc_chain_psis_loo_reff failed ($st): $(last_error())")
+    end
     p_loo_j = similar(lppd_j); tot = Vector{Float64}(undef, 10)
     st = ccall((:kmc_loo_stats, LIB), Cint, (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                count, n[], stats, lppd_j, p_loo_j, tot)
     st == 0 || error("kmc_loo_stats failed ($st): $(last_error())")
     return (elpd_loo=tot[1], se=tot[2], p_loo=tot[3], looic=tot[4], lppd=tot[5], n_nan=Int(tot[6]), k_counts=Tuple(Int.(tot[7:10])), n=n[],
-            elpd_loo_j=stats[:, 1], p_loo_j=p_loo_j, pareto_k=stats[:, 2], n_tail_j=[isnan(v) ? -1 : Int(v) for v in stats[:, 3]], lppd_j=lppd_j)
+            elpd_loo_j=stats[:, 1], p_loo_j=p_loo_j, pareto_k=stats[:, 2], n_tail_j=[isnan(v) ? -1 : Int(v) for v in stats[:, 3]], lppd_j=lppd_j,
+            r_eff_j=r_eff isa Real ? fill(Float64(r_eff), max(count, 1)) : r_eff_j, tail_len_j=tail_len_j, n_reff_nan=n_reff_nan[])
+end
+
+"""
+    relative_eff(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, obs=nothing, split=true, max_lag=0, workspace=0, device=0)
+
+The relative efficiency of PSIS-LOO's importance weights per observation (`kmc_chain_relative_eff`): `r_eff_j = ess_j / (m h)` with
+`ess`, `m`, `h` those of `convergence` on the series `exp(l[k][j] - max_r l[r][j])` of the selected rows.  Returns a named tuple
+`(r_eff_j, ess_j, lag, truncated, m, h, n)`; `obs = (first, count)`, 0-based.  `r_eff_j` is NaN for a constant column and may exceed 1.
+"""
+function relative_eff(pdf::DataDensity, thetas; first_sample=0, thin=1, walkers=nothing, obs=nothing, split=true, max_lag=0, workspace=0, device=0)
+    chain, _, ns, nw, nd = _summary_chain(thetas, nothing)
+    mask = _summary_mask(walkers, nw)
+    first, count = obs === nothing ? (0, pdf.ndata) : obs
+    k = max(count, 1)
+    r = fill(NaN, k); ess = fill(NaN, k); T = zeros(Int64, k); flags = zeros(Int32, k)
+    m = Ref{Int64}(0); h = Ref{Int64}(0); n = Ref{Int64}(0)
+    st = ccall((:kmc_chain_relative_eff, LIB), Cint,
+               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int64, Int64, Int64, Int32, Int64, Int64, Cint,
+                Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               pdf.handle, _pointwise_params(pdf), chain, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, thin, first, count,
+               Int32(split), max_lag, workspace, Cint(device), r, ess, T, flags, m, h, n, C_NULL)
+    st == 0 || error("kmc_chain_relative_eff failed ($st): $(last_error())")
+    return (r_eff_j=r, ess_j=ess, lag=T, truncated=(flags .& Int32(2)) .!= 0, m=m[], h=h[], n=n[])
 end
 
 """

@@ -101,4 +101,9 @@ end
     @test part.elpd_loo_j == w.elpd_loo_j[18:57]
     d = compare_loo(w, w)
     @test d.elpd_diff == 0.0 && d.J == 200
+    # r_eff from the chain: the call with its own r_eff_j given back returns the same bits
+    re = relative_eff(pdf, thetas)
+    wc = loo(pdf, thetas; r_eff=:chain)
+    @test wc.r_eff_j == re.r_eff_j && wc.n_reff_nan == 0 && all(wc.tail_len_j .>= 1)
+    @test loo(pdf, thetas; r_eff=wc.r_eff_j).elpd_loo_j == wc.elpd_loo_j
 end

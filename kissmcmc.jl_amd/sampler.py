@@ -586,19 +586,36 @@ class Sampler:
         from .chain_predictive import sampler_waic
         return sampler_waic(self, first_sample, thin, walkers, data)
 
-    def loo(self, first_sample: int = 0, thin: int = 1, walkers=None, r_eff: float = 1.0, obs=None, workspace=None, with_info: bool = False):
+    def loo(self, first_sample: int = 0, thin: int = 1, walkers=None, r_eff=1.0, obs=None, workspace=None, with_info: bool = False,
+            split: bool = True, max_lag=None, r_eff_j=None):
         """PSIS-LOO of the sampler's :class:`DataDensity` over the stored chain -- the samples ``first_sample, first_sample + thin, ...`` of
         the walkers ``walkers`` -- smoothed on the device (``kmc_sampler_psis_loo``): a dict ``elpd_loo, se, p_loo, looic, lppd, n, tail_len,
-        n_nan, k_counts`` and the arrays ``elpd_loo_j, p_loo_j, pareto_k, n_tail_j, lppd_j``; ``obs = (first, count)`` restricts the
-        observations.  See :func:`kissmcmc_jl_amd.loo`."""
+        n_nan, n_reff_nan, k_counts`` and the arrays ``elpd_loo_j, p_loo_j, pareto_k, n_tail_j, lppd_j, r_eff_j, tail_len_j``; ``obs =
+        (first, count)`` restricts the observations.  ``r_eff`` is one number or ``"chain"``, which computes it per observation from the
+        chain; ``r_eff_j`` gives it as an array with one entry per observation (``kmc_sampler_psis_loo_reff``; ``split``, ``max_lag`` as :meth:`relative_eff`).
+        See :func:`kissmcmc_jl_amd.loo`."""
         from .chain_loo import sampler_loo
-        return sampler_loo(self, first_sample, thin, walkers, r_eff, obs, workspace, with_info)
+        return sampler_loo(self, first_sample, thin, walkers, r_eff, obs, workspace, with_info, split, max_lag, r_eff_j)
 
-    def psis_tail(self, first_sample: int = 0, thin: int = 1, walkers=None, r_eff: float = 1.0, obs=None, workspace=None):
-        """The shift, the cut-off and the sorted tail of every observation, as :meth:`loo` selects them (``kmc_sampler_psis_tail``); see
-        :func:`kissmcmc_jl_amd.psis_tail`."""
+    def psis_tail(self, first_sample: int = 0, thin: int = 1, walkers=None, r_eff=1.0, obs=None, workspace=None, split: bool = True, max_lag=None,
+                  r_eff_j=None):
+        """The shift, the cut-off and the sorted tail of every observation, as :meth:`loo` selects them (``kmc_sampler_psis_tail``,
+        ``kmc_sampler_psis_tail_reff``); ``r_eff`` and ``r_eff_j`` are :meth:`loo`'s.  See :func:`kissmcmc_jl_amd.psis_tail`."""
         from .chain_loo import sampler_psis_tail
-        return sampler_psis_tail(self, first_sample, thin, walkers, r_eff, obs, workspace)
+        return sampler_psis_tail(self, first_sample, thin, walkers, r_eff, obs, workspace, split, max_lag, r_eff_j)
+
+    def relative_eff(self, first_sample: int = 0, thin: int = 1, walkers=None, obs=None, split: bool = True, max_lag=None, workspace=None,
+                     with_info: bool = False):
+        """The relative efficiency of PSIS-LOO's importance weights per observation, from the stored chain (``kmc_sampler_relative_eff``):
+        a dict ``r_eff_j, ess_j, lag, truncated, m, h, n``; see :func:`kissmcmc_jl_amd.relative_eff`."""
+        from .chain_loo import sampler_relative_eff
+        return sampler_relative_eff(self, first_sample, thin, walkers, obs, split, max_lag, workspace, with_info)
+
+    def pointwise_weights(self, first_sample: int = 0, thin: int = 1, walkers=None, obs=None, data=None):
+        """``(v, M_j)``: the series ``v[n, stop - first] = exp(l - M_j)`` of the selected rows and the observations ``obs = (first, stop)``
+        and the column maxima (``kmc_sampler_pointwise_weights``); see :func:`kissmcmc_jl_amd.pointwise_weights`."""
+        from .chain_loo import sampler_pointwise_weights
+        return sampler_pointwise_weights(self, first_sample, thin, walkers, obs, data)
 
     def pointwise_loglike(self, first_sample: int = 0, thin: int = 1, walkers=None, obs=None, data=None):
         """The matrix ``l[r, j] = term(x_r, d_j)`` of the selected rows of the stored chain and the observations ``obs = (first, stop)``

@@ -12,6 +12,15 @@ Per shape (a DataDensity over the regression term, chain stored on the device), 
 All are blocking calls; each is bracketed by HIP events (recorded on an otherwise idle stream, so their distance is the time the call
 took, host work included) and by the host clock.  Reported: the median over the child processes with min / max.
 P32 is thinned by 2: unthinned its 2 048 000 rows ask for a tail of 4 294 draws, which the library refuses (M > 4096).
+
+``--reff`` measures the relative efficiency per observation instead (S1 and S2; written under "relative_eff" of the same file), per child:
+  scalar     Sampler.loo(thin=..., r_eff=1.0) on this build, as above; with ``--parent-root DIR`` (a checkout of the parent commit with its
+             library built) the same call by that checkout's own copy of this script, in the same session: the yardstick of the scalar path.
+  stage      Sampler.relative_eff(thin=...): pass 1, the weight passes and the ESS stage (chain moments, lag blocks and their copies, group
+             by group) from the library's own events; WAIC's pass 2 in the same process -- the same walk, one exp per term -- stands
+             beside a weight pass.
+  chain      Sampler.loo(r_eff="chain") at the shape's thinning, doubled until no observation asks for more than 4096 draws.
+  over       the observations whose computed r_eff_j asks for M > 4096 unthinned.
 """
 import argparse
 import json
@@ -92,6 +101,92 @@ def child(idx):
                                       **err)), flush=True)
 
 
+def child_reff(idx):
+    import kissmcmc_jl_amd as kmc
+    from kissmcmc_jl_amd import chain_predictive, summary
+    import psis_yardstick as Y
+    name, nw, nd, J, ns, thin = CASES[idx]
+    nburn = 20
+    D, beta = make_data(J, nd)
+    pdf = kmc.DataDensity(REG_TERM, D, params=[4.0])
+    th = beta + 0.05 * np.random.default_rng(0).standard_normal((nw, nd))
+
+    def over(re):
+        r = re["r_eff_j"]
+        M = np.array([Y.tail_length(re["n"], x if np.isfinite(x) and x > 0 else 1.0) for x in r])
+        return int((M > 4096).sum()), int(M.max())
+
+    with kmc.Sampler(pdf, nw, nd, nburn + ns, nburn, 1, 2.0, 3, store_chain=True) as s:
+        s.set_positions(th)
+        s.run(nburn + ns)
+        s.sync()
+        s.loo(thin=thin)
+        base, b_ev, _ = bracket(lambda: s.loo(thin=thin, with_info=True))
+        s.relative_eff(thin=thin)
+        re, r_ev, _ = bracket(lambda: s.relative_eff(thin=thin, with_info=True))
+        waic_info = chain_predictive.pointwise_stats_from(summary._SamplerProvider(s), pdf, thin)["info"]
+        un = re if thin == 1 else s.relative_eff(thin=1)
+        n_over_unthinned, m_max_unthinned = over(un)
+        t = thin
+        while over(re if t == thin else s.relative_eff(thin=t))[0] > 0:
+            t *= 2
+        s.loo(thin=t, r_eff="chain")
+        ch, c_ev, _ = bracket(lambda: s.loo(thin=t, r_eff="chain", with_info=True))
+        b2, b2_ev, _ = (base, b_ev, 0.0) if t == thin else bracket(lambda: s.loo(thin=t, with_info=True))
+    r = re["r_eff_j"]
+    ri, ci = re["info"], ch["info"]
+    print("RESULT " + json.dumps(dict(case=name, scalar_ms=b_ev, relative_eff_ms=r_ev, pass1_ms=ri["ns_pass1"] * 1e-6, weights_ms=ri["ns_weights"] * 1e-6,
+                                      ess_ms=ri["ns_ess"] * 1e-6, waic_pass2_ms=int(waic_info[5]) * 1e-6, groups=ri["groups"], n=int(re["n"]), m=re["m"], h=re["h"],
+                                      r_eff_min=float(np.nanmin(r)), r_eff_median=float(np.nanmedian(r)), r_eff_max=float(np.nanmax(r)),
+                                      lag_max=int(re["lag"].max()), truncated=int(re["truncated"].sum()), n_reff_nan=int(np.isnan(r).sum()),
+                                      n_over_4096_unthinned=n_over_unthinned, tail_len_max_unthinned=m_max_unthinned, chain_thin=t, chain_n=int(ch["n"]),
+                                      chain_ms=c_ev, scalar_at_chain_thin_ms=b2_ev, chain_weights_ms=ci["ns_weights"] * 1e-6, chain_ess_ms=ci["ns_ess"] * 1e-6,
+                                      chain_tail_len_min=int(ch["tail_len_j"].min()), chain_tail_len_max=int(ch["tail_len_j"].max()),
+                                      scalar_tail_len=int(b2["tail_len"]), chain_k_counts=list(ch["k_counts"]), scalar_k_counts=list(b2["k_counts"]),
+                                      chain_elpd_loo=ch["elpd_loo"], scalar_elpd_loo=b2["elpd_loo"])), flush=True)
+
+
+def run_children(cmd, name, repeats, env=None):
+    runs = []
+    for _ in range(repeats):
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, timeout=CHILD_TIMEOUT, env=env)
+        if p.returncode != 0:                         # a fault: nothing more is started on the device
+            raise SystemExit(f"child for {name} ended with status {p.returncode}")
+        runs.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1][7:]))
+    return runs
+
+
+def main_reff(a):
+    with open(a.out) as f:
+        rec = json.load(f)
+    out = dict(call="Sampler.relative_eff(thin=...) and Sampler.loo(thin=..., r_eff=\"chain\"); split, max_lag at their defaults",
+               timing="HIP events around each blocking call, one untimed call first; median of %d child processes (min, max); pass1 / weights / ess: "
+                      "the library's own events inside Sampler.relative_eff" % a.repeats,
+               yardsticks="scalar path: the parent commit's Sampler.loo(r_eff = 1) in the same session (parent_scalar_ms); a weight pass: WAIC's pass 2 "
+                          "in the same process (waic_pass2_ms)",
+               cases=[])
+    for idx in (int(v) for v in a.cases.split(",")):
+        name = CASES[idx][0]
+        env = dict(os.environ)
+        env.pop("KMC_LIB_PATH", None)
+        runs, prs = [], []
+        for _ in range(a.repeats):                    # this build and the parent's by turns: a drift of the machine meets both alike
+            runs += run_children([sys.executable, os.path.abspath(__file__), "--reff-child", str(idx)], name, 1)
+            if a.parent_root:
+                prs += run_children([sys.executable, os.path.join(a.parent_root, "scripts", "psis_loo_bench.py"), "--child", str(idx)], name + " (parent)", 1, env)
+        row = dict(case=name)
+        for k, v in runs[0].items():
+            row[k] = spread([r[k] for r in runs]) if k.endswith("_ms") else v
+        if prs:
+            row["parent_scalar_ms"] = spread([r["device_ms"] for r in prs])
+        out["cases"].append(row)
+        print(json.dumps(row), flush=True)
+        rec["relative_eff"] = out
+        with open(a.out, "w") as f:
+            json.dump(rec, f, indent=1)
+    print("wrote", a.out)
+
+
 def spread(vals):
     return dict(median=float(np.median(vals)), min=float(min(vals)), max=float(max(vals)))
 
@@ -101,10 +196,18 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "psis_loo.json"))
     ap.add_argument("--child", type=int, default=-1)
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--cases", default=",".join(str(i) for i in range(len(CASES))))
+    ap.add_argument("--cases", default="")
+    ap.add_argument("--reff", action="store_true", help="measure the relative efficiency per observation (S1, S2) into the same file")
+    ap.add_argument("--reff-child", type=int, default=-1)
+    ap.add_argument("--parent-root", default="", help="a checkout of the parent commit with its library built: the scalar path's yardstick")
     a = ap.parse_args()
+    a.cases = a.cases or ("0,1" if a.reff else ",".join(str(i) for i in range(len(CASES))))
     if a.child >= 0:
         return child(a.child)
+    if a.reff_child >= 0:
+        return child_reff(a.reff_child)
+    if a.reff:
+        return main_reff(a)
     rec = dict(device="MI355X", density="DataDensity(REG_TERM), precision 4", call="Sampler.loo(thin=...): every walker, every thin-th stored sample, r_eff = 1",
                timing="HIP events around each blocking call, one untimed call first; median of %d child processes (min, max); stats / min / select / "
                       "gather / fit: the library's own events around each stage inside one call" % a.repeats,
