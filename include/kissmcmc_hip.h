@@ -887,6 +887,54 @@ kmc_status  kmc_chain_rank_convergence(const double* chain_host, const double* l
                                        double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
                                        int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
 
+/* ---- highest-density intervals of a stored chain, scanned on the device ----
+ * The narrowest interval that holds a given share of the draws of a column: what ArviZ's summary reports as hdi_3% / hdi_97% and the
+ * interval people quote for a skewed posterior, where it differs from the equal-tailed one of two quantiles.  The definition is ArviZ's
+ * unimodal rule (arviz.stats.stats._hdi) with the ties and the special values pinned; what follows is the definition.
+ *
+ * Draws.  Per column the N selected draws: the stored samples >= first_sample of the walkers in the mask, every one of them -- the N
+ * of kmc_sampler_order_stats; no split into halves, no middle sample left out.  Columns: every dimension and, when asked, the
+ * log-densities as the last.  The draws are sorted ascending by value as the rank sort above does it: zeros canonicalised (x + 0.0,
+ * so -0.0 sorts and is reported as +0.0), +-inf ordinary values, a chain of floats (KMC_F32) widened exactly.  x_(0) <= ... <= x_(N-1).
+ * Windows.  For a probability p, k = floor(p * N) evaluated in double as written; the windows are i = 0 .. N - k - 1 with the widths
+ * w_i = x_(i+k) - x_(i) in double.
+ * The rule.  The interval is [x_(i*), x_(i*+k)] with i* the window of the smallest width and, among equal widths, the smallest i.  A
+ * NaN width (inf - inf) loses to every number; if every width is NaN, i* = 0.  A column with a NaN among its draws gets NaN for both
+ * ends and i* = -1, and nan_count says how many; the other columns are unaffected.
+ * Exactness.  Both ends are elements of the chain, bit for bit, up to the sign of zero.  w_i is never negative, so the order
+ * "(is NaN, width, i)" is an unsigned compare of the bits of w (NaN mapped to all-ones) followed by i: a total order with a unique
+ * minimum.  Nothing depends on the launch geometry; two identical calls return the same bits, and kmc_sampler_hdi equals kmc_chain_hdi
+ * on the downloaded chain.
+ *
+ * Algorithm.  Gather and sort are those of the rank statistics on the unsplit selection, once for all
+ * probabilities.  Then a workgroup of 256 lanes scans 4096 consecutive window starts of one sorted column, keeping per probability its
+ * best (bits(w), i) in two 64-bit integers -- integer compares only, no atomics, no floating-point minimum -- and one wave per (column,
+ * probability) takes the minimum of the tiles' partials.  Work space: the sort's 16 B of keys per draw and column, its counts, and 16 B
+ * per (column, probability, tile); KMC_ERR_UNSUPPORTED, naming the sizes, when that does not fit -- never a partial answer.
+ *
+ * probs [nprob], 1 <= nprob <= 16, each with its own k.  lo, hi [nprob][ncols]; start [nprob][ncols] gets i*; *n_out (may be NULL)
+ * gets N; nan_count [ncols] (may be NULL); info (may be NULL) gets 6 numbers for benchmarks: N, the tiles of the scan per column, the
+ * bytes the scan loads (8 B per window start and 8 B per window and probability, times the columns), and the nanoseconds of the gather,
+ * the sort, and the scan with its fold.  The sampler's route runs on the sampler's own stream.
+ * KMC_ERR_BAD_ARG, naming the value: a prob that is not finite, <= 0 or >= 1; k < 1 (p N < 1) or k = N; nprob outside 1..16; N < 2; an
+ * empty selection; a null probs, lo, hi or start.  KMC_ERR_UNSUPPORTED: N >= 2^31 or more than 65535 columns (the sort's limits).  The
+ * other refusals are those of kmc_sampler_order_stats (no KMC_STORE_CHAIN, with_logp without KMC_STORE_LOGP, a streamed chain, a
+ * sharded or P2P sampler, a host chain that does not fit).  All from the sizes, before the device is touched, but the work space.
+ * A tempered sampler's chain is rung 0's.  Not built: ArviZ's multimodal intervals, circular variables, the MCSE of the ends, a column
+ * subset, sorting in column groups when the work space does not fit, several GPUs. */
+kmc_status  kmc_sampler_hdi(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int32_t with_logp,
+                            const double* probs, int32_t nprob, double* lo, double* hi, int64_t* start, int64_t* n_out, int64_t* nan_count,
+                            int64_t* info);
+/* The same on a chain in host memory, uploaded to `device` first.  The log-densities are the last column exactly when logp_host is
+ * not NULL. */
+kmc_status  kmc_chain_hdi(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                          int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                          const double* probs, int32_t nprob, int device, double* lo, double* hi, int64_t* start, int64_t* n_out,
+                          int64_t* nan_count, int64_t* info);
+/* k = floor(p * n) and the number of windows n - k for n draws, with the argument checks of the two calls above on n and p.  Needs
+ * no device; pointers may be NULL. */
+kmc_status  kmc_hdi_span(int64_t n, double p, int64_t* k, int64_t* nwindows);
+
 /* ---- the posterior covariance and correlation matrix of a stored chain, summed on the device ----
  * What a corner plot only shows: the covariance of every pair of columns over the selection -- the Gaussian approximation of the
  * posterior, the shape a proposal, a re-parametrisation or a new starting ball is built from.

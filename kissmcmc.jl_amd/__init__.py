@@ -21,7 +21,7 @@ from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
 from .metropolis import GaussianStep, HostProposal, metropolis, metropolis_chains
 from .sampler import Sampler
-from .summary import corner, credible_levels, hist_mode, histogram, map_sample, quantile_ranks, quantiles, summarize_run
+from .summary import corner, credible_levels, hdi, hdi_span, hist_mode, histogram, map_sample, quantile_ranks, quantiles, summarize_run
 from .tempering import geometric_betas, thermodynamic_integration
 
 __all__ = [
@@ -31,6 +31,7 @@ __all__ = [
     "quantiles", "quantile_ranks", "map_sample", "summarize_run", "histogram", "corner", "hist_mode", "credible_levels",
     "convergence", "convergence_stats", "lag_sums", "evaluate_convergence", "error_of_estimated_mean", "samples_vs_tau",
     "rank_convergence", "rank_scores", "rank_plan", "normal_scores",
+    "hdi", "hdi_span",
     "covariance", "correlation", "cov_plan",
     "waic", "pointwise_loglike", "pointwise_stats", "compare_waic", "waic_stats", "pointwise_plan",
     "loo", "compare_loo", "psis_plan", "loo_stats", "psis_smooth", "psis_tail", "relative_eff", "pointwise_weights",

@@ -64,6 +64,7 @@ SYMBOLS = [
     "kmc_convergence_plan",
     "kmc_rank_plan", "kmc_rank_normal_scores", "kmc_sampler_rank_scores", "kmc_chain_rank_scores", "kmc_sampler_rank_convergence",
     "kmc_chain_rank_convergence",
+    "kmc_sampler_hdi", "kmc_chain_hdi", "kmc_hdi_span",
     "kmc_sampler_covariance", "kmc_chain_covariance", "kmc_cov_plan", "kmc_cov_correlation",
     "kmc_sampler_pointwise_stats", "kmc_chain_pointwise_stats", "kmc_sampler_pointwise_loglike", "kmc_chain_pointwise_loglike",
     "kmc_pointwise_plan", "kmc_waic_stats",
@@ -300,6 +301,9 @@ def lib() -> C.CDLL:
     L.kmc_chain_rank_scores.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int, ip, dp, dp, ip, ip, ip]
     L.kmc_sampler_rank_convergence.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64] + [dp] * 10 + [ip, i32p, ip, ip, ip]
     L.kmc_chain_rank_convergence.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int] + [dp] * 10 + [ip, i32p, ip, ip, ip]
+    L.kmc_sampler_hdi.argtypes = [vp, C.c_int64, bp, C.c_int32, dp, C.c_int32, dp, dp, ip, ip, ip, ip]
+    L.kmc_chain_hdi.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, dp, C.c_int32, C.c_int, dp, dp, ip, ip, ip, ip]
+    L.kmc_hdi_span.argtypes = [C.c_int64, C.c_double, ip, ip]
     L.kmc_sampler_covariance.argtypes = [vp, C.c_int64, bp, C.c_int32, dp, dp, ip, ip]
     L.kmc_chain_covariance.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int, dp, dp, ip, ip]
     L.kmc_cov_plan.argtypes = [C.c_int64, i32p, i32p, i32p, i32p]

@@ -1,5 +1,5 @@
 // kmc_chain_kernels.hpp -- what the device kernels that read a stored chain where it lies share (kmc_summary_kernels.hpp,
-// kmc_hist_kernels.hpp, kmc_convergence_kernels.hpp, kmc_rank_kernels.hpp): the load of one element, the key whose unsigned order is the
+// kmc_hist_kernels.hpp, kmc_convergence_kernels.hpp, kmc_rank_kernels.hpp, kmc_hdi_kernels.hpp): the load of one element, the key whose unsigned order is the
 // value order, and the decode of a position of a row for the kernels that select walkers by a rank table.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>

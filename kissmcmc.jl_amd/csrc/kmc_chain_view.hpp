@@ -1,5 +1,5 @@
 // kmc_chain_view.hpp -- what the calls that read a stored chain where it lies share on the host side (kmc_summary.hip, kmc_hist.hip,
-// kmc_convergence.hip, kmc_rank.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
+// kmc_convergence.hip, kmc_rank.hip, kmc_hdi.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
 // such a view -- the chain a sampler holds, or a dense host chain uploaded for the call.  Internal.
 #pragma once
 #include "kmc_host.hpp"

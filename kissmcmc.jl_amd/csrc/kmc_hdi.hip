@@ -1,0 +1,183 @@
+// kmc_hdi.hip -- highest-density intervals of a stored chain, scanned on the device: per column the narrowest interval that holds
+// k = floor(p N) + 1 consecutive draws of the sorted selection (ArviZ's unimodal rule with the ties and the special values pinned:
+// include/kissmcmc_hip.h).  Gather and sort are those of the rank statistics (kmc_rank_host.hpp), on an unsplit
+// shape; the scan over the sorted columns is here.  Kernels: kmc_hdi_kernels.hpp.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <vector>
+
+#include "kmc_chain_view.hpp"
+#include "kmc_hdi_kernels.hpp"
+#include "kmc_rank_host.hpp"
+
+using namespace kmc_host;
+using namespace kmc_chain_view;
+using namespace kmc_conv_host;
+using namespace kmc_rank_host;
+using namespace kmc_hdi;
+
+namespace {
+
+struct HdiBuffers {
+    uint64_t *part = nullptr, *out = nullptr;
+    ~HdiBuffers() { (void)hipFree(part); (void)hipFree(out); }
+};
+
+// the events around the three stages, for info: gather, sort, scan + fold
+struct StageEvents {
+    hipEvent_t e[4] = {};
+    hipError_t create()
+    {
+        for (auto& x : e) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
+        return hipSuccess;
+    }
+    ~StageEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+std::string num(double x)
+{
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", x);
+    return buf;
+}
+
+// k = floor(p n) in double as written, and the refusals that need only n and p
+kmc_status span(int64_t n, double p, int64_t* k)
+{
+    if (!std::isfinite(p) || p <= 0.0 || p >= 1.0) return fail(KMC_ERR_BAD_ARG, "prob must be finite and lie in (0, 1) (prob = " + num(p) + ")");
+    if (n < 2) return fail(KMC_ERR_BAD_ARG, "an interval needs at least 2 draws (N = " + std::to_string(n) + ")");
+    if (n >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "2^31 draws or more per column (N = " + std::to_string(n) + ")");
+    const int64_t kk = (int64_t)std::floor(p * (double)n);
+    if (kk < 1) return fail(KMC_ERR_BAD_ARG, "prob * N < 1: no draw besides the first lies in the interval (prob = " + num(p) + ", N = " + std::to_string(n) + ")");
+    if (kk > n - 1) return fail(KMC_ERR_BAD_ARG, "floor(prob * N) = N: no window is left (prob = " + num(p) + ", N = " + std::to_string(n) + ")");
+    *k = kk;
+    return KMC_OK;
+}
+
+template <int P>
+void launch_scan(const HdiArgs& a, int64_t ncols, hipStream_t st)
+{
+    hipLaunchKernelGGL(hdi_scan<P>, dim3((unsigned)a.ntiles, (unsigned)ncols), dim3(kHdiThreads), 0, st, a);
+}
+
+kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask_host, const double* probs, int32_t nprob, double* lo, double* hi,
+               int64_t* start, int64_t* n_out, int64_t* nan_count, int64_t* info)
+{
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    if (!probs || !lo || !hi || !start) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (nprob < 1 || nprob > kHdiMaxProbs) return fail(KMC_ERR_BAD_ARG, "between 1 and 16 probabilities per call (nprob = " + std::to_string(nprob) + ")");
+    for (int p = 0; p < nprob; ++p)
+        if (!std::isfinite(probs[p]) || probs[p] <= 0.0 || probs[p] >= 1.0)
+            return fail(KMC_ERR_BAD_ARG, "prob must be finite and lie in (0, 1) (probs[" + std::to_string(p) + "] = " + num(probs[p]) + ")");
+    int64_t N = 0;
+    KMC_TRY(selection_size(v, first_sample, mask_host, &N));
+    if (n_out) *n_out = N;
+    const bool with_logp = src.with_logp;
+    const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
+    ConvShape sh;                                             // the unsplit shape: every selected walker one chain of all selected samples
+    sh.first = first_sample; sh.n = v.nsamples - first_sample; sh.nw = N / sh.n; sh.nhalf = 1; sh.h = sh.n; sh.m = sh.nw; sh.half_off = 0;
+    HdiArgs a{};
+    a.N = N; a.nprob = nprob;
+    int64_t kmin = 0, windows = 0;
+    for (int p = 0; p < nprob; ++p) {
+        KMC_TRY(span(N, probs[p], &a.k[p]));
+        kmin = p == 0 ? a.k[p] : std::min(kmin, a.k[p]);
+        windows += N - a.k[p];
+    }
+    KMC_TRY(rank_limits(sh, ncols));
+    a.ntiles = (N - kmin + kHdiTileStarts - 1) / kHdiTileStarts;
+    const size_t part_bytes = (size_t)ncols * (size_t)nprob * (size_t)a.ntiles * 2 * sizeof(uint64_t);
+    const size_t out_bytes = (size_t)ncols * (size_t)nprob * 3 * sizeof(uint64_t);
+
+    ConvBuffers b;
+    KMC_TRY(src.open(b, &v));
+    KMC_TRY(rank_room(sh, ncols, 0, false, (double)part_bytes + (double)out_bytes));
+    RankBuffers rb;
+    HdiBuffers hb;
+    // Never the legacy stream (kmc_host.hpp: copy_sync).  A sampler's own stream, which describe() has drained, serves: creating and
+    // destroying a stream for the call costs milliseconds, more than the whole call at a small shape.  (Declared after the buffers:
+    // the stream is drained before they go.)
+    ScopedStream ss;
+    if (src.host || !src.s->stream) HIP_TRY(ss.create());
+    else ss.borrowed = src.s->stream;
+    const hipStream_t st = ss.get();
+    StageEvents ev;
+    if (info) HIP_TRY(ev.create());
+    KMC_TRY(upload_rank(b, mask_host, v.nl, st));
+    KMC_TRY(rank_alloc(rb, ncols, N, false));
+    HIP_TRY(hipMalloc((void**)&hb.part, part_bytes));
+    HIP_TRY(hipMalloc((void**)&hb.out, out_bytes));
+    a.keys = rb.key_a; a.part = hb.part; a.out = hb.out;
+
+    std::vector<int64_t> nan;
+    if (info) HIP_TRY(hipEventRecord(ev.e[0], st));
+    KMC_TRY(gather(rb, b, v, sh, with_logp, false, st, &nan));
+    if (info) HIP_TRY(hipEventRecord(ev.e[1], st));
+    KMC_TRY(sort_columns(rb, ncols, N, st));
+    if (info) HIP_TRY(hipEventRecord(ev.e[2], st));
+    if (nprob == 1) launch_scan<1>(a, ncols, st);
+    else if (nprob <= 4) launch_scan<4>(a, ncols, st);
+    else launch_scan<kHdiMaxProbs>(a, ncols, st);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(hdi_fold, dim3((unsigned)(ncols * nprob)), dim3(kHdiLanes), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (info) HIP_TRY(hipEventRecord(ev.e[3], st));
+    std::vector<uint64_t> got((size_t)ncols * (size_t)nprob * 3);
+    HIP_TRY(copy_sync(got.data(), hb.out, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+
+    const double nan_v = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t c = 0; c < ncols; ++c) {
+        if (nan_count) nan_count[c] = nan[(size_t)c];
+        for (int p = 0; p < nprob; ++p) {
+            const uint64_t* g = &got[(size_t)((c * nprob + p) * 3)];
+            const int64_t at = (int64_t)p * ncols + c;
+            if (nan[(size_t)c] || g[0] == kHdiNone) {         // a NaN among the draws: no interval
+                lo[at] = hi[at] = nan_v;
+                start[at] = -1;
+            } else {
+                lo[at] = unkey(g[1]); hi[at] = unkey(g[2]);
+                start[at] = (int64_t)g[0];
+            }
+        }
+    }
+    if (info) {
+        info[0] = N; info[1] = a.ntiles;
+        info[2] = 8 * ncols * ((N - kmin) + windows);         // the scan's loads: key[i] once per start, key[i + k_p] per window
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
+            info[3 + k] = (int64_t)((double)ms * 1e6);
+        }
+    }
+    return KMC_OK;
+}
+
+}  // namespace
+
+// k = floor(p n) and the number of windows n - k, with the argument checks of the chain calls.  Touches no device.
+KMC_EXPORT kmc_status kmc_hdi_span(int64_t n, double p, int64_t* k, int64_t* nwindows)
+{
+    int64_t kk = 0;
+    KMC_TRY(span(n, p, &kk));
+    if (k) *k = kk;
+    if (nwindows) *nwindows = n - kk;
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_sampler_hdi(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t with_logp, const double* probs,
+                                      int32_t nprob, double* lo, double* hi, int64_t* start, int64_t* n_out, int64_t* nan_count, int64_t* info)
+{
+    return hdi(ChainSource(s, with_logp != 0, "kmc_chain_hdi"), first_sample, walker_mask, probs, nprob, lo, hi, start, n_out, nan_count, info);
+}
+
+KMC_EXPORT kmc_status kmc_chain_hdi(const double* chain_host, const double* logp_host, int64_t nsamples, int64_t nwalkers, int64_t ndim,
+                                    int64_t first_sample, const uint8_t* walker_mask, const double* probs, int32_t nprob, int device, double* lo,
+                                    double* hi, int64_t* start, int64_t* n_out, int64_t* nan_count, int64_t* info)
+{
+    return hdi(ChainSource(chain_host, logp_host, nsamples, nwalkers, ndim, device), first_sample, walker_mask, probs, nprob, lo, hi, start,
+               n_out, nan_count, info);
+}

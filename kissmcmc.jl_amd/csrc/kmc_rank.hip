@@ -11,31 +11,25 @@
 
 #include "kmc_chain_view.hpp"
 #include "kmc_convergence_host.hpp"
+#include "kmc_rank_host.hpp"
 #include "kmc_rank_kernels.hpp"
 
 using namespace kmc_host;
 using namespace kmc_chain_view;
 using namespace kmc_conv_host;
 using namespace kmc_rank;
+using namespace kmc_rank_host;
 
 namespace {
 
 constexpr int kTransforms = 4;                               // bulk z, folded z, I05, I95: the column sets of the scratch chain
 
-struct RankBuffers {
-    uint64_t *key_a = nullptr, *key_b = nullptr, *picked = nullptr;
-    uint32_t* counts = nullptr;
-    unsigned long long* nan = nullptr;
-    double *centre = nullptr, *out_z = nullptr;
-    int64_t* out_rank2 = nullptr;
-    ~RankBuffers()
-    {
-        (void)hipFree(key_a); (void)hipFree(key_b); (void)hipFree(picked); (void)hipFree(counts); (void)hipFree(nan); (void)hipFree(centre);
-        (void)hipFree(out_z); (void)hipFree(out_rank2);
-    }
-};
-
 int64_t tiles_of(int64_t S) { return (S + kRankTileKeys - 1) / kRankTileKeys; }
+
+}  // namespace
+
+// ---- the sort's host side, shared with kmc_hdi.hip (kmc_rank_host.hpp) ----
+namespace kmc_rank_host {
 
 // the sizes one call may have, from the shape alone
 kmc_status rank_limits(const ConvShape& sh, int64_t ncols)
@@ -47,12 +41,12 @@ kmc_status rank_limits(const ConvShape& sh, int64_t ncols)
 }
 
 // The work space: two key buffers (16 B), the digit counts, and 8 B per transformed column (or 16 B for rank2 and z), per pooled draw.
-kmc_status rank_room(const ConvShape& sh, int64_t ncols, int transformed, bool outputs)
+kmc_status rank_room(const ConvShape& sh, int64_t ncols, int transformed, bool outputs, double extra)
 {
     const int64_t S = sh.m * sh.h;
     const double keys = 16.0 * (double)ncols * (double)S, counts = 4.0 * kRankBins * (double)tiles_of(S) * (double)ncols;
     const double scratch = 8.0 * (double)transformed * (double)ncols * (double)sh.n * (double)sh.nw, outs = outputs ? 16.0 * (double)ncols * (double)S : 0.0;
-    const double need = keys + counts + scratch + outs + 64.0 * 1048576.0;
+    const double need = keys + counts + scratch + outs + extra + 64.0 * 1048576.0;
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     if (need > (double)free_b)
@@ -130,6 +124,10 @@ double unkey(uint64_t key)
     std::memcpy(&x, &bits, sizeof x);
     return x;
 }
+
+}  // namespace kmc_rank_host
+
+namespace {
 
 // The quantiles 0.5, 0.05, 0.95 of the sorted columns in key_a by the rule of the order statistics (kmc.quantile_ranks with N = S):
 // h = q (S - 1), lo = floor(h), hi = min(lo + 1, S - 1), frac = h - lo, x_lo + frac (x_hi - x_lo), and x_lo itself where frac == 0.

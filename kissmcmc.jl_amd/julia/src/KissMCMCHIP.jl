@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, covariance, waic, pointwise_loglike, loo, compare_loo, relative_eff, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, hdi, covariance, waic, pointwise_loglike, loo, compare_loo, relative_eff, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -943,6 +943,41 @@ function rank_scores(thetas; logdensities=nothing, first_sample=0, walkers=nothi
                Int32(folded ? 1 : 0), Cint(device), rank2, z, centre, nan_count, m, h)
     st == 0 || error("kmc_chain_rank_scores failed ($st): $(last_error())")
     return (rank2=rank2, z=z, centre=folded ? centre : nothing, nan_count=nan_count, S=m[] * h[], m=m[], h=h[])
+end
+
+"""
+    hdi(thetas; prob=0.94, logdensities=nothing, first_sample=0, walkers=nothing, device=0)
+
+Highest-density intervals per dimension of `thetas[walker][sample]` as `emcee` / `metropolis_chains` return it (and of `logdensities`, as
+a last column, when given): the narrowest interval `[x_(i), x_(i + k)]` of the sorted draws with `k = floor(prob * N)`, the smallest `i`
+among equal widths, sorted and scanned on the GPU (`kmc_chain_hdi`; the definition is in include/kissmcmc_hip.h).  Returns a named tuple
+`(lo, hi, width, start, k, n, has_nan)`: vectors over the columns for a scalar `prob`, `nprob x ncols` matrices for a vector of up to 16;
+`start` is 0-based, -1 with NaN ends for a column that holds a NaN.
+"""
+function hdi(thetas; prob=0.94, logdensities=nothing, first_sample=0, walkers=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    ncols = nd + (logp === nothing ? 0 : 1)
+    probs = prob isa Number ? Float64[prob] : collect(Float64, prob)
+    np = length(probs)
+    lo = fill(NaN, ncols, np); hi = fill(NaN, ncols, np); start = fill(Int64(-1), ncols, np)       # column-major: C's [nprob][ncols]
+    nan_count = zeros(Int64, ncols); n = Ref{Int64}(0)
+    st = ccall((:kmc_chain_hdi, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Ptr{Float64}, Int32, Cint,
+                Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, probs, Int32(np), Cint(device),
+               lo, hi, start, n, nan_count, C_NULL)
+    st == 0 || error("kmc_chain_hdi failed ($st): $(last_error())")
+    k = Vector{Int64}(undef, np)
+    for (i, p) in enumerate(probs)
+        ki = Ref{Int64}(0)
+        st = ccall((:kmc_hdi_span, LIB), Cint, (Int64, Float64, Ptr{Int64}, Ptr{Int64}), n[], p, ki, C_NULL)
+        st == 0 || error("kmc_hdi_span failed ($st): $(last_error())")
+        k[i] = ki[]
+    end
+    has_nan = nan_count .> 0
+    prob isa Number && return (lo=lo[:, 1], hi=hi[:, 1], width=hi[:, 1] .- lo[:, 1], start=start[:, 1], k=k[1], n=n[], has_nan=has_nan)
+    return (lo=permutedims(lo), hi=permutedims(hi), width=permutedims(hi .- lo), start=permutedims(start), k=k, n=n[], has_nan=has_nan)
 end
 
 # make_theta0s (src/samplers.jl:311-349) and squash_walkers (src/samplers.jl:372-428): KissMCMC's own, imported above.

@@ -107,3 +107,16 @@ end
     @test wc.r_eff_j == re.r_eff_j && wc.n_reff_nan == 0 && all(wc.tail_len_j .>= 1)
     @test loo(pdf, thetas; r_eff=wc.r_eff_j).elpd_loo_j == wc.elpd_loo_j
 end
+
+@testset "highest-density intervals" begin
+    # the exponential is skewed: its 94 % highest-density interval starts below the 3 % quantile and is narrower than the equal-tailed one
+    logpdf = Exponential(1.0)
+    theta0 = make_theta0s(0.5, 0.1, logpdf, 100)
+    thetas, _, _ = emcee(logpdf, theta0; niter=10^5, use_progress_meter=false)
+    h = hdi(thetas; prob=0.94)
+    q = quantiles(thetas, [0.03, 0.97])
+    @test h.n == 10^5 ÷ 2 && h.k >= 1 && h.start[1] >= 0 && !h.has_nan[1]
+    @test 0 <= h.lo[1] <= q[1, 1] && h.width[1] < q[2, 1] - q[1, 1] && h.width[1] == h.hi[1] - h.lo[1]
+    two = hdi(thetas; prob=[0.5, 0.94])
+    @test two.lo[2, 1] == h.lo[1] && two.hi[2, 1] == h.hi[1] && two.width[1, 1] <= two.width[2, 1]
+end

@@ -571,6 +571,13 @@ class Sampler:
         from .chain_convergence import rank_columns, sampler_rank_convergence_raw
         return rank_columns(sampler_rank_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
 
+    def hdi(self, prob=0.94, first_sample: int = 0, walkers=None, logp: bool = False):
+        """Highest-density intervals of the stored chain (with ``logp=True`` the stored log-densities are the last column), sorted and
+        scanned on the device where it lies (``kmc_sampler_hdi``): a dict ``lo, hi, width, start, k, n, has_nan``, arrays ``[ncols]``
+        for a scalar ``prob`` and ``[nprob, ncols]`` for a sequence of up to 16; see :func:`kissmcmc_jl_amd.hdi`."""
+        from .summary import _SamplerProvider, hdi_from
+        return hdi_from(_SamplerProvider(self, first_sample, walkers), prob, logp)
+
     def covariance(self, first_sample: int = 0, walkers=None, logp: bool = False):
         """The covariance matrix of the stored chain (with ``logp=True`` the stored log-densities are the last column), summed on the
         device where it lies (``kmc_sampler_covariance``): a dict ``mean[C], cov[C, C], corr[C, C], std[C], n``; see
@@ -623,11 +630,12 @@ class Sampler:
         from .chain_predictive import sampler_pointwise_loglike
         return sampler_pointwise_loglike(self, first_sample, thin, walkers, obs, data)
 
-    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False, covariance=False):
+    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False, covariance=False, hdi=None):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
         from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain;
         ``convergence=True`` adds the columns ``rhat, ess, mcse`` of :meth:`convergence`, ``convergence="rank"`` also
-        ``rhat_rank, ess_bulk, ess_tail``; ``covariance=True`` adds the matrices ``cov`` and ``corr`` of :meth:`covariance`."""
+        ``rhat_rank, ess_bulk, ess_tail``; ``covariance=True`` adds the matrices ``cov`` and ``corr`` of :meth:`covariance`;
+        ``hdi=0.94`` adds the columns ``hdi_lo, hdi_hi`` of :meth:`hdi` for that probability."""
         from .summary import _SamplerProvider, quantiles_from, summary_columns
         p = _SamplerProvider(self)
         median = quantiles_from(p, [0.5])[0]
@@ -641,7 +649,7 @@ class Sampler:
             mean = flat.mean(axis=0)
             std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(self.ndim, np.nan)
         conv = self.convergence(rank=convergence == "rank") if convergence else None
-        cols = summary_columns(names, median, mean, std, mode, theta_true, eff_samples, conv)
+        cols = summary_columns(names, median, mean, std, mode, theta_true, eff_samples, conv, None if hdi is None else self.hdi(float(hdi)))
         if covariance:
             c = self.covariance()
             cols.update(cov=c["cov"], corr=c["corr"])

@@ -9,6 +9,10 @@ So are the marginal histograms of a corner plot (:func:`histogram`, :func:`corne
 ``kmc_chain_histograms``): every selected column's 1-D histogram and every pair's 2-D histogram, exact integer counts by numpy's
 binning rule.
 
+And the highest-density intervals (:func:`hdi`; ``kmc_sampler_hdi`` / ``kmc_chain_hdi``): every column sorted on the device by the
+sort of the rank statistics and scanned there for the narrowest window of ``floor(p N) + 1`` consecutive draws; both ends are elements
+of the chain.
+
 Input layout of the module-level functions: what ``emcee`` / ``metropolis_chains`` return, ``thetas[walker][sample]`` (scalar
 walkers) or ``thetas[walker][sample][dim]``, and ``logdensities[walker][sample]``.
 """
@@ -122,6 +126,22 @@ class _Provider:
         return c1, out, c2
 
 
+    def hdi(self, probs, logp=False):
+        """``(lo[nprob, ncols], hi[nprob, ncols], start[nprob, ncols], nan_count[ncols], info[6])`` of ``kmc_sampler_hdi`` /
+        ``kmc_chain_hdi`` for the probabilities ``probs``; the log-densities are the last column with ``logp``."""
+        self.require_logp(logp)
+        probs = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+        ncols = self.ndim + (1 if logp else 0)
+        lo, hi = np.full((probs.size, ncols), np.nan), np.full((probs.size, ncols), np.nan)
+        start, nan_count, info = np.full((probs.size, ncols), -1, dtype=np.int64), np.zeros(ncols, dtype=np.int64), np.zeros(6, dtype=np.int64)
+        n = C.c_int64()
+        self.call("hdi", [_p(probs, C.c_double), probs.size],
+                  [_p(lo, C.c_double), _p(hi, C.c_double), _p(start, C.c_int64), C.byref(n), _p(nan_count, C.c_int64), _p(info, C.c_int64)],
+                  logp, logp_at=0)
+        self.n = n.value
+        return lo, hi, start, nan_count, info
+
+
 class _SamplerProvider(_Provider):
     """The chain a :class:`Sampler` holds on the device (``kmc_sampler_*``)."""
 
@@ -201,6 +221,50 @@ def map_sample(thetas, logdensities, first_sample: int = 0, walkers=None, device
     """The stored sample of the largest log-density: ``(theta[ndim], logp, sample, walker)``; ties go to the smallest sample, then the
     smallest walker; NaN log-densities are ignored."""
     return _HostProvider(thetas, logdensities, first_sample, walkers, device).argmax()
+
+
+# ---- highest-density intervals ----------------------------------------------------------------------------------------------------
+
+MAX_PROBS = 16          # per call of the library (kmc_sampler_hdi)
+
+
+def hdi_span(n: int, prob: float):
+    """``(k, nwindows)`` for ``n`` draws and the probability ``prob``: ``k = floor(prob * n)`` in double and ``nwindows = n - k``, with
+    the library's refusals (``kmc_hdi_span``; needs no device): ``prob`` finite in (0, 1), ``n >= 2``, ``1 <= k <= n - 1``."""
+    k, w = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().kmc_hdi_span(int(n), float(prob), C.byref(k), C.byref(w)))
+    return k.value, w.value
+
+
+def hdi_from(provider, prob=0.94, logp=False, with_info=False):
+    """:func:`hdi` from a provider (``.hdi(probs, logp)``)."""
+    scalar = np.ndim(prob) == 0
+    probs = np.atleast_1d(np.asarray(prob, dtype=np.float64))
+    if probs.ndim != 1:
+        raise ValueError("prob must be a scalar or a 1-D sequence of probabilities")
+    lo, hi, start, nan_count, info = provider.hdi(probs, logp)
+    k = np.array([hdi_span(provider.n, p)[0] for p in probs.tolist()], dtype=np.int64)
+    with np.errstate(invalid="ignore"):
+        width = hi - lo
+    out = {"lo": lo, "hi": hi, "width": width, "start": start, "k": k}
+    if scalar:
+        out = {key: v[0] for key, v in out.items()}
+        out["k"] = int(out["k"])
+    out.update(n=provider.n, has_nan=nan_count > 0)
+    if with_info:
+        out.update(nan_count=nan_count, info=info)
+    return out
+
+
+def hdi(thetas, prob=0.94, logdensities=None, first_sample: int = 0, walkers=None, device: int = 0):
+    """Highest-density intervals per dimension of ``thetas[walker][sample](dim)`` (and, as a last column, of ``logdensities`` when
+    given), over the samples ``>= first_sample`` of the walkers ``walkers``: the narrowest interval ``[x_(i), x_(i + k)]`` of the
+    sorted draws with ``k = floor(prob * N)``, the smallest ``i`` among equal widths (ArviZ's unimodal rule; ``include/kissmcmc_hip.h``
+    has the definition), sorted and scanned on the GPU.  A dict ``lo, hi, width, start, k, n, has_nan``: arrays ``[ncols]`` for a
+    scalar ``prob``, ``[nprob, ncols]`` for a sequence of up to 16; both ends are elements of the chain, bit for bit; a column that
+    holds a NaN gets NaN ends, ``start = -1`` and ``has_nan``."""
+    p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
+    return hdi_from(p, prob, logp=p.logp is not None)
 
 
 # ---- marginal histograms and the corner table ------------------------------------------------------------------------------------
@@ -324,10 +388,11 @@ def credible_levels(hist2d, levels=(0.393, 0.865)):
     return h[idx]
 
 
-def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_samples=None, convergence=None):
+def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_samples=None, convergence=None, hdi=None):
     """The table of ``summarize_run`` (reference ``src/analysis.jl:14-38``) as a dict of columns, in the reference's order:
     ``var, [err,] median, mean, mode, std[, eff_samples]``; then ``rhat, ess, mcse`` when ``convergence`` (the dict of
-    :func:`kissmcmc_jl_amd.convergence`) is given, and ``rhat_rank, ess_bulk, ess_tail`` when it holds them (``rank=True``)."""
+    :func:`kissmcmc_jl_amd.convergence`) is given, and ``rhat_rank, ess_bulk, ess_tail`` when it holds them (``rank=True``); then
+    ``hdi_lo, hdi_hi`` when ``hdi`` (the dict of :func:`kissmcmc_jl_amd.hdi` for one probability) is given."""
     median, mean, std = (np.asarray(a, dtype=np.float64) for a in (median, mean, std))
     nt = median.size
     names = [str(i + 1) for i in range(nt)] if names is None else [str(v) for v in names]          # :9 names=["$i" for i=1:nt]
@@ -349,11 +414,13 @@ def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_sa
         for k in ("rhat", "ess", "mcse", "rhat_rank", "ess_bulk", "ess_tail"):
             if k in convergence:
                 cols[k] = np.asarray(convergence[k], dtype=np.float64)[:nt]
+    if hdi is not None:
+        cols["hdi_lo"], cols["hdi_hi"] = hdi["lo"][:nt], hdi["hi"][:nt]
     return cols
 
 
 def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_samples=None, provider=None, device: int = 0,
-                  convergence=False, covariance=False):
+                  convergence=False, covariance=False, hdi=None):
     """Summary statistics of a run, reference ``src/analysis.jl:9-42`` (commented out there; followed as written): a dict of columns
     ``var`` (the names, ``"1" .. "ndim"`` by default), ``err = |theta_true - median|`` (only with ``theta_true``), ``median``,
     ``mean``, ``mode``, ``std`` (Julia's: n - 1 in the denominator) and ``eff_samples`` (only when given, passed through).
@@ -366,7 +433,8 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     ``convergence=True`` adds the columns ``rhat``, ``ess`` and ``mcse`` of :func:`kissmcmc_jl_amd.convergence` (split chains, every
     walker a chain; computed on the device); ``convergence="rank"`` also ``rhat_rank``, ``ess_bulk`` and ``ess_tail`` of
     :func:`kissmcmc_jl_amd.rank_convergence`.  ``covariance=True`` adds the matrices ``cov`` and ``corr`` of
-    :func:`kissmcmc_jl_amd.covariance` (of the dimensions; summed on the device)."""
+    :func:`kissmcmc_jl_amd.covariance` (of the dimensions; summed on the device).  ``hdi=0.94`` adds the columns ``hdi_lo`` and
+    ``hdi_hi`` of :func:`kissmcmc_jl_amd.hdi` for that probability."""
     th = np.asarray(thetas, dtype=np.float64)
     if th.ndim == 2:
         th = th[:, :, None]
@@ -382,7 +450,8 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     if convergence:
         from .chain_convergence import convergence as _convergence
         conv = _convergence(th, device=device, rank=convergence == "rank")
-    cols = summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv)
+    intervals = None if hdi is None else hdi_from(provider, float(hdi))
+    cols = summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv, intervals)
     if covariance:
         from .chain_covariance import covariance as _covariance
         c = _covariance(th, device=device)
