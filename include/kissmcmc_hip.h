@@ -636,7 +636,26 @@ kmc_status  kmc_logpdf_eval_host(const kmc_config* cfg, const double* pos_host, 
  * Random stream: Philox4x32-10, key {seed_lo ^ 0x4d455452, seed_hi}, counter {it_lo, it_hi, chain, block};
  * block 0 = words (w0,w1) -> Box-Muller pair for dimensions 0,1 and (w2<<20 | w3>>12) -> the accept uniform;
  * block b >= 1 = (w0,w1) -> dimensions 4b-2,4b-1 and (w2,w3) -> dimensions 4b,4b+1.  A chain's result is
- * a pure function of (seed, chain index, inputs). */
+ * a pure function of (seed, chain index, inputs).
+ *
+ * Covariance-shaped proposal (`chol` instead of `step`): theta + L z with a lower-triangular L [ndim][ndim] and the SAME draws --
+ * iteration `it` of chain `c` has the normals z_0 .. z_{ndim-1} and the accept uniform above, nothing more is drawn.
+ *   delta_i = ((L_i0 z_0 + L_i1 z_1) + ...) + L_ii z_i     j ascending, every j <= i evaluated (zeros included),
+ *   y_i     = x_i + delta_i
+ * every product and every sum rounded to double on its own: NO fused multiply-add.  The proposal is symmetric, the accept test
+ * (p1 - p0 > log u, strict) is the same.  Every entry of the lower triangle must be finite, the diagonal > 0.  A diagonal L is
+ * therefore NOT `step` bit for bit: `step` is fma(step_i, z_i, x_i), one rounding less.  (The few-chains route keeps delta in
+ * its draw table and runs the table kernel with a step of 1.0: fma(1.0, delta, x) is x + delta exactly.)  ndim <= 128.
+ *
+ * Tuning across chains (tune_rounds = R >= 1): burn-in is cut at b_r = floor(r nburnin / (R + 1)), r = 1..R (equal boundaries
+ * collapse into one).  Before iteration b_r runs, Sigma = the covariance of the nchains CURRENT states (kmc_chain_covariance's
+ * definition on them as a chain of one sample and nchains walkers: two passes, divisor nchains - 1, on the device),
+ * C = (scale scale) Sigma entry by entry, scale = tune_scale or 2.38 / sqrt(ndim), and L <- kmc_cholesky_lower(C); if that fails
+ * the previous L stays and the round is counted in tune_skipped.  The last L is in force from b_R < nburnin on: every stored
+ * sample is drawn with one fixed proposal.  A boundary always ends a launch; apart from that results do not depend on how the
+ * iteration range is cut, and a run stays a pure function of (seed, inputs).  With tune_rounds > 0 `step` / `chol` is the
+ * INITIAL proposal, and a `step` is treated as diag(step) under the rule above from iteration 0 on (one arithmetic throughout).
+ * Needs nchains > ndim, nburnin >= tune_rounds + 1, no host_propose. */
 typedef struct kmc_metropolis_config {
     int32_t  dtype;         /* KMC_F64 */
     int32_t  density;       /* kmc_density (menu or KMC_USER_DENSITY) */
@@ -661,6 +680,10 @@ typedef struct kmc_metropolis_config {
     void*                host_user;     /* passed to the three callbacks */
     kmc_host_accepted_fn host_accepted; /* optional: accept outcomes per iteration (blobs: :100-103, :116-118); row0 = 0, generation = iteration */
     kmc_host_propose_fn  host_propose;  /* optional: theta1 = sample_ppdf(theta0) for a batch of rows; `step` may then be NULL */
+    const double* chol;     /* host [ndim][ndim] row-major, lower triangle read: the proposal theta + L z.  Exactly one of step / chol
+                               is non-NULL (neither with host_propose) */
+    int32_t  tune_rounds;   /* R >= 0: tuning boundaries during burn-in (0: none) */
+    double   tune_scale;    /* 0: the default 2.38 / sqrt(ndim) */
 } kmc_metropolis_config;
 
 typedef struct kmc_metropolis_outputs {
@@ -678,7 +701,17 @@ typedef struct kmc_metropolis_outputs {
                                sample (hasblob=true, src/samplers.jl:70-72, :103, :117) of a body density created with
                                kmc_user_density_create_body_blob; in-kernel chains only (no host_propose) */
     double*  final_blob;    /* [nchains][nblob]: blob0 of every chain at the end */
+    double*  chol_out;      /* [ndim][ndim] or NULL: the L in force at the end (upper triangle 0.0); with `step` and no tuning, diag(step) */
+    int64_t  tune_skipped;  /* out: tuning rounds whose covariance could not be factored (the previous L stayed) */
+    double   tune_ms;       /* out: host time spent at the tuning boundaries (covariance kernels, copy, Cholesky, upload), all of them */
 } kmc_metropolis_outputs;
+
+/* Cholesky factor of a symmetric positive-definite matrix, host only, fixed operation order: row by row i = 0..n-1, within a row
+ * j = 0..i; s = a[i][j], then s = s - L_ik L_jk for k = 0..j-1 ascending, each operation rounded on its own (no fused
+ * multiply-add); j < i: L_ij = s / L_jj; j = i: s must be finite and > 0, else KMC_ERR_BAD_ARG with *bad = i, otherwise
+ * L_ii = sqrt(s).  Only the lower triangle of `a` [n][n] is read; the upper triangle of L [n][n] is written as 0.0.  `bad` may be NULL;
+ * it is -1 on success. */
+kmc_status  kmc_cholesky_lower(const double* a, int n, double* L, int* bad);
 
 /* Argument sanity only (the reference asserts nothing for metropolis).  No device needed. */
 kmc_status  kmc_metropolis_validate(const kmc_metropolis_config* cfg);

@@ -48,7 +48,7 @@ SYMBOLS = [
     "kmc_sampler_launch_count", "kmc_sampler_describe", "kmc_sampler_device_ptr", "kmc_sampler_get_positions",
     "kmc_sampler_get_logp", "kmc_sampler_get_naccept", "kmc_sampler_get_accept_ratio",
     "kmc_sampler_get_moments", "kmc_sampler_get_chain", "kmc_sampler_get_chain_by_walker", "kmc_logpdf_eval", "kmc_logpdf_eval_host",
-    "kmc_user_density_create", "kmc_user_density_create_body", "kmc_user_density_destroy", "kmc_metropolis_validate", "kmc_metropolis_run", "kmc_int_acorr", "kmc_sampler_int_acorr",
+    "kmc_user_density_create", "kmc_user_density_create_body", "kmc_user_density_destroy", "kmc_metropolis_validate", "kmc_metropolis_run", "kmc_cholesky_lower", "kmc_int_acorr", "kmc_sampler_int_acorr",
     "kmc_sizeof_config", "kmc_sizeof_metropolis_config", "kmc_sizeof_outputs", "kmc_sizeof_metropolis_outputs", "kmc_deal_seed", "kmc_deal_perm", "kmc_sampler_deal_pack", "kmc_sampler_deal_unpack",
     "kmc_sampler_get_walker_ids", "kmc_sampler_set_walker_ids", "kmc_sampler_set_chain_host", "kmc_rccl_unique_id", "kmc_sampler_rccl_init",
     "kmc_sampler_rccl_capture", "kmc_sampler_rccl_set_capture", "kmc_rccl_version", "kmc_device_free_bytes",
@@ -160,6 +160,9 @@ class MetropolisConfig(C.Structure):
         ("host_user", C.c_void_p),
         ("host_accepted", C.c_void_p),
         ("host_propose", C.c_void_p),
+        ("chol", C.POINTER(C.c_double)),
+        ("tune_rounds", C.c_int32),
+        ("tune_scale", C.c_double),
     ]
 
 
@@ -177,6 +180,9 @@ class MetropolisOutputs(C.Structure):
         ("device_ms", C.c_double),
         ("blobs", C.POINTER(C.c_double)),
         ("final_blob", C.POINTER(C.c_double)),
+        ("chol_out", C.POINTER(C.c_double)),
+        ("tune_skipped", C.c_int64),
+        ("tune_ms", C.c_double),
     ]
 
 
@@ -278,6 +284,7 @@ def lib() -> C.CDLL:
     L.kmc_user_density_destroy.argtypes = [vp]
     L.kmc_metropolis_validate.argtypes = [C.POINTER(MetropolisConfig)]
     L.kmc_metropolis_run.argtypes = [C.POINTER(MetropolisConfig), dp, C.POINTER(MetropolisOutputs)]
+    L.kmc_cholesky_lower.argtypes = [dp, C.c_int, dp, C.POINTER(C.c_int)]
     L.kmc_int_acorr.argtypes = [dp, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_int, dp, dp]
     L.kmc_sampler_int_acorr.argtypes = [vp, C.c_double, dp, dp]
     bp = C.POINTER(C.c_uint8)

@@ -117,4 +117,9 @@ struct ChainSource {
     }
 };
 
+// kmc_cov.hip: mean [ndim] and covariance [ndim][ndim] (divisor nrows - 1) of dense device rows [nrows][ndim] of doubles, the kernels of
+// kmc_chain_covariance on stream `st`; returns after the stream has delivered them.  Bit for bit what kmc_chain_covariance gives on the
+// same rows as a chain of one sample and nrows walkers.
+kmc_status covariance_of_rows(const double* rows_dev, int64_t nrows, int64_t ndim, hipStream_t st, double* mean, double* cov);
+
 }  // namespace kmc_chain_view

@@ -42,35 +42,19 @@ int64_t cov_waves(int64_t rows, int64_t nstrips)
     return std::max<int64_t>(1, std::min(nchunks, kCovTargetWaves / nstrips));
 }
 
-// the work space of one call, one allocation: the mean, the folded sums and the partial sums
-struct CovBuffers : ChainUpload {
-    double* work = nullptr;
-    ~CovBuffers() { (void)hipFree(work); }
-};
-
-kmc_status covariance(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, double* mean, double* cov, int64_t* n_out,
-                      int64_t* info)
+// the device work of a covariance on stream `st`: the n selected rows (mask_dev, or all) of the view at and after first_sample
+kmc_status covariance_on_view(const ChainView& v, bool with_logp, int64_t first_sample, const uint8_t* mask_dev, int64_t n, hipStream_t st,
+                              double* mean, double* cov, int64_t* info)
 {
-    ChainView v;
-    KMC_TRY(src.describe(&v));
-    int64_t n = 0;
-    KMC_TRY(selection_size(v, first_sample, walker_mask, &n));
-    const int64_t C = v.ndim + (src.with_logp ? 1 : 0);
-    if (C > kCovMaxCols)
-        return fail(KMC_ERR_UNSUPPORTED, "a covariance matrix of " + std::to_string(C) + " columns: the limit is " + std::to_string(kCovMaxCols));
-    if (n < 2) return fail(KMC_ERR_BAD_ARG, "a covariance needs at least 2 selected rows (n = " + std::to_string(n) + ")");
-    if (!mean || !cov) return fail(KMC_ERR_BAD_ARG, "null argument");
+    struct Work {
+        double* work = nullptr;
+        ~Work() { (void)hipFree(work); }
+    } b;
+    const int64_t C = v.ndim + (with_logp ? 1 : 0);
     const int64_t rows = (v.nsamples - first_sample) * v.nl;
-    if (rows >= ((int64_t)1 << 40)) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one covariance call");
-    if (n_out) *n_out = n;
     const CovPlan pl = cov_plan(C);
     const int64_t wm = cov_waves(rows, pl.ntiles), wc = cov_waves(rows, pl.nstrips);
-
-    CovBuffers b;
-    KMC_TRY(src.open(b, &v));
-    ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
-    HIP_TRY(ss.create());
-    KMC_TRY(upload_mask(b, walker_mask, v.nl, ss.st));
+    // the work space of one call, one allocation: the mean, the folded sums and the partial sums
     const size_t mean_bytes = (size_t)pl.ntiles * kCovTile * sizeof(double), out_bytes = (size_t)pl.nslots * kCovTileEntries * sizeof(double);
     const size_t part_bytes = std::max((size_t)pl.ntiles * (size_t)wm * kCovLanes, (size_t)pl.nslots * (size_t)wc * kCovTileEntries) * sizeof(double);
     KMC_TRY(check_device_room(mean_bytes + out_bytes + part_bytes, "the covariance work space"));
@@ -78,29 +62,29 @@ kmc_status covariance(const ChainSource& src, int64_t first_sample, const uint8_
     double *d_mean = b.work, *d_out = d_mean + (size_t)pl.ntiles * kCovTile, *d_part = d_out + (size_t)pl.nslots * kCovTileEntries;
 
     CovArgs a{};
-    a.chain = v.chain; a.logp = src.with_logp ? v.logp : nullptr; a.mask = b.mask; a.mean = d_mean; a.part = d_part; a.out = d_out;
+    a.chain = v.chain; a.logp = with_logp ? v.logp : nullptr; a.mask = mask_dev; a.mean = d_mean; a.part = d_part; a.out = d_out;
     a.n = (double)n; a.row0 = first_sample * v.nl; a.rows = rows; a.nl = v.nl; a.ld = v.ld;
     a.ndim = (int32_t)v.ndim; a.ncols = (int32_t)C; a.is_float = v.is_float ? 1 : 0; a.ntiles = pl.ntiles;
 
     // stage 1: the column sums and the mean
     a.nwaves = (int32_t)wm;
-    hipLaunchKernelGGL(cov_mean_partials, dim3((unsigned)((wm + kCovWaves - 1) / kCovWaves), (unsigned)pl.ntiles), dim3(kCovThreads), 0, ss.st, a);
+    hipLaunchKernelGGL(cov_mean_partials, dim3((unsigned)((wm + kCovWaves - 1) / kCovWaves), (unsigned)pl.ntiles), dim3(kCovThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cov_mean_fold, dim3((unsigned)pl.ntiles), dim3(kCovThreads), 0, ss.st, a);
+    hipLaunchKernelGGL(cov_mean_fold, dim3((unsigned)pl.ntiles), dim3(kCovThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
     // stage 2: the cross products, centred on that mean
     a.nwaves = (int32_t)wc;
     const dim3 grid((unsigned)((wc + kCovWaves - 1) / kCovWaves), (unsigned)pl.nstrips);
-    if (pl.ntiles == 1) hipLaunchKernelGGL(cov_tri_partials<1>, grid, dim3(kCovThreads), 0, ss.st, a);
-    else if (pl.ntiles == 2) hipLaunchKernelGGL(cov_tri_partials<2>, grid, dim3(kCovThreads), 0, ss.st, a);
-    else hipLaunchKernelGGL(cov_strip_partials, grid, dim3(kCovThreads), 0, ss.st, a);
+    if (pl.ntiles == 1) hipLaunchKernelGGL(cov_tri_partials<1>, grid, dim3(kCovThreads), 0, st, a);
+    else if (pl.ntiles == 2) hipLaunchKernelGGL(cov_tri_partials<2>, grid, dim3(kCovThreads), 0, st, a);
+    else hipLaunchKernelGGL(cov_strip_partials, grid, dim3(kCovThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cov_fold, dim3((unsigned)(pl.nslots * (kCovTileEntries / kCovTile))), dim3(kCovThreads), 0, ss.st, a);
+    hipLaunchKernelGGL(cov_fold, dim3((unsigned)(pl.nslots * (kCovTileEntries / kCovTile))), dim3(kCovThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
 
     std::vector<double> mu((size_t)pl.ntiles * kCovTile), sums((size_t)pl.nslots * kCovTileEntries);
-    HIP_TRY(copy_sync(mu.data(), d_mean, mean_bytes, hipMemcpyDeviceToHost, ss.st));
-    HIP_TRY(copy_sync(sums.data(), d_out, out_bytes, hipMemcpyDeviceToHost, ss.st));
+    HIP_TRY(copy_sync(mu.data(), d_mean, mean_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(copy_sync(sums.data(), d_out, out_bytes, hipMemcpyDeviceToHost, st));
     std::copy(mu.begin(), mu.begin() + C, mean);
     // the upper triangle from the accumulator map -- lane l, register r: row (l >> 4) + 4 r of the A tile, column l & 15 of the B tile --
     // divided once, and mirrored
@@ -145,7 +129,41 @@ kmc_status covariance(const ChainSource& src, int64_t first_sample, const uint8_
     return KMC_OK;
 }
 
+kmc_status covariance(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, double* mean, double* cov, int64_t* n_out,
+                      int64_t* info)
+{
+    ChainView v;
+    KMC_TRY(src.describe(&v));
+    int64_t n = 0;
+    KMC_TRY(selection_size(v, first_sample, walker_mask, &n));
+    const int64_t C = v.ndim + (src.with_logp ? 1 : 0);
+    if (C > kCovMaxCols)
+        return fail(KMC_ERR_UNSUPPORTED, "a covariance matrix of " + std::to_string(C) + " columns: the limit is " + std::to_string(kCovMaxCols));
+    if (n < 2) return fail(KMC_ERR_BAD_ARG, "a covariance needs at least 2 selected rows (n = " + std::to_string(n) + ")");
+    if (!mean || !cov) return fail(KMC_ERR_BAD_ARG, "null argument");
+    const int64_t rows = (v.nsamples - first_sample) * v.nl;
+    if (rows >= ((int64_t)1 << 40)) return fail(KMC_ERR_UNSUPPORTED, "chain too large for one covariance call");
+    if (n_out) *n_out = n;
+
+    ChainUpload b;
+    KMC_TRY(src.open(b, &v));
+    ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
+    HIP_TRY(ss.create());
+    KMC_TRY(upload_mask(b, walker_mask, v.nl, ss.st));
+    return covariance_on_view(v, src.with_logp, first_sample, b.mask, n, ss.st, mean, cov, info);
+}
+
 }  // namespace
+
+// The covariance of dense device rows [nrows][ndim] (one sample of nrows walkers): kmc_chain_covariance's kernels, plan and host
+// stage on the caller's stream, no copy of the rows (kmc_metropolis_api.hip: the tuning boundaries of kmc_metropolis_run).
+kmc_status kmc_chain_view::covariance_of_rows(const double* rows_dev, int64_t nrows, int64_t ndim, hipStream_t st, double* mean, double* cov)
+{
+    ChainView v;
+    v.chain = rows_dev; v.ld = ndim; v.ndim = ndim; v.nsamples = 1; v.nl = nrows;
+    if (ndim > kCovMaxCols || nrows < 2) return fail(KMC_ERR_BAD_ARG, "covariance_of_rows: at most " + std::to_string(kCovMaxCols) + " columns, at least 2 rows");
+    return covariance_on_view(v, false, 0, nullptr, nrows, st, mean, cov, nullptr);
+}
 
 KMC_EXPORT kmc_status kmc_sampler_covariance(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t with_logp, double* mean,
                                              double* cov, int64_t* n_out, int64_t* info)

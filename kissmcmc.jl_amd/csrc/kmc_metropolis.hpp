@@ -19,10 +19,27 @@
 //       r = sqrt(-2 log u1), n0 = r cos(2 pi u2), n1 = r sin(2 pi u2)           (Box-Muller)
 // A chain's result is a pure function of (seed, chain index, inputs): independent of launch geometry
 // and of how the iteration range is cut into launches.
+//
+// Covariance-shaped proposal (MVNormalStep; the MV = true bodies): theta + L z with a lower-triangular L and the SAME normals
+// z_0 .. z_{ndim-1} -- nothing more is drawn.  delta_i = ((L_i0 z_0 + L_i1 z_1) + ...) + L_ii z_i, j ascending, every j <= i
+// evaluated (zeros included), every product and every sum rounded on its own (no fused multiply-add: the library and the
+// runtime-compiled programs are built with -ffp-contract=off), then y_i = x_i + delta_i, one more rounding.  Symmetric, so the
+// accept test is the same.  L comes packed by rows, entry (i, j) at i (i + 1) / 2 + j, in MetropolisArgs::step.
 #pragma once
 #include "kmc_device.hpp"
 
 namespace kmc {
+
+// The packed L is the same for every lane and constant while a kernel runs: read through the constant address space, loads at
+// uniform indices are scalar loads whatever the kernel stores in between.
+using ConstDoubles = const __attribute__((address_space(4))) double*;
+__device__ __forceinline__ ConstDoubles const_doubles(const double* p)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    return (ConstDoubles)p;
+#pragma clang diagnostic pop
+}
 
 struct MetropolisArgs {
     double*       pos;         // [nchains][ndim] theta0 of every chain (in/out)
@@ -32,7 +49,7 @@ struct MetropolisArgs {
     double*       chain_logp;  // [nsamples][nchains] or nullptr                       (:119)
     double*       csum;        // [nchains][ndim] per-chain sum over the stored samples, or nullptr
     double*       csumsq;
-    const double* step;        // [ndim] proposal scale per dimension
+    const double* step;        // [ndim] proposal scale per dimension; MV kernels: the packed lower triangle of L, [ndim (ndim + 1) / 2]
     double*       xt;          // any-ndim kernel: the chains' state, DIMENSION-major [ndim][nchains] (coalesced over lanes)
     double*       yt;          // any-ndim kernel: the proposals, [ndim][nchains]
     double*       st1;         // any-ndim kernel: per-chain sums, [ndim][nchains], or nullptr
@@ -68,18 +85,19 @@ __device__ __forceinline__ double normal_first(uint32_t a, uint32_t b)
     return sqrt(-2.0 * log_pos_normal(u1)) * cospi(2.0 * u2);
 }
 
-// ND > 0: ndim <= ND, the chain lives in registers.
-template <class Dens, int ND>
+// ND > 0: ndim <= ND, the chain lives in registers.  MV: the proposal theta + L z (top of this file) instead of theta + step .* z.
+template <class Dens, int ND, bool MV = false>
 __device__ __forceinline__ void metropolis_chains_body(const MetropolisArgs& a)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= a.nchains) return;
     const int ndim = a.ndim;
-    double x[ND], y[ND], sc[ND], s1[ND], s2[ND];
+    double x[ND], y[ND], sc[MV ? 1 : ND], s1[ND], s2[ND];
+    [[maybe_unused]] const ConstDoubles Lp = const_doubles(a.step);
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
         x[d]  = d < ndim ? a.pos[c * ndim + d] : 0.0;
-        sc[d] = d < ndim ? a.step[d] : 0.0;
+        if constexpr (!MV) sc[d] = d < ndim ? a.step[d] : 0.0;
         s1[d] = (a.csum != nullptr && d < ndim) ? a.csum[c * ndim + d] : 0.0;
         s2[d] = (a.csum != nullptr && d < ndim) ? a.csumsq[c * ndim + d] : 0.0;
     }
@@ -108,7 +126,14 @@ __device__ __forceinline__ void metropolis_chains_body(const MetropolisArgs& a)
 #pragma unroll
         for (int d = 0; d < ND; ++d) {
             if (d < ndim) {
-                y[d] = fma(sc[d], nr[d], x[d]);                              // :98  theta1 = sample_ppdf(theta0)
+                if constexpr (MV) {
+                    double dl = Lp[d * (d + 1) / 2] * nr[0];                 // row d of L: compile-time indices, scalar loads
+#pragma unroll
+                    for (int j = 1; j <= d; ++j) dl = dl + Lp[d * (d + 1) / 2 + j] * nr[j];
+                    y[d] = x[d] + dl;                                        // :98  theta1 = theta0 + L z
+                } else {
+                    y[d] = fma(sc[d], nr[d], x[d]);                          // :98  theta1 = sample_ppdf(theta0)
+                }
                 Dens::seq_add(q, y[d], d, a.dp);
             }
         }
@@ -175,6 +200,11 @@ struct MetroDrawArgs {
     int32_t  nsteps;           // table length T (a multiple of the tile's steps)
     int32_t  ndim;
     uint32_t seed_lo, seed_hi;
+};
+
+struct MetroDrawMvArgs {       // metro_draw_shape
+    MetroDrawArgs a;
+    const double* chol;        // the packed lower triangle of L
 };
 
 __host__ __device__ __forceinline__ int metro_tile_steps(int nl, int ndim)
@@ -330,7 +360,9 @@ __global__ __launch_bounds__(128) void metropolis_chains_tabled(const Metropolis
 // Any ndim: the chain stays in memory, dimension-major ([ndim][nchains]) so that the 64 chains of a wave
 // read and write consecutive doubles; pos / csum (chain-major, the C ABI's layout) are converted by
 // metropolis_transpose before the first and after the last launch.
-template <class Dens>
+// MV: the normals go into yt first, then y_i = x_i + (row i of L) . z is formed DESCENDING in i, in place -- row i needs z_j for
+// j <= i only -- and the density reads the finished proposal in index order.
+template <class Dens, bool MV = false>
 __device__ __forceinline__ void metropolis_chains_any_body(const MetropolisArgs& a)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -363,9 +395,23 @@ __device__ __forceinline__ void metropolis_chains_any_body(const MetropolisArgs&
                 }
                 nd = r == 0 ? n0 : r == 1 ? n1 : r == 2 ? n2 : n3;
             }
-            const double yd = fma(a.step[d], nd, x[(int64_t)d * nc]);        // :98
-            y[(int64_t)d * nc] = yd;
-            Dens::seq_add(q, yd, d, a.dp);
+            if constexpr (MV) {
+                y[(int64_t)d * nc] = nd;
+            } else {
+                const double yd = fma(a.step[d], nd, x[(int64_t)d * nc]);    // :98
+                y[(int64_t)d * nc] = yd;
+                Dens::seq_add(q, yd, d, a.dp);
+            }
+        }
+        if constexpr (MV) {
+            const ConstDoubles Lp = const_doubles(a.step);
+            for (int i = ndim - 1; i >= 0; --i) {
+                const ConstDoubles Li = Lp + (int64_t)i * (i + 1) / 2;
+                double dl = Li[0] * y[0];
+                for (int j = 1; j <= i; ++j) dl = dl + Li[j] * y[(int64_t)j * nc];
+                y[(int64_t)i * nc] = x[(int64_t)i * nc] + dl;                // :98  theta1 = theta0 + L z
+            }
+            for (int d = 0; d < ndim; ++d) Dens::seq_add(q, y[(int64_t)d * nc], d, a.dp);
         }
         const double p1 = Dens::seq_finish(q, ndim, a.dp);                   // :99
         const uint64_t kk = ((uint64_t)w.z << 20) | (uint64_t)(w.w >> 12);
@@ -429,6 +475,13 @@ __global__ __launch_bounds__(256) void metropolis_chains(const MetropolisArgs a)
     else metropolis_chains_any_body<Dens>(a);
 }
 
+template <class Dens, int ND>
+__global__ __launch_bounds__(256) void metropolis_chains_mv(const MetropolisArgs a)     // the proposal theta + L z
+{
+    if constexpr (ND > 0) metropolis_chains_body<Dens, ND, true>(a);
+    else metropolis_chains_any_body<Dens, true>(a);
+}
+
 // Host route (kmc_metropolis_config.host_logpdf / host_propose: ANY closure for `pdf` and / or `sample_ppdf`, reference
 // src/samplers.jl:59-61): one iteration of all chains per round trip.  PROPOSE draws the Gaussian step on the device (same
 // stream as the in-kernel chains) unless the proposals come from the host; ACCEPT takes the proposals' log-pdfs (from the
@@ -443,7 +496,7 @@ struct MetroHostArgs {
     double*        chain_logp;
     double*        csum;       // [nchains][ndim] or nullptr
     double*        csumsq;
-    const double*  step;       // [ndim] (PROPOSE)
+    const double*  step;       // [ndim] (PROPOSE); metro_host_propose_mv: the packed lower triangle of L
     unsigned char* acc_out;    // [nchains] or nullptr
     int64_t        nchains;
     int64_t        it;         // 0-based iteration; reference n = it + 1 - nburnin (:96)
@@ -491,7 +544,31 @@ __global__ __launch_bounds__(256) void metro_draw_fill(const MetroDrawArgs a)
     const uint64_t kk = ((uint64_t)w.z << 20) | (uint64_t)(w.w >> 12);
     e[(int64_t)ndim * nl] = log_pos_normal(((double)kk + 0.5) * 0x1.0p-52);
 }
-__global__ __launch_bounds__(256) void metro_host_propose(const MetroHostArgs a)
+// MVNormalStep on the few-chains route, a second pass over the table metro_draw_fill has written: the entries of the normals get
+// delta = L z instead (same thread per (step, chain); formed descending in i, in place: row i needs z_j for j <= i only);
+// metropolis_chains_tabled then runs with a step of 1.0 -- fma(1.0, delta, x) is x + delta exactly.
+__global__ __launch_bounds__(256) void metro_draw_shape(const MetroDrawMvArgs m)
+{
+    const MetroDrawArgs& a = m.a;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)a.nsteps * a.nchains) return;
+    const int64_t s = idx / a.nchains;
+    const int64_t c = idx - s * a.nchains;
+    const int ndim = a.ndim;
+    const int64_t c0 = c & ~(int64_t)63;
+    const int nl = (int)(a.nchains - c0 < 64 ? a.nchains - c0 : 64);
+    double* e = a.out + c0 * (int64_t)a.nsteps * (ndim + 1) + s * (int64_t)(ndim + 1) * nl + (c - c0);
+    const ConstDoubles Lp = const_doubles(m.chol);
+    for (int i = ndim - 1; i >= 0; --i) {
+        const ConstDoubles Li = Lp + (int64_t)i * (i + 1) / 2;
+        double dl = Li[0] * e[0];
+        for (int j = 1; j <= i; ++j) dl = dl + Li[j] * e[(int64_t)j * nl];
+        e[(int64_t)i * nl] = dl;
+    }
+}
+
+template <bool MV>
+__device__ __forceinline__ void metro_host_propose_body(const MetroHostArgs a)
 {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= a.nchains) return;
@@ -512,9 +589,22 @@ __global__ __launch_bounds__(256) void metro_host_propose(const MetroHostArgs a)
             }
             nd = r == 0 ? n0 : r == 1 ? n1 : r == 2 ? n2 : n3;
         }
-        a.prop[c * a.ndim + d] = fma(a.step[d], nd, a.pos[c * a.ndim + d]);          // :98 theta1 = sample_ppdf(theta0)
+        if constexpr (MV) a.prop[c * a.ndim + d] = nd;
+        else a.prop[c * a.ndim + d] = fma(a.step[d], nd, a.pos[c * a.ndim + d]);     // :98 theta1 = sample_ppdf(theta0)
+    }
+    if constexpr (MV) {                                                              // :98 theta1 = theta0 + L z, descending in place
+        const ConstDoubles Lp = const_doubles(a.step);
+        double* z = a.prop + c * a.ndim;
+        for (int i = a.ndim - 1; i >= 0; --i) {
+            const ConstDoubles Li = Lp + (int64_t)i * (i + 1) / 2;
+            double dl = Li[0] * z[0];
+            for (int j = 1; j <= i; ++j) dl = dl + Li[j] * z[j];
+            z[i] = a.pos[c * a.ndim + i] + dl;
+        }
     }
 }
+__global__ __launch_bounds__(256) void metro_host_propose(const MetroHostArgs a) { metro_host_propose_body<false>(a); }
+__global__ __launch_bounds__(256) void metro_host_propose_mv(const MetroHostArgs a) { metro_host_propose_body<true>(a); }
 
 __global__ __launch_bounds__(256) void metro_host_accept(const MetroHostArgs a)
 {

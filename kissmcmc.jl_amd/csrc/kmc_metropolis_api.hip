@@ -1,6 +1,7 @@
 // kmc_metropolis_api.hip -- host side of the many-chain Metropolis entry points of include/kissmcmc_hip.h
 // (kmc_metropolis_validate / kmc_metropolis_run; kernels: kmc_metropolis.hpp).
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,7 @@
 
 #define KMC_DEFINE_METROPOLIS_KERNELS
 #include "kmc_host.hpp"
+#include "kmc_chain_view.hpp"
 
 using namespace kmc;
 using namespace kmc_host;
@@ -22,18 +24,23 @@ int metropolis_nd(int64_t ndim) { return ndim <= 1 ? 1 : ndim <= 2 ? 2 : ndim <=
 
 // runtime-compiled density: the Metropolis kernel (and the initial log-pdf kernel) for one register geometry
 // (TND > 0: also the few-chains kernel that reads its draws from a table, chains in registers -- body densities included)
-kmc_status compile_user_metropolis(kmc_user_density* ud, int ND, const std::vector<char>** out, int64_t ndim = 0, int TND = 0)
+// (mv: the same program with the covariance-shaped proposal theta + L z in kmc_user_metropolis -- a program of its own, with its own
+// name and key; the isotropic programs keep their text and their cache entries)
+kmc_status compile_user_metropolis(kmc_user_density* ud, int ND, const std::vector<char>** out, int64_t ndim = 0, int TND = 0, bool mv = false)
 {
     if (ud->is_body) ND = 0;                     // a body density: the chain-in-memory kernel (the proposal is collected per lane)
     char key[64];
-    std::snprintf(key, sizeof(key), "M:%d:%lld:%d", ND, ud->is_body ? (long long)ndim : 0ll, TND);
+    std::snprintf(key, sizeof(key), mv ? "MV:%d:%lld:%d" : "M:%d:%lld:%d", ND, ud->is_body ? (long long)ndim : 0ll, TND);
     static const RtcModule m{"user density", "kmc_user_metropolis.hip", {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_metropolis.hpp"}, rtc_options()};
-    return compile_keyed(ud, key, m, [&](std::string* text) {
+    static const RtcModule mmv{"user density", "kmc_user_metropolis_mv.hip", {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_metropolis.hpp"}, rtc_options()};
+    return compile_keyed(ud, key, mv ? mmv : m, [&](std::string* text) {
         std::ostringstream src;
         src << "#include \"kmc_kernels.hpp\"\n#include \"kmc_metropolis.hpp\"\n" << user_functor_source(ud) << user_density_alias(ud, ndim)
             << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
             << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_metropolis(const kmc::MetropolisArgs a) { ";
-        if (ND > 0) src << "kmc::metropolis_chains_body<UD, " << ND << ">(a); }\n";
+        if (mv && ND > 0) src << "kmc::metropolis_chains_body<UD, " << ND << ", true>(a); }\n";
+        else if (mv) src << "kmc::metropolis_chains_any_body<UD, true>(a); }\n";
+        else if (ND > 0) src << "kmc::metropolis_chains_body<UD, " << ND << ">(a); }\n";
         else src << "kmc::metropolis_chains_any_body<UD>(a); }\n";
         if (TND > 0)
             src << "extern \"C\" __global__ __launch_bounds__(128) void kmc_user_metropolis_tabled(const kmc::MetropolisTabledArgs t) { "
@@ -52,6 +59,7 @@ struct MetroBuffers {
            *step = nullptr, *xt = nullptr, *yt = nullptr, *st1 = nullptr, *st2 = nullptr, *blob = nullptr, *chain_blob = nullptr;
     uint32_t* naccept = nullptr;
     double* draws = nullptr;          // few chains: the draw table of a launch (metro_draw_fill)
+    double* chol = nullptr;           // the packed L of a covariance-shaped proposal
     hipModule_t mod = nullptr;        // (held through keep)
     std::shared_ptr<void> keep;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -61,7 +69,7 @@ struct MetroBuffers {
         if (stream) (void)hipStreamSynchronize(stream);
         cache_free(pos); cache_free(logp); cache_free(chain); cache_free(chain_logp); cache_free(csum);
         cache_free(csumsq); cache_free(step); cache_free(xt); cache_free(yt); cache_free(st1); cache_free(st2);
-        cache_free(naccept); cache_free(blob); cache_free(chain_blob); cache_free(draws);
+        cache_free(naccept); cache_free(blob); cache_free(chain_blob); cache_free(draws); cache_free(chol);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
     }
@@ -70,6 +78,115 @@ struct MetroBuffers {
 }  // namespace
 
 namespace {
+
+constexpr int64_t kMetroCholMaxDim = 128;         // L is ndim^2 / 2 doubles read per step and lane; nothing larger is tested
+
+// the Cholesky factorisation of include/kissmcmc_hip.h (kmc_cholesky_lower): fixed order, every operation rounded on its own
+// (the library is built with -ffp-contract=off).  Returns the failing pivot, or -1.
+int cholesky_lower(const double* a, int64_t n, double* L)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        for (int64_t j = 0; j <= i; ++j) {
+            double s = a[i * n + j];
+            for (int64_t k = 0; k < j; ++k) {
+                const double t = L[i * n + k] * L[j * n + k];
+                s = s - t;
+            }
+            if (j < i) L[i * n + j] = s / L[j * n + j];
+            else {
+                if (!(std::isfinite(s) && s > 0.0)) return (int)i;
+                L[i * n + i] = std::sqrt(s);
+            }
+        }
+        for (int64_t j = i + 1; j < n; ++j) L[i * n + j] = 0.0;
+    }
+    return -1;
+}
+
+// The proposal of one run with `chol` or tuning: theta + L z (kmc_metropolis.hpp), L packed by rows on the device, replaced at the
+// tuning boundaries by the Cholesky factor of the scaled covariance of the chains' current states.
+struct MetroShape {
+    bool on = false;                  // false: the isotropic route, theta + step .* z
+    int64_t nd = 0;
+    std::vector<double> L;            // host [nd][nd], upper triangle 0.0
+    std::vector<int64_t> bounds;      // the tuning boundaries b_r, ascending and distinct
+    double scale = 0.0;
+    int64_t skipped = 0;
+    double tune_ms = 0.0;
+    double* dev = nullptr;            // device: the packed lower triangle (owned by the run's buffers)
+
+    void init(const kmc_metropolis_config* c)
+    {
+        on = c->chol != nullptr || c->tune_rounds > 0;
+        nd = c->ndim;
+        if (!on) return;
+        L.assign((size_t)(nd * nd), 0.0);
+        for (int64_t i = 0; i < nd; ++i) {
+            if (c->chol) for (int64_t j = 0; j <= i; ++j) L[(size_t)(i * nd + j)] = c->chol[i * nd + j];
+            else L[(size_t)(i * nd + i)] = c->step[i];
+        }
+        scale = c->tune_scale > 0.0 ? c->tune_scale : 2.38 / std::sqrt((double)nd);
+        for (int64_t r = 1; r <= c->tune_rounds; ++r) {
+            const int64_t b = (int64_t)(((__int128)r * c->nburnin) / (c->tune_rounds + 1));
+            if (bounds.empty() || bounds.back() != b) bounds.push_back(b);
+        }
+    }
+    // (room for a 32 x 32 triangle at least: the register kernels index it with compile-time offsets)
+    size_t dev_doubles() const { const int64_t m = std::max<int64_t>(nd, 32); return (size_t)(m * (m + 1) / 2); }
+    hipError_t alloc(double** p, hipStream_t st)
+    {
+        hipError_t e = metro_alloc(p, dev_doubles() * sizeof(double));
+        if (e != hipSuccess) return e;
+        dev = *p;
+        e = fill_sync(dev, 0, dev_doubles() * sizeof(double), st);
+        return e != hipSuccess ? e : upload(st);
+    }
+    hipError_t upload(hipStream_t st)
+    {
+        std::vector<double> packed((size_t)(nd * (nd + 1) / 2));
+        for (int64_t i = 0; i < nd; ++i)
+            for (int64_t j = 0; j <= i; ++j) packed[(size_t)(i * (i + 1) / 2 + j)] = L[(size_t)(i * nd + j)];
+        return copy_sync(dev, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice, st);
+    }
+    bool boundary(int64_t it) const { return std::binary_search(bounds.begin(), bounds.end(), it); }
+    int64_t next_boundary(int64_t it, int64_t end) const      // the first boundary after `it`, or `end`
+    {
+        const auto b = std::upper_bound(bounds.begin(), bounds.end(), it);
+        return b == bounds.end() ? end : std::min(*b, end);
+    }
+    // one tuning boundary: pos_dev [nc][nd] are the chains' current states, everything queued on `st` before is waited for
+    kmc_status tune(const double* pos_dev, int64_t nc, hipStream_t st)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<double> mean((size_t)nd), cov((size_t)(nd * nd)), Ln((size_t)(nd * nd));
+        KMC_TRY(kmc_chain_view::covariance_of_rows(pos_dev, nc, nd, st, mean.data(), cov.data()));
+        const double s2 = scale * scale;
+        for (double& v : cov) v = s2 * v;
+        if (cholesky_lower(cov.data(), nd, Ln.data()) >= 0) ++skipped;       // the previous L stays
+        else {
+            L.swap(Ln);
+            HIP_TRY(upload(st));
+        }
+        tune_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return KMC_OK;
+    }
+    void report(kmc_metropolis_outputs* out) const
+    {
+        out->tune_skipped = skipped;
+        out->tune_ms = tune_ms;
+    }
+};
+
+// kmc_metropolis_outputs.chol_out: the L in force at the end
+void write_chol_out(const kmc_metropolis_config* c, const MetroShape& sh, kmc_metropolis_outputs* out)
+{
+    if (!out->chol_out) return;
+    const int64_t nd = c->ndim;
+    if (sh.on) std::copy(sh.L.begin(), sh.L.end(), out->chol_out);
+    else
+        for (int64_t i = 0; i < nd; ++i)
+            for (int64_t j = 0; j < nd; ++j) out->chol_out[i * nd + j] = (i == j && c->step) ? c->step[i] : 0.0;
+}
 
 // The host route of kmc_metropolis_run: `pdf` and / or `sample_ppdf` are caller's closures (src/samplers.jl:59-61).  One
 // iteration of all chains per pass: proposals (device Gaussian step, or host_propose on the current states), their
@@ -114,7 +231,10 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
     HIP_TRY(metro_alloc(&b.naccept, (size_t)nc * sizeof(uint32_t)));
     HIP_TRY(fill_sync(b.naccept, 0, (size_t)nc * sizeof(uint32_t), st));
     HIP_TRY(copy_sync(b.pos, theta0, rows, hipMemcpyHostToDevice, st));                              // :68 deepcopy
-    if (c->step) {
+    MetroShape sh;
+    sh.init(c);
+    if (sh.on) HIP_TRY(sh.alloc(&b.step, st));                                                       // (the packed L in place of the scales)
+    else if (c->step) {
         HIP_TRY(metro_alloc(&b.step, (size_t)nd * sizeof(double)));
         HIP_TRY(copy_sync(b.step, c->step, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
     }
@@ -170,6 +290,7 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
     int64_t cnt = 0, slot = 0;
     for (int64_t it = 0; it < c->niter; ++it) {
         const int64_t n = it + 1 - c->nburnin;                                                   // :96
+        if (sh.on && sh.boundary(it)) KMC_TRY(sh.tune(b.pos, nc, st));
         MetroHostArgs a{};
         a.pos = b.pos; a.logp = b.logp; a.naccept = b.naccept; a.prop = b.prop; a.p1 = b.p1;
         a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq; a.step = b.step; a.acc_out = b.acc;
@@ -186,7 +307,8 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
                 return fail(KMC_ERR_BAD_ARG, "the host proposal callback failed in iteration " + std::to_string(it));
             HIP_TRY(copy_sync(b.prop, b.h_prop, rows, hipMemcpyHostToDevice, st));
         } else {
-            hipLaunchKernelGGL(metro_host_propose, dim3(grid), dim3(256), 0, st, a);
+            if (sh.on) hipLaunchKernelGGL(metro_host_propose_mv, dim3(grid), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(metro_host_propose, dim3(grid), dim3(256), 0, st, a);
             HIP_TRY(hipGetLastError());
         }
         if (host_pdf) {                                                                          // :99 p1 = pdf(theta1)
@@ -210,6 +332,8 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
     out->device_ms = (double)ms;
+    sh.report(out);
+    if (!c->host_propose) write_chol_out(c, sh, out);
     if (c->flags & KMC_CHAIN_BY_WALKER) {       // thetas[chain][sample], as the reference returns them (:113, :128)
         if (out->chain && b.chain) KMC_TRY(download_by_walker(b.chain, false, nc, nd, nd, nsamples, out->chain, st));
         if (out->chain_logp && b.chain_logp) KMC_TRY(download_by_walker(b.chain_logp, false, nc, 1, 1, nsamples, out->chain_logp, st));
@@ -243,9 +367,38 @@ KMC_EXPORT kmc_status kmc_metropolis_validate(const kmc_metropolis_config* c)
     if (c->nchains <= 0 || c->ndim <= 0 || c->nthin <= 0 || c->niter < 0 || c->nburnin < 0)
         return fail(KMC_ERR_BAD_ARG, "nchains, ndim, nthin must be positive; niter, nburnin non-negative");
     if (c->nchains > 0xffffffffll) return fail(KMC_ERR_BAD_ARG, "at most 2^32 - 1 chains (the chain index is one Philox counter word)");
-    if (!c->step && !c->host_propose) return fail(KMC_ERR_BAD_ARG, "step (proposal scale per dimension) is NULL and there is no host_propose");
+    if (c->step && c->chol) return fail(KMC_ERR_BAD_ARG, "both step and chol are given: exactly one of them is the proposal");
+    if (c->chol && c->host_propose) return fail(KMC_ERR_BAD_ARG, "chol with host_propose: the proposals come from the host, there is no L to apply");
+    if (!c->step && !c->chol && !c->host_propose)
+        return fail(KMC_ERR_BAD_ARG, "step (proposal scale per dimension) is NULL and there is no host_propose (neither step nor chol: exactly one of them is the proposal)");
     for (int64_t d = 0; c->step && d < c->ndim; ++d)
         if (!std::isfinite(c->step[d])) return fail(KMC_ERR_BAD_ARG, "step must be finite");
+    if (c->tune_rounds < 0) return fail(KMC_ERR_BAD_ARG, "tune_rounds = " + std::to_string(c->tune_rounds) + ": must be >= 0");
+    if (!std::isfinite(c->tune_scale) || c->tune_scale < 0.0)
+        return fail(KMC_ERR_BAD_ARG, "tune_scale = " + std::to_string(c->tune_scale) + ": must be finite and >= 0 (0: 2.38 / sqrt(ndim))");
+    if ((c->chol || c->tune_rounds > 0) && c->ndim > kMetroCholMaxDim)
+        return fail(KMC_ERR_UNSUPPORTED, "ndim = " + std::to_string(c->ndim) + " with chol or tuning: the limit is " + std::to_string(kMetroCholMaxDim) +
+                                             " (L is ndim^2 / 2 doubles read per step and lane, and nothing larger is tested)");
+    for (int64_t i = 0; c->chol && i < c->ndim; ++i) {
+        for (int64_t j = 0; j <= i; ++j)
+            if (!std::isfinite(c->chol[i * c->ndim + j]))
+                return fail(KMC_ERR_BAD_ARG, "chol[" + std::to_string(i) + "][" + std::to_string(j) + "] is not finite");
+        if (!(c->chol[i * c->ndim + i] > 0.0))
+            return fail(KMC_ERR_BAD_ARG, "chol[" + std::to_string(i) + "][" + std::to_string(i) + "] = " + std::to_string(c->chol[i * c->ndim + i]) +
+                                             ": the diagonal of L must be > 0");
+    }
+    if (c->tune_rounds > 0) {
+        if (c->host_propose) return fail(KMC_ERR_BAD_ARG, "tune_rounds = " + std::to_string(c->tune_rounds) + " with host_propose: there is no device proposal to tune");
+        if (c->nchains <= c->ndim)
+            return fail(KMC_ERR_BAD_ARG, "tune_rounds > 0 with nchains = " + std::to_string(c->nchains) + " <= ndim = " + std::to_string(c->ndim) +
+                                             ": the covariance across chains would be singular");
+        if (c->nburnin < (int64_t)c->tune_rounds + 1)
+            return fail(KMC_ERR_BAD_ARG, "tune_rounds = " + std::to_string(c->tune_rounds) + " needs nburnin >= " + std::to_string(c->tune_rounds + 1) +
+                                             " (nburnin = " + std::to_string(c->nburnin) + ")");
+        for (int64_t d = 0; c->step && d < c->ndim; ++d)
+            if (!(c->step[d] > 0.0))
+                return fail(KMC_ERR_BAD_ARG, "step[" + std::to_string(d) + "] = " + std::to_string(c->step[d]) + " with tune_rounds > 0: diag(step) is the initial L, its diagonal must be > 0");
+    }
     if (c->flags & ~(uint32_t)(KMC_STORE_CHAIN | KMC_STORE_LOGP | KMC_MOMENTS | KMC_CHAIN_BY_WALKER | KMC_STORE_BLOBS))
         return fail(KMC_ERR_BAD_ARG, "metropolis flags: KMC_STORE_CHAIN | KMC_STORE_LOGP | KMC_MOMENTS | KMC_CHAIN_BY_WALKER | KMC_STORE_BLOBS");
     {
@@ -316,8 +469,14 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     HIP_TRY(metro_alloc(&b.logp, (size_t)nc * sizeof(double)));
     HIP_TRY(metro_alloc(&b.naccept, (size_t)nc * sizeof(uint32_t)));
     HIP_TRY(fill_sync(b.naccept, 0, (size_t)nc * sizeof(uint32_t), st));
+    MetroShape sh;
+    sh.init(c);
     HIP_TRY(metro_alloc(&b.step, (size_t)nd * sizeof(double)));
-    HIP_TRY(copy_sync(b.step, c->step, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+    {   // (with L: a step of 1.0 for the few-chains kernel, whose table then holds L z)
+        const std::vector<double> ones((size_t)nd, 1.0);
+        HIP_TRY(copy_sync(b.step, sh.on ? ones.data() : c->step, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (sh.on) HIP_TRY(sh.alloc(&b.chol, st));
     HIP_TRY(copy_sync(b.pos, theta0, rows, hipMemcpyHostToDevice, st));                              // :68 deepcopy
     if ((want_chain || want_logp) && nsamples > 0)
         KMC_TRY(check_device_room((size_t)nsamples * ((want_chain ? rows : 0) + (want_logp ? (size_t)nc * sizeof(double) : 0)), "the Metropolis chain"));
@@ -367,7 +526,8 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     hipFunction_t ufn = nullptr, ulp = nullptr, utfn = nullptr;
     if (c->density == KMC_USER_DENSITY) {
         const std::vector<char>* code = nullptr;
-        KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), ND, &code, nd, tabled ? metropolis_nd(nd) : 0));
+        // (the few-chains kernel is the same with L: the isotropic program serves it)
+        KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), ND, &code, nd, tabled ? metropolis_nd(nd) : 0, sh.on && !tabled));
         KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep));
         b.mod = static_cast<hipModule_t>(b.keep.get());
         HIP_TRY(hipModuleGetFunction(&ufn, b.mod, "kmc_user_metropolis"));
@@ -375,7 +535,10 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
         if (tabled) HIP_TRY(hipModuleGetFunction(&utfn, b.mod, "kmc_user_metropolis_tabled"));
     } else {
         fn = with_density(c->density, MetropolisFn(nullptr),    // the geometry follows ndim (registers <= 32)
-                          [&](auto d) { return metropolis_lookup<decltype(d)>((int)std::min<int64_t>(nd, 1 << 20)); });
+                          [&](auto d) {
+                              const int n = (int)std::min<int64_t>(nd, 1 << 20);
+                              return sh.on ? metropolis_mv_lookup<decltype(d)>(n) : metropolis_lookup<decltype(d)>(n);
+                          });
         if (!fn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
     }
     const unsigned grid = (unsigned)((nc + 255) / 256);
@@ -413,13 +576,21 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     HIP_TRY(hipEventCreate(&b.ev1));
     HIP_TRY(hipEventRecord(b.ev0, st));
     const int64_t kItersPerLaunch = tabled ? table_steps : (int64_t)1 << 16;   // chains are independent: launches only bound a kernel's run time (and the table)
-    for (int64_t it0 = 0; it0 < c->niter; it0 += kItersPerLaunch) {
+    for (int64_t it0 = 0, it1 = 0; it0 < c->niter; it0 = it1) {
+        it1 = std::min<int64_t>(c->niter, it0 + kItersPerLaunch);
+        if (sh.on) {                                    // a tuning boundary always ends a launch; L is replaced before iteration b_r runs
+            if (sh.boundary(it0)) {
+                if (ND == 0 && !tabled) HIP_TRY(transpose(b.xt, b.pos, false));     // (the covariance reads the states chain-major)
+                KMC_TRY(sh.tune(b.pos, nc, st));
+            }
+            it1 = sh.next_boundary(it0, it1);
+        }
         MetropolisArgs a{};
         a.pos = b.pos; a.logp = b.logp; a.naccept = b.naccept;
         a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq;
-        a.step = b.step; a.xt = b.xt; a.yt = b.yt; a.st1 = b.st1; a.st2 = b.st2;
+        a.step = (sh.on && !tabled) ? b.chol : b.step; a.xt = b.xt; a.yt = b.yt; a.st1 = b.st1; a.st2 = b.st2;
         a.nchains = nc;
-        a.it0 = it0; a.it1 = std::min<int64_t>(c->niter, it0 + kItersPerLaunch);
+        a.it0 = it0; a.it1 = it1;
         a.nburnin = c->nburnin; a.nthin = c->nthin; a.nsamples = nsamples;
         const int64_t npos = it0 - c->nburnin;          // steps with n > 0 taken before it0
         a.cnt0 = npos > 0 ? npos % c->nthin : 0;
@@ -434,6 +605,10 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
             da.out = b.draws; da.nchains = nc; da.it0 = it0; da.nsteps = (int32_t)nit; da.ndim = (int32_t)nd;
             da.seed_lo = a.seed_lo; da.seed_hi = a.seed_hi;
             hipLaunchKernelGGL(metro_draw_fill, dim3((unsigned)((nit * nc + 255) / 256)), dim3(256), 0, st, da);
+            if (sh.on) {                                 // the normals of the table become L z
+                HIP_TRY(hipGetLastError());
+                hipLaunchKernelGGL(metro_draw_shape, dim3((unsigned)((nit * nc + 255) / 256)), dim3(256), 0, st, MetroDrawMvArgs{da, b.chol});
+            }
             HIP_TRY(hipGetLastError());
             if (utfn) {
                 MetropolisTabledArgs ta{};
@@ -459,6 +634,8 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
     out->device_ms = (double)ms;
+    sh.report(out);
+    write_chol_out(c, sh, out);
 
     if (c->flags & KMC_CHAIN_BY_WALKER) {       // thetas[chain][sample], as the reference returns them (:113, :128)
         if (out->chain && b.chain) KMC_TRY(download_by_walker(b.chain, false, nc, nd, nd, nsamples, out->chain, st));
@@ -489,3 +666,14 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     return KMC_OK;
 }
 
+
+KMC_EXPORT kmc_status kmc_cholesky_lower(const double* a, int n, double* L, int* bad)
+{
+    if (bad) *bad = -1;
+    if (!a || !L) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (n < 1) return fail(KMC_ERR_BAD_ARG, "kmc_cholesky_lower: n = " + std::to_string(n) + ", need n >= 1");
+    const int b = cholesky_lower(a, n, L);
+    if (b < 0) return KMC_OK;
+    if (bad) *bad = b;
+    return fail(KMC_ERR_BAD_ARG, "kmc_cholesky_lower: pivot " + std::to_string(b) + " is not finite and positive: the matrix is not positive definite");
+}

@@ -47,6 +47,7 @@ template <class D> GenerationFn generation_lane_lookup(int ndim);
 template <class D> GenerationFn generation_group_lookup(int L, int K);
 template <class D> MetropolisFn metropolis_lookup(int ndim);
 template <class D> MetropolisTabledFn metropolis_tabled_lookup(int ndim);
+template <class D> MetropolisFn metropolis_mv_lookup(int ndim);    // the proposal theta + L z (MVNormalStep)
 HalfStepFn half_step_host();         // kmc_inst_host.hip
 HalfStepFn half_step_host_de();      // KMC_MOVE_DE
 HalfStepFn half_step_host_snooker(); // KMC_MOVE_SNOOKER
@@ -315,6 +316,18 @@ MetropolisFn metropolis_lookup(int ndim)
     if (ndim <= 32) return metropolis_chains<D, 32>;
     return metropolis_chains<D, 0>;
 }
+// the same geometries with the covariance-shaped proposal (the few-chains route needs none: its table holds L z)
+template <class D>
+MetropolisFn metropolis_mv_lookup(int ndim)
+{
+    if (ndim <= 1) return metropolis_chains_mv<D, 1>;
+    if (ndim <= 2) return metropolis_chains_mv<D, 2>;
+    if (ndim <= 4) return metropolis_chains_mv<D, 4>;
+    if (ndim <= 8) return metropolis_chains_mv<D, 8>;
+    if (ndim <= 16) return metropolis_chains_mv<D, 16>;
+    if (ndim <= 32) return metropolis_chains_mv<D, 32>;
+    return metropolis_chains_mv<D, 0>;
+}
 // few chains: the draws from a table (kmc_metropolis.hpp: metropolis_chains_tabled), chains in registers up to 8 dimensions (menu densities -- build time; runtime-compiled ones up to 32)
 template <class D>
 MetropolisTabledFn metropolis_tabled_lookup(int ndim)
@@ -340,7 +353,8 @@ MetropolisTabledFn metropolis_tabled_lookup(int ndim)
     template GenerationFn generation_lane_lookup<D>(int); \
     template GenerationFn generation_group_lookup<D>(int, int); \
     template MetropolisFn metropolis_lookup<D>(int); \
-    template MetropolisTabledFn metropolis_tabled_lookup<D>(int)
+    template MetropolisTabledFn metropolis_tabled_lookup<D>(int); \
+    template MetropolisFn metropolis_mv_lookup<D>(int)
 #endif  // KMC_TABLES_IMPL
 
 }  // namespace kmc

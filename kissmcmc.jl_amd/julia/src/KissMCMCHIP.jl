@@ -416,6 +416,9 @@ Base.@kwdef struct KmcMetropolisConfig
     host_user::Ptr{Cvoid} = C_NULL
     host_accepted::Ptr{Cvoid} = C_NULL                # ... accept outcomes per iteration (blobs)
     host_propose::Ptr{Cvoid} = C_NULL                 # ... `sample_ppdf` is a closure (then `step` may be NULL)
+    chol::Ptr{Float64} = C_NULL                       # the proposal theta + L z: [ndim][ndim] row-major, lower triangle read (instead of `step`)
+    tune_rounds::Int32 = 0                            # tuning boundaries during burn-in: L from the covariance across chains
+    tune_scale::Float64 = 0.0                         # 0: 2.38 / sqrt(ndim)
 end
 
 Base.@kwdef mutable struct KmcMetropolisOutputs
@@ -431,6 +434,9 @@ Base.@kwdef mutable struct KmcMetropolisOutputs
     device_ms::Float64 = 0.0
     blobs::Ptr{Float64} = C_NULL
     final_blob::Ptr{Float64} = C_NULL
+    chol_out::Ptr{Float64} = C_NULL
+    tune_skipped::Int64 = 0
+    tune_ms::Float64 = 0.0
 end
 
 # Layout drift between these mirrors and the library fails here, when the module loads -- not inside the first real ccall.
@@ -471,8 +477,14 @@ chain.  With a menu / `ExprDensity` `pdf` and a `GaussianStep` the chains run in
 a `HostLogPdf(f)` and / or a `HostProposal(g)` keep those closures on the host (one batch call per iteration) while the
 accept test, counters and storage stay on the device.  Returns `(thetas, accept_ratio, logdensities, nothing)` shaped
 like `emcee`'s output (`thetas[chain][sample]`), so `squash_walkers` applies.
+
+`chol=L` (an `ndim x ndim` matrix, lower triangle read) replaces the `GaussianStep`'s scales by the covariance-shaped proposal
+`theta + L z` (include/kissmcmc_hip.h: same draws, `L z` summed in index order without fused multiply-add); `tune_rounds=R > 0`
+replaces `L` at `R` boundaries of burn-in by the Cholesky factor of `tune_scale^2` (default `2.38 / sqrt(ndim)`) times the covariance of
+the chains' current states across chains, the `GaussianStep` or `chol` being the initial proposal.
 """
 function metropolis_chains(pdf::DeviceLogPdf, sample_ppdf::Union{GaussianStep,HostProposal}, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1,
+                           chol::Union{Nothing,AbstractMatrix}=nothing, tune_rounds::Integer=0, tune_scale::Real=0.0,
                            hasblob=false, init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),
                            reduce_blob! =(blobs, blob) -> push!(blobs, blob), seed=rand(UInt64), device=0)
     device_blobs = hasblob && pdf isa ExprDensity && pdf.nblob > 0 && sample_ppdf isa GaussianStep
@@ -489,6 +501,7 @@ function metropolis_chains(pdf::DeviceLogPdf, sample_ppdf::Union{GaussianStep,Ho
     if sample_ppdf isa GaussianStep
         step = length(sample_ppdf.scale) == 1 ? fill(sample_ppdf.scale[1], ndim) : copy(sample_ppdf.scale)
         @assert length(step) == ndim
+        chol === nothing || (step = Float64[])                                            # exactly one of step / chol
     else
         sample_ppdf.scalar = scalar
         prop_fn = @cfunction(metro_propose_trampoline, Cint, (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}))
@@ -498,6 +511,8 @@ function metropolis_chains(pdf::DeviceLogPdf, sample_ppdf::Union{GaussianStep,Ho
         pdf.scalar = scalar
         pdf_fn = @cfunction(metro_pdf_trampoline, Cint, (Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}))
     end
+    cholrm = chol === nothing ? Float64[] : vec(permutedims(Matrix{Float64}(chol)))      # row-major [ndim][ndim], as the C ABI reads it
+    chol === nothing || size(chol) == (ndim, ndim) || error("chol must be $ndim x $ndim")
     ctx = MetroCtx(pdf, sample_ppdf)
     p = params(pdf); p8 = ntuple(i -> i <= length(p) ? p[i] : 0.0, 8)
     chain = Array{Float64}(undef, ndim, nsamples, nchains)      # column-major == C [chain][sample][dim] (KMC_CHAIN_BY_WALKER)
@@ -506,11 +521,12 @@ function metropolis_chains(pdf::DeviceLogPdf, sample_ppdf::Union{GaussianStep,Ho
     nblob = device_blobs ? pdf.nblob : 0
     bl = Array{Float64}(undef, nblob, nsamples, nchains)         # blobs[chain][sample] (:117), nblob doubles each
     out = KmcMetropolisOutputs(chain=pointer(chain), chain_logp=pointer(clogp), accept_ratio=pointer(acc), blobs=(device_blobs ? pointer(bl) : C_NULL))
-    st = GC.@preserve pdf sample_ppdf ctx theta step chain clogp acc bl begin
+    st = GC.@preserve pdf sample_ppdf ctx theta step cholrm chain clogp acc bl begin
         cfg = Ref(KmcMetropolisConfig(density=density_id(pdf), params=p8, nchains=nchains, ndim=ndim, niter=niter, nburnin=nburnin,
                                       nthin=nthin, step=(isempty(step) ? Ptr{Float64}(C_NULL) : pointer(step)), seed=UInt64(seed),
                                       flags=KMC_STORE_CHAIN | KMC_STORE_LOGP | KMC_CHAIN_BY_WALKER | (device_blobs ? KMC_STORE_BLOBS : UInt32(0)), device=Int32(device), user_density=user_handle(pdf),
-                                      host_logpdf=pdf_fn, host_user=pointer_from_objref(ctx), host_propose=prop_fn))
+                                      host_logpdf=pdf_fn, host_user=pointer_from_objref(ctx), host_propose=prop_fn,
+                                      chol=(isempty(cholrm) ? Ptr{Float64}(C_NULL) : pointer(cholrm)), tune_rounds=Int32(tune_rounds), tune_scale=Float64(tune_scale)))
         ccall((:kmc_metropolis_run, LIB), Cint, (Ref{KmcMetropolisConfig}, Ptr{Float64}, Ref{KmcMetropolisOutputs}), cfg, theta, out)
     end
     st == 0 || error("kmc_metropolis_run failed ($st): $(last_error())")

@@ -8,7 +8,9 @@ plus its data-parallel form, many independent chains at once.
 
 Fast path: ``sample_ppdf`` a :class:`GaussianStep` -- the symmetric jump every reference test uses,
 ``theta -> c .* randn(n) .+ theta`` (``test/runtests.jl:54,59,64,75``) -- and ``pdf`` a menu or runtime-compiled
-density: the whole chain runs inside one kernel, one chain per lane.
+density: the whole chain runs inside one kernel, one chain per lane.  :class:`MVNormalStep` (``theta + L randn(n)``, the shape
+of a covariance) and :class:`TunedStep` (``L`` from the covariance across chains, at a few boundaries during burn-in) run on
+the same path.
 
 General path (the reference takes ANY two closures, ``src/samplers.jl:59-61``; its README-style call
 ``metropolis(pdf, sample_prop_normal, theta0)`` works as it is): a callable ``pdf`` and / or a callable ``sample_ppdf``
@@ -47,6 +49,87 @@ def _dp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def cholesky_lower(a):
+    """``L`` with ``L @ L.T == a`` (``kmc_cholesky_lower``; needs no device): lower triangular, computed row by row in a fixed
+    order with every operation rounded on its own, so equal inputs give equal bits everywhere.  Only the lower triangle of ``a``
+    is read.  ``ValueError`` naming the failing pivot when ``a`` is not positive definite."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1:
+        raise ValueError("a must be a square matrix")
+    L, bad = np.empty_like(a), C.c_int(-1)
+    status = _lib.lib().kmc_cholesky_lower(_dp(a), a.shape[0], _dp(L), C.byref(bad))
+    if status != _lib.OK and bad.value >= 0:
+        raise ValueError(f"cholesky_lower: pivot {bad.value} is not finite and positive: the matrix is not positive definite")
+    _lib.check(status)
+    return L
+
+
+class MVNormalStep:
+    """Symmetric proposal ``theta1 = theta0 + L @ randn(ndim)`` with a lower-triangular ``L``: the shape of a covariance.
+
+    Exactly one of ``cov`` / ``chol``.  ``cov`` is scaled by ``scale ** 2`` (default ``scale = 2.38 / sqrt(ndim)``) and factored by
+    :func:`cholesky_lower`; ``chol`` is ``L`` itself, scaled by ``scale`` (default 1).  The same normals as :class:`GaussianStep`
+    are drawn; ``L z`` is summed in index order without fused multiply-add, so a diagonal ``L`` agrees with ``GaussianStep`` to
+    rounding, not bit for bit."""
+
+    def __init__(self, cov=None, chol=None, scale=None):
+        if (cov is None) == (chol is None):
+            raise ValueError("MVNormalStep takes exactly one of cov / chol")
+        m = np.array(cov if chol is None else chol, dtype=np.float64)
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 1:
+            raise ValueError("cov / chol must be a square matrix")
+        n = m.shape[0]
+        if scale is not None and not (np.isfinite(scale) and scale > 0):
+            raise ValueError(f"scale = {scale}: must be finite and positive")
+        if chol is None:
+            sc = 2.38 / np.sqrt(n) if scale is None else float(scale)
+            self.chol = cholesky_lower((sc * sc) * m)
+        else:
+            self.chol = np.tril(m) if scale is None else float(scale) * np.tril(m)
+        self.chol = np.ascontiguousarray(self.chol)
+
+    @classmethod
+    def from_covariance(cls, c, scale=None):
+        """From the dict ``s.covariance()`` / ``kmc.covariance`` return (its ``cov``; a log-density column is not allowed)."""
+        return cls(cov=c["cov"], scale=scale)
+
+    def factor(self, ndim: int) -> np.ndarray:
+        if self.chol.shape[0] != ndim:
+            raise ValueError(f"MVNormalStep has a {self.chol.shape[0]} x {self.chol.shape[0]} factor for {ndim} dimensions")
+        return self.chol
+
+    def __repr__(self):
+        return f"MVNormalStep(chol={self.chol.tolist()})"
+
+
+class TunedStep:
+    """``initial`` (a :class:`GaussianStep` or an :class:`MVNormalStep`) during the first stretch of burn-in, then, at each of
+    ``rounds`` boundaries ``floor(r * nburnin / (rounds + 1))``, ``L`` = the Cholesky factor of ``scale ** 2`` times the
+    covariance of the chains' current states ACROSS chains (default ``scale = 2.38 / sqrt(ndim)``).  Frozen before the first
+    stored sample.  Needs more chains than dimensions and ``nburnin >= rounds + 1``."""
+
+    def __init__(self, initial, rounds: int = 4, scale=None):
+        if not isinstance(initial, (GaussianStep, MVNormalStep)):
+            raise TypeError("TunedStep: initial must be a GaussianStep or an MVNormalStep")
+        if int(rounds) != rounds or rounds < 1:
+            raise ValueError(f"rounds = {rounds}: must be an integer >= 1")
+        if scale is not None and not (np.isfinite(scale) and scale > 0):
+            raise ValueError(f"scale = {scale}: must be finite and positive")
+        self.initial, self.rounds, self.scale = initial, int(rounds), scale
+
+    def __repr__(self):
+        return f"TunedStep({self.initial!r}, rounds={self.rounds}, scale={self.scale})"
+
+
+_DEVICE_STEPS = (GaussianStep, MVNormalStep, TunedStep)
+
+
+def tune_boundaries(nburnin: int, rounds: int):
+    """The iterations before which a :class:`TunedStep` replaces ``L``: ``floor(r * nburnin / (rounds + 1))``, ``r = 1..rounds``,
+    equal ones collapsed."""
+    return sorted({(r * int(nburnin)) // (int(rounds) + 1) for r in range(1, int(rounds) + 1)})
+
+
 class HostProposal:
     """ANY callable as ``sample_ppdf`` (``src/samplers.jl:41, :98``: a symmetric proposal ``theta0 -> theta1``), kept on
     the host and called per iteration on every chain's current state (a float when ``scalar`` else a 1-D array; with
@@ -79,17 +162,18 @@ def run_chains(pdf, sample_ppdf, theta0s, niter, nburnin, nthin, seed, device=0,
                moments=False, scalar=False, by_chain=False, store_blobs=False):
     """``kmc_metropolis_run`` on dense arrays.  Returns a dict: ``chain [nsamples, nchains, ndim]``,
     ``chain_logp [nsamples, nchains]``, ``accept_ratio``, ``naccept``, ``final_pos``, ``final_logp``,
-    ``chain_sum``/``chain_sumsq [nchains, ndim]``, ``nsamples``, ``device_ms``; with ``store_blobs`` (a ``CDensity(..., nblob=m)``)
+    ``chain_sum``/``chain_sumsq [nchains, ndim]``, ``nsamples``, ``device_ms``, ``chol [ndim, ndim]`` (the ``L`` in force at the end;
+    ``diag(scale)`` for a plain :class:`GaussianStep`, ``None`` with a host proposal), ``tune_skipped``, ``tune_ms``; with ``store_blobs`` (a ``CDensity(..., nblob=m)``)
     also ``blobs [nsamples, nchains, m]`` (``[nchains, nsamples, m]`` with ``by_chain``) and ``final_blob [nchains, m]``.
 
     ``pdf``: a device density, a :class:`~.densities.HostLogPdf` or any callable (wrapped in one); ``sample_ppdf``: a
-    :class:`GaussianStep`, a :class:`HostProposal` or any callable (wrapped in one).  ``scalar``: bare callables get a
+    :class:`GaussianStep`, an :class:`MVNormalStep`, a :class:`TunedStep`, a :class:`HostProposal` or any callable (wrapped in one).  ``scalar``: bare callables get a
     float instead of a 1-element array (the reference's convention for a scalar ``theta0``)."""
     if not isinstance(pdf, DeviceLogPdf):
         if not callable(pdf):
             raise TypeError(f"pdf must be a log-density object or a callable; got {type(pdf).__name__}")
         pdf = HostLogPdf(pdf, scalar=scalar)             # an arbitrary closure, as in the reference (:99): evaluated on the host
-    if not isinstance(sample_ppdf, (GaussianStep, HostProposal)):
+    if not isinstance(sample_ppdf, _DEVICE_STEPS + (HostProposal,)):
         if not callable(sample_ppdf):
             raise TypeError("sample_ppdf must be a GaussianStep (theta -> scale .* randn(n) .+ theta) or a callable")
         sample_ppdf = HostProposal(sample_ppdf, scalar=scalar)
@@ -105,10 +189,18 @@ def run_chains(pdf, sample_ppdf, theta0s, niter, nburnin, nthin, seed, device=0,
     for i in range(8):
         c.params[i] = float(p[i])
     c.nchains, c.ndim, c.niter, c.nburnin, c.nthin = nchains, ndim, int(niter), int(nburnin), int(nthin)
-    step = None
-    if isinstance(sample_ppdf, GaussianStep):
-        step = sample_ppdf.scales(ndim)
+    step = chol = None
+    base = sample_ppdf
+    if isinstance(sample_ppdf, TunedStep):
+        base = sample_ppdf.initial
+        c.tune_rounds = sample_ppdf.rounds
+        c.tune_scale = 0.0 if sample_ppdf.scale is None else float(sample_ppdf.scale)
+    if isinstance(base, GaussianStep):
+        step = base.scales(ndim)
         c.step = _dp(step)
+    elif isinstance(base, MVNormalStep):
+        chol = base.factor(ndim)
+        c.chol = _dp(chol)
     else:
         c.host_propose = C.cast(sample_ppdf.c_callback, C.c_void_p)
     c.seed = int(seed)
@@ -144,6 +236,8 @@ def run_chains(pdf, sample_ppdf, theta0s, niter, nburnin, nthin, seed, device=0,
     blobs = np.zeros((nchains, ns, nblob) if by_chain else (ns, nchains, nblob)) if store_blobs else None
     fblob = np.zeros((nchains, nblob)) if store_blobs else None
     o.blobs, o.final_blob = _dp(blobs), _dp(fblob)
+    chol_out = np.zeros((ndim, ndim)) if isinstance(sample_ppdf, _DEVICE_STEPS) else None
+    o.chol_out = _dp(chol_out)
     with np.errstate(all="ignore"):
         status = L.kmc_metropolis_run(C.byref(c), _dp(theta0s), C.byref(o))
     for obj in (pdf, sample_ppdf):                        # an exception raised inside a host callback: re-raise it here
@@ -154,7 +248,8 @@ def run_chains(pdf, sample_ppdf, theta0s, niter, nburnin, nthin, seed, device=0,
     _lib.check(status)
     assert o.nsamples == ns
     return dict(chain=chain, chain_logp=chain_logp, accept_ratio=acc, naccept=nacc, final_pos=fpos, final_logp=flogp,
-                chain_sum=csum, chain_sumsq=csq, nsamples=ns, device_ms=o.device_ms, blobs=blobs, final_blob=fblob)
+                chain_sum=csum, chain_sumsq=csq, nsamples=ns, device_ms=o.device_ms, blobs=blobs, final_blob=fblob,
+                chol=chol_out, tune_skipped=int(o.tune_skipped), tune_ms=o.tune_ms)
 
 
 def _fresh_seed() -> int:
@@ -220,8 +315,8 @@ def _run(pdf, sample_ppdf, th, niter, nburnin, nthin, hasblob, init_blobs, reduc
     if hasblob and isinstance(pdf, DeviceLogPdf) and not isinstance(pdf, HostLogPdf) and int(getattr(pdf, "nblob", 0) or 0) > 0:
         # a CDensity(..., nblob=m): blob0 follows the chain on the device (:72, :103), the blob of every stored sample comes back
         # (:117); a caller's init_blobs / reduce_blob are then fed each chain's series in order
-        if not isinstance(sample_ppdf, GaussianStep):
-            raise NotImplementedError("device blobs run in the in-kernel chains: sample_ppdf must be a GaussianStep")
+        if not isinstance(sample_ppdf, _DEVICE_STEPS):
+            raise NotImplementedError("device blobs run in the in-kernel chains: sample_ppdf must be a GaussianStep, an MVNormalStep or a TunedStep")
         r = run_chains(pdf, sample_ppdf, th, niter, nburnin, nthin, seed, device, scalar=scalar, by_chain=True, store_blobs=True)
         series = r["blobs"]
         if init_blobs is None and reduce_blob is None:
