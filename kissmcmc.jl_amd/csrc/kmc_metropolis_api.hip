@@ -1,5 +1,8 @@
 // kmc_metropolis_api.hip -- host side of the many-chain Metropolis entry points of include/kissmcmc_hip.h
-// (kmc_metropolis_validate / kmc_metropolis_run; kernels: kmc_metropolis.hpp).
+// (kmc_metropolis_validate / kmc_metropolis_run; kernels: kmc_metropolis.hpp).  kmc_metropolis_run is six steps: the argument checks
+// and validate, the device, metropolis_density_params, metropolis_setup (one MetroRun: the facts of the config, the stream, one
+// MetroBuffers), one route -- metropolis_host_route (caller's closures, an iteration per pass) or metropolis_device_route
+// (metropolis_device_setup, metropolis_select_kernels, then metropolis_launch_stretch per launch) -- and metropolis_read_out.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -52,32 +55,6 @@ kmc_status compile_user_metropolis(kmc_user_density* ud, int ND, const std::vect
 
 template <class T>
 hipError_t metro_alloc(T** p, size_t bytes) { return cache_alloc(reinterpret_cast<void**>(p), bytes); }
-
-// device buffers of one kmc_metropolis_run call
-struct MetroBuffers {
-    double *pos = nullptr, *logp = nullptr, *chain = nullptr, *chain_logp = nullptr, *csum = nullptr, *csumsq = nullptr,
-           *step = nullptr, *xt = nullptr, *yt = nullptr, *st1 = nullptr, *st2 = nullptr, *blob = nullptr, *chain_blob = nullptr;
-    uint32_t* naccept = nullptr;
-    double* draws = nullptr;          // few chains: the draw table of a launch (metro_draw_fill)
-    double* chol = nullptr;           // the packed L of a covariance-shaped proposal
-    hipModule_t mod = nullptr;        // (held through keep)
-    std::shared_ptr<void> keep;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipStream_t stream = nullptr;     // the stream the buffers were used on: waited for before they go back to the allocation cache
-    ~MetroBuffers()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        cache_free(pos); cache_free(logp); cache_free(chain); cache_free(chain_logp); cache_free(csum);
-        cache_free(csumsq); cache_free(step); cache_free(xt); cache_free(yt); cache_free(st1); cache_free(st2);
-        cache_free(naccept); cache_free(blob); cache_free(chain_blob); cache_free(draws); cache_free(chol);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-
-}  // namespace
-
-namespace {
 
 constexpr int64_t kMetroCholMaxDim = 128;         // L is ndim^2 / 2 doubles read per step and lane; nothing larger is tested
 
@@ -188,104 +165,194 @@ void write_chol_out(const kmc_metropolis_config* c, const MetroShape& sh, kmc_me
             for (int64_t j = 0; j < nd; ++j) out->chol_out[i * nd + j] = (i == j && c->step) ? c->step[i] : 0.0;
 }
 
-// The host route of kmc_metropolis_run: `pdf` and / or `sample_ppdf` are caller's closures (src/samplers.jl:59-61).  One
-// iteration of all chains per pass: proposals (device Gaussian step, or host_propose on the current states), their
-// log-pdfs (host_logpdf on the proposals, or the device density), then the accept test, counters and storage on the device.
-kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* theta0, kmc_metropolis_outputs* out,
-                                 const DensityParams& dp, int64_t nsamples)
+// the digested parameters of the config's density (a menu density's are checked on the way: kmc_metropolis_validate's last refusals)
+kmc_status metropolis_density_params(const kmc_metropolis_config* c, DensityParams* dp)
 {
-    const int64_t nc = c->nchains, nd = c->ndim;
-    ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
-    HIP_TRY(ss.create());
-    const hipStream_t st = ss.st;
-    const size_t rows = (size_t)nc * (size_t)nd * sizeof(double), vec = (size_t)nc * sizeof(double);
-    const bool host_pdf = c->density == KMC_HOST_DENSITY;
-    const bool want_chain = (c->flags & KMC_STORE_CHAIN) != 0, want_logp = (c->flags & KMC_STORE_LOGP) != 0, want_mom = (c->flags & KMC_MOMENTS) != 0;
-    struct Buf {
-        double *pos = nullptr, *logp = nullptr, *prop = nullptr, *p1 = nullptr, *chain = nullptr, *chain_logp = nullptr, *csum = nullptr,
-               *csumsq = nullptr, *step = nullptr, *h_rows = nullptr, *h_prop = nullptr, *h_p1 = nullptr;
-        uint32_t* naccept = nullptr;
-        unsigned char *acc = nullptr, *h_acc = nullptr;
-        hipModule_t mod = nullptr;        // (held through keep)
-        std::shared_ptr<void> keep;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        hipStream_t stream = nullptr;     // waited for before the buffers go back to the allocation cache
-        ~Buf()
-        {
-            if (stream) (void)hipStreamSynchronize(stream);
-            cache_free(pos); cache_free(logp); cache_free(prop); cache_free(p1); cache_free(chain); cache_free(chain_logp);
-            cache_free(csum); cache_free(csumsq); cache_free(step); cache_free(naccept); cache_free(acc);
-            if (h_rows) (void)hipHostFree(h_rows);
-            if (h_prop) (void)hipHostFree(h_prop);
-            if (h_p1) (void)hipHostFree(h_p1);
-            if (h_acc) (void)hipHostFree(h_acc);
-            if (ev0) (void)hipEventDestroy(ev0);
-            if (ev1) (void)hipEventDestroy(ev1);
-        }
-    } b;
-    b.stream = st;
-    HIP_TRY(metro_alloc(&b.pos, rows));
-    HIP_TRY(metro_alloc(&b.prop, rows));
-    HIP_TRY(metro_alloc(&b.logp, vec));
-    HIP_TRY(metro_alloc(&b.p1, vec));
-    HIP_TRY(metro_alloc(&b.naccept, (size_t)nc * sizeof(uint32_t)));
-    HIP_TRY(fill_sync(b.naccept, 0, (size_t)nc * sizeof(uint32_t), st));
-    HIP_TRY(copy_sync(b.pos, theta0, rows, hipMemcpyHostToDevice, st));                              // :68 deepcopy
-    MetroShape sh;
-    sh.init(c);
-    if (sh.on) HIP_TRY(sh.alloc(&b.step, st));                                                       // (the packed L in place of the scales)
-    else if (c->step) {
-        HIP_TRY(metro_alloc(&b.step, (size_t)nd * sizeof(double)));
-        HIP_TRY(copy_sync(b.step, c->step, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
+    kmc_config e{};
+    e.density = c->density;
+    for (int i = 0; i < 8; ++i) e.params[i] = c->params[i];
+    e.ndim = c->ndim;
+    e.user_density = c->user_density;
+    return digest_params(e, dp);
+}
+
+// device and page-locked host buffers of one kmc_metropolis_run call, whichever route it takes
+struct MetroBuffers {
+    double *pos = nullptr, *logp = nullptr, *chain = nullptr, *chain_logp = nullptr, *csum = nullptr, *csumsq = nullptr;
+    uint32_t* naccept = nullptr;
+    double *step = nullptr, *chol = nullptr;      // the proposal: a scale per dimension, the packed L of a covariance-shaped one
+    double *xt = nullptr, *yt = nullptr, *st1 = nullptr, *st2 = nullptr;     // device route, chains in memory: dimension-major state and moment sums
+    double *blob = nullptr, *chain_blob = nullptr;
+    double* draws = nullptr;          // few chains: the draw table of a launch (metro_draw_fill)
+    double *prop = nullptr, *p1 = nullptr;                                   // host route: the proposals and their log-pdfs ...
+    unsigned char *acc = nullptr, *h_acc = nullptr;                          // ... the accept decisions (host_accepted) ...
+    double *h_rows = nullptr, *h_prop = nullptr, *h_p1 = nullptr;            // ... and, page-locked as h_acc, what crosses to the callbacks
+    std::shared_ptr<void> keep;       // the module of a runtime-compiled density
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t stream = nullptr;     // the stream the buffers were used on: waited for before they go back to the allocation cache
+    ~MetroBuffers()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (void* p : {(void*)pos, (void*)logp, (void*)chain, (void*)chain_logp, (void*)csum, (void*)csumsq, (void*)naccept, (void*)step, (void*)chol,
+                        (void*)xt, (void*)yt, (void*)st1, (void*)st2, (void*)blob, (void*)chain_blob, (void*)draws, (void*)prop, (void*)p1, (void*)acc})
+            cache_free(p);
+        for (void* p : {(void*)h_rows, (void*)h_prop, (void*)h_p1, (void*)h_acc})
+            if (p) (void)hipHostFree(p);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
     }
-    if ((want_chain || want_logp) && nsamples > 0)
-        KMC_TRY(check_device_room((size_t)nsamples * ((want_chain ? rows : 0) + (want_logp ? vec : 0)), "the Metropolis chain"));
-    if (want_chain && nsamples > 0) HIP_TRY(metro_alloc(&b.chain, (size_t)nsamples * rows));
-    if (want_logp && nsamples > 0) HIP_TRY(metro_alloc(&b.chain_logp, (size_t)nsamples * vec));
-    if (want_mom) {
+};
+
+// One kmc_metropolis_run call: what both routes derive from the config, the stream and the buffers.  (Members die in reverse
+// order: the buffers wait for the stream and go back to the allocation cache first, then the stream itself is destroyed.)
+struct MetroRun {
+    const kmc_metropolis_config* c = nullptr;
+    int64_t nc = 0, nd = 0, nsamples = 0;
+    size_t rows = 0, vec = 0;         // bytes of one [nchains][ndim] block and of one value per chain
+    unsigned grid = 0;                // workgroups of 256 over the chains
+    bool want_chain = false, want_logp = false, want_mom = false, want_blobs = false;
+    int nblob = 0;
+    DensityParams dp{};
+    MetroShape sh;
+    ScopedStream ss;                  // never the legacy stream (kmc_host.hpp: copy_sync)
+    MetroBuffers b;
+};
+
+// The set-up both routes share: the stream, the chains' state from theta0, the counters, the chain and the moment sums.
+kmc_status metropolis_setup(const kmc_metropolis_config* c, const double* theta0, const kmc_metropolis_outputs* out, MetroRun* R)
+{
+    MetroBuffers& b = R->b;
+    R->c = c;
+    R->nc = c->nchains; R->nd = c->ndim; R->nsamples = out->nsamples;
+    R->rows = (size_t)R->nc * (size_t)R->nd * sizeof(double);
+    R->vec = (size_t)R->nc * sizeof(double);
+    R->grid = (unsigned)((R->nc + 255) / 256);
+    R->want_chain = (c->flags & KMC_STORE_CHAIN) != 0; R->want_logp = (c->flags & KMC_STORE_LOGP) != 0; R->want_mom = (c->flags & KMC_MOMENTS) != 0;
+    R->nblob = c->density == KMC_USER_DENSITY ? static_cast<const kmc_user_density*>(c->user_density)->nblob : 0;
+    R->want_blobs = R->nblob > 0 && ((c->flags & KMC_STORE_BLOBS) != 0 || out->blobs != nullptr);
+    R->sh.init(c);
+    HIP_TRY(R->ss.create());
+    const hipStream_t st = b.stream = R->ss.st;
+    const size_t rows = R->rows, vec = R->vec, ns = (size_t)R->nsamples;
+    HIP_TRY(metro_alloc(&b.pos, rows));
+    HIP_TRY(metro_alloc(&b.logp, vec));
+    HIP_TRY(metro_alloc(&b.naccept, (size_t)R->nc * sizeof(uint32_t)));
+    HIP_TRY(fill_sync(b.naccept, 0, (size_t)R->nc * sizeof(uint32_t), st));
+    HIP_TRY(copy_sync(b.pos, theta0, rows, hipMemcpyHostToDevice, st));                              // :68 deepcopy
+    if ((R->want_chain || R->want_logp) && ns > 0)
+        KMC_TRY(check_device_room(ns * ((R->want_chain ? rows : 0) + (R->want_logp ? vec : 0)), "the Metropolis chain"));
+    if (R->want_chain && ns > 0) HIP_TRY(metro_alloc(&b.chain, ns * rows));
+    if (R->want_logp && ns > 0) HIP_TRY(metro_alloc(&b.chain_logp, ns * vec));
+    if (R->sh.on) HIP_TRY(R->sh.alloc(&b.chol, st));
+    if (R->want_mom) {
         HIP_TRY(metro_alloc(&b.csum, rows));
         HIP_TRY(metro_alloc(&b.csumsq, rows));
         HIP_TRY(fill_sync(b.csum, 0, rows, st));
         HIP_TRY(fill_sync(b.csumsq, 0, rows, st));
     }
-    HIP_TRY(hipHostMalloc((void**)&b.h_rows, rows, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&b.h_prop, rows, hipHostMallocDefault));
-    HIP_TRY(hipHostMalloc((void**)&b.h_p1, vec, hipHostMallocDefault));
-    if (c->host_accepted) {
-        HIP_TRY(hipMalloc((void**)&b.acc, (size_t)nc));
-        HIP_TRY(hipHostMalloc((void**)&b.h_acc, (size_t)nc, hipHostMallocDefault));
+    HIP_TRY(hipEventCreate(&b.ev0));
+    HIP_TRY(hipEventCreate(&b.ev1));
+    return KMC_OK;
+}
+
+// log-pdf of device rows -> device vector (and those rows' blobs, or nullptr): a module's function, or the menu density's
+hipError_t launch_logpdf(const MetroRun& R, hipFunction_t ulp, const double* rows_dev, double* out_dev, double* blob_dev)
+{
+    const LogpdfArgs la{rows_dev, out_dev, R.nc, (int32_t)R.nd, (int32_t)R.nd, R.dp, blob_dev};
+    if (ulp) return launch_module(ulp, R.grid, 256u, R.ss.st, la);
+    hipLaunchKernelGGL(logpdf_fn(R.c->density), dim3(R.grid), dim3(256), 0, R.ss.st, la);
+    return hipGetLastError();
+}
+
+// The read-out both routes share: device_ms between the two events the route recorded, the tuning report, every output asked for.
+// (The host route has no blobs: those branches see null pointers.)
+kmc_status metropolis_read_out(MetroRun& R, kmc_metropolis_outputs* out)
+{
+    const kmc_metropolis_config* c = R.c;
+    const MetroBuffers& b = R.b;
+    const hipStream_t st = R.ss.st;
+    const int64_t nc = R.nc, nd = R.nd, nsamples = R.nsamples, nblob = R.nblob;
+    const size_t rows = R.rows, vec = R.vec, bb = (size_t)nc * (size_t)nblob * sizeof(double);
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
+    out->device_ms = (double)ms;
+    R.sh.report(out);
+    if (!c->host_propose) write_chol_out(c, R.sh, out);        // (proposals from the host: there is no L)
+    if (c->flags & KMC_CHAIN_BY_WALKER) {       // thetas[chain][sample], as the reference returns them (:113, :128)
+        if (out->chain && b.chain) KMC_TRY(download_by_walker(b.chain, false, nc, nd, nd, nsamples, out->chain, st));
+        if (out->chain_logp && b.chain_logp) KMC_TRY(download_by_walker(b.chain_logp, false, nc, 1, 1, nsamples, out->chain_logp, st));
+        if (out->blobs && b.chain_blob) KMC_TRY(download_by_walker(b.chain_blob, false, nc, nblob, nblob, nsamples, out->blobs, st));      // (:117)
+    } else {
+        if (out->chain && b.chain) HIP_TRY(copy_sync(out->chain, b.chain, (size_t)nsamples * rows, hipMemcpyDeviceToHost, st));
+        if (out->chain_logp && b.chain_logp) HIP_TRY(copy_sync(out->chain_logp, b.chain_logp, (size_t)nsamples * vec, hipMemcpyDeviceToHost, st));
+        if (out->blobs && b.chain_blob) HIP_TRY(copy_sync(out->blobs, b.chain_blob, (size_t)nsamples * bb, hipMemcpyDeviceToHost, st));
     }
-    // log-pdf of device rows -> device vector, for a device density
-    LogpdfFn lp = nullptr;
-    hipFunction_t ulp = nullptr;
-    if (!host_pdf) {
-        if (c->density == KMC_USER_DENSITY) {
-            const std::vector<char>* code = nullptr;
-            KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), metropolis_nd(nd), &code, nd));
-            KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep));
-            b.mod = static_cast<hipModule_t>(b.keep.get());
-            HIP_TRY(hipModuleGetFunction(&ulp, b.mod, "kmc_user_logpdf"));
-        } else {
-            lp = logpdf_fn(c->density);
-            if (!lp) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+    if (out->final_blob && b.blob) HIP_TRY(copy_sync(out->final_blob, b.blob, bb, hipMemcpyDeviceToHost, st));
+    if (out->final_pos) HIP_TRY(copy_sync(out->final_pos, b.pos, rows, hipMemcpyDeviceToHost, st));
+    if (out->final_logp) HIP_TRY(copy_sync(out->final_logp, b.logp, vec, hipMemcpyDeviceToHost, st));
+    if (out->chain_sum && b.csum) HIP_TRY(copy_sync(out->chain_sum, b.csum, rows, hipMemcpyDeviceToHost, st));
+    if (out->chain_sumsq && b.csumsq) HIP_TRY(copy_sync(out->chain_sumsq, b.csumsq, rows, hipMemcpyDeviceToHost, st));
+    if (out->naccept || out->accept_ratio) {
+        std::vector<uint32_t> na((size_t)nc);
+        HIP_TRY(copy_sync(na.data(), b.naccept, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        const double denom = (double)(c->niter - c->nburnin);                                   // :127 (0/0 as in the reference)
+        for (int64_t i = 0; i < nc; ++i) {
+            if (out->naccept) out->naccept[i] = (int64_t)na[(size_t)i];
+            if (out->accept_ratio) out->accept_ratio[i] = (double)na[(size_t)i] / denom;
         }
     }
-    const unsigned grid = (unsigned)((nc + 255) / 256);
-    auto device_logpdf = [&](const double* rows_dev, double* out_dev) -> hipError_t {
-        const LogpdfArgs la{rows_dev, out_dev, nc, (int32_t)nd, (int32_t)nd, dp, nullptr};
-        if (ulp) return launch_module(ulp, grid, 256u, st, la);
-        hipLaunchKernelGGL(lp, dim3(grid), dim3(256), 0, st, la);
-        return hipGetLastError();
-    };
+    return KMC_OK;
+}
+
+// the host route's buffers on top of the shared ones, and the log-pdf function of a device density
+kmc_status metropolis_host_setup(MetroRun& R, hipFunction_t* ulp)
+{
+    const kmc_metropolis_config* c = R.c;
+    MetroBuffers& b = R.b;
+    HIP_TRY(metro_alloc(&b.prop, R.rows));
+    HIP_TRY(metro_alloc(&b.p1, R.vec));
+    if (c->step && !R.sh.on) {
+        HIP_TRY(metro_alloc(&b.step, (size_t)R.nd * sizeof(double)));
+        HIP_TRY(copy_sync(b.step, c->step, (size_t)R.nd * sizeof(double), hipMemcpyHostToDevice, R.ss.st));
+    }
+    HIP_TRY(hipHostMalloc((void**)&b.h_rows, R.rows, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&b.h_prop, R.rows, hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc((void**)&b.h_p1, R.vec, hipHostMallocDefault));
+    if (c->host_accepted) {
+        HIP_TRY(hipMalloc((void**)&b.acc, (size_t)R.nc));
+        HIP_TRY(hipHostMalloc((void**)&b.h_acc, (size_t)R.nc, hipHostMallocDefault));
+    }
+    if (c->density == KMC_USER_DENSITY) {
+        const std::vector<char>* code = nullptr;
+        KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), metropolis_nd(R.nd), &code, R.nd));
+        KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep));
+        HIP_TRY(hipModuleGetFunction(ulp, static_cast<hipModule_t>(b.keep.get()), "kmc_user_logpdf"));
+    } else if (c->density != KMC_HOST_DENSITY && !logpdf_fn(c->density)) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+    return KMC_OK;
+}
+
+// The host route: `pdf` and / or `sample_ppdf` are caller's closures (src/samplers.jl:59-61).  One iteration of all chains per pass:
+// proposals (the device's step, or host_propose on the current states), their log-pdfs
+// (host_logpdf on the proposals, or the device density), then the accept test, counters and storage on the device.
+kmc_status metropolis_host_route(MetroRun& R, const double* theta0)
+{
+    const kmc_metropolis_config* c = R.c;
+    MetroBuffers& b = R.b;
+    MetroShape& sh = R.sh;
+    const hipStream_t st = R.ss.st;
+    const int64_t nc = R.nc, nd = R.nd;
+    const size_t rows = R.rows;
+    const bool host_pdf = c->density == KMC_HOST_DENSITY;
+    hipFunction_t ulp = nullptr;
+    KMC_TRY(metropolis_host_setup(R, &ulp));
     // p0 = pdf(theta0) (:70); whatever comes out is carried, -Inf included, as in the reference
     if (host_pdf) {
         if (c->host_logpdf(theta0, nc, nd, b.h_p1, c->host_user) != 0) return fail(KMC_ERR_BAD_ARG, "the host log-pdf callback failed on the initial states");
-        HIP_TRY(copy_sync(b.logp, b.h_p1, vec, hipMemcpyHostToDevice, st));
+        HIP_TRY(copy_sync(b.logp, b.h_p1, R.vec, hipMemcpyHostToDevice, st));
     } else {
-        HIP_TRY(device_logpdf(b.pos, b.logp));
+        HIP_TRY(launch_logpdf(R, ulp, b.pos, b.logp, nullptr));
     }
-    HIP_TRY(hipEventCreate(&b.ev0));
-    HIP_TRY(hipEventCreate(&b.ev1));
     HIP_TRY(hipEventRecord(b.ev0, st));
     int64_t cnt = 0, slot = 0;
     for (int64_t it = 0; it < c->niter; ++it) {
@@ -293,12 +360,13 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
         if (sh.on && sh.boundary(it)) KMC_TRY(sh.tune(b.pos, nc, st));
         MetroHostArgs a{};
         a.pos = b.pos; a.logp = b.logp; a.naccept = b.naccept; a.prop = b.prop; a.p1 = b.p1;
-        a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq; a.step = b.step; a.acc_out = b.acc;
+        a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq; a.acc_out = b.acc;
+        a.step = sh.on ? b.chol : b.step;                                                        // (the packed L in place of the scales)
         a.nchains = nc; a.it = it; a.n = n; a.ndim = (int32_t)nd;
         a.seed_lo = (uint32_t)c->seed; a.seed_hi = (uint32_t)(c->seed >> 32);
         if (n > 0 && ++cnt == c->nthin) {                                                        // :108, :112
             cnt = 0;
-            if (slot < nsamples) { a.store = 1; a.slot = slot; }
+            if (slot < R.nsamples) { a.store = 1; a.slot = slot; }
             ++slot;
         }
         if (c->host_propose) {                                                                   // :98 theta1 = sample_ppdf(theta0)
@@ -307,19 +375,19 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
                 return fail(KMC_ERR_BAD_ARG, "the host proposal callback failed in iteration " + std::to_string(it));
             HIP_TRY(copy_sync(b.prop, b.h_prop, rows, hipMemcpyHostToDevice, st));
         } else {
-            if (sh.on) hipLaunchKernelGGL(metro_host_propose_mv, dim3(grid), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL(metro_host_propose, dim3(grid), dim3(256), 0, st, a);
+            if (sh.on) hipLaunchKernelGGL(metro_host_propose_mv, dim3(R.grid), dim3(256), 0, st, a);
+            else hipLaunchKernelGGL(metro_host_propose, dim3(R.grid), dim3(256), 0, st, a);
             HIP_TRY(hipGetLastError());
         }
         if (host_pdf) {                                                                          // :99 p1 = pdf(theta1)
             if (!c->host_propose) HIP_TRY(copy_sync(b.h_prop, b.prop, rows, hipMemcpyDeviceToHost, st));
             if (c->host_logpdf(b.h_prop, nc, nd, b.h_p1, c->host_user) != 0)
                 return fail(KMC_ERR_BAD_ARG, "the host log-pdf callback failed in iteration " + std::to_string(it));
-            HIP_TRY(copy_sync(b.p1, b.h_p1, vec, hipMemcpyHostToDevice, st));
+            HIP_TRY(copy_sync(b.p1, b.h_p1, R.vec, hipMemcpyHostToDevice, st));
         } else {
-            HIP_TRY(device_logpdf(b.prop, b.p1));
+            HIP_TRY(launch_logpdf(R, ulp, b.prop, b.p1, nullptr));
         }
-        hipLaunchKernelGGL(metro_host_accept, dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(metro_host_accept, dim3(R.grid), dim3(256), 0, st, a);
         HIP_TRY(hipGetLastError());
         if (c->host_accepted) {
             HIP_TRY(copy_sync(b.h_acc, b.acc, (size_t)nc, hipMemcpyDeviceToHost, st));
@@ -328,31 +396,183 @@ kmc_status metropolis_host_route(const kmc_metropolis_config* c, const double* t
         }
     }
     HIP_TRY(hipEventRecord(b.ev1, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
-    out->device_ms = (double)ms;
-    sh.report(out);
-    if (!c->host_propose) write_chol_out(c, sh, out);
-    if (c->flags & KMC_CHAIN_BY_WALKER) {       // thetas[chain][sample], as the reference returns them (:113, :128)
-        if (out->chain && b.chain) KMC_TRY(download_by_walker(b.chain, false, nc, nd, nd, nsamples, out->chain, st));
-        if (out->chain_logp && b.chain_logp) KMC_TRY(download_by_walker(b.chain_logp, false, nc, 1, 1, nsamples, out->chain_logp, st));
+    return KMC_OK;
+}
+
+// The kernels of one run.  ND: the register geometry of the chains, 0 for chains kept dimension-major in memory; tabled: the
+// few-chains route, whose chains stay in registers whatever the density and read the draws of table_steps iterations per launch.
+struct MetroKernels {
+    int ND = 0;
+    bool tabled = false;
+    MetropolisFn fn = nullptr;                    // a menu density's kernels ...
+    MetropolisTabledFn tfn = nullptr;
+    hipFunction_t ufn = nullptr, ulp = nullptr, utfn = nullptr;       // ... or a module's
+    int64_t table_steps = 0;
+};
+
+kmc_status metropolis_select_kernels(MetroRun& R, MetroKernels* k)
+{
+    const kmc_metropolis_config* c = R.c;
+    const int64_t nc = R.nc, nd = R.nd;
+    kmc_user_density* ud = c->density == KMC_USER_DENSITY ? static_cast<kmc_user_density*>(c->user_density) : nullptr;
+    k->ND = ud && ud->is_body ? 0 : metropolis_nd(nd);
+    // Few chains (the reference's call is one): the draws of a stretch of iterations come from a wide kernel first, the chains
+    // only read them (kmc_metropolis.hpp: metropolis_chains_tabled).  Up to a wave per CU (measured: x6.8 at one chain, x4 at
+    // 4096, x2 at 16 384, x0.5 at 65 536 -- there the chains fill the chip themselves).  KMC_DEBUG=metro-table=0|1 forces it off / on.
+    std::string opt;
+    const bool have = debug_opt("metro-table", &opt);
+    const bool off = have && opt == "0", on = have && opt == "1";
+    // (up to 8 dimensions for up to 16 384 chains -- measured --; longer rows for the few chains that leave most of the chip idle)
+    const int64_t nd_max = ud ? 32 : 8;           // (menu densities: instantiated up to 8 -- build time)
+    const bool tabled = k->tabled = !off && R.nblob == 0 && ((nd <= 8 && nc <= 16384) || (nd <= nd_max && nc <= 1024) || (on && nd <= nd_max));
+    if (ud) {
+        const std::vector<char>* code = nullptr;
+        // (the few-chains kernel is the same with L: the isotropic program serves it)
+        KMC_TRY(compile_user_metropolis(ud, k->ND, &code, nd, tabled ? metropolis_nd(nd) : 0, R.sh.on && !tabled));
+        KMC_TRY(shared_module(ud, code, &R.b.keep));
+        const hipModule_t mod = static_cast<hipModule_t>(R.b.keep.get());
+        HIP_TRY(hipModuleGetFunction(&k->ufn, mod, "kmc_user_metropolis"));
+        HIP_TRY(hipModuleGetFunction(&k->ulp, mod, "kmc_user_logpdf"));
+        if (tabled) HIP_TRY(hipModuleGetFunction(&k->utfn, mod, "kmc_user_metropolis_tabled"));
     } else {
-        if (out->chain && b.chain) HIP_TRY(copy_sync(out->chain, b.chain, (size_t)nsamples * rows, hipMemcpyDeviceToHost, st));
-        if (out->chain_logp && b.chain_logp) HIP_TRY(copy_sync(out->chain_logp, b.chain_logp, (size_t)nsamples * vec, hipMemcpyDeviceToHost, st));
+        const int n = (int)std::min<int64_t>(nd, 1 << 20);        // the geometry follows ndim (registers <= 32)
+        k->fn = with_density(c->density, MetropolisFn(nullptr),
+                             [&](auto d) { return R.sh.on ? metropolis_mv_lookup<decltype(d)>(n) : metropolis_lookup<decltype(d)>(n); });
+        if (!k->fn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
     }
-    if (out->final_pos) HIP_TRY(copy_sync(out->final_pos, b.pos, rows, hipMemcpyDeviceToHost, st));
-    if (out->final_logp) HIP_TRY(copy_sync(out->final_logp, b.logp, vec, hipMemcpyDeviceToHost, st));
-    if (out->chain_sum && b.csum) HIP_TRY(copy_sync(out->chain_sum, b.csum, rows, hipMemcpyDeviceToHost, st));
-    if (out->chain_sumsq && b.csumsq) HIP_TRY(copy_sync(out->chain_sumsq, b.csumsq, rows, hipMemcpyDeviceToHost, st));
-    if (out->naccept || out->accept_ratio) {
-        std::vector<uint32_t> na((size_t)nc);
-        HIP_TRY(copy_sync(na.data(), b.naccept, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        const double denom = (double)(c->niter - c->nburnin);                                   // :127
-        for (int64_t i = 0; i < nc; ++i) {
-            if (out->naccept) out->naccept[i] = (int64_t)na[(size_t)i];
-            if (out->accept_ratio) out->accept_ratio[i] = (double)na[(size_t)i] / denom;
+    if (!tabled) return KMC_OK;
+    if (!ud) {
+        k->tfn = with_density(c->density, MetropolisTabledFn(nullptr), [&](auto d) { return metropolis_tabled_lookup<decltype(d)>((int)nd); });
+        if (!k->tfn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k->tfn), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kMetroTileBytes));
+    }
+    const int64_t per_step = nc * (nd + 1) * (int64_t)sizeof(double);
+    k->table_steps = std::max<int64_t>(64, std::min<int64_t>(1 << 16, ((int64_t)128 << 20) / per_step));
+    { const long ts = debug_opt_long("metro-table-steps", 0); if (ts > 0) k->table_steps = ts; }   // (tests: seams)
+    k->table_steps = std::min<int64_t>(k->table_steps, std::max<int64_t>(c->niter, 1));
+    HIP_TRY(metro_alloc(&R.b.draws, (size_t)(k->table_steps * per_step)));
+    return KMC_OK;
+}
+
+// the device route's buffers on top of the shared ones: the scales and the blobs (the kernels chosen add the draw table and the
+// dimension-major state)
+kmc_status metropolis_device_setup(MetroRun& R)
+{
+    const kmc_metropolis_config* c = R.c;
+    MetroBuffers& b = R.b;
+    const hipStream_t st = R.ss.st;
+    const std::vector<double> ones((size_t)R.nd, 1.0);       // (with L: a step of 1.0 for the few-chains kernel, whose table then holds L z)
+    HIP_TRY(metro_alloc(&b.step, (size_t)R.nd * sizeof(double)));
+    HIP_TRY(copy_sync(b.step, R.sh.on ? ones.data() : c->step, (size_t)R.nd * sizeof(double), hipMemcpyHostToDevice, st));
+    if (R.nblob > 0) {
+        const size_t bb = (size_t)R.nc * (size_t)R.nblob * sizeof(double);
+        HIP_TRY(metro_alloc(&b.blob, bb));
+        HIP_TRY(fill_sync(b.blob, 0, bb, st));
+        if (R.want_blobs && R.nsamples > 0) {
+            KMC_TRY(check_device_room((size_t)R.nsamples * bb, "the stored blobs"));
+            HIP_TRY(metro_alloc(&b.chain_blob, (size_t)R.nsamples * bb));
         }
+    }
+    return KMC_OK;
+}
+
+// the iterations [it0, it1) of every chain in the device route: the draw table first (and L applied to it) on the few-chains route, then one kernel
+kmc_status metropolis_launch_stretch(const MetroRun& R, const MetroKernels& k, int64_t it0, int64_t it1)
+{
+    const kmc_metropolis_config* c = R.c;
+    const MetroBuffers& b = R.b;
+    const hipStream_t st = R.ss.st;
+    const int64_t nc = R.nc;
+    MetropolisArgs a{};
+    a.pos = b.pos; a.logp = b.logp; a.naccept = b.naccept;
+    a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq;
+    a.step = (R.sh.on && !k.tabled) ? b.chol : b.step; a.xt = b.xt; a.yt = b.yt; a.st1 = b.st1; a.st2 = b.st2;
+    a.nchains = nc;
+    a.it0 = it0; a.it1 = it1;
+    a.nburnin = c->nburnin; a.nthin = c->nthin; a.nsamples = R.nsamples;
+    const int64_t npos = it0 - c->nburnin;          // steps with n > 0 taken before it0
+    a.cnt0 = npos > 0 ? npos % c->nthin : 0;
+    a.slot0 = npos > 0 ? npos / c->nthin : 0;
+    a.ndim = (int32_t)R.nd;
+    a.seed_lo = (uint32_t)c->seed; a.seed_hi = (uint32_t)(c->seed >> 32);
+    a.dp = R.dp;
+    a.blob = b.blob; a.chain_blob = b.chain_blob;
+    if (!k.tabled) {
+        if (k.ufn) HIP_TRY(launch_module(k.ufn, R.grid, 256u, st, a));
+        else {
+            hipLaunchKernelGGL(k.fn, dim3(R.grid), dim3(256), 0, st, a);
+            HIP_TRY(hipGetLastError());
+        }
+        return KMC_OK;
+    }
+    const int64_t nit = it1 - it0;
+    const unsigned fill_grid = (unsigned)((nit * nc + 255) / 256), chain_grid = (unsigned)((nc + 63) / 64);
+    MetroDrawArgs da{};
+    da.out = b.draws; da.nchains = nc; da.it0 = it0; da.nsteps = (int32_t)nit; da.ndim = (int32_t)R.nd;
+    da.seed_lo = a.seed_lo; da.seed_hi = a.seed_hi;
+    hipLaunchKernelGGL(metro_draw_fill, dim3(fill_grid), dim3(256), 0, st, da);
+    if (R.sh.on) {                                   // the normals of the table become L z
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(metro_draw_shape, dim3(fill_grid), dim3(256), 0, st, MetroDrawMvArgs{da, b.chol});
+    }
+    HIP_TRY(hipGetLastError());
+    if (k.utfn) {
+        MetropolisTabledArgs ta{};
+        ta.a = a; ta.draws = b.draws; ta.nsteps = (int32_t)nit;
+        HIP_TRY(launch_module(k.utfn, chain_grid, 128u, st, ta, 2u * kMetroTileBytes));
+    } else {
+        hipLaunchKernelGGL(k.tfn, dim3(chain_grid), dim3(128), 2 * kMetroTileBytes, st, a, (const double*)b.draws, (int)nit);
+        HIP_TRY(hipGetLastError());
+    }
+    return KMC_OK;
+}
+
+// The device route: the whole run inside kernels, one chain per lane; the loop walks the launches and the tuning boundaries.
+kmc_status metropolis_device_route(MetroRun& R)
+{
+    const kmc_metropolis_config* c = R.c;
+    MetroBuffers& b = R.b;
+    MetroShape& sh = R.sh;
+    const hipStream_t st = R.ss.st;
+    MetroKernels k;
+    KMC_TRY(metropolis_device_setup(R));            // (before the compile: the refusal for the stored blobs' room comes first)
+    KMC_TRY(metropolis_select_kernels(R, &k));
+    if (k.ND == 0) {                                // chains in memory: their state and moment sums dimension-major
+        HIP_TRY(metro_alloc(&b.xt, R.rows));
+        HIP_TRY(metro_alloc(&b.yt, R.rows));
+        if (R.want_mom) {
+            HIP_TRY(metro_alloc(&b.st1, R.rows));
+            HIP_TRY(metro_alloc(&b.st2, R.rows));
+            HIP_TRY(fill_sync(b.st1, 0, R.rows, st));
+            HIP_TRY(fill_sync(b.st2, 0, R.rows, st));
+        }
+    }
+    // p0 = pdf(theta0)  (:70); unlike emcee the reference carries whatever comes out, -Inf included  (and blob0, :70-72)
+    HIP_TRY(launch_logpdf(R, k.ulp, b.pos, b.logp, b.blob));
+    const bool in_memory = k.ND == 0 && !k.tabled;  // (the few-chains kernel keeps its chains in registers whatever the density)
+    auto transpose = [&](const double* src, double* dst, bool to_dim_major) {
+        const TransposeArgs ta{src, dst, R.nc, (int32_t)R.nd, to_dim_major ? 1 : 0};
+        hipLaunchKernelGGL(metropolis_transpose, dim3(R.grid), dim3(256), 0, st, ta);
+        return hipGetLastError();
+    };
+    if (in_memory) HIP_TRY(transpose(b.pos, b.xt, true));
+    HIP_TRY(hipEventRecord(b.ev0, st));
+    const int64_t kItersPerLaunch = k.tabled ? k.table_steps : (int64_t)1 << 16;   // chains are independent: launches only bound a kernel's run time (and the table)
+    for (int64_t it0 = 0, it1 = 0; it0 < c->niter; it0 = it1) {
+        it1 = std::min<int64_t>(c->niter, it0 + kItersPerLaunch);
+        if (sh.on) {                                    // a tuning boundary always ends a launch; L is replaced before iteration b_r runs
+            if (sh.boundary(it0)) {
+                if (in_memory) HIP_TRY(transpose(b.xt, b.pos, false));     // (the covariance reads the states chain-major)
+                KMC_TRY(sh.tune(b.pos, R.nc, st));
+            }
+            it1 = sh.next_boundary(it0, it1);
+        }
+        KMC_TRY(metropolis_launch_stretch(R, k, it0, it1));
+    }
+    HIP_TRY(hipEventRecord(b.ev1, st));
+    if (in_memory) {
+        HIP_TRY(transpose(b.xt, b.pos, false));
+        if (R.want_mom) { HIP_TRY(transpose(b.st1, b.csum, false)); HIP_TRY(transpose(b.st2, b.csumsq, false)); }
     }
     return KMC_OK;
 }
@@ -418,12 +638,8 @@ KMC_EXPORT kmc_status kmc_metropolis_validate(const kmc_metropolis_config* c)
         return KMC_OK;
     }
     KMC_TRY(check_ndim(c->density, c->ndim));
-    kmc_config e{};
-    e.density = c->density;
-    for (int i = 0; i < 8; ++i) e.params[i] = c->params[i];
-    e.ndim = c->ndim;
     DensityParams dp;
-    return digest_params(e, &dp);
+    return metropolis_density_params(c, &dp);
 }
 
 KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const double* theta0, kmc_metropolis_outputs* out)
@@ -437,235 +653,15 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     }
     if (c->device < 0 || c->device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
     HIP_TRY(hipSetDevice(c->device));
-    const int64_t nc = c->nchains, nd = c->ndim;
-    const int64_t nsamples = c->niter > c->nburnin ? (c->niter - c->nburnin) / c->nthin : 0;      // :88
-    out->nsamples = nsamples;
+    out->nsamples = c->niter > c->nburnin ? (c->niter - c->nburnin) / c->nthin : 0;                 // :88
     out->device_ms = 0.0;
-    const bool want_chain = (c->flags & KMC_STORE_CHAIN) != 0, want_logp = (c->flags & KMC_STORE_LOGP) != 0,
-               want_mom = (c->flags & KMC_MOMENTS) != 0;
-
-    kmc_config e{};
-    e.density = c->density;
-    for (int i = 0; i < 8; ++i) e.params[i] = c->params[i];
-    e.ndim = nd;
-    e.user_density = c->user_density;
-    e.device = c->device;
-    DensityParams dp{};
-    if (c->density == KMC_USER_DENSITY) { for (int i = 0; i < 6; ++i) dp.p[i] = c->params[i]; dp.ndim = (int32_t)nd; }
-    else if (c->density == KMC_HOST_DENSITY) dp.ndim = (int32_t)nd;
-    else KMC_TRY(digest_params(e, &dp));
-    if (c->density == KMC_HOST_DENSITY || c->host_propose)
-        return metropolis_host_route(c, theta0, out, dp, nsamples);
-    const int nblob = c->density == KMC_USER_DENSITY ? static_cast<const kmc_user_density*>(c->user_density)->nblob : 0;
-    const bool want_blobs = nblob > 0 && ((c->flags & KMC_STORE_BLOBS) != 0 || out->blobs != nullptr);
-
-    ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
-    HIP_TRY(ss.create());
-    const hipStream_t st = ss.st;
-    MetroBuffers b;
-    b.stream = st;
-    const size_t rows = (size_t)nc * (size_t)nd * sizeof(double);
-    HIP_TRY(metro_alloc(&b.pos, rows));
-    HIP_TRY(metro_alloc(&b.logp, (size_t)nc * sizeof(double)));
-    HIP_TRY(metro_alloc(&b.naccept, (size_t)nc * sizeof(uint32_t)));
-    HIP_TRY(fill_sync(b.naccept, 0, (size_t)nc * sizeof(uint32_t), st));
-    MetroShape sh;
-    sh.init(c);
-    HIP_TRY(metro_alloc(&b.step, (size_t)nd * sizeof(double)));
-    {   // (with L: a step of 1.0 for the few-chains kernel, whose table then holds L z)
-        const std::vector<double> ones((size_t)nd, 1.0);
-        HIP_TRY(copy_sync(b.step, sh.on ? ones.data() : c->step, (size_t)nd * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    if (sh.on) HIP_TRY(sh.alloc(&b.chol, st));
-    HIP_TRY(copy_sync(b.pos, theta0, rows, hipMemcpyHostToDevice, st));                              // :68 deepcopy
-    if ((want_chain || want_logp) && nsamples > 0)
-        KMC_TRY(check_device_room((size_t)nsamples * ((want_chain ? rows : 0) + (want_logp ? (size_t)nc * sizeof(double) : 0)), "the Metropolis chain"));
-    if (want_chain && nsamples > 0) HIP_TRY(metro_alloc(&b.chain, (size_t)nsamples * rows));
-    if (want_logp && nsamples > 0) HIP_TRY(metro_alloc(&b.chain_logp, (size_t)nsamples * (size_t)nc * sizeof(double)));
-    if (want_mom) {
-        HIP_TRY(metro_alloc(&b.csum, rows));
-        HIP_TRY(metro_alloc(&b.csumsq, rows));
-        HIP_TRY(fill_sync(b.csum, 0, rows, st));
-        HIP_TRY(fill_sync(b.csumsq, 0, rows, st));
-    }
-    if (nblob > 0) {
-        const size_t bb = (size_t)nc * (size_t)nblob * sizeof(double);
-        HIP_TRY(metro_alloc(&b.blob, bb));
-        HIP_TRY(fill_sync(b.blob, 0, bb, st));
-        if (want_blobs && nsamples > 0) {
-            KMC_TRY(check_device_room((size_t)nsamples * bb, "the stored blobs"));
-            HIP_TRY(metro_alloc(&b.chain_blob, (size_t)nsamples * bb));
-        }
-    }
-    int ND = metropolis_nd(nd);
-    if (c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->is_body) ND = 0;   // body density: chain in memory
-    if (ND == 0) {      // chains too long for registers (or a body density): state kept dimension-major in memory
-        HIP_TRY(metro_alloc(&b.xt, rows));
-        HIP_TRY(metro_alloc(&b.yt, rows));
-        if (want_mom) {
-            HIP_TRY(metro_alloc(&b.st1, rows));
-            HIP_TRY(metro_alloc(&b.st2, rows));
-            HIP_TRY(fill_sync(b.st1, 0, rows, st));
-            HIP_TRY(fill_sync(b.st2, 0, rows, st));
-        }
-    }
-
-    // Few chains (the reference's call is one): the draws of a stretch of iterations come from a wide kernel first, the chains
-    // only read them (kmc_metropolis.hpp: metropolis_chains_tabled).  Up to a wave per CU (measured: x6.8 at one chain, x4 at
-    // 4096, x2 at 16 384, x0.5 at 65 536 -- there the chains fill the chip themselves).  KMC_DEBUG=metro-table=0|1 forces it off / on.
-    bool tabled = false;
-    {
-        std::string opt;
-        const bool have = debug_opt("metro-table", &opt);
-        const bool off = have && opt == "0", on = have && opt == "1";
-        // (up to 8 dimensions for up to 16 384 chains -- measured --; longer rows for the few chains that leave most of the chip idle)
-        const int64_t nd_max = c->density == KMC_USER_DENSITY ? 32 : 8;       // (menu densities: instantiated up to 8 -- build time)
-        tabled = !off && nblob == 0 && ((nd <= 8 && nc <= 16384) || (nd <= nd_max && nc <= 1024) || (on && nd <= nd_max));
-    }
-    MetropolisFn fn = nullptr;
-    hipFunction_t ufn = nullptr, ulp = nullptr, utfn = nullptr;
-    if (c->density == KMC_USER_DENSITY) {
-        const std::vector<char>* code = nullptr;
-        // (the few-chains kernel is the same with L: the isotropic program serves it)
-        KMC_TRY(compile_user_metropolis(static_cast<kmc_user_density*>(c->user_density), ND, &code, nd, tabled ? metropolis_nd(nd) : 0, sh.on && !tabled));
-        KMC_TRY(shared_module(static_cast<kmc_user_density*>(c->user_density), code, &b.keep));
-        b.mod = static_cast<hipModule_t>(b.keep.get());
-        HIP_TRY(hipModuleGetFunction(&ufn, b.mod, "kmc_user_metropolis"));
-        HIP_TRY(hipModuleGetFunction(&ulp, b.mod, "kmc_user_logpdf"));
-        if (tabled) HIP_TRY(hipModuleGetFunction(&utfn, b.mod, "kmc_user_metropolis_tabled"));
-    } else {
-        fn = with_density(c->density, MetropolisFn(nullptr),    // the geometry follows ndim (registers <= 32)
-                          [&](auto d) {
-                              const int n = (int)std::min<int64_t>(nd, 1 << 20);
-                              return sh.on ? metropolis_mv_lookup<decltype(d)>(n) : metropolis_lookup<decltype(d)>(n);
-                          });
-        if (!fn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
-    }
-    const unsigned grid = (unsigned)((nc + 255) / 256);
-    MetropolisTabledFn tfn = nullptr;
-    int64_t table_steps = 0;
-    if (tabled) {
-        if (c->density != KMC_USER_DENSITY) {
-            tfn = with_density(c->density, MetropolisTabledFn(nullptr), [&](auto d) { return metropolis_tabled_lookup<decltype(d)>((int)nd); });
-            if (!tfn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tfn), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kMetroTileBytes));
-        }
-        const int64_t per_step = nc * (nd + 1) * (int64_t)sizeof(double);
-        table_steps = std::max<int64_t>(64, std::min<int64_t>(1 << 16, ((int64_t)128 << 20) / per_step));
-        { const long ts = debug_opt_long("metro-table-steps", 0); if (ts > 0) table_steps = ts; }   // (tests: seams)
-        table_steps = std::min<int64_t>(table_steps, std::max<int64_t>(c->niter, 1));
-        HIP_TRY(metro_alloc(&b.draws, (size_t)(table_steps * per_step)));
-    }
-
-    // p0 = pdf(theta0)  (:70); unlike emcee the reference carries whatever comes out, -Inf included
-    const LogpdfArgs la{b.pos, b.logp, nc, (int32_t)nd, (int32_t)nd, dp, b.blob};      // (and blob0, :70-72)
-    if (ulp) HIP_TRY(launch_module(ulp, grid, 256u, st, la));
-    else {
-        hipLaunchKernelGGL(logpdf_fn(c->density), dim3(grid), dim3(256), 0, st, la);
-        HIP_TRY(hipGetLastError());
-    }
-
-    auto transpose = [&](const double* src, double* dst, bool to_dim_major) {
-        const TransposeArgs ta{src, dst, nc, (int32_t)nd, to_dim_major ? 1 : 0};
-        hipLaunchKernelGGL(metropolis_transpose, dim3(grid), dim3(256), 0, st, ta);
-        return hipGetLastError();
-    };
-    if (ND == 0 && !tabled) HIP_TRY(transpose(b.pos, b.xt, true));     // (the few-chains kernel keeps its chains in registers whatever the density)
-
-    HIP_TRY(hipEventCreate(&b.ev0));
-    HIP_TRY(hipEventCreate(&b.ev1));
-    HIP_TRY(hipEventRecord(b.ev0, st));
-    const int64_t kItersPerLaunch = tabled ? table_steps : (int64_t)1 << 16;   // chains are independent: launches only bound a kernel's run time (and the table)
-    for (int64_t it0 = 0, it1 = 0; it0 < c->niter; it0 = it1) {
-        it1 = std::min<int64_t>(c->niter, it0 + kItersPerLaunch);
-        if (sh.on) {                                    // a tuning boundary always ends a launch; L is replaced before iteration b_r runs
-            if (sh.boundary(it0)) {
-                if (ND == 0 && !tabled) HIP_TRY(transpose(b.xt, b.pos, false));     // (the covariance reads the states chain-major)
-                KMC_TRY(sh.tune(b.pos, nc, st));
-            }
-            it1 = sh.next_boundary(it0, it1);
-        }
-        MetropolisArgs a{};
-        a.pos = b.pos; a.logp = b.logp; a.naccept = b.naccept;
-        a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq;
-        a.step = (sh.on && !tabled) ? b.chol : b.step; a.xt = b.xt; a.yt = b.yt; a.st1 = b.st1; a.st2 = b.st2;
-        a.nchains = nc;
-        a.it0 = it0; a.it1 = it1;
-        a.nburnin = c->nburnin; a.nthin = c->nthin; a.nsamples = nsamples;
-        const int64_t npos = it0 - c->nburnin;          // steps with n > 0 taken before it0
-        a.cnt0 = npos > 0 ? npos % c->nthin : 0;
-        a.slot0 = npos > 0 ? npos / c->nthin : 0;
-        a.ndim = (int32_t)nd;
-        a.seed_lo = (uint32_t)c->seed; a.seed_hi = (uint32_t)(c->seed >> 32);
-        a.dp = dp;
-        a.blob = b.blob; a.chain_blob = b.chain_blob;
-        if (tabled) {
-            const int64_t nit = a.it1 - a.it0;
-            MetroDrawArgs da{};
-            da.out = b.draws; da.nchains = nc; da.it0 = it0; da.nsteps = (int32_t)nit; da.ndim = (int32_t)nd;
-            da.seed_lo = a.seed_lo; da.seed_hi = a.seed_hi;
-            hipLaunchKernelGGL(metro_draw_fill, dim3((unsigned)((nit * nc + 255) / 256)), dim3(256), 0, st, da);
-            if (sh.on) {                                 // the normals of the table become L z
-                HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(metro_draw_shape, dim3((unsigned)((nit * nc + 255) / 256)), dim3(256), 0, st, MetroDrawMvArgs{da, b.chol});
-            }
-            HIP_TRY(hipGetLastError());
-            if (utfn) {
-                MetropolisTabledArgs ta{};
-                ta.a = a; ta.draws = b.draws; ta.nsteps = (int32_t)nit;
-                HIP_TRY(launch_module(utfn, (unsigned)((nc + 63) / 64), 128u, st, ta, 2u * kMetroTileBytes));
-            } else {
-                hipLaunchKernelGGL(tfn, dim3((unsigned)((nc + 63) / 64)), dim3(128), 2 * kMetroTileBytes, st, a, (const double*)b.draws, (int)nit);
-                HIP_TRY(hipGetLastError());
-            }
-        } else if (ufn) HIP_TRY(launch_module(ufn, grid, 256u, st, a));
-        else {
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(256), 0, st, a);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    HIP_TRY(hipEventRecord(b.ev1, st));
-    if (ND == 0 && !tabled) {
-        HIP_TRY(transpose(b.xt, b.pos, false));
-        if (want_mom) { HIP_TRY(transpose(b.st1, b.csum, false)); HIP_TRY(transpose(b.st2, b.csumsq, false)); }
-    }
-    HIP_TRY(hipEventSynchronize(b.ev1));
-    HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
-    out->device_ms = (double)ms;
-    sh.report(out);
-    write_chol_out(c, sh, out);
-
-    if (c->flags & KMC_CHAIN_BY_WALKER) {       // thetas[chain][sample], as the reference returns them (:113, :128)
-        if (out->chain && b.chain) KMC_TRY(download_by_walker(b.chain, false, nc, nd, nd, nsamples, out->chain, st));
-        if (out->chain_logp && b.chain_logp) KMC_TRY(download_by_walker(b.chain_logp, false, nc, 1, 1, nsamples, out->chain_logp, st));
-    } else {
-        if (out->chain && b.chain) HIP_TRY(copy_sync(out->chain, b.chain, (size_t)nsamples * rows, hipMemcpyDeviceToHost, st));
-        if (out->chain_logp && b.chain_logp)
-            HIP_TRY(copy_sync(out->chain_logp, b.chain_logp, (size_t)nsamples * (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if (out->blobs && b.chain_blob) {            // blobs[chain][sample] (KMC_CHAIN_BY_WALKER) or [sample][chain], nblob doubles each (:117)
-        if (c->flags & KMC_CHAIN_BY_WALKER) KMC_TRY(download_by_walker(b.chain_blob, false, nc, nblob, nblob, nsamples, out->blobs, st));
-        else HIP_TRY(copy_sync(out->blobs, b.chain_blob, (size_t)nsamples * (size_t)nc * (size_t)nblob * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    if (out->final_blob && b.blob) HIP_TRY(copy_sync(out->final_blob, b.blob, (size_t)nc * (size_t)nblob * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->final_pos) HIP_TRY(copy_sync(out->final_pos, b.pos, rows, hipMemcpyDeviceToHost, st));
-    if (out->final_logp) HIP_TRY(copy_sync(out->final_logp, b.logp, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->chain_sum && b.csum) HIP_TRY(copy_sync(out->chain_sum, b.csum, rows, hipMemcpyDeviceToHost, st));
-    if (out->chain_sumsq && b.csumsq) HIP_TRY(copy_sync(out->chain_sumsq, b.csumsq, rows, hipMemcpyDeviceToHost, st));
-    if (out->naccept || out->accept_ratio) {
-        std::vector<uint32_t> na((size_t)nc);
-        HIP_TRY(copy_sync(na.data(), b.naccept, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        const double denom = (double)(c->niter - c->nburnin);                                   // :127 (0/0 as in the reference)
-        for (int64_t i = 0; i < nc; ++i) {
-            if (out->naccept) out->naccept[i] = (int64_t)na[(size_t)i];
-            if (out->accept_ratio) out->accept_ratio[i] = (double)na[(size_t)i] / denom;
-        }
-    }
-    return KMC_OK;
+    MetroRun R;
+    KMC_TRY(metropolis_density_params(c, &R.dp));
+    KMC_TRY(metropolis_setup(c, theta0, out, &R));
+    if (c->density == KMC_HOST_DENSITY || c->host_propose) KMC_TRY(metropolis_host_route(R, theta0));
+    else KMC_TRY(metropolis_device_route(R));
+    return metropolis_read_out(R, out);
 }
-
 
 KMC_EXPORT kmc_status kmc_cholesky_lower(const double* a, int n, double* L, int* bad)
 {
