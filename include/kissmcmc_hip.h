@@ -1264,6 +1264,14 @@ kmc_status  kmc_debug_rows_compact(const double* src_host, int64_t rows, int64_t
 /* 1 when the library holds the phase-specialised (credit) instance of the lane-striped stretch kernel (double rows of exact size, one GPU)
  * for a menu density in the geometry L lanes x K chunks, iter walkers per group; else 0.  Needs no GPU. */
 int         kmc_debug_phase_spec(int density, int L, int K, int iter);
+/* Waves per workgroup of the workgroup-shared-draws instance of that kernel (burn-in replays of the updated-graph launch mode: one wave draws for
+ * the whole workgroup) for a menu density in that geometry; 0 where the library holds none.  Needs no GPU. */
+int         kmc_debug_shared_draws(int density, int L, int K, int iter);
+/* The kernel variant behind a replay of n generations from generation g0 on, for a menu-density sampler of nwalkers x ndim (double rows, one GPU,
+ * stretch move) on the two-launch route in the updated-graph launch mode: 0 the generic kernel, 1 the phase-specialised (credit) instance, 2 the
+ * workgroup-shared-draws instance of burn-in.  moments / chain != 0: the sampler credits streaming moments / stores a chain.  Follows KMC_PLAN and
+ * KMC_DEBUG (spec=0, share=0) as a sampler does.  Needs no GPU. */
+int         kmc_debug_replay_variant(int density, int64_t nwalkers, int64_t ndim, int64_t nburnin, int64_t g0, int64_t n, int moments, int chain);
 
 #ifdef __cplusplus
 }

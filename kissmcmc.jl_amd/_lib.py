@@ -53,7 +53,7 @@ SYMBOLS = [
     "kmc_sampler_get_walker_ids", "kmc_sampler_set_walker_ids", "kmc_sampler_set_chain_host", "kmc_rccl_unique_id", "kmc_sampler_rccl_init",
     "kmc_sampler_rccl_capture", "kmc_sampler_rccl_set_capture", "kmc_rccl_version", "kmc_device_free_bytes",
     "kmc_sampler_launch_mode", "kmc_updated_budget", "kmc_set_updated_budget_mb", "kmc_debug_accept_terms",
-    "kmc_debug_chain_by_walker", "kmc_debug_rows_compact", "kmc_debug_phase_spec",
+    "kmc_debug_chain_by_walker", "kmc_debug_rows_compact", "kmc_debug_phase_spec", "kmc_debug_shared_draws", "kmc_debug_replay_variant",
     "kmc_user_density_create_body_blob", "kmc_user_density_nblob", "kmc_logpdf_blob_eval_host", "kmc_sampler_get_blobs",
     "kmc_device_cache_release", "kmc_user_density_is_separable", "kmc_host_prefault", "kmc_data_density_create",
     "kmc_sampler_get_rung_state", "kmc_sampler_set_rung_state", "kmc_sampler_get_swaps",
@@ -370,6 +370,10 @@ def lib() -> C.CDLL:
     L.kmc_debug_rows_compact.argtypes = [dp, C.c_int64, C.c_int64, C.c_int64, dp, C.c_int64, C.c_int]
     L.kmc_debug_phase_spec.restype = C.c_int
     L.kmc_debug_phase_spec.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.kmc_debug_shared_draws.restype = C.c_int
+    L.kmc_debug_shared_draws.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.kmc_debug_replay_variant.restype = C.c_int
+    L.kmc_debug_replay_variant.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int]
     # layout drift between this mirror and the library fails here, at load, not inside the first real call
     for fn, T in ((L.kmc_sizeof_config, Config), (L.kmc_sizeof_metropolis_config, MetropolisConfig),
                   (L.kmc_sizeof_outputs, Outputs), (L.kmc_sizeof_metropolis_outputs, MetropolisOutputs)):

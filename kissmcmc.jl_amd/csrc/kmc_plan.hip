@@ -55,6 +55,16 @@ HalfStepFn lookup_spec(int density, int L, int K, int iter)
     return with_density(density, HalfStepFn(nullptr), [&](auto d) { return spec_part<decltype(d)>(L, K, iter); });
 }
 
+// ... and its workgroup-shared-draws instance for burn-in (kmc_tables.hpp: share_part)
+HalfStepFn lookup_share(int density, int L, int K, int iter, int* share)
+{
+    *share = 0;
+    return with_density(density, HalfStepFn(nullptr), [&](auto d) -> HalfStepFn {
+        if constexpr (std::is_same<decltype(d), MvNormal2>::value) return nullptr;      // (two-dimensional rows: one lane per walker, nothing to share -- no unit)
+        else return share_part<decltype(d)>(L, K, iter, share);
+    });
+}
+
 LogpdfFn logpdf_fn(int density)
 {
     return with_density(density, LogpdfFn(nullptr), [](auto d) { return logpdf_lookup<decltype(d)>(); });
@@ -200,7 +210,10 @@ Plan make_plan(const kmc_config& c, int64_t n_active)
     if (!force_generic && L > 0 && 2 * L * K >= c.ndim && vec != nullptr) {
         p.fn = vec; p.vec = true; p.L = L; p.K = K; p.ITER = iter;
         // the stretch move on one GPU, double rows of exact size, one or two walkers per group: PART 0's kernel has a phase-specialised instance
-        if (!tempered(c) && !de && !(c.flags & KMC_P2P) && !ragged && !f32 && iter <= 2) p.fn_credit = lookup_spec(c.density, L, K, iter);
+        if (!tempered(c) && !de && !(c.flags & KMC_P2P) && !ragged && !f32 && iter <= 2) {
+            p.fn_credit = lookup_spec(c.density, L, K, iter);
+            p.fn_share_burnin = lookup_share(c.density, L, K, iter, &p.share_burnin);
+        }
     } else {
         p.fn = gen; p.vec = false; p.L = 1; p.K = 1; p.ITER = 1;
     }
@@ -260,4 +273,11 @@ kmc_status kmc_host::digest_params(const kmc_config& c, DensityParams* dp)
 KMC_EXPORT int kmc_debug_phase_spec(int density, int L, int K, int iter)
 {
     return kmc_host::lookup_spec(density, L, K, iter) != nullptr ? 1 : 0;
+}
+
+// waves per workgroup of the shared-draws instance (burn-in replays) for this geometry, 0: none
+KMC_EXPORT int kmc_debug_shared_draws(int density, int L, int K, int iter)
+{
+    int share = 0;
+    return kmc_host::lookup_share(density, L, K, iter, &share) != nullptr ? share : 0;
 }

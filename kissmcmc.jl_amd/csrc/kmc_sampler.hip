@@ -1137,6 +1137,9 @@ KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int6
             const char* why = nullptr;
             if (spec_variant_possible(s, kVarCredit, &why)) o << "; phase-specialised kernel instance in counted replays";
             else o << "; generic kernel in every phase (" << why << ")";
+            // ... and whether one draw pass serves a whole workgroup in burn-in replays (kmc_shared_draws.hpp)
+            if (spec_variant_possible(s, kVarShareBurnin, &why)) o << "; workgroup-shared draws in burn-in replays (" << variant_share(s, kVarShareBurnin) << " waves per workgroup)";
+            else o << "; no workgroup-shared draws (" << why << ")";
         }
     } else
         o << "multi-launch (exact): " << (s->user && s->uk.staged ? "half_step_staged (one walker per lane, rows staged through LDS)" : "half_step_generic (one walker per lane)")
@@ -1244,6 +1247,20 @@ KMC_EXPORT void* kmc_sampler_device_ptr(kmc_sampler* s, int which)
     }
 }
 
+// (tests; touches no device) The kernel variant -- kVarGeneric, kVarCredit or kVarShareBurnin -- behind a replay of n generations from g0 on, for a menu-density
+// sampler of this shape on the two-launch route in the updated-graph mode: the plan, the launch geometry and spec_of_chunk as a real sampler has them.
+KMC_EXPORT int kmc_debug_replay_variant(int density, int64_t nwalkers, int64_t ndim, int64_t nburnin, int64_t g0, int64_t n, int moments, int chain)
+{
+    static double some = 0.0;
+    kmc_sampler s;
+    s.cfg.density = density; s.cfg.nwalkers = nwalkers; s.cfg.ndim = ndim; s.cfg.nburnin = nburnin; s.cfg.shard_count = 1;
+    s.h = s.h_loc = nwalkers / 2;
+    s.plan = make_plan(s.cfg, s.h_loc);
+    setup_launch_geometry(&s);
+    s.d_msum = moments ? &some : nullptr;
+    s.d_chain = chain ? &some : nullptr;
+    return spec_of_chunk(&s, g0, n);
+}
 
 KMC_EXPORT int kmc_sizeof_config(void) { return (int)sizeof(kmc_config); }
 KMC_EXPORT int kmc_sizeof_metropolis_config(void) { return (int)sizeof(kmc_metropolis_config); }

@@ -17,13 +17,16 @@ static_assert(1024 % kmc::kDrawBatch == 0, "the draw table holds whole batches")
 constexpr int64_t kDrawTableGens = 1024;   // resident mode with a draw table: generations per launch (table = 32 B x nwalkers x this)
 constexpr int64_t kGraphChunk = 64;   // generations per hipGraph replay (128 kernel nodes + 1)
 constexpr int kUExec = 6;             // executables of the "updated graph" launch mode (kmc_sampler::uexec), per kernel variant
-enum : int { kVarGeneric = 0, kVarCredit = 1, kUVariants = 2 };     // the kernel behind an updated graph's nodes (kmc_kernels.hpp: Spec)
+// the kernel behind an updated graph's nodes (kmc_kernels.hpp: Spec; kmc_shared_draws.hpp: the workgroup-shared-draws instance of burn-in)
+enum : int { kVarGeneric = 0, kVarCredit = 1, kVarShareBurnin = 2, kUVariants = 3 };
 constexpr size_t kGuardBytes = 4096;  // KMC_DEBUG=poison: guard band behind every device allocation of a sampler
 constexpr int kHostPieces = 8;        // KMC_HOST_DENSITY: most pieces a half-step's proposals travel to the host in
 
 struct Plan {
     kmc::HalfStepFn fn = nullptr;
     kmc::HalfStepFn fn_credit = nullptr;      // the phase-specialised instance of fn (kmc_kernels.hpp: Spec::Credit), nullptr where there is none
+    kmc::HalfStepFn fn_share_burnin = nullptr;     // the workgroup-shared-draws instance of fn for burn-in (kmc_shared_draws.hpp), nullptr where there is none
+    int share_burnin = 0;                     //   ... and its waves per workgroup
     bool vec = false;
     bool ragged = false;
     int L = 1, K = 1, ITER = 1;
@@ -298,6 +301,7 @@ kmc::GenerationFront generation_front_of(const kmc::GenerationArgs& a, int tpb);
 // kmc_updated.hip
 bool updated_graph_possible(const kmc_sampler* s);
 bool spec_variant_possible(const kmc_sampler* s, int variant, const char** why_not = nullptr);   // may a replay of this sampler ever run that kernel variant?
+int variant_share(const kmc_sampler* s, int variant);    // waves per workgroup of the shared-draws variant (0: the variant launches in the sampler's own grid and block)
 int spec_of_chunk(const kmc_sampler* s, int64_t g0, int64_t n);                                  // the variant for generations [g0, g0 + n)
 kmc_status ensure_updated_graph(kmc_sampler* s);         // the template graph and its executables (no-op when they exist)
 kmc_status launch_updated_graph(kmc_sampler* s, bool* launched);   // one replay of s->uchunk generations from s->generation on

@@ -12,6 +12,7 @@
 //   kmc_inst_<density>_temper_snooker.hip  temper_part of the snooker move and the mixtures (exact and ragged double rows, one GPU, like PART 3 .. 5)
 //   kmc_inst_host_temper*.hip    temper_part of the host-evaluated density: likelihood tempering of a data density (generic kernels only)
 //   kmc_inst_<density>_spec.hip  spec_part: the phase-specialised instance (Spec::Credit) of PART 0's vector kernels, planner geometries with ITER <= 2
+//   kmc_inst_<density>_share.hip share_part: the workgroup-shared-draws instance for burn-in (kmc_shared_draws.hpp) of the geometry it serves
 //   kmc_inst_<density>_lds.hip   the LDS-resident (islands, resident mode), one-launch-per-generation and many-chain Metropolis kernels
 // Which part serves a configuration is decided on the host (kmc_plan.hip: lookup, lookup_move).
 #pragma once
@@ -37,6 +38,9 @@ template <class D, int PART> void density_part(int L, int K, int iter, bool ragg
 template <class D, Move M> void temper_part(int L, int K, int iter, bool ragged, HalfStepFn* vec, HalfStepFn* gen);
 // (the credit instance of half_step_vec<D, L, K, iter, false, false, double>, nullptr where there is none)
 template <class D> HalfStepFn spec_part(int L, int K, int iter);
+// (the workgroup-shared-draws instance of that kernel for burn-in replays and its waves per workgroup, nullptr and 0 where there is none; defined in
+//  kmc_shared_draws.hpp)
+template <class D> HalfStepFn share_part(int L, int K, int iter, int* share);
 template <class D> LogpdfFn logpdf_lookup();
 template <class D> InitBallFn init_ball_lookup();
 template <class D> IslandFn island_lookup(int S, int K, bool ragged);

@@ -36,7 +36,22 @@ struct ParamPack {
 // the kernel behind the nodes of a variant's graph (half-step kernels of a menu density; everything else has the generic variant only)
 HalfStepFn variant_fn(const kmc_sampler* s, int variant)
 {
-    return variant == kVarCredit ? s->plan.fn_credit : s->plan.fn;
+    return variant == kVarCredit ? s->plan.fn_credit : variant == kVarShareBurnin ? s->plan.fn_share_burnin : s->plan.fn;
+}
+}  // namespace
+
+// The shared-draws variant launches SHARE waves per workgroup over the same waves (the global wave index keeps its meaning): its own grid and block.
+int variant_share(const kmc_sampler* s, int variant)
+{
+    return variant == kVarShareBurnin ? s->plan.share_burnin : 0;
+}
+
+namespace {
+// walkers per workgroup of a variant's launch
+int64_t variant_walkers_per_wg(const kmc_sampler* s, int variant)
+{
+    const int share = variant_share(s, variant);
+    return (int64_t)(share > 0 ? share : s->tpb / 64) * (64 / s->plan.L) * s->plan.ITER;
 }
 
 hipKernelNodeParams node_params(const kmc_sampler* s, int variant, ParamPack* pk)
@@ -53,6 +68,10 @@ hipKernelNodeParams node_params(const kmc_sampler* s, int variant, ParamPack* pk
         np.func = s->user ? reinterpret_cast<void*>(s->uk.vec) : reinterpret_cast<void*>(variant_fn(s, variant));
         np.gridDim = dim3((unsigned)s->grid);
         np.blockDim = dim3((unsigned)s->tpb);
+        if (const int share = variant_share(s, variant); share > 0) {       // (spec_variant_possible: h_loc is a whole number of its workgroups)
+            np.gridDim = dim3((unsigned)(s->h_loc / variant_walkers_per_wg(s, variant)));
+            np.blockDim = dim3(64u * (unsigned)share);
+        }
         np.sharedMemBytes = s->user ? s->vec_lds : 0u;
     }
     np.kernelParams = pk->ptrs;
@@ -98,28 +117,32 @@ void drop_updated_graph(kmc_sampler* s)
 
 // The phase-specialised instance (kmc_kernels.hpp: Spec::Credit) serves the two-launch vector route of a menu density whose grid is exactly full, with
 // streaming moments and nothing stored per sample.  KMC_DEBUG=spec=0: the generic kernel everywhere (A/B runs, tests).
+// The workgroup-shared-draws instance (kmc_shared_draws.hpp) serves burn-in replays of the same route where the grid is exactly full in ITS workgroups,
+// whatever the sampler stores or credits later (a burn-in generation stores and credits nothing).  KMC_DEBUG=share=0: the generic kernel in burn-in, as
+// before it.
 bool spec_variant_possible(const kmc_sampler* s, int variant, const char** why_not)
 {
     const char* why = nullptr;
     std::string v;
-    const int64_t per_wg = (int64_t)(s->tpb / 64) * (64 / s->plan.L) * s->plan.ITER;
+    const bool credits = variant == kVarCredit;
     if (variant == kVarGeneric) return true;
     if (debug_opt("spec", &v) && v == "0") why = "KMC_DEBUG=spec=0";
+    else if (variant == kVarShareBurnin && debug_opt("share", &v) && v == "0") why = "KMC_DEBUG=share=0";
     else if (s->user || s->fused || s->host_eval || !s->plan.vec) why = "not the two-launch vector route of a menu density";
     else if (variant_fn(s, variant) == nullptr) why = "no instance for this move, row type or geometry";
-    else if (s->h_loc != (int64_t)s->grid * per_wg) why = "grid not full";
-    else if (variant == kVarCredit && !s->d_msum) why = "moments off";
-    else if (variant == kVarCredit && (s->d_chain || s->d_chain_logp || s->d_chain_blob)) why = "chain on";
+    else if (s->h_loc != (int64_t)s->grid * variant_walkers_per_wg(s, kVarGeneric) || s->h_loc % variant_walkers_per_wg(s, variant) != 0) why = "grid not full";
+    else if (credits && !s->d_msum) why = "moments off";
+    else if (credits && (s->d_chain || s->d_chain_logp || s->d_chain_blob)) why = "chain on";
     if (why_not) *why_not = why;
     return why == nullptr;
 }
 
-// A replay runs the specialised variant only when every generation of it qualifies: all of them counted.  (Burn-in replays and the one that
-// straddles nburnin run the generic kernel.)
+// A replay runs a specialised variant only when every generation of it qualifies: all of them counted, or all of them burn-in.  (The replay that
+// straddles nburnin runs the generic kernel, and so do burn-in replays without the shared-draws instance.)
 int spec_of_chunk(const kmc_sampler* s, int64_t g0, int64_t n)
 {
-    (void)n;
     if (g0 >= s->cfg.nburnin) return spec_variant_possible(s, kVarCredit) ? kVarCredit : kVarGeneric;
+    if (g0 + n <= s->cfg.nburnin && spec_variant_possible(s, kVarShareBurnin)) return kVarShareBurnin;
     return kVarGeneric;
 }
 

@@ -13,6 +13,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LIGHT = os.environ.get("KMC_PROBE_LIGHT") == "1"        # -DKMC_PROBE=2: entry and last-store stamps only, nothing pinned in between (the records' duration source)
+BURNIN = os.environ.get("KMC_PROBE_PHASE") == "burnin"  # every generation of the run is burn-in (default: every generation counted)
 VAR = os.path.join(ROOT, "kissmcmc.jl_amd", "libkmc_var_probe2.so" if LIGHT else "libkmc_var_probe.so")
 os.environ["KMC_LIB_PATH"] = VAR
 if not os.path.exists(VAR):
@@ -37,7 +38,7 @@ def main():
     th = np.random.default_rng(0).standard_normal((nw, nd)) * (0.1 if name == "C3" else 1.0)
     L = _lib.lib()
     for mom in (True, False):
-        s = kmc.Sampler(pdf, nw, nd, 10 ** 9, 0, 1, 2.0, 7, moments=mom)
+        s = kmc.Sampler(pdf, nw, nd, 10 ** 9, 10 ** 9 // 2 if BURNIN else 0, 1, 2.0, 7, moments=mom)
         s.set_positions(th)
         s.run(1024)
         s.sync()
@@ -74,8 +75,10 @@ def main():
                                               "period_us_hip_events_probe_build": ms / 1024 * 1e3, "wave_duration_median_us": float(np.median(t[0, :, 7] - t[0, :, 0]))}))
             s.close()
             continue
-        spec = name == 'C2' and "phase-specialised kernel instance in counted replays" in how      # (counted replays ran the credit instance: its stamps are its own unit's)
-        rc = (L.kmc_probe_read_spec if spec else L.kmc_probe_read_rosenbrock if name == 'C3' else L.kmc_probe_read_var if name[0] == 'R' else L.kmc_probe_read)(buf.ctypes.data_as(ctypes.c_void_p))
+        spec = name == 'C2' and not BURNIN and "phase-specialised kernel instance in counted replays" in how      # (counted replays ran the credit instance: its stamps are its own unit's)
+        # ... and burn-in replays the shared-draws instance (kmc_shared_draws.hpp), a unit of its own as well
+        share = name == 'C2' and BURNIN and "workgroup-shared draws in burn-in replays" in how
+        rc = (L.kmc_probe_read_share if share else L.kmc_probe_read_spec if spec else L.kmc_probe_read_rosenbrock if name == 'C3' else L.kmc_probe_read_var if name[0] == 'R' else L.kmc_probe_read)(buf.ctypes.data_as(ctypes.c_void_p))
         assert rc == 0
         print(f"== {name} moments={int(mom)} KMC_LAUNCH={os.environ.get('KMC_LAUNCH', 'auto')}: {how}  {ms / 2048 * 1e3:.2f} us per half-step launch")
         nwave = int((buf[0, :, 0] != 0).sum())
