@@ -1,4 +1,4 @@
-// kmc_host.hpp -- what the host-side translation units of the library share (kmc_sampler.hip and its siblings: samplers;
+// kmc_host.hpp -- what the host-side translation units of the library share (kmc_sampler.hip and its siblings, kmc_validate.hip among them: samplers;
 // kmc_metropolis_api.hip: many-chain Metropolis; kmc_acorr.hip: autocorrelation diagnostics).  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,7 +23,7 @@
 
 namespace kmc_host {
 
-// message of the last failure on the calling thread (kmc_last_error)
+// message of the last failure on the calling thread (kmc_last_error; both in kmc_sampler.hip)
 extern thread_local std::string g_err;
 inline kmc_status fail(kmc_status st, const std::string& msg)
 {

@@ -1,6 +1,6 @@
-// kmc_sampler.hip -- the sampler's lifecycle behind the C ABI (include/kissmcmc_hip.h): validation of a configuration
-// (the reference's asserts, src/samplers.jl:200-205), creation / destruction of the device state of the `emcee` front-end
-// (src/samplers.jl:188-216), and the description of how a sampler executes.  Kernel tables and the launch plan per ndim are kmc_plan.hip.
+// kmc_sampler.hip -- the sampler's lifecycle behind the C ABI (include/kissmcmc_hip.h): creation / destruction of the device state of
+// the `emcee` front-end (src/samplers.jl:188-216) and the small getters.  Which configurations it takes is kmc_validate.hip; the
+// description of how a sampler executes is kmc_describe.hip.  Kernel tables and the launch plan per ndim are kmc_plan.hip.
 // kmc_sampler_create runs named steps: init_shape; the route (setup_islands, setup_user_density / setup_menu_resident, setup_generation,
 // setup_launch_geometry); the device state (alloc_*).  Every execution route of the library is decided there and nowhere else.
 // The generation loop (src/samplers.jl:232-293) is kmc_launch.hip; state in and out is kmc_state.hip; copies and the chain
@@ -11,7 +11,6 @@
 #include <cstdlib>
 #include <mutex>
 #include <random>
-#include <sstream>
 
 #include "kmc_sampler.hpp"
 
@@ -30,192 +29,6 @@ KMC_EXPORT int kmc_device_count(void)
 }
 
 KMC_EXPORT const char* kmc_last_error(void) { return g_err.c_str(); }
-
-KMC_EXPORT const char* kmc_status_string(kmc_status st)
-{
-    switch (st) {
-    case KMC_OK: return "ok";
-    case KMC_ERR_A_SCALE: return "a_scale must be > 1";
-    case KMC_ERR_ODD_WALKERS: return "Use an even number of walkers.";
-    case KMC_ERR_TOO_FEW_WALKERS: return "Use more walkers: at least DOF+2, but better many more.";
-    case KMC_ERR_BAD_ARG: return "bad argument";
-    case KMC_ERR_NONFINITE_LOGP: return "initial walker with non-finite log-pdf";
-    case KMC_ERR_HIP: return "HIP runtime error";
-    case KMC_ERR_OOM: return "out of device memory";
-    case KMC_ERR_NO_DEVICE: return "no HIP device";
-    case KMC_ERR_UNSUPPORTED: return "unsupported configuration";
-    }
-    return "unknown status";
-}
-
-namespace {
-// dynamic LDS a workgroup of the resident and island kernels may ask for (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
-constexpr size_t kResidentLdsMax = 156 * 1024;
-
-// The own-stream moves and the tempered ladder run the two-launch kernels on one GPU with double rows: what a configuration has that
-// they cannot take (nullptr: nothing), in the words of their refusals.  P: the shard count.
-const char* not_on_one_gpu_with_double_rows(const kmc_config* c, int P)
-{
-    if (c->flags & KMC_ISLANDS) return "KMC_ISLANDS";
-    if (c->flags & KMC_P2P) return "KMC_P2P";
-    if (P > 1) return "shard_count > 1";
-    if (c->deal_count > 0) return "dealt sub-ensembles (deal_count > 0)";
-    if (c->dtype == KMC_F32) return "KMC_F32";
-    if (c->flags & KMC_STORE_BLOBS) return "KMC_STORE_BLOBS";
-    if (c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->nblob > 0) return "a density with blobs";
-    return nullptr;
-}
-}  // namespace
-
-// src/samplers.jl:200-205
-KMC_EXPORT kmc_status kmc_validate(const kmc_config* c)
-{
-    if (!c) return fail(KMC_ERR_BAD_ARG, "null config");
-    if (c->nwalkers <= 0 || c->ndim <= 0 || c->nthin <= 0 || c->ngenerations < 0 || c->nburnin < 0)
-        return fail(KMC_ERR_BAD_ARG, "nwalkers, ndim, nthin must be > 0 and ngenerations, nburnin >= 0");
-    if (!(c->a_scale > 1.0)) return fail(KMC_ERR_A_SCALE, kmc_status_string(KMC_ERR_A_SCALE));
-    if (c->nwalkers % 2 != 0) return fail(KMC_ERR_ODD_WALKERS, kmc_status_string(KMC_ERR_ODD_WALKERS));
-    if (c->nwalkers < c->ndim + 2) return fail(KMC_ERR_TOO_FEW_WALKERS, kmc_status_string(KMC_ERR_TOO_FEW_WALKERS));
-    if (c->nwalkers >= (int64_t)1 << 31 || c->ndim >= (int64_t)1 << 24)
-        return fail(KMC_ERR_UNSUPPORTED, "ensemble too large");
-    if (c->ngenerations >= (int64_t)1 << 31) return fail(KMC_ERR_UNSUPPORTED, "at most 2^31 - 1 generations (the step index is 32 bits)");
-    if (c->density == KMC_USER_DENSITY && !c->user_density) return fail(KMC_ERR_BAD_ARG, "KMC_USER_DENSITY needs kmc_config.user_density");
-    if (c->density == KMC_USER_DENSITY && static_cast<const kmc_user_density*>(c->user_density)->is_data)
-        return fail(KMC_ERR_BAD_ARG, "this handle was made by kmc_data_density_create: use density = KMC_DATA_DENSITY");
-    if (c->density == KMC_DATA_DENSITY) {
-        const kmc_user_density* ud = static_cast<const kmc_user_density*>(c->user_density);
-        if (!ud || !ud->is_data) return fail(KMC_ERR_BAD_ARG, "KMC_DATA_DENSITY needs kmc_config.user_density made by kmc_data_density_create");
-        if (c->dtype != KMC_F64) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: double rows only (no KMC_F32)");
-        if (c->flags & KMC_ISLANDS) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: no island mode (KMC_ISLANDS)");
-        if (c->flags & KMC_P2P) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: one GPU, no KMC_P2P");
-        if (c->shard_count > 1) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: one GPU, no sharding (shard_count must be 1)");
-        if (c->deal_count > 0) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: no dealt sub-ensembles (deal_count must be 0)");
-        if (c->flags & KMC_STORE_BLOBS) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: no blobs (KMC_STORE_BLOBS)");
-        if (c->ndim > kDataMaxDim) return fail(KMC_ERR_UNSUPPORTED, "KMC_DATA_DENSITY: ndim must be <= " + std::to_string(kDataMaxDim));
-    }
-    if (c->density == KMC_HOST_DENSITY) {
-        if (!c->host_logpdf) return fail(KMC_ERR_BAD_ARG, "KMC_HOST_DENSITY needs kmc_config.host_logpdf");
-        if ((c->flags & (KMC_P2P | KMC_ISLANDS)) || c->shard_count > 1)
-            return fail(KMC_ERR_UNSUPPORTED, "KMC_HOST_DENSITY runs on one GPU, without KMC_P2P / KMC_ISLANDS / sharding");
-    }
-    if (c->dtype != KMC_F64 && c->dtype != KMC_F32) return fail(KMC_ERR_UNSUPPORTED, "dtype must be KMC_F64 or KMC_F32");
-    if (c->dtype == KMC_F32) {
-        if ((c->flags & (KMC_P2P | KMC_ISLANDS)) || c->shard_count > 1)
-            return fail(KMC_ERR_UNSUPPORTED, "KMC_F32 rows: one GPU, without KMC_P2P / KMC_ISLANDS / sharding");
-        if (c->density == KMC_HOST_DENSITY)
-            return fail(KMC_ERR_UNSUPPORTED, "KMC_F32 rows: densities evaluated on the device only (built-in or runtime-compiled)");
-    }
-    if (c->host_accepted && c->density != KMC_HOST_DENSITY) return fail(KMC_ERR_BAD_ARG, "kmc_config.host_accepted needs KMC_HOST_DENSITY");
-    KMC_TRY(check_ndim(c->density, c->ndim));
-    const int P = c->shard_count <= 0 ? 1 : c->shard_count;
-    if (c->shard_rank < 0 || c->shard_rank >= P) return fail(KMC_ERR_BAD_ARG, "shard_rank out of range");
-    if ((c->nwalkers / 2) % P != 0) return fail(KMC_ERR_BAD_ARG, "nwalkers/2 must be divisible by shard_count");
-    if ((c->flags & KMC_P2P) && P > 8) return fail(KMC_ERR_UNSUPPORTED, "KMC_P2P supports at most 8 shards (one node)");
-    if (c->flags & ((1u << 8) | (1u << 10)))                 // (KMC_P2P_FOLD_SIGNAL, KMC_P2P_LAZY of rounds 1-4)
-        return fail(KMC_ERR_UNSUPPORTED, "the lazy-pull and folded-signal exchange variants were removed in round 5 (they read peer-written memory through the local L2 and could "
-                                         "not move the fabric bound): the exchanges are the pull of drawn rows and the push of accepted rows (KMC_P2P_PUSH), both read with "
-                                         "system-scope loads");
-    if ((c->flags & KMC_P2P_PUSH) && !(c->flags & KMC_P2P)) return fail(KMC_ERR_BAD_ARG, "KMC_P2P_PUSH needs KMC_P2P");
-    if (c->flags & KMC_ISLANDS) {
-        const int64_t S = c->island_size > 0 ? c->island_size : kIslandSizeDefault;
-        if ((S != 64 && S != 128 && S != 256) || c->nwalkers % S != 0 || c->ndim > 32 || c->ndim + 2 > S || P != 1 ||
-            (c->flags & (KMC_P2P | KMC_STORE_CHAIN | KMC_STORE_LOGP)) || c->island_gens < 0)
-            return fail(KMC_ERR_UNSUPPORTED, "KMC_ISLANDS needs island_size in {64,128,256} >= ndim+2 dividing nwalkers, ndim <= 32, one shard and no chain storage");
-        if (c->density == KMC_USER_DENSITY && (size_t)S * (size_t)(2 * c->ndim + 9) * sizeof(double) > kResidentLdsMax)
-            return fail(KMC_ERR_UNSUPPORTED, "KMC_ISLANDS with a user density: island_size * (2 ndim + 9) * 8 must stay below 156 KiB");
-    }
-    if (c->flags & KMC_STREAM_CHAIN) {
-        if (!(c->flags & (KMC_STORE_CHAIN | KMC_STORE_LOGP))) return fail(KMC_ERR_BAD_ARG, "KMC_STREAM_CHAIN needs KMC_STORE_CHAIN and / or KMC_STORE_LOGP");
-        if (c->dtype != KMC_F64 || P != 1 || (c->flags & (KMC_P2P | KMC_ISLANDS)))
-            return fail(KMC_ERR_UNSUPPORTED, "KMC_STREAM_CHAIN: KMC_F64, one GPU, without KMC_P2P / KMC_ISLANDS / sharding");
-    }
-    if (c->move != KMC_MOVE_STRETCH && c->move != KMC_MOVE_DE && c->move != KMC_MOVE_SNOOKER && c->move != KMC_MOVE_MIX)
-        return fail(KMC_ERR_BAD_ARG, "kmc_config.move must be KMC_MOVE_STRETCH, KMC_MOVE_DE, KMC_MOVE_SNOOKER or KMC_MOVE_MIX");
-    if (c->move != KMC_MOVE_STRETCH) {
-        const std::string name = move_name(c->move);
-        auto check_de = [&](double gamma0, double sigma) -> kmc_status {
-            if (!std::isfinite(gamma0) || gamma0 < 0.0) return fail(KMC_ERR_BAD_ARG, name + ": de_gamma0 must be finite and >= 0 (0: 2.38 / sqrt(2 ndim))");
-            if (!std::isfinite(sigma) || sigma < 0.0 || sigma >= 1.0) return fail(KMC_ERR_BAD_ARG, name + ": de_sigma must be in [0, 1)");
-            return KMC_OK;
-        };
-        auto check_snooker = [&](double gamma) -> kmc_status {
-            if (!std::isfinite(gamma) || gamma < 0.0) return fail(KMC_ERR_BAD_ARG, name + ": snooker_gamma must be finite and >= 0 (0: 1.7)");
-            if (c->ndim < 2) return fail(KMC_ERR_BAD_ARG, name + ": the snooker move needs ndim >= 2 (it is degenerate in one dimension)");
-            if (c->nwalkers < 6) return fail(KMC_ERR_BAD_ARG, name + ": the snooker move needs nwalkers >= 6 (three distinct partners in a half)");
-            return KMC_OK;
-        };
-        if (c->move == KMC_MOVE_DE) KMC_TRY(check_de(c->de_gamma0, c->de_sigma));
-        if (c->move == KMC_MOVE_SNOOKER) KMC_TRY(check_snooker(c->snooker_gamma));
-        if (c->move == KMC_MOVE_MIX) {
-            if (c->mix_count < 2 || c->mix_count > KMC_MIX_MAX) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: mix_count must be 2 .. 4");
-            for (int i = 0; i < c->mix_count; ++i) {
-                if (c->mix_move[i] == KMC_MOVE_STRETCH)
-                    return fail(KMC_ERR_UNSUPPORTED, "KMC_MOVE_MIX: a stretch member is not supported yet (members are KMC_MOVE_DE and KMC_MOVE_SNOOKER; DESIGN.md section 8)");
-                if (c->mix_move[i] != KMC_MOVE_DE && c->mix_move[i] != KMC_MOVE_SNOOKER) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: a member must be KMC_MOVE_DE or KMC_MOVE_SNOOKER");
-                if (!std::isfinite(c->mix_weight[i]) || !(c->mix_weight[i] > 0.0)) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: weights must be finite and > 0");
-                if (c->mix_move[i] == KMC_MOVE_DE) KMC_TRY(check_de(c->mix_gamma[i], c->mix_sigma[i]));
-                else KMC_TRY(check_snooker(c->mix_gamma[i]));
-            }
-            double sum = 0.0;
-            for (int i = 0; i < c->mix_count; ++i) sum += c->mix_weight[i];
-            if (!std::isfinite(sum)) return fail(KMC_ERR_BAD_ARG, "KMC_MOVE_MIX: the weights' sum must be finite");
-        }
-        if (const char* what = not_on_one_gpu_with_double_rows(c, P)) return fail(KMC_ERR_UNSUPPORTED, name + ": two launches per generation on one GPU with double rows -- not with " + what);
-    }
-    {
-        const int nb = c->density == KMC_USER_DENSITY && c->user_density ? static_cast<const kmc_user_density*>(c->user_density)->nblob : 0;
-        if ((c->flags & KMC_STORE_BLOBS) && nb == 0)
-            return fail(KMC_ERR_BAD_ARG, "KMC_STORE_BLOBS needs a body density with blobs (kmc_user_density_create_body_blob)");
-        if (nb > 0 && (c->dtype != KMC_F64 || P != 1 || c->deal_count > 0 || (c->flags & (KMC_P2P | KMC_ISLANDS | KMC_STREAM_CHAIN))))
-            return fail(KMC_ERR_UNSUPPORTED, "a density with blobs: KMC_F64, one GPU, without KMC_P2P / KMC_ISLANDS / KMC_STREAM_CHAIN / sharding / dealt sub-ensembles");
-    }
-    if (c->ntemps < 0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps must be >= 0 (0 or 1: off)");
-    if (c->swap_every < 0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: swap_every must be >= 0 (0: never)");
-    if (c->temper_mode != KMC_TEMPER_WHOLE && c->temper_mode != KMC_TEMPER_LIKELIHOOD)
-        return fail(KMC_ERR_BAD_ARG, "parallel tempering: temper_mode must be KMC_TEMPER_WHOLE or KMC_TEMPER_LIKELIHOOD");
-    const bool like = c->temper_mode == KMC_TEMPER_LIKELIHOOD;
-    if (like && c->ntemps < 2) return fail(KMC_ERR_BAD_ARG, "parallel tempering: KMC_TEMPER_LIKELIHOOD needs a ladder (ntemps >= 2)");
-    if (c->ntemps >= 2) {
-        if (c->ntemps > KMC_TEMPS_MAX) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps must be 2 .. " + std::to_string(KMC_TEMPS_MAX));
-        if (!c->betas) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must point to ntemps inverse temperatures");
-        if (c->betas[0] != 1.0) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas[0] must be 1");
-        for (int t = 0; t < c->ntemps; ++t) {
-            const bool prior_rung = like && t == c->ntemps - 1 && c->betas[t] == 0.0;      // (the rung that samples the prior closes the thermodynamic integral)
-            if (!std::isfinite(c->betas[t]) || !(c->betas[t] > 0.0 || prior_rung))
-                return fail(KMC_ERR_BAD_ARG, like ? "parallel tempering: betas must be finite and > 0 (KMC_TEMPER_LIKELIHOOD: the last one may be 0)" : "parallel tempering: betas must be finite and > 0");
-            if (t > 0 && !(c->betas[t] < c->betas[t - 1])) return fail(KMC_ERR_BAD_ARG, "parallel tempering: betas must be strictly decreasing");
-        }
-        if ((int64_t)c->ntemps * c->nwalkers >= (int64_t)1 << 31) return fail(KMC_ERR_BAD_ARG, "parallel tempering: ntemps * nwalkers must stay below 2^31");
-        if (like && c->density != KMC_DATA_DENSITY)
-            return fail(KMC_ERR_UNSUPPORTED, "parallel tempering: KMC_TEMPER_LIKELIHOOD needs KMC_DATA_DENSITY (prior + beta * S): nothing says where another density's prior ends");
-        const char* what = c->density == KMC_HOST_DENSITY ? "KMC_HOST_DENSITY"
-                         : (c->density == KMC_DATA_DENSITY && !like) ? "KMC_DATA_DENSITY in the default temper_mode (temper_mode = KMC_TEMPER_LIKELIHOOD, temper=\"likelihood\", tempers its likelihood)"
-                         : not_on_one_gpu_with_double_rows(c, P);
-        if (what) return fail(KMC_ERR_UNSUPPORTED, std::string("parallel tempering (ntemps >= 2): a ladder of ensembles on one GPU with double rows and a device density -- not with ") + what);
-    }
-    if (c->adapt != 0) {
-        if (c->adapt != 1) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt must be 0 or 1");
-        if (c->ntemps < 2) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt needs a ladder (parallel tempering: betas, ntemps)");
-        if (c->ntemps < 3) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: ntemps must be >= 3 (the first and the last rung never move)");
-        if (c->swap_every == 0) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: swap_every must be >= 1 (the ladder adapts to the swap sweeps' acceptance)");
-        if (c->adapt_until < 0 || c->adapt_until > c->nburnin)
-            return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt_until must be 0 .. nburnin (0: nburnin) -- every stored sample comes from the frozen ladder");
-        if (!std::isfinite(c->adapt_lag) || !(c->adapt_lag > 0.0)) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt_lag must be finite and > 0");
-        if (!std::isfinite(c->adapt_time) || !(c->adapt_time > 0.0)) return fail(KMC_ERR_BAD_ARG, "adaptive ladder: adapt_time must be finite and > 0");
-    }
-    if (c->deal_count < 0 || (c->deal_count > 0 && (c->deal_rank < 0 || c->deal_rank >= c->deal_count)))
-        return fail(KMC_ERR_BAD_ARG, "deal_rank / deal_count out of range");
-    if (c->deal_count > 0) {
-        // (a stored chain is by SLOT: which walker a slot held when a sample was taken follows from kmc_deal_perm, distributed.py)
-        if (P != 1 || (c->flags & (KMC_P2P | KMC_ISLANDS | KMC_STREAM_CHAIN)) || c->dtype != KMC_F64 || c->density == KMC_HOST_DENSITY)
-            return fail(KMC_ERR_UNSUPPORTED, "dealt sub-ensembles: KMC_F64, a device density, one shard, no KMC_P2P / KMC_ISLANDS / KMC_STREAM_CHAIN");
-        if (c->nwalkers % c->deal_count != 0)
-            return fail(KMC_ERR_BAD_ARG, "dealt sub-ensembles: nwalkers (this sub-ensemble's size) must be divisible by deal_count");
-        if (c->nwalkers * (int64_t)c->deal_count >= (int64_t)1 << 32) return fail(KMC_ERR_UNSUPPORTED, "dealt sub-ensembles: at most 2^32 - 1 walkers in all");
-    }
-    DensityParams dp;
-    return digest_params(*c, &dp);
-}
 
 KMC_EXPORT double kmc_g_pdf(double z, double a)   // src/samplers.jl:224
 {
@@ -1080,160 +893,6 @@ KMC_EXPORT kmc_status kmc_sampler_bind_positions(kmc_sampler* s, void* pos_dev)
 KMC_EXPORT int64_t kmc_sampler_generation(const kmc_sampler* s) { return s ? s->generation : -1; }
 KMC_EXPORT int64_t kmc_sampler_nsamples(const kmc_sampler* s) { return s ? s->nsamples : -1; }
 KMC_EXPORT int64_t kmc_sampler_launch_count(const kmc_sampler* s) { return s ? s->launches : -1; }
-
-namespace {
-// how kmc_sampler_run issues the launches of the multi-launch kernels (two per generation, or one): kmc_launch.hip
-std::string launch_mode_text(const kmc_sampler* s, const char* what)
-{
-    std::string t = ((s->cfg.flags & KMC_NO_GRAPH) || s->launch_mode == 2) ? std::string(", eager launches (") + what + " among the preloaded kernel parameters)"
-                    : s->launch_mode == 3 ? ", hipGraph replay of " + std::to_string(s->uchunk) + " generations with per-replay parameter updates (" + what + " preloaded)"
-                                          : std::string(", hipGraph replay of 64 generations");
-    if (s->calib_graph_ms > 0.f) {
-        char b[128];
-        std::snprintf(b, sizeof(b), " (measured per 64 generations: table graph %.3f ms, %s %.3f ms)", s->calib_graph_ms, s->launch_mode == 2 ? "eager launches" : "updated graph", s->calib_eager_ms);
-        t += b;
-    }
-    return t;
-}
-}  // namespace
-
-// Human-readable description of how this sampler executes (kernel family, geometry, exchange).
-KMC_EXPORT kmc_status kmc_sampler_describe(const kmc_sampler* s, char* buf, int64_t buflen)
-{
-    if (!s || !buf || buflen <= 0) return fail(KMC_ERR_BAD_ARG, "bad argument");
-    std::ostringstream o;
-    if (s->islands)
-        o << "island mode: " << s->nislands << " islands of " << s->island_size << " walkers in LDS, " << s->island_gens
-          << " generations per launch, rows 2 lanes x " << s->island_K << " chunks";
-    else if (s->resident)
-        o << "resident mode (exact): whole ensemble in one workgroup's LDS (" << s->resident_tpb
-          << " threads), up to " << kDrawTableGens << " generations per launch, "
-          << (s->resident_lane2 ? std::string("two walkers per thread") : s->resident_lane ? std::string("one walker per thread") : "rows 2 lanes x " + std::to_string(s->island_K) + " chunks")
-          << ", the launch's draws from a wide kernel before it";
-    else if (s->fused) {
-        if (s->fused_L == 0)
-            o << "one launch per generation (exact): generation_lane ND=" << s->cfg.ndim << ", one walker per lane, second-half walkers recompute their partner's first-half move, grid "
-              << 2 * ((s->h + s->fused_tpb - 1) / s->fused_tpb) << " x " << s->fused_tpb;
-        else
-            o << "one launch per generation (exact): generation_group L=" << s->fused_L << " K=" << s->plan.K << ", rows lane-striped, second-half walkers recompute their partner's first-half move, grid "
-              << 2 * ((s->h + s->fused_tpb / s->fused_L - 1) / (s->fused_tpb / s->fused_L)) << " x " << s->fused_tpb;
-        o << launch_mode_text(s, "generation");
-    } else if (s->data_eval) {
-        const DataPlan& ph = s->plan_half;
-        const int64_t np = (int64_t)s->ntemps * s->h;                      // (a likelihood-tempered ladder: every rung's proposals in one pass)
-        o << "data density (exact): per half-step propose kernel -> " << (ph.obs ? "data_partial_obs (one observation per lane, grid " + std::to_string(np)
-                                                                                 : "data_partial_lane (one proposal per lane, grid " + std::to_string((np + 63) / 64))
-          << " x " << ph.nblocks << " workgroups of 256, " << ph.rounds << " rounds per wave) -> " << (s->temper_like ? "data_fold_split" : "data_fold") << " -> accept kernel, eager launches; "
-          << s->data_ud->ndata << " observations of " << s->data_ud->ncols << " doubles; scratch " << ph.nblocks << " x " << np
-          << " tree nodes (at most 4096 x " << (s->temper_like ? "ntemps x " : "") << "nwalkers doubles)";
-    } else if (s->host_eval)
-        o << "host-evaluated density (exact): per half-step propose kernel -> D2H -> callback -> H2D -> accept kernel, grid "
-          << s->grid << " x 256";
-    else if (s->plan.vec) {
-        o << "multi-launch (exact): half_step_vec L=" << s->plan.L << " K=" << s->plan.K << " ITER=" << s->plan.ITER
-          << (s->plan.ragged ? " ragged" : " exact-size") << ", grid " << s->grid << " x " << s->tpb
-          << launch_mode_text(s, "step");
-        if (s->launch_mode == 3 && !(s->cfg.flags & KMC_NO_GRAPH)) {      // which kernel variant a replay's nodes run (kmc_updated.hip: spec_of_chunk)
-            const char* why = nullptr;
-            if (spec_variant_possible(s, kVarCredit, &why)) o << "; phase-specialised kernel instance in counted replays";
-            else o << "; generic kernel in every phase (" << why << ")";
-            // ... and whether one draw pass serves a whole workgroup in burn-in replays (kmc_shared_draws.hpp)
-            if (spec_variant_possible(s, kVarShareBurnin, &why)) o << "; workgroup-shared draws in burn-in replays (" << variant_share(s, kVarShareBurnin) << " waves per workgroup)";
-            else o << "; no workgroup-shared draws (" << why << ")";
-        }
-    } else
-        o << "multi-launch (exact): " << (s->user && s->uk.staged ? "half_step_staged (one walker per lane, rows staged through LDS)" : "half_step_generic (one walker per lane)")
-          << ", grid " << s->grid << " x " << s->tpb;
-    if (s->feed_replays > 0 && debug_opt("feed-stats")) {
-        char b[200];
-        std::snprintf(b, sizeof(b), "; feeding thread per replay of %lld generations: wait for a free executable %.1f us, parameter updates %.1f us, hipGraphLaunch %.1f us (%lld replays)",
-                      (long long)s->uchunk, s->feed_wait_ns / 1e3 / s->feed_replays, s->feed_update_ns / 1e3 / s->feed_replays, s->feed_launch_ns / 1e3 / s->feed_replays, (long long)s->feed_replays);
-        o << b;
-    }
-    if (s->cfg.move == KMC_MOVE_DE) {
-        char b[160];
-        std::snprintf(b, sizeof(b), "; differential-evolution move (KMC_MOVE_DE): gamma0 %.6g, sigma %.3g, kernel %s", de_gamma0_of(s->cfg), s->cfg.de_sigma,
-                      s->host_eval ? "half_step_de_generic (propose / accept passes)" : s->plan.vec ? "half_step_de_vec" : "half_step_de_generic");
-        o << b;
-    }
-    if (s->cfg.move == KMC_MOVE_SNOOKER) {
-        char b[160];
-        std::snprintf(b, sizeof(b), "; snooker move (KMC_MOVE_SNOOKER): gamma %.6g, kernel %s", snooker_gamma_of(s->cfg.snooker_gamma),
-                      s->host_eval ? "half_step_snooker_generic (propose / accept passes)" : s->plan.vec ? "half_step_snooker_vec" : "half_step_snooker_generic");
-        o << b;
-    }
-    if (s->cfg.move == KMC_MOVE_MIX) {
-        double w[KMC_MIX_MAX] = {0.0, 0.0, 0.0, 0.0};
-        const MixTable mt = mix_table_of(s->cfg, w);
-        o << "; move mixture (KMC_MOVE_MIX), one member per half-step:";
-        for (int i = 0; i < mt.count; ++i) {
-            char b[160];
-            if (mt.move[i] == KMC_MOVE_DE) std::snprintf(b, sizeof(b), " %.6g x DE (gamma0 %.6g, sigma %.3g)", w[i], mt.c0[i], mt.c1[i]);
-            else std::snprintf(b, sizeof(b), " %.6g x snooker (gamma %.6g)", w[i], mt.c0[i]);
-            o << (i ? "," : "") << b;
-        }
-        o << ", kernel " << (s->host_eval ? "half_step_mix_generic (propose / accept passes)" : s->plan.vec ? "half_step_mix_vec" : "half_step_mix_generic");
-    }
-    if (s->temper) {
-        o << "; parallel tempering: ntemps " << s->ntemps << " rungs in one launch per half-step (grid y = rung), kernel "
-          << (s->plan.vec ? "half_step_temper_vec" : "half_step_temper_generic") << ", betas 1 .. ";
-        char b[64];
-        std::snprintf(b, sizeof(b), "%.6g", s->betas.back());
-        o << b << ", swap sweep " << (s->cfg.swap_every > 0 ? "every " + std::to_string(s->cfg.swap_every) + " generations (" + (s->adapt ? (s->temper_like ? "temper_sweep_adapt<like>" : "temper_sweep_adapt<whole>") : s->temper_like ? "temper_sweep_like" : "temper_sweep") + ")" : std::string("off"));
-        if (s->adapt) {
-            char ab[96];
-            std::snprintf(ab, sizeof(ab), ", lag %.6g, time %.6g", s->cfg.adapt_lag, s->cfg.adapt_time);
-            o << "; adaptive ladder: until generation " << s->cfg.adapt_until << ab << " (betas above: the initial ladder)";
-        }
-        if (s->temper_like) o << "; likelihood tempering: rung t samples prior + beta_t S, four launches per half-step for the whole ladder";
-        if (s->temper_updated_fallback) o << "; KMC_LAUNCH=updated asked for: the updated-graph mode is not built for tempered samplers, fell back to the table graph";
-    }
-    if (s->budget_fallback) o << "; updated-graph budget of the process spent (kmc_set_updated_budget_mb): fell back to " << (s->launch_mode == 2 ? "eager launches" : "the table graph");
-    if (s->push) o << "; accepted rows pushed into the peers' local copies (KMC_P2P_PUSH)";
-    if (s->f32) o << "; rows kept in float (KMC_F32), arithmetic in double";
-    if (s->stream_chain) o << "; chain streamed to host memory in blocks of " << s->ring_blk << " samples (device ring of 3 blocks" << (s->dst_chain_reg || s->dst_logp_reg ? ", destination page-locked" : "") << ")";
-    if (s->d_ids) o << "; dealt sub-ensemble " << s->cfg.deal_rank << "/" << s->cfg.deal_count << " (walkers re-dealt between epochs)";
-    if (s->d_mring) o << "; moments through a ring of " << s->mring_depth << " posted rows per wave";
-    if (s->user) o << "; runtime-compiled density";
-    if (s->user && s->user->is_body && s->fused)
-        o << (s->fused_L == 0 ? " (function body, evaluated as written: one walker per lane)"
-                              : " (function body recognised as a sum over elements and checked against the body on test rows: lane-striped)");
-    else if (s->user && s->user->is_body && s->plan.vec && !s->resident && !s->islands)
-    {
-        const std::string& why_not = s->sep_off ? s->sep_off_note : s->user->sep_note;
-        o << ((s->user->sep && !s->sep_off) ? " (function body recognised as a sum over elements and checked against the body on test rows: lane-striped)"
-                                            : " (function body: rows lane-striped, the body evaluated per walker on the whole proposal" + (why_not.empty() ? std::string() : "; taken for a sum over elements, but " + why_not) + ")");
-    }
-    if (s->nblob > 0) o << " with a blob of " << s->nblob << " doubles per walker" << (s->d_chain_blob ? " (stored with every sample)" : "");
-    if (s->p2p) o << "; P2P shard " << s->cfg.shard_rank << "/" << s->cfg.shard_count << (s->connected ? "" : " (not connected)");
-    else if (s->cfg.shard_count > 1 || s->comm)
-        o << "; replica shard " << s->cfg.shard_rank << "/" << s->cfg.shard_count
-          << (s->comm ? ((s->comm_graph_ok && !(s->cfg.flags & KMC_NO_GRAPH) && s->launch_mode != 2) ? ", RCCL all-gather of the updated half after every half-step (captured in the graph)"
-                                                                                                         : ", RCCL all-gather of the updated half after every half-step (enqueued launch by launch)") : "");
-    if (debug_opt("geometry")) {
-        // what creation derived from the configuration and the text above does not show (tests/test_gpu_create_routes.py pins it); nothing
-        // that depends on the machine: no addresses, no word on whether pinned host memory got a device alias
-        const Plan& p = s->plan;
-        auto data_plan_text = [](const DataPlan& d) { return std::to_string((int)d.obs) + "/" + std::to_string(d.rounds) + "/" + std::to_string(d.nblocks); };
-        o << "; geometry: plan=" << (p.vec ? "vec" : "generic") << "/" << p.L << "/" << p.K << "/" << p.ITER << "/" << (p.ragged ? "ragged" : "exact")
-          << " tpb=" << s->tpb << " grid=" << s->grid << " macc_stride=" << s->macc_stride << " macc_elems=" << s->macc_elems << " vec_lds=" << s->vec_lds
-          << " nrows=" << s->nrows << " resident=" << s->resident << " resident_tpb=" << s->resident_tpb << " resident_lane=" << s->resident_lane
-          << " resident_lane2=" << s->resident_lane2 << " islands=" << s->islands << " island_K=" << s->island_K << " island_ragged=" << s->island_ragged
-          << " nislands=" << s->nislands << " island_lds=" << s->island_lds << " fused=" << s->fused << " fused_L=" << s->fused_L
-          << " fused_tpb=" << s->fused_tpb << " fused_fold=" << s->fused_fold << " mring_depth=" << s->mring_depth << " mring_waves=" << s->mring_waves
-          << " ring_blk=" << s->ring_blk << " ring_slots=" << s->ring_slots << " stream_by_walker=" << s->stream_by_walker << " push=" << s->push
-          << " part_doubles=" << s->part_doubles << " plan_half=" << data_plan_text(s->plan_half) << " plan_all=" << data_plan_text(s->plan_all);
-        const std::pair<const char*, const void*> bufs[] = {
-            {"d_ring", s->d_ring}, {"d_draws", s->d_draws}, {"d_pos2", s->d_pos2}, {"d_glast", s->d_glast}, {"d_isum", s->d_isum}, {"d_msum", s->d_msum},
-            {"d_mring", s->d_mring}, {"bw_scratch", s->bw_scratch}, {"bw_scratch_logp", s->bw_scratch_logp}, {"d_ids", s->d_ids}, {"d_mix", s->d_mix},
-            {"d_like", s->d_like}, {"d_acc", s->d_acc}, {"d_prop", s->d_prop}, {"d_part", s->d_part}, {"d_betas", s->d_betas}, {"d_chain", s->d_chain},
-            {"d_chain_logp", s->d_chain_logp}, {"d_blob", s->d_blob}, {"d_chain_blob", s->d_chain_blob}, {"d_err", s->d_err}};
-        for (const auto& b : bufs) o << " " << b.first << "=" << (b.second != nullptr);
-    }
-    const std::string t = o.str();
-    std::snprintf(buf, (size_t)buflen, "%s", t.c_str());
-    return KMC_OK;
-}
 
 KMC_EXPORT void* kmc_sampler_device_ptr(kmc_sampler* s, int which)
 {

@@ -1,4 +1,5 @@
-// kmc_sampler.hpp -- what the sampler's translation units share (kmc_sampler.hip: lifecycle; kmc_launch.hip: the generation
+// kmc_sampler.hpp -- what the sampler's translation units share (kmc_sampler.hip: lifecycle; kmc_validate.hip: which configurations
+// it takes; kmc_describe.hip: how a sampler executes, in words; kmc_launch.hip: the generation
 // loop; kmc_updated.hip: its updated-graph launch mode; kmc_state.hip: state in and out; kmc_copy.hip: copies and the chain ring; kmc_rtc.hip: runtime-compiled densities;
 // kmc_p2p.hip: multi-GPU wiring; kmc_diag.hip: diagnostics): the handle behind kmc_sampler* and the internal entry points
 // that cross those files.  Internal.
@@ -21,6 +22,8 @@ constexpr int kUExec = 6;             // executables of the "updated graph" laun
 enum : int { kVarGeneric = 0, kVarCredit = 1, kVarShareBurnin = 2, kUVariants = 3 };
 constexpr size_t kGuardBytes = 4096;  // KMC_DEBUG=poison: guard band behind every device allocation of a sampler
 constexpr int kHostPieces = 8;        // KMC_HOST_DENSITY: most pieces a half-step's proposals travel to the host in
+// dynamic LDS a workgroup of the resident and island kernels may ask for (hipModuleLaunchKernel takes dynamic LDS beyond 64 KiB as it is)
+constexpr size_t kResidentLdsMax = 156 * 1024;
 
 struct Plan {
     kmc::HalfStepFn fn = nullptr;

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import de_yardstick as yd
+import validate_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,25 +62,9 @@ def test_partner_map_is_exactly_uniform_for_power_of_two_halves(h):
         assert all(kp + (kp >= jj) != jj for kp in range(h - 1))
 
 
-def _cfg(lib, **kw):
-    c = lib.Config()
-    c.dtype = lib.F64
-    c.density = lib.GAUSSIAN_ISO
-    c.params[0], c.params[1] = 0.0, 1.0
-    c.nwalkers, c.ndim, c.ngenerations, c.nburnin, c.nthin = 64, 4, 10, 0, 1
-    c.a_scale = 2.0
-    c.shard_count = 1
-    c.move = lib.MOVE_DE
-    for k, v in kw.items():
-        setattr(c, k, v)
-    return c
-
-
 def _validate(kmc, **kw):
     from kissmcmc_jl_amd import _lib
-    L = _lib.lib()
-    st = L.kmc_validate(C.byref(_cfg(_lib, **kw)))
-    return st, L.kmc_last_error().decode() if st else ""
+    return validate_cases.validate(**dict(dict(nwalkers=64, ndim=4, move=_lib.MOVE_DE), **kw))
 
 
 def test_de_config_validates(kmc):

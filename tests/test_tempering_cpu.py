@@ -12,6 +12,7 @@ import pytest
 import de_yardstick as yd
 import snooker_yardstick as sy
 import tempering_yardstick as ty
+import validate_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAUSS, ROSEN = 0, 2
@@ -142,23 +143,7 @@ def test_new_fields_agree_with_the_header(tmp_path):
 
 
 def _validate(**kw):
-    from kissmcmc_jl_amd import _lib
-    L = _lib.lib()
-    c = _lib.Config()
-    c.dtype, c.density = _lib.F64, _lib.GAUSSIAN_ISO
-    c.params[0], c.params[1] = 0.0, 1.0
-    c.nwalkers, c.ndim, c.ngenerations, c.nburnin, c.nthin = 64, 4, 10, 0, 1
-    c.a_scale, c.shard_count = 2.0, 1
-    betas = kw.pop("betas", None)
-    keep = None
-    if betas is not None:
-        keep = (C.c_double * len(betas))(*betas)
-        c.betas = C.cast(keep, C.c_void_p)
-        c.ntemps = len(betas)
-    for k, v in kw.items():
-        setattr(c, k, v)
-    st = L.kmc_validate(C.byref(c))
-    return st, L.kmc_last_error().decode()
+    return validate_cases.validate(**dict(dict(nwalkers=64, ndim=4), **kw))
 
 
 def test_kmc_validate_on_ladders_and_refusals():
