@@ -1,5 +1,5 @@
 // kmc_chain_view.hpp -- what the calls that read a stored chain where it lies share on the host side (kmc_summary.hip, kmc_hist.hip,
-// kmc_convergence.hip, kmc_rank.hip, kmc_hdi.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
+// kmc_convergence.hip, kmc_rank.hip, kmc_hdi.hip, kmc_pointwise.hip, kmc_psis.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
 // such a view -- the chain a sampler holds, or a dense host chain uploaded for the call.  Internal.
 #pragma once
 #include "kmc_host.hpp"
@@ -114,6 +114,17 @@ struct ChainSource {
         }
         v->chain = b.chain; v->logp = b.logp;
         return KMC_OK;
+    }
+
+    // The stream of one call, after describe().  Never the legacy stream (kmc_host.hpp: copy_sync).  A sampler's own stream, which
+    // describe() has drained, serves: creating and destroying a stream for the call costs 3.4 to 4.4 ms, several times the two
+    // pointwise passes at the README's small shape and more than a whole interval scan at a small one.  Declare `ss` after the call's
+    // buffers: the stream is drained before they go.
+    hipError_t stream(ScopedStream* ss) const
+    {
+        if (host || !s->stream) return ss->create();
+        ss->borrowed = s->stream;
+        return hipSuccess;
     }
 };
 

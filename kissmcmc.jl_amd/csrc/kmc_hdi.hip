@@ -25,17 +25,6 @@ struct HdiBuffers {
     ~HdiBuffers() { (void)hipFree(part); (void)hipFree(out); }
 };
 
-// the events around the three stages, for info: gather, sort, scan + fold
-struct StageEvents {
-    hipEvent_t e[4] = {};
-    hipError_t create()
-    {
-        for (auto& x : e) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
-        return hipSuccess;
-    }
-    ~StageEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 std::string num(double x)
 {
     char buf[40];
@@ -97,14 +86,10 @@ kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask
     KMC_TRY(rank_room(sh, ncols, 0, false, (double)part_bytes + (double)out_bytes));
     RankBuffers rb;
     HdiBuffers hb;
-    // Never the legacy stream (kmc_host.hpp: copy_sync).  A sampler's own stream, which describe() has drained, serves: creating and
-    // destroying a stream for the call costs milliseconds, more than the whole call at a small shape.  (Declared after the buffers:
-    // the stream is drained before they go.)
-    ScopedStream ss;
-    if (src.host || !src.s->stream) HIP_TRY(ss.create());
-    else ss.borrowed = src.s->stream;
+    ScopedStream ss;                                          // (declared after the buffers: the stream is drained before they go)
+    HIP_TRY(src.stream(&ss));
     const hipStream_t st = ss.get();
-    StageEvents ev;
+    TimedEvents<4> ev;                                        // around the three stages, for info: gather, sort, scan + fold
     if (info) HIP_TRY(ev.create());
     KMC_TRY(upload_rank(b, mask_host, v.nl, st));
     KMC_TRY(rank_alloc(rb, ncols, N, false));
@@ -147,11 +132,7 @@ kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask
     if (info) {
         info[0] = N; info[1] = a.ntiles;
         info[2] = 8 * ncols * ((N - kmin) + windows);         // the scan's loads: key[i] once per start, key[i + k_p] per window
-        for (int k = 0; k < 3; ++k) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.e[k], ev.e[k + 1]));
-            info[3 + k] = (int64_t)((double)ms * 1e6);
-        }
+        for (int k = 0; k < 3; ++k) HIP_TRY(ev.elapsed_ns(k, k + 1, &info[3 + k]));
     }
     return KMC_OK;
 }

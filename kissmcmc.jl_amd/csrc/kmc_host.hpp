@@ -170,6 +170,24 @@ struct ScopedStream {
         else if (borrowed) (void)hipStreamSynchronize(borrowed);
     }
 };
+// N events around the stages of one call, for its info: created only when info is asked for, read after the stream has passed them
+template <int N>
+struct TimedEvents {
+    hipEvent_t e[N] = {};
+    hipError_t create()
+    {
+        for (auto& x : e) { const hipError_t r = hipEventCreate(&x); if (r != hipSuccess) return r; }
+        return hipSuccess;
+    }
+    hipError_t elapsed_ns(int i, int j, int64_t* ns) const
+    {
+        float ms = 0.f;
+        const hipError_t r = hipEventElapsedTime(&ms, e[i], e[j]);
+        *ns = (int64_t)((double)ms * 1e6);
+        return r;
+    }
+    ~TimedEvents() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
 // a hipMalloc block for the duration of one call: freed with the scope, so the stream that uses it is synchronised before the scope ends
 struct ScopedDeviceBlock {
     void* p = nullptr;
