@@ -920,6 +920,90 @@ kmc_status  kmc_chain_rank_convergence(const double* chain_host, const double* l
                                        double* ess_tail, double* ess_q05, double* ess_q95, double* median, double* q05, double* q95,
                                        int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out, int64_t* info);
 
+/* ---- the effective sample size and Monte-Carlo standard error of quantiles, from bit-packed indicator chains ----
+ * How many digits of a reported quantile mean anything.  Vehtari, Gelman, Simpson, Carpenter and Buerkner (2021): the ess of the
+ * indicator x <= q_p, then the width of a Beta-distributed rank interval read off the sorted draws.  The formulas below are the
+ * definition (the construction of the paper, as posterior::mcse_quantile is understood to use it).
+ *
+ * Selection, chains and columns: as for kmc_sampler_lag_sums / kmc_sampler_rank_convergence (first_sample, walker_mask, split, chain
+ * j = half * nw + k, m chains of h samples; columns: every dimension and, when asked, the log-densities as the last).  Everything is
+ * per column over the pooled draws, S = m h of them, S < 2^31, h >= 4, m >= 2.
+ * Probabilities: nprobs values p, 1 <= nprobs <= 16, each finite and strictly inside (0, 1); repeats are allowed.  Anything else is
+ * KMC_ERR_BAD_ARG, naming the index and the value, before the device is touched.
+ *
+ * For column c and probability p:
+ * 1. quantile.  q_p by the rule of the order statistics with N = S: h = p (S - 1), lo = floor(h), hi = min(lo + 1, S - 1),
+ *    frac = h - lo, q_p = x_lo + frac (x_hi - x_lo), and x_lo itself where frac == 0; read out of the sorted column, by value as in the
+ *    ranking (x + 0.0 first, +-inf ordinary values).  For p in {0.5, 0.05, 0.95}: kmc_sampler_rank_convergence's median, q05, q95, bit
+ *    for bit.
+ * 2. Indicator.  I[i][j] = (x[i][j] <= q_p), one bit per draw.
+ * 3. Chain moments, from counts.  k_j = sum_i I[i][j]; mu_j = k_j / h; ss_j = k_j ((1 - mu_j)(1 - mu_j)) + (h - k_j)(mu_j mu_j);
+ *    s2_j = ss_j / (h - 1).  Every operation rounded to double on its own, in this order, no fused multiply-add (kmc_indicator_moments).
+ * 4. Lag counts.  D_t = #{(i, j) : t <= i < h, I[i][j] != I[i - t][j]}: for an indicator (x_i - x_(i-t))^2 is the XOR of two bits.  An
+ *    integer, handed on as the double of that integer.  A pair never straddles the halves of a walker or reaches before first_sample.
+ * 5. ess, T, flags: kmc_convergence_stats, unchanged, on (m, h, mu, s2, D), with the lag-doubling loop of kmc_sampler_convergence (32,
+ *    64, 128, ... lags until every series' rule has fired, or max_lag).  A series with W == 0 -- the indicator that is 1 everywhere: a
+ *    constant or two-valued column -- gives ess = NaN, T = 0 and no error.
+ * 6. lower, upper, mcse.  A = ess p + 1, B = ess (1 - p) + 1; a = Bq(Phi(-1); A, B), b = Bq(Phi(1); A, B) with Bq the quantile
+ *    function of the Beta distribution (kmc_beta_quantile), Phi(-1) = 0.15865525393145707, Phi(1) = 0.8413447460685429;
+ *    i1 = max(floor(a S), 1) - 1, i2 = min(ceil(b S), S) - 1, the products rounded once (kmc_quantile_mcse_ranks); lower = sorted[i1],
+ *    upper = sorted[i2], both elements of the chain bit for bit (up to the sign of zero); mcse = (upper - lower) / 2.  ess NaN or <= 0:
+ *    lower = upper = mcse = NaN.  inf - inf gives NaN and is not an error.
+ * 7. NaN.  A column whose selection holds a NaN gets NaN in every output, T = 0 and KMC_CONV_HAS_NAN; other columns are unaffected.
+ *
+ * Algorithm.  One gather and one sort of the rank statistics; the quantiles are picked and become the thresholds;
+ * qind_pack reads the chain where it lies and writes, for every (p, c, chain), words of 64 consecutive samples (bit i & 63 of word
+ * i >> 6 is I[i][j], the bits at and beyond h zero) and k_j; qind_lag_counts forms the XOR of each word with the series shifted by t (a
+ * funnel of the words t >> 6 and (t >> 6) + 1 back), masks it to the valid pairs and adds its popcount into 64-bit counters by integer
+ * adds only.  D_t is an exact integer: equal bits from equal calls, however the lags are cut into calls.  The Beta quantile and the
+ * index rule are host stages; the second pick reads the sorted keys, which stay allocated until then.  Work space: the keys of one
+ * sort (16 B per pooled draw and column), nprobs ncols m ceil(h / 64) words and the counters; KMC_ERR_UNSUPPORTED, naming the sizes,
+ * when that does not fit -- never a partial answer.
+ * Not built: the MCSE of the standard deviation and of the ends of a highest-density interval, the ess of the indicator of an interval
+ * (ess_local), several GPUs, a streamed chain. */
+/* The quantile function of Beta(A, B) at prob: the x with I_x(A, B) = prob.  Host only.  The algorithm is fixed: the regularised
+ * incomplete beta function as x^A (1 - x)^B / (A B(A, B)) times the continued fraction of Numerical Recipes' betacf (modified Lentz,
+ * ended when a factor is within 4.5e-16 of 1), taken for 1 - x with A and B exchanged when x >= (A + 1) / (A + B + 2); the logarithm
+ * of the leading term by the C library's lgamma while A and B are below 10, by Stirling's series (five terms) for an argument from 10
+ * on, and with both there in the form of TOMS 708's BRCOMP (lambda = A - (A + B) x and e - log(1 + e)), which forms nothing of the
+ * size of A log x; inverted by Newton's iteration from mean -+ sd inside a bracket that every evaluation narrows, a bisection step
+ * whenever Newton's leaves the bracket, until the step no longer changes x or the bracket's ends are neighbouring doubles, at most
+ * 200 evaluations.  Equal inputs give equal bits on every run.  Works for A, B from 1 up to 2^31 + 1 and beyond.  The library's value
+ * is the definition of a and b above; against scipy.special.betaincinv it differs by at most 1.5e-12 relatively over the grid of
+ * tests/test_quantile_mcse_cpu.py.  KMC_ERR_BAD_ARG: prob outside (0, 1), A or B not finite or < 1. */
+kmc_status  kmc_beta_quantile(double prob, double A, double B, double* x);
+/* Step 6's ranks for S pooled draws: a, b, i1, i2 (0-based; each pointer may be NULL).  ess NaN or <= 0: a = b = NaN, i1 = i2 = -1, and
+ * KMC_OK.  Host only.  KMC_ERR_BAD_ARG: S < 1 or >= 2^52, p outside (0, 1). */
+kmc_status  kmc_quantile_mcse_ranks(int64_t S, double p, double ess, double* a, double* b, int64_t* i1, int64_t* i2);
+/* Step 3: mu and s2 of an indicator with k ones among h samples.  Host only.  KMC_ERR_BAD_ARG: h < 2, k outside [0, h]. */
+kmc_status  kmc_indicator_moments(int64_t h, int64_t k, double* mu, double* s2);
+/* The tile shape of the indicator kernels: samples per word (64), threads per workgroup (256), the words of one (p, c) a workgroup of
+ * qind_lag_counts stages in LDS (2048) and the bytes of LDS it uses.  Needs no device; pointers may be NULL. */
+kmc_status  kmc_indicator_plan(int32_t* word_bits, int32_t* threads, int32_t* chunk_words, int32_t* lds_bytes);
+/* The device stage alone: the indicators x <= thresholds[p][c] (thresholds [nprobs][ncols], any doubles; nothing is <= NaN), their counts
+ * ones [nprobs][ncols][m] and the lag counts lagcount [nprobs][ncols][nlags], lagcount[.][.][k] = D_(lag0 + k); the lags must lie in
+ * [1, h - 1], nlags may be 0.  No sort.  Refusals as for kmc_sampler_lag_sums (no KMC_STORE_CHAIN, with_logp without KMC_STORE_LOGP, a
+ * streamed chain, a sharded or P2P sampler, an empty selection), and nprobs outside 1..16, before the device is touched. */
+kmc_status  kmc_sampler_indicator_lags(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask /* [nlocal] or NULL */, int32_t split,
+                                       int32_t with_logp, int32_t nprobs, const double* thresholds, int64_t lag0, int64_t nlags,
+                                       int64_t* ones, uint64_t* lagcount, int64_t* m_out, int64_t* h_out);
+kmc_status  kmc_chain_indicator_lags(const double* chain_host /* [nsamples][nwalkers][ndim] */, const double* logp_host /* or NULL */,
+                                     int64_t nsamples, int64_t nwalkers, int64_t ndim, int64_t first_sample, const uint8_t* walker_mask,
+                                     int32_t split, int32_t nprobs, const double* thresholds, int64_t lag0, int64_t nlags, int device,
+                                     int64_t* ones, uint64_t* lagcount, int64_t* m_out, int64_t* h_out);
+/* The whole thing.  [nprobs][ncols]: quantile, ess, mcse, lower, upper, T, flags (those of kmc_convergence_stats and KMC_CONV_HAS_NAN).
+ * max_lag as for kmc_sampler_convergence.  info (may be NULL) gets 4 numbers for benchmarks: the lags computed, the bytes the sort
+ * moved, the bytes qind_pack read and the words qind_lag_counts read. */
+kmc_status  kmc_sampler_quantile_mcse(kmc_sampler* s, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t with_logp,
+                                      int64_t max_lag, int32_t nprobs, const double* probs, double* quantile, double* ess, double* mcse,
+                                      double* lower, double* upper, int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out,
+                                      int64_t* info);
+kmc_status  kmc_chain_quantile_mcse(const double* chain_host, const double* logp_host /* or NULL */, int64_t nsamples, int64_t nwalkers,
+                                    int64_t ndim, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag,
+                                    int32_t nprobs, const double* probs, int device, double* quantile, double* ess, double* mcse,
+                                    double* lower, double* upper, int64_t* T, int32_t* flags, int64_t* m_out, int64_t* h_out,
+                                    int64_t* info);
+
 /* ---- highest-density intervals of a stored chain, scanned on the device ----
  * The narrowest interval that holds a given share of the draws of a column: what ArviZ's summary reports as hdi_3% / hdi_97% and the
  * interval people quote for a skewed posterior, where it differs from the equal-tailed one of two quantiles.  The definition is ArviZ's

@@ -14,6 +14,7 @@ from .densities import (CDensity, DataDensity, DeviceLogPdf, Exponential, ExprDe
                         Rosenbrock)
 from .chain_convergence import convergence, convergence_stats, error_of_estimated_mean, evaluate_convergence, lag_sums, samples_vs_tau
 from .chain_convergence import normal_scores, rank_convergence, rank_plan, rank_scores
+from .chain_convergence import beta_quantile, indicator_lags, indicator_moments, indicator_plan, quantile_mcse, quantile_mcse_ranks
 from .chain_covariance import correlation, cov_plan, covariance
 from .chain_predictive import compare_waic, pointwise_loglike, pointwise_plan, pointwise_stats, waic, waic_stats
 from .chain_loo import compare_loo, loo, loo_stats, pointwise_weights, psis_plan, psis_smooth, psis_tail, relative_eff
@@ -31,6 +32,7 @@ __all__ = [
     "quantiles", "quantile_ranks", "map_sample", "summarize_run", "histogram", "corner", "hist_mode", "credible_levels",
     "convergence", "convergence_stats", "lag_sums", "evaluate_convergence", "error_of_estimated_mean", "samples_vs_tau",
     "rank_convergence", "rank_scores", "rank_plan", "normal_scores",
+    "quantile_mcse", "indicator_lags", "beta_quantile", "quantile_mcse_ranks", "indicator_moments", "indicator_plan",
     "hdi", "hdi_span",
     "covariance", "correlation", "cov_plan",
     "waic", "pointwise_loglike", "pointwise_stats", "compare_waic", "waic_stats", "pointwise_plan",

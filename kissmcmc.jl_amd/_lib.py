@@ -64,6 +64,8 @@ SYMBOLS = [
     "kmc_convergence_plan",
     "kmc_rank_plan", "kmc_rank_normal_scores", "kmc_sampler_rank_scores", "kmc_chain_rank_scores", "kmc_sampler_rank_convergence",
     "kmc_chain_rank_convergence",
+    "kmc_beta_quantile", "kmc_quantile_mcse_ranks", "kmc_indicator_moments", "kmc_indicator_plan", "kmc_sampler_indicator_lags",
+    "kmc_chain_indicator_lags", "kmc_sampler_quantile_mcse", "kmc_chain_quantile_mcse",
     "kmc_sampler_hdi", "kmc_chain_hdi", "kmc_hdi_span",
     "kmc_sampler_covariance", "kmc_chain_covariance", "kmc_cov_plan", "kmc_cov_correlation",
     "kmc_sampler_pointwise_stats", "kmc_chain_pointwise_stats", "kmc_sampler_pointwise_loglike", "kmc_chain_pointwise_loglike",
@@ -308,6 +310,17 @@ def lib() -> C.CDLL:
     L.kmc_chain_rank_scores.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int, ip, dp, dp, ip, ip, ip]
     L.kmc_sampler_rank_convergence.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64] + [dp] * 10 + [ip, i32p, ip, ip, ip]
     L.kmc_chain_rank_convergence.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int] + [dp] * 10 + [ip, i32p, ip, ip, ip]
+    u64p = C.POINTER(C.c_uint64)
+    L.kmc_beta_quantile.argtypes = [C.c_double, C.c_double, C.c_double, dp]
+    L.kmc_quantile_mcse_ranks.argtypes = [C.c_int64, C.c_double, C.c_double, dp, dp, ip, ip]
+    L.kmc_indicator_moments.argtypes = [C.c_int64, C.c_int64, dp, dp]
+    L.kmc_indicator_plan.argtypes = [i32p, i32p, i32p, i32p]
+    L.kmc_sampler_indicator_lags.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int32, dp, C.c_int64, C.c_int64, ip, u64p, ip, ip]
+    L.kmc_chain_indicator_lags.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int32, dp, C.c_int64, C.c_int64, C.c_int,
+                                           ip, u64p, ip, ip]
+    L.kmc_sampler_quantile_mcse.argtypes = [vp, C.c_int64, bp, C.c_int32, C.c_int32, C.c_int64, C.c_int32, dp] + [dp] * 5 + [ip, i32p, ip, ip, ip]
+    L.kmc_chain_quantile_mcse.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, C.c_int32, C.c_int64, C.c_int32, dp, C.c_int] + [dp] * 5 + \
+        [ip, i32p, ip, ip, ip]
     L.kmc_sampler_hdi.argtypes = [vp, C.c_int64, bp, C.c_int32, dp, C.c_int32, dp, dp, ip, ip, ip, ip]
     L.kmc_chain_hdi.argtypes = [dp, dp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, bp, dp, C.c_int32, C.c_int, dp, dp, ip, ip, ip, ip]
     L.kmc_hdi_span.argtypes = [C.c_int64, C.c_double, ip, ip]

@@ -225,6 +225,122 @@ def rank_convergence(thetas, logdensities=None, first_sample: int = 0, walkers=N
     return rank_columns(chain_rank_convergence_raw(thetas, logdensities, first_sample, walkers, split, max_lag, device))
 
 
+# ---- the ess and the Monte-Carlo standard error of quantiles ------------------------------------------------------------------------
+
+MAX_PROBS = 16          # per call of the library (kmc_sampler_quantile_mcse, kmc_sampler_indicator_lags)
+QUANTILE_COLUMNS = ("quantile", "ess", "mcse", "lower", "upper")
+
+
+def beta_quantile(prob: float, A: float, B: float) -> float:
+    """The quantile function of the Beta distribution (``kmc_beta_quantile``; needs no device): the ``x`` with ``I_x(A, B) = prob``, for
+    ``0 < prob < 1`` and finite ``A, B >= 1``, by the fixed algorithm written down in ``include/kissmcmc_hip.h``."""
+    x = C.c_double()
+    _lib.check(_lib.lib().kmc_beta_quantile(float(prob), float(A), float(B), C.byref(x)))
+    return x.value
+
+
+def quantile_mcse_ranks(S: int, p: float, ess: float):
+    """The rank interval behind the MCSE of the quantile ``p`` among ``S`` draws of effective size ``ess``
+    (``kmc_quantile_mcse_ranks``; needs no device): ``(a, b, i1, i2)`` with ``a, b`` the Beta quantiles at ``Phi(-1)``, ``Phi(1)`` for
+    ``A = ess p + 1``, ``B = ess (1 - p) + 1`` and the 0-based ``i1 = max(floor(a S), 1) - 1``, ``i2 = min(ceil(b S), S) - 1``.  An
+    ``ess`` that is NaN or ``<= 0`` gives ``(nan, nan, -1, -1)``."""
+    a, b, i1, i2 = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().kmc_quantile_mcse_ranks(int(S), float(p), float(ess), C.byref(a), C.byref(b), C.byref(i1), C.byref(i2)))
+    return a.value, b.value, i1.value, i2.value
+
+
+def indicator_moments(h: int, k: int):
+    """``(mu, s2)`` of a chain of ``h`` indicator samples with ``k`` ones (``kmc_indicator_moments``; needs no device)."""
+    mu, s2 = C.c_double(), C.c_double()
+    _lib.check(_lib.lib().kmc_indicator_moments(int(h), int(k), C.byref(mu), C.byref(s2)))
+    return mu.value, s2.value
+
+
+def indicator_plan():
+    """The tile shape of the indicator kernels (``kmc_indicator_plan``): dict ``word_bits, threads, chunk_words, lds_bytes``."""
+    v = [C.c_int32() for _ in range(4)]
+    _lib.check(_lib.lib().kmc_indicator_plan(*[C.byref(x) for x in v]))
+    return dict(zip(("word_bits", "threads", "chunk_words", "lds_bytes"), [x.value for x in v]))
+
+
+def indicator_lags_from(p, thresholds, lag0=1, nlags=0, split=True, logp=False):
+    """:func:`indicator_lags` from a provider: ``kmc_sampler_indicator_lags`` / ``kmc_chain_indicator_lags``."""
+    ncols = p.ndim + (1 if logp else 0)
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if thr.ndim == 1:
+        thr = thr[None, :]
+    if thr.ndim != 2 or thr.shape[1] != ncols:
+        raise ValueError(f"thresholds must be [nprobs, {ncols}]")
+    nprobs, mm = thr.shape[0], max(1, (2 if split else 1) * p.nselected)
+    ones = np.zeros((nprobs, ncols, mm), dtype=np.int64)
+    counts = np.zeros((nprobs, ncols, max(0, int(nlags))), dtype=np.uint64)
+    m, h = C.c_int64(), C.c_int64()
+    p.call("indicator_lags", [int(bool(split)), nprobs, _p(thr, C.c_double), int(lag0), int(nlags)],
+           [_p(ones, C.c_int64), _p(counts, C.c_uint64), C.byref(m), C.byref(h)], logp, logp_at=1)
+    return {"ones": ones, "lagcount": counts, "lag0": int(lag0), "m": m.value, "h": h.value}
+
+
+def sampler_indicator_lags(s, thresholds, lag0=1, nlags=0, first_sample=0, walkers=None, split=True, logp=False):
+    """:func:`indicator_lags` on the chain a :class:`Sampler` holds (``kmc_sampler_indicator_lags``)."""
+    return indicator_lags_from(_SamplerProvider(s, first_sample, walkers), thresholds, lag0, nlags, split, logp)
+
+
+def indicator_lags(thetas, thresholds, logdensities=None, lag0=1, nlags=0, first_sample=0, walkers=None, split=True, device=0):
+    """The device stage of :func:`quantile_mcse` alone (``kmc_chain_indicator_lags``): for ``thresholds[nprobs, ncols]`` the indicators
+    ``x <= threshold`` of every column, bit-packed on the device, as a dict ``ones[nprobs, ncols, m]`` (int64: the ones of every chain),
+    ``lagcount[nprobs, ncols, nlags]`` (uint64: ``lagcount[..., k] = D_(lag0 + k)``, the pairs ``(i, i - t)`` of a chain whose indicators
+    differ, counted by XOR and popcount -- exact integers, the same however the lags are cut into calls) and ``m``, ``h``.  Chains as in
+    :func:`lag_sums`."""
+    p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
+    return indicator_lags_from(p, thresholds, lag0, nlags, split, p.logp is not None)
+
+
+def quantile_mcse_raw_from(p, probs, split=True, logp=False, max_lag=None):
+    """Everything ``kmc_sampler_quantile_mcse`` / ``kmc_chain_quantile_mcse`` returns: ``[nprobs, ncols]`` arrays ``quantile, ess, mcse,
+    lower, upper, T`` (int64), ``flags`` (int32), and ``m``, ``h``, ``info`` (lags computed, bytes the sort moved, bytes the pack kernel
+    read, words the lag-count kernel read)."""
+    probs = np.ascontiguousarray(probs, dtype=np.float64).ravel()
+    ncols = p.ndim + (1 if logp else 0)
+    out = {k: np.full((probs.size, ncols), np.nan) for k in QUANTILE_COLUMNS}
+    out["T"] = np.zeros((probs.size, ncols), dtype=np.int64)
+    out["flags"] = np.zeros((probs.size, ncols), dtype=np.int32)
+    out["info"] = np.zeros(4, dtype=np.int64)
+    m, h = C.c_int64(), C.c_int64()
+    p.call("quantile_mcse", [int(bool(split)), _max_lag_arg(max_lag), probs.size, _p(probs, C.c_double)],
+           [_p(out[k], C.c_double) for k in QUANTILE_COLUMNS] + [_p(out["T"], C.c_int64), _p(out["flags"], C.c_int32), C.byref(m), C.byref(h),
+                                                                  _p(out["info"], C.c_int64)], logp, logp_at=1)
+    out["m"], out["h"] = m.value, h.value
+    return out
+
+
+def quantile_mcse_columns(raw):
+    """The public dict from what the library returned: ``quantile, ess, mcse, lower, upper, T, flags`` ``[nprobs, ncols]`` and ``m, h``."""
+    out = {k: raw[k] for k in QUANTILE_COLUMNS + ("T", "flags")}
+    out.update(m=raw["m"], h=raw["h"])
+    return out
+
+
+def sampler_quantile_mcse(s, probs, first_sample=0, walkers=None, split=True, logp=False, max_lag=None, raw=False):
+    """:func:`quantile_mcse` on the chain a :class:`Sampler` holds (``kmc_sampler_quantile_mcse``)."""
+    r = quantile_mcse_raw_from(_SamplerProvider(s, first_sample, walkers), probs, split, logp, max_lag)
+    return r if raw else quantile_mcse_columns(r)
+
+
+def quantile_mcse(thetas, probs, logdensities=None, first_sample: int = 0, walkers=None, split: bool = True, max_lag=None, device: int = 0,
+                  raw: bool = False):
+    """Quantiles of the pooled draws with their effective sample sizes and Monte-Carlo standard errors (Vehtari, Gelman, Simpson,
+    Carpenter and Buerkner 2021; ``kmc_chain_quantile_mcse``): for up to 16 probabilities ``probs``, each strictly inside (0, 1), a dict of
+    ``[nprobs, ncols]`` arrays ``quantile`` (by the rule of :func:`quantile_ranks` over the ``S = m h`` draws that belong to a chain),
+    ``ess`` (of the indicator ``x <= quantile``: the variogram estimator of :func:`convergence` on bit-packed indicator chains, whose lag
+    sums are popcounts), ``lower``, ``upper`` (the draws at the ends of the rank interval of :func:`quantile_mcse_ranks`; elements of the
+    chain), ``mcse = (upper - lower) / 2``, ``T`` and ``flags`` (as :func:`convergence_stats`; bit 2: the column holds a NaN and
+    everything of it is NaN), and ``m``, ``h``.  A constant or two-valued column, whose indicator is 1 everywhere, gives ``ess = mcse =
+    NaN`` and no error.  Chains and arguments as in :func:`convergence`; ``raw=True`` adds ``info``."""
+    p = _HostProvider(thetas, logdensities, first_sample, walkers, device)
+    r = quantile_mcse_raw_from(p, probs, split, p.logp is not None, max_lag)
+    return r if raw else quantile_mcse_columns(r)
+
+
 def add_rank_columns(cols, rank):
     """``cols`` of :func:`columns` with ``rhat_rank, ess_bulk, ess_tail`` of :func:`rank_columns` appended."""
     cols = dict(cols)

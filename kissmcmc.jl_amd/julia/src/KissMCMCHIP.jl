@@ -19,7 +19,7 @@ module KissMCMCHIP
 import KissMCMC
 import KissMCMC: emcee, metropolis, make_theta0s, squash_walkers     # extended (emcee, metropolis) / re-exported as they are
 
-export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, hdi, covariance, waic, pointwise_loglike, loo, compare_loo, relative_eff, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
+export emcee, make_theta0s, squash_walkers, metropolis, metropolis_chains, GaussianStep, HostProposal, int_acorr, quantiles, map_sample, histograms, corner, convergence, rank_convergence, rank_scores, quantile_mcse, hdi, covariance, waic, pointwise_loglike, loo, compare_loo, relative_eff, GaussianIso, Exponential, Rosenbrock, LogNormal, MvNormal2, ExprDensity, CDensity, DataDensity, HostLogPdf
 
 using LinearAlgebra: inv
 
@@ -760,6 +760,31 @@ function rank_convergence(thetas; logdensities=nothing, first_sample=0, walkers=
     return (rhat=cols[1], rhat_bulk=cols[2], rhat_folded=cols[3], ess_bulk=cols[4], ess_tail=cols[5], ess_q05=cols[6], ess_q95=cols[7],
             median=cols[8], q05=cols[9], q95=cols[10], lag=T, truncated=(flags .& Int32(2)) .!= 0, has_nan=(flags .& Int32(4)) .!= 0,
             m=m[], h=h[])
+end
+
+"""
+    quantile_mcse(thetas, probs; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+
+Quantiles of the pooled draws with their effective sample sizes and Monte-Carlo standard errors (Vehtari et al. 2021), from bit-packed
+indicator chains on the GPU (`kmc_chain_quantile_mcse`; the definitions are in include/kissmcmc_hip.h).  `probs`: 1 to 16 probabilities
+strictly inside (0, 1).  Returns a named tuple `(quantile, ess, mcse, lower, upper, lag, flags, m, h)` of `[column, probability]` arrays.
+"""
+function quantile_mcse(thetas, probs; logdensities=nothing, first_sample=0, walkers=nothing, split=true, max_lag=nothing, device=0)
+    chain, logp, ns, nw, nd = _summary_chain(thetas, logdensities)
+    mask = _summary_mask(walkers, nw)
+    ncols = nd + (logp === nothing ? 0 : 1)
+    pr = collect(Float64, probs)
+    cols = [Matrix{Float64}(undef, ncols, length(pr)) for _ in 1:5]          # column-major [column, probability] is the library's [nprobs][ncols]
+    T = Matrix{Int64}(undef, ncols, length(pr)); flags = Matrix{Int32}(undef, ncols, length(pr))
+    m = Ref{Int64}(0); h = Ref{Int64}(0)
+    st = ccall((:kmc_chain_quantile_mcse, LIB), Cint,
+               (Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int64, Ptr{UInt8}, Int32, Int64, Int32, Ptr{Float64}, Cint,
+                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+               chain, logp === nothing ? C_NULL : logp, ns, nw, nd, first_sample, mask === nothing ? C_NULL : mask, Int32(split ? 1 : 0),
+               max_lag === nothing ? 0 : (max_lag == 0 ? -1 : max_lag), Int32(length(pr)), pr, Cint(device),
+               cols[1], cols[2], cols[3], cols[4], cols[5], T, flags, m, h, C_NULL)
+    st == 0 || error("kmc_chain_quantile_mcse failed ($st): $(last_error())")
+    return (quantile=cols[1], ess=cols[2], mcse=cols[3], lower=cols[4], upper=cols[5], lag=T, flags=flags, m=m[], h=h[])
 end
 
 """

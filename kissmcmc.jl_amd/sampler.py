@@ -571,6 +571,21 @@ class Sampler:
         from .chain_convergence import rank_columns, sampler_rank_convergence_raw
         return rank_columns(sampler_rank_convergence_raw(self, first_sample, walkers, split, logp, max_lag))
 
+    def quantile_mcse(self, probs, first_sample: int = 0, walkers=None, split: bool = True, logp: bool = False, max_lag=None):
+        """Quantiles of the stored chain with their effective sample sizes and Monte-Carlo standard errors
+        (``kmc_sampler_quantile_mcse``): a dict of ``[nprobs, ncols]`` arrays ``quantile, ess, mcse, lower, upper, T, flags`` and ``m``,
+        ``h``; see :func:`kissmcmc_jl_amd.quantile_mcse`."""
+        from .chain_convergence import sampler_quantile_mcse
+        return sampler_quantile_mcse(self, probs, first_sample, walkers, split, logp, max_lag)
+
+    def indicator_lags(self, thresholds, lag0: int = 1, nlags: int = 0, first_sample: int = 0, walkers=None, split: bool = True,
+                       logp: bool = False):
+        """The bit-packed indicators ``x <= thresholds[nprobs, ncols]`` of the stored chain and their lag counts
+        (``kmc_sampler_indicator_lags``): a dict ``ones[nprobs, ncols, m], lagcount[nprobs, ncols, nlags], m, h``; see
+        :func:`kissmcmc_jl_amd.indicator_lags`."""
+        from .chain_convergence import sampler_indicator_lags
+        return sampler_indicator_lags(self, thresholds, lag0, nlags, first_sample, walkers, split, logp)
+
     def hdi(self, prob=0.94, first_sample: int = 0, walkers=None, logp: bool = False):
         """Highest-density intervals of the stored chain (with ``logp=True`` the stored log-densities are the last column), sorted and
         scanned on the device where it lies (``kmc_sampler_hdi``): a dict ``lo, hi, width, start, k, n, has_nan``, arrays ``[ncols]``
@@ -630,12 +645,13 @@ class Sampler:
         from .chain_predictive import sampler_pointwise_loglike
         return sampler_pointwise_loglike(self, first_sample, thin, walkers, obs, data)
 
-    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False, covariance=False, hdi=None):
+    def summary(self, theta_true=None, names=None, eff_samples=None, convergence=False, covariance=False, hdi=None, quantile_mcse=False):
         """:func:`kissmcmc_jl_amd.summarize_run` of the device chain: median and MAP sample (``mode``; None without ``store_logp``)
         from the device, mean and std from the streaming moments when the sampler keeps them, else from the downloaded chain;
         ``convergence=True`` adds the columns ``rhat, ess, mcse`` of :meth:`convergence`, ``convergence="rank"`` also
         ``rhat_rank, ess_bulk, ess_tail``; ``covariance=True`` adds the matrices ``cov`` and ``corr`` of :meth:`covariance`;
-        ``hdi=0.94`` adds the columns ``hdi_lo, hdi_hi`` of :meth:`hdi` for that probability."""
+        ``hdi=0.94`` adds the columns ``hdi_lo, hdi_hi`` of :meth:`hdi` for that probability; ``quantile_mcse=True`` adds the column
+        ``median_mcse`` of :meth:`quantile_mcse`."""
         from .summary import _SamplerProvider, quantiles_from, summary_columns
         p = _SamplerProvider(self)
         median = quantiles_from(p, [0.5])[0]
@@ -650,6 +666,8 @@ class Sampler:
             std = flat.std(axis=0, ddof=1) if flat.shape[0] > 1 else np.full(self.ndim, np.nan)
         conv = self.convergence(rank=convergence == "rank") if convergence else None
         cols = summary_columns(names, median, mean, std, mode, theta_true, eff_samples, conv, None if hdi is None else self.hdi(float(hdi)))
+        if quantile_mcse:
+            cols["median_mcse"] = self.quantile_mcse([0.5])["mcse"][0][:self.ndim]
         if covariance:
             c = self.covariance()
             cols.update(cov=c["cov"], corr=c["corr"])

@@ -420,7 +420,7 @@ def summary_columns(names, median, mean, std, mode=None, theta_true=None, eff_sa
 
 
 def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_samples=None, provider=None, device: int = 0,
-                  convergence=False, covariance=False, hdi=None):
+                  convergence=False, covariance=False, hdi=None, quantile_mcse=False):
     """Summary statistics of a run, reference ``src/analysis.jl:9-42`` (commented out there; followed as written): a dict of columns
     ``var`` (the names, ``"1" .. "ndim"`` by default), ``err = |theta_true - median|`` (only with ``theta_true``), ``median``,
     ``mean``, ``mode``, ``std`` (Julia's: n - 1 in the denominator) and ``eff_samples`` (only when given, passed through).
@@ -434,7 +434,8 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
     walker a chain; computed on the device); ``convergence="rank"`` also ``rhat_rank``, ``ess_bulk`` and ``ess_tail`` of
     :func:`kissmcmc_jl_amd.rank_convergence`.  ``covariance=True`` adds the matrices ``cov`` and ``corr`` of
     :func:`kissmcmc_jl_amd.covariance` (of the dimensions; summed on the device).  ``hdi=0.94`` adds the columns ``hdi_lo`` and
-    ``hdi_hi`` of :func:`kissmcmc_jl_amd.hdi` for that probability."""
+    ``hdi_hi`` of :func:`kissmcmc_jl_amd.hdi` for that probability.  ``quantile_mcse=True`` adds the column ``median_mcse``, the
+    Monte-Carlo standard error of the median of :func:`kissmcmc_jl_amd.quantile_mcse` (split chains, every walker a chain)."""
     th = np.asarray(thetas, dtype=np.float64)
     if th.ndim == 2:
         th = th[:, :, None]
@@ -452,6 +453,9 @@ def summarize_run(thetas, logdensities=None, theta_true=None, names=None, eff_sa
         conv = _convergence(th, device=device, rank=convergence == "rank")
     intervals = None if hdi is None else hdi_from(provider, float(hdi))
     cols = summary_columns(names, median, flat.mean(axis=0), std, mode, theta_true, eff_samples, conv, intervals)
+    if quantile_mcse:
+        from .chain_convergence import quantile_mcse as _quantile_mcse
+        cols["median_mcse"] = _quantile_mcse(th, [0.5], device=device)["mcse"][0]
     if covariance:
         from .chain_covariance import covariance as _covariance
         c = _covariance(th, device=device)
