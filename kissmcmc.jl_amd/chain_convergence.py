@@ -27,6 +27,15 @@ from .summary import _HostProvider, _SamplerProvider, _p
 COLUMNS = ("mean", "std", "rhat", "ess", "mcse", "lag", "truncated", "m", "h")
 
 
+def _stats_buffers(ncols):
+    """The per-column outputs of the statistics, and their pointers in the order of the C calls."""
+    out = {k: np.empty(ncols) for k in ("mean", "W", "B", "var_plus", "rhat", "ess", "mcse")}
+    out["T"] = np.empty(ncols, dtype=np.int64)
+    out["flags"] = np.empty(ncols, dtype=np.int32)
+    args = [_p(out[k], C.c_double) for k in ("mean", "W", "B", "var_plus", "rhat", "ess", "mcse")] + [_p(out["T"], C.c_int64), _p(out["flags"], C.c_int32)]
+    return out, args
+
+
 def convergence_stats(m: int, h: int, chain_mean, chain_var, lagsum, max_lag: int):
     """The host stage (``kmc_convergence_stats``; needs no device): from ``chain_mean[ncols, m]``, ``chain_var[ncols, m]`` and
     ``lagsum[ncols, nlags]`` (the lag sums ``D_1 .. D_nlags``) a dict of per-column arrays ``mean, W, B, var_plus, rhat, ess, mcse``,
@@ -38,12 +47,9 @@ def convergence_stats(m: int, h: int, chain_mean, chain_var, lagsum, max_lag: in
     if cm.ndim != 2 or cv.shape != cm.shape or lag.ndim != 2 or lag.shape[0] != cm.shape[0]:
         raise ValueError("chain_mean and chain_var must be [ncols, m], lagsum [ncols, nlags]")
     ncols = cm.shape[0]
-    out = {k: np.empty(ncols) for k in ("mean", "W", "B", "var_plus", "rhat", "ess", "mcse")}
-    out["T"] = np.empty(ncols, dtype=np.int64)
-    out["flags"] = np.empty(ncols, dtype=np.int32)
+    out, args = _stats_buffers(ncols)
     _lib.check(_lib.lib().kmc_convergence_stats(int(m), int(h), ncols, _p(cm, C.c_double), _p(cv, C.c_double), _p(lag, C.c_double), lag.shape[1],
-                                                int(max_lag), *[_p(out[k], C.c_double) for k in ("mean", "W", "B", "var_plus", "rhat", "ess", "mcse")],
-                                                _p(out["T"], C.c_int64), _p(out["flags"], C.c_int32)))
+                                                int(max_lag), *args))
     return out
 
 
@@ -100,11 +106,8 @@ def _raw(p, name, out, args, split, logp, max_lag):
 
 
 def _full_buffers(ncols):
-    out = {k: np.empty(ncols) for k in ("mean", "W", "B", "var_plus", "rhat", "ess", "mcse")}
-    out["T"] = np.empty(ncols, dtype=np.int64)
-    out["flags"] = np.empty(ncols, dtype=np.int32)
+    out, args = _stats_buffers(ncols)
     out["info"] = np.zeros(4, dtype=np.int64)
-    args = [_p(out[k], C.c_double) for k in ("mean", "W", "B", "var_plus", "rhat", "ess", "mcse")] + [_p(out["T"], C.c_int64), _p(out["flags"], C.c_int32)]
     return out, args
 
 

@@ -1,5 +1,5 @@
 // kmc_chain_view.hpp -- what the calls that read a stored chain where it lies share on the host side (kmc_summary.hip, kmc_hist.hip,
-// kmc_convergence.hip, kmc_rank.hip, kmc_hdi.hip, kmc_pointwise.hip, kmc_psis.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
+// kmc_convergence.hip, kmc_rank.hip, kmc_quantile.hip, kmc_hdi.hip, kmc_pointwise.hip, kmc_psis.hip): the view of a chain on the device, the selection (first_sample, walker mask) and the source of
 // such a view -- the chain a sampler holds, or a dense host chain uploaded for the call.  Internal.
 #pragma once
 #include "kmc_host.hpp"
@@ -97,10 +97,11 @@ struct ChainSource {
         }
         if (device < 0 || device >= ndev) return fail(KMC_ERR_BAD_ARG, "device ordinal out of range");
         HIP_TRY(hipSetDevice(device));
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+        size_t free_b = 0;
+        bool fits = false;
         const double need = (double)nsamples * (double)nwalkers * ((double)ndim + 1.0) * 8.0 + 64.0 * 1048576.0;
-        if (need > (double)free_b)
+        KMC_TRY(device_fits(need, &fits, &free_b));
+        if (!fits)
             return fail(KMC_ERR_UNSUPPORTED, "the chain (" + std::to_string((int64_t)(need / 1048576.0)) + " MiB with its work space) does not fit the device (" +
                                                  std::to_string(free_b >> 20) + " MiB free); streaming a host chain through the device is not built");
         const size_t rows = (size_t)nsamples * (size_t)nwalkers;

@@ -2,13 +2,14 @@
 // standard error of the mean (BDA3, Gelman et al. 2014, pp. 284-287; the evaluate_convergence and error_of_estimated_mean that reference
 // src/analysis.jl sketches).  Three stages: the device stage (kmc_sampler_lag_sums, kmc_chain_lag_sums: chain means, chain variances and
 // the lag sums of the variogram, read from the chain where it lies), the pure host stage (kmc_convergence_stats: everything else, in the
-// fixed order of DESIGN.md section 2) and the two in one call (kmc_sampler_convergence, kmc_chain_convergence).
+// fixed order of DESIGN.md section 2) and the two in one call (kmc_sampler_convergence, kmc_chain_convergence).  Every entry point is
+// its own argument checks between the steps of a ConvSession (kmc_convergence_host.hpp: describe, the chains of the request, open on
+// the stream of the source), then its stages; the lag-growth loop of the family (grow_lags) is here.
 // Kernels: kmc_convergence_kernels.hpp.
 #include <algorithm>
 #include <limits>
 #include <vector>
 
-#include "kmc_chain_view.hpp"
 #include "kmc_convergence_host.hpp"
 #include "kmc_convergence_kernels.hpp"
 
@@ -16,7 +17,7 @@ using namespace kmc_host;
 using namespace kmc_chain_view;
 using namespace kmc_conv;
 
-namespace kmc_conv_host {                  // (kmc_convergence_host.hpp: kmc_rank.hip runs the same stages on its transformed columns)
+namespace kmc_conv_host {                  // (kmc_convergence_host.hpp: kmc_rank.hip and kmc_quantile.hip run the same stages on their series)
 
 constexpr int64_t kConvDefaultMaxLag = 1024;
 constexpr int64_t kConvTargetWorkgroups = 2048;            // of conv_lag_partials and conv_moment_partials: 8 per compute unit
@@ -181,8 +182,7 @@ kmc_status lags_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, 
 kmc_status stats_check(int64_t m, int64_t h, int64_t ncols, const double* chain_mean, const double* chain_var, const double* lagsum, int64_t nlags,
                        int64_t max_lag, const StatsOut& o)
 {
-    if (!chain_mean || !chain_var || (!lagsum && nlags > 0) || !o.mean || !o.W || !o.B || !o.var_plus || !o.rhat || !o.ess || !o.mcse || !o.T || !o.flags)
-        return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (!chain_mean || !chain_var || (!lagsum && nlags > 0) || !o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
     if (ncols < 1) return fail(KMC_ERR_BAD_ARG, "need ncols >= 1");
     if (h < 4) return fail(KMC_ERR_BAD_ARG, "a chain needs at least 4 samples (h)");
     if (m < 2) return fail(KMC_ERR_BAD_ARG, "at least 2 chains are needed (m)");
@@ -234,37 +234,47 @@ void stats_host(int64_t m, int64_t h, int64_t ncols, const double* chain_mean, c
     }
 }
 
-// the whole thing on a view: chain moments once, then lag blocks until every column's rule has fired or max_lag is reached
-kmc_status convergence_device(ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, bool with_logp, int64_t max_lag,
-                              const StatsOut& o, int64_t* info)
+// the lag-growth loop (kmc_convergence_host.hpp)
+kmc_status grow_lags(int64_t nseries, int64_t max_lag, const LagFetch& fetch, const LagStats& stats, const int32_t* flags, int64_t* have_out)
 {
-    ScopedStream ss;                              // never the legacy stream (kmc_host.hpp: copy_sync)
-    HIP_TRY(ss.create());
-    KMC_TRY(upload_rank(b, mask_host, v.nl, ss.st));
-    return convergence_on_stream(b, v, sh, with_logp, max_lag, o, info, ss.st);
+    std::vector<double> lag, next;
+    int64_t have = 0;
+    for (;;) {
+        const int64_t want = std::min(max_lag, have == 0 ? (int64_t)kConvLagBlock : 2 * have);        // 32, 64, 128, ... lags in all
+        next.assign((size_t)(nseries * want), 0.0);
+        for (int64_t s = 0; s < nseries; ++s) std::copy(lag.begin() + s * have, lag.begin() + (s + 1) * have, next.begin() + s * want);
+        KMC_TRY(fetch(have + 1, want - have, next.data(), want, have));
+        lag.swap(next);
+        have = want;
+        KMC_TRY(stats(lag.data(), have));
+        bool more = false;
+        for (int64_t s = 0; s < nseries; ++s) more = more || (flags[s] & KMC_CONV_NEED_LAGS);
+        if (!more) break;                                      // (have == max_lag: the rule reports KMC_CONV_TRUNCATED instead)
+    }
+    *have_out = have;
+    return KMC_OK;
 }
 
-// ... on the caller's stream, with b.rank in place: a caller that runs many views of one shape keeps its stream and its buffers
+// the whole thing on a view, on the caller's stream, with b.rank in place: chain moments once, then lag blocks until every column's rule
+// has fired or max_lag is reached
 kmc_status convergence_on_stream(ConvBuffers& b, const ChainView& v, const ConvShape& sh, bool with_logp, int64_t max_lag, const StatsOut& o,
                                  int64_t* info, hipStream_t st)
 {
     const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
-    std::vector<double> cm((size_t)(ncols * sh.m)), cv((size_t)(ncols * sh.m)), lag, next;
+    std::vector<double> cm((size_t)(ncols * sh.m)), cv((size_t)(ncols * sh.m));
     KMC_TRY(moments_device(b, v, sh, with_logp, st, cm.data(), cv.data()));
     LagWork work;
     int64_t have = 0;
-    for (;;) {
-        const int64_t want = std::min(max_lag, have == 0 ? (int64_t)kConvLagBlock : 2 * have);        // 32, 64, 128, ... lags in all
-        next.assign((size_t)(ncols * want), 0.0);
-        for (int64_t c = 0; c < ncols; ++c) std::copy(lag.begin() + c * have, lag.begin() + (c + 1) * have, next.begin() + c * want);
-        KMC_TRY(lags_device(b, v, sh, with_logp, have + 1, want - have, st, next.data(), want, have, &work));
-        lag.swap(next);
-        have = want;
-        stats_host(sh.m, sh.h, ncols, cm.data(), cv.data(), lag.data(), have, max_lag, o);
-        bool more = false;
-        for (int64_t c = 0; c < ncols; ++c) more = more || (o.flags[c] & KMC_CONV_NEED_LAGS);
-        if (!more) break;                                      // (have == max_lag: the rule reports KMC_CONV_TRUNCATED instead)
-    }
+    KMC_TRY(grow_lags(
+        ncols, max_lag,
+        [&](int64_t lag0, int64_t nlags, double* block, int64_t stride, int64_t out0) {
+            return lags_device(b, v, sh, with_logp, lag0, nlags, st, block, stride, out0, &work);
+        },
+        [&](const double* block, int64_t nlags) {
+            stats_host(sh.m, sh.h, ncols, cm.data(), cv.data(), block, nlags, max_lag, o);
+            return KMC_OK;
+        },
+        o.flags, &have));
     if (info) {
         const int64_t elem = v.is_float ? 4 : 8;
         info[0] = have; info[1] = work.lag_blocks; info[2] = work.bytes_read;
@@ -292,38 +302,27 @@ namespace {
 kmc_status lag_sums(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t lag0, int64_t nlags,
                     double* chain_mean, double* chain_var, double* lagsum, int64_t* m_out, int64_t* h_out)
 {
-    ChainView v;
-    KMC_TRY(src.describe(&v));
+    ConvSession S(src);
+    KMC_TRY(S.describe());
     if ((chain_mean == nullptr) != (chain_var == nullptr)) return fail(KMC_ERR_BAD_ARG, "chain_mean and chain_var go together: both or neither");
     if (nlags > 0 && !lagsum) return fail(KMC_ERR_BAD_ARG, "null lagsum with nlags > 0");
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(check_lags(sh, lag0, nlags));
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    KMC_TRY(src.open(b, &v));
-    ScopedStream ss;
-    HIP_TRY(ss.create());
-    KMC_TRY(upload_rank(b, walker_mask, v.nl, ss.st));
-    if (chain_mean) KMC_TRY(moments_device(b, v, sh, src.with_logp, ss.st, chain_mean, chain_var));
-    return lags_device(b, v, sh, src.with_logp, lag0, nlags, ss.st, lagsum, nlags, 0, nullptr);
+    KMC_TRY(S.chains(first_sample, walker_mask, split != 0));
+    KMC_TRY(S.lags(lag0, nlags));
+    KMC_TRY(S.open(m_out, h_out));
+    if (chain_mean) KMC_TRY(moments_device(S.b, S.v, S.sh, S.with_logp, S.st(), chain_mean, chain_var));
+    return lags_device(S.b, S.v, S.sh, S.with_logp, lag0, nlags, S.st(), lagsum, nlags, 0, nullptr);
 }
 
 kmc_status convergence(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag, const StatsOut& o,
                        int64_t* m_out, int64_t* h_out, int64_t* info)
 {
-    ChainView v;
-    KMC_TRY(src.describe(&v));
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(resolve_max_lag(sh, &max_lag));
-    if (!o.mean || !o.W || !o.B || !o.var_plus || !o.rhat || !o.ess || !o.mcse || !o.T || !o.flags) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    KMC_TRY(src.open(b, &v));
-    return convergence_device(b, v, sh, walker_mask, src.with_logp, max_lag, o, info);
+    ConvSession S(src);
+    KMC_TRY(S.describe());
+    KMC_TRY(S.chains(first_sample, walker_mask, split != 0));
+    KMC_TRY(S.max_lag_from(max_lag));
+    if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
+    KMC_TRY(S.open(m_out, h_out));
+    return convergence_on_stream(S.b, S.v, S.sh, S.with_logp, S.max_lag, o, info, S.st());
 }
 
 }  // namespace

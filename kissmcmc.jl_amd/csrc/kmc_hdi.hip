@@ -1,21 +1,17 @@
 // kmc_hdi.hip -- highest-density intervals of a stored chain, scanned on the device: per column the narrowest interval that holds
 // k = floor(p N) + 1 consecutive draws of the sorted selection (ArviZ's unimodal rule with the ties and the special values pinned:
 // include/kissmcmc_hip.h).  Gather and sort are those of the rank statistics (kmc_rank_host.hpp), on an unsplit
-// shape; the scan over the sorted columns is here.  Kernels: kmc_hdi_kernels.hpp.
+// shape (the sorted-columns service of kmc_rank_host.hpp on a ConvSession opened unsplit: kmc_convergence_host.hpp); the scan over the
+// sorted columns is here.  Kernels: kmc_hdi_kernels.hpp.
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
 #include <limits>
 #include <vector>
 
-#include "kmc_chain_view.hpp"
 #include "kmc_hdi_kernels.hpp"
 #include "kmc_rank_host.hpp"
 
-using namespace kmc_host;
-using namespace kmc_chain_view;
-using namespace kmc_conv_host;
-using namespace kmc_rank_host;
+using namespace kmc_rank_host;                               // (and through it kmc_host, kmc_chain_view, kmc_conv_host)
 using namespace kmc_hdi;
 
 namespace {
@@ -25,22 +21,21 @@ struct HdiBuffers {
     ~HdiBuffers() { (void)hipFree(part); (void)hipFree(out); }
 };
 
-std::string num(double x)
+// the one check of a probability; `name`: what the message calls it
+kmc_status check_prob(double p, const std::string& name)
 {
-    char buf[40];
-    std::snprintf(buf, sizeof buf, "%.17g", x);
-    return buf;
+    if (!std::isfinite(p) || p <= 0.0 || p >= 1.0) return fail(KMC_ERR_BAD_ARG, "prob must be finite and lie in (0, 1) (" + name + " = " + num(p, "%.17g") + ")");
+    return KMC_OK;
 }
 
-// k = floor(p n) in double as written, and the refusals that need only n and p
+// k = floor(p n) in double as written, and the refusals that need n beside a checked p
 kmc_status span(int64_t n, double p, int64_t* k)
 {
-    if (!std::isfinite(p) || p <= 0.0 || p >= 1.0) return fail(KMC_ERR_BAD_ARG, "prob must be finite and lie in (0, 1) (prob = " + num(p) + ")");
     if (n < 2) return fail(KMC_ERR_BAD_ARG, "an interval needs at least 2 draws (N = " + std::to_string(n) + ")");
     if (n >= ((int64_t)1 << 31)) return fail(KMC_ERR_UNSUPPORTED, "2^31 draws or more per column (N = " + std::to_string(n) + ")");
     const int64_t kk = (int64_t)std::floor(p * (double)n);
-    if (kk < 1) return fail(KMC_ERR_BAD_ARG, "prob * N < 1: no draw besides the first lies in the interval (prob = " + num(p) + ", N = " + std::to_string(n) + ")");
-    if (kk > n - 1) return fail(KMC_ERR_BAD_ARG, "floor(prob * N) = N: no window is left (prob = " + num(p) + ", N = " + std::to_string(n) + ")");
+    if (kk < 1) return fail(KMC_ERR_BAD_ARG, "prob * N < 1: no draw besides the first lies in the interval (prob = " + num(p, "%.17g") + ", N = " + std::to_string(n) + ")");
+    if (kk > n - 1) return fail(KMC_ERR_BAD_ARG, "floor(prob * N) = N: no window is left (prob = " + num(p, "%.17g") + ", N = " + std::to_string(n) + ")");
     *k = kk;
     return KMC_OK;
 }
@@ -54,20 +49,17 @@ void launch_scan(const HdiArgs& a, int64_t ncols, hipStream_t st)
 kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask_host, const double* probs, int32_t nprob, double* lo, double* hi,
                int64_t* start, int64_t* n_out, int64_t* nan_count, int64_t* info)
 {
-    ChainView v;
-    KMC_TRY(src.describe(&v));
+    HdiBuffers hb;                                            // (before the session: the stream is drained before they go)
+    ConvSession S(src);
+    SortedColumns sc;                                         // (after it: the service drains the session's live stream itself)
+    KMC_TRY(S.describe());
     if (!probs || !lo || !hi || !start) return fail(KMC_ERR_BAD_ARG, "null argument");
     if (nprob < 1 || nprob > kHdiMaxProbs) return fail(KMC_ERR_BAD_ARG, "between 1 and 16 probabilities per call (nprob = " + std::to_string(nprob) + ")");
-    for (int p = 0; p < nprob; ++p)
-        if (!std::isfinite(probs[p]) || probs[p] <= 0.0 || probs[p] >= 1.0)
-            return fail(KMC_ERR_BAD_ARG, "prob must be finite and lie in (0, 1) (probs[" + std::to_string(p) + "] = " + num(probs[p]) + ")");
+    for (int p = 0; p < nprob; ++p) KMC_TRY(check_prob(probs[p], "probs[" + std::to_string(p) + "]"));
     int64_t N = 0;
-    KMC_TRY(selection_size(v, first_sample, mask_host, &N));
+    KMC_TRY(S.unsplit(first_sample, mask_host, &N));          // every selected walker one chain of all selected samples
     if (n_out) *n_out = N;
-    const bool with_logp = src.with_logp;
-    const int64_t ncols = v.ndim + (with_logp ? 1 : 0);
-    ConvShape sh;                                             // the unsplit shape: every selected walker one chain of all selected samples
-    sh.first = first_sample; sh.n = v.nsamples - first_sample; sh.nw = N / sh.n; sh.nhalf = 1; sh.h = sh.n; sh.m = sh.nw; sh.half_off = 0;
+    const int64_t ncols = S.ncols;
     HdiArgs a{};
     a.N = N; a.nprob = nprob;
     int64_t kmin = 0, windows = 0;
@@ -76,33 +68,20 @@ kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask
         kmin = p == 0 ? a.k[p] : std::min(kmin, a.k[p]);
         windows += N - a.k[p];
     }
-    KMC_TRY(rank_limits(sh, ncols));
+    KMC_TRY(rank_limits(S.sh, ncols));
     a.ntiles = (N - kmin + kHdiTileStarts - 1) / kHdiTileStarts;
     const size_t part_bytes = (size_t)ncols * (size_t)nprob * (size_t)a.ntiles * 2 * sizeof(uint64_t);
     const size_t out_bytes = (size_t)ncols * (size_t)nprob * 3 * sizeof(uint64_t);
 
-    ConvBuffers b;
-    KMC_TRY(src.open(b, &v));
-    KMC_TRY(rank_room(sh, ncols, 0, false, (double)part_bytes + (double)out_bytes));
-    RankBuffers rb;
-    HdiBuffers hb;
-    ScopedStream ss;                                          // (declared after the buffers: the stream is drained before they go)
-    HIP_TRY(src.stream(&ss));
-    const hipStream_t st = ss.get();
+    KMC_TRY(S.open(nullptr, nullptr));
+    const hipStream_t st = S.st();
     TimedEvents<4> ev;                                        // around the three stages, for info: gather, sort, scan + fold
     if (info) HIP_TRY(ev.create());
-    KMC_TRY(upload_rank(b, mask_host, v.nl, st));
-    KMC_TRY(rank_alloc(rb, ncols, N, false));
+    KMC_TRY(sc.sort(S, 0, false, (double)part_bytes + (double)out_bytes, info ? ev.e : nullptr));
     HIP_TRY(hipMalloc((void**)&hb.part, part_bytes));
     HIP_TRY(hipMalloc((void**)&hb.out, out_bytes));
-    a.keys = rb.key_a; a.part = hb.part; a.out = hb.out;
+    a.keys = sc.key_a; a.part = hb.part; a.out = hb.out;
 
-    std::vector<int64_t> nan;
-    if (info) HIP_TRY(hipEventRecord(ev.e[0], st));
-    KMC_TRY(gather(rb, b, v, sh, with_logp, false, st, &nan));
-    if (info) HIP_TRY(hipEventRecord(ev.e[1], st));
-    KMC_TRY(sort_columns(rb, ncols, N, st));
-    if (info) HIP_TRY(hipEventRecord(ev.e[2], st));
     if (nprob == 1) launch_scan<1>(a, ncols, st);
     else if (nprob <= 4) launch_scan<4>(a, ncols, st);
     else launch_scan<kHdiMaxProbs>(a, ncols, st);
@@ -116,11 +95,11 @@ kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask
 
     const double nan_v = std::numeric_limits<double>::quiet_NaN();
     for (int64_t c = 0; c < ncols; ++c) {
-        if (nan_count) nan_count[c] = nan[(size_t)c];
+        if (nan_count) nan_count[c] = sc.nan[(size_t)c];
         for (int p = 0; p < nprob; ++p) {
             const uint64_t* g = &got[(size_t)((c * nprob + p) * 3)];
             const int64_t at = (int64_t)p * ncols + c;
-            if (nan[(size_t)c] || g[0] == kHdiNone) {         // a NaN among the draws: no interval
+            if (sc.nan[(size_t)c] || g[0] == kHdiNone) {         // a NaN among the draws: no interval
                 lo[at] = hi[at] = nan_v;
                 start[at] = -1;
             } else {
@@ -143,6 +122,7 @@ kmc_status hdi(const ChainSource& src, int64_t first_sample, const uint8_t* mask
 KMC_EXPORT kmc_status kmc_hdi_span(int64_t n, double p, int64_t* k, int64_t* nwindows)
 {
     int64_t kk = 0;
+    KMC_TRY(check_prob(p, "prob"));
     KMC_TRY(span(n, p, &kk));
     if (k) *k = kk;
     if (nwindows) *nwindows = n - kk;

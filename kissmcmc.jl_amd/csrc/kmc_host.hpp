@@ -6,6 +6,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
@@ -157,6 +158,22 @@ inline kmc_status check_device_room(size_t need, const char* what)
     if (need > free_b)
         return fail(KMC_ERR_OOM, std::string(what) + " needs " + std::to_string(need >> 20) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB are free");
     return KMC_OK;
+}
+// The free bytes of the current device and whether `need` fits them, for the calls that refuse in their own words, with their own status
+// and margin.  A double: the need is a sum of products of sizes, formed before any of them is known to fit an integer.
+inline kmc_status device_fits(double need, bool* fits, size_t* free_b)
+{
+    size_t total_b = 0;
+    HIP_TRY(hipMemGetInfo(free_b, &total_b));
+    *fits = !(need > (double)*free_b);
+    return KMC_OK;
+}
+// a number in a message, by the printf format of the message's family ("%g", "%.17g")
+inline std::string num(double v, const char* fmt)
+{
+    char buf[40];
+    std::snprintf(buf, sizeof buf, fmt, v);
+    return buf;
 }
 // a private non-blocking stream for the duration of one call
 struct ScopedStream {

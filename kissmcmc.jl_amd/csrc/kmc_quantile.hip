@@ -2,37 +2,22 @@
 // Simpson, Carpenter and Buerkner 2021): the ess of the indicator x <= q_p, and the width of a Beta-distributed rank interval read off
 // the sorted draws (include/kissmcmc_hip.h).  The columns are sorted once by the sort of kmc_rank.hip; the
 // indicators are bit-packed series whose lag counts are popcounts (kmc_quantile_kernels.hpp); the statistics are kmc_convergence_stats,
-// the Beta quantile and the index rule are pure host stages (kmc_quantile_host.hpp).
+// the Beta quantile and the index rule are pure host stages (kmc_quantile_host.hpp).  The two entry points are their checks between the
+// steps of a ConvSession (kmc_convergence_host.hpp); the quantiles and the ends of the rank intervals come out of the sorted-columns
+// service (kmc_rank_host.hpp), the lag counts grow in the one loop of the family (grow_lags).
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
 #include <limits>
-#include <string>
 #include <vector>
 
-#include "kmc_chain_view.hpp"
-#include "kmc_convergence_host.hpp"
 #include "kmc_quantile_host.hpp"
 #include "kmc_quantile_kernels.hpp"
 #include "kmc_rank_host.hpp"
 
-using namespace kmc_host;
-using namespace kmc_chain_view;
-using namespace kmc_conv_host;
-using namespace kmc_rank_host;
+using namespace kmc_rank_host;                              // (and through it kmc_host, kmc_chain_view, kmc_conv_host)
 using namespace kmc_quantile;
 using namespace kmc_quantile_host;
 
 namespace {
-
-constexpr int64_t kFirstLags = 32;                          // the lag-doubling loop of kmc_sampler_convergence: 32, 64, 128, ... lags in all
-
-std::string num(double v)
-{
-    char buf[40];
-    std::snprintf(buf, sizeof buf, "%g", v);
-    return buf;
-}
 
 int64_t words_of(int64_t h) { return (h + kQindWordBits - 1) / kQindWordBits; }
 
@@ -44,7 +29,7 @@ kmc_status check_probs(int32_t nprobs, const double* probs, bool inside_unit)
     if (inside_unit)
         for (int32_t k = 0; k < nprobs; ++k)
             if (!(probs[k] > 0.0 && probs[k] < 1.0))
-                return fail(KMC_ERR_BAD_ARG, "probs[" + std::to_string(k) + "] = " + num(probs[k]) + ": a probability must be finite and lie strictly inside (0, 1)");
+                return fail(KMC_ERR_BAD_ARG, "probs[" + std::to_string(k) + "] = " + num(probs[k], "%g") + ": a probability must be finite and lie strictly inside (0, 1)");
     return KMC_OK;
 }
 
@@ -53,12 +38,7 @@ struct IndicatorBuffers {
     double* thr = nullptr;
     uint64_t* words = nullptr;
     unsigned long long *ones = nullptr, *counts = nullptr;
-    int64_t *pos = nullptr;
-    uint64_t* picked = nullptr;
-    ~IndicatorBuffers()
-    {
-        (void)hipFree(thr); (void)hipFree(words); (void)hipFree(ones); (void)hipFree(counts); (void)hipFree(pos); (void)hipFree(picked);
-    }
+    ~IndicatorBuffers() { (void)hipFree(thr); (void)hipFree(words); (void)hipFree(ones); (void)hipFree(counts); }
 };
 
 // bytes of the words, the counts of the ones, the lag counters and the thresholds
@@ -79,10 +59,14 @@ kmc_status indicator_alloc(IndicatorBuffers& ib, const ConvShape& sh, int64_t nc
 }
 
 // thresholds [nprobs][ncols] up, words and ones [nprobs][ncols][m] made; ones to the host
-kmc_status pack(IndicatorBuffers& ib, const ConvBuffers& b, const ChainView& v, const ConvShape& sh, bool with_logp, int32_t nprobs, const double* thr,
-                hipStream_t st, int64_t* ones)
+kmc_status pack(IndicatorBuffers& ib, const ConvSession& ses, int32_t nprobs, const double* thr, int64_t* ones)
 {
-    const int64_t ncols = v.ndim + (with_logp ? 1 : 0), nwords = words_of(sh.h);
+    const ChainView& v = ses.v;
+    const ConvShape& sh = ses.sh;
+    const ConvBuffers& b = ses.b;
+    const hipStream_t st = ses.st();
+    const bool with_logp = ses.with_logp;
+    const int64_t ncols = ses.ncols, nwords = words_of(sh.h);
     const size_t series = (size_t)nprobs * (size_t)ncols;
     HIP_TRY(copy_sync(ib.thr, thr, series * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(ib.ones, 0, series * (size_t)sh.m * sizeof(unsigned long long), st));
@@ -102,9 +86,9 @@ kmc_status pack(IndicatorBuffers& ib, const ConvBuffers& b, const ChainView& v, 
     return KMC_OK;
 }
 
-// counts[series * out_stride + out0 + k] = D_(lag0 + k), k < nlags; *words_read grows by the words the kernel loaded
+// counts[series * nlags + k] = D_(lag0 + k), k < nlags; *words_read grows by the words the kernel loaded
 kmc_status lag_counts(IndicatorBuffers& ib, const ConvShape& sh, int64_t ncols, int32_t nprobs, int64_t lag0, int64_t nlags, hipStream_t st,
-                      uint64_t* counts, int64_t out_stride, int64_t out0, int64_t* words_read)
+                      uint64_t* counts, int64_t* words_read)
 {
     if (nlags == 0) return KMC_OK;
     const int64_t nwords = words_of(sh.h), wpc = sh.m * nwords, series = (int64_t)nprobs * ncols;
@@ -116,39 +100,18 @@ kmc_status lag_counts(IndicatorBuffers& ib, const ConvShape& sh, int64_t ncols, 
     const int64_t nchunks = (wpc + kQindChunkWords - 1) / kQindChunkWords;
     hipLaunchKernelGGL(qind_lag_counts, dim3((unsigned)nchunks, (unsigned)ncols, (unsigned)nprobs), dim3(kQindThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
-    std::vector<unsigned long long> got((size_t)(series * nlags));
-    HIP_TRY(copy_sync(got.data(), ib.counts, got.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    for (int64_t s = 0; s < series; ++s)
-        for (int64_t k = 0; k < nlags; ++k) counts[s * out_stride + out0 + k] = got[(size_t)(s * nlags + k)];
+    HIP_TRY(copy_sync(counts, ib.counts, (size_t)(series * nlags) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (words_read) *words_read += series * wpc;
-    return KMC_OK;
-}
-
-// out[e] = the key at pos[e] of the sorted columns; every pos checked against the buffer
-kmc_status pick_at(IndicatorBuffers& ib, const uint64_t* sorted, int64_t total, const std::vector<int64_t>& pos, hipStream_t st, std::vector<uint64_t>* out)
-{
-    for (int64_t at : pos)
-        if (at < 0 || at >= total) return fail(KMC_ERR_HIP, "internal: an order statistic outside the sorted columns");
-    if (!ib.pos) {
-        HIP_TRY(hipMalloc((void**)&ib.pos, pos.size() * sizeof(int64_t)));
-        HIP_TRY(hipMalloc((void**)&ib.picked, pos.size() * sizeof(uint64_t)));
-    }
-    HIP_TRY(copy_sync(ib.pos, pos.data(), pos.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    PickAtArgs a{};
-    a.sorted = sorted; a.pos = ib.pos; a.out = ib.picked; a.n = (int64_t)pos.size();
-    hipLaunchKernelGGL(qind_pick, dim3((unsigned)((a.n + kQindThreads - 1) / kQindThreads)), dim3(kQindThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    out->resize(pos.size());
-    HIP_TRY(copy_sync(out->data(), ib.picked, pos.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     return KMC_OK;
 }
 
 kmc_status indicator_room(const ConvShape& sh, int64_t ncols, int32_t nprobs, int64_t nlags)
 {
     const double need = indicator_bytes(sh, ncols, nprobs, nlags) + 64.0 * 1048576.0;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (need > (double)free_b)
+    size_t free_b = 0;
+    bool fits = false;
+    KMC_TRY(device_fits(need, &fits, &free_b));
+    if (!fits)
         return fail(KMC_ERR_UNSUPPORTED, "the indicators of " + std::to_string(nprobs) + " probabilities, " + std::to_string(ncols) + " columns and " +
                                              std::to_string(sh.m) + " chains of " + std::to_string(sh.h) + " samples need " +
                                              std::to_string((int64_t)(need / 1048576.0)) + " MiB of device memory, " + std::to_string(free_b >> 20) + " MiB are free");
@@ -159,28 +122,19 @@ kmc_status indicator_room(const ConvShape& sh, int64_t ncols, int32_t nprobs, in
 kmc_status indicator_lags(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int32_t nprobs, const double* thr,
                           int64_t lag0, int64_t nlags, int64_t* ones, uint64_t* lagcount, int64_t* m_out, int64_t* h_out)
 {
-    ChainView v;
-    KMC_TRY(src.describe(&v));
+    IndicatorBuffers ib;                                      // (before the session: the stream is drained before they go)
+    ConvSession S(src);
+    KMC_TRY(S.describe());
     KMC_TRY(check_probs(nprobs, thr, false));
     if (!ones || (nlags > 0 && !lagcount)) return fail(KMC_ERR_BAD_ARG, "null argument");
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    if (lag0 < 1 || nlags < 0 || lag0 + nlags - 1 > sh.h - 1)
-        return fail(KMC_ERR_BAD_ARG, "the lags lag0 .. lag0 + nlags - 1 must lie in [1, h - 1] (h = " + std::to_string(sh.h) + ")");
-    const int64_t ncols = v.ndim + (src.with_logp ? 1 : 0);
-    KMC_TRY(rank_limits(sh, ncols));
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    KMC_TRY(src.open(b, &v));
-    KMC_TRY(indicator_room(sh, ncols, nprobs, nlags));
-    IndicatorBuffers ib;                                      // (declared before the stream: the stream is drained before they go)
-    ScopedStream ss;
-    HIP_TRY(src.stream(&ss));                                 // (a sampler's own, drained stream serves: kmc_chain_view.hpp)
-    KMC_TRY(upload_rank(b, walker_mask, v.nl, ss.get()));
-    KMC_TRY(indicator_alloc(ib, sh, ncols, nprobs, nlags));
-    KMC_TRY(pack(ib, b, v, sh, src.with_logp, nprobs, thr, ss.get(), ones));
-    return lag_counts(ib, sh, ncols, nprobs, lag0, nlags, ss.get(), lagcount, nlags, 0, nullptr);
+    KMC_TRY(S.chains(first_sample, walker_mask, split != 0));
+    KMC_TRY(S.lags(lag0, nlags));
+    KMC_TRY(rank_limits(S.sh, S.ncols));
+    KMC_TRY(S.open(m_out, h_out));
+    KMC_TRY(indicator_room(S.sh, S.ncols, nprobs, nlags));
+    KMC_TRY(indicator_alloc(ib, S.sh, S.ncols, nprobs, nlags));
+    KMC_TRY(pack(ib, S, nprobs, thr, ones));
+    return lag_counts(ib, S.sh, S.ncols, nprobs, lag0, nlags, S.st(), lagcount, nullptr);
 }
 
 // ---- the whole thing ----
@@ -191,48 +145,21 @@ struct QuantileOut {
     bool complete() const { return quantile && ess && mcse && lower && upper && T && flags; }
 };
 
-kmc_status quantile_mcse_device(const ChainSource& src, ConvBuffers& b, const ChainView& v, const ConvShape& sh, const uint8_t* mask_host, int64_t max_lag,
-                                int32_t nprobs, const double* probs, const QuantileOut& o, int64_t* info)
+kmc_status quantile_mcse_stage(IndicatorBuffers& ib, const ConvSession& ses, int32_t nprobs, const double* probs, const QuantileOut& o, int64_t* info)
 {
-    const bool with_logp = src.with_logp;
-    const int64_t ncols = v.ndim + (with_logp ? 1 : 0), S = sh.m * sh.h, series = (int64_t)nprobs * ncols;
+    SortedColumns sc;                                         // (dies before the session: it drains the session's live stream itself)
+    const ChainView& v = ses.v;
+    const ConvShape& sh = ses.sh;
+    const int64_t ncols = ses.ncols, S = sh.m * sh.h, series = (int64_t)nprobs * ncols, max_lag = ses.max_lag;
     const double nan_v = std::numeric_limits<double>::quiet_NaN();
-    KMC_TRY(rank_room(sh, ncols, 0, false, indicator_bytes(sh, ncols, nprobs, max_lag) + 32.0 * (double)series));
-    RankBuffers rb;
-    IndicatorBuffers ib;
-    ScopedStream ss;
-    HIP_TRY(src.stream(&ss));                                 // (a sampler's own, drained stream serves: kmc_chain_view.hpp)
-    const hipStream_t st = ss.get();
-    KMC_TRY(upload_rank(b, mask_host, v.nl, st));
-    KMC_TRY(rank_alloc(rb, ncols, S, false));
+    const hipStream_t st = ses.st();
+    KMC_TRY(sc.sort(ses, 0, false, indicator_bytes(sh, ncols, nprobs, max_lag) + 32.0 * (double)series));
     KMC_TRY(indicator_alloc(ib, sh, ncols, nprobs, max_lag));
-    std::vector<int64_t> nan;
-    KMC_TRY(gather(rb, b, v, sh, with_logp, false, st, &nan));
-    KMC_TRY(sort_columns(rb, ncols, S, st));
+    KMC_TRY(sc.quantiles(probs, nprobs, o.quantile));
 
-    // the quantiles, by the rule of the order statistics with N = S: two picks per (probability, column)
-    std::vector<int64_t> pos((size_t)(2 * series));
-    std::vector<double> frac((size_t)nprobs);
-    for (int32_t p = 0; p < nprobs; ++p) {
-        const double hq = probs[p] * (double)(S - 1), lo = std::floor(hq);
-        frac[(size_t)p] = hq - lo;
-        for (int64_t c = 0; c < ncols; ++c) {
-            pos[(size_t)(2 * (p * ncols + c))] = c * S + (int64_t)lo;
-            pos[(size_t)(2 * (p * ncols + c) + 1)] = c * S + std::min<int64_t>((int64_t)lo + 1, S - 1);
-        }
-    }
-    std::vector<uint64_t> got;
-    KMC_TRY(pick_at(ib, rb.key_a, ncols * S, pos, st, &got));
-    for (int32_t p = 0; p < nprobs; ++p)
-        for (int64_t c = 0; c < ncols; ++c) {
-            const size_t e = (size_t)(p * ncols + c);
-            const double x_lo = unkey(got[2 * e]), x_hi = unkey(got[2 * e + 1]);
-            o.quantile[e] = nan[(size_t)c] ? nan_v : (frac[(size_t)p] == 0.0 ? x_lo : x_lo + frac[(size_t)p] * (x_hi - x_lo));
-        }
-
-    // the indicators, their chain moments from the counts, and the lag counts in doubling blocks until every series' rule has fired
+    // the indicators, their chain moments from the counts, and the lag counts in the growing blocks of grow_lags until every series' rule has fired
     std::vector<int64_t> ones((size_t)(series * sh.m));
-    KMC_TRY(pack(ib, b, v, sh, with_logp, nprobs, o.quantile, st, ones.data()));
+    KMC_TRY(pack(ib, ses, nprobs, o.quantile, ones.data()));
     std::vector<double> mu(ones.size()), s2(ones.size());
     if ((size_t)sh.h < ones.size()) {                        // many chains: the moments of every count 0 .. h once, the same bits
         std::vector<double> tmu((size_t)sh.h + 1), ts2((size_t)sh.h + 1);
@@ -245,44 +172,44 @@ kmc_status quantile_mcse_device(const ChainSource& src, ConvBuffers& b, const Ch
         for (size_t i = 0; i < ones.size(); ++i) indicator_moments(sh.h, ones[i], &mu[i], &s2[i]);
     }
     std::vector<double> mean((size_t)series), W((size_t)series), B((size_t)series), vp((size_t)series), rhat((size_t)series), mc((size_t)series);
-    std::vector<uint64_t> cnt, next;
-    std::vector<double> D;
+    std::vector<uint64_t> cnt;
     int64_t have = 0, words_read = 0;
-    for (;;) {
-        const int64_t want = std::min(max_lag, have == 0 ? kFirstLags : 2 * have);
-        next.assign((size_t)(series * want), 0);
-        for (int64_t s = 0; s < series; ++s) std::copy(cnt.begin() + s * have, cnt.begin() + (s + 1) * have, next.begin() + s * want);
-        KMC_TRY(lag_counts(ib, sh, ncols, nprobs, have + 1, want - have, st, next.data(), want, have, &words_read));
-        cnt.swap(next);
-        have = want;
-        D.resize(cnt.size());
-        for (size_t i = 0; i < cnt.size(); ++i) D[i] = (double)cnt[i];
-        KMC_TRY(kmc_convergence_stats(sh.m, sh.h, series, mu.data(), s2.data(), D.data(), have, max_lag, mean.data(), W.data(), B.data(), vp.data(),
-                                      rhat.data(), o.ess, mc.data(), o.T, o.flags));
-        bool more = false;
-        for (int64_t s = 0; s < series; ++s) more = more || (o.flags[s] & KMC_CONV_NEED_LAGS);
-        if (!more) break;
-    }
+    KMC_TRY(grow_lags(
+        series, max_lag,
+        [&](int64_t lag0, int64_t nlags, double* block, int64_t stride, int64_t out0) {        // the counts are integers below 2^53: exact doubles
+            cnt.resize((size_t)(series * nlags));
+            KMC_TRY(lag_counts(ib, sh, ncols, nprobs, lag0, nlags, st, cnt.data(), &words_read));
+            for (int64_t s = 0; s < series; ++s)
+                for (int64_t k = 0; k < nlags; ++k) block[s * stride + out0 + k] = (double)cnt[(size_t)(s * nlags + k)];
+            return KMC_OK;
+        },
+        [&](const double* block, int64_t nlags) {
+            return kmc_convergence_stats(sh.m, sh.h, series, mu.data(), s2.data(), block, nlags, max_lag, mean.data(), W.data(), B.data(), vp.data(),
+                                         rhat.data(), o.ess, mc.data(), o.T, o.flags);
+        },
+        o.flags, &have));
 
     // the rank interval of every quantile, and its ends out of the sorted columns (still in key_a)
     std::vector<char> has((size_t)series, 0);
+    std::vector<int64_t> pos((size_t)(2 * series));
+    std::vector<uint64_t> got;
     for (int32_t p = 0; p < nprobs; ++p)
         for (int64_t c = 0; c < ncols; ++c) {
             const size_t e = (size_t)(p * ncols + c);
             pos[2 * e] = pos[2 * e + 1] = c * S;
-            if (nan[(size_t)c]) {
+            if (sc.nan[(size_t)c]) {
                 o.ess[e] = nan_v; o.T[e] = 0; o.flags[e] = KMC_CONV_HAS_NAN;
                 continue;
             }
             double qa, qb;
             int64_t i1, i2;
             if (!quantile_mcse_ranks(S, probs[p], o.ess[e], &qa, &qb, &i1, &i2))
-                return fail(KMC_ERR_UNSUPPORTED, "the Beta quantile did not converge for ess = " + num(o.ess[e]) + ", p = " + num(probs[p]));
+                return fail(KMC_ERR_UNSUPPORTED, "the Beta quantile did not converge for ess = " + num(o.ess[e], "%g") + ", p = " + num(probs[p], "%g"));
             if (i1 < 0) continue;
             has[e] = 1;
             pos[2 * e] = c * S + i1; pos[2 * e + 1] = c * S + i2;
         }
-    KMC_TRY(pick_at(ib, rb.key_a, ncols * S, pos, st, &got));
+    KMC_TRY(sc.pick_at(pos, &got));
     for (int64_t e = 0; e < series; ++e) {
         o.lower[e] = has[(size_t)e] ? unkey(got[(size_t)(2 * e)]) : nan_v;
         o.upper[e] = has[(size_t)e] ? unkey(got[(size_t)(2 * e + 1)]) : nan_v;
@@ -294,7 +221,7 @@ kmc_status quantile_mcse_device(const ChainSource& src, ConvBuffers& b, const Ch
         const int64_t elem = v.is_float ? 4 : 8;
         info[0] = have;
         info[1] = (int64_t)passes * 24 * ncols * S;                                                   // one sort: a pass reads the keys twice and writes them once
-        info[2] = sh.nhalf * sh.h * sh.nw * (v.ndim * elem + (with_logp ? 8 : 0));
+        info[2] = sh.nhalf * sh.h * sh.nw * (v.ndim * elem + (ses.with_logp ? 8 : 0));
         info[3] = words_read;
     }
     return KMC_OK;
@@ -303,19 +230,16 @@ kmc_status quantile_mcse_device(const ChainSource& src, ConvBuffers& b, const Ch
 kmc_status quantile_mcse(const ChainSource& src, int64_t first_sample, const uint8_t* walker_mask, int32_t split, int64_t max_lag, int32_t nprobs,
                          const double* probs, const QuantileOut& o, int64_t* m_out, int64_t* h_out, int64_t* info)
 {
-    ChainView v;
-    KMC_TRY(src.describe(&v));
+    IndicatorBuffers ib;                                      // (before the session: the stream is drained before they go)
+    ConvSession S(src);
+    KMC_TRY(S.describe());
     KMC_TRY(check_probs(nprobs, probs, true));
-    ConvShape sh;
-    KMC_TRY(conv_shape(v, first_sample, walker_mask, split != 0, &sh));
-    KMC_TRY(resolve_max_lag(sh, &max_lag));
-    KMC_TRY(rank_limits(sh, v.ndim + (src.with_logp ? 1 : 0)));
+    KMC_TRY(S.chains(first_sample, walker_mask, split != 0));
+    KMC_TRY(S.max_lag_from(max_lag));
+    KMC_TRY(rank_limits(S.sh, S.ncols));
     if (!o.complete()) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (m_out) *m_out = sh.m;
-    if (h_out) *h_out = sh.h;
-    ConvBuffers b;
-    KMC_TRY(src.open(b, &v));
-    return quantile_mcse_device(src, b, v, sh, walker_mask, max_lag, nprobs, probs, o, info);
+    KMC_TRY(S.open(m_out, h_out));
+    return quantile_mcse_stage(ib, S, nprobs, probs, o, info);
 }
 
 }  // namespace
@@ -324,21 +248,21 @@ kmc_status quantile_mcse(const ChainSource& src, int64_t first_sample, const uin
 KMC_EXPORT kmc_status kmc_beta_quantile(double prob, double A, double B, double* x)
 {
     if (!x) return fail(KMC_ERR_BAD_ARG, "null argument");
-    if (!(prob > 0.0 && prob < 1.0)) return fail(KMC_ERR_BAD_ARG, "prob = " + num(prob) + ": need 0 < prob < 1");
+    if (!(prob > 0.0 && prob < 1.0)) return fail(KMC_ERR_BAD_ARG, "prob = " + num(prob, "%g") + ": need 0 < prob < 1");
     if (!(A >= 1.0 && A <= std::numeric_limits<double>::max()) || !(B >= 1.0 && B <= std::numeric_limits<double>::max()))
-        return fail(KMC_ERR_BAD_ARG, "A = " + num(A) + ", B = " + num(B) + ": both must be finite and >= 1");
-    if (!beta_quantile(prob, A, B, x)) return fail(KMC_ERR_UNSUPPORTED, "the continued fraction did not converge for A = " + num(A) + ", B = " + num(B));
+        return fail(KMC_ERR_BAD_ARG, "A = " + num(A, "%g") + ", B = " + num(B, "%g") + ": both must be finite and >= 1");
+    if (!beta_quantile(prob, A, B, x)) return fail(KMC_ERR_UNSUPPORTED, "the continued fraction did not converge for A = " + num(A, "%g") + ", B = " + num(B, "%g"));
     return KMC_OK;
 }
 
 KMC_EXPORT kmc_status kmc_quantile_mcse_ranks(int64_t S, double p, double ess, double* a, double* b, int64_t* i1, int64_t* i2)
 {
     if (S < 1 || S >= ((int64_t)1 << 52)) return fail(KMC_ERR_BAD_ARG, "S = " + std::to_string(S) + ": need 1 <= S < 2^52");
-    if (!(p > 0.0 && p < 1.0)) return fail(KMC_ERR_BAD_ARG, "p = " + num(p) + ": a probability must be finite and lie strictly inside (0, 1)");
+    if (!(p > 0.0 && p < 1.0)) return fail(KMC_ERR_BAD_ARG, "p = " + num(p, "%g") + ": a probability must be finite and lie strictly inside (0, 1)");
     double qa, qb;
     int64_t r1, r2;
     if (!quantile_mcse_ranks(S, p, ess, &qa, &qb, &r1, &r2))
-        return fail(KMC_ERR_UNSUPPORTED, "the Beta quantile did not converge for ess = " + num(ess) + ", p = " + num(p));
+        return fail(KMC_ERR_UNSUPPORTED, "the Beta quantile did not converge for ess = " + num(ess, "%g") + ", p = " + num(p, "%g"));
     if (a) *a = qa;
     if (b) *b = qb;
     if (i1) *i1 = r1;

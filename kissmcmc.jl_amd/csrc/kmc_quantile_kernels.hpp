@@ -14,7 +14,6 @@
 //                     valid pairs, popcount.  Per workgroup the counts are folded in LDS (32-bit integer atomics) and added to the
 //                     64-bit counters [p][c][lag] by one integer atomic per lag: the totals are integers, so nothing depends on order,
 //                     geometry or how the lags are cut into calls.
-//   qind_pick         order statistics out of the sorted columns at a list of positions.
 //
 // No floating-point atomics anywhere.
 #pragma once
@@ -137,20 +136,6 @@ __global__ __launch_bounds__(kQindThreads) void qind_lag_counts(LagCountArgs a)
         if (tid < nlt && tb + tid < a.nlags && cnt[tid]) atomicAdd(&a.counts[pc * a.nlags + tb + tid], (unsigned long long)cnt[tid]);
         __syncthreads();
     }
-}
-
-// ---- order statistics out of the sorted columns, at given positions ----
-struct PickAtArgs {
-    const uint64_t* sorted;            // [ncols][S]
-    const int64_t* pos;                // [n]: c S + index, checked by the host
-    uint64_t* out;                     // [n]
-    int64_t n;
-};
-
-__global__ __launch_bounds__(kQindThreads) void qind_pick(PickAtArgs a)
-{
-    const int64_t e = (int64_t)blockIdx.x * kQindThreads + threadIdx.x;
-    if (e < a.n) a.out[e] = a.sorted[a.pos[e]];
 }
 
 }  // namespace kmc_quantile

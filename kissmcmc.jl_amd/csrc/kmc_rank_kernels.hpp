@@ -10,7 +10,8 @@
 //                     [ncols][S] buffers.  A pass is three kernels: the digit counts of every tile of kRankTileKeys keys (32-bit LDS
 //                     atomics, written to the tile's own slot), an exclusive scan over (digit, tile) per column, and a STABLE scatter.
 //                     The sorted column is unique, so nothing depends on the geometry or on arrival order; no atomics in the scatter.
-//   rank_pick         a few order statistics per column out of the sorted keys (the quantiles' neighbours).
+//   rank_select       order statistics out of the sorted keys at a list of positions (the quantiles' neighbours, the ends of a rank
+//                     interval).
 //   rank_score        for every draw in chain order: lower and upper bound in its sorted column by binary search (one shared path until
 //                     an equal key parts them), rank2 = #{y < x} + #{y <= x} + 1, the normal score z and, on request, the indicators
 //                     x <= q05, x <= q95; written into a scratch chain [sample][selected walker][column] of doubles, which the kernels of
@@ -288,21 +289,18 @@ __global__ __launch_bounds__(kRankThreads) void rank_sort_scatter(SortArgs a)
     }
 }
 
-// ---- order statistics out of the sorted columns ----
-constexpr int kRankPicks = 6;
-struct PickArgs {
+// ---- order statistics out of the sorted columns, at given positions ----
+struct SelectArgs {
     const uint64_t* sorted;            // [ncols][S]
-    uint64_t* out;                     // [ncols][6]
-    int64_t S, ncols;
-    int64_t at[kRankPicks];
+    const int64_t* pos;                // [n]: c S + index, checked by the host
+    uint64_t* out;                     // [n]
+    int64_t n;
 };
 
-__global__ __launch_bounds__(kRankThreads) void rank_pick(PickArgs a)
+__global__ __launch_bounds__(kRankThreads) void rank_select(SelectArgs a)
 {
     const int64_t e = (int64_t)blockIdx.x * kRankThreads + threadIdx.x;
-    if (e >= a.ncols * kRankPicks) return;
-    const int64_t c = e / kRankPicks;
-    a.out[e] = a.sorted[c * a.S + a.at[e - c * kRankPicks]];
+    if (e < a.n) a.out[e] = a.sorted[a.pos[e]];
 }
 
 // ---- score ----
