@@ -323,6 +323,14 @@ kmc_status  kmc_user_density_create(const char* term_expr, const char* pair_expr
  * as written; kmc_user_density_is_separable then returns 0 and kmc_sampler_describe says why).  Reference: the arbitrary closure pdf(theta), src/samplers.jl:257. */
 kmc_status  kmc_user_density_create_body(const char* body, kmc_user_density** out);
 int         kmc_user_density_is_separable(const kmc_user_density* ud);
+/* The gradient of a density made by kmc_user_density_create_body (not one with blobs), for the HMC step of kmc_metropolis_run
+ * (hmc_nleap > 0) and kmc_grad_eval_host: `grad_body` is the body of
+ *     void grad(const double* x, int n, const double* p, double* g)
+ * which writes d log p / d x_i to g[i]; g[0 .. n) is zero on entry.  Compiled once here, so a body that does not compile is
+ * KMC_ERR_BAD_ARG with the compiler's message (the previous gradient then stays); a later call replaces the gradient for every call
+ * that starts after it returns.  Nothing checks that it IS the gradient of the
+ * body: a wrong one costs acceptance, never correctness (compare kmc_grad_eval_host with differences of kmc_logpdf_eval_host). */
+kmc_status  kmc_user_density_set_grad(kmc_user_density* ud, const char* grad_body);
 /* ... returning a BLOB with the log-density -- the reference's `pdf(theta) -> (p, blob)` under hasblob=true
  * (src/samplers.jl:150-151, :194-196, :257) for device densities -- the body of
  *     double logpdf(const double* x, int n, const double* p, double* blob) { BODY }
@@ -623,6 +631,10 @@ kmc_status  kmc_logpdf_eval(const kmc_config* cfg, const double* pos_dev, double
 /* Same on dense host rows [nrows][ndim] (allocates, copies, evaluates, copies back). */
 kmc_status  kmc_logpdf_eval_host(const kmc_config* cfg, const double* pos_host, double* logp_host, int64_t nrows);
 
+/* grad[i] = the gradient of log pdf at pos[i] for dense host rows [nrows][ndim], evaluated on the device with the arithmetic of the
+ * HMC step (kmc_metropolis_config): a menu density, or a body density with kmc_user_density_set_grad; ndim <= 32. */
+kmc_status  kmc_grad_eval_host(const kmc_config* cfg, const double* pos_host, double* grad_host /* [nrows][ndim] */, int64_t nrows);
+
 /* ---- many-chain Metropolis: metropolis / _metropolis, reference src/samplers.jl:59-128 ----
  *
  * The reference's `metropolis(pdf, sample_ppdf, theta0; niter, nburnin, nthin)` is one serial Markov
@@ -655,7 +667,37 @@ kmc_status  kmc_logpdf_eval_host(const kmc_config* cfg, const double* pos_host, 
  * sample is drawn with one fixed proposal.  A boundary always ends a launch; apart from that results do not depend on how the
  * iteration range is cut, and a run stays a pure function of (seed, inputs).  With tune_rounds > 0 `step` / `chol` is the
  * INITIAL proposal, and a `step` is treated as diag(step) under the rule above from iteration 0 on (one arithmetic throughout).
- * Needs nchains > ndim, nburnin >= tune_rounds + 1, no host_propose. */
+ * Needs nchains > ndim, nburnin >= tune_rounds + 1, no host_propose.
+ *
+ * Hamiltonian Monte Carlo step (hmc_nleap = nleap >= 1; `step` holds the step sizes, a diagonal metric): a gradient-informed
+ * proposal from the SAME draws.  Iteration `it` of chain `c` has the normals z_0 .. z_{ndim-1} and the accept uniform u above, and
+ * j = w3 & 0xFFF of block 0 (the uniform uses w3 >> 12: nothing else reads these 12 bits).  Nothing more is drawn.
+ *   f    = 1.0 + jitter * (((double)j + 0.5) * 0x1p-11 - 1.0)       jitter = hmc_jitter in [0, 1); jitter == 0 gives f == 1.0 exactly
+ *   e_i  = step_i * f ;   h_i = 0.5 * e_i
+ *   m    = z ;            K0 = 0.5 * ((m_0 m_0 + m_1 m_1) + ...)     i ascending
+ *   y    = x ;            g  = grad(y)
+ *   nleap times:   m_i = m_i + h_i * g_i ;  y_i = y_i + e_i * m_i  (every i) ;  g = grad(y) ;  m_i = m_i + h_i * g_i
+ *   p1   = logpdf(y) ;    K1 as K0 from the final m
+ *   accept  iff  (p1 - K1) - (p0 - K0) > log u                       strict, as src/samplers.jl:101
+ * Every product and every sum is rounded to double on its own: NO fused multiply-add.  logpdf is the density's evaluation as
+ * everywhere else, so a stored chain_logp entry has the bits kmc_logpdf_eval gives for that stored position.  grad is a pure function
+ * of the position: for a menu density the gradient below, for a runtime-compiled body density the body given to
+ * kmc_user_density_set_grad.  A non-finite gradient or log-density is not an error: NaN or inf propagates and the strict comparison
+ * rejects (a divergent trajectory is a rejected proposal); p0 = -inf at the start is carried as the reference carries it, and the
+ * first finite proposal is then accepted.  Counters, burn-in, thinning, storage and moments are those of the random walk; a chain's
+ * result stays a pure function of (seed, chain index, inputs).  The iteration range is cut into launches of max(1, 65536 / nleap)
+ * iterations, and never takes the few-chains table route.
+ * Gradients of the menu densities (p = the digested parameters the kernels take; the operation order is fixed in kmc_hmc.hpp):
+ *   KMC_GAUSSIAN_ISO  (p0 = mu, p1 = 1 / sigma)        t = (x_i - p0) * p1;  g_i = -(t * p1)
+ *   KMC_EXPONENTIAL   (p0 = rate)                      g_i = -p0, outside the support as well
+ *   KMC_ROSENBROCK    (a, b, s = p0, p1, p2 = 1/scale) acc = 0.0;  k >= 1: d = x_k - x_{k-1} * x_{k-1}, acc = (2.0 * b) * d;
+ *                                                      k <= n - 2: d = x_{k+1} - x_k * x_k, acc = acc - ((4.0 * b) * x_k) * d,
+ *                                                      acc = acc - 2.0 * (a - x_k);   g_k = -(acc * s)
+ *   KMC_LOGNORMAL     (p0 = mu, p1 = sigma)            x_i > 0: lx = log(x_i), t = (lx - p0) / p1, g_i = -((1.0 + t / p1) / x_i);
+ *                                                      otherwise g_i = 0.0
+ *   KMC_MVNORMAL2     (d0 = x_0 - p0, d1 = x_1 - p1)   g_0 = -(p2 * d0 + p3 * d1);  g_1 = -(p3 * d0 + p4 * d1)
+ * Not with chol, tune_rounds > 0, host_propose, KMC_HOST_DENSITY, a runtime-compiled density without a gradient or of the term / pair
+ * form, a density with blobs, or ndim > 32 (the chain lives in registers). */
 typedef struct kmc_metropolis_config {
     int32_t  dtype;         /* KMC_F64 */
     int32_t  density;       /* kmc_density (menu or KMC_USER_DENSITY) */
@@ -684,6 +726,9 @@ typedef struct kmc_metropolis_config {
                                is non-NULL (neither with host_propose) */
     int32_t  tune_rounds;   /* R >= 0: tuning boundaries during burn-in (0: none) */
     double   tune_scale;    /* 0: the default 2.38 / sqrt(ndim) */
+    int32_t  hmc_nleap;     /* 0: off (the random walk above); 1 .. 1024: the HMC step, leapfrog steps per iteration; `step` then
+                               holds the step sizes, every one finite and > 0 */
+    double   hmc_jitter;    /* in [0, 1): the relative half-width of the per-iteration step-size jitter (0 without hmc_nleap) */
 } kmc_metropolis_config;
 
 typedef struct kmc_metropolis_outputs {

@@ -11,7 +11,7 @@ from . import _lib
 from ._lib import KmcError
 from .api import emcee, emcee_counts, make_theta0s, squash_walkers
 from .densities import (CDensity, DataDensity, DeviceLogPdf, Exponential, ExprDensity, GaussianIso, HostLogPdf, LogNormal, MvNormal2,
-                        Rosenbrock)
+                        Rosenbrock, check_grad, grad)
 from .chain_convergence import convergence, convergence_stats, error_of_estimated_mean, evaluate_convergence, lag_sums, samples_vs_tau
 from .chain_convergence import normal_scores, rank_convergence, rank_plan, rank_scores
 from .chain_convergence import beta_quantile, indicator_lags, indicator_moments, indicator_plan, quantile_mcse, quantile_mcse_ranks
@@ -20,7 +20,7 @@ from .chain_predictive import compare_waic, pointwise_loglike, pointwise_plan, p
 from .chain_loo import compare_loo, loo, loo_stats, pointwise_weights, psis_plan, psis_smooth, psis_tail, relative_eff
 from .diagnostics import eff_samples, int_acorr
 from .moves import DEMove, DESnookerMove
-from .metropolis import GaussianStep, HostProposal, MVNormalStep, TunedStep, cholesky_lower, metropolis, metropolis_chains
+from .metropolis import GaussianStep, HMCStep, HostProposal, MVNormalStep, TunedStep, cholesky_lower, metropolis, metropolis_chains
 from .sampler import Sampler
 from .summary import corner, credible_levels, hdi, hdi_span, hist_mode, histogram, map_sample, quantile_ranks, quantiles, summarize_run
 from .tempering import geometric_betas, thermodynamic_integration
@@ -28,7 +28,7 @@ from .tempering import geometric_betas, thermodynamic_integration
 __all__ = [
     "emcee", "make_theta0s", "squash_walkers", "emcee_counts", "Sampler", "KmcError",
     "DeviceLogPdf", "GaussianIso", "Exponential", "Rosenbrock", "LogNormal", "MvNormal2", "ExprDensity", "CDensity", "DataDensity", "HostLogPdf",
-    "DEMove", "DESnookerMove", "geometric_betas", "thermodynamic_integration", "cdf_g_inv", "g_pdf", "metropolis", "metropolis_chains", "GaussianStep", "HostProposal", "MVNormalStep", "TunedStep", "cholesky_lower", "int_acorr", "eff_samples",
+    "DEMove", "DESnookerMove", "geometric_betas", "thermodynamic_integration", "cdf_g_inv", "g_pdf", "metropolis", "metropolis_chains", "GaussianStep", "HostProposal", "MVNormalStep", "TunedStep", "HMCStep", "grad", "check_grad", "cholesky_lower", "int_acorr", "eff_samples",
     "quantiles", "quantile_ranks", "map_sample", "summarize_run", "histogram", "corner", "hist_mode", "credible_levels",
     "convergence", "convergence_stats", "lag_sums", "evaluate_convergence", "error_of_estimated_mean", "samples_vs_tau",
     "rank_convergence", "rank_scores", "rank_plan", "normal_scores",

@@ -72,6 +72,7 @@ SYMBOLS = [
     "kmc_pointwise_plan", "kmc_waic_stats",
     "kmc_sampler_psis_loo", "kmc_chain_psis_loo", "kmc_sampler_psis_tail", "kmc_chain_psis_tail", "kmc_psis_plan", "kmc_loo_stats",
     "kmc_psis_smooth_host",
+    "kmc_user_density_set_grad", "kmc_grad_eval_host",
     "kmc_sampler_relative_eff", "kmc_chain_relative_eff", "kmc_sampler_pointwise_weights", "kmc_chain_pointwise_weights",
     "kmc_sampler_psis_loo_reff", "kmc_chain_psis_loo_reff", "kmc_sampler_psis_tail_reff", "kmc_chain_psis_tail_reff",
 ]
@@ -165,6 +166,8 @@ class MetropolisConfig(C.Structure):
         ("chol", C.POINTER(C.c_double)),
         ("tune_rounds", C.c_int32),
         ("tune_scale", C.c_double),
+        ("hmc_nleap", C.c_int32),       # 0: off; leapfrog steps per iteration of the HMC step (`step` then holds the step sizes)
+        ("hmc_jitter", C.c_double),     # in [0, 1)
     ]
 
 
@@ -274,6 +277,8 @@ def lib() -> C.CDLL:
     L.kmc_logpdf_eval_host.argtypes = [cfgp, dp, dp, C.c_int64]
     L.kmc_user_density_create.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp)]
     L.kmc_user_density_create_body.argtypes = [C.c_char_p, C.POINTER(vp)]
+    L.kmc_user_density_set_grad.argtypes = [vp, C.c_char_p]
+    L.kmc_grad_eval_host.argtypes = [cfgp, dp, dp, C.c_int64]
     L.kmc_user_density_create_body_blob.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
     L.kmc_data_density_create.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_int64, C.c_int32, C.POINTER(vp)]
     L.kmc_user_density_is_separable.restype = C.c_int

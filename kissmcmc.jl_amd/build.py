@@ -8,10 +8,10 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libkissmcmc_hip.so")
-SOURCES = ["kmc_sampler.hip", "kmc_validate.hip", "kmc_describe.hip", "kmc_plan.hip", "kmc_launch.hip", "kmc_updated.hip", "kmc_state.hip", "kmc_copy.hip", "kmc_rtc.hip", "kmc_p2p.hip", "kmc_metropolis_api.hip", "kmc_acorr.hip", "kmc_summary.hip", "kmc_hist.hip", "kmc_convergence.hip", "kmc_rank.hip", "kmc_quantile.hip", "kmc_hdi.hip", "kmc_cov.hip", "kmc_pointwise.hip", "kmc_psis.hip", "kmc_pointwise_stages.hip", "kmc_rccl.hip", "kmc_diag.hip", "kmc_inst_host.hip", "kmc_inst_host_temper.hip", "kmc_inst_host_temper_snooker.hip", "kmc_data.hip"] + \
+SOURCES = ["kmc_sampler.hip", "kmc_validate.hip", "kmc_describe.hip", "kmc_plan.hip", "kmc_launch.hip", "kmc_updated.hip", "kmc_state.hip", "kmc_copy.hip", "kmc_rtc.hip", "kmc_p2p.hip", "kmc_metropolis_api.hip", "kmc_acorr.hip", "kmc_summary.hip", "kmc_hist.hip", "kmc_convergence.hip", "kmc_rank.hip", "kmc_quantile.hip", "kmc_hdi.hip", "kmc_cov.hip", "kmc_pointwise.hip", "kmc_psis.hip", "kmc_pointwise_stages.hip", "kmc_rccl.hip", "kmc_diag.hip", "kmc_inst_host.hip", "kmc_inst_host_temper.hip", "kmc_inst_host_temper_snooker.hip", "kmc_inst_hmc.hip", "kmc_data.hip"] + \
           [f"kmc_inst_{d}{part}.hip" for part in ("", "_var", "_p2p", "_lds", "_spec", "_share", "_de", "_snooker", "_temper", "_temper_snooker") for d in ("lognormal", "exponential", "gaussian_iso", "rosenbrock", "mvnormal2")
            if (part, d) != ("_share", "mvnormal2")]   # (longest jobs first; mvnormal2 rows are one lane wide: nothing to share)
-HEADERS = ["kmc_psis_fit.hpp", "kmc_host.hpp", "kmc_sampler.hpp", "kmc_device.hpp", "kmc_kernels.hpp", "kmc_islands.hpp", "kmc_generation.hpp", "kmc_copy_kernels.hpp", "kmc_summary_kernels.hpp", "kmc_hist_kernels.hpp", "kmc_convergence_kernels.hpp", "kmc_convergence_host.hpp", "kmc_rank_kernels.hpp", "kmc_rank_host.hpp", "kmc_quantile_kernels.hpp", "kmc_quantile_host.hpp", "kmc_hdi_kernels.hpp", "kmc_cov_kernels.hpp", "kmc_chain_view.hpp", "kmc_chain_kernels.hpp", "kmc_metropolis.hpp", "kmc_tables.hpp", "kmc_shared_draws.hpp", "kmc_recognise.hpp", "kmc_data.hpp", "kmc_pointwise.hpp", "kmc_pointwise_host.hpp", os.path.join("..", "..", "include", "kissmcmc_hip.h")]
+HEADERS = ["kmc_psis_fit.hpp", "kmc_host.hpp", "kmc_sampler.hpp", "kmc_device.hpp", "kmc_kernels.hpp", "kmc_islands.hpp", "kmc_generation.hpp", "kmc_copy_kernels.hpp", "kmc_summary_kernels.hpp", "kmc_hist_kernels.hpp", "kmc_convergence_kernels.hpp", "kmc_convergence_host.hpp", "kmc_rank_kernels.hpp", "kmc_rank_host.hpp", "kmc_quantile_kernels.hpp", "kmc_quantile_host.hpp", "kmc_hdi_kernels.hpp", "kmc_cov_kernels.hpp", "kmc_chain_view.hpp", "kmc_chain_kernels.hpp", "kmc_metropolis.hpp", "kmc_hmc.hpp", "kmc_tables.hpp", "kmc_shared_draws.hpp", "kmc_recognise.hpp", "kmc_data.hpp", "kmc_pointwise.hpp", "kmc_pointwise_host.hpp", os.path.join("..", "..", "include", "kissmcmc_hip.h")]
 # kernarg preload: the half-step kernels' leading scalar parameters arrive in SGPRs at wave launch (kmc_kernels.hpp)
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",

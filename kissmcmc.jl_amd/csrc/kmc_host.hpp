@@ -299,6 +299,7 @@ struct kmc_user_density {
     std::string body;                                // kmc_user_density_create_body: the whole function body instead of term / pair
     bool is_body = false;
     int nblob = 0;                                   // kmc_user_density_create_body_blob: doubles the body writes to blob[] per evaluation
+    std::string grad_body;                           // kmc_user_density_set_grad: the body of its gradient (the HMC step; under `mu`)
     // A body of the form  `double s = 0; for (int i = 0; i < n; ++i) s += f(x[i]);  return g(s);`  (optionally with the neighbour
     // x[i + 1] and the bound i + 1 < n) is a sum over elements: kmc_user_density_create_body recognises it (kmc_rtc.hip:
     // recognise_separable) and the samplers then run it in the lane-striped vector kernels like a term / pair density, with g as

@@ -1,8 +1,9 @@
 // kmc_metropolis_api.hip -- host side of the many-chain Metropolis entry points of include/kissmcmc_hip.h
 // (kmc_metropolis_validate / kmc_metropolis_run; kernels: kmc_metropolis.hpp).  kmc_metropolis_run is six steps: the argument checks
 // and validate, the device, metropolis_density_params, metropolis_setup (one MetroRun: the facts of the config, the stream, one
-// MetroBuffers), one route -- metropolis_host_route (caller's closures, an iteration per pass) or metropolis_device_route
-// (metropolis_device_setup, metropolis_select_kernels, then metropolis_launch_stretch per launch) -- and metropolis_read_out.
+// MetroBuffers), one route -- metropolis_host_route (caller's closures, an iteration per pass), metropolis_device_route
+// (metropolis_device_setup, metropolis_select_kernels, then metropolis_launch_stretch per launch) or metropolis_hmc_route (the HMC step,
+// kmc_hmc.hpp) -- and metropolis_read_out.  Also here: kmc_user_density_set_grad and kmc_grad_eval_host.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -14,6 +15,7 @@
 #define KMC_DEFINE_METROPOLIS_KERNELS
 #include "kmc_host.hpp"
 #include "kmc_chain_view.hpp"
+#include "kmc_hmc.hpp"
 
 using namespace kmc;
 using namespace kmc_host;
@@ -48,6 +50,55 @@ kmc_status compile_user_metropolis(kmc_user_density* ud, int ND, const std::vect
         if (TND > 0)
             src << "extern \"C\" __global__ __launch_bounds__(128) void kmc_user_metropolis_tabled(const kmc::MetropolisTabledArgs t) { "
                 << "kmc::metropolis_chains_tabled_body<UD, " << TND << ">(t.a, t.draws, t.nsteps); }\n";
+        *text = src.str();
+        return KMC_OK;
+    }, out);
+}
+
+// A body density with a gradient (kmc_user_density_set_grad): the functor of its two bodies, and the module of the HMC step for one
+// ndim -- a template constant there (as for a data density), so that a body's `for (i < n)` unrolls and its arrays stay in registers.
+constexpr int64_t kHmcMaxDim = 32;                // the chain lives in registers (kmc_hmc.hpp)
+constexpr int32_t kHmcMaxLeap = 1024;
+
+std::string hmc_functor_source(const kmc_user_density* ud, const std::string& grad_body)
+{
+    std::ostringstream src;
+    src << "namespace {\nstruct UserB {\n"
+        << "  __device__ static double eval(const double* x, int n, const double* p) { (void)x; (void)n; (void)p;\n" << ud->body << "\n  }\n"
+        << "  __device__ static void grad(const double* x, int n, const double* p, double* g) { (void)x; (void)n; (void)p; (void)g;\n" << grad_body << "\n  }\n};\n}\n";
+    return src.str();
+}
+
+const RtcModule& hmc_rtc_module()
+{
+    static const RtcModule m{"user density", "kmc_user_hmc.hip", {"kmc_kernels.hpp", "kmc_device.hpp", "kmc_metropolis.hpp", "kmc_hmc.hpp"}, rtc_options()};
+    return m;
+}
+
+// The identity of a gradient body in the keys of a density's code objects: FNV-1a over its text, and its length.
+std::string hmc_grad_id(const std::string& grad_body)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (const unsigned char ch : grad_body) h = (h ^ ch) * 0x100000001b3ull;
+    char buf[48];
+    std::snprintf(buf, sizeof(buf), "%016llx.%zu", (unsigned long long)h, grad_body.size());
+    return buf;
+}
+
+// The code object of the density's CURRENT gradient for one ndim, under the key "hmc:<gradient id>:<ndim>".  Code objects are never
+// erased from ud->code -- shared_module keys the loaded modules by their addresses -- so a replaced gradient's entries stay, unused,
+// and the body read here is the one the key names whatever another thread sets meanwhile.
+kmc_status compile_user_hmc(kmc_user_density* ud, int64_t ndim, const std::vector<char>** out)
+{
+    std::string grad_body;
+    { std::lock_guard<std::mutex> lock(ud->mu); grad_body = ud->grad_body; }
+    return compile_keyed(ud, "hmc:" + hmc_grad_id(grad_body) + ":" + std::to_string(ndim), hmc_rtc_module(), [&](std::string* text) {
+        std::ostringstream src;
+        src << "#include \"kmc_kernels.hpp\"\n#include \"kmc_hmc.hpp\"\n" << hmc_functor_source(ud, grad_body)
+            << "using UD = kmc::BodyGradDensity<UserB, " << ndim << ">;\n"
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_logpdf(const kmc::LogpdfArgs a) { kmc::logpdf_rows_body<UD>(a); }\n"
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_hmc(const kmc::HmcArgs h) { kmc::metropolis_hmc_body<UD, " << ndim << ", true>(h); }\n"
+            << "extern \"C\" __global__ __launch_bounds__(256) void kmc_user_grad(const kmc::GradArgs a) { kmc::grad_rows_body<UD, " << ndim << ", true>(a); }\n";
         *text = src.str();
         return KMC_OK;
     }, out);
@@ -477,17 +528,16 @@ kmc_status metropolis_device_setup(MetroRun& R)
 }
 
 // the iterations [it0, it1) of every chain in the device route: the draw table first (and L applied to it) on the few-chains route, then one kernel
-kmc_status metropolis_launch_stretch(const MetroRun& R, const MetroKernels& k, int64_t it0, int64_t it1)
+// the kernel arguments of the iterations [it0, it1) of every chain, `step` aside
+MetropolisArgs metropolis_stretch_args(const MetroRun& R, int64_t it0, int64_t it1)
 {
     const kmc_metropolis_config* c = R.c;
     const MetroBuffers& b = R.b;
-    const hipStream_t st = R.ss.st;
-    const int64_t nc = R.nc;
     MetropolisArgs a{};
     a.pos = b.pos; a.logp = b.logp; a.naccept = b.naccept;
     a.chain = b.chain; a.chain_logp = b.chain_logp; a.csum = b.csum; a.csumsq = b.csumsq;
-    a.step = (R.sh.on && !k.tabled) ? b.chol : b.step; a.xt = b.xt; a.yt = b.yt; a.st1 = b.st1; a.st2 = b.st2;
-    a.nchains = nc;
+    a.xt = b.xt; a.yt = b.yt; a.st1 = b.st1; a.st2 = b.st2;
+    a.nchains = R.nc;
     a.it0 = it0; a.it1 = it1;
     a.nburnin = c->nburnin; a.nthin = c->nthin; a.nsamples = R.nsamples;
     const int64_t npos = it0 - c->nburnin;          // steps with n > 0 taken before it0
@@ -497,6 +547,16 @@ kmc_status metropolis_launch_stretch(const MetroRun& R, const MetroKernels& k, i
     a.seed_lo = (uint32_t)c->seed; a.seed_hi = (uint32_t)(c->seed >> 32);
     a.dp = R.dp;
     a.blob = b.blob; a.chain_blob = b.chain_blob;
+    return a;
+}
+
+kmc_status metropolis_launch_stretch(const MetroRun& R, const MetroKernels& k, int64_t it0, int64_t it1)
+{
+    const MetroBuffers& b = R.b;
+    const hipStream_t st = R.ss.st;
+    const int64_t nc = R.nc;
+    MetropolisArgs a = metropolis_stretch_args(R, it0, it1);
+    a.step = (R.sh.on && !k.tabled) ? b.chol : b.step;
     if (!k.tabled) {
         if (k.ufn) HIP_TRY(launch_module(k.ufn, R.grid, 256u, st, a));
         else {
@@ -577,6 +637,84 @@ kmc_status metropolis_device_route(MetroRun& R)
     return KMC_OK;
 }
 
+// The HMC route (hmc_nleap > 0; kmc_hmc.hpp): one chain per lane in registers, whatever the number of chains -- the draws of an iteration
+// are amortised over the trajectory, so there is no few-chains table -- in launches of max(1, 65536 / nleap) iterations.
+kmc_status metropolis_hmc_route(MetroRun& R)
+{
+    const kmc_metropolis_config* c = R.c;
+    MetroBuffers& b = R.b;
+    const hipStream_t st = R.ss.st;
+    // (room for 32 step sizes, zeros beyond ndim: the kernels index them with compile-time offsets)
+    std::vector<double> steps((size_t)kHmcMaxDim, 0.0);
+    std::copy(c->step, c->step + R.nd, steps.begin());
+    HIP_TRY(metro_alloc(&b.step, steps.size() * sizeof(double)));
+    HIP_TRY(copy_sync(b.step, steps.data(), steps.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HmcFn fn = nullptr;
+    hipFunction_t ufn = nullptr, ulp = nullptr;
+    if (c->density == KMC_USER_DENSITY) {
+        kmc_user_density* ud = static_cast<kmc_user_density*>(c->user_density);
+        const std::vector<char>* code = nullptr;
+        KMC_TRY(compile_user_hmc(ud, R.nd, &code));
+        KMC_TRY(shared_module(ud, code, &b.keep));
+        const hipModule_t mod = static_cast<hipModule_t>(b.keep.get());
+        HIP_TRY(hipModuleGetFunction(&ufn, mod, "kmc_user_hmc"));
+        HIP_TRY(hipModuleGetFunction(&ulp, mod, "kmc_user_logpdf"));
+    } else {
+        fn = hmc_lookup(c->density, (int)R.nd);
+        if (!fn) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+    }
+    HIP_TRY(launch_logpdf(R, ulp, b.pos, b.logp, nullptr));     // p0 = pdf(theta0)  (:70), carried whatever it is
+    HIP_TRY(hipEventRecord(b.ev0, st));
+    int64_t iters = std::max<int64_t>(1, 65536 / c->hmc_nleap);
+    { const long n = debug_opt_long("metro-hmc-iters", 0); if (n > 0) iters = n; }     // (tests: the seams between launches)
+    for (int64_t it0 = 0, it1 = 0; it0 < c->niter; it0 = it1) {
+        it1 = std::min<int64_t>(c->niter, it0 + iters);
+        HmcArgs h{};
+        h.a = metropolis_stretch_args(R, it0, it1);
+        h.a.step = b.step;
+        h.nleap = c->hmc_nleap;
+        h.jitter = c->hmc_jitter;
+        if (ufn) HIP_TRY(launch_module(ufn, R.grid, 256u, st, h));
+        else {
+            hipLaunchKernelGGL(fn, dim3(R.grid), dim3(256), 0, st, h);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipEventRecord(b.ev1, st));
+    return KMC_OK;
+}
+
+// kmc_metropolis_validate's refusals of the HMC step, each naming the value
+kmc_status metropolis_validate_hmc(const kmc_metropolis_config* c)
+{
+    if (c->hmc_nleap < 0 || c->hmc_nleap > kHmcMaxLeap)
+        return fail(KMC_ERR_BAD_ARG, "hmc_nleap = " + std::to_string(c->hmc_nleap) + ": must be in 0 .. " + std::to_string(kHmcMaxLeap) + " (0: no HMC step)");
+    if (!std::isfinite(c->hmc_jitter) || c->hmc_jitter < 0.0 || c->hmc_jitter >= 1.0)
+        return fail(KMC_ERR_BAD_ARG, "hmc_jitter = " + num(c->hmc_jitter, "%g") + ": must be finite and in [0, 1)");
+    if (c->hmc_nleap == 0) {
+        if (c->hmc_jitter != 0.0) return fail(KMC_ERR_BAD_ARG, "hmc_jitter = " + num(c->hmc_jitter, "%g") + " with hmc_nleap = 0: there is no HMC step to jitter");
+        return KMC_OK;
+    }
+    const std::string with = "hmc_nleap = " + std::to_string(c->hmc_nleap) + " with ";
+    if (c->chol) return fail(KMC_ERR_UNSUPPORTED, with + "chol: the HMC step has a diagonal metric, the step sizes in `step` (no dense mass matrix)");
+    if (c->tune_rounds > 0) return fail(KMC_ERR_UNSUPPORTED, with + "tune_rounds = " + std::to_string(c->tune_rounds) + ": the step sizes of the HMC step are not tuned");
+    if (c->host_propose) return fail(KMC_ERR_UNSUPPORTED, with + "host_propose: the HMC step is the proposal");
+    if (c->density == KMC_HOST_DENSITY) return fail(KMC_ERR_UNSUPPORTED, with + "KMC_HOST_DENSITY: the HMC step needs the gradient on the device");
+    if (c->ndim > kHmcMaxDim)
+        return fail(KMC_ERR_UNSUPPORTED, with + "ndim = " + std::to_string(c->ndim) + ": the limit is " + std::to_string(kHmcMaxDim) + " (the chain lives in registers)");
+    for (int64_t d = 0; c->step && d < c->ndim; ++d)
+        if (!(std::isfinite(c->step[d]) && c->step[d] > 0.0))
+            return fail(KMC_ERR_BAD_ARG, "step[" + std::to_string(d) + "] = " + num(c->step[d], "%g") + " with hmc_nleap > 0: every step size must be finite and > 0");
+    if (c->density == KMC_USER_DENSITY && c->user_density) {
+        kmc_user_density* ud = static_cast<kmc_user_density*>(c->user_density);
+        if (!ud->is_body) return fail(KMC_ERR_UNSUPPORTED, with + "a term / pair density (kmc_user_density_create): the HMC step takes a body density with kmc_user_density_set_grad");
+        if (ud->nblob > 0) return fail(KMC_ERR_UNSUPPORTED, with + "a density with blobs (nblob = " + std::to_string(ud->nblob) + "): the HMC step carries none");
+        std::lock_guard<std::mutex> lock(ud->mu);
+        if (ud->grad_body.empty()) return fail(KMC_ERR_BAD_ARG, with + "a runtime-compiled density without a gradient: give it one with kmc_user_density_set_grad");
+    }
+    return KMC_OK;
+}
+
 }  // namespace
 
 KMC_EXPORT kmc_status kmc_metropolis_validate(const kmc_metropolis_config* c)
@@ -628,6 +766,7 @@ KMC_EXPORT kmc_status kmc_metropolis_validate(const kmc_metropolis_config* c)
         if (nb > 0 && c->host_propose)
             return fail(KMC_ERR_UNSUPPORTED, "a density with blobs runs in the in-kernel chains: not with host_propose (use a host log-pdf returning blobs)");
     }
+    KMC_TRY(metropolis_validate_hmc(c));
     if (c->density == KMC_HOST_DENSITY) {
         if (!c->host_logpdf) return fail(KMC_ERR_BAD_ARG, "KMC_HOST_DENSITY needs kmc_metropolis_config.host_logpdf");
         return KMC_OK;
@@ -659,8 +798,86 @@ KMC_EXPORT kmc_status kmc_metropolis_run(const kmc_metropolis_config* c, const d
     KMC_TRY(metropolis_density_params(c, &R.dp));
     KMC_TRY(metropolis_setup(c, theta0, out, &R));
     if (c->density == KMC_HOST_DENSITY || c->host_propose) KMC_TRY(metropolis_host_route(R, theta0));
+    else if (c->hmc_nleap > 0) KMC_TRY(metropolis_hmc_route(R));
     else KMC_TRY(metropolis_device_route(R));
     return metropolis_read_out(R, out);
+}
+
+KMC_EXPORT kmc_status kmc_user_density_set_grad(kmc_user_density* ud, const char* grad_body)
+{
+    if (!ud || !grad_body) return fail(KMC_ERR_BAD_ARG, "null argument");
+    if (!ud->is_body || ud->is_data || ud->nblob > 0)
+        return fail(KMC_ERR_BAD_ARG, "kmc_user_density_set_grad: the density must be one made by kmc_user_density_create_body (a function body, no blobs)");
+    if (grad_body[0] == '\0') return fail(KMC_ERR_BAD_ARG, "kmc_user_density_set_grad: the gradient body is empty");
+    // Compiled once here (any ndim): the compiler's verdict comes now, not at the first run.  Only the verdict is kept: the check's
+    // code object is never loaded (no module is keyed by its address), so it is dropped again.
+    const std::string body = grad_body;
+    static std::atomic<uint64_t> serial{0};
+    const std::string key = "hmc-syntax:" + std::to_string(serial.fetch_add(1));      // (a key of this call's own: nobody else holds or erases it)
+    const std::vector<char>* code = nullptr;
+    const kmc_status st = compile_keyed(ud, key, hmc_rtc_module(), [&](std::string* text) {
+        *text = "#include \"kmc_kernels.hpp\"\n#include \"kmc_hmc.hpp\"\n" + hmc_functor_source(ud, body) +
+                "extern \"C\" __global__ void kmc_user_grad_check(const double* x, int n, const double* p, double* g) { UserB::grad(x, n, p, g); }\n";
+        return KMC_OK;
+    }, &code);
+    std::lock_guard<std::mutex> lock(ud->mu);
+    ud->code.erase(key);
+    if (st != KMC_OK) return st;
+    ud->grad_body = body;                                     // (the modules of a gradient are keyed by its text: compile_user_hmc)
+    return KMC_OK;
+}
+
+KMC_EXPORT kmc_status kmc_grad_eval_host(const kmc_config* cfg, const double* pos_host, double* grad_host, int64_t nrows)
+{
+    if (!cfg || !pos_host || !grad_host || nrows < 0) return fail(KMC_ERR_BAD_ARG, "bad argument");
+    if (cfg->ndim < 1 || cfg->ndim > kHmcMaxDim)
+        return fail(KMC_ERR_UNSUPPORTED, "kmc_grad_eval_host: ndim = " + std::to_string(cfg->ndim) + ", must be in 1 .. " + std::to_string(kHmcMaxDim));
+    kmc_user_density* ud = nullptr;
+    if (cfg->density == KMC_USER_DENSITY) {
+        ud = static_cast<kmc_user_density*>(cfg->user_density);
+        if (!ud) return fail(KMC_ERR_BAD_ARG, "KMC_USER_DENSITY needs kmc_config.user_density");
+        std::lock_guard<std::mutex> lock(ud->mu);
+        if (ud->grad_body.empty()) return fail(KMC_ERR_BAD_ARG, "kmc_grad_eval_host: the density has no gradient (kmc_user_density_set_grad)");
+    } else if (cfg->density == KMC_HOST_DENSITY || cfg->density == KMC_DATA_DENSITY) {
+        return fail(KMC_ERR_UNSUPPORTED, "kmc_grad_eval_host: a menu density or a body density with kmc_user_density_set_grad");
+    } else {
+        KMC_TRY(check_ndim(cfg->density, cfg->ndim));
+    }
+    DensityParams dp;
+    KMC_TRY(digest_params(*cfg, &dp));
+    if (nrows == 0) return KMC_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(KMC_ERR_NO_DEVICE, "no HIP device visible");
+    }
+    HIP_TRY(hipSetDevice(cfg->device));
+    ScopedStream ss;
+    HIP_TRY(ss.create());
+    std::shared_ptr<void> keep;                                      // (the module's hold ends after the blocks are freed and the stream is gone)
+    ScopedDeviceBlock dgrad, dpos;
+    const size_t nb = (size_t)nrows * (size_t)cfg->ndim * sizeof(double);
+    HIP_TRY(dpos.alloc(nb));
+    HIP_TRY(dgrad.alloc(nb));
+    HIP_TRY(copy_sync(dpos.p, pos_host, nb, hipMemcpyHostToDevice, ss.st));
+    const GradArgs ga{dpos.as<double>(), dgrad.as<double>(), nrows, (int32_t)cfg->ndim, 0, dp};
+    const unsigned grid = (unsigned)((nrows + 255) / 256);
+    if (ud) {
+        const std::vector<char>* code = nullptr;
+        KMC_TRY(compile_user_hmc(ud, cfg->ndim, &code));
+        KMC_TRY(shared_module(ud, code, &keep));
+        hipFunction_t f = nullptr;
+        HIP_TRY(hipModuleGetFunction(&f, static_cast<hipModule_t>(keep.get()), "kmc_user_grad"));
+        HIP_TRY(launch_module(f, grid, 256u, ss.st, ga));
+    } else {
+        const GradFn f = grad_lookup(cfg->density, (int)cfg->ndim);
+        if (!f) return fail(KMC_ERR_BAD_ARG, "unknown density id");
+        hipLaunchKernelGGL(f, dim3(grid), dim3(256), 0, ss.st, ga);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(ss.st));
+    HIP_TRY(copy_sync(grad_host, dgrad.p, nb, hipMemcpyDeviceToHost, ss.st));
+    return KMC_OK;
 }
 
 KMC_EXPORT kmc_status kmc_cholesky_lower(const double* a, int n, double* L, int* bad)

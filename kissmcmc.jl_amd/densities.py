@@ -252,15 +252,25 @@ class CDensity(ExprDensity):
     ``blob[0..m)`` (zero on entry); the sampler carries each walker's current blob next to its log-pdf and ``emcee(...,
     hasblob=True)`` returns ``blobs[w][k]`` as an array ``[nwalkers, nsamples, m]`` (or whatever ``init_blobs`` / ``reduce_blob``
     build from that series) -- without the host round trip per half-step a Python callable costs.
+
+    ``grad=GRAD_BODY`` gives it a gradient, for :class:`~.metropolis.HMCStep` and :func:`grad`: the body of
+    ``void grad(const double* x, int n, const double* p, double* g)``, which writes ``d log p / d x[i]`` to ``g[i]`` (``g`` is zero on
+    entry).  Nothing checks that it is the gradient of ``body``; a wrong one costs acceptance, never correctness -- :func:`check_grad`
+    shows the difference.
     """
 
     name = "cbody"
 
-    def __init__(self, body: str, params=(), nblob: int = 0):
+    def __init__(self, body: str, params=(), nblob: int = 0, grad: str | None = None):
         import ctypes as C
         if len(params) > 6:
             raise ValueError("at most 6 parameters")
+        if grad is not None and not (isinstance(grad, str) and grad.strip()):
+            raise ValueError("grad must be a non-empty C++ function body (a str)")
+        if grad is not None and int(nblob) > 0:
+            raise ValueError("grad with nblob > 0: a density with blobs has no HMC step")
         self.body = str(body)
+        self.grad_body = None
         self.term, self.pair = None, None
         self._params = [float(v) for v in params]
         self.nblob = int(nblob)
@@ -271,6 +281,19 @@ class CDensity(ExprDensity):
         else:
             _lib.check(self._L.kmc_user_density_create_body(self.body.encode(), C.byref(h)))
         self.user_handle = h
+        if grad is not None:          # compiled now: a body that does not compile raises here, with the compiler's message
+            self.set_grad(grad)
+
+    def set_grad(self, grad: str) -> None:
+        """Give the density a gradient, or replace the one it has (``kmc_user_density_set_grad``): every later :func:`grad`,
+        :func:`check_grad` and :class:`~.metropolis.HMCStep` run uses the new body.  A body that does not compile raises and leaves
+        the previous gradient in force."""
+        if not (isinstance(grad, str) and grad.strip()):
+            raise ValueError("grad must be a non-empty C++ function body (a str)")
+        if self.nblob > 0:
+            raise ValueError("grad with nblob > 0: a density with blobs has no HMC step")
+        _lib.check(self._L.kmc_user_density_set_grad(self.user_handle, grad.encode()))
+        self.grad_body = grad
 
     @property
     def separable(self) -> bool:
@@ -300,6 +323,66 @@ class CDensity(ExprDensity):
         dp = C.POINTER(C.c_double)
         _lib.check(self._L.kmc_logpdf_blob_eval_host(C.byref(cfg), X.ctypes.data_as(dp), lp.ctypes.data_as(dp), bl.ctypes.data_as(dp), n))
         return lp, bl
+
+
+def _eval_config(pdf, n, nd):
+    cfg = _lib.Config()
+    cfg.dtype, cfg.density = _lib.F64, pdf.density_id
+    p = list(pdf.params()) + [0.0] * 8
+    for i in range(8):
+        cfg.params[i] = float(p[i])
+    cfg.nwalkers, cfg.ndim, cfg.nthin, cfg.a_scale = max(2, n + (n & 1)), nd, 1, 2.0
+    cfg.user_density = pdf.user_handle
+    return cfg
+
+
+def _rows_of(pdf, x):
+    if not isinstance(pdf, DeviceLogPdf) or pdf.density_id in (_lib.HOST_DENSITY, _lib.DATA_DENSITY):
+        raise TypeError("pdf must be a menu density or a CDensity(body, grad=grad_body)")
+    X = np.asarray(x, dtype=np.float64)
+    one = X.ndim == 1
+    X = np.ascontiguousarray(np.atleast_2d(X))
+    if X.ndim != 2 or X.shape[1] < 1:
+        raise ValueError("x must be one point [ndim] or rows [n, ndim]")
+    pdf.check_ndim(X.shape[1])
+    return X, one
+
+
+def grad(pdf, x):
+    """The gradient of ``log pdf`` at ``x`` (one point ``[ndim]`` or rows ``[n, ndim]``), evaluated on the device with the arithmetic
+    of the HMC step (``kmc_grad_eval_host``): a menu density, or a ``CDensity(body, grad=grad_body)``; up to 32 dimensions."""
+    import ctypes as C
+    X, one = _rows_of(pdf, x)
+    n, nd = X.shape
+    out = np.empty((n, nd))
+    dp = C.POINTER(C.c_double)
+    cfg = _eval_config(pdf, n, nd)
+    _lib.check(_lib.lib().kmc_grad_eval_host(C.byref(cfg), X.ctypes.data_as(dp), out.ctypes.data_as(dp), n))
+    return out[0] if one else out
+
+
+def check_grad(pdf, x, h: float = 1e-6):
+    """The largest ``|grad(pdf, x) - central differences of the device log-density|`` over the points and dimensions of ``x``, the
+    differences taken with the step ``h * max(1, |x_i|)``.  For a correct gradient it is of the order of ``h ** 2`` times the third
+    derivative plus ``1e-16 |log p| / h``; a wrong gradient body shows as a value of the order of the gradient itself."""
+    import ctypes as C
+    X, _ = _rows_of(pdf, x)
+    n, nd = X.shape
+    g = np.atleast_2d(grad(pdf, X))
+    P = np.repeat(X, 2 * nd, axis=0).reshape(n, nd, 2, nd)
+    hs = float(h) * np.maximum(1.0, np.abs(X))
+    for i in range(nd):
+        P[:, i, 0, i] += hs[:, i]
+        P[:, i, 1, i] -= hs[:, i]
+    rows = np.ascontiguousarray(P.reshape(-1, nd))
+    lp = np.empty(rows.shape[0])
+    dp = C.POINTER(C.c_double)
+    cfg = _eval_config(pdf, rows.shape[0], nd)
+    _lib.check(_lib.lib().kmc_logpdf_eval_host(C.byref(cfg), rows.ctypes.data_as(dp), lp.ctypes.data_as(dp), rows.shape[0]))
+    lp = lp.reshape(n, nd, 2)
+    with np.errstate(all="ignore"):
+        fd = (lp[:, :, 0] - lp[:, :, 1]) / ((X + hs) - (X - hs))
+        return float(np.max(np.abs(g - fd)))
 
 
 class DataDensity(ExprDensity):

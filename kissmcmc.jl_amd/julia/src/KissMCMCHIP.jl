@@ -156,11 +156,18 @@ end
 # between the dimensions; runs one walker per lane (kmc_user_density_create_body).  `nblob=m`: the reference's
 # `pdf(theta) -> (p, blob)` of hasblob=true (src/samplers.jl:150-151) on the device -- the body is then that of
 # `double logpdf(const double* x, int n, const double* p, double* blob)` and fills blob[0..m) (kmc_user_density_create_body_blob).
-function CDensity(body::String; params=Float64[], nblob::Int=0)
+# `grad=GRAD_BODY`: the body of `void grad(const double* x, int n, const double* p, double* g)` (g zero on entry), the gradient the HMC
+# step of `metropolis_chains(...; hmc_nleap)` follows (kmc_user_density_set_grad; compiled here, not with blobs).
+function CDensity(body::String; params=Float64[], nblob::Int=0, grad::Union{Nothing,String}=nothing)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     st = nblob > 0 ? ccall((:kmc_user_density_create_body_blob, LIB), Cint, (Cstring, Cint, Ref{Ptr{Cvoid}}), body, nblob, h) :
                      ccall((:kmc_user_density_create_body, LIB), Cint, (Cstring, Ref{Ptr{Cvoid}}), body, h)
     st == 0 || error("kmc_user_density_create_body failed: $(last_error())")
+    if grad !== nothing && ccall((:kmc_user_density_set_grad, LIB), Cint, (Ptr{Cvoid}, Cstring), h[], grad) != 0
+        msg = last_error()
+        ccall((:kmc_user_density_destroy, LIB), Cvoid, (Ptr{Cvoid},), h[])
+        error("kmc_user_density_set_grad failed: $msg")
+    end
     d = ExprDensity(h[], collect(Float64, params), nblob)
     finalizer(x -> ccall((:kmc_user_density_destroy, LIB), Cvoid, (Ptr{Cvoid},), x.handle), d)
     return d
@@ -419,6 +426,8 @@ Base.@kwdef struct KmcMetropolisConfig
     chol::Ptr{Float64} = C_NULL                       # the proposal theta + L z: [ndim][ndim] row-major, lower triangle read (instead of `step`)
     tune_rounds::Int32 = 0                            # tuning boundaries during burn-in: L from the covariance across chains
     tune_scale::Float64 = 0.0                         # 0: 2.38 / sqrt(ndim)
+    hmc_nleap::Int32 = 0                              # 0: off; 1 .. 1024: the HMC step, leapfrog steps per iteration (`step`: the step sizes)
+    hmc_jitter::Float64 = 0.0                         # in [0, 1): relative half-width of the per-iteration step-size jitter
 end
 
 Base.@kwdef mutable struct KmcMetropolisOutputs
@@ -482,9 +491,17 @@ like `emcee`'s output (`thetas[chain][sample]`), so `squash_walkers` applies.
 `theta + L z` (include/kissmcmc_hip.h: same draws, `L z` summed in index order without fused multiply-add); `tune_rounds=R > 0`
 replaces `L` at `R` boundaries of burn-in by the Cholesky factor of `tune_scale^2` (default `2.38 / sqrt(ndim)`) times the covariance of
 the chains' current states across chains, the `GaussianStep` or `chol` being the initial proposal.
+
+`hmc_nleap=n > 0` makes the step a Hamiltonian Monte Carlo proposal (include/kissmcmc_hip.h holds the rule): the `GaussianStep`'s scales are
+the step sizes `step_i` (all > 0), the momentum `m` is the normals `z` the random walk would have drawn, `f = 1 + hmc_jitter * (((j + 1/2) 2^-11) - 1)`
+with `j` the low 12 bits of word 3 of Philox block 0, `e_i = step_i f`, `h_i = e_i / 2`; from `y = x`, `g = grad(y)`, `n` times
+`m += h .* g; y += e .* m; g = grad(y); m += h .* g`; accepted iff `(p1 - K1) - (p0 - K0) > log u` (strict) with `K = 1/2 sum m_i^2`, every product
+and sum rounded on its own.  `pdf` is a menu density, or a `CDensity` given a gradient body with `kmc_user_density_set_grad`; `ndim <= 32`; not
+with `chol`, `tune_rounds`, a `HostProposal`, a `HostLogPdf` or blobs.
 """
 function metropolis_chains(pdf::DeviceLogPdf, sample_ppdf::Union{GaussianStep,HostProposal}, theta0s; niter=10^5, nburnin=niter ÷ 2, nthin=1,
                            chol::Union{Nothing,AbstractMatrix}=nothing, tune_rounds::Integer=0, tune_scale::Real=0.0,
+                           hmc_nleap::Integer=0, hmc_jitter::Real=0.0,
                            hasblob=false, init_blobs=(blob0, nsamples) -> sizehint!(typeof(blob0)[], nsamples),
                            reduce_blob! =(blobs, blob) -> push!(blobs, blob), seed=rand(UInt64), device=0)
     device_blobs = hasblob && pdf isa ExprDensity && pdf.nblob > 0 && sample_ppdf isa GaussianStep
@@ -526,7 +543,8 @@ function metropolis_chains(pdf::DeviceLogPdf, sample_ppdf::Union{GaussianStep,Ho
                                       nthin=nthin, step=(isempty(step) ? Ptr{Float64}(C_NULL) : pointer(step)), seed=UInt64(seed),
                                       flags=KMC_STORE_CHAIN | KMC_STORE_LOGP | KMC_CHAIN_BY_WALKER | (device_blobs ? KMC_STORE_BLOBS : UInt32(0)), device=Int32(device), user_density=user_handle(pdf),
                                       host_logpdf=pdf_fn, host_user=pointer_from_objref(ctx), host_propose=prop_fn,
-                                      chol=(isempty(cholrm) ? Ptr{Float64}(C_NULL) : pointer(cholrm)), tune_rounds=Int32(tune_rounds), tune_scale=Float64(tune_scale)))
+                                      chol=(isempty(cholrm) ? Ptr{Float64}(C_NULL) : pointer(cholrm)), tune_rounds=Int32(tune_rounds), tune_scale=Float64(tune_scale),
+                                      hmc_nleap=Int32(hmc_nleap), hmc_jitter=Float64(hmc_jitter)))
         ccall((:kmc_metropolis_run, LIB), Cint, (Ref{KmcMetropolisConfig}, Ptr{Float64}, Ref{KmcMetropolisOutputs}), cfg, theta, out)
     end
     st == 0 || error("kmc_metropolis_run failed ($st): $(last_error())")

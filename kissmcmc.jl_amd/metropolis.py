@@ -10,7 +10,8 @@ Fast path: ``sample_ppdf`` a :class:`GaussianStep` -- the symmetric jump every r
 ``theta -> c .* randn(n) .+ theta`` (``test/runtests.jl:54,59,64,75``) -- and ``pdf`` a menu or runtime-compiled
 density: the whole chain runs inside one kernel, one chain per lane.  :class:`MVNormalStep` (``theta + L randn(n)``, the shape
 of a covariance) and :class:`TunedStep` (``L`` from the covariance across chains, at a few boundaries during burn-in) run on
-the same path.
+the same path, and so does :class:`HMCStep`, a gradient-informed proposal (leapfrog steps along the gradient of ``pdf``: a menu
+density, or a ``CDensity`` with ``grad=``).
 
 General path (the reference takes ANY two closures, ``src/samplers.jl:59-61``; its README-style call
 ``metropolis(pdf, sample_prop_normal, theta0)`` works as it is): a callable ``pdf`` and / or a callable ``sample_ppdf``
@@ -121,7 +122,36 @@ class TunedStep:
         return f"TunedStep({self.initial!r}, rounds={self.rounds}, scale={self.scale})"
 
 
-_DEVICE_STEPS = (GaussianStep, MVNormalStep, TunedStep)
+class HMCStep:
+    """Hamiltonian Monte Carlo proposal: ``nleap`` leapfrog steps of size ``eps`` (a scalar or one value per dimension: a diagonal
+    metric) from the current state, the momentum being the normals a :class:`GaussianStep` would have drawn; accepted on the change
+    of ``log p - |m|^2 / 2``.  ``jitter`` in ``[0, 1)`` scales every step size of an iteration by one factor spread evenly over
+    ``1 - jitter .. 1 + jitter`` (4096 values, from 12 bits of the stream nothing else reads): it breaks the resonances of a fixed
+    trajectory length.  The rule is in ``include/kissmcmc_hip.h``.
+
+    ``pdf`` is a menu density or a ``CDensity(body, grad=grad_body)``; up to 32 dimensions.  Nothing is tuned: choose ``eps`` for an
+    acceptance around 0.65 - 0.9 (it falls as ``eps`` grows), ``nleap * eps`` of the order of the target's scale."""
+
+    def __init__(self, eps, nleap: int = 8, jitter: float = 0.0):
+        self.eps = np.atleast_1d(np.asarray(eps, dtype=np.float64))
+        if self.eps.ndim != 1 or self.eps.size < 1 or not np.all(np.isfinite(self.eps)) or not np.all(self.eps > 0):
+            raise ValueError("eps must be a finite positive scalar or vector")
+        if isinstance(nleap, bool) or int(nleap) != nleap or not 1 <= nleap <= 1024:
+            raise ValueError(f"nleap = {nleap}: must be an integer in 1 .. 1024")
+        if not (np.isfinite(jitter) and 0.0 <= jitter < 1.0):
+            raise ValueError(f"jitter = {jitter}: must be in [0, 1)")
+        self.nleap, self.jitter = int(nleap), float(jitter)
+
+    def scales(self, ndim: int) -> np.ndarray:
+        if self.eps.size not in (1, ndim):
+            raise ValueError(f"HMCStep has {self.eps.size} step sizes for {ndim} dimensions")
+        return np.ascontiguousarray(np.broadcast_to(self.eps, (ndim,)), dtype=np.float64)
+
+    def __repr__(self):
+        return f"HMCStep({self.eps.tolist() if self.eps.size > 1 else float(self.eps[0])}, nleap={self.nleap}, jitter={self.jitter})"
+
+
+_DEVICE_STEPS = (GaussianStep, MVNormalStep, TunedStep, HMCStep)
 
 
 def tune_boundaries(nburnin: int, rounds: int):
@@ -167,7 +197,7 @@ def run_chains(pdf, sample_ppdf, theta0s, niter, nburnin, nthin, seed, device=0,
     also ``blobs [nsamples, nchains, m]`` (``[nchains, nsamples, m]`` with ``by_chain``) and ``final_blob [nchains, m]``.
 
     ``pdf``: a device density, a :class:`~.densities.HostLogPdf` or any callable (wrapped in one); ``sample_ppdf``: a
-    :class:`GaussianStep`, an :class:`MVNormalStep`, a :class:`TunedStep`, a :class:`HostProposal` or any callable (wrapped in one).  ``scalar``: bare callables get a
+    :class:`GaussianStep`, an :class:`MVNormalStep`, a :class:`TunedStep`, an :class:`HMCStep`, a :class:`HostProposal` or any callable (wrapped in one).  ``scalar``: bare callables get a
     float instead of a 1-element array (the reference's convention for a scalar ``theta0``)."""
     if not isinstance(pdf, DeviceLogPdf):
         if not callable(pdf):
@@ -198,6 +228,10 @@ def run_chains(pdf, sample_ppdf, theta0s, niter, nburnin, nthin, seed, device=0,
     if isinstance(base, GaussianStep):
         step = base.scales(ndim)
         c.step = _dp(step)
+    elif isinstance(base, HMCStep):
+        step = base.scales(ndim)
+        c.step = _dp(step)
+        c.hmc_nleap, c.hmc_jitter = base.nleap, base.jitter
     elif isinstance(base, MVNormalStep):
         chol = base.factor(ndim)
         c.chol = _dp(chol)
